@@ -1,20 +1,32 @@
 #!/usr/bin/env python
 """Benchmark of the north-star hot path: denoising steps/sec of the CMDM (AMDM) `p_sample_loop`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher environment: re-executes itself under the line below)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                 (N > 1 without a launcher environment: re-executes itself under the line below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
 One "step" = one `p_sample` (CMDM denoiser forward over the rank's batch + DDPM posterior update) of
 BASELINE.json configs[1]: B = 32 samples per GPU, L = 196 frames, D = 263, N = 8192 scene points
 (128 contact-group tokens), hoisted step-invariant conditions, synthetic inputs, name-keyed random weights.
+The K timed steps are one K-step loop call (a schedule respaced from the 1000 diffusion steps); K > 1000 runs as ceil(K / 1000)
+near-equal loop calls back to back, each starting from the previous one's x.  K >= 2; W = 1 warms up on the shortest loop (2 steps).
 `--scaling strong` (the default for N > 1: BASELINE configs[4] is "k_sample = 32 sharded 8x"): ONE 32-sample job (k_sample = 32,
 reference test.py:88-101) is sharded over the ranks (32 / N samples per GPU), one all_gather at the end, value = K / max-over-ranks
 wall time.  `--scaling weak`: every rank runs its own 32 samples (global sample indices rank*32 ...), value = (ranks x K steps) /
-max-over-ranks wall time.  At N = 1 the two are the same job; with N > 1 the line carries the OTHER mode as well
-(`other_scaling_mode`).  Rank 0 prints ONE JSON line.  At N = 1 the line also carries `secondary`: the other BASELINE configs
+max-over-ranks wall time.  At N = 1 the two are the same job; with N > 1 and `--full` the line carries the OTHER mode as well
+(`other_scaling_mode`).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up (including the priming loop call, see its comment), W warm-up steps, the K timed
+steps, the outputs of the timed loop if `--dump-outputs DIR` is given, the line.  `--full` adds everything else, all measured after the
+headline and outside its timed region: the dominant kernel's roofline, p50 sample latency, the other GEMM arithmetic settings, the CPU
+baseline, with N > 1 the other scaling mode and the all_gather on its own, and at N = 1 `secondary`: the other BASELINE configs
 ([0], [2], [3], [4]), the headline shape with the conditions recomputed every step ("faithful") and the per-GPU batch sizes of the
-strong-scaling job (B = 16 / 8 / 4 / 1), all measured after the headline and outside its timed region.
+strong-scaling job (B = 16 / 8 / 4 / 1).  Entries a plain run does not measure are null in its line.
+
+`--dump-outputs DIR` writes DIR/sample.npy (float32): the final x of the timed K-step loop, every rank's rows gathered in rank order -
+what a caller of `p_sample_loop` receives.  Inputs, weights and noise are seeded, so the same arguments give the same file on every run.
+Above DUMP_MAX_BYTES a fixed, seeded choice of whole samples is written instead (sorted sample indices from a generator seeded with 0).
 """
 import argparse
 import json
@@ -38,6 +50,9 @@ import torch.distributed as dist  # noqa: E402
 B_PER_GPU, L, D, NPTS = 32, 196, 263, 8192
 F32_MFMA_PEAK_TFLOPS = 157.3            # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 BF16_MFMA_PEAK_TFLOPS = 2500.0          # same guide: v_mfma_f32_32x32x16_bf16, dense
+DUMP_MAX_BYTES = 64 << 20
+BASE_STEPS = 1000                       # diffusion.steps of the config: the most steps one respaced schedule (one loop call) can take
+CHAIN_SEED_STRIDE = 7919                # loop j of a chain draws its noise with seed + j * this (j = 0: the seed of a single loop call)
 
 
 def step_flops(batch: int, frames: int = L, groups: int = NPTS // 64) -> float:
@@ -117,6 +132,7 @@ def cpu_baseline(n_steps: int = 20, reps: int = 3):
     # torch-CPU scales badly past the physical cores of one socket on these ops: probe a few thread
     # counts with one step each and report the FASTEST (the fairest CPU number we can produce here)
     avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    avail = min(avail, int(os.environ.get("OMP_NUM_THREADS") or avail))      # a shared host's thread budget, when it sets one
     cands = sorted({c for c in (avail, avail // 2, avail // 4, 64, 32, 16, 8) if 1 <= c <= avail}, reverse=True)
     best = (None, float("inf"))
     probe = {}                                         # thread count -> ms per step (best of two single steps after a warm-up step): the whole probe is reported
@@ -155,6 +171,19 @@ def cpu_baseline(n_steps: int = 20, reps: int = 3):
             "host": {"cpu": cpu_model, "logical_cpus": avail, "torch": torch.__version__, "threads_used": torch.get_num_threads()}}
 
 
+def dump_outputs(out_dir: str, sample: torch.Tensor) -> None:
+    """`--dump-outputs`: the timed loop's final x as float32 .npy; whole samples, a seeded fixed choice of them above DUMP_MAX_BYTES."""
+    import numpy as np
+    x = sample.detach().float().cpu()
+    per_sample = x[0].numel() * 4
+    if x.shape[0] * per_sample > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES // per_sample)
+        idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        x = x[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample.npy"), x.contiguous().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -179,7 +208,16 @@ def main():
     ap.add_argument("--gemm-tile", type=int, default=0, help="measurement: AFM_TUNE_TILE code forced on the wide encoder GEMMs (5 = 128x128; bit-neutral)")
     ap.add_argument("--pair-launch", type=int, default=None, help="1 / 0: sub-batch A's out_proj + sub-batch B's linear1 as one 128x128-tile launch per layer (bit-identical; default: the model's setting)")
     ap.add_argument("--attn-group", type=int, default=None, help="waves per attention workgroup (bit-neutral tuning; default: library choice)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure roofline, latency, GEMM arithmetic settings, CPU baseline, "
+                                                       "the other scaling mode / all_gather (N > 1) and `secondary` (N = 1); the --no-* / --latency-* / "
+                                                       "--cpu-* options shape these passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed loop's final sample to DIR/sample.npy (float32)")
     args = ap.parse_args()
+    # the shortest schedule gaussian_diffusion.py can build has 2 steps (posterior_variance[1]): K must be >= 2, and W = 1 warms up on 2 steps
+    if args.steps < 2:
+        ap.error("--steps must be >= 2")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
 
     from afm import dist as adist
     if adist.needs_self_launch(args.gpus) and not os.environ.get("AFM_SELF_LAUNCHED"):
@@ -205,7 +243,7 @@ def main():
     assert shared_gpu or adist.distinct_devices(seen) == world, f"{world} ranks on {adist.distinct_devices(seen)} distinct devices: {seen}"
 
     K, W = args.steps, args.warmup
-    model, diff_k, cfg = build(dev, str(K))
+    model, _, cfg = build(dev, str(min(K, BASE_STEPS)))
     if args.streams is not None:
         model.loop_streams, model.loop_streams_auto = args.streams, False
     model.gemm_tile = args.gemm_tile
@@ -216,11 +254,22 @@ def main():
     model.fused_layernorm = bool(args.fused_ln)
     model.no_ln_fold = bool(args.no_ln_fold)
     from afm.base import create_gaussian_diffusion
-    cfg.diffusion.timestep_respacing = str(max(W, 1))
-    diff_w = create_gaussian_diffusion(cfg)
-    # the schedule tables are built at construction in the reference (gaussian_diffusion.py:119-170, "init only"); ours are uploaded
-    # lazily per device, so touch them here instead of inside the timed region
-    diff_k.tables(dev); diff_w.tables(dev)
+
+    def chain(n):
+        """Schedules whose loops, run back to back, take exactly n steps: ONE n-step schedule respaced from the BASE_STEPS diffusion
+        steps when n <= BASE_STEPS (a single loop call, as a sampling request runs), else ceil(n / BASE_STEPS) near-equal ones."""
+        parts = -(-n // BASE_STEPS)
+        out = []
+        for i in range(parts):
+            cfg.diffusion.timestep_respacing = str(n // parts + (i < n % parts))
+            d = create_gaussian_diffusion(cfg)
+            # the schedule tables are built at construction in the reference (gaussian_diffusion.py:119-170, "init only"); ours are
+            # uploaded lazily per device, so touch them here instead of inside the timed region
+            d.tables(dev)
+            out.append(d)
+        return out
+    diff_k = chain(K)
+    diff_w = chain(max(W, 2))                                  # W = 0: no warm-up steps; the --full passes warm up on a 2-step loop
 
     # this rank's shard [i0, i0 + B) of the job, resident in HBM before any timing.  weak: every rank owns --batch samples (global
     # sample indices rank * batch ...); strong: the --batch samples of ONE job are sharded contiguously (afm.dist.shard_range)
@@ -255,11 +304,16 @@ def main():
         return statistics.median(ts)
 
     def run(diffusion, seed, kwargs=None, nb=None, index0=None, gather=True):
+        """`diffusion`: one schedule or a chain of them (each loop starts from the previous one's x, with noise of its own seed).
+        -> the job's rows: this rank's x, or with N > 1 every rank's x in rank order."""
         kwargs, nb, index0 = kwargs or kw, B if nb is None else nb, i0 if index0 is None else index0
-        x = diffusion.p_sample_loop(model, (nb, L, D), clip_denoised=False, model_kwargs=kwargs, seed=seed, sample_index0=index0)
+        x = None
+        for j, d in enumerate(diffusion if isinstance(diffusion, list) else [diffusion]):
+            x = d.p_sample_loop(model, (nb, L, D), noise=x, clip_denoised=False, model_kwargs=kwargs, seed=seed + CHAIN_SEED_STRIDE * j,
+                                sample_index0=index0)
         if world > 1 and gather:                       # the path's only collective: gather the shards at the end (RCCL over xGMI)
-            adist.all_gather_rows(x, world)
-        return x
+            return adist.all_gather_rows(x, world)
+        return [x]
 
     def timed(kwargs=None, nb=None, index0=None):
         """W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; max over ranks."""
@@ -269,7 +323,7 @@ def main():
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
-        run(diff_k, 2, kwargs, nb, index0)             # exactly K steps
+        parts = run(diff_k, 2, kwargs, nb, index0)     # exactly K steps
         t_enq = time.perf_counter() - t0               # host time to enqueue the K steps (the loop never synchronises)
         torch.cuda.synchronize()
         if world > 1:
@@ -279,7 +333,7 @@ def main():
             tt = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = tt.item()
-        return dt, t_enq
+        return dt, t_enq, parts
 
     # ---- process-start transient (profiles/r04_first_loop_transient.md, tools/probe_first_ms.py): the FIRST native-loop call of a process is
     # followed, 50 - 150 ms after it began, by one ~70 ms stall of the device (at every batch size; it passes unseen when the GPU idles;
@@ -311,11 +365,14 @@ def main():
     if world > 1:
         dist.barrier()
 
-    dt, t_enq = timed()
+    dt, t_enq, parts = timed()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch.cat(parts))
+    del parts
 
     # the path's only collective on its own (N > 1): all_gather of this rank's [B / G, L, D] f32 shard - already inside `dt`, priced here
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         gather = adist.time_all_gather(torch.zeros(B, L, D, device=dev), world)
         gt = torch.tensor([gather["median_us"]], device=dev, dtype=torch.float64)
         if dist.get_backend() == "gloo":
@@ -327,11 +384,11 @@ def main():
     # the other scaling mode in the same invocation (N > 1 only; informational): the driver calls bench.py without --scaling, so a
     # weak run also reports the strong-scaling rate of ONE 32-sample job sharded over the ranks (B/N samples per GPU), and vice versa
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         o_mode = "strong" if args.scaling == "weak" else "weak"
         o_i0, o_B, o_total = shard(o_mode)
         o_kw = batch_kwargs(o_total, o_i0, o_B)
-        o_dt, _ = timed(o_kw, o_B, o_i0)
+        o_dt, _, _ = timed(o_kw, o_B, o_i0)
         o_steps = (world if o_mode == "weak" else 1) * K
         other = {"scaling": o_mode, "value": round(o_steps / o_dt, 2), "unit": "steps/s", "ms_per_step": round(1e3 * o_dt / K, 4),
                  "batch_per_gpu": o_B, "job_samples": o_total,
@@ -342,7 +399,7 @@ def main():
     # (with 2 streams the other sub-batch's kernels share the GPU inside every bracket); same kernels, same
     # total work, launches of twice the rows.  `rocprofv3 ... bench.py --streams 1` reproduces these averages.
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         streams_timed = model.loop_streams
         model.loop_streams = 1
         # the multi-stream loop runs its wide GEMMs on 128 x 128 tiles when every sub-batch has >= 4096 rows (csrc/cmdm.hip, round 6): the
@@ -379,7 +436,7 @@ def main():
 
     # p50 sequence-sample latency: full 1000-step p_sample_loop, wall time of the whole call incl. the final synchronise
     lat = None
-    if rank == 0 and world == 1 and (args.latency_runs > 0 or args.latency_runs_b1 > 0):
+    if rank == 0 and world == 1 and args.full and (args.latency_runs > 0 or args.latency_runs_b1 > 0):
         cfg.diffusion.timestep_respacing = ""
         diff_full = create_gaussian_diffusion(cfg)
         diff_full.tables(dev)
@@ -405,7 +462,7 @@ def main():
     # round 6): the SIX largest cross products of the bf16x3 split on every eligible GEMM (K >= 128, K % 16 == 0) and in the attention - the
     # worst-case table of tests/test_gpu_arith.py (profiles/r06_arith_worstcase.json) is the evidence; all nine products are an alternative here.
     alt = None
-    if rank == 0 and world == 1 and not args.no_alt_gemm:
+    if rank == 0 and world == 1 and args.full and not args.no_alt_gemm:
         from afm import ops as afm_ops
         alt = {}
         saved = afm_ops.get_gemm_split()
@@ -454,13 +511,13 @@ def main():
         alt["unit"] = "steps/s"
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_steps, args.cpu_reps)
 
     sub_streams = max(1, min(model.loop_streams, B // 8 if model.loop_streams_auto else B))       # of the timed headline run
     # ---- `secondary` (N = 1 only; after the headline, outside its timed region): everything else BASELINE.json names, driver-visible
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         secondary = {}
         K2, W2 = 100, 10
         cfg.diffusion.timestep_respacing = str(K2)
@@ -497,12 +554,12 @@ def main():
             # recomputed inside EVERY step (models/cmdm.py:134-156), p_sample by p_sample
             Kf = 10
             model.hoist_conditions = False
-            tvec = diff_k.tables(dev).timesteps(B)
+            tvec = diff_k[0].tables(dev).timesteps(B)
 
             def faithful():
                 x = torch.zeros(B, L, D, device=dev)
                 for j in range(Kf):
-                    x = diff_k.p_sample(model, x, tvec[K - 1 - j], clip_denoised=False, model_kwargs=kw, seed=1, step=j)["sample"]
+                    x = diff_k[0].p_sample(model, x, tvec[diff_k[0].num_timesteps - 1 - j], clip_denoised=False, model_kwargs=kw, seed=1, step=j)["sample"]
                 return x
             faithful()
             torch.cuda.synchronize()

@@ -62,11 +62,11 @@ def test_two_ranks_over_rccl_equal_one_process(tmp_path):
 
 
 def test_bench_two_ranks_end_to_end():
-    """`bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one JSON line from rank 0): strong scaling is the
+    """`bench.py --gpus 2 --full` under torch.distributed.run (one JSON line from rank 0): strong scaling is the
     headline for N > 1, the weak-scaling rate rides along, both values are positive and consistent with their ms_per_step."""
     share = torch.cuda.device_count() < 2
     env = dict(AFM_BENCH_SHARE_GPU="1", AFM_DIST_BACKEND="gloo") if share else {}
-    r = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"], env)
+    r = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"], env)
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["steps"] == 5 and line["warmup"] == 2
     assert line["scaling"] == "strong" and line["config"]["batch_per_gpu"] == 16 and line["config"]["job_samples"] == 32
@@ -105,14 +105,14 @@ def test_plain_bench_command_with_two_gpus_launches_its_own_ranks():
 
 
 def test_bench_two_ranks_over_rccl_one_rank_per_gpu():
-    """The first multi-GPU lease, made boring: `bench.py --gpus 2` with NO backend override and NO device sharing, i.e.
-    exactly the driver's command - the line must prove that RCCL saw two ranks on two DISTINCT devices (`ranks_seen` comes from an
+    """The first multi-GPU lease, made boring: `bench.py --gpus 2 --full` with NO backend override and NO device sharing
+    - the line must prove that RCCL saw two ranks on two DISTINCT devices (`ranks_seen` comes from an
     all_gather over the job's own backend).  A 1-GPU box cannot run it and says why."""
     n = torch.cuda.device_count()
     if n < 2:
         pytest.skip(f"needs >= 2 GPUs for one rank per GPU over RCCL; this box has {n} (the shared-GPU gloo variant above covers the control flow)")
     env = {k: "" for k in ("AFM_BENCH_SHARE_GPU", "AFM_DIST_BACKEND")}
-    r = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"], env)
+    r = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"], env)
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     seen = line["ranks_seen"]
     assert line["n_gpus"] == 2 and line["distinct_devices"] == 2 and not line["shared_gpu_test_mode"]

@@ -17,7 +17,7 @@ export TMPDIR=/tmp
 RECIPE=${1:-validate}; shift
 O=gpurun_out/$RECIPE; mkdir -p $O
 LIB=afford-motion_amd/afm/libafm_hip.so
-BENCH_LEAN="--no-secondary --no-cpu-baseline --no-alt-gemm --latency-runs 0 --latency-runs-b1 0"
+BENCH_LEAN="--full --no-secondary --no-cpu-baseline --no-alt-gemm --latency-runs 0 --latency-runs-b1 0"
 
 bench_line() {        # <label> <json file>: value, ms/step, all-kernel ms/step
   python - "$1" "$2" <<'PY'
@@ -141,7 +141,7 @@ validate)
   R=${1:-r05}
   ( time timeout 1500 python -m pytest tests -m gpu -q -x --timeout=900 2>&1 | tail -6 ) > $O/pytest_gpu.log 2>&1
   ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke.log 2>&1
-  ( timeout 900 python bench.py ) > $O/bench_b32.json 2> $O/bench_b32.err
+  ( timeout 900 python bench.py --full ) > $O/bench_b32.json 2> $O/bench_b32.err
   ( timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_k20.json 2> $O/bench_k20.err
   ( timeout 600 bash tools/collect_profiles.sh ${R/r0/r} ) > $O/collect.log 2>&1
   ( timeout 500 bash tools/collect_profiles.sh ${R/r0/r} cdm ) > $O/collect_cdm.log 2>&1

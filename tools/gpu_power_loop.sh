@@ -14,5 +14,5 @@ sample() {
   done > $O/$tag.smi
   wait $pid
 }
-sample cmdm timeout 200 python bench.py --steps 1000 --warmup 10 --no-cpu-baseline --no-alt-gemm --latency-runs 6 --latency-runs-b1 0
+sample cmdm timeout 200 python bench.py --full --steps 1000 --warmup 10 --no-cpu-baseline --no-alt-gemm --latency-runs 6 --latency-runs-b1 0
 cat $O/cap.txt; sort -t' ' -k3 -n -r $O/cmdm.smi | head -12; echo; wc -l $O/cmdm.smi; tail -1 $O/cmdm.out | cut -c1-200
