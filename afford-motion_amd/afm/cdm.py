@@ -9,7 +9,7 @@ per-point scene features must be supplied as `c_pc_feat` (the `use_openscene` pa
 from __future__ import annotations
 
 import ctypes as C
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -627,8 +627,9 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
     # ------------------------------------------------------------------ native sampling loop
     def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                        clip_denoised=False):
-        """Whole p_sample_loop of the ADM on the device (afm_cdm_sample_loop): x holds x_T on entry, returns the sample.  ``progress``
+                        clip_denoised=False, ddim_eta: Optional[float] = None):
+        """Whole p_sample_loop of the ADM on the device (afm_cdm_sample_loop): x holds x_T on entry, returns the sample.  ``ddim_eta`` not
+        None: ddim_sample_loop with that eta (afm_cdm_ddim_loop_range, the DDIM update fused where the DDPM update is in every form).  ``progress``
         slices the chain (afm_cdm_sample_loop_range) so a tqdm bar can advance, with bit-identical results.  The batch
         runs as `loop_sub_batches` sub-batches on their own stream pairs (see __init__; bit-identical results).  ``snapshots`` =
         {executed step count: None} is filled with clones of x after those steps, as in CMDM.afm_native_loop."""
@@ -645,7 +646,8 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             tq0, tu, tcu = self._text_latent(w, model_kwargs, dev)
             tab = diffusion.tables(dev)
             n = diffusion.num_timesteps
-            sched = ffi.sched_scratch(self, n, B, dev)
+            sched = ffi.sched_scratch(self, n, B, dev, ddim=ddim_eta is not None)
+            ddim = None if ddim_eta is None else diffusion.ddim_tables(dev, ddim_eta)
             nsub = int(self.loop_sub_batches) or 1
             nsub = max(1, min(nsub, B))
             need = 2 * nsub if nsub > 1 else (1 if self.overlap_streams else 0)
@@ -667,6 +669,13 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def enqueue(j0, j1):        # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo, cnt = n - j1, j1 - j0
+                if ddim is not None:
+                    ffi.check(lib.afm_cdm_ddim_loop_range(
+                        C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(),
+                        None if step_noise is None else step_noise[j0:j1].data_ptr(), tab.timestep_map[lo:].data_ptr(),
+                        C.byref(ddim.rows(lo)), cnt, j0, seed & (2**64 - 1),
+                        sample_index0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream), "afm_cdm_ddim_loop_range")
+                    return
                 ffi.check(lib.afm_cdm_sample_loop_range(
                     C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(),
                     None if step_noise is None else step_noise[j0:j1].data_ptr(), tab.timestep_map[lo:].data_ptr(),
@@ -684,7 +693,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 ffi.run_slices(slices, enqueue_snap, progress, dev)
             else:
                 ffi.run_slices(slices, enqueue, progress, dev)
-            self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu)
+            self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu, ddim)
         return x
 
     # ------------------------------------------------------------------ 'MLP' arch (per-operator composition, inference and training)

@@ -539,9 +539,10 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
     # ------------------------------------------------------------------ native sampling loop
     def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                        clip_denoised=False):
+                        clip_denoised=False, ddim_eta: Optional[float] = None):
         """Whole p_sample_loop on the device: x holds x_T on entry, returns the final sample.  ``clip_denoised``: pred_xstart clamped to
-        [-1, 1] inside the fused DDPM update (the reference's default argument; test.py passes False).  ``progress`` (test.py:85 passes
+        [-1, 1] inside the fused DDPM update (the reference's default argument; test.py passes False).  ``ddim_eta`` not None: the
+        ddim_sample_loop with that eta instead (afm_cmdm_ddim_loop_range: the same launches, the DDIM update in the same epilogue).  ``progress`` (test.py:85 passes
         True) splits the chain into ~50 native slices (afm_cmdm_sample_loop_range) and advances a tqdm bar between them; the
         result is bit-identical to the unsliced loop."""
         if any(k in model_kwargs for k in COND_SWITCHES):
@@ -559,7 +560,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             fm = model_kwargs["x_mask"].to(device=x.device, dtype=torch.uint8).contiguous() if self.mask_motion else None
             tab = diffusion.tables(x.device)
             n = diffusion.num_timesteps
-            sched = ffi.sched_scratch(self, n, B, x.device)
+            sched = ffi.sched_scratch(self, n, B, x.device, ddim=ddim_eta is not None)
+            ddim = None if ddim_eta is None else diffusion.ddim_tables(x.device, ddim_eta)
             # sub-batch streams fill the wave-quantisation tails of B >= 16 launches; below that every launch is latency-bound and a
             # second stream only adds launches (B = 4: 1311 steps/s on one stream vs 1159 on two, profiles/r02_small_batch.md)
             nsub = max(1, min(int(self.loop_streams), B // 8 if self.loop_streams_auto else B))
@@ -579,6 +581,13 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def enqueue(j0, j1):        # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo, cnt = n - j1, j1 - j0
+                if ddim is not None:
+                    ffi.check(lib.afm_cmdm_ddim_loop_range(
+                        C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm),
+                        None if step_noise is None else step_noise[j0:j1].data_ptr(), tab.timestep_map[lo:].data_ptr(), C.byref(ddim.rows(lo)),
+                        cnt, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
+                        nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream), "afm_cmdm_ddim_loop_range")
+                    return
                 ffi.check(lib.afm_cmdm_sample_loop_range(
                     C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm),
                     None if step_noise is None else step_noise[j0:j1].data_ptr(),
@@ -600,5 +609,5 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             else:
                 ffi.run_slices(slices, enqueue, progress, x.device)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (sched, step_noise, cond, fm)
+            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim)
         return x

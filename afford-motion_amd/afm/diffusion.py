@@ -4,13 +4,14 @@ cosine schedule, x0-prediction, fixed-small variance, MSE loss - SURVEY.md secti
 Public surface mirrors the reference (diffusion/gaussian_diffusion.py, diffusion/respace.py):
 `get_named_beta_schedule`, `ModelMeanType/ModelVarType/LossType`, `GaussianDiffusion`,
 `space_timesteps`, `SpacedDiffusion` with `num_timesteps`, `q_sample`, `p_sample`,
-`p_sample_loop(_progressive)` and `training_losses` taking the same arguments.
+`p_sample_loop(_progressive)`, `ddim_sample`, `ddim_reverse_sample`, `ddim_sample_loop(_progressive)` and `training_losses`
+taking the same arguments.
 
 MI355X-first differences (results unchanged):
   * schedule rows live on the device as float32 tensors (the reference re-uploads five
     float64 tables and rebuilds the timestep map every step, gaussian_diffusion.py:829-842,
     respace.py:124-129); per-step timestep vectors are slices of one pre-built tensor.
-  * the posterior update is one HIP kernel (afm_ddpm_step) or the fused epilogue of the
+  * the posterior update is one HIP kernel (afm_ddpm_step / afm_ddim_step) or the fused epilogue of the
     denoiser's last GEMM; for our own denoisers the whole loop is enqueued natively
     (afm_cmdm_sample_loop) with no host synchronisation.
   * noise is explicit (`step_noise`) or counter-based Philox keyed by (seed, global sample
@@ -92,6 +93,37 @@ class _DeviceTables:
         return self._tvec[batch]
 
 
+class _DdimTables:
+    """DDIM rows of one (device, eta) - or of the reverse step - as float32 device tensors indexed by the spaced timestep.
+
+    Built ONCE on the CPU in float32 torch, one operation at a time in the reference's order (ddim_sample, gaussian_diffusion.py:565-579,
+    on the `_extract_into_tensor(...).float()` casts of the float64 tables), then uploaded: a DDIM loop does no host arithmetic and launches
+    no ATen arithmetic kernel.  ``sigma`` is the noise coefficient (t != 0) * sigma_t; None when it is zero everywhere (eta = 0, and the
+    reverse step): then the update has no noise term and no noise is drawn (mean + 0 * noise == mean)."""
+
+    def __init__(self, d: "GaussianDiffusion", device: torch.device, eta: float, reverse: bool = False):
+        f = lambda arr: torch.from_numpy(np.asarray(arr, dtype=np.float64)).float()
+        a, b = f(d.sqrt_recip_alphas_cumprod), f(d.sqrt_recipm1_alphas_cumprod)
+        if reverse:                        # ddim_reverse_sample (gaussian_diffusion.py:612-620)
+            abn = f(d.alphas_cumprod_next)
+            c, dd, s = torch.sqrt(abn), torch.sqrt(1 - abn), None
+        else:
+            ab, abp = f(d.alphas_cumprod), f(d.alphas_cumprod_prev)
+            sigma = eta * torch.sqrt((1 - abp) / (1 - ab)) * torch.sqrt(1 - ab / abp)
+            c = torch.sqrt(abp)
+            dd = torch.sqrt(1 - abp - sigma ** 2)
+            s = (torch.arange(d.num_timesteps) != 0).float() * sigma
+            if not bool((s != 0).any()):
+                s = None
+        up = lambda t: None if t is None else t.contiguous().to(device)
+        self.a, self.b, self.c, self.d, self.sigma = up(a), up(b), up(c), up(dd), up(s)
+
+    def rows(self, lo: int = 0) -> "ffi.DdimRows":
+        """afm_ddim_rows of the timestep indices lo.. (device pointers; the tensors stay owned by this object)."""
+        p = lambda t: None if t is None else t[lo:].data_ptr()
+        return ffi.DdimRows(p(self.a), p(self.b), p(self.c), p(self.d), p(self.sigma))
+
+
 class GaussianDiffusion:
     """Schedule tables (float64 numpy, same attribute names as the reference,
     gaussian_diffusion.py:119-170) + sampling / loss entry points."""
@@ -131,6 +163,7 @@ class GaussianDiffusion:
         else:   # FIXED_LARGE (gaussian_diffusion.py:283-286)
             self.model_log_variance_table = np.log(np.append(self.posterior_variance[1], betas[1:]))
         self._tables: Dict[str, _DeviceTables] = {}
+        self._ddim: Dict[tuple, _DdimTables] = {}
 
     # ------------------------------------------------------------------ helpers
     def tables(self, device) -> _DeviceTables:
@@ -138,6 +171,13 @@ class GaussianDiffusion:
         if key not in self._tables:
             self._tables[key] = _DeviceTables(self, torch.device(device))
         return self._tables[key]
+
+    def ddim_tables(self, device, eta: float = 0.0, reverse: bool = False) -> _DdimTables:
+        """DDIM rows for (device, eta) - or of the reverse step - built once and cached like `tables`."""
+        key = (str(torch.device(device)), "reverse" if reverse else float(eta))
+        if key not in self._ddim:
+            self._ddim[key] = _DdimTables(self, torch.device(device), float(eta), reverse)
+        return self._ddim[key]
 
     def _model_timesteps(self, t: torch.Tensor, tab: _DeviceTables) -> torch.Tensor:
         ts = tab.timestep_map[t]
@@ -210,6 +250,78 @@ class GaussianDiffusion:
         (seed, sample_index0 + b, step).  Denoisers exposing ``afm_native_loop`` (our CMDM / CDM)
         run the whole loop natively without host synchronisation.  ``snapshots`` = {executed-step count: None} is filled with
         clones of x after those steps (what iterating p_sample_loop_progressive would have shown)."""
+        return self._sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
+                                 step_noise, seed, sample_index0, snapshots, ddim_eta=None)
+
+    # ------------------------------------------------------------------ DDIM
+    def _pred_xstart(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, tab):
+        """p_mean_variance's pred_xstart for START_X models (gaussian_diffusion.py:289-294), as p_sample computes it."""
+        x0 = model(x, self._model_timesteps(t, tab), **(model_kwargs or {}))
+        if denoised_fn is not None:
+            x0 = denoised_fn(x0)
+        if clip_denoised:      # on a private copy (see p_sample)
+            x0 = ops.clamp_(ffi.f32c(x0).clone(), -1.0, 1.0)
+        return x0
+
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0, *,
+                    noise: Optional[torch.Tensor] = None, seed: int = 0, sample_index0: int = 0, step: int = 0):
+        """One DDIM step x_t -> x_{t-1} (reference gaussian_diffusion.py:538-586): the update is afm_ddim_step with the cached rows of eta.
+        ``noise`` replaces the `randn_like` draw, otherwise Philox keyed by (seed, sample_index0 + b, step)."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn guidance is unreachable from the reference's entry points")
+        tab = self.tables(x.device)
+        rows = self.ddim_tables(x.device, eta)
+        with torch.no_grad():
+            x0 = self._pred_xstart(model, x, t, clip_denoised, denoised_fn, model_kwargs, tab)
+            sg = None if rows.sigma is None else rows.sigma[t]
+            sample = ops.ddim_step(x0, x, noise, rows.a[t], rows.b[t], rows.c[t], rows.d[t], sg, seed=seed,
+                                   sample_index0=sample_index0, step=step)
+        return {"sample": sample, "pred_xstart": x0}
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """One reverse-ODE step x_t -> x_{t+1} (reference gaussian_diffusion.py:588-624): deterministic, eta must be 0."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        tab = self.tables(x.device)
+        rows = self.ddim_tables(x.device, reverse=True)
+        with torch.no_grad():
+            x0 = self._pred_xstart(model, x, t, clip_denoised, denoised_fn, model_kwargs, tab)
+            sample = ops.ddim_step(x0, x, None, rows.a[t], rows.b[t], rows.c[t], rows.d[t], None)
+        return {"sample": sample, "pred_xstart": x0}
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, eta=0.0, *,
+                                     step_noise: Optional[Sequence[torch.Tensor]] = None, seed: Optional[int] = None,
+                                     sample_index0: int = 0):
+        """Generator over the DDIM steps (reference gaussian_diffusion.py:672-710); noise keyed as p_sample_loop_progressive."""
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        seed = self._fresh_seed("_sample_calls") if seed is None else seed
+        img = noise if noise is not None else ops.randn(tuple(shape), device, seed=seed, sample_index0=sample_index0, step=-1)
+        tvec = self.tables(device).timesteps(shape[0])
+        steps: Iterable[int] = range(self.num_timesteps - 1, -1, -1)
+        if progress:
+            from tqdm.auto import tqdm
+            steps = tqdm(list(steps))
+        for j, i in enumerate(steps):
+            out = self.ddim_sample(model, img, tvec[i], clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                   model_kwargs=model_kwargs, eta=eta, noise=None if step_noise is None else step_noise[j],
+                                   seed=seed, sample_index0=sample_index0, step=j)
+            yield out
+            img = out["sample"]
+
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, eta=0.0, *, step_noise=None, seed: Optional[int] = None, sample_index0: int = 0,
+                         snapshots: Optional[dict] = None):
+        """DDIM sampling (reference gaussian_diffusion.py:626-670).  The keyword-only extras are p_sample_loop's; denoisers exposing
+        ``afm_native_loop`` run the whole chain natively (the DDIM update fused where the DDPM update is) under the same conditions."""
+        return self._sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
+                                 step_noise, seed, sample_index0, snapshots, ddim_eta=float(eta))
+
+    def _sample_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, step_noise, seed,
+                     sample_index0, snapshots, ddim_eta: Optional[float]):
+        """p_sample_loop (ddim_eta None) / ddim_sample_loop: the native loop when the denoiser has one and nothing needs the host between
+        steps, else the progressive generator."""
         native = getattr(model, "afm_native_loop", None)
         switches = any(k in (model_kwargs or {}) for k in ("c_text_mask", "c_text_erase", "c_pc_mask", "c_pc_erase"))
         if native is not None and denoised_fn is None and cond_fn is None and not self.rescale_timesteps and not switches:
@@ -221,15 +333,18 @@ class GaussianDiffusion:
             if isinstance(step_noise, (list, tuple)):
                 step_noise = torch.stack(list(step_noise), 0)
             extra = {} if snapshots is None else {"snapshots": snapshots}
-            if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused DDPM update
+            if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused update
                 extra["clip_denoised"] = True
+            if ddim_eta is not None:
+                extra["ddim_eta"] = ddim_eta
             return native(self, x, model_kwargs or {}, step_noise=step_noise, seed=seed, sample_index0=sample_index0,
                           progress=bool(progress), **extra)
+        gen = self.p_sample_loop_progressive if ddim_eta is None else \
+            (lambda *a, **k: self.ddim_sample_loop_progressive(*a, eta=ddim_eta, **k))
         final, done = None, 0
-        for final in self.p_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                    denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs,
-                                                    device=device, progress=progress, step_noise=step_noise, seed=seed,
-                                                    sample_index0=sample_index0):
+        for final in gen(model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                         model_kwargs=model_kwargs, device=device, progress=progress, step_noise=step_noise, seed=seed,
+                         sample_index0=sample_index0):
             done += 1
             if snapshots is not None and done in snapshots:
                 snapshots[done] = final["sample"].clone()

@@ -146,6 +146,11 @@ class DdpmArgs(C.Structure):
                 ("seed", u64), ("sample_index0", i64), ("step", i32)]
 
 
+class DdimRows(C.Structure):
+    """afm_ddim_rows (v7-additive): device pointers of the five DDIM rows (a, b, c, d, sigma); sigma None = no noise term."""
+    _fields_ = [("a", c_f32p), ("b", c_f32p), ("c", c_f32p), ("d", c_f32p), ("sigma", c_f32p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "afm_version": (C.c_int, []),
@@ -161,6 +166,12 @@ EXPORTS = {
     "afm_layernorm_rows": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, i64, i32, C.c_float, i32, i32, i32, C.c_void_p]),
     "afm_ddpm_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i64, u64, i64, i32, C.c_void_p]),
     "afm_randn": (C.c_int, [c_f32p, i32, i64, u64, i64, i32, C.c_void_p]),
+    "afm_ddim_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(DdimRows), i32, i64, u64, i64, i32, C.c_void_p]),
+    "afm_ddim_sched_scratch_bytes": (i64, [i32, i32]),
+    "afm_cmdm_ddim_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                           i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_cdm_ddim_loop_range": (C.c_int, [C.POINTER(CdmWeights), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                          i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),
@@ -280,14 +291,15 @@ def stream_of(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
-def sched_scratch(owner, n_steps: int, batch: int, device) -> torch.Tensor:
+def sched_scratch(owner, n_steps: int, batch: int, device, *, ddim: bool = False) -> torch.Tensor:
     """The expanded-schedule scratch of a native sampling loop (afm_cmdm_sched_scratch_bytes), kept on `owner` (the model) across calls and
     grown geometrically from 1 MiB (1000 steps x 32 samples need 0.64 MB): a loop call allocates NOTHING after the first one, whatever its
     step count - a fresh device allocation inside a short loop call costs tens of milliseconds (tools/probe_k20_first.py: the first 20-step
     call 100 ms instead of 46).  Calls are stream-ordered, so the next call's expand kernel cannot overtake the previous call's readers."""
-    need = int(load().afm_cmdm_sched_scratch_bytes(n_steps, batch))
+    fn = "afm_ddim_sched_scratch_bytes" if ddim else "afm_cmdm_sched_scratch_bytes"     # (the DDIM loops: float4 row records)
+    need = int(getattr(load(), fn)(n_steps, batch))
     if need < 0:
-        check(need, "afm_cmdm_sched_scratch_bytes")
+        check(need, fn)
     cache = owner.__dict__.setdefault("_afm_sched", {})
     buf = cache.get(str(device))
     if buf is None or buf.numel() < need:

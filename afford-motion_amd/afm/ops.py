@@ -310,6 +310,25 @@ def ddpm_step(x0: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor]
     return out
 
 
+def ddim_step(x0: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor], a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
+              d: torch.Tensor, sigma: Optional[torch.Tensor], *, seed: int = 0, sample_index0: int = 0, step: int = 0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """DDIM update (afm_ddim_step): eps = (a*x_t - x0) / b, x_next = (x0*c + d*eps) + sigma*noise, per-sample rows [B], every operation
+    rounded on its own.  sigma None: no noise term (ddim_reverse_sample); noise None: Philox keyed like ddpm_step."""
+    lib = ffi.load()
+    ffi.require_gpu(x0, x_t)
+    x0, x_t = ffi.f32c(x0), ffi.f32c(x_t)
+    B = x0.shape[0]
+    per = x0.numel() // max(B, 1)
+    out = torch.empty_like(x0) if out is None else out
+    nz = None if noise is None or sigma is None else ffi.f32c(noise)
+    keep = [ffi.f32c(r) for r in (a, b, c, d)] + ([] if sigma is None else [ffi.f32c(sigma)])
+    rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], None if sigma is None else keep[4].data_ptr())
+    ffi.check(lib.afm_ddim_step(x0.data_ptr(), x_t.data_ptr(), ffi.ptr(nz), out.data_ptr(), C.byref(rows), B, per, seed & (2**64 - 1),
+                                sample_index0, step, ffi.stream_of(x0)), "afm_ddim_step")
+    return out
+
+
 def randn(shape, device, *, seed: int, sample_index0: int = 0, step: int = 0) -> torch.Tensor:
     """Counter-based N(0,1) noise keyed by (seed, global sample index, step, element)."""
     lib = ffi.load()

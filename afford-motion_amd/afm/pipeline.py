@@ -20,25 +20,33 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
                      x_mask: Optional[torch.Tensor] = None, sigma: float = 0.8, contact_mean: float = 0.0,
                      contact_std: float = 1.0, seed: int = 0, sample_index0: int = 0,
                      adm_noise: Optional[Dict[str, torch.Tensor]] = None,
-                     amdm_noise: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                     amdm_noise: Optional[Dict[str, torch.Tensor]] = None, sampler: str = "ddpm",
+                     eta: float = 0.0) -> Dict[str, torch.Tensor]:
     """text_feat [B, text_dim], xyz [B, N, 3] (B = scenes x k_sample, already flattened) ->
     {"contact": [B, N, J] ADM sample, "cond": [B, N, J] AMDM condition, "motion": [B, frames, D]}.
 
     ``*_noise`` = optional {"x_T": ..., "steps": [T, ...]} explicit noise (parity tests); otherwise Philox
-    keyed by (seed, sample_index0 + b), stage 2 uses seed + 1."""
+    keyed by (seed, sample_index0 + b), stage 2 uses seed + 1.  ``sampler`` = "ddpm" (p_sample_loop) or "ddim" (ddim_sample_loop with
+    ``eta``) for both stages; DDIM runs the spaced process of each diffusion (e.g. timestep_respacing="ddim50")."""
+    if sampler not in ("ddpm", "ddim"):
+        raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+
+    def loop(diffusion, *args, **kw):
+        if sampler == "ddim":
+            return diffusion.ddim_sample_loop(*args, eta=eta, **kw)
+        return diffusion.p_sample_loop(*args, **kw)
+
     B, N = xyz.shape[0], xyz.shape[1]
     dev = xyz.device
     adm_kw = dict(c_text_feat=text_feat, c_pc_xyz=xyz)
     an = adm_noise or {}
-    contact = adm_diffusion.p_sample_loop(adm, (B, N, adm.contact_dim), noise=an.get("x_T"), clip_denoised=False,
-                                          model_kwargs=adm_kw, step_noise=an.get("steps"), seed=seed,
-                                          sample_index0=sample_index0)
+    contact = loop(adm_diffusion, adm, (B, N, adm.contact_dim), noise=an.get("x_T"), clip_denoised=False,
+                   model_kwargs=adm_kw, step_noise=an.get("steps"), seed=seed, sample_index0=sample_index0)
     cond = adist.adm_to_amdm_condition(contact, sigma=sigma, mean=contact_mean, std=contact_std)
     if x_mask is None:
         x_mask = torch.zeros(B, frames, dtype=torch.bool, device=dev)
     amdm_kw = dict(c_text_feat=text_feat, c_pc_xyz=xyz, c_pc_contact=cond, x_mask=x_mask)
     mn = amdm_noise or {}
-    motion = amdm_diffusion.p_sample_loop(amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
-                                          model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1,
-                                          sample_index0=sample_index0)
+    motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
+                  model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
     return {"contact": contact, "cond": cond, "motion": motion}

@@ -13,6 +13,11 @@
 #include "common.h"
 
 extern "C" int afm_linear(const afm_linear_args*, void*);
+// elementwise.hip: the DDIM update of a native loop's step from the stored pred_xstart (see afm_ddim_update_rows)
+__attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, float* x, const float* noise, const float4* rec, const float* s, int32_t B,
+                                                               int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
+__attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tmap, const afm_ddim_rows* rows, int32_t n_steps, int32_t B, int64_t* t_all,
+                                                               float4* rec_all, float* s_all, void* stream);
 extern "C" int afm_linear_pair(const afm_linear_args*, const afm_linear_args*, void*);
 extern "C" int afm_mha_fwd_grouped(const float*, const uint8_t*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, void*);
 extern "C" int afm_mha_fwd_rows(const float*, const uint8_t*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, void*);
@@ -29,6 +34,7 @@ inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 constexpr int NOISE_STEPS = 16;
 struct Workspace {
     float *seq0, *y, *x1, *tmp, *qkv, *qkv0, *att, *hid, *noise, *xpad;
+    float* x0;                // loop workspaces only: pred_xstart [B][L][motion_dim] of the DDIM loop's step (its update launch reads it)
     uint8_t* keymask;
     uint32_t* lncnt;          // tickets of the fused LayerNorm (one word per 32 output rows; zero between launches)
     float *stat1, *stat2;     // folded LayerNorm: (mean, M2) per row and 64-column group of the raw out_proj / linear2 outputs
@@ -54,6 +60,8 @@ Workspace carve(const afm_cmdm_weights& w, int B, int L, void* base, int noise_s
     ws.lncnt = (uint32_t*)take(((M + 31) / 32) * 4);
     ws.stat1 = (float*)take(M * (d / 64 + 1) * 2 * 4); ws.stat2 = (float*)take(M * (d / 64 + 1) * 2 * 4);
     ws.xpad = w.motion_adapter_kpad > 0 ? (float*)take((int64_t)B * L * w.motion_adapter_kpad * 4) : nullptr;      // x_t with rows padded to the GEMM's K
+    // behind every other region, so the single-step layout is unchanged
+    ws.x0 = noise_steps > 1 ? (float*)take((int64_t)B * L * w.motion_dim * 4) : nullptr;
     ws.bytes = off;
     return ws;
 }
@@ -294,7 +302,12 @@ int forward_impl(const afm_cmdm_weights& w, const float* x_t, const int64_t* t, 
             a.W = w.motion_layer_wg; a.bias = w.motion_layer_c; a.a_stat = ws.stat2; a.a_stat_groups = sg; a.a_fold_g = w.motion_layer_g; a.ln_eps2 = 1e-5f;
         }
         a.a_grp = L; a.a_stride = T; a.a_off = 1 + w.n_cond;
-        if (ddpm) {
+        if (ddpm && (w.flags & AFM_PRIV_DDIM)) {
+            // native DDIM loop: pred_xstart goes to the loop workspace's own buffer; the loop's DDIM update launch (afm_ddim_update_rows)
+            // then writes x_next and its K-padded copy.  The GEMM's epilogue is the one of the plain forward.
+            if (!ws.x0) return AFM_E_BADARG;
+            a.C = ws.x0; a.ldc = w.motion_dim;
+        } else if (ddpm) {
             const float* nz = ddpm->noise;
             if (rec && !nz) return AFM_E_UNSUPPORTED;      // (recorded steps get their noise from the loop)
             if (!nz) {
@@ -341,6 +354,10 @@ extern "C" int afm_cmdm_forward(const afm_cmdm_weights* w, const float* x_t, con
     if (!x0_out && !ddpm) return AFM_E_BADARG;
     if (ddpm && (!ddpm->x_next || !ddpm->c1 || !ddpm->c2 || !ddpm->sigma)) return AFM_E_BADARG;
     if (B == 0) return 0;
+    afm_cmdm_weights wpub;
+    if (w->flags & (AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE)) {        // library-private bits: never taken from a caller
+        wpub = *w; wpub.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE); w = &wpub;
+    }
     const Workspace ws = carve(*w, B, L, workspace);
     if (ws.bytes > workspace_bytes) return AFM_E_WORKSPACE;
     if ((w->flags & AFM_CMDM_FUSED_LN) &&           // ticket words of the opt-in fused LayerNorm only
@@ -351,6 +368,12 @@ extern "C" int afm_cmdm_forward(const afm_cmdm_weights* w, const float* x_t, con
 extern "C" int64_t afm_cmdm_sched_scratch_bytes(int32_t n_steps, int32_t B) {
     if (n_steps <= 0 || B < 0) return AFM_E_BADARG;
     return align256((int64_t)n_steps * B * 8) + 3 * align256((int64_t)n_steps * B * 4);
+}
+
+// DDIM loops (CMDM and CDM): t [n_steps][B] int64, {a, b, c, d} records [n_steps][B] float4, s [n_steps][B] float
+extern "C" int64_t afm_ddim_sched_scratch_bytes(int32_t n_steps, int32_t B) {
+    if (n_steps <= 0 || B < 0) return AFM_E_BADARG;
+    return align256((int64_t)n_steps * B * 8) + align256((int64_t)n_steps * B * 16) + align256((int64_t)n_steps * B * 4);
 }
 
 namespace {
@@ -402,16 +425,23 @@ static int issue_paired(const Recorder& A, const Recorder& B, hipStream_t sa, hi
     return 0;
 }
 
+// One loop body for both updates: `ddim` == NULL runs the ancestral DDPM update with the rows d_c1 / d_c2 / d_sigma (fused into the
+// motion_layer epilogue), otherwise the DDIM update with the rows *ddim (d_c* unused): motion_layer stores pred_xstart and ONE elementwise
+// launch per sub-batch and step (afm_ddim_update_rows) applies ddim_update.  (The update fused into the shared GEMM epilogue grew the
+// registers - and on three variants the scratch - of DDPM GEMM kernels that every sampling step runs; a launch of its own leaves them as
+// they were.)
 static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
                             const float* step_noise, const int64_t* d_timestep_map, const float* d_c1,
-                            const float* d_c2, const float* d_sigma, int32_t n_steps, int32_t first_step, uint64_t seed,
+                            const float* d_c2, const float* d_sigma, const afm_ddim_rows* ddim, int32_t n_steps, int32_t first_step, uint64_t seed,
                             int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                             int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
     AFM_TRY(validate(w, B, L));
-    if (!x || (w->n_cond > 0 && !cond_tokens) || !d_timestep_map || !d_c1 || !d_c2 || !d_sigma || n_steps <= 0 ||
+    const bool rows_ok = ddim ? (ddim->a && ddim->b && ddim->c && ddim->d) : (d_c1 && d_c2 && d_sigma);
+    if (!x || (w->n_cond > 0 && !cond_tokens) || !d_timestep_map || !rows_ok || n_steps <= 0 ||
         !sched_scratch || !workspace || n_streams < 0 || (n_streams > 1 && !side_streams))
         return AFM_E_BADARG;
     if (B == 0) return 0;
+    const bool noise_term = !ddim || ddim->sigma;          // eta = 0 DDIM rows: no noise is generated or read
     hipStream_t s0 = (hipStream_t)stream;
     int nsub = n_streams > 1 ? (n_streams < B ? n_streams : B) : 1;
     if (nsub > 16) nsub = 16;
@@ -419,11 +449,20 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
     char* sp = (char*)sched_scratch;
     const int64_t nb = (int64_t)n_steps * B;
     int64_t* t_all = (int64_t*)sp; sp += align256(nb * 8);
-    float* c1_all = (float*)sp; sp += align256(nb * 4);
-    float* c2_all = (float*)sp; sp += align256(nb * 4);
-    float* sg_all = (float*)sp;
-    hipLaunchKernelGGL(expand_schedule_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s0, d_timestep_map, d_c1, d_c2,
-                       d_sigma, n_steps, B, t_all, c1_all, c2_all, sg_all);
+    float *c1_all, *c2_all, *sg_all;
+    float4* rec_all = nullptr;
+    if (ddim) {                                            // layout of afm_ddim_sched_scratch_bytes
+        rec_all = (float4*)sp; sp += align256(nb * 16);
+        sg_all = (float*)sp;
+        c1_all = c2_all = (float*)rec_all;
+        AFM_TRY(afm_ddim_expand_rows(d_timestep_map, ddim, n_steps, B, t_all, rec_all, sg_all, s0));
+    } else {
+        c1_all = (float*)sp; sp += align256(nb * 4);
+        c2_all = (float*)sp; sp += align256(nb * 4);
+        sg_all = (float*)sp;
+        hipLaunchKernelGGL(expand_schedule_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s0, d_timestep_map, d_c1, d_c2,
+                           d_sigma, n_steps, B, t_all, c1_all, c2_all, sg_all);
+    }
     AFM_CHECK_LAUNCH();
 
     // carve one workspace per sub-batch
@@ -456,6 +495,8 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
     // calls, but 853 against 995 at 8 + 8 and 1168 against 1470 at 4 + 4 (profiles/r06_tile_rule.md) - so: sub-batches of >= 4096 rows only.
     // Tile shapes of one arithmetic are bit-identical; a caller's explicit AFM_CMDM_WIDE_TILE code wins.
     afm_cmdm_weights wl = *w;
+    wl.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE);                  // library-private: never taken from a caller
+    if (ddim) wl.flags |= AFM_PRIV_DDIM | (noise_term ? 0 : AFM_PRIV_NO_NOISE);
     if (nsub >= 2 && ((wl.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < nsub; ++s) big = big && (int64_t)count[s] * T >= 4096;
@@ -481,13 +522,20 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
             }
         recs = new Recorder[2];
     }
+    // the DDIM update of sub-batch s from its stored pred_xstart (ws.x0), in place on x, with the K-padded copy the next step reads
+    auto ddim_update = [&](int s, const afm_ddpm_args& dd) -> int {
+        return afm_ddim_update_rows(ws[s].x0, x + (int64_t)start[s] * row, noise_term ? dd.noise : nullptr, (const float4*)dd.c1,
+                                    noise_term ? dd.sigma : nullptr, count[s], row, w->motion_dim, (w->flags & AFM_CMDM_CLIP_X0) ? 1 : 0,
+                                    ws[s].xpad, w->motion_adapter_kpad, st[s]);
+    };
     for (int j = 0; j < n_steps && rc == 0; ++j) {
         const bool rec_step = paired && j > 0;
         if (rec_step) recs[0].n = recs[1].n = 0;
         for (int s = 0; s < nsub && rc == 0; ++s) {
             if (count[s] == 0) continue;
             afm_ddpm_args dd = {};
-            if (step_noise) dd.noise = step_noise + ((int64_t)j * B + start[s]) * row;
+            if (!noise_term) dd.noise = x + (int64_t)start[s] * row;        // (never read: AFM_UPD_NO_NOISE)
+            else if (step_noise) dd.noise = step_noise + ((int64_t)j * B + start[s]) * row;
             else {
                 if (j % NOISE_STEPS == 0) {               // one launch per NOISE_STEPS steps instead of one per step (a launch is ~5 us of a small-batch step)
                     rc = afm_randn_steps(ws[s].noise, count[s], row, seed, sample_index0 + start[s], first_step + j, n_steps - j < NOISE_STEPS ? n_steps - j : NOISE_STEPS, st[s]);
@@ -496,15 +544,23 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
                 dd.noise = ws[s].noise + (int64_t)(j % NOISE_STEPS) * count[s] * row;
             }
             dd.x_next = x + (int64_t)start[s] * row;      // in place: each element is read then written by the same lane
-            dd.c1 = c1_all + (int64_t)j * B + start[s]; dd.c2 = c2_all + (int64_t)j * B + start[s];
+            if (ddim) { dd.c1 = dd.c2 = (const float*)(rec_all + (int64_t)j * B + start[s]); }       // {a, b, c, d} records (AFM_UPD_DDIM)
+            else { dd.c1 = c1_all + (int64_t)j * B + start[s]; dd.c2 = c2_all + (int64_t)j * B + start[s]; }
             dd.sigma = sg_all + (int64_t)j * B + start[s];
             dd.seed = seed; dd.sample_index0 = sample_index0 + start[s]; dd.step = first_step + j;
             rc = forward_impl(*w, x + (int64_t)start[s] * row, t_all + (int64_t)j * B + start[s],
                               cond_tokens ? cond_tokens + (int64_t)start[s] * w->n_cond * w->d : nullptr,
                               frame_mask ? frame_mask + (int64_t)start[s] * L : nullptr, nullptr, &dd, count[s], L, ws[s], j == 0,
                               st[s], rec_step ? &recs[s] : nullptr);
+            if (rc == 0 && ddim && !rec_step) rc = ddim_update(s, dd);
         }
         if (rec_step && rc == 0) rc = issue_paired(recs[0], recs[1], st[0], st[1], pev, NEV);
+        for (int s = 0; ddim && rec_step && rc == 0 && s < nsub; ++s) {      // (the paired schedule: behind the sub-batch's recorded launches)
+            afm_ddpm_args dd = {};
+            dd.noise = !noise_term ? nullptr : step_noise ? step_noise + ((int64_t)j * B + start[s]) * row : ws[s].noise + (int64_t)(j % NOISE_STEPS) * count[s] * row;
+            dd.c1 = (const float*)(rec_all + (int64_t)j * B + start[s]); dd.sigma = sg_all + (int64_t)j * B + start[s];
+            rc = ddim_update(s, dd);
+        }
     }
     if (paired) {
         delete[] recs;
@@ -529,7 +585,7 @@ extern "C" int afm_cmdm_sample_loop(const afm_cmdm_weights* w, float* x, const f
                                     const float* d_c2, const float* d_sigma, int32_t n_steps, uint64_t seed,
                                     int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                     int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
-    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, n_steps, 0, seed,
+    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, 0, seed,
                             sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
 }
 
@@ -540,6 +596,16 @@ extern "C" int afm_cmdm_sample_loop_range(const afm_cmdm_weights* w, float* x, c
                                           void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                           void* const* side_streams, void* stream) {
     if (first_step < 0) return AFM_E_BADARG;
-    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, n_steps, first_step,
+    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step,
+                            seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
+}
+
+extern "C" int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                                        const uint8_t* frame_mask, const float* step_noise, const int64_t* d_timestep_map,
+                                        const afm_ddim_rows* rows, int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0,
+                                        int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
+                                        void* const* side_streams, void* stream) {
+    if (first_step < 0 || !rows) return AFM_E_BADARG;
+    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step,
                             seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
 }

@@ -290,3 +290,33 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, int64_t sample, in
     __sincosf(6.283185307179586f * u3, &s1, &c1);
     z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
 }
+
+// ---- DDIM update (ddim_sample / ddim_reverse_sample of gaussian_diffusion.py) of one element, the reference's float32 expression with every
+// operation rounded on its own:  eps = (a * x_t - x0) / b;  x_next = (x0 * c + d * eps) + s * noise.  r = {a, b, c, d} of the element's
+// sample (the per-step rows built by the host, afm_ddim_rows), s = (t != 0) * sigma.  Every DDIM site of the library (afm_ddim_step, the loops'
+// update launch, the CDM output kernels) calls this one helper: the same x0 gives the same bits in every form.
+__device__ __forceinline__ float ddim_update(float x0, float xt, const float4& r) {
+#pragma clang fp contract(off)
+    const float ax = r.x * xt;
+    const float df = ax - x0;
+    const float eps = df / r.y;                 // IEEE division (no reciprocal, no fast-math)
+    const float m1 = x0 * r.z;
+    const float m2 = r.w * eps;
+    return m1 + m2;
+}
+__device__ __forceinline__ float ddim_update(float x0, float xt, const float4& r, float s, float nz) {
+#pragma clang fp contract(off)
+    const float mean = ddim_update(x0, xt, r);
+    const float sn = s * nz;
+    return mean + sn;
+}
+
+// Selectors of the sampling update of the CDM's fused output kernels (their `clip` argument; library-private):
+//   AFM_UPD_DDIM      c1 -> float4 {a, b, c, d} per sample (16-byte aligned), sigma -> s per sample, c2 unused
+//   AFM_UPD_NO_NOISE  DDIM without the noise term (eta = 0 rows: s == 0 everywhere; noise is never read)
+#define AFM_UPD_CLIP 0x1
+#define AFM_UPD_DDIM 0x2
+#define AFM_UPD_NO_NOISE 0x4
+// private bits of afm_cmdm_weights.flags / afm_cdm_weights.flags inside the library (set on the loop's own copy of the pack)
+#define AFM_PRIV_DDIM 0x40000000
+#define AFM_PRIV_NO_NOISE 0x20000000

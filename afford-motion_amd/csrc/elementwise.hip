@@ -66,6 +66,51 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict_
     }
 }
 
+// DDIM update (ddim_sample / ddim_reverse_sample): ddim_update of common.h per element; sg == NULL: no noise term
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict__ x0, const float* xt, const float* __restrict__ noise,
+                                                        float* xn, const float* __restrict__ ra, const float* __restrict__ rb,
+                                                        const float* __restrict__ rc, const float* __restrict__ rd,
+                                                        const float* __restrict__ sg, int64_t per_sample, uint64_t seed, int64_t sample0, int step) {
+    const int b = blockIdx.y;
+    const float4 r = make_float4(ra[b], rb[b], rc[b], rd[b]);
+    const float s = sg ? sg[b] : 0.f;
+    const int64_t base = (int64_t)b * per_sample;
+    const int64_t nquad = (per_sample + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
+        float z[4];
+        if (sg && !noise) philox_normal4(seed, sample0 + b, step, (uint64_t)q, z);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = q * 4 + e;
+            if (i < per_sample) {
+                const float v0 = x0[base + i], vt = xt[base + i];
+                xn[base + i] = sg ? ddim_update(v0, vt, r, s, noise ? noise[base + i] : z[e]) : ddim_update(v0, vt, r);
+            }
+        }
+    }
+}
+
+// DDIM update of a native loop's step: x <- ddim_update(clamp?(x0), x, rec[b], s[b], noise) in place (one thread reads then writes an element),
+// plus the copy into the K-padded rows the next step's motion adapter reads (xpad [rows][ldpad], columns >= cols stay zero)
+__global__ __launch_bounds__(256) void ddim_update_rows_kernel(const float* __restrict__ x0, float* x, const float* __restrict__ noise,
+                                                               const float4* __restrict__ rec, const float* __restrict__ sg, int64_t per_sample,
+                                                               int cols, int clip, float* __restrict__ xpad, int64_t ldpad) {
+    const int b = blockIdx.y;
+    const float4 r = rec[b];
+    const float s = sg ? sg[b] : 0.f;
+    const int64_t base = (int64_t)b * per_sample;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * blockDim.x) {
+        float v = x0[base + i];
+        if (clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised (NaN passes through, as torch.clamp)
+        const float xn = sg ? ddim_update(v, x[base + i], r, s, noise[base + i]) : ddim_update(v, x[base + i], r);
+        x[base + i] = xn;
+        if (xpad) {
+            const int64_t g = base + i, row = g / cols;
+            xpad[row * ldpad + (g - row * cols)] = xn;
+        }
+    }
+}
+
 // grid (x, B, steps): blockIdx.z = a further step of the same keying, its [B][per_sample] block behind the previous one
 __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int64_t per_sample, uint64_t seed,
                                                     int64_t sample0, int step) {
@@ -232,6 +277,56 @@ extern "C" int afm_ddpm_step(const float* x0, const float* x_t, const float* noi
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(ddpm_step_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x_t, noise, x_next, c1, c2, sigma,
                        per_sample, seed, sample_index0, step);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int afm_ddim_step(const float* x0, const float* x_t, const float* noise, float* x_next, const afm_ddim_rows* rows,
+                             int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0, int32_t step, void* stream) {
+    if (!x0 || !x_t || !x_next || !rows || !rows->a || !rows->b || !rows->c || !rows->d || B < 0 || per_sample <= 0) return AFM_E_BADARG;
+    if (B == 0) return 0;
+    const int64_t nquad = (per_sample + 3) >> 2;
+    unsigned gx = (unsigned)((nquad + 255) / 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x_t, noise, x_next, rows->a, rows->b, rows->c,
+                       rows->d, rows->sigma, per_sample, seed, sample_index0, step);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+// the DDIM update of a native loop's step (cmdm.hip, perceiver.hip): x0 [B][per_sample] pred_xstart, x [B][per_sample] x_t -> x_next in
+// place, rec [B] {a, b, c, d}, s [B] (NULL: no noise term, `noise` not read), rows of `cols` values copied to xpad (row stride ldpad) if given
+__attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, float* x, const float* noise, const float4* rec, const float* s, int32_t B,
+                                                               int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream) {
+    if (!x0 || !x || !rec || (s && !noise) || B < 0 || per_sample <= 0 || cols <= 0 || (xpad && ldpad < cols)) return AFM_E_BADARG;
+    if (B == 0) return 0;
+    unsigned gx = (unsigned)((per_sample + 255) / 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(ddim_update_rows_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x, noise, rec, s, per_sample, cols, clip, xpad, ldpad);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+// the DDIM rows of a native loop (cmdm.hip, perceiver.hip), expanded like their DDPM rows: entry e = j * B + b of step j (timestep index
+// n_steps - 1 - j of the slice's rows): t_all[e] = tmap[i], rec_all[e] = {a, b, c, d}[i], s_all[e] = sigma[i] (rows->sigma NULL: s_all not written)
+__global__ void ddim_expand_kernel(const int64_t* __restrict__ tmap, const float* __restrict__ ra, const float* __restrict__ rb,
+                                   const float* __restrict__ rc, const float* __restrict__ rd, const float* __restrict__ sg, int n_steps, int B,
+                                   int64_t* __restrict__ t_all, float4* __restrict__ rec_all, float* __restrict__ s_all) {
+    const int64_t n = (int64_t)n_steps * B;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const int i = n_steps - 1 - (int)(e / B);
+        t_all[e] = tmap[i]; rec_all[e] = make_float4(ra[i], rb[i], rc[i], rd[i]);
+        if (sg) s_all[e] = sg[i];
+    }
+}
+
+__attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tmap, const afm_ddim_rows* rows, int32_t n_steps, int32_t B, int64_t* t_all,
+                                                               float4* rec_all, float* s_all, void* stream) {
+    if (!tmap || !rows || !t_all || !rec_all || (rows->sigma && !s_all) || n_steps <= 0 || B < 0) return AFM_E_BADARG;
+    const int64_t nb = (int64_t)n_steps * B;
+    if (nb == 0) return 0;
+    hipLaunchKernelGGL(ddim_expand_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tmap, rows->a, rows->b, rows->c, rows->d,
+                       rows->sigma, n_steps, B, t_all, rec_all, s_all);
     AFM_CHECK_LAUNCH();
     return 0;
 }

@@ -22,6 +22,10 @@
 #include "perceiver_internal.h"
 
 extern "C" int afm_linear(const afm_linear_args*, void*);
+__attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, float* x, const float* noise, const float4* rec, const float* s, int32_t B,
+                                                               int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
+__attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tmap, const afm_ddim_rows* rows, int32_t n_steps, int32_t B, int64_t* t_all,
+                                                               float4* rec_all, float* s_all, void* stream);
 
 using namespace afm_cdm;
 
@@ -296,6 +300,16 @@ static int cdm_forward_impl(const afm_cdm_weights* wp, const float* feat, const 
     a = {};
     a.A = ws.z; a.lda = dkv; a.W = w.contact_layer.w; a.ldw = dkv; a.C = x0_out; a.ldc = w.contact_dim;
     a.M = M; a.N = w.contact_dim; a.K = dkv; a.bias = w.contact_layer.b;
+    const int upd = ddpm ? cdm_update_bits(w) : 0;
+    if (upd & AFM_UPD_DDIM) {       // native DDIM loop: pred_xstart to bufB (read by nothing after fc2), then the DDIM update in place on x_t
+        if (dkv < w.contact_dim) return AFM_E_UNSUPPORTED;          // (bufB holds [M][dkv]; pred_xstart needs [M][contact_dim])
+        a.C = ws.bufB;
+        a.arith = w.gemm_arith; a.arith_min_n = w.gemm_arith_min_n;
+        AFM_TRY(afm_linear(&a, s));
+        return afm_ddim_update_rows(ws.bufB, ddpm->x_next, (upd & AFM_UPD_NO_NOISE) ? nullptr : ddpm->noise, (const float4*)ddpm->c1,
+                                    (upd & AFM_UPD_NO_NOISE) ? nullptr : ddpm->sigma, B, (int64_t)N * w.contact_dim, w.contact_dim, upd & AFM_UPD_CLIP,
+                                    nullptr, 0, s);
+    }
     if (ddpm) {
         a.ddpm_xt = x_t; a.ddpm_noise = ddpm->noise; a.ddpm_out = ddpm->x_next; a.ldx = w.contact_dim;
         a.ddpm_c1 = ddpm->c1; a.ddpm_c2 = ddpm->c2; a.ddpm_sigma = ddpm->sigma; a.rows_per_sample = N;
@@ -310,6 +324,8 @@ extern "C" int afm_cdm_forward(const afm_cdm_weights* wp, const float* feat, con
                                const float* text_q0, const float* text_u, const float* text_cu, float* x0_out,
                                const afm_ddpm_args* ddpm, int32_t B, int32_t N, void* workspace, int64_t workspace_bytes,
                                void* stream) {
+    afm_cdm_weights wpub;
+    if (wp && (wp->flags & (AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE))) { wpub = *wp; wpub.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE); wp = &wpub; }      // library-private bits
     return cdm_forward_impl(wp, feat, x_t, t, text_q0, text_u, text_cu, x0_out, ddpm, B, N, workspace, workspace_bytes, nullptr, stream);
 }
 
@@ -317,6 +333,8 @@ extern "C" int afm_cdm_forward_overlap(const afm_cdm_weights* wp, const float* f
                                        const float* text_q0, const float* text_u, const float* text_cu, float* x0_out,
                                        const afm_ddpm_args* ddpm, int32_t B, int32_t N, void* workspace, int64_t workspace_bytes,
                                        void* side_stream, void* stream) {
+    afm_cdm_weights wpub;
+    if (wp && (wp->flags & (AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE))) { wpub = *wp; wpub.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE); wp = &wpub; }      // library-private bits
     return cdm_forward_impl(wp, feat, x_t, t, text_q0, text_u, text_cu, x0_out, ddpm, B, N, workspace, workspace_bytes, side_stream, stream);
 }
 
@@ -369,16 +387,24 @@ extern "C" int64_t afm_cdm_loop_workspace_bytes(const afm_cdm_weights* w, int32_
 // sample on exit; feat [B,N,feat_dim] holds the step-invariant columns (point features, xyz) - its leading contact_dim columns are
 // rewritten from x every step.  Sub-batch s runs on streams[2s] with streams[2s+1] as the side stream of its decoder-adapter GEMM
 // (n_sub <= 1: everything on `stream`, streams[0] = optional side stream).
+// One loop body for both updates: `ddim` == NULL runs the DDPM update with d_c1 / d_c2 / d_sigma, otherwise the DDIM update with the rows
+// *ddim - in the same fused site of every sampling form, with the same launches per step.
 static int cdm_sample_loop_impl(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
                                 const float* text_cu, const float* step_noise, const int64_t* d_timestep_map, const float* d_c1,
-                                const float* d_c2, const float* d_sigma, int32_t n_steps, int32_t first_step, uint64_t seed,
+                                const float* d_c2, const float* d_sigma, const afm_ddim_rows* ddim, int32_t n_steps, int32_t first_step, uint64_t seed,
                                 int64_t sample_index0, int32_t B, int32_t N, void* sched_scratch, void* workspace, int64_t workspace_bytes,
                                 int32_t n_sub, void* const* streams, void* stream) {
     AFM_TRY(validate(w, B, N));
-    if (!x || !feat || !text_q0 || !text_u || !text_cu || !d_timestep_map || !d_c1 || !d_c2 || !d_sigma || n_steps <= 0 || !sched_scratch ||
+    const bool rows_ok = ddim ? (ddim->a && ddim->b && ddim->c && ddim->d) : (d_c1 && d_c2 && d_sigma);
+    if (!x || !feat || !text_q0 || !text_u || !text_cu || !d_timestep_map || !rows_ok || n_steps <= 0 || !sched_scratch ||
         !workspace || n_sub < 0 || (n_sub > 1 && !streams))
         return AFM_E_BADARG;
     if (B == 0) return 0;
+    const bool noise_term = !ddim || ddim->sigma;          // eta = 0 DDIM rows: no noise is generated or read
+    afm_cdm_weights wl = *w;                               // the loop's own pack: the update selectors are library-private flag bits
+    wl.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE);
+    if (ddim) wl.flags |= AFM_PRIV_DDIM | (noise_term ? 0 : AFM_PRIV_NO_NOISE);
+    w = &wl;
     hipStream_t s0 = (hipStream_t)stream;
     int nsub = n_sub > 1 ? (n_sub < B ? n_sub : B) : 1;
     if (nsub > 8) nsub = 8;
@@ -387,11 +413,20 @@ static int cdm_sample_loop_impl(const afm_cdm_weights* w, float* x, float* feat,
     char* sp = (char*)sched_scratch;
     const int64_t nb = (int64_t)n_steps * B;
     int64_t* t_all = (int64_t*)sp; sp += align256(nb * 8);
-    float* c1_all = (float*)sp; sp += align256(nb * 4);
-    float* c2_all = (float*)sp; sp += align256(nb * 4);
-    float* sg_all = (float*)sp;
-    hipLaunchKernelGGL(cdm_expand_schedule_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s0, d_timestep_map, d_c1, d_c2, d_sigma, n_steps, B,
-                       t_all, c1_all, c2_all, sg_all);
+    float *c1_all, *c2_all, *sg_all;
+    if (ddim) {                                            // layout of afm_ddim_sched_scratch_bytes; c1 / c2 -> the {a, b, c, d} records
+        float4* rec_all = (float4*)sp; sp += align256(nb * 16);
+        sg_all = (float*)sp;
+        c1_all = (float*)rec_all; c2_all = c1_all;
+        AFM_TRY(afm_ddim_expand_rows(d_timestep_map, ddim, n_steps, B, t_all, rec_all, sg_all, s0));
+    } else {
+        c1_all = (float*)sp; sp += align256(nb * 4);
+        c2_all = (float*)sp; sp += align256(nb * 4);
+        sg_all = (float*)sp;
+        hipLaunchKernelGGL(cdm_expand_schedule_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s0, d_timestep_map, d_c1, d_c2, d_sigma, n_steps, B,
+                           t_all, c1_all, c2_all, sg_all);
+    }
+    const int rstride = ddim ? 4 : 1;                      // floats per row entry of c1_all / c2_all
     AFM_CHECK_LAUNCH();
 
     const bool rowless = cdm_mode(*w) == 3;
@@ -468,7 +503,7 @@ static int cdm_sample_loop_impl(const afm_cdm_weights* w, float* x, float* feat,
         }
         auto part1 = [&](int s, int j) -> int {           // noise (every NOISE_STEPS steps), enc_point on H; the chain + decoder tables on the sub-batch's side stream
             if (count[s] == 0) return 0;
-            if (!step_noise && j % NOISE_STEPS == 0)
+            if (noise_term && !step_noise && j % NOISE_STEPS == 0)
                 AFM_TRY(afm_randn_steps(noise[s], count[s], per, seed, sample_index0 + start[s], first_step + j, n_steps - j < NOISE_STEPS ? n_steps - j : NOISE_STEPS, H));
             const int64_t* tj = t_all + (int64_t)j * B + start[s];
             AFM_TRY(launch_enc_point(*w, text_u + (int64_t)start[s] * He * dkv, text_cu + (int64_t)start[s] * He, tj, count[s], N, wss[s],
@@ -483,10 +518,10 @@ static int cdm_sample_loop_impl(const afm_cdm_weights* w, float* x, float* feat,
             if (count[s] == 0) return 0;
             if (hipStreamWaitEvent(H, e2[s], 0) != hipSuccess) return (int)hipGetLastError();
             afm_ddpm_args dd = {};
-            dd.noise = step_noise ? step_noise + ((int64_t)j * B + start[s]) * per : noise[s] + (int64_t)(j % NOISE_STEPS) * count[s] * per;
             float* xs = x + (int64_t)start[s] * per;
+            dd.noise = !noise_term ? xs : step_noise ? step_noise + ((int64_t)j * B + start[s]) * per : noise[s] + (int64_t)(j % NOISE_STEPS) * count[s] * per;
             dd.x_next = xs;
-            dd.c1 = c1_all + (int64_t)j * B + start[s]; dd.c2 = c2_all + (int64_t)j * B + start[s]; dd.sigma = sg_all + (int64_t)j * B + start[s];
+            dd.c1 = c1_all + ((int64_t)j * B + start[s]) * rstride; dd.c2 = c2_all + ((int64_t)j * B + start[s]) * rstride; dd.sigma = sg_all + (int64_t)j * B + start[s];
             dd.seed = seed; dd.sample_index0 = sample_index0 + start[s]; dd.step = first_step + j;
             return launch_dec_point(*w, count[s], N, wss[s], xs, feat + (int64_t)start[s] * N * fd, nullptr, &dd, H, false);
         };
@@ -510,7 +545,8 @@ static int cdm_sample_loop_impl(const afm_cdm_weights* w, float* x, float* feat,
             int64_t gx = (rows * cd + 255) / 256; if (gx > 2048) gx = 2048;
             if (!folded) hipLaunchKernelGGL(pack_x_kernel, dim3((unsigned)gx), dim3(256), 0, mainst[s], xs, fs, rows, cd, fd);
             afm_ddpm_args dd = {};
-            if (step_noise) dd.noise = step_noise + ((int64_t)j * B + start[s]) * per;
+            if (!noise_term) dd.noise = xs;               // (never read: AFM_UPD_NO_NOISE)
+            else if (step_noise) dd.noise = step_noise + ((int64_t)j * B + start[s]) * per;
             else {
                 if (j % NOISE_STEPS == 0) {               // the noise of the next NOISE_STEPS steps in one launch (6 us of launch per step otherwise)
                     rc = afm_randn_steps(noise[s], count[s], per, seed, sample_index0 + start[s], first_step + j, n_steps - j < NOISE_STEPS ? n_steps - j : NOISE_STEPS, mainst[s]);
@@ -519,7 +555,7 @@ static int cdm_sample_loop_impl(const afm_cdm_weights* w, float* x, float* feat,
                 dd.noise = noise[s] + (int64_t)(j % NOISE_STEPS) * count[s] * per;
             }
             dd.x_next = xs;                               // in place: each element is read then written by the same lane
-            dd.c1 = c1_all + (int64_t)j * B + start[s]; dd.c2 = c2_all + (int64_t)j * B + start[s]; dd.sigma = sg_all + (int64_t)j * B + start[s];
+            dd.c1 = c1_all + ((int64_t)j * B + start[s]) * rstride; dd.c2 = c2_all + ((int64_t)j * B + start[s]) * rstride; dd.sigma = sg_all + (int64_t)j * B + start[s];
             dd.seed = seed; dd.sample_index0 = sample_index0 + start[s]; dd.step = first_step + j;
             rc = cdm_forward_impl(w, fs, xs, t_all + (int64_t)j * B + start[s], text_q0 + (int64_t)start[s] * dq,
                                   text_u + (int64_t)start[s] * He * dkv, text_cu + (int64_t)start[s] * He, nullptr, &dd, count[s], N, wsp[s], wsb[s],
@@ -546,7 +582,7 @@ extern "C" int afm_cdm_sample_loop(const afm_cdm_weights* w, float* x, float* fe
                                    const float* d_c2, const float* d_sigma, int32_t n_steps, uint64_t seed, int64_t sample_index0, int32_t B,
                                    int32_t N, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams,
                                    void* stream) {
-    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, n_steps, 0, seed,
+    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, 0, seed,
                                 sample_index0, B, N, sched_scratch, workspace, workspace_bytes, n_sub, streams, stream);
 }
 
@@ -556,6 +592,15 @@ extern "C" int afm_cdm_sample_loop_range(const afm_cdm_weights* w, float* x, flo
                                          int64_t sample_index0, int32_t B, int32_t N, void* sched_scratch, void* workspace,
                                          int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream) {
     if (first_step < 0) return AFM_E_BADARG;
-    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, n_steps, first_step,
+    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step,
+                                seed, sample_index0, B, N, sched_scratch, workspace, workspace_bytes, n_sub, streams, stream);
+}
+
+extern "C" int afm_cdm_ddim_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
+                                       const float* text_cu, const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows,
+                                       int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t N,
+                                       void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream) {
+    if (first_step < 0 || !rows) return AFM_E_BADARG;
+    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step,
                                 seed, sample_index0, B, N, sched_scratch, workspace, workspace_bytes, n_sub, streams, stream);
 }

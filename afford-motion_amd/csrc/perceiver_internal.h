@@ -9,6 +9,13 @@
 __attribute__((visibility("hidden"))) int afm_randn_steps(float* out, int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0, int32_t step0, int32_t nsteps,
                                                           void* stream);
 
+// the AFM_UPD_* bits (common.h) of a sampling form's fused update: clip_denoised, and the DDIM selectors the native DDIM loop puts into its
+// own copy of the pack (AFM_PRIV_*, never taken from a caller)
+inline int cdm_update_bits(const afm_cdm_weights& w) {
+    return ((w.flags & AFM_CDM_CLIP_X0) ? AFM_UPD_CLIP : 0) | ((w.flags & AFM_PRIV_DDIM) ? AFM_UPD_DDIM : 0) |
+           ((w.flags & AFM_PRIV_NO_NOISE) ? AFM_UPD_NO_NOISE : 0);
+}
+
 namespace afm_cdm {
 
 constexpr int NSPLIT = 16;          // workgroups per sample in enc_reduce (x4 waves = 64 partials per sample)

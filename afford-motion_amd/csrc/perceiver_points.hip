@@ -344,7 +344,9 @@ template <int NKS> constexpr int dp_lds_floats() {
 
 // NPROD (round 6): cross products of linear1's three-term bf16 operands - 9 (all, exact f32 products) or 6 (the six largest: the arithmetic of
 // afm_linear's AFM_ARITH_BF16X6 / AFM_ARITH_DEFAULT, tests/test_gpu_arith.py), chosen by afm_cdm_weights.gemm_arith like every GEMM of the denoiser.
-template <int NKS, int NPROD>
+// DDIM: the update of x_next is ddim_update (common.h) with c1 -> {a, b, c, d} records and sigma -> s, `clip` carrying the AFM_UPD_* bits
+// (a template parameter: the DDPM instantiations are the code they were)
+template <int NKS, int NPROD, bool DDIM>
 __global__ __launch_bounds__(64 * RowLess<NKS>::NW, NKS <= 4 ? 2 : 1)
 void dec_point_kernel(const float* __restrict__ twp, const float* __restrict__ qtab, const float* __restrict__ qdd, const float* __restrict__ twx,
                       const float* __restrict__ cvec, const float* __restrict__ w2f, const float* __restrict__ gen_qe, const float* __restrict__ c0, int N, int cd,
@@ -537,9 +539,14 @@ void dec_point_kernel(const float* __restrict__ twp, const float* __restrict__ q
                 if (j < cd) {
                     const int64_t i = pt * cd + j;
                     float v = sat[r] + c0s[j];
-                    if (clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);      // clip_denoised
+                    if (clip & AFM_UPD_CLIP) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);      // clip_denoised
                     if (x0_out) x0_out[i] = v;
-                    if (x_next) x_next[i] = (c1[b] * v + c2[b] * xt[i]) + sigma[b] * noise[i];
+                    if (DDIM) {
+                        if (x_next) {
+                            const float4 r = reinterpret_cast<const float4*>(c1)[b];
+                            x_next[i] = (clip & AFM_UPD_NO_NOISE) ? ddim_update(v, xt[i], r) : ddim_update(v, xt[i], r, sigma[b], noise[i]);
+                        }
+                    } else if (x_next) x_next[i] = (c1[b] * v + c2[b] * xt[i]) + sigma[b] * noise[i];
                 }
             }
         }
@@ -608,7 +615,10 @@ int launch_dec_point_p(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, 
                        const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables) {
     constexpr int LDS = dp_lds_floats<NKS>() * (int)sizeof(float);
     static_assert(LDS <= 160 * 1024, "dec_point_kernel's tables fit the LDS");
-    static const int attr = []() { return (int)hipFuncSetAttribute((const void*)dec_point_kernel<NKS, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); }();
+    static const int attr = []() {
+        const int rc = (int)hipFuncSetAttribute((const void*)dec_point_kernel<NKS, NPROD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        return rc ? rc : (int)hipFuncSetAttribute((const void*)dec_point_kernel<NKS, NPROD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    }();
     if (attr != 0) return attr;
     if (with_tables) AFM_TRY(launch_dec_tables_t<NKS>(w, B, ws, s));
     int chunks = (N + 511) / 512;                     // 512 points per workgroup: the per-sample tables are staged once per 8 tiles and wave
@@ -616,10 +626,16 @@ int launch_dec_point_p(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, 
     if (cap) chunks = cap;
     else if (chunks > 16) chunks = 16;                // (three workgroups per CU measured slower: the kernel is bound by VALU + f32 MFMA issue, not by latency)
     if (chunks > (N + 15) / 16) chunks = (N + 15) / 16;
-    hipLaunchKernelGGL((dec_point_kernel<NKS, NPROD>), dim3(chunks, B), dim3(64 * RowLess<NKS>::NW), LDS, s, ws.twp, ws.qtab, w.dec_qdd, w.dec_twx, w.dec_c,
-                       w.fold_w2, w.gen_qe, w.fold_c0, N, w.contact_dim, x_t, feat, w.feat_dim, x0_out, ddpm ? ddpm->noise : nullptr,
-                       ddpm ? ddpm->x_next : nullptr, ddpm ? ddpm->c1 : nullptr, ddpm ? ddpm->c2 : nullptr, ddpm ? ddpm->sigma : nullptr,
-                       (ddpm && (w.flags & AFM_CDM_CLIP_X0)) ? 1 : 0);
+    const int upd = ddpm ? cdm_update_bits(w) : 0;
+    if (upd & AFM_UPD_DDIM)
+        hipLaunchKernelGGL((dec_point_kernel<NKS, NPROD, true>), dim3(chunks, B), dim3(64 * RowLess<NKS>::NW), LDS, s, ws.twp, ws.qtab, w.dec_qdd, w.dec_twx, w.dec_c,
+                           w.fold_w2, w.gen_qe, w.fold_c0, N, w.contact_dim, x_t, feat, w.feat_dim, x0_out, ddpm->noise, ddpm->x_next, ddpm->c1, ddpm->c2,
+                           ddpm->sigma, upd);
+    else
+        hipLaunchKernelGGL((dec_point_kernel<NKS, NPROD, false>), dim3(chunks, B), dim3(64 * RowLess<NKS>::NW), LDS, s, ws.twp, ws.qtab, w.dec_qdd, w.dec_twx, w.dec_c,
+                           w.fold_w2, w.gen_qe, w.fold_c0, N, w.contact_dim, x_t, feat, w.feat_dim, x0_out, ddpm ? ddpm->noise : nullptr,
+                           ddpm ? ddpm->x_next : nullptr, ddpm ? ddpm->c1 : nullptr, ddpm ? ddpm->c2 : nullptr, ddpm ? ddpm->sigma : nullptr,
+                           (ddpm && (w.flags & AFM_CDM_CLIP_X0)) ? 1 : 0);
     AFM_CHECK_LAUNCH();
     return 0;
 }

@@ -462,6 +462,7 @@ __global__ __launch_bounds__(256, 2) void dec_attend_mfma_kernel(const float* __
 // out[n, j] = (((p0 + p1) + p2) + p3) + s1[n, j] + (E[n, j] + q[j] . x_t[n]) + c0[j] from the row-dot partials of the fc1 GEMM, optional DDPM
 // update IN PLACE.  Every output channel needs the point's whole contact row (through q), so a block owns WHOLE rows (256 / cd of
 // them per trip, one thread per element) and all its reads of x_t happen before a barrier, its writes after.
+template <bool DDIM>       // DDIM: c1 -> {a, b, c, d} records, sigma -> s, `clip` carries the AFM_UPD_* bits (as dec_point_kernel)
 __global__ __launch_bounds__(256) void cdm_output_kernel(const float* __restrict__ rdot, int ngrp, const float* __restrict__ s1,
                                                          const float* __restrict__ qe, const float* __restrict__ fq,
                                                          const float* __restrict__ c0, int cd, int64_t rows, int rows_per_sample,
@@ -492,11 +493,16 @@ __global__ __launch_bounds__(256) void cdm_output_kernel(const float* __restrict
         }
         __syncthreads();                                                            // every read of this block's rows of x_t is done
         if (ok) {
-            if (clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);               // clip_denoised
+            if (clip & AFM_UPD_CLIP) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);               // clip_denoised
             if (x0_out) x0_out[i] = v;
             if (x_next) {
                 const int b = (int)(r / rows_per_sample);
-                x_next[i] = (c1[b] * v + c2[b] * xj) + sigma[b] * noise[i];
+                if (DDIM) {
+                    const float4 rr = reinterpret_cast<const float4*>(c1)[b];
+                    x_next[i] = (clip & AFM_UPD_NO_NOISE) ? ddim_update(v, xj, rr) : ddim_update(v, xj, rr, sigma[b], noise[i]);
+                } else {
+                    x_next[i] = (c1[b] * v + c2[b] * xj) + sigma[b] * noise[i];
+                }
             }
         }
     }
@@ -547,9 +553,14 @@ int launch_cdm_output(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, c
     AfmProf prof(AFM_PROF_CDM, 0.0, s);
     const int M = B * N, cd = w.contact_dim, rpb = 256 / cd;
     int64_t g = ((int64_t)M + rpb - 1) / rpb; if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(cdm_output_kernel, dim3((unsigned)g), dim3(256), 0, s, ws.rdot, w.dkv / 64, ws.s1, ws.qe, w.fold_q, w.fold_c0, cd, (int64_t)M, N, x0_out, x_t,
-                       ddpm ? ddpm->noise : nullptr, ddpm ? ddpm->x_next : nullptr, ddpm ? ddpm->c1 : nullptr, ddpm ? ddpm->c2 : nullptr,
-                       ddpm ? ddpm->sigma : nullptr, (ddpm && (w.flags & AFM_CDM_CLIP_X0)) ? 1 : 0);
+    const int upd = ddpm ? cdm_update_bits(w) : 0;
+    if (upd & AFM_UPD_DDIM)
+        hipLaunchKernelGGL(cdm_output_kernel<true>, dim3((unsigned)g), dim3(256), 0, s, ws.rdot, w.dkv / 64, ws.s1, ws.qe, w.fold_q, w.fold_c0, cd, (int64_t)M, N, x0_out,
+                           x_t, ddpm->noise, ddpm->x_next, ddpm->c1, ddpm->c2, ddpm->sigma, upd);
+    else
+        hipLaunchKernelGGL(cdm_output_kernel<false>, dim3((unsigned)g), dim3(256), 0, s, ws.rdot, w.dkv / 64, ws.s1, ws.qe, w.fold_q, w.fold_c0, cd, (int64_t)M, N, x0_out, x_t,
+                           ddpm ? ddpm->noise : nullptr, ddpm ? ddpm->x_next : nullptr, ddpm ? ddpm->c1 : nullptr, ddpm ? ddpm->c2 : nullptr,
+                           ddpm ? ddpm->sigma : nullptr, (ddpm && (w.flags & AFM_CDM_CLIP_X0)) ? 1 : 0);
     AFM_CHECK_LAUNCH();
     return 0;
 }

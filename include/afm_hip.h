@@ -232,6 +232,24 @@ int afm_ddpm_step(const float* x0, const float* x_t, const float* noise, float* 
                   int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0,
                   int32_t step, void* stream);
 
+/* ---- DDIM (v7-additive: new struct and entry points, no existing struct changed).
+ * afm_ddim_rows: five float32 rows of the DDIM update, each indexed like the afm_ddpm_step coefficients (afm_ddim_step: per sample [B];
+ * the loops below: per timestep index [T], like d_c1).  The host builds them in float32 in the reference's order of operations
+ * (ddim_sample, gaussian_diffusion.py:538-586) from the float32-cast tables:
+ *   a = sqrt_recip_alphas_cumprod, b = sqrt_recipm1_alphas_cumprod, c = sqrt(alphas_cumprod_prev),
+ *   d = sqrt(1 - alphas_cumprod_prev - sigma^2), sigma = (t != 0) * eta * sqrt((1 - abar_prev) / (1 - abar)) * sqrt(1 - abar / abar_prev)
+ * ddim_reverse_sample uses c = sqrt(alphas_cumprod_next), d = sqrt(1 - alphas_cumprod_next) and sigma = NULL (no noise term). */
+typedef struct {
+    const float* a; const float* b; const float* c; const float* d; const float* sigma;
+} afm_ddim_rows;
+
+/* afm_ddim_step: eps = (a[b] * x_t - x0) / b[b];  x_next = (x0 * c[b] + d[b] * eps) + sigma[b] * noise, every operation rounded on its own
+ * (no fma contraction, IEEE division): bit-identical to the reference's float32 expression given the same inputs.  rows: host struct of
+ * per-sample [B] device arrays.  rows->sigma == NULL: no noise term (x_next = the mean; `noise` is not read).  noise == NULL: Philox noise
+ * keyed like afm_ddpm_step.  x_next may alias x_t. */
+int afm_ddim_step(const float* x0, const float* x_t, const float* noise, float* x_next, const afm_ddim_rows* rows,
+                  int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0, int32_t step, void* stream);
+
 /* afm_clamp: x <- min(max(x, lo), hi) in place (NaN propagates, as torch.clamp): `process_xstart` with clip_denoised=True on the
  * step-by-step path (gaussian_diffusion.py:289-294).  ABI v6. */
 int afm_clamp(float* x, int64_t n, float lo, float hi, void* stream);
@@ -599,6 +617,19 @@ int afm_cmdm_sample_loop_range(const afm_cmdm_weights* w, float* x, const float*
                                int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
 
+/* DDIM form of the native loop (v7-additive; ddim_sample_loop, gaussian_diffusion.py:626-710): the arguments of
+ * afm_cmdm_sample_loop_range with the three DDPM rows replaced by `rows`, a host struct of DDIM rows per timestep index (device arrays,
+ * the slice's rows in ascending order, as d_c1).  rows->sigma == NULL: no noise term (eta = 0) and no noise is generated or read.
+ * The launches of a step are the DDPM loop's plus ONE elementwise launch per sub-batch: motion_layer stores pred_xstart and that launch
+ * applies the DDIM update (clip_denoised included) and writes the next step's K-padded copy of x (the DDPM update stays fused in the GEMM
+ * epilogue, whose registers a second update form would grow).  Sub-batch streams and AFM_CMDM_PAIR_LAUNCH are bit-identical to one stream.  sched_scratch >= afm_ddim_sched_scratch_bytes(n_steps, B). */
+int64_t afm_ddim_sched_scratch_bytes(int32_t n_steps, int32_t B);
+int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                             const uint8_t* frame_mask, const float* step_noise,
+                             const int64_t* d_timestep_map, const afm_ddim_rows* rows, int32_t n_steps, int32_t first_step, uint64_t seed,
+                             int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                             int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
@@ -723,6 +754,14 @@ int afm_cdm_sample_loop_range(const afm_cdm_weights* w, float* x, float* feat, c
                               const float* d_c2, const float* d_sigma, int32_t n_steps, int32_t first_step, uint64_t seed,
                               int64_t sample_index0, int32_t B, int32_t N, void* sched_scratch, void* workspace,
                               int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream);
+/* DDIM form of the loop slice (v7-additive), as afm_cmdm_ddim_loop_range: the DDIM update is fused into the last kernel of the row-less
+ * (dec_point) and folded-rows (output kernel) forms; the layer-by-layer form adds one elementwise launch behind its contact_layer GEMM.
+ * sched_scratch >= afm_ddim_sched_scratch_bytes(n_steps, B). */
+int afm_cdm_ddim_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
+                            const float* text_cu, const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows,
+                            int32_t n_steps, int32_t first_step, uint64_t seed,
+                            int64_t sample_index0, int32_t B, int32_t N, void* sched_scratch, void* workspace,
+                            int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream);
 
 /* Latent-token precomputation (step-invariant, off the per-step path): for n input rows `in` [n, text_dim] (which = 0,
  * language_adapter) or [n, time_dim] (which = 1, time_embedding_adapter) compute the latent's enc_q0 row
