@@ -493,6 +493,8 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
     // slots a partial round leaves, and what counts is the work per matrix instruction (the loop runs at the board's power limit): with the
     // six-product arithmetic, 128 x 128 on EVERY GEMM with N >= 512 measured 588-590 against 568-574 steps/s at 16 + 16 samples in the same
     // calls, but 853 against 995 at 8 + 8 and 1168 against 1470 at 4 + 4 (profiles/r06_tile_rule.md) - so: sub-batches of >= 4096 rows only.
+    // Round 7: the same 128 x 128 tile on 512 threads (tile code 14: two of the tile's waves per SIMD) - 611-612 against 580 steps/s for code 5
+    // in one call (profiles/r07_gemm128_timeline.md); code 5 stays reachable through the override.
     // Tile shapes of one arithmetic are bit-identical; a caller's explicit AFM_CMDM_WIDE_TILE code wins.
     afm_cmdm_weights wl = *w;
     wl.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE);                  // library-private: never taken from a caller
@@ -500,7 +502,7 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
     if (nsub >= 2 && ((wl.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < nsub; ++s) big = big && (int64_t)count[s] * T >= 4096;
-        if (big) wl.flags |= 5 << AFM_CMDM_WIDE_TILE_SHIFT;
+        if (big) wl.flags |= 14 << AFM_CMDM_WIDE_TILE_SHIFT;
     }
     w = &wl;
     for (int s = 0; s < nsub; ++s)        // ticket words of the fused LayerNorm: zero once, every launch leaves them zero

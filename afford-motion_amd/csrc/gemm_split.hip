@@ -103,13 +103,19 @@ __global__ __launch_bounds__(256, AFM_WALK_LB) void gemm_f32_split_bf16_walk(con
     }
 }
 
-// ---- WIDE (round 6; MEASUREMENT, tile code 13): a 256 x 128 tile on 512 threads = 4 x 2 waves, each wave the 64 x 64 wave tile of the 128 x 128 program.
-// Per matrix instruction the workgroup stages 25 % fewer operand rows (384 rows for 32 wave-tiles against 256 for 16: global loads, split VALU, LDS stores);
-// the price is one workgroup per CU (139 KB of LDS: the staged accumulators outgrow the operand stages) whose eight waves meet at every K16 barrier.
+// ---- 512-THREAD TILES: 4 x 2 waves per workgroup, the same tile program text (AFM_BODY_WM = 4).
+//   tile code 13 (round 6; MEASUREMENT): a 256 x 128 tile, each wave the 64 x 64 wave tile of the 128 x 128 program.  Per matrix instruction the
+//   workgroup stages 25 % fewer operand rows (384 rows for 32 wave-tiles against 256 for 16: global loads, split VALU, LDS stores); the price is one
+//   workgroup per CU (139 KB of LDS: the staged accumulators outgrow the operand stages) whose eight waves meet at every K16 barrier.
+//   tile code 14 (round 7): the 128 x 128 tile, each wave a 32 x 64 wave tile (TM = 1, TN = 2: 12 MFMAs and one A + one W staging item per wave
+//   and K16).  The workgroup's operand work per matrix instruction, its LDS (two stages, 74 KB) and so its two workgroups per CU are those of
+//   tile code 5; what changes is that each SIMD now holds two of the tile's waves, so one wave's split VALU, LDS traffic and barrier wait can
+//   issue while the other's MFMAs run.  Two workgroups per CU are four waves per SIMD: <= 128 VGPRs (the second launch bound is hipcc's
+//   amdgpu_waves_per_eu, i.e. waves per SIMD, not workgroups per CU; build_hip.py rejects spills).
 // Same tile program text, same products in the same order: bit-identical to every other tile shape.
-template <int NPROD>
-__global__ __launch_bounds__(512, 1) void gemm_f32_split_bf16_wide(const afm_linear_args p, int nbm, int nbn) {
-    constexpr int BM = 256, BN = 128, BKS = 16, KG = 1, RING = 2, GSEG = 1;
+template <int BM, int NPROD>
+__global__ __launch_bounds__(512, BM == 128 ? 4 : 1) void gemm_f32_split_bf16_wide(const afm_linear_args p, int nbm, int nbn) {
+    constexpr int BN = 128, BKS = 16, KG = 1, RING = 2, GSEG = 1;
 #define AFM_BODY_WM 4
 #define AFM_WG ((int)blockIdx.x)
 #define AFM_TIDX threadIdx.x
@@ -121,22 +127,35 @@ __global__ __launch_bounds__(512, 1) void gemm_f32_split_bf16_wide(const afm_lin
 #undef AFM_BODY_WM
 }
 
-template <int NPROD>
+// Every element offset the 128 x 128 / 512-thread tile program forms (row of A through its row map, or of W, times the row stride, plus K) is
+// addressed as a 32-bit BYTE offset from the operand's base (SOFF in gemm_split_body.inc): true when the largest such offset stays below 4 GiB.
+inline bool split_offsets_fit_u32(const afm_linear_args& a) {
+    const int64_t arow = a.a_grp ? (int64_t)((a.M - 1) / a.a_grp) * a.a_stride + a.a_off + (a.a_grp - 1) + (a.a_skip > 0 ? a.a_skip : 0) : (int64_t)a.M - 1;
+    const int64_t amax = (arow * a.lda + a.K) * 4, wmax = ((int64_t)(a.N - 1) * a.ldw + a.K) * 4;
+    return a.a_stride >= 0 && a.a_off >= 0 && arow >= 0 && amax < (int64_t(1) << 32) && wmax < (int64_t(1) << 32);
+}
+
+template <int BM, int BN, int BKS, int NPROD, int KG = 1, int RING = 2, int GSEG = 1>
+int launch_split(const afm_linear_args& a, hipStream_t s);
+
+template <int BM, int NPROD>
 int launch_split_wide(const afm_linear_args& a, hipStream_t s) {
-    constexpr int BM = 256, BN = 128, BKS = 16;
+    static_assert(BM == 128 || BM == 256, "512-thread tiles: 128 x 128 or 256 x 128");
+    constexpr int BN = 128, BKS = 16;
     constexpr int STAGE = 3 * (BM + BN) * (BKS * 2 + 16);
     constexpr int OPER = 2 * STAGE > BM * (BN + 4) * 4 ? 2 * STAGE : BM * (BN + 4) * 4;
     constexpr int LDS_BYTES = OPER + 2 * BM * 2 * 4;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS of one CU");
-    if (a.ln_out) return AFM_E_UNSUPPORTED;                 // (the fused LayerNorm's tickets are per 128-row block at most)
+    static_assert(LDS_BYTES <= (BM == 128 ? 80 : 160) * 1024, "LDS of one CU (the 128 x 128 form: two workgroups per CU)");
+    if (BM > 128 && a.ln_out) return AFM_E_UNSUPPORTED;                 // (the fused LayerNorm's tickets are per 128-row block at most)
+    if (BM == 128 && !split_offsets_fit_u32(a)) return launch_split<128, 128, 16, NPROD, 1, 2, 1>(a, s);      // the 256-thread form: same tile, same bits
     if (a.aux_dst && a.aux_rows > (int64_t)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)) return AFM_E_UNSUPPORTED;      // one rider row per workgroup
     static const int attr = []() {
-        return (int)hipFuncSetAttribute((const void*)gemm_f32_split_bf16_wide<NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        return (int)hipFuncSetAttribute((const void*)gemm_f32_split_bf16_wide<BM, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     }();
     if (attr != 0) return attr;
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
     AfmProf prof(AFM_PROF_GEMM_SPLIT128, 2.0 * a.M * a.N * a.K, s);
-    hipLaunchKernelGGL((gemm_f32_split_bf16_wide<NPROD>), dim3(nbm * nbn), dim3(512), LDS_BYTES, s, a, nbm, nbn);
+    hipLaunchKernelGGL((gemm_f32_split_bf16_wide<BM, NPROD>), dim3(nbm * nbn), dim3(512), LDS_BYTES, s, a, nbm, nbn);
     AFM_CHECK_LAUNCH();
     return 0;
 }
@@ -190,7 +209,7 @@ int launch_split_pair(const afm_linear_args& a0, const afm_linear_args& a1, hipS
     return 0;
 }
 
-template <int BM, int BN, int BKS, int NPROD, int KG = 1, int RING = 2, int GSEG = 1>
+template <int BM, int BN, int BKS, int NPROD, int KG, int RING, int GSEG>
 int launch_split(const afm_linear_args& a, hipStream_t s) {
     constexpr int STAGE = 3 * (BM + BN) * (BKS * 2 + 16);
     static_assert(RING * STAGE >= BM * (BN + 4) * 4, "the staged accumulators fit group 0's operand stages");
@@ -274,7 +293,8 @@ int dispatch_split(const afm_linear_args& a, hipStream_t s) {
     // steps/s in one call).  Round 3 also measured 128x64 / 64x128 tiles in the CMDM loop: 431 / 437 steps/s against 449 for this rule.
     const bool full_rounds = tiles128 * 10 >= rounds * resident * 9 && a.K > KSEG;      // >= 90 % of the resident slots used over all rounds
     if (tile == 12) return launch_split_walk<NPROD>(a, s);          // measurement: force the walking form
-    if (tile == 13) return launch_split_wide<NPROD>(a, s);          // measurement: the 256 x 128 tile on 512 threads
+    if (tile == 13) return launch_split_wide<256, NPROD>(a, s);     // measurement: the 256 x 128 tile on 512 threads
+    if (tile == 14) return launch_split_wide<128, NPROD>(a, s);     // the 128 x 128 tile on 512 threads (two waves per SIMD)
     if (tile == 3 || (tile != 5 && !full_rounds)) {
         const int64_t tiles64w = (int64_t)((a.M + 63) / 64) * ((a.N + 63) / 64);
         if (tile != 3 && AFM_WALK_GRID > 0 && tiles64w > AFM_WALK_GRID) return launch_split_walk<NPROD>(a, s);      // (A/B builds only: AFM_WALK_GRID is 0 in the library)

@@ -56,14 +56,25 @@
     // TCP_TOTAL_CACHE_ACCESSES 11.7 M -> 6.0 M per out_proj launch, 2-3 % faster), and every thread carries the same mix of A and W
     // work.  16 consecutive lanes (the unit ds_write_b64 is serviced in) take the four quarters of four rows of equal parity inside a
     // block of 8 rows: with rows 48 B apart those are four disjoint 32-byte windows of the 128-byte bank row.
+    // (The 512-thread 128 x 128 tile - one A and one W item per thread, it = tid for both - maps a 16-lane group exactly as the 256-thread
+    // tiles do, so the same row permutation stays conflict-free.)
+    // SOFF (the 512-thread 128 x 128 tile, tile code 14): the items are addressed as 32-bit byte offsets from the uniform bases p.A / p.W
+    // (saddr + voffset loads) instead of 64-bit pointers - two VGPRs less, what it takes to fit four waves per SIMD without spilling a
+    // register set in the K loop.  Its launcher checks that every offset fits.  Its K loop also keeps ONE register set instead of two: an
+    // item's next tile (kt + 2) is requested as soon as the item's split of tile kt + 1 is done (A after the sixth MFMA, W after the twelfth),
+    // about half a K-tile of lead instead of one - the other waves of the SIMD (four per SIMD) cover the rest.  Eight VGPRs: with both sets
+    // hipcc parks one set in scratch behind a vmcnt(0) wait per load.
+    constexpr bool SOFF = GT == 512 && BM == 128;
     const RowMap amap{p.a_grp, p.a_stride, p.a_off, p.a_skip_after, p.a_skip};
     const float* src[NI];
+    uint32_t soff[NI];
     int dst[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int it = tid + GT * (i < NA ? i : i - NA), q = it & 3, v = it >> 2, row = (v & ~7) + ((v & 3) << 1) + ((v >> 2) & 1);
-        src[i] = (i < NA ? p.A + amap(min(bm * BM + row, p.M - 1)) * p.lda
-                         : p.W + (int64_t)min(bn * BN + row, p.N - 1) * p.ldw) + q * 4 + grp * (GSEG * KSEG);
+        const int64_t eoff = (i < NA ? amap(min(bm * BM + row, p.M - 1)) * p.lda : (int64_t)min(bn * BN + row, p.N - 1) * p.ldw) + q * 4 + grp * (GSEG * KSEG);
+        src[i] = (i < NA ? p.A : p.W) + eoff;
+        soff[i] = (uint32_t)eoff * 4u;
         dst[i] = ((i < NA ? 0 : BM) + row) * ROWB + q * 8;
     }
 
@@ -88,6 +99,11 @@
     constexpr int SEGT = KSEG / BKS;                  // K-tiles per segment
     f32x16 tot[TM][TN];                               // sum of the finished segments (KG == 1 with K > KSEG only)
     bool have_tot = false;
+    auto load_item = [&](auto SETC, int i, int kt) {  // (SOFF: one item of one register set)
+        constexpr int S = decltype(SETC)::value;
+        const int k = min(kt, nk - 1) * BKS;
+        g[S][i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const unsigned char*>(i < NA ? p.A : p.W) + (soff[i] + (uint32_t)k * 4u));
+    };
     auto load = [&](auto SETC, int kt) {
         constexpr int S = decltype(SETC)::value;
         const int k = min(kt, nk - 1) * BKS;          // past the end: re-load the last tile (never consumed)
@@ -100,7 +116,8 @@
         for (int i = 0; i < NI; ++i) {
             if ((AFM_ABLATE & 32) && i >= NA && kt >= 2) { asm volatile("" : "+v"(g[S][i])); continue; }
             if ((AFM_ABLATE & 64) && i < NA && kt >= 2) { asm volatile("" : "+v"(g[S][i])); continue; }
-            g[S][i] = *reinterpret_cast<const f32x4*>(src[i] + k);
+            if constexpr (SOFF) g[S][i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const unsigned char*>(i < NA ? p.A : p.W) + (soff[i] + (uint32_t)k * 4u));
+            else g[S][i] = *reinterpret_cast<const f32x4*>(src[i] + k);
         }
     };
     using Set0 = std::integral_constant<int, 0>;
@@ -135,6 +152,10 @@
         split_set(Set1{}, 1);
     } else {
         split_set(Set0{}, 0);
+        if constexpr (SOFF) {                         // the K loop's single register set holds tile 1 (set 1 is dead from here on)
+#pragma unroll
+            for (int i = 0; i < NI; ++i) g[0][i] = g[1][i];
+        }
     }
     __syncthreads();
 #ifdef AFM_TIMELINE
@@ -152,7 +173,8 @@
     uint4 af[TM][3], bf[TN][3];
     auto body = [&](auto CURC, int kt) {          // K-tile kt with kt & 1 == cur: register set cur is free, set cur ^ 1 holds tile kt + 1
         constexpr int cur = decltype(CURC)::value;
-        load(CURC, kt + 2);
+        constexpr int RS = SOFF ? 0 : cur ^ 1;        // register set holding tile kt + 1
+        if constexpr (!SOFF) load(CURC, kt + 2);
         const unsigned char* base = lds + cur * STAGE;
         unsigned char* wbase = lds + (cur ^ 1) * STAGE;
         float r0[NI * 2], r1[NI * 2];
@@ -163,8 +185,8 @@
             if ((AFM_ABLATE & 32) && i >= NA && kt >= 1) return;          // W items: nothing to split, nothing to store
             if ((AFM_ABLATE & 64) && i < NA && kt >= 1) return;           // A items likewise (the floor of "A already in LDS": out_proj fused behind attention)
             if (lvl == 0) {
-                r0[u] = g[cur ^ 1][i][2 * c];
-                r1[u] = g[cur ^ 1][i][2 * c + 1];
+                r0[u] = g[RS][i][2 * c];
+                r1[u] = g[RS][i][2 * c + 1];
             }
             const uint32_t pk = (AFM_ABLATE & 2) ? __float_as_uint(lvl == 1 ? r1[u] : r0[u]) : cvt_pk_bf16(r0[u], r1[u]);
             sp[u][lvl] = pk;
@@ -205,6 +227,11 @@
 #pragma unroll
                     for (int t = 0; t < NPIECE; ++t)
                         if (t >= piece && t < (m * NPIECE) / NMFMA) do_piece(t);
+                    if constexpr (SOFF) {             // an item whose split just finished: request its tile kt + 2 into the same registers
+#pragma unroll
+                        for (int i = 0; i < NI; ++i)
+                            if (piece < (i + 1) * 6 && (m * NPIECE) / NMFMA >= (i + 1) * 6) load_item(Set0{}, i, kt + 2);
+                    }
                     piece = (m * NPIECE) / NMFMA;
                     __builtin_amdgcn_sched_barrier(0);
                 }
