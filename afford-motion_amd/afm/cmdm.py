@@ -10,6 +10,8 @@ What differs from the reference (results identical, SURVEY.md section 7 "hard pa
   * TimestepEmbedder(t) depends on t only -> a [1000, d] table built once per weight version.
   * sampling can run as one native loop (afm_cmdm_sample_loop) with the DDPM update fused into
     the last GEMM's epilogue.
+  * classifier-free guided sampling (`GuidedCMDM`, at the end of this file): both branches and
+    the guided update inside the same native loops.
 """
 from __future__ import annotations
 
@@ -539,12 +541,13 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
     # ------------------------------------------------------------------ native sampling loop
     def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                        clip_denoised=False, ddim_eta: Optional[float] = None):
+                        clip_denoised=False, ddim_eta: Optional[float] = None, _guidance=None):
         """Whole p_sample_loop on the device: x holds x_T on entry, returns the final sample.  ``clip_denoised``: pred_xstart clamped to
         [-1, 1] inside the fused DDPM update (the reference's default argument; test.py passes False).  ``ddim_eta`` not None: the
         ddim_sample_loop with that eta instead (afm_cmdm_ddim_loop_range: the same launches, the DDIM update in the same epilogue).  ``progress`` (test.py:85 passes
         True) splits the chain into ~50 native slices (afm_cmdm_sample_loop_range) and advances a tqdm bar between them; the
-        result is bit-identical to the unsliced loop."""
+        result is bit-identical to the unsliced loop.  ``_guidance``: GuidedCMDM's (afm_cfg_args, branch streams?) (the guided loops; not a
+        caller's argument)."""
         if any(k in model_kwargs for k in COND_SWITCHES):
             raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
                                       "p_sample_loop samples them step by step (p_sample_loop_progressive)")
@@ -567,10 +570,24 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             nsub = max(1, min(int(self.loop_streams), B // 8 if self.loop_streams_auto else B))
             self._side_streams = ffi.stream_pool(x.device, nsub)          # process-wide pool (hardware queues are few: ffi.stream_pool)
             handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in self._side_streams[:nsub]])
-            nbytes = lib.afm_cmdm_loop_workspace_bytes(C.byref(w), B, L, nsub)
+            # _guidance (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)
+            cfg, branch_streams = _guidance if _guidance is not None else (None, False)
+            if branch_streams:
+                # the unconditioned branch of every sub-batch on a pool stream of its own: 2 * nsub <= 4 streams (the process has four hardware
+                # queues; more streams than queues serialise, ffi.stream_pool)
+                nsub = min(nsub, 2)
+                pool = ffi.stream_pool(x.device, 2 * nsub)
+                self._side_streams = pool
+                handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[:nsub]])
+                branch_handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[nsub:2 * nsub]])
+                cfg.branch_streams = C.cast(branch_handles, C.POINTER(C.c_void_p))
+            if cfg is None:
+                nbytes = lib.afm_cmdm_loop_workspace_bytes(C.byref(w), B, L, nsub)
+            else:
+                nbytes = lib.afm_cmdm_cfg_loop_workspace_bytes(C.byref(w), B, L, nsub, C.byref(cfg))
             if nbytes < 0:
                 ffi.check(int(nbytes), "afm_cmdm_loop_workspace_bytes")
-            key = ("loop", B, L, nsub, str(x.device))
+            key = ("loop" if cfg is None else ("cfg_loop", cfg.drop_text, cfg.drop_pc, cfg.flags), B, L, nsub, str(x.device))
             if key not in self._ws:
                 self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
             ws = self._ws[key]
@@ -581,6 +598,18 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def enqueue(j0, j1):        # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo, cnt = n - j1, j1 - j0
+                nz = None if step_noise is None else step_noise[j0:j1].data_ptr()
+                tail = (cnt, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
+                        nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream)
+                if cfg is not None and ddim is not None:
+                    ffi.check(lib.afm_cmdm_cfg_ddim_loop_range(C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), nz, tab.timestep_map[lo:].data_ptr(),
+                                                               C.byref(ddim.rows(lo)), C.byref(cfg), *tail), "afm_cmdm_cfg_ddim_loop_range")
+                    return
+                if cfg is not None:
+                    ffi.check(lib.afm_cmdm_cfg_sample_loop_range(C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), nz, tab.timestep_map[lo:].data_ptr(),
+                                                                 tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr(),
+                                                                 C.byref(cfg), *tail), "afm_cmdm_cfg_sample_loop_range")
+                    return
                 if ddim is not None:
                     ffi.check(lib.afm_cmdm_ddim_loop_range(
                         C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm),
@@ -609,5 +638,110 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             else:
                 ffi.run_slices(slices, enqueue, progress, x.device)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim)
+            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim, _guidance)
         return x
+
+
+# ---------------------------------------------------------------------- classifier-free guidance
+GUIDANCE_DROPS = ("text", "pc")
+
+
+class GuidedCMDM(nn.Module):
+    """Classifier-free guided denoiser over a CMDM:  x0_guided = x0_u + scale[b] * (x0_c - x0_u)  (float32, this association).
+
+    The reference trains every motion task with condition dropout (datasets/transforms.py:46-92 sets c_text_mask / c_pc_mask with
+    probability 0.1; cmdm.py:142-166 turns them into key-padding masks), so a CMDM checkpoint is a guidance model.  ``x0_c`` is the ordinary
+    forward, ``x0_u`` the forward of the same x_t, t, x_mask with the conditions named in ``drop`` masked as training masks them.
+    ``scale``: a float or a [B] tensor.  Calling the wrapper is a denoiser (``wrapper(x, t, **kwargs) -> x0_guided``): both fused forwards and
+    the combine kernel in one native call (afm_cmdm_cfg_forward), so ``diffusion.p_sample_loop(wrapper, shape, model_kwargs=...)`` and
+    ``ddim_sample_loop`` work unchanged; it exposes ``afm_native_loop``, so they run the guided native loop under the conditions of the
+    unguided one.  With every condition dropped the unconditioned branch runs in its compact form (no condition rows at all);
+    ``force_masked=True`` (measurement) keeps the masked full-length form.  ``branch_streams=True`` (measurement; bit-identical) queues
+    the unconditioned branch of a native loop on a second stream per sub-batch instead of behind the conditioned branch."""
+
+    def __init__(self, model: "CMDM", scale, drop=GUIDANCE_DROPS, *, force_masked: bool = False, branch_streams: bool = False):
+        super().__init__()
+        if not isinstance(model, CMDM):
+            raise TypeError(f"GuidedCMDM wraps a CMDM, not {type(model).__name__} (the CDM never reads the condition switches)")
+        if model.arch == "trans_dec":
+            raise NotImplementedError("classifier-free guidance is built for arch='trans_enc' only")
+        if not model.mask_motion:
+            raise ValueError("classifier-free guidance needs mask_motion=True: with mask_motion=False the condition masks are no-ops (cmdm.py:165)")
+        drop = (drop,) if isinstance(drop, str) else tuple(drop)
+        if not drop:
+            raise ValueError("GuidedCMDM: `drop` is empty - name at least one of " + repr(GUIDANCE_DROPS))
+        unknown = [d for d in drop if d not in GUIDANCE_DROPS]
+        if unknown:
+            raise ValueError(f"GuidedCMDM: unknown condition(s) {unknown} in `drop`; valid names: {GUIDANCE_DROPS}")
+        if isinstance(scale, torch.Tensor):
+            if scale.dim() > 1 or not scale.is_floating_point():
+                raise ValueError(f"GuidedCMDM: `scale` must be a float or a floating [B] tensor, got shape {tuple(scale.shape)} {scale.dtype}")
+            scale = scale.detach().clone().float().reshape(-1)
+        else:
+            scale = float(scale)
+        self.model, self.scale, self.drop, self.force_masked = model, scale, tuple(sorted(set(drop))), bool(force_masked)
+        self.branch_streams = bool(branch_streams)
+        self._scales: Dict[tuple, torch.Tensor] = {}
+
+    @property
+    def motion_dim(self) -> int:
+        return self.model.motion_dim
+
+    def _cfg(self, B: int, device) -> ffi.CfgArgs:
+        """afm_cfg_args for a batch of B on `device`; the [B] scale tensor is built once per (B, device) and kept on the wrapper."""
+        key = (B, str(device))
+        if key not in self._scales:
+            if isinstance(self.scale, torch.Tensor):
+                if self.scale.numel() != B:
+                    raise ValueError(f"GuidedCMDM: `scale` holds {self.scale.numel()} values for a batch of {B}")
+                self._scales[key] = self.scale.to(device).contiguous()
+            else:
+                self._scales[key] = torch.full((B,), self.scale, dtype=torch.float32, device=device)
+        return ffi.CfgArgs(self._scales[key].data_ptr(), int("text" in self.drop), int("pc" in self.drop),
+                           ffi.CFG_FORCE_MASKED if self.force_masked else 0)
+
+    @staticmethod
+    def _no_switches(kwargs) -> None:
+        used = [k for k in COND_SWITCHES if k in kwargs]
+        if used:
+            raise ValueError(f"GuidedCMDM sets the condition masks itself: remove {used} from model_kwargs")
+
+    def branches(self, x, timesteps, **kwargs):
+        """(x0_c, x0_u, x0_guided) of one guided evaluation - afm_cmdm_cfg_forward: the conditioned branch is CMDM.forward's launches."""
+        self._no_switches(kwargs)
+        m = self.model
+        if m.training:
+            raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
+        ffi.require_gpu(x)
+        with torch.no_grad():
+            lib = ffi.load()
+            x = ffi.f32c(x)
+            B, L, _ = x.shape
+            cfg = self._cfg(B, x.device)
+            w = m._weights()
+            cond = m.condition_tokens(**kwargs)
+            fm = kwargs["x_mask"].to(device=x.device, dtype=torch.uint8).contiguous()
+            out = torch.empty((3,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+            key = ("cfg", B, L, str(x.device))
+            if key not in m._ws:
+                nbytes = lib.afm_cmdm_cfg_workspace_bytes(C.byref(w), B, L)
+                if nbytes < 0:
+                    ffi.check(int(nbytes), "afm_cmdm_cfg_workspace_bytes")
+                m._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
+            ws = m._ws[key]
+            t = timesteps.to(device=x.device, dtype=torch.int64).contiguous()
+            ffi.check(lib.afm_cmdm_cfg_forward(C.byref(w), x.data_ptr(), t.data_ptr(), cond.data_ptr(), fm.data_ptr(), C.byref(cfg),
+                                               out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), B, L, ws.data_ptr(), ws.numel(),
+                                               ffi.stream_of(x)), "afm_cmdm_cfg_forward")
+        return out[0], out[1], out[2]
+
+    def forward(self, x, timesteps, **kwargs):
+        return self.branches(x, timesteps, **kwargs)[2]
+
+    def afm_native_loop(self, diffusion, x, model_kwargs, **kw):
+        """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range): CMDM.afm_native_loop's arguments."""
+        self._no_switches(model_kwargs)
+        if self.model.training:
+            raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
+        ffi.require_gpu(x)
+        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(self._cfg(x.shape[0], x.device), self.branch_streams), **kw)

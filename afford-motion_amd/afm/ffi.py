@@ -151,6 +151,20 @@ class DdimRows(C.Structure):
     _fields_ = [("a", c_f32p), ("b", c_f32p), ("c", c_f32p), ("d", c_f32p), ("sigma", c_f32p)]
 
 
+class CfgArgs(C.Structure):
+    """afm_cfg_args (v7-additive): classifier-free guidance of the CMDM - device [B] scales, the dropped conditions, AFM_CFG_* flags."""
+    _fields_ = [("scale", c_f32p), ("drop_text", i32), ("drop_pc", i32), ("flags", i32), ("branch_streams", C.POINTER(C.c_void_p))]
+
+
+class CfgStepArgs(C.Structure):
+    """afm_cfg_step_args (v7-additive): one guided sampling update from the two branches' pred_xstart."""
+    _fields_ = [("x0_c", c_f32p), ("x0_u", c_f32p), ("scale", c_f32p), ("x_t", c_f32p), ("noise", c_f32p), ("x_next", c_f32p),
+                ("c1", c_f32p), ("c2", c_f32p), ("sigma", c_f32p), ("ddim", C.POINTER(DdimRows)), ("clip", i32), ("B", i32),
+                ("per_sample", i64), ("seed", u64), ("sample_index0", i64), ("step", i32)]
+
+
+CFG_FORCE_MASKED = 0x1
+
 EXPORTS = {
     # name: (restype, argtypes)
     "afm_version": (C.c_int, []),
@@ -172,6 +186,18 @@ EXPORTS = {
                                            i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_cdm_ddim_loop_range": (C.c_int, [C.POINTER(CdmWeights), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
                                           i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_cfg_combine": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, i32, i64, C.c_void_p]),
+    "afm_cfg_step": (C.c_int, [C.POINTER(CfgStepArgs), C.c_void_p]),
+    "afm_cmdm_cfg_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32]),
+    "afm_cmdm_cfg_forward": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(CfgArgs), c_f32p, c_f32p, c_f32p,
+                                       i32, i32, C.c_void_p, i64, C.c_void_p]),
+    "afm_cmdm_cfg_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs)]),
+    "afm_cmdm_cfg_sample_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p,
+                                                 C.POINTER(CfgArgs), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                                 C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_cmdm_cfg_ddim_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                               C.POINTER(CfgArgs), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                               C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

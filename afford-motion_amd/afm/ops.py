@@ -329,6 +329,52 @@ def ddim_step(x0: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor]
     return out
 
 
+def cfg_combine(x0_c: torch.Tensor, x0_u: torch.Tensor, scale: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Classifier-free guidance of an x_start prediction (afm_cfg_combine): x0_u + scale[b] * (x0_c - x0_u), float32, every operation
+    rounded on its own; scale [B]."""
+    lib = ffi.load()
+    ffi.require_gpu(x0_c, x0_u, scale)
+    x0_c, x0_u, scale = ffi.f32c(x0_c), ffi.f32c(x0_u), ffi.f32c(scale)
+    B = x0_c.shape[0]
+    if scale.numel() != B or x0_u.shape != x0_c.shape:
+        raise ValueError(f"cfg_combine: scale must hold one value per sample ({B}), got {tuple(scale.shape)}; branches {tuple(x0_c.shape)} / {tuple(x0_u.shape)}")
+    out = torch.empty_like(x0_c) if out is None else out
+    ffi.check(lib.afm_cfg_combine(x0_c.data_ptr(), x0_u.data_ptr(), scale.data_ptr(), out.data_ptr(), B, x0_c.numel() // max(B, 1),
+                                  ffi.stream_of(x0_c)), "afm_cfg_combine")
+    return out
+
+
+def cfg_step(x0_c: torch.Tensor, x0_u: torch.Tensor, scale: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor], *,
+             ddpm=None, ddim=None, clip: bool = False, seed: int = 0, sample_index0: int = 0, step: int = 0,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One guided sampling update (afm_cfg_step): cfg_combine, the clamp to [-1, 1] if ``clip``, then the ddpm_step expression with
+    ``ddpm`` = (c1, c2, sigma) per-sample rows or the ddim_step expression with ``ddim`` = (a, b, c, d, sigma | None).  noise None: Philox."""
+    if (ddpm is None) == (ddim is None):
+        raise ValueError("cfg_step: exactly one of ddpm= / ddim= rows")
+    lib = ffi.load()
+    ffi.require_gpu(x0_c, x0_u, x_t)
+    x0_c, x0_u, scale, x_t = ffi.f32c(x0_c), ffi.f32c(x0_u), ffi.f32c(scale), ffi.f32c(x_t)
+    B = x0_c.shape[0]
+    if scale.numel() != B:
+        raise ValueError(f"cfg_step: scale must hold one value per sample ({B}), got {tuple(scale.shape)}")
+    out = torch.empty_like(x0_c) if out is None else out
+    a = ffi.CfgStepArgs()
+    a.x0_c, a.x0_u, a.scale, a.x_t, a.x_next = x0_c.data_ptr(), x0_u.data_ptr(), scale.data_ptr(), x_t.data_ptr(), out.data_ptr()
+    nz = None if noise is None else ffi.f32c(noise)
+    a.noise = ffi.ptr(nz)
+    keep = [ffi.f32c(r) for r in (ddpm if ddpm is not None else ddim) if r is not None]
+    rows = None
+    if ddpm is not None:
+        a.c1, a.c2, a.sigma = (r.data_ptr() for r in keep)
+    else:
+        rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], keep[4].data_ptr() if len(keep) > 4 else None)
+        a.ddim = C.pointer(rows)
+    a.clip, a.B, a.per_sample = int(bool(clip)), B, x0_c.numel() // max(B, 1)
+    a.seed, a.sample_index0, a.step = seed & (2**64 - 1), sample_index0, step
+    ffi.check(lib.afm_cfg_step(C.byref(a), ffi.stream_of(x0_c)), "afm_cfg_step")
+    return out
+
+
 def randn(shape, device, *, seed: int, sample_index0: int = 0, step: int = 0) -> torch.Tensor:
     """Counter-based N(0,1) noise keyed by (seed, global sample index, step, element)."""
     lib = ffi.load()

@@ -21,13 +21,15 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
                      contact_std: float = 1.0, seed: int = 0, sample_index0: int = 0,
                      adm_noise: Optional[Dict[str, torch.Tensor]] = None,
                      amdm_noise: Optional[Dict[str, torch.Tensor]] = None, sampler: str = "ddpm",
-                     eta: float = 0.0) -> Dict[str, torch.Tensor]:
+                     eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc")) -> Dict[str, torch.Tensor]:
     """text_feat [B, text_dim], xyz [B, N, 3] (B = scenes x k_sample, already flattened) ->
     {"contact": [B, N, J] ADM sample, "cond": [B, N, J] AMDM condition, "motion": [B, frames, D]}.
 
     ``*_noise`` = optional {"x_T": ..., "steps": [T, ...]} explicit noise (parity tests); otherwise Philox
     keyed by (seed, sample_index0 + b), stage 2 uses seed + 1.  ``sampler`` = "ddpm" (p_sample_loop) or "ddim" (ddim_sample_loop with
-    ``eta``) for both stages; DDIM runs the spaced process of each diffusion (e.g. timestep_respacing="ddim50")."""
+    ``eta``) for both stages; DDIM runs the spaced process of each diffusion (e.g. timestep_respacing="ddim50").
+    ``guidance_scale`` (a float or a [B] tensor; None = unguided): classifier-free guidance of the MOTION stage, dropping the conditions named
+    in ``guidance_drop`` (afm.cmdm.GuidedCMDM; the CDM of the first stage never reads the condition switches)."""
     if sampler not in ("ddpm", "ddim"):
         raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
 
@@ -47,6 +49,9 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
         x_mask = torch.zeros(B, frames, dtype=torch.bool, device=dev)
     amdm_kw = dict(c_text_feat=text_feat, c_pc_xyz=xyz, c_pc_contact=cond, x_mask=x_mask)
     mn = amdm_noise or {}
+    if guidance_scale is not None:
+        from .cmdm import GuidedCMDM
+        amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
     motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
                   model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
     return {"contact": contact, "cond": cond, "motion": motion}

@@ -10,6 +10,8 @@
 //   buffer, +bias +positional rows) -> n_layers x { in_proj GEMM, flash MHA, out_proj GEMM(+bias
 //   +residual), LN, FFN1 GEMM(+bias+GELU), FFN2 GEMM(+bias+residual), LN } -> motion_layer GEMM
 //   (gather motion tokens, +bias, fused DDPM posterior update).
+// Classifier-free guided steps (afm_cmdm_cfg_*): this sequence twice - the conditioned branch, then the unconditioned one (struct Branch) -
+// with both motion_layer GEMMs storing pred_xstart, and one elementwise launch for the guided update (afm_cfg_update_rows).
 #include "common.h"
 
 extern "C" int afm_linear(const afm_linear_args*, void*);
@@ -18,6 +20,10 @@ __attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, 
                                                                int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
 __attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tmap, const afm_ddim_rows* rows, int32_t n_steps, int32_t B, int64_t* t_all,
                                                                float4* rec_all, float* s_all, void* stream);
+// elementwise.hip: the guided update of a guided loop's step from the two branches' pred_xstart (see afm_cfg_update_rows)
+__attribute__((visibility("hidden"))) int afm_cfg_update_rows(const float* x0_c, const float* x0_u, const float* scale, float* x, const float* noise,
+                                                              const float4* rec, const float* c1, const float* c2, const float* s, int32_t B,
+                                                              int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
 extern "C" int afm_linear_pair(const afm_linear_args*, const afm_linear_args*, void*);
 extern "C" int afm_mha_fwd_grouped(const float*, const uint8_t*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, void*);
 extern "C" int afm_mha_fwd_rows(const float*, const uint8_t*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, void*);
@@ -103,6 +109,17 @@ __global__ __launch_bounds__(128) void prologue_kernel(float* __restrict__ seq0,
     }
 }
 
+// The unconditioned branch of a guided evaluation (classifier-free guidance).  Compact form: the weight pack's copy has n_cond = 0 (no
+// condition rows exist) and the motion tokens keep the positional rows of the full layout, pos_off = 1 + n_cond of the real pack.  Masked
+// form: the full layout, with the key mask also set on the dropped condition tokens (token 1 = text, tokens 2 .. n_cond = contact groups).
+struct Branch { int pos_off, mask_text, mask_pc; };
+
+// grid (B): the condition tokens' entries of the key mask the prologue has just written (0 there): 1 on the dropped ones
+__global__ __launch_bounds__(64) void cond_keymask_kernel(uint8_t* __restrict__ keymask, int T, int n_cond, int mask_text, int mask_pc) {
+    for (int i = threadIdx.x; i < n_cond; i += blockDim.x)
+        keymask[(int64_t)blockIdx.x * T + 1 + i] = (uint8_t)(i == 0 ? mask_text : mask_pc);
+}
+
 // per-step per-sample schedule rows for the whole loop: row j <-> spaced timestep i = n_steps-1-j
 __global__ void expand_schedule_kernel(const int64_t* __restrict__ tmap, const float* __restrict__ c1,
                                        const float* __restrict__ c2, const float* __restrict__ sg, int n_steps, int B,
@@ -163,10 +180,13 @@ inline int run_mha(const afm_cmdm_weights& w, const float* qkv, const uint8_t* k
 
 int forward_impl(const afm_cmdm_weights& w, const float* x_t, const int64_t* t, const float* cond,
                  const uint8_t* frame_mask, float* x0_out, const afm_ddpm_args* ddpm, int B, int L, const Workspace& ws,
-                 bool copy_cond, hipStream_t s, Recorder* rec = nullptr) {
+                 bool copy_cond, hipStream_t s, Recorder* rec = nullptr, const Branch* br = nullptr) {
     const int d = w.d, T = 1 + w.n_cond + L;
     const int M = B * T;
     uint8_t* keymask = frame_mask ? ws.keymask : nullptr;
+    const int pos_off = br ? br->pos_off : 1 + w.n_cond;          // positional row of the first motion token
+    const bool mask_cond = br && (br->mask_text || br->mask_pc);
+    if (mask_cond && (!keymask || w.n_cond < 1 || rec)) return AFM_E_BADARG;
 
     // Steps after the first of a native loop need no prologue launch: the condition tokens and the key mask persist in the workspace, the
     // K-padded copy of x_t was written by the previous step's DDPM update (ddpm_out2), and the time tokens ride on the motion adapter's
@@ -178,6 +198,10 @@ int forward_impl(const afm_cmdm_weights& w, const float* x_t, const int64_t* t, 
         hipLaunchKernelGGL(prologue_kernel, dim3(B, 1 + w.n_cond), dim3(128), 0, s, ws.seq0, w.time_table, w.pos_table, t, cond,
                            frame_mask, keymask, T, L, w.n_cond, d, w.n_timesteps, copy_cond ? 1 : 0, x_t, ws.xpad, w.motion_dim, w.motion_adapter_kpad);
         AFM_CHECK_LAUNCH();
+        if (mask_cond) {                              // (with the riders the mask of the loop's first step persists in the workspace)
+            hipLaunchKernelGGL(cond_keymask_kernel, dim3(B), dim3(64), 0, s, keymask, T, w.n_cond, br->mask_text, br->mask_pc);
+            AFM_CHECK_LAUNCH();
+        }
     }
 
     {   // motion_adapter (cmdm.py:159) scattered to token rows 1+n_cond.., + positional encoding (cmdm.py:162)
@@ -186,7 +210,7 @@ int forward_impl(const afm_cmdm_weights& w, const float* x_t, const int64_t* t, 
         a.A = kp ? ws.xpad : x_t; a.lda = kp ? kp : w.motion_dim; a.W = w.motion_adapter_w; a.ldw = a.lda;
         a.C = ws.seq0; a.ldc = d; a.M = B * L; a.N = d; a.K = (int)a.lda;
         a.bias = w.motion_adapter_b;
-        a.rowtab = w.pos_table + (int64_t)(1 + w.n_cond) * d; a.rowtab_period = L;
+        a.rowtab = w.pos_table + (int64_t)pos_off * d; a.rowtab_period = L;
         a.c_grp = L; a.c_stride = T; a.c_off = 1 + w.n_cond;
         if (riders) {       // time token of every sample: seq0[b T] = time_table[t_b] + pos[0]
             a.aux_src = w.time_table; a.aux_idx = t; a.aux_idx_max = w.n_timesteps; a.aux_add = w.pos_table; a.aux_dst = ws.seq0;
@@ -337,6 +361,19 @@ int validate(const afm_cmdm_weights* w, int B, int L) {
     return 0;
 }
 
+// the unconditioned branch of a guided evaluation: its copy of the pack and its Branch (compact when every condition is dropped)
+int uncond_setup(const afm_cmdm_weights& w, const afm_cfg_args* cfg, const uint8_t* frame_mask, afm_cmdm_weights* wu, Branch* br) {
+    if (!cfg || !cfg->scale || (!cfg->drop_text && !cfg->drop_pc) || w.n_cond < 1) return AFM_E_BADARG;
+    const bool compact = cfg->drop_text && cfg->drop_pc && !(cfg->flags & AFM_CFG_FORCE_MASKED);
+    if (!compact && !frame_mask) return AFM_E_BADARG;          // (the key mask is built from the frame mask)
+    *wu = w;
+    br->pos_off = 1 + w.n_cond;
+    br->mask_text = compact ? 0 : (cfg->drop_text ? 1 : 0);
+    br->mask_pc = compact ? 0 : (cfg->drop_pc ? 1 : 0);
+    if (compact) wu->n_cond = 0;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int afm_version(void) { return AFM_ABI_VERSION; }
@@ -363,6 +400,32 @@ extern "C" int afm_cmdm_forward(const afm_cmdm_weights* w, const float* x_t, con
     if ((w->flags & AFM_CMDM_FUSED_LN) &&           // ticket words of the opt-in fused LayerNorm only
         hipMemsetAsync(ws.lncnt, 0, (size_t)(((int64_t)B * (1 + w->n_cond + L) + 31) / 32) * 4, (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
     return forward_impl(*w, x_t, t, cond_tokens, frame_mask, x0_out, ddpm, B, L, ws, true, (hipStream_t)stream);
+}
+
+extern "C" int64_t afm_cmdm_cfg_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L) {
+    if (validate(w, B, L) != 0) return AFM_E_BADARG;
+    return carve(*w, B, L, nullptr).bytes + 2 * align256((int64_t)B * L * w->motion_dim * 4);
+}
+
+// Both branches in turn on one workspace (the unconditioned branch's layout is never larger), then the combine launch.
+extern "C" int afm_cmdm_cfg_forward(const afm_cmdm_weights* w, const float* x_t, const int64_t* t, const float* cond_tokens,
+                                    const uint8_t* frame_mask, const afm_cfg_args* cfg, float* x0_c, float* x0_u, float* x0_guided,
+                                    int32_t B, int32_t L, void* workspace, int64_t workspace_bytes, void* stream) {
+    AFM_TRY(validate(w, B, L));
+    if (!x_t || !t || !cond_tokens || !workspace || !x0_guided) return AFM_E_BADARG;
+    afm_cmdm_weights wc = *w, wu;
+    wc.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE | AFM_CMDM_FUSED_LN);         // (library-private bits; the opt-in fused LayerNorm is not built here)
+    Branch br;
+    AFM_TRY(uncond_setup(wc, cfg, frame_mask, &wu, &br));
+    if (B == 0) return 0;
+    const Workspace ws = carve(wc, B, L, workspace), wsu = carve(wu, B, L, workspace);
+    const int64_t xb = align256((int64_t)B * L * w->motion_dim * 4);
+    if (ws.bytes + 2 * xb > workspace_bytes || wsu.bytes > ws.bytes) return AFM_E_WORKSPACE;
+    if (!x0_c) x0_c = (float*)((char*)workspace + ws.bytes);
+    if (!x0_u) x0_u = (float*)((char*)workspace + ws.bytes + xb);
+    AFM_TRY(forward_impl(wc, x_t, t, cond_tokens, frame_mask, x0_c, nullptr, B, L, ws, true, (hipStream_t)stream));
+    AFM_TRY(forward_impl(wu, x_t, t, wu.n_cond ? cond_tokens : nullptr, frame_mask, x0_u, nullptr, B, L, wsu, true, (hipStream_t)stream, nullptr, &br));
+    return afm_cfg_combine(x0_c, x0_u, cfg->scale, x0_guided, B, (int64_t)L * w->motion_dim, stream);
 }
 
 extern "C" int64_t afm_cmdm_sched_scratch_bytes(int32_t n_steps, int32_t B) {
@@ -392,6 +455,22 @@ extern "C" int64_t afm_cmdm_loop_workspace_bytes(const afm_cmdm_weights* w, int3
         int st, cnt;
         sub_range(B, n, s, &st, &cnt);
         total += carve(*w, cnt, L, nullptr, NOISE_STEPS).bytes;
+    }
+    return total;
+}
+
+extern "C" int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg) {
+    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
+    afm_cmdm_weights wu;
+    Branch br;
+    const uint8_t some_mask = 0;                              // (sizes do not depend on the frame mask)
+    if (uncond_setup(*w, cfg, &some_mask, &wu, &br) != 0) return AFM_E_BADARG;
+    const int n = n_streams > 1 ? (n_streams < B ? n_streams : (B > 0 ? B : 1)) : 1;
+    int64_t total = 0;
+    for (int s = 0; s < n; ++s) {
+        int st, cnt;
+        sub_range(B, n, s, &st, &cnt);
+        total += carve(*w, cnt, L, nullptr, NOISE_STEPS).bytes + carve(wu, cnt, L, nullptr, 2).bytes;
     }
     return total;
 }
@@ -434,8 +513,15 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
                             const float* step_noise, const int64_t* d_timestep_map, const float* d_c1,
                             const float* d_c2, const float* d_sigma, const afm_ddim_rows* ddim, int32_t n_steps, int32_t first_step, uint64_t seed,
                             int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
-                            int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
+                            int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream,
+                            const afm_cfg_args* cfg = nullptr) {
     AFM_TRY(validate(w, B, L));
+    // Guided loop (cfg != NULL): per sub-batch and step the conditioned branch (this loop's step as it is, pred_xstart stored the DDIM
+    // loop's way, for DDPM too), the unconditioned branch on a workspace of its own behind it on the same stream, and ONE update launch
+    // (afm_cfg_update_rows).  Both branches read the same x / K-padded copy; only the update writes them.
+    afm_cmdm_weights wu;
+    Branch br = {};
+    if (cfg) AFM_TRY(uncond_setup(*w, cfg, frame_mask, &wu, &br));
     const bool rows_ok = ddim ? (ddim->a && ddim->b && ddim->c && ddim->d) : (d_c1 && d_c2 && d_sigma);
     if (!x || (w->n_cond > 0 && !cond_tokens) || !d_timestep_map || !rows_ok || n_steps <= 0 ||
         !sched_scratch || !workspace || n_streams < 0 || (n_streams > 1 && !side_streams))
@@ -466,7 +552,7 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
     AFM_CHECK_LAUNCH();
 
     // carve one workspace per sub-batch
-    Workspace ws[16];
+    Workspace ws[16], wsu[16];
     int start[16], count[16];
     hipStream_t st[16];
     {
@@ -476,13 +562,32 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
             sub_range(B, nsub, s, &start[s], &count[s]);
             ws[s] = carve(*w, count[s], L, base + off, NOISE_STEPS);
             off += ws[s].bytes;
+            if (cfg) {                                    // (2 "noise steps": a pred_xstart region of its own, as little noise space as the layout allows)
+                wsu[s] = carve(wu, count[s], L, base + off, 2);
+                off += wsu[s].bytes;
+                wsu[s].xpad = ws[s].xpad;                 // one K-padded copy of x_t serves both branches
+            }
             st[s] = nsub > 1 ? (hipStream_t)side_streams[s] : s0;
         }
         if (off > workspace_bytes) return AFM_E_WORKSPACE;
     }
+    // guided loop with branch streams: the unconditioned branch of sub-batch s runs on bst[s]; two events per sub-batch order it against the
+    // guided update, the only writer of x and of its K-padded copy (ev_x[s]: x is ready, ev_u[s]: the branch's pred_xstart is ready)
+    hipStream_t bst[16] = {};
+    hipEvent_t ev_x[16] = {}, ev_u[16] = {};
+    const bool branch_streams = cfg && cfg->branch_streams;
+    auto drop_branch_events = [&]() { for (int s = 0; s < 16; ++s) { if (ev_x[s]) (void)hipEventDestroy(ev_x[s]); if (ev_u[s]) (void)hipEventDestroy(ev_u[s]); } };
+    for (int s = 0; branch_streams && s < nsub; ++s) {
+        bst[s] = (hipStream_t)cfg->branch_streams[s];
+        if (hipEventCreateWithFlags(&ev_x[s], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_u[s], hipEventDisableTiming) != hipSuccess) {
+            const int rc_ev = (int)hipGetLastError();
+            drop_branch_events();
+            return rc_ev;
+        }
+    }
     hipEvent_t fork = nullptr;
     if (nsub > 1) {      // side streams start after everything already queued on `stream` (inputs, schedule rows)
-        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
+        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) { drop_branch_events(); return (int)hipGetLastError(); }
         (void)hipEventRecord(fork, s0);
         for (int s = 0; s < nsub; ++s) (void)hipStreamWaitEvent(st[s], fork, 0);
     }
@@ -499,12 +604,14 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
     afm_cmdm_weights wl = *w;
     wl.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE);                  // library-private: never taken from a caller
     if (ddim) wl.flags |= AFM_PRIV_DDIM | (noise_term ? 0 : AFM_PRIV_NO_NOISE);
+    if (cfg) wl.flags = (wl.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
     if (nsub >= 2 && ((wl.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < nsub; ++s) big = big && (int64_t)count[s] * T >= 4096;
         if (big) wl.flags |= 14 << AFM_CMDM_WIDE_TILE_SHIFT;
     }
     w = &wl;
+    if (cfg) { const int nc_u = wu.n_cond; wu = wl; wu.n_cond = nc_u; }       // the loop's flags (tile code, private bits) on the branch's pack
     for (int s = 0; s < nsub; ++s)        // ticket words of the fused LayerNorm: zero once, every launch leaves them zero
         if (count[s] > 0 && (w->flags & AFM_CMDM_FUSED_LN) && hipMemsetAsync(ws[s].lncnt, 0, (size_t)(((int64_t)count[s] * T + 31) / 32) * 4, st[s]) != hipSuccess) return (int)hipGetLastError();
     const int64_t row = (int64_t)L * w->motion_dim;
@@ -554,7 +661,28 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
                               cond_tokens ? cond_tokens + (int64_t)start[s] * w->n_cond * w->d : nullptr,
                               frame_mask ? frame_mask + (int64_t)start[s] * L : nullptr, nullptr, &dd, count[s], L, ws[s], j == 0,
                               st[s], rec_step ? &recs[s] : nullptr);
-            if (rc == 0 && ddim && !rec_step) rc = ddim_update(s, dd);
+            if (rc == 0 && cfg) {
+                // step 0: the branch's prologue rewrites the shared K-padded copy (same values), so it starts behind the conditioned branch;
+                // later steps: behind the previous update, next to the conditioned branch
+                const hipStream_t su = branch_streams ? bst[s] : st[s];
+                if (branch_streams) {
+                    if (j == 0) (void)hipEventRecord(ev_x[s], st[s]);
+                    (void)hipStreamWaitEvent(su, ev_x[s], 0);
+                }
+                rc = forward_impl(wu, x + (int64_t)start[s] * row, t_all + (int64_t)j * B + start[s],
+                                  wu.n_cond && cond_tokens ? cond_tokens + (int64_t)start[s] * w->n_cond * w->d : nullptr,
+                                  frame_mask ? frame_mask + (int64_t)start[s] * L : nullptr, nullptr, &dd, count[s], L, wsu[s], j == 0,
+                                  su, nullptr, &br);
+                if (branch_streams) {
+                    (void)hipEventRecord(ev_u[s], su);
+                    (void)hipStreamWaitEvent(st[s], ev_u[s], 0);
+                }
+                if (rc == 0)
+                    rc = afm_cfg_update_rows(ws[s].x0, wsu[s].x0, cfg->scale + start[s], x + (int64_t)start[s] * row, noise_term ? dd.noise : nullptr,
+                                             ddim ? (const float4*)dd.c1 : nullptr, dd.c1, dd.c2, noise_term ? dd.sigma : nullptr, count[s], row,
+                                             w->motion_dim, (w->flags & AFM_CMDM_CLIP_X0) ? 1 : 0, ws[s].xpad, w->motion_adapter_kpad, st[s]);
+                if (branch_streams) (void)hipEventRecord(ev_x[s], st[s]);       // x and its padded copy of the next step
+            } else if (rc == 0 && ddim && !rec_step) rc = ddim_update(s, dd);
         }
         if (rec_step && rc == 0) rc = issue_paired(recs[0], recs[1], st[0], st[1], pev, NEV);
         for (int s = 0; ddim && rec_step && rc == 0 && s < nsub; ++s) {      // (the paired schedule: behind the sub-batch's recorded launches)
@@ -568,6 +696,7 @@ static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* co
         delete[] recs;
         for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(pev[i]);
     }
+    drop_branch_events();      // (every branch stream's last work is joined to its sub-batch's stream before the last update)
     if (nsub > 1) {      // join: `stream` continues only after every sub-batch loop has finished
         for (int s = 0; s < nsub; ++s) {
             hipEvent_t done;
@@ -610,4 +739,25 @@ extern "C" int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, con
     if (first_step < 0 || !rows) return AFM_E_BADARG;
     return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step,
                             seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
+}
+
+extern "C" int afm_cmdm_cfg_sample_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                                              const uint8_t* frame_mask, const float* step_noise, const int64_t* d_timestep_map,
+                                              const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg, int32_t n_steps,
+                                              int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                              void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
+                                              void* const* side_streams, void* stream) {
+    if (first_step < 0 || !cfg) return AFM_E_BADARG;
+    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step,
+                            seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg);
+}
+
+extern "C" int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                                            const uint8_t* frame_mask, const float* step_noise, const int64_t* d_timestep_map,
+                                            const afm_ddim_rows* rows, const afm_cfg_args* cfg, int32_t n_steps, int32_t first_step, uint64_t seed,
+                                            int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes,
+                                            int32_t n_streams, void* const* side_streams, void* stream) {
+    if (first_step < 0 || !rows || !cfg) return AFM_E_BADARG;
+    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step,
+                            seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg);
 }

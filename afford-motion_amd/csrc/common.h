@@ -311,6 +311,25 @@ __device__ __forceinline__ float ddim_update(float x0, float xt, const float4& r
     return mean + sn;
 }
 
+// ---- classifier-free guidance of an x_start-predicting denoiser, one element: x0_u + s * (x0_c - x0_u) in float32, this association,
+// every operation rounded on its own (what the float32 torch expression gives).  s = the guidance scale of the element's sample.  Every
+// guided site (afm_cfg_combine, the guided update of afm_cfg_step and of the guided native loops) calls this one helper.
+__device__ __forceinline__ float cfg_combine(float x0_c, float x0_u, float s) {
+#pragma clang fp contract(off)
+    const float df = x0_c - x0_u;
+    const float m = s * df;
+    return x0_u + m;
+}
+// the ancestral (DDPM) update of one element as ddpm_step_kernel and the GEMM epilogue write it: (c1 * x0 + c2 * x_t) + sigma * noise
+__device__ __forceinline__ float ddpm_update(float x0, float xt, float c1, float c2, float sg, float nz) {
+#pragma clang fp contract(off)
+    const float m1 = c1 * x0;
+    const float m2 = c2 * xt;
+    const float mean = m1 + m2;
+    const float sn = sg * nz;
+    return mean + sn;
+}
+
 // Selectors of the sampling update of the CDM's fused output kernels (their `clip` argument; library-private):
 //   AFM_UPD_DDIM      c1 -> float4 {a, b, c, d} per sample (16-byte aligned), sigma -> s per sample, c2 unused
 //   AFM_UPD_NO_NOISE  DDIM without the noise term (eta = 0 rows: s == 0 everywhere; noise is never read)

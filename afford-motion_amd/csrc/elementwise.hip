@@ -354,3 +354,119 @@ extern "C" int afm_randn(float* out, int32_t B, int64_t per_sample, uint64_t see
     AFM_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- classifier-free guidance (afm_cfg_combine, afm_cfg_step, the guided native loops of cmdm.hip)
+namespace {
+
+// x0_guided = cfg_combine(x0_c, x0_u, scale[b]) per element
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ x0c, const float* __restrict__ x0u, const float* __restrict__ scale,
+                                                          float* __restrict__ out, int64_t per_sample) {
+    const int b = blockIdx.y;
+    const float s = scale[b];
+    const int64_t base = (int64_t)b * per_sample;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * blockDim.x)
+        out[base + i] = cfg_combine(x0c[base + i], x0u[base + i], s);
+}
+
+// The guided sampling update, the guided sibling of ddim_update_rows_kernel: x0 = cfg_combine(x0_c, x0_u, scale[b]), clamped if asked,
+// then ddpm_update (ddim == 0; rows c1 / c2 / sg per sample) or ddim_update (rows rec, or ra..rd, per sample; sg == NULL: no noise term).
+// xn may alias xt (one thread reads then writes an element).  noise == NULL with a noise term: Philox keyed like ddpm_step_kernel (quad q).
+// xpad: x_next also into rows of ldpad floats (the next motion-adapter GEMM's K-padded A rows; columns >= cols stay zero).
+struct CfgUpd {
+    const float *x0c, *x0u, *scale, *xt, *noise;
+    float* xn;
+    const float *c1, *c2, *sg;
+    const float *ra, *rb, *rc, *rd;
+    const float4* rec;
+    float* xpad;
+    int64_t ldpad, per_sample, sample0;
+    uint64_t seed;
+    int cols, clip, ddim, step;
+};
+
+__global__ __launch_bounds__(256) void cfg_update_kernel(const CfgUpd p) {
+    const int b = blockIdx.y;
+    const float s = p.scale[b];
+    const float sg = p.sg ? p.sg[b] : 0.f;
+    float4 r = make_float4(0.f, 1.f, 0.f, 0.f);
+    float c1 = 0.f, c2 = 0.f;
+    if (p.ddim) r = p.rec ? p.rec[b] : make_float4(p.ra[b], p.rb[b], p.rc[b], p.rd[b]);
+    else { c1 = p.c1[b]; c2 = p.c2[b]; }
+    const int64_t base = (int64_t)b * p.per_sample;
+    const int64_t nquad = (p.per_sample + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (p.sg && !p.noise) philox_normal4(p.seed, p.sample0 + b, p.step, (uint64_t)q, z);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = q * 4 + e;
+            if (i < p.per_sample) {
+                const int64_t g = base + i;
+                float v = cfg_combine(p.x0c[g], p.x0u[g], s);
+                if (p.clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised on x0_guided (NaN passes through, as torch.clamp)
+                const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
+                const float vt = p.xt[g];
+                float xn;
+                if (p.ddim) xn = p.sg ? ddim_update(v, vt, r, sg, nz) : ddim_update(v, vt, r);
+                else xn = ddpm_update(v, vt, c1, c2, sg, nz);
+                p.xn[g] = xn;
+                if (p.xpad) {
+                    const int64_t row = g / p.cols;
+                    p.xpad[row * p.ldpad + (g - row * p.cols)] = xn;
+                }
+            }
+        }
+    }
+}
+
+int launch_cfg_update(const CfgUpd& p, int32_t B, void* stream) {
+    if (!p.x0c || !p.x0u || !p.scale || !p.xt || !p.xn || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
+    if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && p.rd)) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
+    if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
+    if (B == 0) return 0;
+    const int64_t nquad = (p.per_sample + 3) >> 2;
+    unsigned gx = (unsigned)((nquad + 255) / 256);
+    if (gx > 1024) gx = 1024;
+    AfmProf prof(AFM_PROF_MISC, 5.0 * B * p.per_sample, (hipStream_t)stream);
+    hipLaunchKernelGGL(cfg_update_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, p);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int afm_cfg_combine(const float* x0_c, const float* x0_u, const float* scale, float* out, int32_t B, int64_t per_sample, void* stream) {
+    if (!x0_c || !x0_u || !scale || !out || B < 0 || per_sample <= 0) return AFM_E_BADARG;
+    if (B == 0) return 0;
+    unsigned gx = (unsigned)((per_sample + 255) / 256);
+    if (gx > 1024) gx = 1024;
+    AfmProf prof(AFM_PROF_MISC, 3.0 * B * per_sample, (hipStream_t)stream);
+    hipLaunchKernelGGL(cfg_combine_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0_c, x0_u, scale, out, per_sample);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int afm_cfg_step(const afm_cfg_step_args* a, void* stream) {
+    if (!a) return AFM_E_BADARG;
+    CfgUpd p = {};
+    p.x0c = a->x0_c; p.x0u = a->x0_u; p.scale = a->scale; p.xt = a->x_t; p.noise = a->noise; p.xn = a->x_next;
+    p.per_sample = a->per_sample; p.clip = a->clip ? 1 : 0; p.seed = a->seed; p.sample0 = a->sample_index0; p.step = a->step;
+    if (a->ddim) { p.ddim = 1; p.ra = a->ddim->a; p.rb = a->ddim->b; p.rc = a->ddim->c; p.rd = a->ddim->d; p.sg = a->ddim->sigma; }
+    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    return launch_cfg_update(p, a->B, stream);
+}
+
+// the guided update of a native loop's step (cmdm.hip): x0_c / x0_u [B][per_sample] the two branches' pred_xstart, x [B][per_sample] x_t ->
+// x_next in place, scale [B]; rec != NULL: DDIM records {a, b, c, d} [B] with s [B] (NULL: no noise term), else the DDPM rows c1 / c2 / s [B];
+// rows of `cols` values copied to xpad (row stride ldpad) if given
+__attribute__((visibility("hidden"))) int afm_cfg_update_rows(const float* x0_c, const float* x0_u, const float* scale, float* x, const float* noise,
+                                                              const float4* rec, const float* c1, const float* c2, const float* s, int32_t B,
+                                                              int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream) {
+    if (s && !noise) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside this launch)
+    CfgUpd p = {};
+    p.x0c = x0_c; p.x0u = x0_u; p.scale = scale; p.xt = x; p.xn = x; p.noise = noise; p.per_sample = per_sample; p.clip = clip ? 1 : 0;
+    p.cols = cols; p.xpad = xpad; p.ldpad = ldpad;
+    if (rec) { p.ddim = 1; p.rec = rec; p.sg = s; }
+    else { p.c1 = c1; p.c2 = c2; p.sg = s; }
+    return launch_cfg_update(p, B, stream);
+}

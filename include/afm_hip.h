@@ -630,6 +630,71 @@ int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* c
                              int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                              int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
 
+/* ---- Classifier-free guided sampling of the CMDM (v7-additive: new structs and entry points, no existing struct changed).
+ * The reference trains every motion task with condition dropout (datasets/transforms.py:46-92: c_text_mask / c_pc_mask with probability
+ * 0.1; models/cmdm.py:142-166 turns them into key-padding masks when mask_motion is true), so a CMDM checkpoint is a guidance model.
+ * For sample b with scale s[b]:   x0_guided = x0_u + s[b] * (x0_c - x0_u)     (float32, no contraction, this association)
+ * x0_c is the ordinary forward; x0_u the forward of the SAME x_t, t, frame mask with the dropped condition tokens key-masked in every
+ * layer (token 1 = text, tokens 2 .. n_cond = the contact groups).  clip_denoised clamps x0_guided, not the branches.
+ * The unconditioned branch has two forms.  Compact (every condition dropped): a masked key is read by no query in any layer, so the
+ * condition rows need not exist - the branch runs on [time | motion] tokens only (T_u = 1 + L), the motion tokens keeping their
+ * positional rows 1 + n_cond ..; it differs from the masked form only in where the attention's key blocks fall.  Masked (partial drop, or
+ * AFM_CFG_FORCE_MASKED): all T rows, the key mask also covering the dropped tokens.  Both need frame_mask != NULL for a partial drop or
+ * the forced masked form (the key mask is built from it). */
+typedef struct {
+    const float* scale;                    /* device [B]: guidance scale per sample                                      */
+    int32_t drop_text, drop_pc;            /* which conditions the unconditioned branch drops (at least one)             */
+    int32_t flags;                         /* AFM_CFG_* bits                                                             */
+    void* const* branch_streams;           /* guided loops only: one more stream per sub-batch (max(n_streams, 1) handles) for the
+                                            * unconditioned branch, or NULL = both branches on the sub-batch's stream (bit-identical) */
+} afm_cfg_args;
+#define AFM_CFG_FORCE_MASKED 0x1           /* measurement: the masked full-T form although every condition is dropped   */
+
+/* out = x0_u + scale[b] * (x0_c - x0_u), [B][per_sample]; out may alias either input. */
+int afm_cfg_combine(const float* x0_c, const float* x0_u, const float* scale, float* out, int32_t B, int64_t per_sample, void* stream);
+
+/* One guided sampling update from the two branches' pred_xstart: x0 = the combination above, clamped to [-1, 1] if `clip`, then the
+ * afm_ddpm_step expression with the per-sample rows c1 / c2 / sigma (ddim == NULL) or the afm_ddim_step expression with the per-sample
+ * rows *ddim (ddim->sigma == NULL: no noise term).  noise == NULL: Philox keyed like afm_ddpm_step.  x_next may alias x_t.  Bit-identical
+ * to afm_cfg_combine -> afm_clamp -> afm_ddpm_step / afm_ddim_step. */
+typedef struct {
+    const float* x0_c; const float* x0_u; const float* scale;       /* [B][per_sample] x 2, [B] */
+    const float* x_t; const float* noise; float* x_next;            /* [B][per_sample]          */
+    const float* c1; const float* c2; const float* sigma;           /* DDPM rows [B]            */
+    const afm_ddim_rows* ddim;                                      /* or DDIM rows [B]         */
+    int32_t clip; int32_t B; int64_t per_sample;
+    uint64_t seed; int64_t sample_index0; int32_t step;
+} afm_cfg_step_args;
+int afm_cfg_step(const afm_cfg_step_args* args, void* stream);
+
+/* Both branches of one guided evaluation and their combination: x0_c, x0_u, x0_guided [B,L,motion_dim] (x0_c / x0_u may be NULL: the
+ * workspace then holds them).  The conditioned branch is afm_cmdm_forward's launches; the workspace of afm_cmdm_workspace_bytes plus
+ * 2 * B * L * motion_dim floats (afm_cmdm_cfg_workspace_bytes) serves both branches in turn. */
+int64_t afm_cmdm_cfg_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L);
+int afm_cmdm_cfg_forward(const afm_cmdm_weights* w, const float* x_t, const int64_t* t, const float* cond_tokens,
+                         const uint8_t* frame_mask, const afm_cfg_args* cfg, float* x0_c, float* x0_u, float* x0_guided,
+                         int32_t B, int32_t L, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Guided native loops, range form: the arguments of afm_cmdm_sample_loop_range / afm_cmdm_ddim_loop_range plus `cfg` (cfg->scale [B]).
+ * Per sub-batch and step: the conditioned branch (the unguided step's launches, layer-0 cache and riders included), the unconditioned
+ * branch, ONE update launch (the afm_cfg_step expression, in place on x, plus the next step's K-padded copy of x) - all on the
+ * sub-batch's stream, or with cfg->branch_streams the unconditioned branch on a stream of its own between two events per step (after the
+ * previous update, before this one).  Both motion_layer GEMMs store pred_xstart with the plain epilogue, for DDPM too.  AFM_CMDM_PAIR_LAUNCH is ignored
+ * (a guided loop runs unpaired).  workspace >= afm_cmdm_cfg_loop_workspace_bytes; sched_scratch as the unguided loop of the same update. */
+int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg);
+int afm_cmdm_cfg_sample_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                                   const uint8_t* frame_mask, const float* step_noise,
+                                   const int64_t* d_timestep_map, const float* d_c1, const float* d_c2,
+                                   const float* d_sigma, const afm_cfg_args* cfg, int32_t n_steps, int32_t first_step, uint64_t seed,
+                                   int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                                   int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
+int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                                 const uint8_t* frame_mask, const float* step_noise,
+                                 const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_cfg_args* cfg, int32_t n_steps,
+                                 int32_t first_step, uint64_t seed,
+                                 int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                                 int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
