@@ -660,39 +660,21 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if key not in self._ws or self._ws[key].numel() < nbytes:        # (the row-less form's workspace is smaller than the other forms')
                 self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             ws = self._ws[key]
-            if step_noise is not None:
-                step_noise = ffi.f32c(step_noise.to(dev))
-                assert step_noise.shape == (n,) + tuple(x.shape), step_noise.shape
             stream = ffi.stream_of(x)
             if clip_denoised:
                 w.flags |= ffi.CDM_CLIP_X0                   # per call: the next _weights() rewrites the flags
+            entry = "afm_cdm_sample_loop_range" if ddim is None else "afm_cdm_ddim_loop_range"
 
-            def enqueue(j0, j1):        # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
-                lo, cnt = n - j1, j1 - j0
-                if ddim is not None:
-                    ffi.check(lib.afm_cdm_ddim_loop_range(
-                        C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(),
-                        None if step_noise is None else step_noise[j0:j1].data_ptr(), tab.timestep_map[lo:].data_ptr(),
-                        C.byref(ddim.rows(lo)), cnt, j0, seed & (2**64 - 1),
-                        sample_index0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream), "afm_cdm_ddim_loop_range")
-                    return
-                ffi.check(lib.afm_cdm_sample_loop_range(
-                    C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(),
-                    None if step_noise is None else step_noise[j0:j1].data_ptr(), tab.timestep_map[lo:].data_ptr(),
-                    tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr(), cnt, j0, seed & (2**64 - 1),
-                    sample_index0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream), "afm_cdm_sample_loop_range")
+            def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
+                lo = n - j1
+                rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
+                    (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
+                ffi.check(getattr(lib, entry)(
+                    C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(), nz, tab.timestep_map[lo:].data_ptr(),
+                    *rows, j1 - j0, j0, seed & (2**64 - 1), sample_index0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream),
+                    entry)
 
-            slices = ffi.progress_slices(n, progress)
-            if snapshots is not None:
-                slices = ffi.cut_slices(slices, sorted(k for k in snapshots if 0 < k < n))
-
-                def enqueue_snap(j0, j1, _inner=enqueue):
-                    _inner(j0, j1)
-                    if j1 in snapshots:
-                        snapshots[j1] = x.clone()
-                ffi.run_slices(slices, enqueue_snap, progress, dev)
-            else:
-                ffi.run_slices(slices, enqueue, progress, dev)
+            step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu, ddim)
         return x
 

@@ -591,52 +591,21 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if key not in self._ws:
                 self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
             ws = self._ws[key]
-            if step_noise is not None:
-                step_noise = ffi.f32c(step_noise.to(x.device))
-                assert step_noise.shape == (n,) + tuple(x.shape), step_noise.shape
             stream = ffi.stream_of(x)
+            entry = {(True, True): "afm_cmdm_sample_loop_range", (True, False): "afm_cmdm_ddim_loop_range",
+                     (False, True): "afm_cmdm_cfg_sample_loop_range", (False, False): "afm_cmdm_cfg_ddim_loop_range"}[(cfg is None, ddim is None)]
 
-            def enqueue(j0, j1):        # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
-                lo, cnt = n - j1, j1 - j0
-                nz = None if step_noise is None else step_noise[j0:j1].data_ptr()
-                tail = (cnt, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
+            def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
+                lo = n - j1
+                head = (C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), nz, tab.timestep_map[lo:].data_ptr())
+                rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
+                    (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
+                guide = () if cfg is None else (C.byref(cfg),)
+                tail = (j1 - j0, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
                         nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream)
-                if cfg is not None and ddim is not None:
-                    ffi.check(lib.afm_cmdm_cfg_ddim_loop_range(C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), nz, tab.timestep_map[lo:].data_ptr(),
-                                                               C.byref(ddim.rows(lo)), C.byref(cfg), *tail), "afm_cmdm_cfg_ddim_loop_range")
-                    return
-                if cfg is not None:
-                    ffi.check(lib.afm_cmdm_cfg_sample_loop_range(C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), nz, tab.timestep_map[lo:].data_ptr(),
-                                                                 tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr(),
-                                                                 C.byref(cfg), *tail), "afm_cmdm_cfg_sample_loop_range")
-                    return
-                if ddim is not None:
-                    ffi.check(lib.afm_cmdm_ddim_loop_range(
-                        C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm),
-                        None if step_noise is None else step_noise[j0:j1].data_ptr(), tab.timestep_map[lo:].data_ptr(), C.byref(ddim.rows(lo)),
-                        cnt, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
-                        nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream), "afm_cmdm_ddim_loop_range")
-                    return
-                ffi.check(lib.afm_cmdm_sample_loop_range(
-                    C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm),
-                    None if step_noise is None else step_noise[j0:j1].data_ptr(),
-                    tab.timestep_map[lo:].data_ptr(), tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr(),
-                    cnt, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
-                    nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream), "afm_cmdm_sample_loop_range")
+                ffi.check(getattr(lib, entry)(*head, *rows, *guide, *tail), entry)
 
-            slices = ffi.progress_slices(n, progress)
-            if snapshots is not None:
-                # `snapshots` = {executed step count: None}: the chain is cut at those counts and x is cloned there (stream-ordered
-                # device copies, no host synchronisation) - the intermediate states p_sample_loop_progressive would yield
-                slices = ffi.cut_slices(slices, sorted(k for k in snapshots if 0 < k < n))
-
-                def enqueue_snap(j0, j1, _inner=enqueue):
-                    _inner(j0, j1)
-                    if j1 in snapshots:
-                        snapshots[j1] = x.clone()
-                ffi.run_slices(slices, enqueue_snap, progress, x.device)
-            else:
-                ffi.run_slices(slices, enqueue, progress, x.device)
+            step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             # keep scratch alive until the stream has consumed it
             self._last_loop_scratch = (sched, step_noise, cond, fm, ddim, _guidance)
         return x

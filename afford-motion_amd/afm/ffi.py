@@ -445,3 +445,24 @@ def run_slices(ranges, enqueue, progress: bool, device):
     pending[0].synchronize()
     bar.update(pending[1])
     bar.close()
+
+
+def run_native_loop(x, n_steps: int, step_noise, progress: bool, snapshots, call):
+    """The host side shared by the native sampling loops: `call(j0, j1, noise_ptr)` issues the native range call for the executed steps
+    j0..j1-1.  ``step_noise`` ([n_steps, *x.shape] or None) is brought to x's device as contiguous float32 and returned - the caller keeps
+    it alive until the stream has consumed it.  ``progress`` slices the chain for a tqdm bar.  ``snapshots`` = {executed step count: None}:
+    the chain is cut at those counts and x is cloned there (stream-ordered device copies, no host synchronisation) - the intermediate
+    states p_sample_loop_progressive would yield.  Chained slices are bit-identical to the whole loop."""
+    if step_noise is not None:
+        step_noise = f32c(step_noise.to(x.device))
+        assert step_noise.shape == (n_steps,) + tuple(x.shape), step_noise.shape
+    slices = progress_slices(n_steps, progress)
+    if snapshots is not None:
+        slices = cut_slices(slices, sorted(k for k in snapshots if 0 < k < n_steps))
+
+    def enqueue(j0, j1):
+        call(j0, j1, None if step_noise is None else step_noise[j0:j1].data_ptr())
+        if snapshots is not None and j1 in snapshots:
+            snapshots[j1] = x.clone()
+    run_slices(slices, enqueue, progress, x.device)
+    return step_noise

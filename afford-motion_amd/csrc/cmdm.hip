@@ -12,14 +12,13 @@
 //   (gather motion tokens, +bias, fused DDPM posterior update).
 // Classifier-free guided steps (afm_cmdm_cfg_*): this sequence twice - the conditioned branch, then the unconditioned one (struct Branch) -
 // with both motion_layer GEMMs storing pred_xstart, and one elementwise launch for the guided update (afm_cfg_update_rows).
-#include "common.h"
+#include <memory>
+
+#include "sample_loop.h"
+
+using namespace afm_loop;
 
 extern "C" int afm_linear(const afm_linear_args*, void*);
-// elementwise.hip: the DDIM update of a native loop's step from the stored pred_xstart (see afm_ddim_update_rows)
-__attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, float* x, const float* noise, const float4* rec, const float* s, int32_t B,
-                                                               int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
-__attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tmap, const afm_ddim_rows* rows, int32_t n_steps, int32_t B, int64_t* t_all,
-                                                               float4* rec_all, float* s_all, void* stream);
 // elementwise.hip: the guided update of a guided loop's step from the two branches' pred_xstart (see afm_cfg_update_rows)
 __attribute__((visibility("hidden"))) int afm_cfg_update_rows(const float* x0_c, const float* x0_u, const float* scale, float* x, const float* noise,
                                                               const float4* rec, const float* c1, const float* c2, const float* s, int32_t B,
@@ -31,13 +30,9 @@ extern "C" int afm_mha_fwd_arith(const float*, const uint8_t*, float*, int32_t, 
 extern "C" int afm_layernorm(const float*, const float*, const float*, float*, int64_t, int32_t, float, void*);
 extern "C" int afm_layernorm_rows(const float*, const float*, const float*, float*, int64_t, int32_t, float, int32_t, int32_t, int32_t, void*);
 extern "C" int afm_randn(float*, int32_t, int64_t, uint64_t, int64_t, int32_t, void*);
-__attribute__((visibility("hidden"))) int afm_randn_steps(float*, int32_t, int64_t, uint64_t, int64_t, int32_t, int32_t, void*);      // elementwise.hip: [nsteps][B][per_sample]
 
 namespace {
 
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-constexpr int NOISE_STEPS = 16;
 struct Workspace {
     float *seq0, *y, *x1, *tmp, *qkv, *qkv0, *att, *hid, *noise, *xpad;
     float* x0;                // loop workspaces only: pred_xstart [B][L][motion_dim] of the DDIM loop's step (its update launch reads it)
@@ -118,18 +113,6 @@ struct Branch { int pos_off, mask_text, mask_pc; };
 __global__ __launch_bounds__(64) void cond_keymask_kernel(uint8_t* __restrict__ keymask, int T, int n_cond, int mask_text, int mask_pc) {
     for (int i = threadIdx.x; i < n_cond; i += blockDim.x)
         keymask[(int64_t)blockIdx.x * T + 1 + i] = (uint8_t)(i == 0 ? mask_text : mask_pc);
-}
-
-// per-step per-sample schedule rows for the whole loop: row j <-> spaced timestep i = n_steps-1-j
-__global__ void expand_schedule_kernel(const int64_t* __restrict__ tmap, const float* __restrict__ c1,
-                                       const float* __restrict__ c2, const float* __restrict__ sg, int n_steps, int B,
-                                       int64_t* __restrict__ t_all, float* __restrict__ c1_all, float* __restrict__ c2_all,
-                                       float* __restrict__ sg_all) {
-    const int64_t n = (int64_t)n_steps * B;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const int i = n_steps - 1 - (int)(e / B);
-        t_all[e] = tmap[i]; c1_all[e] = c1[i]; c2_all[e] = c2[i]; sg_all[e] = sg[i];
-    }
 }
 
 #define AFM_TRY(expr) do { int rc__ = (expr); if (rc__ != 0) return rc__; } while (0)
@@ -361,6 +344,13 @@ int validate(const afm_cmdm_weights* w, int B, int L) {
     return 0;
 }
 
+// a caller's pack as the library takes it: the library-private flag bits are never taken from a caller (`also`: more bits to clear)
+inline afm_cmdm_weights callers_pack(const afm_cmdm_weights& w, uint32_t also = 0) {
+    afm_cmdm_weights r = w;
+    r.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE | also);
+    return r;
+}
+
 // the unconditioned branch of a guided evaluation: its copy of the pack and its Branch (compact when every condition is dropped)
 int uncond_setup(const afm_cmdm_weights& w, const afm_cfg_args* cfg, const uint8_t* frame_mask, afm_cmdm_weights* wu, Branch* br) {
     if (!cfg || !cfg->scale || (!cfg->drop_text && !cfg->drop_pc) || w.n_cond < 1) return AFM_E_BADARG;
@@ -391,10 +381,8 @@ extern "C" int afm_cmdm_forward(const afm_cmdm_weights* w, const float* x_t, con
     if (!x0_out && !ddpm) return AFM_E_BADARG;
     if (ddpm && (!ddpm->x_next || !ddpm->c1 || !ddpm->c2 || !ddpm->sigma)) return AFM_E_BADARG;
     if (B == 0) return 0;
-    afm_cmdm_weights wpub;
-    if (w->flags & (AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE)) {        // library-private bits: never taken from a caller
-        wpub = *w; wpub.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE); w = &wpub;
-    }
+    const afm_cmdm_weights wpub = callers_pack(*w);
+    w = &wpub;
     const Workspace ws = carve(*w, B, L, workspace);
     if (ws.bytes > workspace_bytes) return AFM_E_WORKSPACE;
     if ((w->flags & AFM_CMDM_FUSED_LN) &&           // ticket words of the opt-in fused LayerNorm only
@@ -413,8 +401,8 @@ extern "C" int afm_cmdm_cfg_forward(const afm_cmdm_weights* w, const float* x_t,
                                     int32_t B, int32_t L, void* workspace, int64_t workspace_bytes, void* stream) {
     AFM_TRY(validate(w, B, L));
     if (!x_t || !t || !cond_tokens || !workspace || !x0_guided) return AFM_E_BADARG;
-    afm_cmdm_weights wc = *w, wu;
-    wc.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE | AFM_CMDM_FUSED_LN);         // (library-private bits; the opt-in fused LayerNorm is not built here)
+    const afm_cmdm_weights wc = callers_pack(*w, AFM_CMDM_FUSED_LN);         // (the opt-in fused LayerNorm is not built here)
+    afm_cmdm_weights wu;
     Branch br;
     AFM_TRY(uncond_setup(wc, cfg, frame_mask, &wu, &br));
     if (B == 0) return 0;
@@ -439,40 +427,179 @@ extern "C" int64_t afm_ddim_sched_scratch_bytes(int32_t n_steps, int32_t B) {
     return align256((int64_t)n_steps * B * 8) + align256((int64_t)n_steps * B * 16) + align256((int64_t)n_steps * B * 4);
 }
 
+// ------------------------------------------------------------------------------------------------ native sampling loop
+// One driver for the four loops: DDPM (the ancestral update with the rows c1 / c2 / sigma, fused into the motion_layer epilogue) or DDIM
+// (`ddim` != NULL: motion_layer stores pred_xstart and ONE elementwise launch per sub-batch and step, afm_ddim_update_rows, applies the
+// update), each unguided or guided (`cfg` != NULL).  (The DDIM update fused into the shared GEMM epilogue grew the registers - and on three
+// variants the scratch - of DDPM GEMM kernels that every sampling step runs; a launch of its own leaves them as they were.)
+// plan_loop decides everything a call fixes before its first launch; the step functions enqueue one (sub-batch, step); sample_loop_impl
+// owns the schedule, the events and the order.  The shared pieces (sub-batches, schedule, noise, events) live in sample_loop.h.
 namespace {
-inline void sub_range(int B, int n, int s, int* start, int* count) {
-    const int base = B / n, extra = B % n;
-    *count = base + (s < extra ? 1 : 0);
-    *start = s * base + (s < extra ? s : extra);
-}
-}  // namespace
 
-extern "C" int64_t afm_cmdm_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams) {
-    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
-    const int n = n_streams > 1 ? (n_streams < B ? n_streams : (B > 0 ? B : 1)) : 1;
+constexpr int MAX_SUB = 16;           // sub-batches (streams) of one loop call
+constexpr int NEV = 2 * AFM_MAX_LAYERS;      // events of the paired schedule: two cross-stream edges per layer
+
+// the arguments of the five loop entry points
+struct LoopCall {
+    const afm_cmdm_weights* w;
+    float* x;
+    const float* cond_tokens;
+    const uint8_t* frame_mask;
+    const afm_cfg_args* cfg;
+    int L;
+    LoopArgs a;                       // (a.streams: one side stream per sub-batch)
+};
+
+struct SubBatch : SubRange {
+    Workspace ws, wsu;                // wsu: the unconditioned branch's (guided loops), behind ws
+    // guided loop with branch streams: the unconditioned branch runs on `branch`; two events order it against the guided update, the only
+    // writer of x and of its K-padded copy (x_ready: x is ready, u_ready: the branch's pred_xstart is ready)
+    hipStream_t branch;
+    hipEvent_t x_ready, u_ready;
+};
+
+// carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
+int64_t carve_sub(const afm_cmdm_weights& w, const afm_cmdm_weights* wu, int L, char* base, SubBatch* sb) {
+    sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
+    if (!wu) return sb->ws.bytes;
+    // (2 "noise steps": a pred_xstart region of its own, as little noise space as the layout allows)
+    sb->wsu = carve(*wu, sb->count, L, base ? base + sb->ws.bytes : nullptr, 2);
+    sb->wsu.xpad = sb->ws.xpad;       // one K-padded copy of x_t serves both branches
+    return sb->ws.bytes + sb->wsu.bytes;
+}
+
+int64_t loop_workspace_bytes(const afm_cmdm_weights& w, const afm_cmdm_weights* wu, int B, int L, int n_streams) {
+    const int n = sub_count(B, n_streams, MAX_SUB);
     int64_t total = 0;
     for (int s = 0; s < n; ++s) {
-        int st, cnt;
-        sub_range(B, n, s, &st, &cnt);
-        total += carve(*w, cnt, L, nullptr, NOISE_STEPS).bytes;
+        SubBatch sb = {};
+        sub_range(B, n, s, &sb.start, &sb.count);
+        total += carve_sub(w, wu, L, nullptr, &sb);
     }
     return total;
 }
 
-extern "C" int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg) {
-    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
-    afm_cmdm_weights wu;
+// what a loop call fixes before its first launch: the loop's own weight packs, the sub-batches with their streams and workspaces, the form
+struct LoopPlan {
+    afm_cmdm_weights w, wu;           // the loop's copies: flags (private bits, tile code) set here; wu: the unconditioned branch's pack
     Branch br;
-    const uint8_t some_mask = 0;                              // (sizes do not depend on the frame mask)
-    if (uncond_setup(*w, cfg, &some_mask, &wu, &br) != 0) return AFM_E_BADARG;
-    const int n = n_streams > 1 ? (n_streams < B ? n_streams : (B > 0 ? B : 1)) : 1;
-    int64_t total = 0;
-    for (int s = 0; s < n; ++s) {
-        int st, cnt;
-        sub_range(B, n, s, &st, &cnt);
-        total += carve(*w, cnt, L, nullptr, NOISE_STEPS).bytes + carve(wu, cnt, L, nullptr, 2).bytes;
+    int nsub;                         // 0: an empty batch, nothing to enqueue
+    SubBatch sb[MAX_SUB];
+    bool paired;                      // AFM_CMDM_PAIR_LAUNCH, two sub-batches: every step after the first is recorded and issued interleaved
+    bool branch_streams;
+    int64_t row;                      // values per sample
+};
+
+int plan_loop(const LoopCall& c, LoopPlan* p) {
+    const LoopArgs& a = c.a;
+    AFM_TRY(validate(c.w, a.B, c.L));
+    // Guided loop (cfg != NULL): per sub-batch and step the conditioned branch (this loop's step as it is, pred_xstart stored the DDIM
+    // loop's way, for DDPM too), the unconditioned branch on a workspace of its own behind it on the same stream, and ONE update launch
+    // (afm_cfg_update_rows).  Both branches read the same x / K-padded copy; only the update writes them.
+    p->br = {};
+    if (c.cfg) AFM_TRY(uncond_setup(*c.w, c.cfg, c.frame_mask, &p->wu, &p->br));
+    if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok()) return AFM_E_BADARG;
+    p->nsub = 0;
+    if (a.B == 0) return 0;
+    p->nsub = sub_count(a.B, a.n_streams, MAX_SUB);
+    p->branch_streams = c.cfg && c.cfg->branch_streams;
+    int64_t off = 0;
+    for (int s = 0; s < p->nsub; ++s) {
+        SubBatch& sb = p->sb[s];
+        sb = {};
+        sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
+        off += carve_sub(*c.w, c.cfg ? &p->wu : nullptr, c.L, (char*)a.workspace + off, &sb);
+        sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
+        if (p->branch_streams) sb.branch = (hipStream_t)c.cfg->branch_streams[s];
     }
-    return total;
+    if (off > a.workspace_bytes) return AFM_E_WORKSPACE;
+
+    // Tile shape of the wide encoder GEMMs inside the multi-stream loop (round 6).  afm_linear's own rule prices ONE launch: 128 x 128 tiles only
+    // when their last resident round is >= 90 % full (in_proj), 64 x 64 otherwise.  Inside this loop a second sub-batch's kernels fill the
+    // slots a partial round leaves, and what counts is the work per matrix instruction (the loop runs at the board's power limit): with the
+    // six-product arithmetic, 128 x 128 on EVERY GEMM with N >= 512 measured 588-590 against 568-574 steps/s at 16 + 16 samples in the same
+    // calls, but 853 against 995 at 8 + 8 and 1168 against 1470 at 4 + 4 (profiles/r06_tile_rule.md) - so: sub-batches of >= 4096 rows only.
+    // Round 7: the same 128 x 128 tile on 512 threads (tile code 14: two of the tile's waves per SIMD) - 611-612 against 580 steps/s for code 5
+    // in one call (profiles/r07_gemm128_timeline.md); code 5 stays reachable through the override.
+    // Tile shapes of one arithmetic are bit-identical; a caller's explicit AFM_CMDM_WIDE_TILE code wins.
+    const int T = 1 + c.w->n_cond + c.L;
+    p->w = *c.w;
+    p->w.flags = a.loop_flags(p->w.flags);
+    if (c.cfg) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
+    if (p->nsub >= 2 && ((p->w.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
+        bool big = true;
+        for (int s = 0; s < p->nsub; ++s) big = big && (int64_t)p->sb[s].count * T >= 4096;
+        if (big) p->w.flags |= 14 << AFM_CMDM_WIDE_TILE_SHIFT;
+    }
+    if (c.cfg) { const int nc_u = p->wu.n_cond; p->wu = p->w; p->wu.n_cond = nc_u; }       // the loop's flags (tile code, private bits) on the branch's pack
+    p->paired = (p->w.flags & AFM_CMDM_PAIR_LAUNCH) && p->nsub == 2 && p->sb[0].count > 0 && p->sb[1].count > 0;
+    p->row = (int64_t)c.L * c.w->motion_dim;
+    return 0;
+}
+
+struct Loop {
+    const LoopCall& c;
+    LoopPlan p;
+    Schedule sched;
+};
+
+inline float* sub_x(const Loop& l, const SubBatch& sb) { return l.c.x + (int64_t)sb.start * l.p.row; }
+
+// the conditioned evaluation of (sub-batch, step j) on the sub-batch's stream, or into `rec`; *rows and *dd: what the update launches
+// behind it read (in a DDPM loop the evaluation's own epilogue is the update)
+int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_ddpm_args* dd, Recorder* rec) {
+    const LoopCall& c = l.c;
+    const afm_cmdm_weights& w = l.p.w;
+    const float* nz;
+    AFM_TRY(step_noise(c.a, l.p.row, sb, sb.ws.noise, j, sub_x(l, sb), &sb.stream, &nz));
+    *rows = l.sched.at(j, sb.start);
+    *dd = ddpm_args(c.a, *rows, nz, sub_x(l, sb), sb, j);
+    return forward_impl(w, sub_x(l, sb), rows->t, c.cond_tokens ? c.cond_tokens + (int64_t)sb.start * w.n_cond * w.d : nullptr,
+                        c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr, nullptr, dd, sb.count, c.L, sb.ws, j == 0, sb.stream, rec);
+}
+
+// the DDIM update of a sub-batch from its stored pred_xstart (ws.x0), in place on x, with the K-padded copy the next step reads
+int ddim_update(const Loop& l, const SubBatch& sb, const StepRows& rows, const float* noise) {
+    const afm_cmdm_weights& w = l.p.w;
+    const bool nt = l.c.a.noise_term();
+    return afm_ddim_update_rows(sb.ws.x0, sub_x(l, sb), nt ? noise : nullptr, rows.rec, nt ? rows.sigma : nullptr, sb.count, l.p.row, w.motion_dim,
+                                (w.flags & AFM_CMDM_CLIP_X0) ? 1 : 0, sb.ws.xpad, w.motion_adapter_kpad, sb.stream);
+}
+
+int unguided_step(const Loop& l, const SubBatch& sb, int j) {
+    StepRows rows;
+    afm_ddpm_args dd;
+    AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
+    return l.c.a.ddim ? ddim_update(l, sb, rows, dd.noise) : 0;
+}
+
+int guided_step(const Loop& l, const SubBatch& sb, int j) {
+    const LoopCall& c = l.c;
+    const afm_cmdm_weights &w = l.p.w, &wu = l.p.wu;
+    const bool nt = c.a.noise_term(), bs = l.p.branch_streams;
+    StepRows rows;
+    afm_ddpm_args dd;
+    AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
+    // step 0: the branch's prologue rewrites the shared K-padded copy (same values), so it starts behind the conditioned branch;
+    // later steps: behind the previous update, next to the conditioned branch
+    const hipStream_t su = bs ? sb.branch : sb.stream;
+    if (bs) {
+        if (j == 0) (void)hipEventRecord(sb.x_ready, sb.stream);
+        (void)hipStreamWaitEvent(su, sb.x_ready, 0);
+    }
+    const int rc = forward_impl(wu, sub_x(l, sb), rows.t, wu.n_cond && c.cond_tokens ? c.cond_tokens + (int64_t)sb.start * w.n_cond * w.d : nullptr,
+                                c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr, nullptr, &dd, sb.count, c.L, sb.wsu, j == 0, su,
+                                nullptr, &l.p.br);
+    if (bs) {       // (also behind a failed branch: the sub-batch's stream never runs ahead of its branch stream)
+        (void)hipEventRecord(sb.u_ready, su);
+        (void)hipStreamWaitEvent(sb.stream, sb.u_ready, 0);
+    }
+    AFM_TRY(rc);
+    AFM_TRY(afm_cfg_update_rows(sb.ws.x0, sb.wsu.x0, c.cfg->scale + sb.start, sub_x(l, sb), nt ? dd.noise : nullptr, rows.rec, rows.c1, rows.c2,
+                                nt ? rows.sigma : nullptr, sb.count, l.p.row, w.motion_dim, (w.flags & AFM_CMDM_CLIP_X0) ? 1 : 0, sb.ws.xpad,
+                                w.motion_adapter_kpad, sb.stream));
+    if (bs) (void)hipEventRecord(sb.x_ready, sb.stream);       // x and its padded copy of the next step
+    return 0;
 }
 
 // ---- the paired schedule of one step (AFM_CMDM_PAIR_LAUNCH; two sub-batches A, B on streams sa, sb).  Both lists hold the same launch
@@ -480,7 +607,7 @@ extern "C" int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, 
 // (afm_linear_pair: 164 + 328 = 492 tiles of 128 x 128 at 16 samples per sub-batch - one full resident round); B continues with linear2 on
 // sb, A with linear1 on sa.  Two cross-stream edges per layer: sb -> sa before the pair (B's out_proj output and statistics), sa -> sb after
 // it (B's hidden rows).  Every element is computed by the same tile program on the same operands: bit-identical to the unpaired schedule.
-static int issue_paired(const Recorder& A, const Recorder& B, hipStream_t sa, hipStream_t sb, hipEvent_t* ev, int nev) {
+int issue_paired(const Recorder& A, const Recorder& B, hipStream_t sa, hipStream_t sb, const hipEvent_t* ev, int nev) {
     if (A.n != B.n) return AFM_E_UNSUPPORTED;
     int ia = 0, ib = 0, e = 0;
     while (ia < A.n) {
@@ -504,211 +631,81 @@ static int issue_paired(const Recorder& A, const Recorder& B, hipStream_t sa, hi
     return 0;
 }
 
-// One loop body for both updates: `ddim` == NULL runs the ancestral DDPM update with the rows d_c1 / d_c2 / d_sigma (fused into the
-// motion_layer epilogue), otherwise the DDIM update with the rows *ddim (d_c* unused): motion_layer stores pred_xstart and ONE elementwise
-// launch per sub-batch and step (afm_ddim_update_rows) applies ddim_update.  (The update fused into the shared GEMM epilogue grew the
-// registers - and on three variants the scratch - of DDPM GEMM kernels that every sampling step runs; a launch of its own leaves them as
-// they were.)
-static int sample_loop_impl(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
-                            const float* step_noise, const int64_t* d_timestep_map, const float* d_c1,
-                            const float* d_c2, const float* d_sigma, const afm_ddim_rows* ddim, int32_t n_steps, int32_t first_step, uint64_t seed,
-                            int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
-                            int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream,
-                            const afm_cfg_args* cfg = nullptr) {
-    AFM_TRY(validate(w, B, L));
-    // Guided loop (cfg != NULL): per sub-batch and step the conditioned branch (this loop's step as it is, pred_xstart stored the DDIM
-    // loop's way, for DDPM too), the unconditioned branch on a workspace of its own behind it on the same stream, and ONE update launch
-    // (afm_cfg_update_rows).  Both branches read the same x / K-padded copy; only the update writes them.
-    afm_cmdm_weights wu;
-    Branch br = {};
-    if (cfg) AFM_TRY(uncond_setup(*w, cfg, frame_mask, &wu, &br));
-    const bool rows_ok = ddim ? (ddim->a && ddim->b && ddim->c && ddim->d) : (d_c1 && d_c2 && d_sigma);
-    if (!x || (w->n_cond > 0 && !cond_tokens) || !d_timestep_map || !rows_ok || n_steps <= 0 ||
-        !sched_scratch || !workspace || n_streams < 0 || (n_streams > 1 && !side_streams))
-        return AFM_E_BADARG;
-    if (B == 0) return 0;
-    const bool noise_term = !ddim || ddim->sigma;          // eta = 0 DDIM rows: no noise is generated or read
-    hipStream_t s0 = (hipStream_t)stream;
-    int nsub = n_streams > 1 ? (n_streams < B ? n_streams : B) : 1;
-    if (nsub > 16) nsub = 16;
+// a step of the paired schedule: both sub-batches' launches recorded, issued interleaved, then (DDIM) each sub-batch's update behind its
+// recorded launches
+int paired_step(const Loop& l, int j, Recorder* recs, const hipEvent_t* pev) {
+    StepRows rows[2];
+    afm_ddpm_args dd[2];
+    for (int s = 0; s < 2; ++s) {
+        recs[s].n = 0;
+        AFM_TRY(cond_forward(l, l.p.sb[s], j, &rows[s], &dd[s], &recs[s]));
+    }
+    AFM_TRY(issue_paired(recs[0], recs[1], l.p.sb[0].stream, l.p.sb[1].stream, pev, NEV));
+    for (int s = 0; l.c.a.ddim && s < 2; ++s) AFM_TRY(ddim_update(l, l.p.sb[s], rows[s], dd[s].noise));
+    return 0;
+}
 
-    char* sp = (char*)sched_scratch;
-    const int64_t nb = (int64_t)n_steps * B;
-    int64_t* t_all = (int64_t*)sp; sp += align256(nb * 8);
-    float *c1_all, *c2_all, *sg_all;
-    float4* rec_all = nullptr;
-    if (ddim) {                                            // layout of afm_ddim_sched_scratch_bytes
-        rec_all = (float4*)sp; sp += align256(nb * 16);
-        sg_all = (float*)sp;
-        c1_all = c2_all = (float*)rec_all;
-        AFM_TRY(afm_ddim_expand_rows(d_timestep_map, ddim, n_steps, B, t_all, rec_all, sg_all, s0));
-    } else {
-        c1_all = (float*)sp; sp += align256(nb * 4);
-        c2_all = (float*)sp; sp += align256(nb * 4);
-        sg_all = (float*)sp;
-        hipLaunchKernelGGL(expand_schedule_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s0, d_timestep_map, d_c1, d_c2,
-                           d_sigma, n_steps, B, t_all, c1_all, c2_all, sg_all);
+// the events of a loop call, all owned by `ev`: the guided branch pairs, the fork of the sub-batch streams, the paired schedule's
+int loop_events(Loop& l, Events& ev, hipEvent_t* pev) {
+    LoopPlan& p = l.p;
+    for (int s = 0; p.branch_streams && s < p.nsub; ++s) {
+        AFM_TRY(ev.make(&p.sb[s].x_ready));
+        AFM_TRY(ev.make(&p.sb[s].u_ready));
     }
-    AFM_CHECK_LAUNCH();
+    hipEvent_t fork;
+    if (p.nsub > 1) AFM_TRY(fork_streams(ev, (hipStream_t)l.c.a.stream, p.sb, p.nsub, &fork));
+    for (int i = 0; p.paired && i < NEV; ++i) AFM_TRY(ev.make(&pev[i]));
+    return 0;
+}
 
-    // carve one workspace per sub-batch
-    Workspace ws[16], wsu[16];
-    int start[16], count[16];
-    hipStream_t st[16];
-    {
-        char* base = (char*)workspace;
-        int64_t off = 0;
-        for (int s = 0; s < nsub; ++s) {
-            sub_range(B, nsub, s, &start[s], &count[s]);
-            ws[s] = carve(*w, count[s], L, base + off, NOISE_STEPS);
-            off += ws[s].bytes;
-            if (cfg) {                                    // (2 "noise steps": a pred_xstart region of its own, as little noise space as the layout allows)
-                wsu[s] = carve(wu, count[s], L, base + off, 2);
-                off += wsu[s].bytes;
-                wsu[s].xpad = ws[s].xpad;                 // one K-padded copy of x_t serves both branches
-            }
-            st[s] = nsub > 1 ? (hipStream_t)side_streams[s] : s0;
-        }
-        if (off > workspace_bytes) return AFM_E_WORKSPACE;
+// ticket words of the fused LayerNorm: zero once, every launch leaves them zero
+int zero_ln_tickets(const Loop& l) {
+    if (!(l.p.w.flags & AFM_CMDM_FUSED_LN)) return 0;
+    const int T = 1 + l.p.w.n_cond + l.c.L;
+    for (int s = 0; s < l.p.nsub; ++s) {
+        const SubBatch& sb = l.p.sb[s];
+        if (sb.count > 0 && hipMemsetAsync(sb.ws.lncnt, 0, (size_t)(((int64_t)sb.count * T + 31) / 32) * 4, sb.stream) != hipSuccess) return (int)hipGetLastError();
     }
-    // guided loop with branch streams: the unconditioned branch of sub-batch s runs on bst[s]; two events per sub-batch order it against the
-    // guided update, the only writer of x and of its K-padded copy (ev_x[s]: x is ready, ev_u[s]: the branch's pred_xstart is ready)
-    hipStream_t bst[16] = {};
-    hipEvent_t ev_x[16] = {}, ev_u[16] = {};
-    const bool branch_streams = cfg && cfg->branch_streams;
-    auto drop_branch_events = [&]() { for (int s = 0; s < 16; ++s) { if (ev_x[s]) (void)hipEventDestroy(ev_x[s]); if (ev_u[s]) (void)hipEventDestroy(ev_u[s]); } };
-    for (int s = 0; branch_streams && s < nsub; ++s) {
-        bst[s] = (hipStream_t)cfg->branch_streams[s];
-        if (hipEventCreateWithFlags(&ev_x[s], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_u[s], hipEventDisableTiming) != hipSuccess) {
-            const int rc_ev = (int)hipGetLastError();
-            drop_branch_events();
-            return rc_ev;
-        }
-    }
-    hipEvent_t fork = nullptr;
-    if (nsub > 1) {      // side streams start after everything already queued on `stream` (inputs, schedule rows)
-        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) { drop_branch_events(); return (int)hipGetLastError(); }
-        (void)hipEventRecord(fork, s0);
-        for (int s = 0; s < nsub; ++s) (void)hipStreamWaitEvent(st[s], fork, 0);
-    }
+    return 0;
+}
 
-    const int T = 1 + w->n_cond + L;
-    // Tile shape of the wide encoder GEMMs inside the multi-stream loop (round 6).  afm_linear's own rule prices ONE launch: 128 x 128 tiles only
-    // when their last resident round is >= 90 % full (in_proj), 64 x 64 otherwise.  Inside this loop a second sub-batch's kernels fill the
-    // slots a partial round leaves, and what counts is the work per matrix instruction (the loop runs at the board's power limit): with the
-    // six-product arithmetic, 128 x 128 on EVERY GEMM with N >= 512 measured 588-590 against 568-574 steps/s at 16 + 16 samples in the same
-    // calls, but 853 against 995 at 8 + 8 and 1168 against 1470 at 4 + 4 (profiles/r06_tile_rule.md) - so: sub-batches of >= 4096 rows only.
-    // Round 7: the same 128 x 128 tile on 512 threads (tile code 14: two of the tile's waves per SIMD) - 611-612 against 580 steps/s for code 5
-    // in one call (profiles/r07_gemm128_timeline.md); code 5 stays reachable through the override.
-    // Tile shapes of one arithmetic are bit-identical; a caller's explicit AFM_CMDM_WIDE_TILE code wins.
-    afm_cmdm_weights wl = *w;
-    wl.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE);                  // library-private: never taken from a caller
-    if (ddim) wl.flags |= AFM_PRIV_DDIM | (noise_term ? 0 : AFM_PRIV_NO_NOISE);
-    if (cfg) wl.flags = (wl.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
-    if (nsub >= 2 && ((wl.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
-        bool big = true;
-        for (int s = 0; s < nsub; ++s) big = big && (int64_t)count[s] * T >= 4096;
-        if (big) wl.flags |= 14 << AFM_CMDM_WIDE_TILE_SHIFT;
-    }
-    w = &wl;
-    if (cfg) { const int nc_u = wu.n_cond; wu = wl; wu.n_cond = nc_u; }       // the loop's flags (tile code, private bits) on the branch's pack
-    for (int s = 0; s < nsub; ++s)        // ticket words of the fused LayerNorm: zero once, every launch leaves them zero
-        if (count[s] > 0 && (w->flags & AFM_CMDM_FUSED_LN) && hipMemsetAsync(ws[s].lncnt, 0, (size_t)(((int64_t)count[s] * T + 31) / 32) * 4, st[s]) != hipSuccess) return (int)hipGetLastError();
-    const int64_t row = (int64_t)L * w->motion_dim;
-    int rc = 0;
-    // paired schedule (AFM_CMDM_PAIR_LAUNCH, two sub-batches): every step after the first is recorded per sub-batch and issued interleaved
-    const bool paired = (w->flags & AFM_CMDM_PAIR_LAUNCH) && nsub == 2 && count[0] > 0 && count[1] > 0;
-    constexpr int NEV = 2 * AFM_MAX_LAYERS;
+int sample_loop_impl(const LoopCall& c) {
+    Loop l{c, {}, {}};
+    AFM_TRY(plan_loop(c, &l.p));
+    if (l.p.nsub == 0) return 0;
+    AFM_TRY(l.sched.expand(c.a));
+    Events ev;                        // every return below releases what was created
     hipEvent_t pev[NEV] = {};
-    Recorder* recs = nullptr;
-    if (paired) {
-        for (int i = 0; i < NEV; ++i)
-            if (hipEventCreateWithFlags(&pev[i], hipEventDisableTiming) != hipSuccess) {
-                const int rc_ev = (int)hipGetLastError();
-                for (int u = 0; u < i; ++u) (void)hipEventDestroy(pev[u]);          // nothing created so far may leak
-                if (fork) (void)hipEventDestroy(fork);
-                return rc_ev;
-            }
-        recs = new Recorder[2];
-    }
-    // the DDIM update of sub-batch s from its stored pred_xstart (ws.x0), in place on x, with the K-padded copy the next step reads
-    auto ddim_update = [&](int s, const afm_ddpm_args& dd) -> int {
-        return afm_ddim_update_rows(ws[s].x0, x + (int64_t)start[s] * row, noise_term ? dd.noise : nullptr, (const float4*)dd.c1,
-                                    noise_term ? dd.sigma : nullptr, count[s], row, w->motion_dim, (w->flags & AFM_CMDM_CLIP_X0) ? 1 : 0,
-                                    ws[s].xpad, w->motion_adapter_kpad, st[s]);
-    };
-    for (int j = 0; j < n_steps && rc == 0; ++j) {
-        const bool rec_step = paired && j > 0;
-        if (rec_step) recs[0].n = recs[1].n = 0;
-        for (int s = 0; s < nsub && rc == 0; ++s) {
-            if (count[s] == 0) continue;
-            afm_ddpm_args dd = {};
-            if (!noise_term) dd.noise = x + (int64_t)start[s] * row;        // (never read: AFM_UPD_NO_NOISE)
-            else if (step_noise) dd.noise = step_noise + ((int64_t)j * B + start[s]) * row;
-            else {
-                if (j % NOISE_STEPS == 0) {               // one launch per NOISE_STEPS steps instead of one per step (a launch is ~5 us of a small-batch step)
-                    rc = afm_randn_steps(ws[s].noise, count[s], row, seed, sample_index0 + start[s], first_step + j, n_steps - j < NOISE_STEPS ? n_steps - j : NOISE_STEPS, st[s]);
-                    if (rc) break;
-                }
-                dd.noise = ws[s].noise + (int64_t)(j % NOISE_STEPS) * count[s] * row;
-            }
-            dd.x_next = x + (int64_t)start[s] * row;      // in place: each element is read then written by the same lane
-            if (ddim) { dd.c1 = dd.c2 = (const float*)(rec_all + (int64_t)j * B + start[s]); }       // {a, b, c, d} records (AFM_UPD_DDIM)
-            else { dd.c1 = c1_all + (int64_t)j * B + start[s]; dd.c2 = c2_all + (int64_t)j * B + start[s]; }
-            dd.sigma = sg_all + (int64_t)j * B + start[s];
-            dd.seed = seed; dd.sample_index0 = sample_index0 + start[s]; dd.step = first_step + j;
-            rc = forward_impl(*w, x + (int64_t)start[s] * row, t_all + (int64_t)j * B + start[s],
-                              cond_tokens ? cond_tokens + (int64_t)start[s] * w->n_cond * w->d : nullptr,
-                              frame_mask ? frame_mask + (int64_t)start[s] * L : nullptr, nullptr, &dd, count[s], L, ws[s], j == 0,
-                              st[s], rec_step ? &recs[s] : nullptr);
-            if (rc == 0 && cfg) {
-                // step 0: the branch's prologue rewrites the shared K-padded copy (same values), so it starts behind the conditioned branch;
-                // later steps: behind the previous update, next to the conditioned branch
-                const hipStream_t su = branch_streams ? bst[s] : st[s];
-                if (branch_streams) {
-                    if (j == 0) (void)hipEventRecord(ev_x[s], st[s]);
-                    (void)hipStreamWaitEvent(su, ev_x[s], 0);
-                }
-                rc = forward_impl(wu, x + (int64_t)start[s] * row, t_all + (int64_t)j * B + start[s],
-                                  wu.n_cond && cond_tokens ? cond_tokens + (int64_t)start[s] * w->n_cond * w->d : nullptr,
-                                  frame_mask ? frame_mask + (int64_t)start[s] * L : nullptr, nullptr, &dd, count[s], L, wsu[s], j == 0,
-                                  su, nullptr, &br);
-                if (branch_streams) {
-                    (void)hipEventRecord(ev_u[s], su);
-                    (void)hipStreamWaitEvent(st[s], ev_u[s], 0);
-                }
-                if (rc == 0)
-                    rc = afm_cfg_update_rows(ws[s].x0, wsu[s].x0, cfg->scale + start[s], x + (int64_t)start[s] * row, noise_term ? dd.noise : nullptr,
-                                             ddim ? (const float4*)dd.c1 : nullptr, dd.c1, dd.c2, noise_term ? dd.sigma : nullptr, count[s], row,
-                                             w->motion_dim, (w->flags & AFM_CMDM_CLIP_X0) ? 1 : 0, ws[s].xpad, w->motion_adapter_kpad, st[s]);
-                if (branch_streams) (void)hipEventRecord(ev_x[s], st[s]);       // x and its padded copy of the next step
-            } else if (rc == 0 && ddim && !rec_step) rc = ddim_update(s, dd);
-        }
-        if (rec_step && rc == 0) rc = issue_paired(recs[0], recs[1], st[0], st[1], pev, NEV);
-        for (int s = 0; ddim && rec_step && rc == 0 && s < nsub; ++s) {      // (the paired schedule: behind the sub-batch's recorded launches)
-            afm_ddpm_args dd = {};
-            dd.noise = !noise_term ? nullptr : step_noise ? step_noise + ((int64_t)j * B + start[s]) * row : ws[s].noise + (int64_t)(j % NOISE_STEPS) * count[s] * row;
-            dd.c1 = (const float*)(rec_all + (int64_t)j * B + start[s]); dd.sigma = sg_all + (int64_t)j * B + start[s];
-            rc = ddim_update(s, dd);
+    AFM_TRY(loop_events(l, ev, pev));
+    AFM_TRY(zero_ln_tickets(l));
+    const std::unique_ptr<Recorder[]> recs(l.p.paired ? new Recorder[2] : nullptr);
+    int rc = 0;
+    for (int j = 0; j < c.a.n_steps && rc == 0; ++j) {
+        if (l.p.paired && j > 0) { rc = paired_step(l, j, recs.get(), pev); continue; }
+        for (int s = 0; s < l.p.nsub && rc == 0; ++s) {
+            if (l.p.sb[s].count == 0) continue;
+            rc = c.cfg ? guided_step(l, l.p.sb[s], j) : unguided_step(l, l.p.sb[s], j);
         }
     }
-    if (paired) {
-        delete[] recs;
-        for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(pev[i]);
-    }
-    drop_branch_events();      // (every branch stream's last work is joined to its sub-batch's stream before the last update)
-    if (nsub > 1) {      // join: `stream` continues only after every sub-batch loop has finished
-        for (int s = 0; s < nsub; ++s) {
-            hipEvent_t done;
-            if (hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess) {
-                (void)hipEventRecord(done, st[s]);
-                (void)hipStreamWaitEvent(s0, done, 0);
-                (void)hipEventDestroy(done);
-            }
-        }
-        (void)hipEventDestroy(fork);
-    }
+    // (every branch stream's last work is joined to its sub-batch's stream before the last update)
+    if (l.p.nsub > 1) join_streams(ev, (hipStream_t)c.a.stream, l.p.sb, l.p.nsub);
     return rc;
+}
+
+}  // namespace
+
+extern "C" int64_t afm_cmdm_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams) {
+    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
+    return loop_workspace_bytes(*w, nullptr, B, L, n_streams);
+}
+
+extern "C" int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg) {
+    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
+    afm_cmdm_weights wu;
+    Branch br;
+    const uint8_t some_mask = 0;                              // (sizes do not depend on the frame mask)
+    if (uncond_setup(*w, cfg, &some_mask, &wu, &br) != 0) return AFM_E_BADARG;
+    return loop_workspace_bytes(*w, &wu, B, L, n_streams);
 }
 
 extern "C" int afm_cmdm_sample_loop(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
@@ -716,8 +713,8 @@ extern "C" int afm_cmdm_sample_loop(const afm_cmdm_weights* w, float* x, const f
                                     const float* d_c2, const float* d_sigma, int32_t n_steps, uint64_t seed,
                                     int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                     int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
-    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, 0, seed,
-                            sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, 0, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
 }
 
 extern "C" int afm_cmdm_sample_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -727,8 +724,8 @@ extern "C" int afm_cmdm_sample_loop_range(const afm_cmdm_weights* w, float* x, c
                                           void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                           void* const* side_streams, void* stream) {
     if (first_step < 0) return AFM_E_BADARG;
-    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step,
-                            seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
 }
 
 extern "C" int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -737,8 +734,8 @@ extern "C" int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, con
                                         int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                         void* const* side_streams, void* stream) {
     if (first_step < 0 || !rows) return AFM_E_BADARG;
-    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step,
-                            seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
 }
 
 extern "C" int afm_cmdm_cfg_sample_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -748,8 +745,8 @@ extern "C" int afm_cmdm_cfg_sample_loop_range(const afm_cmdm_weights* w, float* 
                                               void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                               void* const* side_streams, void* stream) {
     if (first_step < 0 || !cfg) return AFM_E_BADARG;
-    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step,
-                            seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg);
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
 }
 
 extern "C" int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -758,6 +755,6 @@ extern "C" int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x,
                                             int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes,
                                             int32_t n_streams, void* const* side_streams, void* stream) {
     if (first_step < 0 || !rows || !cfg) return AFM_E_BADARG;
-    return sample_loop_impl(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step,
-                            seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg);
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
 }

@@ -307,7 +307,27 @@ __attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, 
     return 0;
 }
 
-// the DDIM rows of a native loop (cmdm.hip, perceiver.hip), expanded like their DDPM rows: entry e = j * B + b of step j (timestep index
+// the DDPM rows of a native loop (sample_loop.h: Schedule), per step and sample: row j <-> spaced timestep i = n_steps - 1 - j
+__global__ void ddpm_expand_schedule_kernel(const int64_t* __restrict__ tmap, const float* __restrict__ c1, const float* __restrict__ c2,
+                                            const float* __restrict__ sg, int n_steps, int B, int64_t* __restrict__ t_all,
+                                            float* __restrict__ c1_all, float* __restrict__ c2_all, float* __restrict__ sg_all) {
+    const int64_t n = (int64_t)n_steps * B;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const int i = n_steps - 1 - (int)(e / B);
+        t_all[e] = tmap[i]; c1_all[e] = c1[i]; c2_all[e] = c2[i]; sg_all[e] = sg[i];
+    }
+}
+
+__attribute__((visibility("hidden"))) int afm_ddpm_expand_rows(const int64_t* tmap, const float* c1, const float* c2, const float* sigma, int32_t n_steps,
+                                                               int32_t B, int64_t* t_all, float* c1_all, float* c2_all, float* s_all, void* stream) {
+    const int64_t nb = (int64_t)n_steps * B;
+    hipLaunchKernelGGL(ddpm_expand_schedule_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tmap, c1, c2, sigma, n_steps, B,
+                       t_all, c1_all, c2_all, s_all);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+// the DDIM rows of a native loop (sample_loop.h: Schedule), expanded like their DDPM rows: entry e = j * B + b of step j (timestep index
 // n_steps - 1 - j of the slice's rows): t_all[e] = tmap[i], rec_all[e] = {a, b, c, d}[i], s_all[e] = sigma[i] (rows->sigma NULL: s_all not written)
 __global__ void ddim_expand_kernel(const int64_t* __restrict__ tmap, const float* __restrict__ ra, const float* __restrict__ rb,
                                    const float* __restrict__ rc, const float* __restrict__ rd, const float* __restrict__ sg, int n_steps, int B,

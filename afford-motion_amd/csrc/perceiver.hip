@@ -20,18 +20,14 @@
 // of the sampling form and the forward / native-loop drivers.  The kernels of a step live in perceiver_rows.hip (forms that read per-point
 // rows: layer by layer, FOLD), perceiver_points.hip (the row-less form of the sampling loop) and perceiver_chain.hip (the latent chain).
 #include "perceiver_internal.h"
+#include "sample_loop.h"
 
 extern "C" int afm_linear(const afm_linear_args*, void*);
-__attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, float* x, const float* noise, const float4* rec, const float* s, int32_t B,
-                                                               int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
-__attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tmap, const afm_ddim_rows* rows, int32_t n_steps, int32_t B, int64_t* t_all,
-                                                               float4* rec_all, float* s_all, void* stream);
 
 using namespace afm_cdm;
+using namespace afm_loop;
 
 namespace {
-
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 // ---------------------------------------------------------------- small device helpers (latent kernels)
 // out[tok][o] = b[o] + sum_k W[o][k] * in[tok][k]   for 2 tokens.  Each wave takes 4 output rows at a time
@@ -341,16 +337,6 @@ extern "C" int afm_cdm_forward_overlap(const afm_cdm_weights* wp, const float* f
 // ------------------------------------------------------------------------------------------------ native sampling loop
 namespace {
 
-__global__ void cdm_expand_schedule_kernel(const int64_t* __restrict__ tmap, const float* __restrict__ c1, const float* __restrict__ c2,
-                                           const float* __restrict__ sg, int n_steps, int B, int64_t* __restrict__ t_all,
-                                           float* __restrict__ c1_all, float* __restrict__ c2_all, float* __restrict__ sg_all) {
-    const int64_t n = (int64_t)n_steps * B;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const int i = n_steps - 1 - (int)(e / B);
-        t_all[e] = tmap[i]; c1_all[e] = c1[i]; c2_all[e] = c2[i]; sg_all[e] = sg[i];
-    }
-}
-
 // feat[r, 0:cd] = x[r, :]  (the noisy contact map is the leading block of the encoder input, cdm.py:167-171)
 __global__ __launch_bounds__(256) void pack_x_kernel(const float* __restrict__ x, float* __restrict__ feat, int64_t rows, int cd, int fd) {
     const int64_t n = rows * cd;
@@ -360,221 +346,213 @@ __global__ __launch_bounds__(256) void pack_x_kernel(const float* __restrict__ x
     }
 }
 
-constexpr int NOISE_STEPS = 16;               // steps of Philox noise generated per launch of the native loop (workspace: NOISE_STEPS x B x N x contact_dim floats)
+constexpr int MAX_SUB = 8;            // sub-batches (stream pairs) of one loop call
 
-inline void cdm_sub_range(int B, int nsub, int s, int* start, int* count) {
-    const int base = B / nsub, extra = B % nsub;
-    *start = s * base + (s < extra ? s : extra);
-    *count = base + (s < extra ? 1 : 0);
+// the arguments of the three loop entry points
+struct LoopCall {
+    const afm_cdm_weights* w;
+    float *x, *feat;
+    const float *text_q0, *text_u, *text_cu;
+    int N;
+    LoopArgs a;                       // (a.streams: a stream pair per sub-batch)
+};
+
+// sub-batch s runs on `stream` (streams[2s]) with `side` (streams[2s+1]) as the side stream of its decoder-adapter GEMM, of its latent chain
+// (AFM_CDM_CHAIN_SIDE, AFM_CDM_PIPELINE); n_sub <= 1: everything on the caller's stream, streams[0] = optional side stream
+struct SubBatch : SubRange {
+    hipStream_t side;
+    char* base;                       // the sub-batch's workspace: ws, then the noise
+    CdmWs ws;
+    float* noise;                     // NOISE_STEPS steps of noise, behind ws
+    // AFM_CDM_CHAIN_SIDE: one event pair per sub-batch, reused by every step (an event re-recorded on a stream orders behind the waits
+    // already enqueued on its previous record)
+    CdmChainSide chain;
+    hipEvent_t enc_done, tables_done; // AFM_CDM_PIPELINE: enc_point -> [enc_done] -> chain + tables -> [tables_done] -> dec_point
+};
+
+// carves the workspace of a sub-batch whose range is set at `base` (NULL: sizes only); -> its bytes
+int64_t carve_sub(const afm_cdm_weights& w, int N, char* base, SubBatch* sb) {
+    sb->base = base;
+    sb->ws = carve(w, sb->count, N, base, cdm_mode(w) != 3);
+    sb->noise = base ? (float*)(base + sb->ws.bytes) : nullptr;
+    return sb->ws.bytes + align256((int64_t)NOISE_STEPS * sb->count * N * w.contact_dim * 4);
+}
+
+// what a loop call fixes before its first launch
+struct LoopPlan {
+    afm_cdm_weights w;                // the loop's own pack: the update selectors are library-private flag bits
+    int nsub;                         // 0: an empty batch, nothing to enqueue
+    SubBatch sb[MAX_SUB];
+    bool rowless, folded, chain_side, pipe;
+    int64_t per;                      // values per sample
+};
+
+int plan_loop(const LoopCall& c, LoopPlan* p) {
+    const LoopArgs& a = c.a;
+    AFM_TRY(validate(c.w, a.B, c.N));
+    if (!c.x || !c.feat || !c.text_q0 || !c.text_u || !c.text_cu || !a.ok()) return AFM_E_BADARG;
+    p->nsub = 0;
+    if (a.B == 0) return 0;
+    p->w = *c.w;
+    p->w.flags = a.loop_flags(p->w.flags);
+    p->nsub = sub_count(a.B, a.n_streams, MAX_SUB);
+    int64_t off = 0;
+    for (int s = 0; s < p->nsub; ++s) {
+        SubBatch& sb = p->sb[s];
+        sb = {};
+        sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
+        off += carve_sub(p->w, c.N, (char*)a.workspace + off, &sb);
+        if (p->nsub > 1) { sb.stream = (hipStream_t)a.streams[2 * s]; sb.side = (hipStream_t)a.streams[2 * s + 1]; }
+        else { sb.stream = (hipStream_t)a.stream; sb.side = a.streams ? (hipStream_t)a.streams[0] : nullptr; }
+    }
+    if (off > a.workspace_bytes) return AFM_E_WORKSPACE;
+    p->rowless = cdm_mode(p->w) == 3;
+    // folded form: the step-invariant parts of the two adapters are computed once for the whole range of steps and x_t is read where
+    // it is needed - no per-step rewrite of the input block, no adapter GEMMs inside the loop
+    p->folded = cdm_folded(p->w);
+    p->chain_side = p->rowless && p->nsub > 1 && (p->w.flags & AFM_CDM_CHAIN_SIDE);
+    p->pipe = p->rowless && p->nsub > 1 && (p->w.flags & AFM_CDM_PIPELINE) && !p->chain_side;
+    p->per = (int64_t)c.N * p->w.contact_dim;
+    return 0;
+}
+
+struct Loop {
+    const LoopCall& c;
+    LoopPlan p;
+    Schedule sched;
+};
+
+inline float* sub_x(const Loop& l, const SubBatch& sb) { return l.c.x + (int64_t)sb.start * l.p.per; }
+inline float* sub_feat(const Loop& l, const SubBatch& sb) { return l.c.feat + (int64_t)sb.start * l.c.N * l.p.w.feat_dim; }
+
+// the events of a loop call, all owned by `ev`: the fork of the sub-batch streams, the chain-side pairs, the pipeline's pairs
+int loop_events(Loop& l, Events& ev) {
+    LoopPlan& p = l.p;
+    hipEvent_t fork = nullptr;
+    if (p.nsub > 1) AFM_TRY(fork_streams(ev, (hipStream_t)l.c.a.stream, p.sb, p.nsub, &fork));
+    for (int s = 0; s < p.nsub; ++s) {
+        SubBatch& sb = p.sb[s];
+        if (p.chain_side) {
+            sb.chain.chain = sb.side;
+            AFM_TRY(ev.make(&sb.chain.forked));
+            AFM_TRY(ev.make(&sb.chain.joined));
+            (void)hipStreamWaitEvent(sb.side, fork, 0);
+        }
+        if (p.pipe) {
+            AFM_TRY(ev.make(&sb.enc_done));
+            AFM_TRY(ev.make(&sb.tables_done));
+        }
+    }
+    return 0;
+}
+
+// mode 1: the step-invariant tensors of every sub-batch, once per call (the generated form has nothing to prepare)
+int prepare_invariants(const Loop& l) {
+    for (int s = 0; cdm_mode(l.p.w) == 1 && s < l.p.nsub; ++s) {
+        const SubBatch& sb = l.p.sb[s];
+        if (sb.count > 0) AFM_TRY(cdm_prepare_invariants(l.p.w, sub_feat(l, sb), sb.count, l.c.N, sb.ws, sb.stream));
+    }
+    return 0;
+}
+
+// ---- AFM_CDM_PIPELINE (round 6; row-less form, sub-batches): the step of a sub-batch is heavy - chain - heavy: enc_point (fills the chip,
+// ~15 us per 32 samples), the 13-launch latent chain (~70 us of launch latency on a handful of CUs), dec_point (fills the chip, ~88 us).
+// Independent sub-batch streams fall into lockstep (a stream that is behind gets the chip to itself and catches up: both chains end up
+// under each other, profiles/r04_cdm_streams.jsonl).  Here the phase is FIXED by construction: the heavy kernels of ALL sub-batches run on
+// ONE stream - the caller's - in round-robin order - dec(s, j), enc(s, j + 1) for s = 0 .. nsub - 1 - and the chain of sub-batch s on its
+// own side stream (streams[2 s + 1]) between two events, so that the chain of one sub-batch always sits under the point kernels of the
+// others.  1 + nsub streams: the runtime has four hardware queues, and two streams on one queue do not overlap whatever the events say.
+// Per-sample arithmetic does not depend on the sub-batching: bit-identical.
+
+// noise (every NOISE_STEPS steps) and enc_point on the caller's stream H; the chain + decoder tables on the sub-batch's side stream
+int pipe_enc(const Loop& l, const SubBatch& sb, int j) {
+    if (sb.count == 0) return 0;
+    const LoopCall& c = l.c;
+    const afm_cdm_weights& w = l.p.w;
+    const hipStream_t H = (hipStream_t)c.a.stream;
+    const float* nz;
+    AFM_TRY(step_noise(c.a, l.p.per, sb, sb.noise, j, sub_x(l, sb), &H, &nz));
+    const int64_t* tj = l.sched.at(j, sb.start).t;
+    AFM_TRY(launch_enc_point(w, c.text_u + (int64_t)sb.start * w.enc_heads * w.dkv, c.text_cu + (int64_t)sb.start * w.enc_heads, tj, sb.count, c.N, sb.ws,
+                             sub_x(l, sb), sub_feat(l, sb), H));
+    if (hipEventRecord(sb.enc_done, H) != hipSuccess || hipStreamWaitEvent(sb.side, sb.enc_done, 0) != hipSuccess) return (int)hipGetLastError();
+    AFM_TRY(cdm_latent_chain(w, c.text_q0 + (int64_t)sb.start * w.dq, tj, sb.ws, sb.count, sb.side, true));
+    AFM_TRY(launch_dec_tables(w, sb.count, sb.ws, sb.side));
+    if (hipEventRecord(sb.tables_done, sb.side) != hipSuccess) return (int)hipGetLastError();
+    return 0;
+}
+
+// dec_point (+ the update, in place) on H once the sub-batch's tables are there
+int pipe_dec(const Loop& l, const SubBatch& sb, int j) {
+    if (sb.count == 0) return 0;
+    const hipStream_t H = (hipStream_t)l.c.a.stream;
+    if (hipStreamWaitEvent(H, sb.tables_done, 0) != hipSuccess) return (int)hipGetLastError();
+    const float* nz;
+    AFM_TRY(step_noise(l.c.a, l.p.per, sb, sb.noise, j, sub_x(l, sb), nullptr, &nz));
+    const afm_ddpm_args dd = ddpm_args(l.c.a, l.sched.at(j, sb.start), nz, sub_x(l, sb), sb, j);
+    return launch_dec_point(l.p.w, sb.count, l.c.N, sb.ws, sub_x(l, sb), sub_feat(l, sb), nullptr, &dd, H, false);
+}
+
+int pipelined_steps(const Loop& l) {
+    for (int s = 0; s < l.p.nsub; ++s) AFM_TRY(pipe_enc(l, l.p.sb[s], 0));
+    for (int j = 0; j < l.c.a.n_steps; ++j)
+        for (int s = 0; s < l.p.nsub; ++s) {
+            AFM_TRY(pipe_dec(l, l.p.sb[s], j));
+            if (j + 1 < l.c.a.n_steps) AFM_TRY(pipe_enc(l, l.p.sb[s], j + 1));
+        }
+    return 0;
+}
+
+// (sub-batch, step j) of every other form, on the sub-batch's streams
+int plain_step(const Loop& l, const SubBatch& sb, int j) {
+    const LoopCall& c = l.c;
+    const afm_cdm_weights& w = l.p.w;
+    float *xs = sub_x(l, sb), *fs = sub_feat(l, sb);
+    const int64_t rows = (int64_t)sb.count * c.N;
+    int64_t gx = (rows * w.contact_dim + 255) / 256; if (gx > 2048) gx = 2048;
+    if (!l.p.folded) hipLaunchKernelGGL(pack_x_kernel, dim3((unsigned)gx), dim3(256), 0, sb.stream, xs, fs, rows, w.contact_dim, w.feat_dim);
+    const float* nz;
+    AFM_TRY(step_noise(c.a, l.p.per, sb, sb.noise, j, xs, &sb.stream, &nz));
+    const StepRows r = l.sched.at(j, sb.start);
+    const afm_ddpm_args dd = ddpm_args(c.a, r, nz, xs, sb, j);
+    return cdm_forward_impl(&w, fs, xs, r.t, c.text_q0 + (int64_t)sb.start * w.dq, c.text_u + (int64_t)sb.start * w.enc_heads * w.dkv,
+                            c.text_cu + (int64_t)sb.start * w.enc_heads, nullptr, &dd, sb.count, c.N, sb.base, sb.ws.bytes, sb.side, sb.stream,
+                            l.p.folded, l.p.rowless, l.p.chain_side ? &sb.chain : nullptr);
+}
+
+// Whole p_sample_loop of the ADM (gaussian_diffusion.py:442-536) enqueued natively: x [B,N,contact_dim] holds x_T on entry and the
+// sample on exit; feat [B,N,feat_dim] holds the step-invariant columns (point features, xyz) - its leading contact_dim columns are
+// rewritten from x every step.
+// One loop body for both updates: `ddim` == NULL runs the DDPM update with c1 / c2 / sigma, otherwise the DDIM update with the rows
+// *ddim - in the same fused site of every sampling form, with the same launches per step.
+int cdm_sample_loop_impl(const LoopCall& c) {
+    Loop l{c, {}, {}};
+    AFM_TRY(plan_loop(c, &l.p));
+    if (l.p.nsub == 0) return 0;
+    AFM_TRY(l.sched.expand(c.a));
+    Events ev;                        // every return below releases what was created
+    AFM_TRY(loop_events(l, ev));
+    int rc = prepare_invariants(l);
+    if (rc == 0 && l.p.pipe) rc = pipelined_steps(l);
+    for (int j = 0; j < c.a.n_steps && rc == 0 && !l.p.pipe; ++j)
+        for (int s = 0; s < l.p.nsub && rc == 0; ++s)
+            if (l.p.sb[s].count > 0) rc = plain_step(l, l.p.sb[s], j);
+    if (l.p.nsub > 1) join_streams(ev, (hipStream_t)c.a.stream, l.p.sb, l.p.nsub);
+    return rc;
 }
 
 }  // namespace
 
 extern "C" int64_t afm_cdm_loop_workspace_bytes(const afm_cdm_weights* w, int32_t B, int32_t N, int32_t n_sub) {
     if (validate(w, B, N) != 0 || n_sub < 0) return AFM_E_BADARG;
-    int nsub = n_sub > 1 ? (n_sub < B ? n_sub : B) : 1;
-    if (nsub > 8) nsub = 8;
+    const int nsub = sub_count(B, n_sub, MAX_SUB);
     int64_t total = 0;
     for (int s = 0; s < nsub; ++s) {
-        int st, cnt;
-        cdm_sub_range(B, nsub, s, &st, &cnt);
-        total += carve(*w, cnt, N, nullptr, cdm_mode(*w) != 3).bytes + align256((int64_t)NOISE_STEPS * cnt * N * w->contact_dim * 4);
+        SubBatch sb = {};
+        sub_range(B, nsub, s, &sb.start, &sb.count);
+        total += carve_sub(*w, N, nullptr, &sb);
     }
     return total;
-}
-
-// Whole p_sample_loop of the ADM (gaussian_diffusion.py:442-536) enqueued natively: x [B,N,contact_dim] holds x_T on entry and the
-// sample on exit; feat [B,N,feat_dim] holds the step-invariant columns (point features, xyz) - its leading contact_dim columns are
-// rewritten from x every step.  Sub-batch s runs on streams[2s] with streams[2s+1] as the side stream of its decoder-adapter GEMM
-// (n_sub <= 1: everything on `stream`, streams[0] = optional side stream).
-// One loop body for both updates: `ddim` == NULL runs the DDPM update with d_c1 / d_c2 / d_sigma, otherwise the DDIM update with the rows
-// *ddim - in the same fused site of every sampling form, with the same launches per step.
-static int cdm_sample_loop_impl(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
-                                const float* text_cu, const float* step_noise, const int64_t* d_timestep_map, const float* d_c1,
-                                const float* d_c2, const float* d_sigma, const afm_ddim_rows* ddim, int32_t n_steps, int32_t first_step, uint64_t seed,
-                                int64_t sample_index0, int32_t B, int32_t N, void* sched_scratch, void* workspace, int64_t workspace_bytes,
-                                int32_t n_sub, void* const* streams, void* stream) {
-    AFM_TRY(validate(w, B, N));
-    const bool rows_ok = ddim ? (ddim->a && ddim->b && ddim->c && ddim->d) : (d_c1 && d_c2 && d_sigma);
-    if (!x || !feat || !text_q0 || !text_u || !text_cu || !d_timestep_map || !rows_ok || n_steps <= 0 || !sched_scratch ||
-        !workspace || n_sub < 0 || (n_sub > 1 && !streams))
-        return AFM_E_BADARG;
-    if (B == 0) return 0;
-    const bool noise_term = !ddim || ddim->sigma;          // eta = 0 DDIM rows: no noise is generated or read
-    afm_cdm_weights wl = *w;                               // the loop's own pack: the update selectors are library-private flag bits
-    wl.flags &= ~(AFM_PRIV_DDIM | AFM_PRIV_NO_NOISE);
-    if (ddim) wl.flags |= AFM_PRIV_DDIM | (noise_term ? 0 : AFM_PRIV_NO_NOISE);
-    w = &wl;
-    hipStream_t s0 = (hipStream_t)stream;
-    int nsub = n_sub > 1 ? (n_sub < B ? n_sub : B) : 1;
-    if (nsub > 8) nsub = 8;
-    const int cd = w->contact_dim, fd = w->feat_dim, He = w->enc_heads, dkv = w->dkv, dq = w->dq;
-
-    char* sp = (char*)sched_scratch;
-    const int64_t nb = (int64_t)n_steps * B;
-    int64_t* t_all = (int64_t*)sp; sp += align256(nb * 8);
-    float *c1_all, *c2_all, *sg_all;
-    if (ddim) {                                            // layout of afm_ddim_sched_scratch_bytes; c1 / c2 -> the {a, b, c, d} records
-        float4* rec_all = (float4*)sp; sp += align256(nb * 16);
-        sg_all = (float*)sp;
-        c1_all = (float*)rec_all; c2_all = c1_all;
-        AFM_TRY(afm_ddim_expand_rows(d_timestep_map, ddim, n_steps, B, t_all, rec_all, sg_all, s0));
-    } else {
-        c1_all = (float*)sp; sp += align256(nb * 4);
-        c2_all = (float*)sp; sp += align256(nb * 4);
-        sg_all = (float*)sp;
-        hipLaunchKernelGGL(cdm_expand_schedule_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s0, d_timestep_map, d_c1, d_c2, d_sigma, n_steps, B,
-                           t_all, c1_all, c2_all, sg_all);
-    }
-    const int rstride = ddim ? 4 : 1;                      // floats per row entry of c1_all / c2_all
-    AFM_CHECK_LAUNCH();
-
-    const bool rowless = cdm_mode(*w) == 3;
-    int start[8], count[8];
-    char* wsp[8];
-    int64_t wsb[8];
-    float* noise[8];
-    hipStream_t mainst[8], sidest[8];
-    {
-        char* base = (char*)workspace;
-        int64_t off = 0;
-        for (int s = 0; s < nsub; ++s) {
-            cdm_sub_range(B, nsub, s, &start[s], &count[s]);
-            wsb[s] = carve(*w, count[s], N, nullptr, !rowless).bytes;
-            wsp[s] = base + off; off += wsb[s];
-            noise[s] = (float*)(base + off); off += align256((int64_t)NOISE_STEPS * count[s] * N * cd * 4);
-            if (nsub > 1) { mainst[s] = (hipStream_t)streams[2 * s]; sidest[s] = (hipStream_t)streams[2 * s + 1]; }
-            else { mainst[s] = s0; sidest[s] = streams ? (hipStream_t)streams[0] : nullptr; }
-        }
-        if (off > workspace_bytes) return AFM_E_WORKSPACE;
-    }
-    hipEvent_t fork = nullptr;
-    if (nsub > 1) {
-        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-        (void)hipEventRecord(fork, s0);
-        for (int s = 0; s < nsub; ++s) (void)hipStreamWaitEvent(mainst[s], fork, 0);
-    }
-    // AFM_CDM_CHAIN_SIDE: the latent chain of sub-batch s on sidest[s] (one event pair per sub-batch, reused by every step: an event
-    // re-recorded on a stream orders behind the waits already enqueued on its previous record)
-    CdmChainSide side[8] = {};
-    const bool chain_side = rowless && nsub > 1 && (w->flags & AFM_CDM_CHAIN_SIDE);
-    for (int s = 0; chain_side && s < nsub; ++s) {
-        side[s].chain = sidest[s];
-        if (hipEventCreateWithFlags(&side[s].forked, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&side[s].joined, hipEventDisableTiming) != hipSuccess) {
-            const int rc_ev = (int)hipGetLastError();
-            for (int u = 0; u <= s; ++u) {                 // nothing created so far may leak (the first event of a failed pair did)
-                if (side[u].forked) (void)hipEventDestroy(side[u].forked);
-                if (side[u].joined) (void)hipEventDestroy(side[u].joined);
-            }
-            if (fork) (void)hipEventDestroy(fork);
-            return rc_ev;
-        }
-        (void)hipStreamWaitEvent(sidest[s], fork, 0);
-    }
-    const int64_t per = (int64_t)N * cd;
-    int rc = 0;
-    // folded form: the step-invariant parts of the two adapters are computed once for the whole range of steps and x_t is read where
-    // it is needed - no per-step rewrite of the input block, no adapter GEMMs inside the loop
-    const bool folded = cdm_folded(*w);
-    if (cdm_mode(*w) == 1) {                   // (the generated form has nothing to prepare)
-        for (int s = 0; s < nsub && rc == 0; ++s) {
-            if (count[s] == 0) continue;
-            rc = cdm_prepare_invariants(*w, feat + (int64_t)start[s] * N * fd, count[s], N, carve(*w, count[s], N, wsp[s]), mainst[s]);
-        }
-    }
-    // ---- AFM_CDM_PIPELINE (round 6; row-less form, sub-batches): the step of a sub-batch is heavy - chain - heavy: enc_point (fills the chip,
-    // ~15 us per 32 samples), the 13-launch latent chain (~70 us of launch latency on a handful of CUs), dec_point (fills the chip, ~88 us).
-    // Independent sub-batch streams fall into lockstep (a stream that is behind gets the chip to itself and catches up: both chains end up
-    // under each other, profiles/r04_cdm_streams.jsonl).  Here the phase is FIXED by construction: the heavy kernels of ALL sub-batches run on
-    // ONE stream - the caller's - in round-robin order - dec(s, j), enc(s, j + 1) for s = 0 .. nsub - 1 - and the chain of sub-batch s on its
-    // own side stream (streams[2 s + 1]) between two events, so that the chain of one sub-batch always sits under the point kernels of the
-    // others.  1 + nsub streams: the runtime has four hardware queues, and two streams on one queue do not overlap whatever the events say.
-    // Per-sample arithmetic does not depend on the sub-batching: bit-identical.
-    const bool pipe = rowless && nsub > 1 && (w->flags & AFM_CDM_PIPELINE) && !chain_side;
-    if (pipe) {
-        hipStream_t H = s0;
-        hipEvent_t e1[8] = {}, e2[8] = {};
-        CdmWs wss[8];
-        for (int s = 0; s < nsub && rc == 0; ++s) {
-            wss[s] = carve(*w, count[s], N, wsp[s], false);
-            if (hipEventCreateWithFlags(&e1[s], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e2[s], hipEventDisableTiming) != hipSuccess)
-                rc = (int)hipGetLastError();
-        }
-        auto part1 = [&](int s, int j) -> int {           // noise (every NOISE_STEPS steps), enc_point on H; the chain + decoder tables on the sub-batch's side stream
-            if (count[s] == 0) return 0;
-            if (noise_term && !step_noise && j % NOISE_STEPS == 0)
-                AFM_TRY(afm_randn_steps(noise[s], count[s], per, seed, sample_index0 + start[s], first_step + j, n_steps - j < NOISE_STEPS ? n_steps - j : NOISE_STEPS, H));
-            const int64_t* tj = t_all + (int64_t)j * B + start[s];
-            AFM_TRY(launch_enc_point(*w, text_u + (int64_t)start[s] * He * dkv, text_cu + (int64_t)start[s] * He, tj, count[s], N, wss[s],
-                                     x + (int64_t)start[s] * per, feat + (int64_t)start[s] * N * fd, H));
-            if (hipEventRecord(e1[s], H) != hipSuccess || hipStreamWaitEvent(sidest[s], e1[s], 0) != hipSuccess) return (int)hipGetLastError();
-            AFM_TRY(cdm_latent_chain(*w, text_q0 + (int64_t)start[s] * dq, tj, wss[s], count[s], sidest[s], true));
-            AFM_TRY(launch_dec_tables(*w, count[s], wss[s], sidest[s]));
-            if (hipEventRecord(e2[s], sidest[s]) != hipSuccess) return (int)hipGetLastError();
-            return 0;
-        };
-        auto part2 = [&](int s, int j) -> int {           // dec_point (+ DDPM update, in place) on H once the sub-batch's tables are there
-            if (count[s] == 0) return 0;
-            if (hipStreamWaitEvent(H, e2[s], 0) != hipSuccess) return (int)hipGetLastError();
-            afm_ddpm_args dd = {};
-            float* xs = x + (int64_t)start[s] * per;
-            dd.noise = !noise_term ? xs : step_noise ? step_noise + ((int64_t)j * B + start[s]) * per : noise[s] + (int64_t)(j % NOISE_STEPS) * count[s] * per;
-            dd.x_next = xs;
-            dd.c1 = c1_all + ((int64_t)j * B + start[s]) * rstride; dd.c2 = c2_all + ((int64_t)j * B + start[s]) * rstride; dd.sigma = sg_all + (int64_t)j * B + start[s];
-            dd.seed = seed; dd.sample_index0 = sample_index0 + start[s]; dd.step = first_step + j;
-            return launch_dec_point(*w, count[s], N, wss[s], xs, feat + (int64_t)start[s] * N * fd, nullptr, &dd, H, false);
-        };
-        for (int s = 0; s < nsub && rc == 0; ++s) rc = part1(s, 0);
-        for (int j = 0; j < n_steps && rc == 0; ++j)
-            for (int s = 0; s < nsub && rc == 0; ++s) {
-                rc = part2(s, j);
-                if (rc == 0 && j + 1 < n_steps) rc = part1(s, j + 1);
-            }
-        for (int s = 0; s < nsub; ++s) {
-            if (e1[s]) (void)hipEventDestroy(e1[s]);
-            if (e2[s]) (void)hipEventDestroy(e2[s]);
-        }
-    }
-    for (int j = 0; j < n_steps && rc == 0 && !pipe; ++j) {
-        for (int s = 0; s < nsub && rc == 0; ++s) {
-            if (count[s] == 0) continue;
-            float* xs = x + (int64_t)start[s] * per;
-            float* fs = feat + (int64_t)start[s] * N * fd;
-            const int64_t rows = (int64_t)count[s] * N;
-            int64_t gx = (rows * cd + 255) / 256; if (gx > 2048) gx = 2048;
-            if (!folded) hipLaunchKernelGGL(pack_x_kernel, dim3((unsigned)gx), dim3(256), 0, mainst[s], xs, fs, rows, cd, fd);
-            afm_ddpm_args dd = {};
-            if (!noise_term) dd.noise = xs;               // (never read: AFM_UPD_NO_NOISE)
-            else if (step_noise) dd.noise = step_noise + ((int64_t)j * B + start[s]) * per;
-            else {
-                if (j % NOISE_STEPS == 0) {               // the noise of the next NOISE_STEPS steps in one launch (6 us of launch per step otherwise)
-                    rc = afm_randn_steps(noise[s], count[s], per, seed, sample_index0 + start[s], first_step + j, n_steps - j < NOISE_STEPS ? n_steps - j : NOISE_STEPS, mainst[s]);
-                    if (rc) break;
-                }
-                dd.noise = noise[s] + (int64_t)(j % NOISE_STEPS) * count[s] * per;
-            }
-            dd.x_next = xs;                               // in place: each element is read then written by the same lane
-            dd.c1 = c1_all + ((int64_t)j * B + start[s]) * rstride; dd.c2 = c2_all + ((int64_t)j * B + start[s]) * rstride; dd.sigma = sg_all + (int64_t)j * B + start[s];
-            dd.seed = seed; dd.sample_index0 = sample_index0 + start[s]; dd.step = first_step + j;
-            rc = cdm_forward_impl(w, fs, xs, t_all + (int64_t)j * B + start[s], text_q0 + (int64_t)start[s] * dq,
-                                  text_u + (int64_t)start[s] * He * dkv, text_cu + (int64_t)start[s] * He, nullptr, &dd, count[s], N, wsp[s], wsb[s],
-                                  sidest[s], mainst[s], folded, rowless, chain_side ? &side[s] : nullptr);
-        }
-    }
-    if (nsub > 1) {
-        for (int s = 0; s < nsub; ++s) {
-            hipEvent_t done;
-            if (hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess) {
-                (void)hipEventRecord(done, mainst[s]);
-                (void)hipStreamWaitEvent(s0, done, 0);
-                (void)hipEventDestroy(done);
-            }
-        }
-        (void)hipEventDestroy(fork);
-    }
-    for (int s = 0; chain_side && s < nsub; ++s) { (void)hipEventDestroy(side[s].forked); (void)hipEventDestroy(side[s].joined); }
-    return rc;
 }
 
 extern "C" int afm_cdm_sample_loop(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
@@ -582,8 +560,8 @@ extern "C" int afm_cdm_sample_loop(const afm_cdm_weights* w, float* x, float* fe
                                    const float* d_c2, const float* d_sigma, int32_t n_steps, uint64_t seed, int64_t sample_index0, int32_t B,
                                    int32_t N, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams,
                                    void* stream) {
-    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, 0, seed,
-                                sample_index0, B, N, sched_scratch, workspace, workspace_bytes, n_sub, streams, stream);
+    return cdm_sample_loop_impl({w, x, feat, text_q0, text_u, text_cu, N, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, 0, seed, sample_index0, B,
+                                 sched_scratch, workspace, workspace_bytes, n_sub, streams, stream}});
 }
 
 extern "C" int afm_cdm_sample_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
@@ -592,8 +570,8 @@ extern "C" int afm_cdm_sample_loop_range(const afm_cdm_weights* w, float* x, flo
                                          int64_t sample_index0, int32_t B, int32_t N, void* sched_scratch, void* workspace,
                                          int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream) {
     if (first_step < 0) return AFM_E_BADARG;
-    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step,
-                                seed, sample_index0, B, N, sched_scratch, workspace, workspace_bytes, n_sub, streams, stream);
+    return cdm_sample_loop_impl({w, x, feat, text_q0, text_u, text_cu, N, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step, seed, sample_index0, B,
+                                 sched_scratch, workspace, workspace_bytes, n_sub, streams, stream}});
 }
 
 extern "C" int afm_cdm_ddim_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
@@ -601,6 +579,6 @@ extern "C" int afm_cdm_ddim_loop_range(const afm_cdm_weights* w, float* x, float
                                        int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t N,
                                        void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream) {
     if (first_step < 0 || !rows) return AFM_E_BADARG;
-    return cdm_sample_loop_impl(w, x, feat, text_q0, text_u, text_cu, step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step,
-                                seed, sample_index0, B, N, sched_scratch, workspace, workspace_bytes, n_sub, streams, stream);
+    return cdm_sample_loop_impl({w, x, feat, text_q0, text_u, text_cu, N, {step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, seed, sample_index0, B,
+                                 sched_scratch, workspace, workspace_bytes, n_sub, streams, stream}});
 }

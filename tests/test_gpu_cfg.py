@@ -278,6 +278,63 @@ def test_two_stage_sample_with_and_without_guidance(cmdm, cdm):
         assert any("cfg_update_kernel" in n for n in names) or not names
 
 
+# ---------------------------------------------------------------------------------------------------------------- argument errors
+class _LoopArgumentProbe:
+    """The loaded library with its loop entry points wrapped: in front of every real call of one, the same call with a workspace one byte
+    too small (AFM_E_WORKSPACE = -2) and with a NULL timestep map (AFM_E_BADARG = -1).  Both return before anything is enqueued.  The two
+    entry points without `first_step` get the same pair of calls with the arguments of their `_range` form."""
+    TMAP = {"afm_cmdm": 5, "afm_cdm_": 7}            # position of d_timestep_map; workspace_bytes is the fourth argument from the end
+    FIRST_STEP = {"afm_cmdm_sample_loop_range": 10, "afm_cdm_sample_loop_range": 12}
+
+    def __init__(self, lib):
+        self.lib, self.seen = lib, set()
+
+    def _errors(self, name, args):
+        small, no_map = list(args), list(args)
+        small[-4] -= 1
+        no_map[self.TMAP[name[:8]]] = None
+        assert getattr(self.lib, name)(*small) == -2, name
+        assert getattr(self.lib, name)(*no_map) == -1, name
+        self.seen.add(name)
+
+    def __getattr__(self, name):
+        fn = getattr(self.lib, name)
+        if "loop_range" not in name:
+            return fn
+
+        def call(*args):
+            self._errors(name, args)
+            if name in self.FIRST_STEP:
+                i = self.FIRST_STEP[name]
+                self._errors(name[:-len("_range")], args[:i] + args[i + 1:])
+            return fn(*args)
+        return call
+
+
+def test_loop_argument_errors_leave_the_next_call_untouched(cmdm, cdm, monkeypatch):
+    """Every loop entry point: a workspace one byte short -> AFM_E_WORKSPACE, a NULL schedule pointer -> AFM_E_BADARG, and the correct
+    call behind them on the same process gives the result of a call without them, bit for bit."""
+    from afm import ffi
+    g = golden("cmdm_forward_N1024_L16")
+    d5 = create_gaussian_diffusion(cmdm_cfg(steps=1000, respacing="5"))
+    dc = create_gaussian_diffusion(cdm_cfg(steps=500, respacing="3"))
+    ckw = dict(c_text_feat=synth.text_feature(2).to(dev()), c_pc_xyz=synth.scene_cloud(2, 1024, seed=14).to(dev()))
+    guided = GuidedCMDM(cmdm, _scale())
+    runs = (lambda: d5.p_sample_loop(cmdm, SHAPE, clip_denoised=False, model_kwargs=_kw(g), seed=4),
+            lambda: d5.ddim_sample_loop(cmdm, SHAPE, clip_denoised=False, model_kwargs=_kw(g), eta=1.0, seed=4),
+            lambda: d5.p_sample_loop(guided, SHAPE, clip_denoised=False, model_kwargs=_kw(g), seed=4),
+            lambda: d5.ddim_sample_loop(guided, SHAPE, clip_denoised=False, model_kwargs=_kw(g), eta=1.0, seed=4),
+            lambda: dc.p_sample_loop(cdm, (2, 1024, 6), clip_denoised=False, model_kwargs=ckw, seed=4),
+            lambda: dc.ddim_sample_loop(cdm, (2, 1024, 6), clip_denoised=False, model_kwargs=ckw, eta=1.0, seed=4))
+    want = [run().clone() for run in runs]
+    probe = _LoopArgumentProbe(ffi.load())
+    monkeypatch.setattr(ffi, "load", lambda: probe)
+    got = [run().clone() for run in runs]
+    assert probe.seen == {"afm_cmdm_sample_loop", "afm_cmdm_sample_loop_range", "afm_cmdm_ddim_loop_range", "afm_cmdm_cfg_sample_loop_range",
+                          "afm_cmdm_cfg_ddim_loop_range", "afm_cdm_sample_loop", "afm_cdm_sample_loop_range", "afm_cdm_ddim_loop_range"}
+    assert all(torch.equal(a, b) for a, b in zip(want, got))
+
+
 # ---------------------------------------------------------------------------------------------------------------- full size
 @pytest.fixture(scope="module")
 def full():
