@@ -155,7 +155,7 @@ def interpolation(xyz, new_xyz, feat, offset, new_offset, k: int = 3):
     idx, d2 = po.knn_query(k, xyz, new_xyz, offset, new_offset)
     dist_recip = 1.0 / (torch.sqrt(d2) + 1e-8)
     weight = dist_recip / dist_recip.sum(dim=1, keepdim=True)
-    out = torch.zeros(new_xyz.shape[0], feat.shape[1])
+    out = torch.zeros(new_xyz.shape[0], feat.shape[1], dtype=feat.dtype)      # (float32 kNN distances into float64 features: the double runs)
     for i in range(k):
         out += feat[idx[:, i].long(), :] * weight[:, i].unsqueeze(-1)
     return out

@@ -2,7 +2,10 @@
 expression, the product's own forms against each other (bit for bit), the reference goldens of tools/make_goldens_cfg.py and the oracle.
 
 Bounds against the reference: at most 20x the error measured on the MI355X (in the comment beside each), and never above the bound of the
-matching unguided test times AMP = |s| + |1 - s| = 14 for the largest scale, 7.5."""
+matching unguided test times AMP = |s| + |1 - s| = 14 for the largest scale, 7.5.  Beside every report() against a reference golden or an
+oracle loop stands report_f32_class (tests/gpu_util.py): the HIP error against the float64 twin of the guided oracle
+(tests/test_cfg_host.py::guided_oracle on float64 weights and inputs) is at most 4 x the float32 reference's own error against that
+twin, plus one float32 ulp of the largest output - the guidance amplifies both sides alike."""
 import pytest
 import torch
 
@@ -11,7 +14,8 @@ from afm.base import create_gaussian_diffusion, create_model
 from afm.cmdm import GuidedCMDM
 from afm.pipeline import two_stage_sample
 from conftest import golden
-from gpu_util import dev, load_named_weights, report
+from gpu_util import dev, load_named_weights, report, report_f32_class, to_f64, write_parity_table
+from test_cfg_host import guided_oracle
 from test_gpu_cdm import cdm_cfg
 from test_gpu_cmdm import _kw, cmdm_cfg
 from test_gpu_no_eager_math import _check, _device_kernel_names
@@ -95,6 +99,20 @@ def test_combine_and_guided_update_kernels_equal_the_cpu_expression(clip):
 
 
 # ---------------------------------------------------------------------------------------------------------------- reference goldens
+def _twin():
+    """Float64 state dict and conditions of the goldens' case, for guided_oracle and the oracle's branches."""
+    from oracle import shapes as sh
+    return to_f64(sh.weights(sh.cmdm())), to_f64(golden("cmdm_forward_N1024_L16"))
+
+
+def _branches64(sd64, g64, x, t, drop):
+    from oracle import denoiser_ref as dr
+    ones = torch.ones(x.shape[0], 1, dtype=torch.bool)
+    sw = {f"c_{k}_mask": ones for k in drop}
+    base = dict(x_mask=g64["x_mask"], cont_emb=g64["cont_emb"])
+    return dr.cmdm_forward(sd64, x, t, g64["text_feat"], **base), dr.cmdm_forward(sd64, x, t, g64["text_feat"], **base, **sw)
+
+
 @pytest.mark.parametrize("tt", [999, 500, 0])
 def test_guided_forward_vs_reference_golden(cmdm, tt):
     g = golden("cmdm_forward_N1024_L16")
@@ -110,9 +128,16 @@ def test_guided_forward_vs_reference_golden(cmdm, tt):
         report(f"guided forward t={tt} drop={k}: x0_c", c, gg["x0_c"], TOL_FWD_BRANCH)
         report(f"guided forward t={tt} drop={k}: x0_u", u, gg["x0_u"], TOL_FWD_BRANCH)
         report(f"guided forward t={tt} drop={k}: guided", gd, gg["guided"], TOL_FWD_GUIDED)
+        sd64, g64 = _twin()
+        c64, u64 = _branches64(sd64, g64, g64["x"], t.cpu(), drop)
+        gd64 = guided_oracle(sd64, g64, _scale().cpu().double(), drop)(g64["x"], t.cpu())
+        report_f32_class(f"guided forward t={tt} drop={k}: x0_c", c, gg["x0_c"], c64, TOL_FWD_BRANCH)
+        report_f32_class(f"guided forward t={tt} drop={k}: x0_u", u, gg["x0_u"], u64, TOL_FWD_BRANCH)
+        report_f32_class(f"guided forward t={tt} drop={k}: guided", gd, gg["guided"], gd64, TOL_FWD_GUIDED)
         if k == "both":                                       # the masked full-length form of the same branch
             um = GuidedCMDM(cmdm, _scale(), drop, force_masked=True).branches(g["x"].to(dev()), t, **_kw(g))[1]
             report(f"guided forward t={tt}: x0_u, masked form", um, gg["x0_u"], TOL_FWD_BRANCH)
+            report_f32_class(f"guided forward t={tt}: x0_u, masked form", um, gg["x0_u"], u64, TOL_FWD_BRANCH)
             report(f"guided forward t={tt}: compact vs masked form", u, um, TOL_FWD_FORMS)
 
 
@@ -123,6 +148,12 @@ def test_guided_p_sample_vs_reference_golden(cmdm):
                      model_kwargs=_kw(g), noise=synth.gaussian("p_sample_noise_500", SHAPE).to(dev()))
     report("guided p_sample t=500 pred_xstart", out["pred_xstart"], gs["pred_xstart"], TOL_FWD_GUIDED)
     report("guided p_sample t=500 sample", out["sample"], gs["sample"], TOL_PSAMPLE)
+    from oracle import diffusion_ref as df
+    sd64, g64 = _twin()
+    w64 = df.p_sample(df.Schedule(1000), guided_oracle(sd64, g64, _scale().cpu().double(), DROPS["both"]), g64["x"], torch.tensor([500, 500]),
+                      synth.gaussian("p_sample_noise_500", SHAPE).double())
+    report_f32_class("guided p_sample t=500 pred_xstart", out["pred_xstart"], gs["pred_xstart"], w64["pred_xstart"], TOL_FWD_GUIDED)
+    report_f32_class("guided p_sample t=500 sample", out["sample"], gs["sample"], w64["sample"], TOL_PSAMPLE)
 
 
 @pytest.mark.parametrize("tag,drop,clip", [("r5", "both", False), ("r5_clip", "both", True), ("r5_text", "text", False)])
@@ -133,6 +164,11 @@ def test_guided_ddpm_loop_vs_reference_golden(cmdm, tag, drop, clip):
     w = GuidedCMDM(cmdm, _scale(), DROPS[drop])
     native = d.p_sample_loop(w, SHAPE, noise=xT, clip_denoised=clip, model_kwargs=_kw(g), step_noise=nz)
     report(f"guided native DDPM loop {tag}", native, want, TOL_LOOP[tag])
+    from oracle import diffusion_ref as df
+    sd64, g64 = _twin()
+    want64 = df.p_sample_loop(df.Schedule(1000, "cosine", "5"), guided_oracle(sd64, g64, _scale().cpu().double(), DROPS[drop]), xT.cpu().double(),
+                              list(nz.cpu().double()), clip_denoised=clip)
+    report_f32_class(f"guided native DDPM loop {tag}", native, want, want64, TOL_LOOP[tag])
     generic = _last(d.p_sample_loop_progressive(w, SHAPE, noise=xT, clip_denoised=clip, model_kwargs=_kw(g), step_noise=nz))
     assert torch.equal(native, generic)                       # the same kernels and forms compute the same bits
     assert torch.equal(native, d.p_sample_loop(w, SHAPE, noise=xT, clip_denoised=clip, model_kwargs=_kw(g), step_noise=nz, progress=True))
@@ -143,6 +179,7 @@ def test_guided_ddpm_loop_vs_reference_golden(cmdm, tag, drop, clip):
         wm = GuidedCMDM(cmdm, _scale(), DROPS[drop], force_masked=True)
         masked = d.p_sample_loop(wm, SHAPE, noise=xT, clip_denoised=clip, model_kwargs=_kw(g), step_noise=nz)
         report(f"guided native DDPM loop {tag}, masked form", masked, want, TOL_LOOP[tag])
+        report_f32_class(f"guided native DDPM loop {tag}, masked form", masked, want, want64, TOL_LOOP[tag])
         assert torch.equal(masked, _last(d.p_sample_loop_progressive(wm, SHAPE, noise=xT, clip_denoised=clip, model_kwargs=_kw(g), step_noise=nz)))
 
 
@@ -378,3 +415,16 @@ def test_full_size_guided_loop_vs_oracle(full):
     got = d.p_sample_loop(GuidedCMDM(model, _scale()), (B, L, 263), noise=xT.to(dev()), clip_denoised=False, step_noise=torch.stack(nz).to(dev()),
                           model_kwargs=dict(c_text_feat=text.to(dev()), c_cont_emb=cont.to(dev()), x_mask=mask.to(dev())))
     report("full-size 20-step guided loop vs oracle", got, want, TOL_FULL_LOOP)
+    sd64, s64, text64, cont64 = to_f64(sd), s.double(), text.double(), cont.double()
+
+    def guided64(x, t, **k):
+        c = dr.cmdm_forward(sd64, x, t, text64, x_mask=mask, cont_emb=cont64)
+        u = dr.cmdm_forward(sd64, x, t, text64, x_mask=mask, cont_emb=cont64, c_text_mask=ones, c_pc_mask=ones)
+        return u + s64 * (c - u)
+    want64 = df.p_sample_loop(df.Schedule(1000, "cosine", "20"), guided64, xT.double(), to_f64(nz))
+    report_f32_class("full-size 20-step guided loop vs oracle", got, want, want64, TOL_FULL_LOOP)
+
+
+def test_zz_write_parity_table():
+    """Not a check: stores the [parity-f32] figures measured so far (gpu_util.write_parity_table -> profiles/r07_parity_f32_class.json)."""
+    write_parity_table()
