@@ -207,14 +207,7 @@ class GaussianDiffusion:
             raise NotImplementedError("cond_fn guidance is unreachable from the reference's entry points")
         tab = self.tables(x.device)
         with torch.no_grad():
-            x0 = model(x, self._model_timesteps(t, tab), **(model_kwargs or {}))
-            if denoised_fn is not None:
-                x0 = denoised_fn(x0)
-            if clip_denoised:
-                # afm_clamp (HIP) on a PRIVATE copy: the denoiser (or denoised_fn) may hand back x itself, a view of it, a non-contiguous /
-                # non-f32 tensor, or a buffer it caches - `x0.clamp(-1, 1)` of the reference never mutates its input, so neither do we
-                # (one copy of [B, L, D] per step on the step-by-step path; the native loop clamps inside its fused DDPM epilogue)
-                x0 = ops.clamp_(ffi.f32c(x0).clone(), -1.0, 1.0)
+            x0 = self._pred_xstart(model, x, t, clip_denoised, denoised_fn, model_kwargs, tab)
             sample = ops.ddpm_step(x0, x, noise, tab.coef1[t], tab.coef2[t], tab.sigma[t], seed=seed,
                                    sample_index0=sample_index0, step=step)
         return {"sample": sample, "pred_xstart": x0}
@@ -224,6 +217,12 @@ class GaussianDiffusion:
                                   step_noise: Optional[Sequence[torch.Tensor]] = None, seed: Optional[int] = None,
                                   sample_index0: int = 0):
         """Generator over the T steps (reference gaussian_diffusion.py:488-536)."""
+        yield from self._progressive(self.p_sample, model, shape, noise, device, progress, step_noise, seed, sample_index0,
+                                     dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs))
+
+    def _progressive(self, step_fn, model, shape, noise, device, progress, step_noise, seed, sample_index0, step_kwargs):
+        """The loop of both progressive generators: x_T (``noise`` or Philox step -1), then ``step_fn`` (p_sample / ddim_sample) per
+        executed step j at timestep index T - 1 - j, each output yielded and its sample fed to the next step."""
         if device is None:
             device = next(model.parameters()).device
         seed = self._fresh_seed("_sample_calls") if seed is None else seed
@@ -234,9 +233,8 @@ class GaussianDiffusion:
             from tqdm.auto import tqdm
             steps = tqdm(list(steps))
         for j, i in enumerate(steps):
-            out = self.p_sample(model, img, tvec[i], clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                model_kwargs=model_kwargs, noise=None if step_noise is None else step_noise[j],
-                                seed=seed, sample_index0=sample_index0, step=j)
+            out = step_fn(model, img, tvec[i], noise=None if step_noise is None else step_noise[j], seed=seed,
+                          sample_index0=sample_index0, step=j, **step_kwargs)
             yield out
             img = out["sample"]
 
@@ -255,11 +253,14 @@ class GaussianDiffusion:
 
     # ------------------------------------------------------------------ DDIM
     def _pred_xstart(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, tab):
-        """p_mean_variance's pred_xstart for START_X models (gaussian_diffusion.py:289-294), as p_sample computes it."""
+        """p_mean_variance's pred_xstart for START_X models (gaussian_diffusion.py:289-294), for p_sample and the DDIM steps."""
         x0 = model(x, self._model_timesteps(t, tab), **(model_kwargs or {}))
         if denoised_fn is not None:
             x0 = denoised_fn(x0)
-        if clip_denoised:      # on a private copy (see p_sample)
+        if clip_denoised:
+            # afm_clamp (HIP) on a PRIVATE copy: the denoiser (or denoised_fn) may hand back x itself, a view of it, a non-contiguous /
+            # non-f32 tensor, or a buffer it caches - `x0.clamp(-1, 1)` of the reference never mutates its input, so neither do we
+            # (one copy of [B, L, D] per step on the step-by-step path; the native loop clamps inside its fused update)
             x0 = ops.clamp_(ffi.f32c(x0).clone(), -1.0, 1.0)
         return x0
 
@@ -293,22 +294,9 @@ class GaussianDiffusion:
                                      step_noise: Optional[Sequence[torch.Tensor]] = None, seed: Optional[int] = None,
                                      sample_index0: int = 0):
         """Generator over the DDIM steps (reference gaussian_diffusion.py:672-710); noise keyed as p_sample_loop_progressive."""
-        if device is None:
-            device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
-        seed = self._fresh_seed("_sample_calls") if seed is None else seed
-        img = noise if noise is not None else ops.randn(tuple(shape), device, seed=seed, sample_index0=sample_index0, step=-1)
-        tvec = self.tables(device).timesteps(shape[0])
-        steps: Iterable[int] = range(self.num_timesteps - 1, -1, -1)
-        if progress:
-            from tqdm.auto import tqdm
-            steps = tqdm(list(steps))
-        for j, i in enumerate(steps):
-            out = self.ddim_sample(model, img, tvec[i], clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                   model_kwargs=model_kwargs, eta=eta, noise=None if step_noise is None else step_noise[j],
-                                   seed=seed, sample_index0=sample_index0, step=j)
-            yield out
-            img = out["sample"]
+        yield from self._progressive(self.ddim_sample, model, shape, noise, device, progress, step_noise, seed, sample_index0,
+                                     dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta))
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, eta=0.0, *, step_noise=None, seed: Optional[int] = None, sample_index0: int = 0,

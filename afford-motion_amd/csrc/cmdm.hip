@@ -11,7 +11,7 @@
 //   +residual), LN, FFN1 GEMM(+bias+GELU), FFN2 GEMM(+bias+residual), LN } -> motion_layer GEMM
 //   (gather motion tokens, +bias, fused DDPM posterior update).
 // Classifier-free guided steps (afm_cmdm_cfg_*): this sequence twice - the conditioned branch, then the unconditioned one (struct Branch) -
-// with both motion_layer GEMMs storing pred_xstart, and one elementwise launch for the guided update (afm_cfg_update_rows).
+// with both motion_layer GEMMs storing pred_xstart, and one elementwise launch for the guided update (afm_sampling_update).
 #include <memory>
 
 #include "sample_loop.h"
@@ -19,10 +19,6 @@
 using namespace afm_loop;
 
 extern "C" int afm_linear(const afm_linear_args*, void*);
-// elementwise.hip: the guided update of a guided loop's step from the two branches' pred_xstart (see afm_cfg_update_rows)
-__attribute__((visibility("hidden"))) int afm_cfg_update_rows(const float* x0_c, const float* x0_u, const float* scale, float* x, const float* noise,
-                                                              const float4* rec, const float* c1, const float* c2, const float* s, int32_t B,
-                                                              int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
 extern "C" int afm_linear_pair(const afm_linear_args*, const afm_linear_args*, void*);
 extern "C" int afm_mha_fwd_grouped(const float*, const uint8_t*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, void*);
 extern "C" int afm_mha_fwd_rows(const float*, const uint8_t*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, void*);
@@ -310,7 +306,7 @@ int forward_impl(const afm_cmdm_weights& w, const float* x_t, const int64_t* t, 
         }
         a.a_grp = L; a.a_stride = T; a.a_off = 1 + w.n_cond;
         if (ddpm && (w.flags & AFM_PRIV_DDIM)) {
-            // native DDIM loop: pred_xstart goes to the loop workspace's own buffer; the loop's DDIM update launch (afm_ddim_update_rows)
+            // native DDIM loop: pred_xstart goes to the loop workspace's own buffer; the loop's update launch (afm_sampling_update)
             // then writes x_next and its K-padded copy.  The GEMM's epilogue is the one of the plain forward.
             if (!ws.x0) return AFM_E_BADARG;
             a.C = ws.x0; a.ldc = w.motion_dim;
@@ -429,7 +425,7 @@ extern "C" int64_t afm_ddim_sched_scratch_bytes(int32_t n_steps, int32_t B) {
 
 // ------------------------------------------------------------------------------------------------ native sampling loop
 // One driver for the four loops: DDPM (the ancestral update with the rows c1 / c2 / sigma, fused into the motion_layer epilogue) or DDIM
-// (`ddim` != NULL: motion_layer stores pred_xstart and ONE elementwise launch per sub-batch and step, afm_ddim_update_rows, applies the
+// (`ddim` != NULL: motion_layer stores pred_xstart and ONE elementwise launch per sub-batch and step, afm_sampling_update, applies the
 // update), each unguided or guided (`cfg` != NULL).  (The DDIM update fused into the shared GEMM epilogue grew the registers - and on three
 // variants the scratch - of DDPM GEMM kernels that every sampling step runs; a launch of its own leaves them as they were.)
 // plan_loop decides everything a call fixes before its first launch; the step functions enqueue one (sub-batch, step); sample_loop_impl
@@ -495,7 +491,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     AFM_TRY(validate(c.w, a.B, c.L));
     // Guided loop (cfg != NULL): per sub-batch and step the conditioned branch (this loop's step as it is, pred_xstart stored the DDIM
     // loop's way, for DDPM too), the unconditioned branch on a workspace of its own behind it on the same stream, and ONE update launch
-    // (afm_cfg_update_rows).  Both branches read the same x / K-padded copy; only the update writes them.
+    // (afm_sampling_update).  Both branches read the same x / K-padded copy; only the update writes them.
     p->br = {};
     if (c.cfg) AFM_TRY(uncond_setup(*c.w, c.cfg, c.frame_mask, &p->wu, &p->br));
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok()) return AFM_E_BADARG;
@@ -558,25 +554,27 @@ int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_d
                         c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr, nullptr, dd, sb.count, c.L, sb.ws, j == 0, sb.stream, rec);
 }
 
-// the DDIM update of a sub-batch from its stored pred_xstart (ws.x0), in place on x, with the K-padded copy the next step reads
-int ddim_update(const Loop& l, const SubBatch& sb, const StepRows& rows, const float* noise) {
+// the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and the unconditioned branch's, wsu.x0), in place on x, with the
+// K-padded copy the next step reads
+int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const float* noise) {
     const afm_cmdm_weights& w = l.p.w;
-    const bool nt = l.c.a.noise_term();
-    return afm_ddim_update_rows(sb.ws.x0, sub_x(l, sb), nt ? noise : nullptr, rows.rec, nt ? rows.sigma : nullptr, sb.count, l.p.row, w.motion_dim,
-                                (w.flags & AFM_CMDM_CLIP_X0) ? 1 : 0, sb.ws.xpad, w.motion_adapter_kpad, sb.stream);
+    Update u = loop_update(l.c.a, rows, sb.ws.x0, sub_x(l, sb), noise, l.p.row, w.flags & AFM_CMDM_CLIP_X0);
+    if (l.c.cfg) { u.x0_u = sb.wsu.x0; u.scale = l.c.cfg->scale + sb.start; }
+    u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
+    return afm_sampling_update(u, sb.count, sb.stream);
 }
 
 int unguided_step(const Loop& l, const SubBatch& sb, int j) {
     StepRows rows;
     afm_ddpm_args dd;
     AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
-    return l.c.a.ddim ? ddim_update(l, sb, rows, dd.noise) : 0;
+    return l.c.a.ddim ? update_launch(l, sb, rows, dd.noise) : 0;
 }
 
 int guided_step(const Loop& l, const SubBatch& sb, int j) {
     const LoopCall& c = l.c;
     const afm_cmdm_weights &w = l.p.w, &wu = l.p.wu;
-    const bool nt = c.a.noise_term(), bs = l.p.branch_streams;
+    const bool bs = l.p.branch_streams;
     StepRows rows;
     afm_ddpm_args dd;
     AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
@@ -595,9 +593,7 @@ int guided_step(const Loop& l, const SubBatch& sb, int j) {
         (void)hipStreamWaitEvent(sb.stream, sb.u_ready, 0);
     }
     AFM_TRY(rc);
-    AFM_TRY(afm_cfg_update_rows(sb.ws.x0, sb.wsu.x0, c.cfg->scale + sb.start, sub_x(l, sb), nt ? dd.noise : nullptr, rows.rec, rows.c1, rows.c2,
-                                nt ? rows.sigma : nullptr, sb.count, l.p.row, w.motion_dim, (w.flags & AFM_CMDM_CLIP_X0) ? 1 : 0, sb.ws.xpad,
-                                w.motion_adapter_kpad, sb.stream));
+    AFM_TRY(update_launch(l, sb, rows, dd.noise));
     if (bs) (void)hipEventRecord(sb.x_ready, sb.stream);       // x and its padded copy of the next step
     return 0;
 }
@@ -641,7 +637,7 @@ int paired_step(const Loop& l, int j, Recorder* recs, const hipEvent_t* pev) {
         AFM_TRY(cond_forward(l, l.p.sb[s], j, &rows[s], &dd[s], &recs[s]));
     }
     AFM_TRY(issue_paired(recs[0], recs[1], l.p.sb[0].stream, l.p.sb[1].stream, pev, NEV));
-    for (int s = 0; l.c.a.ddim && s < 2; ++s) AFM_TRY(ddim_update(l, l.p.sb[s], rows[s], dd[s].noise));
+    for (int s = 0; l.c.a.ddim && s < 2; ++s) AFM_TRY(update_launch(l, l.p.sb[s], rows[s], dd[s].noise));
     return 0;
 }
 

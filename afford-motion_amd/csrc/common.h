@@ -293,8 +293,8 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, int64_t sample, in
 
 // ---- DDIM update (ddim_sample / ddim_reverse_sample of gaussian_diffusion.py) of one element, the reference's float32 expression with every
 // operation rounded on its own:  eps = (a * x_t - x0) / b;  x_next = (x0 * c + d * eps) + s * noise.  r = {a, b, c, d} of the element's
-// sample (the per-step rows built by the host, afm_ddim_rows), s = (t != 0) * sigma.  Every DDIM site of the library (afm_ddim_step, the loops'
-// update launch, the CDM output kernels) calls this one helper: the same x0 gives the same bits in every form.
+// sample (the per-step rows built by the host, afm_ddim_rows), s = (t != 0) * sigma.  Every DDIM site of the library (the sampling update kernel of
+// afm_ddim_step and the loops, the CDM output kernels) calls this one helper: the same x0 gives the same bits in every form.
 __device__ __forceinline__ float ddim_update(float x0, float xt, const float4& r) {
 #pragma clang fp contract(off)
     const float ax = r.x * xt;
@@ -320,7 +320,10 @@ __device__ __forceinline__ float cfg_combine(float x0_c, float x0_u, float s) {
     const float m = s * df;
     return x0_u + m;
 }
-// the ancestral (DDPM) update of one element as ddpm_step_kernel and the GEMM epilogue write it: (c1 * x0 + c2 * x_t) + sigma * noise
+// the ancestral (DDPM) update of one element: (c1 * x0 + c2 * x_t) + sigma * noise, every operation rounded on its own (the reference's
+// float32 torch expression).  The sampling update kernel (afm_ddpm_step, the guided updates) calls this helper.  The fused DDPM updates of
+// the GEMM epilogue and the CDM output kernels spell the expression inline with contraction allowed ("Contraction at the fused
+// DDPM sites"): they are not this helper and may round differently.
 __device__ __forceinline__ float ddpm_update(float x0, float xt, float c1, float c2, float sg, float nz) {
 #pragma clang fp contract(off)
     const float m1 = c1 * x0;

@@ -1,9 +1,16 @@
-// LayerNorm, DDPM posterior update, Philox normal generator.
+// LayerNorm, the sampling update (DDPM, DDIM, guided), Philox normal generator.
 // All three are HBM/L2-streaming kernels: float4 accesses, one wave per LayerNorm row.
-#include "common.h"
 #include "profile.h"
+#include "sample_loop.h"
 
 namespace {
+
+// grid of a grid-stride elementwise launch over n items per (y, z) slice: 256-thread blocks, at most `cap` of them along x
+inline dim3 stream_grid(int64_t n, int64_t cap, int y = 1, int z = 1) {
+    const int64_t g = (n + 255) / 256;
+    return dim3((unsigned)(g < cap ? g : cap), (unsigned)y, (unsigned)z);
+}
+inline int64_t quads(int64_t per_sample) { return (per_sample + 3) >> 2; }
 
 // one wave per row; the row lives in registers (dim <= 64 * 4 * MAXV)
 template <int MAXV>
@@ -36,77 +43,43 @@ __global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __r
     for (int c = lane; c < dim; c += 64) yp[c] = (xp[c] - mean) * rstd * gamma[c] + beta[c];
 }
 
-// x_next = (c1*x0 + c2*x_t) + sigma*noise with every product and sum individually rounded
-// (bit-identical to the reference's float32 torch expression).
-__global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict__ x0, const float* __restrict__ xt,
-                                                        const float* __restrict__ noise, float* __restrict__ xn,
-                                                        const float* __restrict__ c1, const float* __restrict__ c2,
-                                                        const float* __restrict__ sigma, int64_t per_sample, uint64_t seed,
-                                                        int64_t sample0, int step) {
-#pragma clang fp contract(off)
+// The sampling update of sample_loop.h (afm_loop::Update), one quad of a sample per thread iteration: v = x0, or cfg_combine(x0, x0_u,
+// scale[b]) when guided, clamped if asked; then ddpm_update (rows c1 / c2 / sg per sample) or ddim_update (rows rec, or ra..rd, per sample;
+// sg == NULL: no noise term).  Every operation is one of common.h's individually rounded helpers (the reference's float32 torch expression,
+// bit for bit).  xn may alias xt (one thread reads then writes an element).  noise == NULL with a noise term: Philox keyed by the quad q.
+// xpad: x_next also into rows of ldpad floats (the next motion-adapter GEMM's K-padded A rows; columns >= cols stay zero).
+__global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Update p) {
     const int b = blockIdx.y;
-    const float a1 = c1[b], a2 = c2[b], sg = sigma[b];
-    const int64_t base = (int64_t)b * per_sample;
-    const int64_t nquad = (per_sample + 3) >> 2;
+    const float s = p.x0_u ? p.scale[b] : 0.f;
+    const float sg = p.sg ? p.sg[b] : 0.f;
+    float4 r = make_float4(0.f, 1.f, 0.f, 0.f);
+    float c1 = 0.f, c2 = 0.f;
+    if (p.ddim) r = p.rec ? p.rec[b] : make_float4(p.ra[b], p.rb[b], p.rc[b], p.rd[b]);
+    else { c1 = p.c1[b]; c2 = p.c2[b]; }
+    const int64_t base = (int64_t)b * p.per_sample;
+    const int64_t nquad = (p.per_sample + 3) >> 2;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
-        float z[4];
-        if (!noise) philox_normal4(seed, sample0 + b, step, (uint64_t)q, z);
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (p.sg && !p.noise) philox_normal4(p.seed, p.sample0 + b, p.step, (uint64_t)q, z);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int64_t i = q * 4 + e;
-            if (i < per_sample) {
-                const float nz = noise ? noise[base + i] : z[e];
-                const float m1 = a1 * x0[base + i];
-                const float m2 = a2 * xt[base + i];
-                const float mean = m1 + m2;
-                const float sn = sg * nz;
-                xn[base + i] = mean + sn;
+            if (i < p.per_sample) {
+                const int64_t g = base + i;
+                float v = p.x0[g];
+                if (p.x0_u) v = cfg_combine(v, p.x0_u[g], s);
+                if (p.clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised (NaN passes through, as torch.clamp)
+                const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
+                const float vt = p.xt[g];
+                float xn;
+                if (p.ddim) xn = p.sg ? ddim_update(v, vt, r, sg, nz) : ddim_update(v, vt, r);
+                else xn = ddpm_update(v, vt, c1, c2, sg, nz);
+                p.xn[g] = xn;
+                if (p.xpad) {
+                    const int64_t row = g / p.cols;
+                    p.xpad[row * p.ldpad + (g - row * p.cols)] = xn;
+                }
             }
-        }
-    }
-}
-
-// DDIM update (ddim_sample / ddim_reverse_sample): ddim_update of common.h per element; sg == NULL: no noise term
-__global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict__ x0, const float* xt, const float* __restrict__ noise,
-                                                        float* xn, const float* __restrict__ ra, const float* __restrict__ rb,
-                                                        const float* __restrict__ rc, const float* __restrict__ rd,
-                                                        const float* __restrict__ sg, int64_t per_sample, uint64_t seed, int64_t sample0, int step) {
-    const int b = blockIdx.y;
-    const float4 r = make_float4(ra[b], rb[b], rc[b], rd[b]);
-    const float s = sg ? sg[b] : 0.f;
-    const int64_t base = (int64_t)b * per_sample;
-    const int64_t nquad = (per_sample + 3) >> 2;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
-        float z[4];
-        if (sg && !noise) philox_normal4(seed, sample0 + b, step, (uint64_t)q, z);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t i = q * 4 + e;
-            if (i < per_sample) {
-                const float v0 = x0[base + i], vt = xt[base + i];
-                xn[base + i] = sg ? ddim_update(v0, vt, r, s, noise ? noise[base + i] : z[e]) : ddim_update(v0, vt, r);
-            }
-        }
-    }
-}
-
-// DDIM update of a native loop's step: x <- ddim_update(clamp?(x0), x, rec[b], s[b], noise) in place (one thread reads then writes an element),
-// plus the copy into the K-padded rows the next step's motion adapter reads (xpad [rows][ldpad], columns >= cols stay zero)
-__global__ __launch_bounds__(256) void ddim_update_rows_kernel(const float* __restrict__ x0, float* x, const float* __restrict__ noise,
-                                                               const float4* __restrict__ rec, const float* __restrict__ sg, int64_t per_sample,
-                                                               int cols, int clip, float* __restrict__ xpad, int64_t ldpad) {
-    const int b = blockIdx.y;
-    const float4 r = rec[b];
-    const float s = sg ? sg[b] : 0.f;
-    const int64_t base = (int64_t)b * per_sample;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * blockDim.x) {
-        float v = x0[base + i];
-        if (clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised (NaN passes through, as torch.clamp)
-        const float xn = sg ? ddim_update(v, x[base + i], r, s, noise[base + i]) : ddim_update(v, x[base + i], r);
-        x[base + i] = xn;
-        if (xpad) {
-            const int64_t g = base + i, row = g / cols;
-            xpad[row * ldpad + (g - row * cols)] = xn;
         }
     }
 }
@@ -201,8 +174,7 @@ __global__ void clamp_kernel(float* __restrict__ x, int64_t n, float lo, float h
 extern "C" int afm_clamp(float* x, int64_t n, float lo, float hi, void* stream) {
     if (n == 0) return 0;
     if (!x || n < 0 || !(lo <= hi)) return AFM_E_BADARG;
-    int64_t g = (n + 255) / 256; if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, n, lo, hi);
+    hipLaunchKernelGGL(clamp_kernel, stream_grid(n, 4096), dim3(256), 0, (hipStream_t)stream, x, n, lo, hi);
     AFM_CHECK_LAUNCH();
     return 0;
 }
@@ -219,8 +191,7 @@ extern "C" int afm_bn_fold(const float* w, const float* b, const float* mean, co
 extern "C" int afm_contact_glue(const float* sample, float* out, int64_t n, float sigma_sq, float mean, float std, void* stream) {
     if (n == 0) return 0;
     if (!sample || !out || n < 0 || !(sigma_sq > 0.0f)) return AFM_E_BADARG;
-    int64_t g = (n + 255) / 256; if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(contact_glue_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, sample, out, n, sigma_sq, mean, std);
+    hipLaunchKernelGGL(contact_glue_kernel, stream_grid(n, 4096), dim3(256), 0, (hipStream_t)stream, sample, out, n, sigma_sq, mean, std);
     AFM_CHECK_LAUNCH();
     return 0;
 }
@@ -254,7 +225,6 @@ extern "C" int afm_layernorm_rows(const float* x, const float* gamma, const floa
         AFM_CHECK_LAUNCH();
         return 0;
     }
-    if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const dim3 block(256), grid((unsigned)((rows + 3) / 4));
     AfmProf prof(AFM_PROF_LN, 8.0 * rows * dim, s);
@@ -267,44 +237,63 @@ extern "C" int afm_layernorm_rows(const float* x, const float* gamma, const floa
     return 0;
 }
 
+// ---- the sampling update: one launcher behind afm_ddpm_step, afm_ddim_step, afm_cfg_step and the update launch of the native loops
+namespace {
+int enqueue_update(const afm_loop::Update& p, int32_t B, hipStream_t s) {
+    hipLaunchKernelGGL(sampling_update_kernel, stream_grid(quads(p.per_sample), 1024, B), dim3(256), 0, s, p);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace
+
+__attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream) {
+    if (!p.x0 || !p.xt || !p.xn || !p.x0_u != !p.scale || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
+    if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && p.rd)) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
+    if (p.sg && !p.noise && !p.philox) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside their launch)
+    if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
+    if (B == 0) return 0;
+    if (!p.x0_u) return enqueue_update(p, B, (hipStream_t)stream);
+    AfmProf prof(AFM_PROF_MISC, 5.0 * B * p.per_sample, (hipStream_t)stream);          // (profiling records: the guided launches only)
+    return enqueue_update(p, B, (hipStream_t)stream);
+}
+
+namespace {
+// the update of a public single-step entry point: out of place, noise given or drawn in the kernel
+afm_loop::Update step_update(const float* x0, const float* x_t, const float* noise, float* x_next, int64_t per_sample, uint64_t seed,
+                             int64_t sample_index0, int32_t step) {
+    afm_loop::Update p = {};
+    p.x0 = x0; p.xt = x_t; p.noise = noise; p.xn = x_next; p.per_sample = per_sample;
+    p.philox = 1; p.seed = seed; p.sample0 = sample_index0; p.step = step;
+    return p;
+}
+void set_ddim_rows(afm_loop::Update* p, const afm_ddim_rows* r) {
+    p->ddim = 1; p->ra = r->a; p->rb = r->b; p->rc = r->c; p->rd = r->d; p->sg = r->sigma;
+}
+}  // namespace
+
 extern "C" int afm_ddpm_step(const float* x0, const float* x_t, const float* noise, float* x_next, const float* c1,
                              const float* c2, const float* sigma, int32_t B, int64_t per_sample, uint64_t seed,
                              int64_t sample_index0, int32_t step, void* stream) {
-    if (!x0 || !x_t || !x_next || !c1 || !c2 || !sigma || B < 0 || per_sample <= 0) return AFM_E_BADARG;
-    if (B == 0) return 0;
-    const int64_t nquad = (per_sample + 3) >> 2;
-    unsigned gx = (unsigned)((nquad + 255) / 256);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x_t, noise, x_next, c1, c2, sigma,
-                       per_sample, seed, sample_index0, step);
-    AFM_CHECK_LAUNCH();
-    return 0;
+    afm_loop::Update p = step_update(x0, x_t, noise, x_next, per_sample, seed, sample_index0, step);
+    p.c1 = c1; p.c2 = c2; p.sg = sigma;
+    return afm_sampling_update(p, B, stream);
 }
 
 extern "C" int afm_ddim_step(const float* x0, const float* x_t, const float* noise, float* x_next, const afm_ddim_rows* rows,
                              int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0, int32_t step, void* stream) {
-    if (!x0 || !x_t || !x_next || !rows || !rows->a || !rows->b || !rows->c || !rows->d || B < 0 || per_sample <= 0) return AFM_E_BADARG;
-    if (B == 0) return 0;
-    const int64_t nquad = (per_sample + 3) >> 2;
-    unsigned gx = (unsigned)((nquad + 255) / 256);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x_t, noise, x_next, rows->a, rows->b, rows->c,
-                       rows->d, rows->sigma, per_sample, seed, sample_index0, step);
-    AFM_CHECK_LAUNCH();
-    return 0;
+    if (!rows) return AFM_E_BADARG;
+    afm_loop::Update p = step_update(x0, x_t, noise, x_next, per_sample, seed, sample_index0, step);
+    set_ddim_rows(&p, rows);
+    return afm_sampling_update(p, B, stream);
 }
 
-// the DDIM update of a native loop's step (cmdm.hip, perceiver.hip): x0 [B][per_sample] pred_xstart, x [B][per_sample] x_t -> x_next in
-// place, rec [B] {a, b, c, d}, s [B] (NULL: no noise term, `noise` not read), rows of `cols` values copied to xpad (row stride ldpad) if given
-__attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, float* x, const float* noise, const float4* rec, const float* s, int32_t B,
-                                                               int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream) {
-    if (!x0 || !x || !rec || (s && !noise) || B < 0 || per_sample <= 0 || cols <= 0 || (xpad && ldpad < cols)) return AFM_E_BADARG;
-    if (B == 0) return 0;
-    unsigned gx = (unsigned)((per_sample + 255) / 256);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(ddim_update_rows_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x, noise, rec, s, per_sample, cols, clip, xpad, ldpad);
-    AFM_CHECK_LAUNCH();
-    return 0;
+extern "C" int afm_cfg_step(const afm_cfg_step_args* a, void* stream) {
+    if (!a || !a->x0_c || !a->x0_u || !a->scale) return AFM_E_BADARG;
+    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
+    p.x0_u = a->x0_u; p.scale = a->scale; p.clip = a->clip ? 1 : 0;
+    if (a->ddim) set_ddim_rows(&p, a->ddim);
+    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    return afm_sampling_update(p, a->B, stream);
 }
 
 // the DDPM rows of a native loop (sample_loop.h: Schedule), per step and sample: row j <-> spaced timestep i = n_steps - 1 - j
@@ -355,27 +344,17 @@ __attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tm
 __attribute__((visibility("hidden"))) int afm_randn_steps(float* out, int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0, int32_t step0, int32_t nsteps, void* stream) {
     if (!out || B < 0 || per_sample <= 0 || nsteps < 0 || nsteps > 65535) return AFM_E_BADARG;
     if (B == 0 || nsteps == 0) return 0;
-    const int64_t nquad = (per_sample + 3) >> 2;
-    unsigned gx = (unsigned)((nquad + 255) / 256);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(randn_kernel, dim3(gx, B, nsteps), dim3(256), 0, (hipStream_t)stream, out, per_sample, seed, sample_index0, step0);
+    hipLaunchKernelGGL(randn_kernel, stream_grid(quads(per_sample), 1024, B, nsteps), dim3(256), 0, (hipStream_t)stream, out, per_sample, seed, sample_index0, step0);
     AFM_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int afm_randn(float* out, int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0, int32_t step,
                          void* stream) {
-    if (!out || B < 0 || per_sample <= 0) return AFM_E_BADARG;
-    if (B == 0) return 0;
-    const int64_t nquad = (per_sample + 3) >> 2;
-    unsigned gx = (unsigned)((nquad + 255) / 256);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(randn_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, out, per_sample, seed, sample_index0, step);
-    AFM_CHECK_LAUNCH();
-    return 0;
+    return afm_randn_steps(out, B, per_sample, seed, sample_index0, step, 1, stream);
 }
 
-// ---- classifier-free guidance (afm_cfg_combine, afm_cfg_step, the guided native loops of cmdm.hip)
+// ---- classifier-free guidance of an x0 alone (the guided updates are the sampling update above)
 namespace {
 
 // x0_guided = cfg_combine(x0_c, x0_u, scale[b]) per element
@@ -388,105 +367,13 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restric
         out[base + i] = cfg_combine(x0c[base + i], x0u[base + i], s);
 }
 
-// The guided sampling update, the guided sibling of ddim_update_rows_kernel: x0 = cfg_combine(x0_c, x0_u, scale[b]), clamped if asked,
-// then ddpm_update (ddim == 0; rows c1 / c2 / sg per sample) or ddim_update (rows rec, or ra..rd, per sample; sg == NULL: no noise term).
-// xn may alias xt (one thread reads then writes an element).  noise == NULL with a noise term: Philox keyed like ddpm_step_kernel (quad q).
-// xpad: x_next also into rows of ldpad floats (the next motion-adapter GEMM's K-padded A rows; columns >= cols stay zero).
-struct CfgUpd {
-    const float *x0c, *x0u, *scale, *xt, *noise;
-    float* xn;
-    const float *c1, *c2, *sg;
-    const float *ra, *rb, *rc, *rd;
-    const float4* rec;
-    float* xpad;
-    int64_t ldpad, per_sample, sample0;
-    uint64_t seed;
-    int cols, clip, ddim, step;
-};
-
-__global__ __launch_bounds__(256) void cfg_update_kernel(const CfgUpd p) {
-    const int b = blockIdx.y;
-    const float s = p.scale[b];
-    const float sg = p.sg ? p.sg[b] : 0.f;
-    float4 r = make_float4(0.f, 1.f, 0.f, 0.f);
-    float c1 = 0.f, c2 = 0.f;
-    if (p.ddim) r = p.rec ? p.rec[b] : make_float4(p.ra[b], p.rb[b], p.rc[b], p.rd[b]);
-    else { c1 = p.c1[b]; c2 = p.c2[b]; }
-    const int64_t base = (int64_t)b * p.per_sample;
-    const int64_t nquad = (p.per_sample + 3) >> 2;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * blockDim.x) {
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (p.sg && !p.noise) philox_normal4(p.seed, p.sample0 + b, p.step, (uint64_t)q, z);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t i = q * 4 + e;
-            if (i < p.per_sample) {
-                const int64_t g = base + i;
-                float v = cfg_combine(p.x0c[g], p.x0u[g], s);
-                if (p.clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised on x0_guided (NaN passes through, as torch.clamp)
-                const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
-                const float vt = p.xt[g];
-                float xn;
-                if (p.ddim) xn = p.sg ? ddim_update(v, vt, r, sg, nz) : ddim_update(v, vt, r);
-                else xn = ddpm_update(v, vt, c1, c2, sg, nz);
-                p.xn[g] = xn;
-                if (p.xpad) {
-                    const int64_t row = g / p.cols;
-                    p.xpad[row * p.ldpad + (g - row * p.cols)] = xn;
-                }
-            }
-        }
-    }
-}
-
-int launch_cfg_update(const CfgUpd& p, int32_t B, void* stream) {
-    if (!p.x0c || !p.x0u || !p.scale || !p.xt || !p.xn || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
-    if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && p.rd)) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
-    if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
-    if (B == 0) return 0;
-    const int64_t nquad = (p.per_sample + 3) >> 2;
-    unsigned gx = (unsigned)((nquad + 255) / 256);
-    if (gx > 1024) gx = 1024;
-    AfmProf prof(AFM_PROF_MISC, 5.0 * B * p.per_sample, (hipStream_t)stream);
-    hipLaunchKernelGGL(cfg_update_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, p);
-    AFM_CHECK_LAUNCH();
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int afm_cfg_combine(const float* x0_c, const float* x0_u, const float* scale, float* out, int32_t B, int64_t per_sample, void* stream) {
     if (!x0_c || !x0_u || !scale || !out || B < 0 || per_sample <= 0) return AFM_E_BADARG;
     if (B == 0) return 0;
-    unsigned gx = (unsigned)((per_sample + 255) / 256);
-    if (gx > 1024) gx = 1024;
     AfmProf prof(AFM_PROF_MISC, 3.0 * B * per_sample, (hipStream_t)stream);
-    hipLaunchKernelGGL(cfg_combine_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0_c, x0_u, scale, out, per_sample);
+    hipLaunchKernelGGL(cfg_combine_kernel, stream_grid(per_sample, 1024, B), dim3(256), 0, (hipStream_t)stream, x0_c, x0_u, scale, out, per_sample);
     AFM_CHECK_LAUNCH();
     return 0;
-}
-
-extern "C" int afm_cfg_step(const afm_cfg_step_args* a, void* stream) {
-    if (!a) return AFM_E_BADARG;
-    CfgUpd p = {};
-    p.x0c = a->x0_c; p.x0u = a->x0_u; p.scale = a->scale; p.xt = a->x_t; p.noise = a->noise; p.xn = a->x_next;
-    p.per_sample = a->per_sample; p.clip = a->clip ? 1 : 0; p.seed = a->seed; p.sample0 = a->sample_index0; p.step = a->step;
-    if (a->ddim) { p.ddim = 1; p.ra = a->ddim->a; p.rb = a->ddim->b; p.rc = a->ddim->c; p.rd = a->ddim->d; p.sg = a->ddim->sigma; }
-    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
-    return launch_cfg_update(p, a->B, stream);
-}
-
-// the guided update of a native loop's step (cmdm.hip): x0_c / x0_u [B][per_sample] the two branches' pred_xstart, x [B][per_sample] x_t ->
-// x_next in place, scale [B]; rec != NULL: DDIM records {a, b, c, d} [B] with s [B] (NULL: no noise term), else the DDPM rows c1 / c2 / s [B];
-// rows of `cols` values copied to xpad (row stride ldpad) if given
-__attribute__((visibility("hidden"))) int afm_cfg_update_rows(const float* x0_c, const float* x0_u, const float* scale, float* x, const float* noise,
-                                                              const float4* rec, const float* c1, const float* c2, const float* s, int32_t B,
-                                                              int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream) {
-    if (s && !noise) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside this launch)
-    CfgUpd p = {};
-    p.x0c = x0_c; p.x0u = x0_u; p.scale = scale; p.xt = x; p.xn = x; p.noise = noise; p.per_sample = per_sample; p.clip = clip ? 1 : 0;
-    p.cols = cols; p.xpad = xpad; p.ldpad = ldpad;
-    if (rec) { p.ddim = 1; p.rec = rec; p.sg = s; }
-    else { p.c1 = c1; p.c2 = c2; p.sg = s; }
-    return launch_cfg_update(p, B, stream);
 }

@@ -231,7 +231,8 @@ int cdm_forward_folded(const afm_cdm_weights& w, const float* feat, const float*
 static int cdm_forward_impl(const afm_cdm_weights* wp, const float* feat, const float* x_t, const int64_t* t,
                             const float* text_q0, const float* text_u, const float* text_cu, float* x0_out,
                             const afm_ddpm_args* ddpm, int32_t B, int32_t N, void* workspace, int64_t workspace_bytes,
-                            void* side_stream, void* stream, bool prepared = false, bool rowless_ws = false, const CdmChainSide* cs = nullptr) {
+                            void* side_stream, void* stream, bool prepared = false, bool rowless_ws = false, const CdmChainSide* cs = nullptr,
+                            const afm_loop::Update* loop_upd = nullptr) {      // loop_upd: the layer-by-layer DDIM loop's update launch, its x0 set here
     AFM_TRY(validate(wp, B, N));
     if (!feat || !t || !text_q0 || !text_u || !text_cu || !workspace || (!x0_out && !ddpm)) return AFM_E_BADARG;
     if (!wp->time_q0 || !wp->time_u || !wp->time_cu) return AFM_E_BADARG;
@@ -302,9 +303,10 @@ static int cdm_forward_impl(const afm_cdm_weights* wp, const float* feat, const 
         a.C = ws.bufB;
         a.arith = w.gemm_arith; a.arith_min_n = w.gemm_arith_min_n;
         AFM_TRY(afm_linear(&a, s));
-        return afm_ddim_update_rows(ws.bufB, ddpm->x_next, (upd & AFM_UPD_NO_NOISE) ? nullptr : ddpm->noise, (const float4*)ddpm->c1,
-                                    (upd & AFM_UPD_NO_NOISE) ? nullptr : ddpm->sigma, B, (int64_t)N * w.contact_dim, w.contact_dim, upd & AFM_UPD_CLIP,
-                                    nullptr, 0, s);
+        if (!loop_upd) return AFM_E_BADARG;
+        Update u = *loop_upd;
+        u.x0 = ws.bufB;
+        return afm_sampling_update(u, B, s);
     }
     if (ddpm) {
         a.ddpm_xt = x_t; a.ddpm_noise = ddpm->noise; a.ddpm_out = ddpm->x_next; a.ldx = w.contact_dim;
@@ -515,9 +517,10 @@ int plain_step(const Loop& l, const SubBatch& sb, int j) {
     AFM_TRY(step_noise(c.a, l.p.per, sb, sb.noise, j, xs, &sb.stream, &nz));
     const StepRows r = l.sched.at(j, sb.start);
     const afm_ddpm_args dd = ddpm_args(c.a, r, nz, xs, sb, j);
+    const Update upd = loop_update(c.a, r, nullptr, xs, nz, l.p.per, w.flags & AFM_CDM_CLIP_X0);
     return cdm_forward_impl(&w, fs, xs, r.t, c.text_q0 + (int64_t)sb.start * w.dq, c.text_u + (int64_t)sb.start * w.enc_heads * w.dkv,
                             c.text_cu + (int64_t)sb.start * w.enc_heads, nullptr, &dd, sb.count, c.N, sb.base, sb.ws.bytes, sb.side, sb.stream,
-                            l.p.folded, l.p.rowless, l.p.chain_side ? &sb.chain : nullptr);
+                            l.p.folded, l.p.rowless, l.p.chain_side ? &sb.chain : nullptr, &upd);
 }
 
 // Whole p_sample_loop of the ADM (gaussian_diffusion.py:442-536) enqueued natively: x [B,N,contact_dim] holds x_T on entry and the

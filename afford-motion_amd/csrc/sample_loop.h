@@ -9,12 +9,30 @@ __attribute__((visibility("hidden"))) int afm_ddpm_expand_rows(const int64_t* tm
                                                                int32_t B, int64_t* t_all, float* c1_all, float* c2_all, float* s_all, void* stream);
 __attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tmap, const afm_ddim_rows* rows, int32_t n_steps, int32_t B, int64_t* t_all,
                                                                float4* rec_all, float* s_all, void* stream);
-// the DDIM update of a native loop's step from the stored pred_xstart
-__attribute__((visibility("hidden"))) int afm_ddim_update_rows(const float* x0, float* x, const float* noise, const float4* rec, const float* s, int32_t B,
-                                                               int64_t per_sample, int32_t cols, int32_t clip, float* xpad, int64_t ldpad, void* stream);
 __attribute__((visibility("hidden"))) int afm_randn_steps(float*, int32_t, int64_t, uint64_t, int64_t, int32_t, int32_t, void*);      // [nsteps][B][per_sample]
+namespace afm_loop { struct Update; }
+// checks and enqueues one sampling update over B samples (AFM_E_BADARG: a NULL tensor or row, x0_u without scale or the reverse, a noise
+// term without noise unless `philox`, xpad with ldpad < cols; B == 0: nothing to do)
+__attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream);
 
 namespace afm_loop {
+
+// ---- the sampling update x_t -> x_next of one launch, [B][per_sample] floats: every DDPM, DDIM and guided update outside the fused GEMM /
+// CDM output epilogues is this one description (elementwise.hip: sampling_update_kernel).
+struct Update {
+    const float* x0;                // pred_xstart (the conditioned branch's when guided)
+    const float *x0_u, *scale;      // guided: the unconditioned branch's pred_xstart and scale [B]; both NULL: unguided
+    const float* xt;
+    float* xn;                      // x_next; may alias xt (the loops update in place)
+    const float* noise;             // NULL with a noise term: drawn in the kernel from (seed, sample0 + b, step) if `philox`, else rejected
+    const float *c1, *c2, *sg;      // DDPM rows [B]; sg is also the DDIM noise coefficient (NULL there: no noise term, noise never read)
+    const float *ra, *rb, *rc, *rd; // DDIM rows [B] (`ddim` set), or
+    const float4* rec;              //   the same as {a, b, c, d} records [B]
+    float* xpad;                    // x_next also as rows of `cols` values at row stride ldpad (NULL: none)
+    int64_t ldpad, per_sample, sample0;
+    uint64_t seed;
+    int cols, clip, ddim, philox, step;
+};
 
 inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
@@ -119,6 +137,16 @@ inline int step_noise(const LoopArgs& a, int64_t per, const SubRange& r, float* 
     if (!draw_on || j % NOISE_STEPS != 0) return 0;
     return afm_randn_steps(slot, r.count, per, a.seed, a.sample_index0 + r.start, a.first_step + j,
                            a.n_steps - j < NOISE_STEPS ? a.n_steps - j : NOISE_STEPS, *draw_on);
+}
+
+// the update launch of a loop step from its stored pred_xstart: in place on x, the step's rows, noise only where the rows have a noise term
+inline Update loop_update(const LoopArgs& a, const StepRows& rows, const float* x0, float* x, const float* noise, int64_t per_sample, int clip) {
+    Update u = {};
+    u.x0 = x0; u.xt = x; u.xn = x; u.per_sample = per_sample; u.clip = clip ? 1 : 0;
+    if (rows.rec) { u.ddim = 1; u.rec = rows.rec; }
+    else { u.c1 = rows.c1; u.c2 = rows.c2; }
+    if (a.noise_term()) { u.sg = rows.sigma; u.noise = noise; }
+    return u;
 }
 
 // the update arguments of (sub-batch r, step j): in place on the sub-batch's x

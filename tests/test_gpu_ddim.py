@@ -48,21 +48,23 @@ def _loop_inputs(resp):
 def test_ddim_step_kernel_equals_the_cpu_expression(tt):
     d = create_gaussian_diffusion(cmdm_cfg())
     g = golden(f"cmdm_ddim_sample_t{tt}")
-    x0, x, nz = g["pred_xstart"], g["x"], g["noise"]
-    t = torch.tensor([tt, tt], device=dev())
-    for eta in (0.0, 0.5, 1.0):
-        rows = d.ddim_tables(dev(), eta)
-        sg = None if rows.sigma is None else rows.sigma[t]
-        got = ops.ddim_step(x0.to(dev()), x.to(dev()), nz.to(dev()), rows.a[t], rows.b[t], rows.c[t], rows.d[t], sg).cpu()
-        assert torch.equal(got, _cpu_update(x0, x, nz, rows, tt)), (tt, eta)
-        if sg is not None:          # noise=NULL: the in-kernel Philox draw equals afm_randn of the same keying
-            phil = ops.ddim_step(x0.to(dev()), x.to(dev()), None, rows.a[t], rows.b[t], rows.c[t], rows.d[t], sg, seed=11, sample_index0=3, step=7)
-            given = ops.randn(SHAPE, dev(), seed=11, sample_index0=3, step=7)
-            assert torch.equal(phil, ops.ddim_step(x0.to(dev()), x.to(dev()), given, rows.a[t], rows.b[t], rows.c[t], rows.d[t], sg,
-                                                   seed=11, sample_index0=3, step=7))
-    rows = d.ddim_tables(dev(), reverse=True)
-    got = ops.ddim_step(x0.to(dev()), x.to(dev()), None, rows.a[t], rows.b[t], rows.c[t], rows.d[t], None).cpu()
-    assert torch.equal(got, _cpu_update(x0, x, None, rows, tt))
+    # (3, 5, 263): 1315 values per sample, not a multiple of 4 - the last quad of a sample is partial
+    odd = tuple(synth.gaussian(f"ddim_odd_{n}", (3, 5, 263)) for n in ("x0", "x", "nz"))
+    for x0, x, nz in ((g["pred_xstart"], g["x"], g["noise"]), odd):
+        t = torch.full((x.shape[0],), tt, device=dev())
+        for eta in (0.0, 0.5, 1.0):
+            rows = d.ddim_tables(dev(), eta)
+            sg = None if rows.sigma is None else rows.sigma[t]
+            got = ops.ddim_step(x0.to(dev()), x.to(dev()), nz.to(dev()), rows.a[t], rows.b[t], rows.c[t], rows.d[t], sg).cpu()
+            assert torch.equal(got, _cpu_update(x0, x, nz, rows, tt)), (tt, eta, x.shape)
+            if sg is not None:          # noise=NULL: the in-kernel Philox draw equals afm_randn of the same keying
+                phil = ops.ddim_step(x0.to(dev()), x.to(dev()), None, rows.a[t], rows.b[t], rows.c[t], rows.d[t], sg, seed=11, sample_index0=3, step=7)
+                given = ops.randn(tuple(x.shape), dev(), seed=11, sample_index0=3, step=7)
+                assert torch.equal(phil, ops.ddim_step(x0.to(dev()), x.to(dev()), given, rows.a[t], rows.b[t], rows.c[t], rows.d[t], sg,
+                                                       seed=11, sample_index0=3, step=7))
+        rows = d.ddim_tables(dev(), reverse=True)
+        got = ops.ddim_step(x0.to(dev()), x.to(dev()), None, rows.a[t], rows.b[t], rows.c[t], rows.d[t], None).cpu()
+        assert torch.equal(got, _cpu_update(x0, x, None, rows, tt))
 
 
 @pytest.mark.parametrize("tt", [999, 500, 1, 0])
@@ -102,6 +104,15 @@ def test_cmdm_ddim_loop_vs_reference_golden(cmdm, resp, eta, clip, tag):
     snaps = {1: None, d.num_timesteps - 1: None}
     snapped = d.ddim_sample_loop(cmdm, SHAPE, noise=xT, clip_denoised=clip, model_kwargs=_kw(g), eta=eta, step_noise=nz, snapshots=snaps)
     assert torch.equal(native, snapped) and all(v is not None for v in snaps.values())
+    if resp == "ddim5":         # L = 15: 3945 values per sample, the update's last quad and its K-padded row copy end on a partial quad
+        odd = (2, 15, 263)
+        kw = dict(c_text_feat=g["text_feat"].to(dev()), c_cont_emb=g["cont_emb"].to(dev()), x_mask=synth.frame_mask(2, 15, min_len=8).to(dev()))
+        onz = torch.stack([synth.gaussian(f"ddim_loop_L15_{j}", odd) for j in range(d.num_timesteps)]).to(dev())
+        oxT = synth.gaussian("ddim_loop_L15_xT", odd).to(dev())
+        native = d.ddim_sample_loop(cmdm, odd, noise=oxT, clip_denoised=clip, model_kwargs=kw, eta=eta, step_noise=onz)
+        for out in d.ddim_sample_loop_progressive(cmdm, odd, noise=oxT, clip_denoised=clip, model_kwargs=kw, eta=eta, step_noise=onz):
+            generic = out["sample"]
+        assert torch.equal(native, generic)
 
 
 def test_cdm_ddim_loop_in_every_sampling_form(cdm):

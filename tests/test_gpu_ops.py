@@ -523,18 +523,19 @@ def test_ddpm_step_bit_exact():
     """Same float32 expression as gaussian_diffusion.py:222-225,439 -> bit-identical to torch-CPU."""
     from oracle import diffusion_ref as df
     s = df.Schedule(1000)
-    B, L, D = 4, 196, 263
-    x0, xt, nz = (synth.gaussian(n, (B, L, D)) for n in ("dd_x0", "dd_xt", "dd_nz"))
-    t = torch.tensor([999, 500, 1, 0])
-    c1 = df._extract(s.posterior_mean_coef1, t, x0.shape); c2 = df._extract(s.posterior_mean_coef2, t, x0.shape)
-    lv = df._extract(s.posterior_log_variance_clipped, t, x0.shape)
-    nzm = (t != 0).float().view(-1, 1, 1)
-    want = (c1 * x0 + c2 * xt) + nzm * torch.exp(0.5 * lv) * nz
-    f = lambda a: torch.from_numpy(a).float()[t]
-    sig = (t != 0).float() * torch.exp(0.5 * f(s.posterior_log_variance_clipped))
-    got = ops.ddpm_step(x0.to(dev()), xt.to(dev()), nz.to(dev()), f(s.posterior_mean_coef1).to(dev()),
-                        f(s.posterior_mean_coef2).to(dev()), sig.to(dev()))
-    assert torch.equal(got.cpu(), want), (got.cpu() - want).abs().max()
+    f = lambda a: torch.from_numpy(a).float()
+    # (3, 5, 263): 1315 values per sample, not a multiple of 4 - the last quad of a sample is partial
+    for tag, shape, ts in (("", (4, 196, 263), [999, 500, 1, 0]), ("_odd", (3, 5, 263), [999, 1, 0])):
+        x0, xt, nz = (synth.gaussian(n + tag, shape) for n in ("dd_x0", "dd_xt", "dd_nz"))
+        t = torch.tensor(ts)
+        c1 = df._extract(s.posterior_mean_coef1, t, x0.shape); c2 = df._extract(s.posterior_mean_coef2, t, x0.shape)
+        lv = df._extract(s.posterior_log_variance_clipped, t, x0.shape)
+        nzm = (t != 0).float().view(-1, 1, 1)
+        want = (c1 * x0 + c2 * xt) + nzm * torch.exp(0.5 * lv) * nz
+        sig = (t != 0).float() * torch.exp(0.5 * f(s.posterior_log_variance_clipped)[t])
+        got = ops.ddpm_step(x0.to(dev()), xt.to(dev()), nz.to(dev()), f(s.posterior_mean_coef1)[t].to(dev()),
+                            f(s.posterior_mean_coef2)[t].to(dev()), sig.to(dev()))
+        assert torch.equal(got.cpu(), want), (shape, (got.cpu() - want).abs().max())
 
 
 def test_philox_randn_statistics_and_sharding_invariance():
