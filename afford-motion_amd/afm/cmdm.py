@@ -541,13 +541,14 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
     # ------------------------------------------------------------------ native sampling loop
     def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                        clip_denoised=False, ddim_eta: Optional[float] = None, _guidance=None):
+                        clip_denoised=False, ddim_eta: Optional[float] = None, impute=None, _guidance=None):
         """Whole p_sample_loop on the device: x holds x_T on entry, returns the final sample.  ``clip_denoised``: pred_xstart clamped to
         [-1, 1] inside the fused DDPM update (the reference's default argument; test.py passes False).  ``ddim_eta`` not None: the
         ddim_sample_loop with that eta instead (afm_cmdm_ddim_loop_range: the same launches, the DDIM update in the same epilogue).  ``progress`` (test.py:85 passes
         True) splits the chain into ~50 native slices (afm_cmdm_sample_loop_range) and advances a tqdm bar between them; the
-        result is bit-identical to the unsliced loop.  ``_guidance``: GuidedCMDM's (afm_cfg_args, branch streams?) (the guided loops; not a
-        caller's argument)."""
+        result is bit-identical to the unsliced loop.  ``impute``: an afm.diffusion.Impute - its known values are written over every step's
+        pred_xstart before the clamp, inside the loop's update launch (afm_cmdm_impute_loop_range, all four forms).  ``_guidance``:
+        GuidedCMDM's (afm_cfg_args, branch streams?) (the guided loops; not a caller's argument)."""
         if any(k in model_kwargs for k in COND_SWITCHES):
             raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
                                       "p_sample_loop samples them step by step (p_sample_loop_progressive)")
@@ -556,6 +557,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         with torch.no_grad():
             x = ffi.f32c(x)
             B, L, _ = x.shape
+            if impute is not None:
+                impute.check(x)
             w = self._weights()
             if clip_denoised:
                 w.flags |= ffi.CMDM_CLIP_X0                  # per call: _stamp() rewrites the flags on the next _weights()
@@ -594,6 +597,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             stream = ffi.stream_of(x)
             entry = {(True, True): "afm_cmdm_sample_loop_range", (True, False): "afm_cmdm_ddim_loop_range",
                      (False, True): "afm_cmdm_cfg_sample_loop_range", (False, False): "afm_cmdm_cfg_ddim_loop_range"}[(cfg is None, ddim is None)]
+            if impute is not None:
+                entry = "afm_cmdm_impute_loop_range"
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
@@ -601,13 +606,16 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
                     (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
                 guide = () if cfg is None else (C.byref(cfg),)
+                if impute is not None:       # one entry for the four forms: both kinds of rows, cfg or NULL, known and mask
+                    rows = (rows[0], None, None, None) if ddim is not None else (None,) + rows
+                    guide = (None if cfg is None else C.byref(cfg), impute.known.data_ptr(), impute.mask.data_ptr())
                 tail = (j1 - j0, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
                         nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream)
                 ffi.check(getattr(lib, entry)(*head, *rows, *guide, *tail), entry)
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim, _guidance)
+            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim, _guidance, impute)
         return x
 
 
@@ -707,10 +715,12 @@ class GuidedCMDM(nn.Module):
     def forward(self, x, timesteps, **kwargs):
         return self.branches(x, timesteps, **kwargs)[2]
 
-    def afm_native_loop(self, diffusion, x, model_kwargs, **kw):
-        """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range): CMDM.afm_native_loop's arguments."""
+    def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, **kw):
+        """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range; with ``impute``: the guided form of
+        afm_cmdm_impute_loop_range): CMDM.afm_native_loop's arguments."""
         self._no_switches(model_kwargs)
         if self.model.training:
             raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
         ffi.require_gpu(x)
-        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(self._cfg(x.shape[0], x.device), self.branch_streams), **kw)
+        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(self._cfg(x.shape[0], x.device), self.branch_streams), impute=impute,
+                                          **kw)

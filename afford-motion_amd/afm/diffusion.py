@@ -69,6 +69,73 @@ class LossType(enum.Enum):
         return self in (LossType.KL, LossType.RESCALED_KL)
 
 
+class Impute:
+    """Known motion values imputed into every pred_xstart of a sampling chain (editing: keyframes to in-between, a root trajectory, a
+    prefix to continue): ``x0 = where(mask, known, x0)`` after the denoiser and before the clamp - what the reference's ``denoised_fn``
+    hook of p_mean_variance exists for (gaussian_diffusion.py:289-294).  A select: ``known`` is never read where the mask is 0.
+
+    ``known``: float32 [B, L, D] in the model's normalised motion space.  ``mask``: bool or uint8 (nonzero = known), broadcastable to it
+    ([L, D], [B, L, 1], [B, 1, D], ...); expanded ONCE to a contiguous uint8 [B, L, D] on known's device.
+
+    The object is a callable ``imp(x0) -> ops.impute(x0, known, mask)`` (afm_impute, HIP), so it IS a ``denoised_fn`` wherever one is
+    accepted - p_sample, ddim_sample, the progressive generators, the CDM; handed to p_sample_loop / ddim_sample_loop of a denoiser whose
+    native loop takes ``impute=`` (CMDM `trans_enc`, GuidedCMDM) the whole chain stays in the native loop (afm_cmdm_impute_loop_range)."""
+
+    def __init__(self, known: torch.Tensor, mask: torch.Tensor):
+        if known.dim() != 3:
+            raise ValueError(f"Impute: known must be [B, L, D], got {tuple(known.shape)}")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"Impute: mask must be bool or uint8, not {mask.dtype}")
+        if mask.dim() > 3:
+            raise ValueError(f"Impute: mask {tuple(mask.shape)} does not broadcast to known {tuple(known.shape)}")
+        try:
+            full = torch.broadcast_shapes(tuple(mask.shape), tuple(known.shape))
+        except RuntimeError:
+            full = None
+        if full != tuple(known.shape):
+            raise ValueError(f"Impute: mask {tuple(mask.shape)} does not broadcast to known {tuple(known.shape)}")
+        self.known = ffi.f32c(known.detach())
+        # bool storage is one byte of 0 / 1 and the kernels read "nonzero": the expansion is one copy, no arithmetic
+        m = mask.detach().to(device=self.known.device).expand(full).contiguous()
+        self.mask = m.view(torch.uint8) if m.dtype == torch.bool else m
+
+    @classmethod
+    def _of(cls, known: torch.Tensor, mask: torch.Tensor) -> "Impute":
+        imp = cls.__new__(cls)
+        imp.known, imp.mask = known, mask
+        return imp
+
+    @property
+    def shape(self):
+        return tuple(self.known.shape)
+
+    def __call__(self, x0: torch.Tensor) -> torch.Tensor:
+        self.check(x0)
+        return ops.impute(x0, self.known, self.mask)
+
+    def check(self, x: torch.Tensor) -> None:
+        """shape and device against a sample tensor"""
+        if tuple(x.shape) != self.shape:
+            raise ValueError(f"Impute: known is {self.shape}, the sample is {tuple(x.shape)}")
+        if x.device != self.known.device:
+            raise ValueError(f"Impute: known is on {self.known.device}, the sample on {x.device}")
+
+    def narrow(self, start: int, count: int) -> "Impute":
+        """the samples [start, start + count) - the slice of one rank of a sharded job (afm.dist.sharded_sample's sample_fn)"""
+        if start < 0 or count < 0 or start + count > self.known.shape[0]:
+            raise ValueError(f"Impute.narrow({start}, {count}) of a batch of {self.known.shape[0]}")
+        return Impute._of(self.known[start:start + count], self.mask[start:start + count])
+
+
+def _takes_impute(native) -> bool:
+    """does a denoiser's afm_native_loop accept the ``impute=`` keyword (CMDM trans_enc, GuidedCMDM; not the CDM)"""
+    import inspect
+    try:
+        return "impute" in inspect.signature(native).parameters
+    except (TypeError, ValueError):
+        return False
+
+
 class _DeviceTables:
     """float32 schedule rows on one device (cast exactly like `_extract_into_tensor(...).float()`)."""
 
@@ -309,10 +376,12 @@ class GaussianDiffusion:
     def _sample_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, step_noise, seed,
                      sample_index0, snapshots, ddim_eta: Optional[float]):
         """p_sample_loop (ddim_eta None) / ddim_sample_loop: the native loop when the denoiser has one and nothing needs the host between
-        steps, else the progressive generator."""
+        steps, else the progressive generator.  A ``denoised_fn`` that is an `Impute` stays native where the denoiser's loop takes
+        ``impute=``; any other callable samples step by step."""
         native = getattr(model, "afm_native_loop", None)
         switches = any(k in (model_kwargs or {}) for k in ("c_text_mask", "c_text_erase", "c_pc_mask", "c_pc_erase"))
-        if native is not None and denoised_fn is None and cond_fn is None and not self.rescale_timesteps and not switches:
+        impute = denoised_fn if isinstance(denoised_fn, Impute) and native is not None and _takes_impute(native) else None
+        if native is not None and (denoised_fn is None or impute is not None) and cond_fn is None and not self.rescale_timesteps and not switches:
             if device is None:
                 device = next(model.parameters()).device
             seed = self._fresh_seed("_sample_calls") if seed is None else seed
@@ -321,6 +390,9 @@ class GaussianDiffusion:
             if isinstance(step_noise, (list, tuple)):
                 step_noise = torch.stack(list(step_noise), 0)
             extra = {} if snapshots is None else {"snapshots": snapshots}
+            if impute is not None:
+                impute.check(x)
+                extra["impute"] = impute
             if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused update
                 extra["clip_denoised"] = True
             if ddim_eta is not None:

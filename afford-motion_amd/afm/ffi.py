@@ -163,6 +163,13 @@ class CfgStepArgs(C.Structure):
                 ("per_sample", i64), ("seed", u64), ("sample_index0", i64), ("step", i32)]
 
 
+class ImputeStepArgs(C.Structure):
+    """afm_impute_step_args (v7-additive): afm_cfg_step_args with known / mask, the unconditioned branch optional."""
+    _fields_ = [("x0_c", c_f32p), ("x0_u", c_f32p), ("scale", c_f32p), ("known", c_f32p), ("mask", C.c_void_p), ("x_t", c_f32p),
+                ("noise", c_f32p), ("x_next", c_f32p), ("c1", c_f32p), ("c2", c_f32p), ("sigma", c_f32p), ("ddim", C.POINTER(DdimRows)),
+                ("clip", i32), ("B", i32), ("per_sample", i64), ("seed", u64), ("sample_index0", i64), ("step", i32)]
+
+
 CFG_FORCE_MASKED = 0x1
 
 EXPORTS = {
@@ -198,6 +205,11 @@ EXPORTS = {
     "afm_cmdm_cfg_ddim_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
                                                C.POINTER(CfgArgs), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                                C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_impute": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i64, C.c_void_p]),
+    "afm_impute_step": (C.c_int, [C.POINTER(ImputeStepArgs), C.c_void_p]),
+    "afm_cmdm_impute_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                             c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), c_f32p, C.c_void_p, i32, i32, u64, i64, i32, i32,
+                                             C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

@@ -375,6 +375,69 @@ def cfg_step(x0_c: torch.Tensor, x0_u: torch.Tensor, scale: torch.Tensor, x_t: t
     return out
 
 
+def impute(x0: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Imputation of known values into an x_start prediction (afm_impute): where(mask, known, x0), a select - ``known`` is not read where
+    the mask is 0.  known float32 and mask uint8 / bool, both of x0's shape; ``out`` may be x0."""
+    lib = ffi.load()
+    ffi.require_gpu(x0, known, mask)
+    x0, known = ffi.f32c(x0), ffi.f32c(known)
+    mask = _mask_u8(mask)
+    if known.shape != x0.shape or mask.shape != x0.shape:
+        raise ValueError(f"impute: known {tuple(known.shape)} and mask {tuple(mask.shape)} must have x0's shape {tuple(x0.shape)}")
+    out = torch.empty_like(x0) if out is None else out
+    ffi.check(lib.afm_impute(x0.data_ptr(), known.data_ptr(), mask.data_ptr(), out.data_ptr(), x0.numel(), ffi.stream_of(x0)), "afm_impute")
+    return out
+
+
+def _mask_u8(mask: torch.Tensor) -> torch.Tensor:
+    """a bool / uint8 mask as contiguous uint8 (bool storage is one byte of 0 / 1: a view, no kernel)"""
+    if mask.dtype == torch.bool:
+        mask = mask.contiguous().view(torch.uint8)
+    if mask.dtype != torch.uint8:
+        raise ValueError(f"mask must be bool or uint8, not {mask.dtype}")
+    return mask.contiguous()
+
+
+def impute_step(x0: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor], *,
+                x0_u: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None, ddpm=None, ddim=None, clip: bool = False,
+                seed: int = 0, sample_index0: int = 0, step: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One imputing sampling update (afm_impute_step): x0 (with ``x0_u`` and ``scale``: cfg_combine(x0, x0_u, scale)), then impute, the clamp
+    to [-1, 1] if ``clip``, then the ddpm_step expression with ``ddpm`` = (c1, c2, sigma) per-sample rows or the ddim_step expression with
+    ``ddim`` = (a, b, c, d, sigma | None).  noise None: Philox."""
+    if (ddpm is None) == (ddim is None):
+        raise ValueError("impute_step: exactly one of ddpm= / ddim= rows")
+    if (x0_u is None) != (scale is None):
+        raise ValueError("impute_step: x0_u= and scale= go together")
+    lib = ffi.load()
+    ffi.require_gpu(x0, known, mask, x_t)
+    x0, known, x_t = ffi.f32c(x0), ffi.f32c(known), ffi.f32c(x_t)
+    mask = _mask_u8(mask)
+    B = x0.shape[0]
+    if known.shape != x0.shape or mask.shape != x0.shape:
+        raise ValueError(f"impute_step: known {tuple(known.shape)} and mask {tuple(mask.shape)} must have x0's shape {tuple(x0.shape)}")
+    out = torch.empty_like(x0) if out is None else out
+    a = ffi.ImputeStepArgs()
+    a.x0_c, a.known, a.mask, a.x_t, a.x_next = x0.data_ptr(), known.data_ptr(), mask.data_ptr(), x_t.data_ptr(), out.data_ptr()
+    if x0_u is not None:
+        x0_u, scale = ffi.f32c(x0_u), ffi.f32c(scale)
+        if scale.numel() != B or x0_u.shape != x0.shape:
+            raise ValueError(f"impute_step: scale must hold one value per sample ({B}), got {tuple(scale.shape)}; x0_u {tuple(x0_u.shape)}")
+        a.x0_u, a.scale = x0_u.data_ptr(), scale.data_ptr()
+    nz = None if noise is None else ffi.f32c(noise)
+    a.noise = ffi.ptr(nz)
+    keep = [ffi.f32c(r) for r in (ddpm if ddpm is not None else ddim) if r is not None]
+    rows = None
+    if ddpm is not None:
+        a.c1, a.c2, a.sigma = (r.data_ptr() for r in keep)
+    else:
+        rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], keep[4].data_ptr() if len(keep) > 4 else None)
+        a.ddim = C.pointer(rows)
+    a.clip, a.B, a.per_sample = int(bool(clip)), B, x0.numel() // max(B, 1)
+    a.seed, a.sample_index0, a.step = seed & (2**64 - 1), sample_index0, step
+    ffi.check(lib.afm_impute_step(C.byref(a), ffi.stream_of(x0)), "afm_impute_step")
+    return out
+
+
 def randn(shape, device, *, seed: int, sample_index0: int = 0, step: int = 0) -> torch.Tensor:
     """Counter-based N(0,1) noise keyed by (seed, global sample index, step, element)."""
     lib = ffi.load()

@@ -21,7 +21,7 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
                      contact_std: float = 1.0, seed: int = 0, sample_index0: int = 0,
                      adm_noise: Optional[Dict[str, torch.Tensor]] = None,
                      amdm_noise: Optional[Dict[str, torch.Tensor]] = None, sampler: str = "ddpm",
-                     eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc")) -> Dict[str, torch.Tensor]:
+                     eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None) -> Dict[str, torch.Tensor]:
     """text_feat [B, text_dim], xyz [B, N, 3] (B = scenes x k_sample, already flattened) ->
     {"contact": [B, N, J] ADM sample, "cond": [B, N, J] AMDM condition, "motion": [B, frames, D]}.
 
@@ -53,5 +53,5 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
         from .cmdm import GuidedCMDM
         amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
     motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
-                  model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
+                  denoised_fn=motion_impute, model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
     return {"contact": contact, "cond": cond, "motion": motion}

@@ -435,7 +435,7 @@ namespace {
 constexpr int MAX_SUB = 16;           // sub-batches (streams) of one loop call
 constexpr int NEV = 2 * AFM_MAX_LAYERS;      // events of the paired schedule: two cross-stream edges per layer
 
-// the arguments of the five loop entry points
+// the arguments of the six loop entry points
 struct LoopCall {
     const afm_cmdm_weights* w;
     float* x;
@@ -444,6 +444,8 @@ struct LoopCall {
     const afm_cfg_args* cfg;
     int L;
     LoopArgs a;                       // (a.streams: one side stream per sub-batch)
+    const float* known = nullptr;     // imputing loop: [B][L][motion_dim] each, both set (neither: no imputation)
+    const uint8_t* mask = nullptr;
 };
 
 struct SubBatch : SubRange {
@@ -494,7 +496,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     // (afm_sampling_update).  Both branches read the same x / K-padded copy; only the update writes them.
     p->br = {};
     if (c.cfg) AFM_TRY(uncond_setup(*c.w, c.cfg, c.frame_mask, &p->wu, &p->br));
-    if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok()) return AFM_E_BADARG;
+    if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     p->nsub = 0;
     if (a.B == 0) return 0;
     p->nsub = sub_count(a.B, a.n_streams, MAX_SUB);
@@ -521,7 +523,8 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     const int T = 1 + c.w->n_cond + c.L;
     p->w = *c.w;
     p->w.flags = a.loop_flags(p->w.flags);
-    if (c.cfg) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
+    // (an imputing loop likewise: the update fused into the motion_layer epilogue is contracted and has no place for the select)
+    if (c.cfg || c.mask) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
     if (p->nsub >= 2 && ((p->w.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < p->nsub; ++s) big = big && (int64_t)p->sb[s].count * T >= 4096;
@@ -560,6 +563,7 @@ int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const
     const afm_cmdm_weights& w = l.p.w;
     Update u = loop_update(l.c.a, rows, sb.ws.x0, sub_x(l, sb), noise, l.p.row, w.flags & AFM_CMDM_CLIP_X0);
     if (l.c.cfg) { u.x0_u = sb.wsu.x0; u.scale = l.c.cfg->scale + sb.start; }
+    if (l.c.mask) { u.known = l.c.known + (int64_t)sb.start * l.p.row; u.mask = l.c.mask + (int64_t)sb.start * l.p.row; }
     u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
     return afm_sampling_update(u, sb.count, sb.stream);
 }
@@ -568,7 +572,7 @@ int unguided_step(const Loop& l, const SubBatch& sb, int j) {
     StepRows rows;
     afm_ddpm_args dd;
     AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
-    return l.c.a.ddim ? update_launch(l, sb, rows, dd.noise) : 0;
+    return l.c.a.ddim || l.c.mask ? update_launch(l, sb, rows, dd.noise) : 0;
 }
 
 int guided_step(const Loop& l, const SubBatch& sb, int j) {
@@ -753,4 +757,16 @@ extern "C" int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x,
     if (first_step < 0 || !rows || !cfg) return AFM_E_BADARG;
     return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, seed, sample_index0, B,
                              sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
+}
+
+extern "C" int afm_cmdm_impute_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                                          const uint8_t* frame_mask, const float* step_noise, const int64_t* d_timestep_map,
+                                          const afm_ddim_rows* rows, const float* d_c1, const float* d_c2, const float* d_sigma,
+                                          const afm_cfg_args* cfg, const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step,
+                                          uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                                          int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
+    if (first_step < 0 || !known || !mask) return AFM_E_BADARG;
+    if (rows) d_c1 = d_c2 = d_sigma = nullptr;
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask});
 }

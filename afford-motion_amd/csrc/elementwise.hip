@@ -44,7 +44,8 @@ __global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __r
 }
 
 // The sampling update of sample_loop.h (afm_loop::Update), one quad of a sample per thread iteration: v = x0, or cfg_combine(x0, x0_u,
-// scale[b]) when guided, clamped if asked; then ddpm_update (rows c1 / c2 / sg per sample) or ddim_update (rows rec, or ra..rd, per sample;
+// scale[b]) when guided, then known where mask is set (a select: known is not read where mask == 0; the mask by byte loads, a sample's base
+// need not be 4-aligned), clamped if asked; then ddpm_update (rows c1 / c2 / sg per sample) or ddim_update (rows rec, or ra..rd, per sample;
 // sg == NULL: no noise term).  Every operation is one of common.h's individually rounded helpers (the reference's float32 torch expression,
 // bit for bit).  xn may alias xt (one thread reads then writes an element).  noise == NULL with a noise term: Philox keyed by the quad q.
 // xpad: x_next also into rows of ldpad floats (the next motion-adapter GEMM's K-padded A rows; columns >= cols stay zero).
@@ -68,6 +69,7 @@ __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Up
                 const int64_t g = base + i;
                 float v = p.x0[g];
                 if (p.x0_u) v = cfg_combine(v, p.x0_u[g], s);
+                if (p.mask && p.mask[g]) v = p.known[g];
                 if (p.clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised (NaN passes through, as torch.clamp)
                 const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
                 const float vt = p.xt[g];
@@ -247,7 +249,7 @@ int enqueue_update(const afm_loop::Update& p, int32_t B, hipStream_t s) {
 }  // namespace
 
 __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream) {
-    if (!p.x0 || !p.xt || !p.xn || !p.x0_u != !p.scale || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
+    if (!p.x0 || !p.xt || !p.xn || !p.x0_u != !p.scale || !p.known != !p.mask || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
     if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && p.rd)) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
     if (p.sg && !p.noise && !p.philox) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside their launch)
     if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
@@ -291,6 +293,15 @@ extern "C" int afm_cfg_step(const afm_cfg_step_args* a, void* stream) {
     if (!a || !a->x0_c || !a->x0_u || !a->scale) return AFM_E_BADARG;
     afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
     p.x0_u = a->x0_u; p.scale = a->scale; p.clip = a->clip ? 1 : 0;
+    if (a->ddim) set_ddim_rows(&p, a->ddim);
+    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    return afm_sampling_update(p, a->B, stream);
+}
+
+extern "C" int afm_impute_step(const afm_impute_step_args* a, void* stream) {
+    if (!a || !a->x0_c || !a->known || !a->mask) return AFM_E_BADARG;
+    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
+    p.x0_u = a->x0_u; p.scale = a->scale; p.known = a->known; p.mask = a->mask; p.clip = a->clip ? 1 : 0;
     if (a->ddim) set_ddim_rows(&p, a->ddim);
     else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
     return afm_sampling_update(p, a->B, stream);
@@ -368,6 +379,23 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restric
 }
 
 }  // namespace
+
+// ---- imputation of an x0 alone (the imputing updates are the sampling update above)
+namespace {
+__global__ __launch_bounds__(256) void impute_kernel(const float* __restrict__ known, const uint8_t* __restrict__ mask, const float* x0, float* out,
+                                                     int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = mask[i] ? known[i] : x0[i];          // out may alias x0: one thread reads then writes an element
+}
+}  // namespace
+
+extern "C" int afm_impute(const float* x0, const float* known, const uint8_t* mask, float* out, int64_t n, void* stream) {
+    if (n == 0) return 0;
+    if (!x0 || !known || !mask || !out || n < 0) return AFM_E_BADARG;
+    hipLaunchKernelGGL(impute_kernel, stream_grid(n, 4096), dim3(256), 0, (hipStream_t)stream, known, mask, x0, out, n);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int afm_cfg_combine(const float* x0_c, const float* x0_u, const float* scale, float* out, int32_t B, int64_t per_sample, void* stream) {
     if (!x0_c || !x0_u || !scale || !out || B < 0 || per_sample <= 0) return AFM_E_BADARG;

@@ -696,6 +696,47 @@ int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x, const floa
                                  int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Imputation of known motion values (editing: keyframes, a root trajectory, a prefix).  The reference's denoised_fn hook of
+ * p_mean_variance (gaussian_diffusion.py:289-294), as a SELECT on pred_xstart, per element and in this order:
+ *   v = x0 (guided: the afm_cfg_combine expression)  ->  v = mask ? known : v  ->  clamp to [-1, 1] if clip  ->  the update.
+ * mask: uint8, nonzero = known.  Where mask == 0, `known` is never read into the result (a NaN there does not propagate).  Known values
+ * outside [-1, 1] are clamped with clip (denoised_fn runs before the clamp).  Nothing is imputed in x_t space.
+ * ------------------------------------------------------------------------------------------ */
+
+/* out[i] = mask[i] ? known[i] : x0[i], n values; out may alias x0. */
+int afm_impute(const float* x0, const float* known, const uint8_t* mask, float* out, int64_t n, void* stream);
+
+/* One imputing sampling update: afm_cfg_step with known / mask [B][per_sample] (both required), and x0_u / scale optional (both NULL:
+ * unguided, x0 = x0_c).  Rows and noise as afm_cfg_step.  x_next may alias x_t.  Bit-identical to (afm_cfg_combine ->) afm_impute ->
+ * afm_clamp -> afm_ddpm_step / afm_ddim_step.  per_sample need not be a multiple of 4 (the mask is read bytewise). */
+typedef struct {
+    const float* x0_c; const float* x0_u; const float* scale;       /* [B][per_sample] x 2, [B]; x0_u, scale: both or neither */
+    const float* known; const uint8_t* mask;                        /* [B][per_sample]          */
+    const float* x_t; const float* noise; float* x_next;            /* [B][per_sample]          */
+    const float* c1; const float* c2; const float* sigma;           /* DDPM rows [B]            */
+    const afm_ddim_rows* ddim;                                      /* or DDIM rows [B]         */
+    int32_t clip; int32_t B; int64_t per_sample;
+    uint64_t seed; int64_t sample_index0; int32_t step;
+} afm_impute_step_args;
+int afm_impute_step(const afm_impute_step_args* args, void* stream);
+
+/* The imputing native loop, all four forms behind one entry: the arguments of the *_loop_range entries with both kinds of rows
+ * (rows != NULL: the DDIM loop, d_c1 / d_c2 / d_sigma ignored; rows == NULL: the DDPM loop), cfg (NULL: unguided) and known / mask
+ * [B][L][motion_dim] (both required; AFM_E_BADARG otherwise).  Every step stores pred_xstart with the plain motion_layer epilogue - for
+ * DDPM too: the update fused into that epilogue has no place for the select - and runs ONE update launch per sub-batch (the
+ * afm_impute_step expression, in place on x, plus the next step's K-padded copy).  Launches per step: the unguided DDPM loop's + 1; the
+ * DDIM and guided loops' unchanged.  AFM_CMDM_PAIR_LAUNCH and AFM_CMDM_FUSED_LN are ignored.  Noise, sub-batch streams, branch streams
+ * and first_step as the other loops.  workspace >= afm_cmdm_loop_workspace_bytes (cfg == NULL; the loop workspace always holds a
+ * pred_xstart region) or afm_cmdm_cfg_loop_workspace_bytes (cfg != NULL); sched_scratch: afm_ddim_sched_scratch_bytes with rows,
+ * afm_cmdm_sched_scratch_bytes without. */
+int afm_cmdm_impute_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                               const uint8_t* frame_mask, const float* step_noise, const int64_t* d_timestep_map,
+                               const afm_ddim_rows* rows, const float* d_c1, const float* d_c2, const float* d_sigma,
+                               const afm_cfg_args* cfg, const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step,
+                               uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                               int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
  * CrossAttentionLayer, SelfAttentionBlock, MLP, Residual; pad mask / rotary / kv-cache never used).
