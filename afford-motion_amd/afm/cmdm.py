@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, Mapping, Optional
 
 import torch
 import torch.nn as nn
@@ -548,7 +548,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         True) splits the chain into ~50 native slices (afm_cmdm_sample_loop_range) and advances a tqdm bar between them; the
         result is bit-identical to the unsliced loop.  ``impute``: an afm.diffusion.Impute - its known values are written over every step's
         pred_xstart before the clamp, inside the loop's update launch (afm_cmdm_impute_loop_range, all four forms).  ``_guidance``:
-        GuidedCMDM's (afm_cfg_args, branch streams?) (the guided loops; not a caller's argument)."""
+        GuidedCMDM's (afm_cfg_args or afm_cfg2_args, branch streams?) (the guided loops; not a caller's argument)."""
         if any(k in model_kwargs for k in COND_SWITCHES):
             raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
                                       "p_sample_loop samples them step by step (p_sample_loop_progressive)")
@@ -575,6 +575,9 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in self._side_streams[:nsub]])
             # _guidance (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)
             cfg, branch_streams = _guidance if _guidance is not None else (None, False)
+            two = isinstance(cfg, ffi.Cfg2Args)             # one scale per condition: three branches (afm_cmdm_cfg2_loop_range)
+            if two and branch_streams:
+                raise ValueError("branch streams are not built for the two-scale guided loop (three branches)")
             if branch_streams:
                 # the unconditioned branch of every sub-batch on a pool stream of its own: 2 * nsub <= 4 streams (the process has four hardware
                 # queues; more streams than queues serialise, ffi.stream_pool)
@@ -586,11 +589,14 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 cfg.branch_streams = C.cast(branch_handles, C.POINTER(C.c_void_p))
             if cfg is None:
                 nbytes = lib.afm_cmdm_loop_workspace_bytes(C.byref(w), B, L, nsub)
+            elif two:
+                nbytes = lib.afm_cmdm_cfg2_loop_workspace_bytes(C.byref(w), B, L, nsub, C.byref(cfg))
             else:
                 nbytes = lib.afm_cmdm_cfg_loop_workspace_bytes(C.byref(w), B, L, nsub, C.byref(cfg))
             if nbytes < 0:
                 ffi.check(int(nbytes), "afm_cmdm_loop_workspace_bytes")
-            key = ("loop" if cfg is None else ("cfg_loop", cfg.drop_text, cfg.drop_pc, cfg.flags), B, L, nsub, str(x.device))
+            form = "loop" if cfg is None else ("cfg2_loop", cfg.first, cfg.flags) if two else ("cfg_loop", cfg.drop_text, cfg.drop_pc, cfg.flags)
+            key = (form, B, L, nsub, str(x.device))
             if key not in self._ws:
                 self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
             ws = self._ws[key]
@@ -599,6 +605,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                      (False, True): "afm_cmdm_cfg_sample_loop_range", (False, False): "afm_cmdm_cfg_ddim_loop_range"}[(cfg is None, ddim is None)]
             if impute is not None:
                 entry = "afm_cmdm_impute_loop_range"
+            if two:
+                entry = "afm_cmdm_cfg2_loop_range"
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
@@ -606,9 +614,10 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
                     (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
                 guide = () if cfg is None else (C.byref(cfg),)
-                if impute is not None:       # one entry for the four forms: both kinds of rows, cfg or NULL, known and mask
+                if impute is not None or two:       # one entry for every form: both kinds of rows, cfg or NULL, known and mask (two scales: or NULL)
                     rows = (rows[0], None, None, None) if ddim is not None else (None,) + rows
-                    guide = (None if cfg is None else C.byref(cfg), impute.known.data_ptr(), impute.mask.data_ptr())
+                    guide = (None if cfg is None else C.byref(cfg),) + \
+                        ((None, None) if impute is None else (impute.known.data_ptr(), impute.mask.data_ptr()))
                 tail = (j1 - j0, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
                         nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream)
                 ffi.check(getattr(lib, entry)(*head, *rows, *guide, *tail), entry)
@@ -634,7 +643,15 @@ class GuidedCMDM(nn.Module):
     ``ddim_sample_loop`` work unchanged; it exposes ``afm_native_loop``, so they run the guided native loop under the conditions of the
     unguided one.  With every condition dropped the unconditioned branch runs in its compact form (no condition rows at all);
     ``force_masked=True`` (measurement) keeps the masked full-length form.  ``branch_streams=True`` (measurement; bit-identical) queues
-    the unconditioned branch of a native loop on a second stream per sub-batch instead of behind the conditioned branch."""
+    the unconditioned branch of a native loop on a second stream per sub-batch instead of behind the conditioned branch.
+
+    One scale per condition: ``scale={"pc": 1.5, "text": 5.0}`` - a mapping with exactly the keys "text" and "pc", each value a float or a
+    [B] tensor; the insertion order names (first, second).  Three evaluations, u (both dropped), a (only `first` kept), c (nothing dropped):
+
+        x0_guided = (u + s_first[b] * (a - u)) + s_second[b] * (c - a)          (float32, this association)
+
+    ``drop`` stays at its default, ``force_masked`` applies to u, branch streams are not built for three branches (ValueError).
+    ``branches`` then returns (x0_c, x0_a, x0_u, x0_guided).  Equal scales are not bit-equal to the single-scale form."""
 
     def __init__(self, model: "CMDM", scale, drop=GUIDANCE_DROPS, *, force_masked: bool = False, branch_streams: bool = False):
         super().__init__()
@@ -650,32 +667,56 @@ class GuidedCMDM(nn.Module):
         unknown = [d for d in drop if d not in GUIDANCE_DROPS]
         if unknown:
             raise ValueError(f"GuidedCMDM: unknown condition(s) {unknown} in `drop`; valid names: {GUIDANCE_DROPS}")
-        if isinstance(scale, torch.Tensor):
-            if scale.dim() > 1 or not scale.is_floating_point():
-                raise ValueError(f"GuidedCMDM: `scale` must be a float or a floating [B] tensor, got shape {tuple(scale.shape)} {scale.dtype}")
-            scale = scale.detach().clone().float().reshape(-1)
+        self.order = None                     # (first, second) with one scale per condition
+        if isinstance(scale, Mapping):
+            if len(scale) != len(GUIDANCE_DROPS) or set(scale) != set(GUIDANCE_DROPS):
+                raise ValueError(f"GuidedCMDM: a `scale` mapping has exactly the keys {GUIDANCE_DROPS}, got {list(scale)}")
+            if set(drop) != set(GUIDANCE_DROPS):
+                raise ValueError(f"GuidedCMDM: with one scale per condition `drop` stays at its default {GUIDANCE_DROPS}, got {drop}")
+            if branch_streams:
+                raise ValueError("GuidedCMDM: branch streams are not built for one scale per condition (three branches)")
+            self.order = tuple(scale)
+            scale = {k: self._scale_value(v) for k, v in scale.items()}
         else:
-            scale = float(scale)
+            scale = self._scale_value(scale)
         self.model, self.scale, self.drop, self.force_masked = model, scale, tuple(sorted(set(drop))), bool(force_masked)
         self.branch_streams = bool(branch_streams)
         self._scales: Dict[tuple, torch.Tensor] = {}
+
+    @staticmethod
+    def _scale_value(scale):
+        if isinstance(scale, torch.Tensor):
+            if scale.dim() > 1 or not scale.is_floating_point():
+                raise ValueError(f"GuidedCMDM: `scale` must be a float or a floating [B] tensor, got shape {tuple(scale.shape)} {scale.dtype}")
+            return scale.detach().clone().float().reshape(-1)
+        return float(scale)
 
     @property
     def motion_dim(self) -> int:
         return self.model.motion_dim
 
-    def _cfg(self, B: int, device) -> ffi.CfgArgs:
-        """afm_cfg_args for a batch of B on `device`; the [B] scale tensor is built once per (B, device) and kept on the wrapper."""
-        key = (B, str(device))
+    def _scale_row(self, which, B: int, device) -> torch.Tensor:
+        """the [B] scale tensor (`which`: a condition's name with one scale per condition, else None), built once per (B, device)"""
+        key = (which, B, str(device))
         if key not in self._scales:
-            if isinstance(self.scale, torch.Tensor):
-                if self.scale.numel() != B:
-                    raise ValueError(f"GuidedCMDM: `scale` holds {self.scale.numel()} values for a batch of {B}")
-                self._scales[key] = self.scale.to(device).contiguous()
+            scale = self.scale if which is None else self.scale[which]
+            if isinstance(scale, torch.Tensor):
+                if scale.numel() != B:
+                    name = "`scale`" if which is None else f"`scale[{which!r}]`"
+                    raise ValueError(f"GuidedCMDM: {name} holds {scale.numel()} values for a batch of {B}")
+                self._scales[key] = scale.to(device).contiguous()
             else:
-                self._scales[key] = torch.full((B,), self.scale, dtype=torch.float32, device=device)
-        return ffi.CfgArgs(self._scales[key].data_ptr(), int("text" in self.drop), int("pc" in self.drop),
-                           ffi.CFG_FORCE_MASKED if self.force_masked else 0)
+                self._scales[key] = torch.full((B,), scale, dtype=torch.float32, device=device)
+        return self._scales[key]
+
+    def _cfg(self, B: int, device):
+        """afm_cfg_args (one scale per condition: afm_cfg2_args) for a batch of B on `device`; the [B] scale tensors are kept on the wrapper."""
+        flags = ffi.CFG_FORCE_MASKED if self.force_masked else 0
+        if self.order is not None:
+            first, second = self.order
+            return ffi.Cfg2Args(self._scale_row(first, B, device).data_ptr(), self._scale_row(second, B, device).data_ptr(),
+                                GUIDANCE_DROPS.index(first), flags)
+        return ffi.CfgArgs(self._scale_row(None, B, device).data_ptr(), int("text" in self.drop), int("pc" in self.drop), flags)
 
     @staticmethod
     def _no_switches(kwargs) -> None:
@@ -684,7 +725,8 @@ class GuidedCMDM(nn.Module):
             raise ValueError(f"GuidedCMDM sets the condition masks itself: remove {used} from model_kwargs")
 
     def branches(self, x, timesteps, **kwargs):
-        """(x0_c, x0_u, x0_guided) of one guided evaluation - afm_cmdm_cfg_forward: the conditioned branch is CMDM.forward's launches."""
+        """(x0_c, x0_u, x0_guided) of one guided evaluation - afm_cmdm_cfg_forward: the conditioned branch is CMDM.forward's launches.
+        One scale per condition: (x0_c, x0_a, x0_u, x0_guided) - afm_cmdm_cfg2_forward."""
         self._no_switches(kwargs)
         m = self.model
         if m.training:
@@ -698,29 +740,31 @@ class GuidedCMDM(nn.Module):
             w = m._weights()
             cond = m.condition_tokens(**kwargs)
             fm = kwargs["x_mask"].to(device=x.device, dtype=torch.uint8).contiguous()
-            out = torch.empty((3,) + tuple(x.shape), dtype=torch.float32, device=x.device)
-            key = ("cfg", B, L, str(x.device))
+            two = self.order is not None
+            name = "afm_cmdm_cfg2" if two else "afm_cmdm_cfg"
+            out = torch.empty((4 if two else 3,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+            key = ("cfg2" if two else "cfg", B, L, str(x.device))
             if key not in m._ws:
-                nbytes = lib.afm_cmdm_cfg_workspace_bytes(C.byref(w), B, L)
+                nbytes = getattr(lib, name + "_workspace_bytes")(C.byref(w), B, L)
                 if nbytes < 0:
-                    ffi.check(int(nbytes), "afm_cmdm_cfg_workspace_bytes")
+                    ffi.check(int(nbytes), name + "_workspace_bytes")
                 m._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
             ws = m._ws[key]
             t = timesteps.to(device=x.device, dtype=torch.int64).contiguous()
-            ffi.check(lib.afm_cmdm_cfg_forward(C.byref(w), x.data_ptr(), t.data_ptr(), cond.data_ptr(), fm.data_ptr(), C.byref(cfg),
-                                               out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), B, L, ws.data_ptr(), ws.numel(),
-                                               ffi.stream_of(x)), "afm_cmdm_cfg_forward")
-        return out[0], out[1], out[2]
+            ffi.check(getattr(lib, name + "_forward")(C.byref(w), x.data_ptr(), t.data_ptr(), cond.data_ptr(), fm.data_ptr(), C.byref(cfg),
+                                                      *[o.data_ptr() for o in out], B, L, ws.data_ptr(), ws.numel(), ffi.stream_of(x)),
+                      name + "_forward")
+        return tuple(out)
 
     def forward(self, x, timesteps, **kwargs):
-        return self.branches(x, timesteps, **kwargs)[2]
+        return self.branches(x, timesteps, **kwargs)[-1]
 
     def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, **kw):
         """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range; with ``impute``: the guided form of
-        afm_cmdm_impute_loop_range): CMDM.afm_native_loop's arguments."""
+        afm_cmdm_impute_loop_range; one scale per condition: afm_cmdm_cfg2_loop_range, every form): CMDM.afm_native_loop's arguments."""
         self._no_switches(model_kwargs)
         if self.model.training:
             raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
+        cfg = self._cfg(x.shape[0], x.device)          # (a [B] scale of the wrong length is refused here)
         ffi.require_gpu(x)
-        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(self._cfg(x.shape[0], x.device), self.branch_streams), impute=impute,
-                                          **kw)
+        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams), impute=impute, **kw)

@@ -170,6 +170,19 @@ class ImputeStepArgs(C.Structure):
                 ("clip", i32), ("B", i32), ("per_sample", i64), ("seed", u64), ("sample_index0", i64), ("step", i32)]
 
 
+class Cfg2Args(C.Structure):
+    """afm_cfg2_args (v7-additive): two-scale guidance of the CMDM - device [B] scales of the first and second condition, first: 0 = text,
+    1 = pc, AFM_CFG_* flags."""
+    _fields_ = [("scale_first", c_f32p), ("scale_second", c_f32p), ("first", i32), ("flags", i32)]
+
+
+class Cfg2StepArgs(C.Structure):
+    """afm_cfg2_step_args (v7-additive): one two-scale sampling update from the three branches' pred_xstart, known / mask optional."""
+    _fields_ = [("x0_c", c_f32p), ("x0_a", c_f32p), ("x0_u", c_f32p), ("scale_first", c_f32p), ("scale_second", c_f32p), ("known", c_f32p),
+                ("mask", C.c_void_p), ("x_t", c_f32p), ("noise", c_f32p), ("x_next", c_f32p), ("c1", c_f32p), ("c2", c_f32p), ("sigma", c_f32p),
+                ("ddim", C.POINTER(DdimRows)), ("clip", i32), ("B", i32), ("per_sample", i64), ("seed", u64), ("sample_index0", i64), ("step", i32)]
+
+
 CFG_FORCE_MASKED = 0x1
 
 EXPORTS = {
@@ -210,6 +223,15 @@ EXPORTS = {
     "afm_cmdm_impute_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
                                              c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), c_f32p, C.c_void_p, i32, i32, u64, i64, i32, i32,
                                              C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_cfg2_combine": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i64, C.c_void_p]),
+    "afm_cfg2_step": (C.c_int, [C.POINTER(Cfg2StepArgs), C.c_void_p]),
+    "afm_cmdm_cfg2_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32]),
+    "afm_cmdm_cfg2_forward": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(Cfg2Args), c_f32p, c_f32p, c_f32p,
+                                        c_f32p, i32, i32, C.c_void_p, i64, C.c_void_p]),
+    "afm_cmdm_cfg2_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(Cfg2Args)]),
+    "afm_cmdm_cfg2_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                           c_f32p, c_f32p, c_f32p, C.POINTER(Cfg2Args), c_f32p, C.c_void_p, i32, i32, u64, i64, i32, i32,
+                                           C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

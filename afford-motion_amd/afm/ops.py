@@ -438,6 +438,65 @@ def impute_step(x0: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, x_t: 
     return out
 
 
+def cfg2_combine(x0_c: torch.Tensor, x0_a: torch.Tensor, x0_u: torch.Tensor, scale_first: torch.Tensor, scale_second: torch.Tensor, *,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Two-scale guidance of an x_start prediction (afm_cfg2_combine): (x0_u + scale_first[b] * (x0_a - x0_u)) + scale_second[b] *
+    (x0_c - x0_a), float32, every operation rounded on its own; both scales [B]."""
+    lib = ffi.load()
+    ffi.require_gpu(x0_c, x0_a, x0_u, scale_first, scale_second)
+    x0_c, x0_a, x0_u, s1, s2 = (ffi.f32c(v) for v in (x0_c, x0_a, x0_u, scale_first, scale_second))
+    B = x0_c.shape[0]
+    if s1.numel() != B or s2.numel() != B or x0_a.shape != x0_c.shape or x0_u.shape != x0_c.shape:
+        raise ValueError(f"cfg2_combine: each scale must hold one value per sample ({B}), got {tuple(s1.shape)} / {tuple(s2.shape)}; "
+                         f"branches {tuple(x0_c.shape)} / {tuple(x0_a.shape)} / {tuple(x0_u.shape)}")
+    out = torch.empty_like(x0_c) if out is None else out
+    ffi.check(lib.afm_cfg2_combine(x0_c.data_ptr(), x0_a.data_ptr(), x0_u.data_ptr(), s1.data_ptr(), s2.data_ptr(), out.data_ptr(), B,
+                                   x0_c.numel() // max(B, 1), ffi.stream_of(x0_c)), "afm_cfg2_combine")
+    return out
+
+
+def cfg2_step(x0_c: torch.Tensor, x0_a: torch.Tensor, x0_u: torch.Tensor, scale_first: torch.Tensor, scale_second: torch.Tensor,
+              x_t: torch.Tensor, noise: Optional[torch.Tensor], *, known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+              ddpm=None, ddim=None, clip: bool = False, seed: int = 0, sample_index0: int = 0, step: int = 0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One two-scale sampling update (afm_cfg2_step): cfg2_combine, impute with ``known`` / ``mask`` (both or neither), the clamp to
+    [-1, 1] if ``clip``, then the ddpm_step expression with ``ddpm`` = (c1, c2, sigma) per-sample rows or the ddim_step expression with
+    ``ddim`` = (a, b, c, d, sigma | None).  noise None: Philox."""
+    if (ddpm is None) == (ddim is None):
+        raise ValueError("cfg2_step: exactly one of ddpm= / ddim= rows")
+    if (known is None) != (mask is None):
+        raise ValueError("cfg2_step: known= and mask= go together")
+    lib = ffi.load()
+    ffi.require_gpu(x0_c, x0_a, x0_u, x_t)
+    x0_c, x0_a, x0_u, s1, s2, x_t = (ffi.f32c(v) for v in (x0_c, x0_a, x0_u, scale_first, scale_second, x_t))
+    B = x0_c.shape[0]
+    if s1.numel() != B or s2.numel() != B or x0_a.shape != x0_c.shape or x0_u.shape != x0_c.shape:
+        raise ValueError(f"cfg2_step: each scale must hold one value per sample ({B}), got {tuple(s1.shape)} / {tuple(s2.shape)}; "
+                         f"branches {tuple(x0_c.shape)} / {tuple(x0_a.shape)} / {tuple(x0_u.shape)}")
+    out = torch.empty_like(x0_c) if out is None else out
+    a = ffi.Cfg2StepArgs()
+    a.x0_c, a.x0_a, a.x0_u, a.scale_first, a.scale_second = x0_c.data_ptr(), x0_a.data_ptr(), x0_u.data_ptr(), s1.data_ptr(), s2.data_ptr()
+    a.x_t, a.x_next = x_t.data_ptr(), out.data_ptr()
+    if known is not None:
+        known, mask = ffi.f32c(known), _mask_u8(mask)
+        if known.shape != x0_c.shape or mask.shape != x0_c.shape:
+            raise ValueError(f"cfg2_step: known {tuple(known.shape)} and mask {tuple(mask.shape)} must have x0's shape {tuple(x0_c.shape)}")
+        a.known, a.mask = known.data_ptr(), mask.data_ptr()
+    nz = None if noise is None else ffi.f32c(noise)
+    a.noise = ffi.ptr(nz)
+    keep = [ffi.f32c(r) for r in (ddpm if ddpm is not None else ddim) if r is not None]
+    rows = None
+    if ddpm is not None:
+        a.c1, a.c2, a.sigma = (r.data_ptr() for r in keep)
+    else:
+        rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], keep[4].data_ptr() if len(keep) > 4 else None)
+        a.ddim = C.pointer(rows)
+    a.clip, a.B, a.per_sample = int(bool(clip)), B, x0_c.numel() // max(B, 1)
+    a.seed, a.sample_index0, a.step = seed & (2**64 - 1), sample_index0, step
+    ffi.check(lib.afm_cfg2_step(C.byref(a), ffi.stream_of(x0_c)), "afm_cfg2_step")
+    return out
+
+
 def randn(shape, device, *, seed: int, sample_index0: int = 0, step: int = 0) -> torch.Tensor:
     """Counter-based N(0,1) noise keyed by (seed, global sample index, step, element)."""
     lib = ffi.load()

@@ -9,7 +9,7 @@ exp(-d^2 / (2 sigma^2)) (datasets/humanml3d.py:763-774), looping `for k in range
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Mapping, Optional
 
 import torch
 
@@ -29,9 +29,15 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     keyed by (seed, sample_index0 + b), stage 2 uses seed + 1.  ``sampler`` = "ddpm" (p_sample_loop) or "ddim" (ddim_sample_loop with
     ``eta``) for both stages; DDIM runs the spaced process of each diffusion (e.g. timestep_respacing="ddim50").
     ``guidance_scale`` (a float or a [B] tensor; None = unguided): classifier-free guidance of the MOTION stage, dropping the conditions named
-    in ``guidance_drop`` (afm.cmdm.GuidedCMDM; the CDM of the first stage never reads the condition switches)."""
+    in ``guidance_drop`` (afm.cmdm.GuidedCMDM; the CDM of the first stage never reads the condition switches).  A mapping
+    ``{"pc": s_pc, "text": s_text}`` (insertion order = first, second) gives every condition a scale of its own; ``guidance_drop`` must
+    then name exactly the mapping's keys."""
     if sampler not in ("ddpm", "ddim"):
         raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+    if isinstance(guidance_scale, Mapping):          # (refused before the first stage runs)
+        dropped = {guidance_drop} if isinstance(guidance_drop, str) else set(guidance_drop)
+        if dropped != set(guidance_scale):
+            raise ValueError(f"guidance_drop {sorted(dropped)} contradicts the conditions of the guidance_scale mapping {list(guidance_scale)}")
 
     def loop(diffusion, *args, **kw):
         if sampler == "ddim":

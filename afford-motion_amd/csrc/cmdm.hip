@@ -12,6 +12,7 @@
 //   (gather motion tokens, +bias, fused DDPM posterior update).
 // Classifier-free guided steps (afm_cmdm_cfg_*): this sequence twice - the conditioned branch, then the unconditioned one (struct Branch) -
 // with both motion_layer GEMMs storing pred_xstart, and one elementwise launch for the guided update (afm_sampling_update).
+// Two-scale guided steps (afm_cmdm_cfg2_*): three times - conditioned, the middle branch (only the first condition kept), unconditioned.
 #include <memory>
 
 #include "sample_loop.h"
@@ -360,6 +361,15 @@ int uncond_setup(const afm_cmdm_weights& w, const afm_cfg_args* cfg, const uint8
     return 0;
 }
 
+// Two-scale guidance as the two single-scale descriptions its extra branches are built from: *u drops both conditions (scale: the first
+// condition's, the row cfg_combine2's inner cfg_combine reads), *a drops the second condition only (always a masked form).
+int cfg2_split(const afm_cfg2_args* c2, afm_cfg_args* u, afm_cfg_args* a) {
+    if (!c2 || !c2->scale_first || !c2->scale_second || (c2->first != 0 && c2->first != 1)) return AFM_E_BADARG;
+    *u = afm_cfg_args{c2->scale_first, 1, 1, c2->flags & AFM_CFG_FORCE_MASKED, nullptr};
+    *a = afm_cfg_args{c2->scale_first, c2->first == 1 ? 1 : 0, c2->first == 0 ? 1 : 0, 0, nullptr};
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int afm_version(void) { return AFM_ABI_VERSION; }
@@ -412,6 +422,38 @@ extern "C" int afm_cmdm_cfg_forward(const afm_cmdm_weights* w, const float* x_t,
     return afm_cfg_combine(x0_c, x0_u, cfg->scale, x0_guided, B, (int64_t)L * w->motion_dim, stream);
 }
 
+extern "C" int64_t afm_cmdm_cfg2_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L) {
+    if (validate(w, B, L) != 0) return AFM_E_BADARG;
+    return carve(*w, B, L, nullptr).bytes + 3 * align256((int64_t)B * L * w->motion_dim * 4);
+}
+
+// The three branches in turn on one workspace (no branch's layout is larger than the conditioned one's), then the combine launch.
+extern "C" int afm_cmdm_cfg2_forward(const afm_cmdm_weights* w, const float* x_t, const int64_t* t, const float* cond_tokens,
+                                     const uint8_t* frame_mask, const afm_cfg2_args* cfg, float* x0_c, float* x0_a, float* x0_u, float* x0_guided,
+                                     int32_t B, int32_t L, void* workspace, int64_t workspace_bytes, void* stream) {
+    AFM_TRY(validate(w, B, L));
+    if (!x_t || !t || !cond_tokens || !frame_mask || !workspace || !x0_guided) return AFM_E_BADARG;
+    const afm_cmdm_weights wc = callers_pack(*w, AFM_CMDM_FUSED_LN);
+    afm_cfg_args cu, ca;
+    afm_cmdm_weights wu, wa;
+    Branch bru, bra;
+    AFM_TRY(cfg2_split(cfg, &cu, &ca));
+    AFM_TRY(uncond_setup(wc, &cu, frame_mask, &wu, &bru));
+    AFM_TRY(uncond_setup(wc, &ca, frame_mask, &wa, &bra));
+    if (B == 0) return 0;
+    const Workspace ws = carve(wc, B, L, workspace), wsu = carve(wu, B, L, workspace);
+    const int64_t xb = align256((int64_t)B * L * w->motion_dim * 4);
+    if (ws.bytes + 3 * xb > workspace_bytes || wsu.bytes > ws.bytes) return AFM_E_WORKSPACE;
+    if (!x0_c) x0_c = (float*)((char*)workspace + ws.bytes);
+    if (!x0_a) x0_a = (float*)((char*)workspace + ws.bytes + xb);
+    if (!x0_u) x0_u = (float*)((char*)workspace + ws.bytes + 2 * xb);
+    const hipStream_t s = (hipStream_t)stream;
+    AFM_TRY(forward_impl(wc, x_t, t, cond_tokens, frame_mask, x0_c, nullptr, B, L, ws, true, s));
+    AFM_TRY(forward_impl(wa, x_t, t, cond_tokens, frame_mask, x0_a, nullptr, B, L, ws, true, s, nullptr, &bra));
+    AFM_TRY(forward_impl(wu, x_t, t, wu.n_cond ? cond_tokens : nullptr, frame_mask, x0_u, nullptr, B, L, wsu, true, s, nullptr, &bru));
+    return afm_cfg2_combine(x0_c, x0_a, x0_u, cfg->scale_first, cfg->scale_second, x0_guided, B, (int64_t)L * w->motion_dim, stream);
+}
+
 extern "C" int64_t afm_cmdm_sched_scratch_bytes(int32_t n_steps, int32_t B) {
     if (n_steps <= 0 || B < 0) return AFM_E_BADARG;
     return align256((int64_t)n_steps * B * 8) + 3 * align256((int64_t)n_steps * B * 4);
@@ -435,7 +477,7 @@ namespace {
 constexpr int MAX_SUB = 16;           // sub-batches (streams) of one loop call
 constexpr int NEV = 2 * AFM_MAX_LAYERS;      // events of the paired schedule: two cross-stream edges per layer
 
-// the arguments of the six loop entry points
+// the arguments of the seven loop entry points
 struct LoopCall {
     const afm_cmdm_weights* w;
     float* x;
@@ -446,10 +488,14 @@ struct LoopCall {
     LoopArgs a;                       // (a.streams: one side stream per sub-batch)
     const float* known = nullptr;     // imputing loop: [B][L][motion_dim] each, both set (neither: no imputation)
     const uint8_t* mask = nullptr;
+    // two-scale guided loop: `cfg` then describes the unconditioned branch (scale: the first condition's row), cfg_a the middle branch
+    // (only the first condition kept), scale2 the second condition's row [B]
+    const afm_cfg_args* cfg_a = nullptr;
+    const float* scale2 = nullptr;
 };
 
 struct SubBatch : SubRange {
-    Workspace ws, wsu;                // wsu: the unconditioned branch's (guided loops), behind ws
+    Workspace ws, wsa, wsu;           // guided loops: wsa the middle branch's (two scales only) behind ws, wsu the unconditioned branch's behind that
     // guided loop with branch streams: the unconditioned branch runs on `branch`; two events order it against the guided update, the only
     // writer of x and of its K-padded copy (x_ready: x is ready, u_ready: the branch's pred_xstart is ready)
     hipStream_t branch;
@@ -457,30 +503,36 @@ struct SubBatch : SubRange {
 };
 
 // carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
-int64_t carve_sub(const afm_cmdm_weights& w, const afm_cmdm_weights* wu, int L, char* base, SubBatch* sb) {
+int64_t carve_sub(const afm_cmdm_weights& w, const afm_cmdm_weights* wa, const afm_cmdm_weights* wu, int L, char* base, SubBatch* sb) {
     sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
-    if (!wu) return sb->ws.bytes;
+    int64_t off = sb->ws.bytes;
     // (2 "noise steps": a pred_xstart region of its own, as little noise space as the layout allows)
-    sb->wsu = carve(*wu, sb->count, L, base ? base + sb->ws.bytes : nullptr, 2);
-    sb->wsu.xpad = sb->ws.xpad;       // one K-padded copy of x_t serves both branches
-    return sb->ws.bytes + sb->wsu.bytes;
+    for (int i = 0; i < 2; ++i) {
+        const afm_cmdm_weights* wb = i == 0 ? wa : wu;
+        if (!wb) continue;
+        Workspace& wsb = i == 0 ? sb->wsa : sb->wsu;
+        wsb = carve(*wb, sb->count, L, base ? base + off : nullptr, 2);
+        wsb.xpad = sb->ws.xpad;       // one K-padded copy of x_t serves every branch
+        off += wsb.bytes;
+    }
+    return off;
 }
 
-int64_t loop_workspace_bytes(const afm_cmdm_weights& w, const afm_cmdm_weights* wu, int B, int L, int n_streams) {
+int64_t loop_workspace_bytes(const afm_cmdm_weights& w, const afm_cmdm_weights* wa, const afm_cmdm_weights* wu, int B, int L, int n_streams) {
     const int n = sub_count(B, n_streams, MAX_SUB);
     int64_t total = 0;
     for (int s = 0; s < n; ++s) {
         SubBatch sb = {};
         sub_range(B, n, s, &sb.start, &sb.count);
-        total += carve_sub(w, wu, L, nullptr, &sb);
+        total += carve_sub(w, wa, wu, L, nullptr, &sb);
     }
     return total;
 }
 
 // what a loop call fixes before its first launch: the loop's own weight packs, the sub-batches with their streams and workspaces, the form
 struct LoopPlan {
-    afm_cmdm_weights w, wu;           // the loop's copies: flags (private bits, tile code) set here; wu: the unconditioned branch's pack
-    Branch br;
+    afm_cmdm_weights w, wu, wa;       // the loop's copies: flags (private bits, tile code) set here; wu / wa: the unconditioned / middle branch's pack
+    Branch br, bra;
     int nsub;                         // 0: an empty batch, nothing to enqueue
     SubBatch sb[MAX_SUB];
     bool paired;                      // AFM_CMDM_PAIR_LAUNCH, two sub-batches: every step after the first is recorded and issued interleaved
@@ -496,6 +548,12 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     // (afm_sampling_update).  Both branches read the same x / K-padded copy; only the update writes them.
     p->br = {};
     if (c.cfg) AFM_TRY(uncond_setup(*c.w, c.cfg, c.frame_mask, &p->wu, &p->br));
+    p->bra = {};
+    if (c.cfg_a) {
+        if (!c.cfg || !c.scale2 || !c.frame_mask) return AFM_E_BADARG;
+        if (c.cfg->branch_streams) return AFM_E_UNSUPPORTED;       // (four hardware queues do not fit 2 sub-batches x 3 branches)
+        AFM_TRY(uncond_setup(*c.w, c.cfg_a, c.frame_mask, &p->wa, &p->bra));
+    }
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     p->nsub = 0;
     if (a.B == 0) return 0;
@@ -506,7 +564,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         SubBatch& sb = p->sb[s];
         sb = {};
         sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, c.cfg ? &p->wu : nullptr, c.L, (char*)a.workspace + off, &sb);
+        off += carve_sub(*c.w, c.cfg_a ? &p->wa : nullptr, c.cfg ? &p->wu : nullptr, c.L, (char*)a.workspace + off, &sb);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
         if (p->branch_streams) sb.branch = (hipStream_t)c.cfg->branch_streams[s];
     }
@@ -531,6 +589,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         if (big) p->w.flags |= 14 << AFM_CMDM_WIDE_TILE_SHIFT;
     }
     if (c.cfg) { const int nc_u = p->wu.n_cond; p->wu = p->w; p->wu.n_cond = nc_u; }       // the loop's flags (tile code, private bits) on the branch's pack
+    if (c.cfg_a) p->wa = p->w;                                                             // (a masked form: the full layout)
     p->paired = (p->w.flags & AFM_CMDM_PAIR_LAUNCH) && p->nsub == 2 && p->sb[0].count > 0 && p->sb[1].count > 0;
     p->row = (int64_t)c.L * c.w->motion_dim;
     return 0;
@@ -557,12 +616,14 @@ int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_d
                         c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr, nullptr, dd, sb.count, c.L, sb.ws, j == 0, sb.stream, rec);
 }
 
-// the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and the unconditioned branch's, wsu.x0), in place on x, with the
+// the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and the unconditioned branch's, wsu.x0; two scales: and the middle
+// branch's, wsa.x0), in place on x, with the
 // K-padded copy the next step reads
 int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const float* noise) {
     const afm_cmdm_weights& w = l.p.w;
     Update u = loop_update(l.c.a, rows, sb.ws.x0, sub_x(l, sb), noise, l.p.row, w.flags & AFM_CMDM_CLIP_X0);
     if (l.c.cfg) { u.x0_u = sb.wsu.x0; u.scale = l.c.cfg->scale + sb.start; }
+    if (l.c.cfg_a) { u.x0_a = sb.wsa.x0; u.scale2 = l.c.scale2 + sb.start; }
     if (l.c.mask) { u.known = l.c.known + (int64_t)sb.start * l.p.row; u.mask = l.c.mask + (int64_t)sb.start * l.p.row; }
     u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
     return afm_sampling_update(u, sb.count, sb.stream);
@@ -582,6 +643,10 @@ int guided_step(const Loop& l, const SubBatch& sb, int j) {
     StepRows rows;
     afm_ddpm_args dd;
     AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
+    const float* conds = c.cond_tokens ? c.cond_tokens + (int64_t)sb.start * w.n_cond * w.d : nullptr;
+    const uint8_t* fmask = c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr;
+    // two scales: the middle branch behind the conditioned one on the sub-batch's stream, on its own workspace
+    if (c.cfg_a) AFM_TRY(forward_impl(l.p.wa, sub_x(l, sb), rows.t, conds, fmask, nullptr, &dd, sb.count, c.L, sb.wsa, j == 0, sb.stream, nullptr, &l.p.bra));
     // step 0: the branch's prologue rewrites the shared K-padded copy (same values), so it starts behind the conditioned branch;
     // later steps: behind the previous update, next to the conditioned branch
     const hipStream_t su = bs ? sb.branch : sb.stream;
@@ -589,9 +654,7 @@ int guided_step(const Loop& l, const SubBatch& sb, int j) {
         if (j == 0) (void)hipEventRecord(sb.x_ready, sb.stream);
         (void)hipStreamWaitEvent(su, sb.x_ready, 0);
     }
-    const int rc = forward_impl(wu, sub_x(l, sb), rows.t, wu.n_cond && c.cond_tokens ? c.cond_tokens + (int64_t)sb.start * w.n_cond * w.d : nullptr,
-                                c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr, nullptr, &dd, sb.count, c.L, sb.wsu, j == 0, su,
-                                nullptr, &l.p.br);
+    const int rc = forward_impl(wu, sub_x(l, sb), rows.t, wu.n_cond ? conds : nullptr, fmask, nullptr, &dd, sb.count, c.L, sb.wsu, j == 0, su, nullptr, &l.p.br);
     if (bs) {       // (also behind a failed branch: the sub-batch's stream never runs ahead of its branch stream)
         (void)hipEventRecord(sb.u_ready, su);
         (void)hipStreamWaitEvent(sb.stream, sb.u_ready, 0);
@@ -696,7 +759,7 @@ int sample_loop_impl(const LoopCall& c) {
 
 extern "C" int64_t afm_cmdm_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams) {
     if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
-    return loop_workspace_bytes(*w, nullptr, B, L, n_streams);
+    return loop_workspace_bytes(*w, nullptr, nullptr, B, L, n_streams);
 }
 
 extern "C" int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg) {
@@ -705,7 +768,18 @@ extern "C" int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, 
     Branch br;
     const uint8_t some_mask = 0;                              // (sizes do not depend on the frame mask)
     if (uncond_setup(*w, cfg, &some_mask, &wu, &br) != 0) return AFM_E_BADARG;
-    return loop_workspace_bytes(*w, &wu, B, L, n_streams);
+    return loop_workspace_bytes(*w, nullptr, &wu, B, L, n_streams);
+}
+
+extern "C" int64_t afm_cmdm_cfg2_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg2_args* cfg) {
+    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
+    afm_cfg_args cu, ca;
+    afm_cmdm_weights wu, wa;
+    Branch br;
+    const uint8_t some_mask = 0;                              // (sizes do not depend on the frame mask)
+    if (cfg2_split(cfg, &cu, &ca) != 0 || uncond_setup(*w, &cu, &some_mask, &wu, &br) != 0 || uncond_setup(*w, &ca, &some_mask, &wa, &br) != 0)
+        return AFM_E_BADARG;
+    return loop_workspace_bytes(*w, &wa, &wu, B, L, n_streams);
 }
 
 extern "C" int afm_cmdm_sample_loop(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
@@ -769,4 +843,18 @@ extern "C" int afm_cmdm_impute_loop_range(const afm_cmdm_weights* w, float* x, c
     if (rows) d_c1 = d_c2 = d_sigma = nullptr;
     return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
                              sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask});
+}
+
+extern "C" int afm_cmdm_cfg2_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                                        const uint8_t* frame_mask, const float* step_noise, const int64_t* d_timestep_map,
+                                        const afm_ddim_rows* rows, const float* d_c1, const float* d_c2, const float* d_sigma,
+                                        const afm_cfg2_args* cfg, const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step,
+                                        uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                                        int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
+    afm_cfg_args cu, ca;
+    if (first_step < 0 || !frame_mask || !known != !mask) return AFM_E_BADARG;
+    AFM_TRY(cfg2_split(cfg, &cu, &ca));
+    if (rows) d_c1 = d_c2 = d_sigma = nullptr;
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, &cu, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, &ca, cfg->scale_second});
 }

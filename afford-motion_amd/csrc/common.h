@@ -320,6 +320,18 @@ __device__ __forceinline__ float cfg_combine(float x0_c, float x0_u, float s) {
     const float m = s * df;
     return x0_u + m;
 }
+// ---- two-scale guidance (one scale per condition), one element: the three evaluations u (both conditions dropped), a (only the first
+// kept) and c (nothing dropped), s1 / s2 = the first / second condition's scale of the element's sample:
+//   g1 = u + s1 * (a - u)   (== cfg_combine(a, u, s1));   x0 = g1 + s2 * (c - a)
+// float32, this association, every operation rounded on its own.  The only place the expression is written: afm_cfg2_combine, the update of
+// afm_cfg2_step and of the two-scale native loops call this helper.  No shortcut for equal or zero scales.
+__device__ __forceinline__ float cfg_combine2(float x0_c, float x0_a, float x0_u, float s1, float s2) {
+#pragma clang fp contract(off)
+    const float g1 = cfg_combine(x0_a, x0_u, s1);
+    const float df = x0_c - x0_a;
+    const float m = s2 * df;
+    return g1 + m;
+}
 // the ancestral (DDPM) update of one element: (c1 * x0 + c2 * x_t) + sigma * noise, every operation rounded on its own (the reference's
 // float32 torch expression).  The sampling update kernel (afm_ddpm_step, the guided updates) calls this helper.  The fused DDPM updates of
 // the GEMM epilogue and the CDM output kernels spell the expression inline with contraction allowed ("Contraction at the fused

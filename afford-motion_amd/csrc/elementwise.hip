@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __r
 }
 
 // The sampling update of sample_loop.h (afm_loop::Update), one quad of a sample per thread iteration: v = x0, or cfg_combine(x0, x0_u,
-// scale[b]) when guided, then known where mask is set (a select: known is not read where mask == 0; the mask by byte loads, a sample's base
+// scale[b]) when guided (cfg_combine2(x0, x0_a, x0_u, scale[b], scale2[b]) with a middle branch), then known where mask is set (a select: known is not read where mask == 0; the mask by byte loads, a sample's base
 // need not be 4-aligned), clamped if asked; then ddpm_update (rows c1 / c2 / sg per sample) or ddim_update (rows rec, or ra..rd, per sample;
 // sg == NULL: no noise term).  Every operation is one of common.h's individually rounded helpers (the reference's float32 torch expression,
 // bit for bit).  xn may alias xt (one thread reads then writes an element).  noise == NULL with a noise term: Philox keyed by the quad q.
@@ -52,6 +52,7 @@ __global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __r
 __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Update p) {
     const int b = blockIdx.y;
     const float s = p.x0_u ? p.scale[b] : 0.f;
+    const float s2 = p.x0_a ? p.scale2[b] : 0.f;
     const float sg = p.sg ? p.sg[b] : 0.f;
     float4 r = make_float4(0.f, 1.f, 0.f, 0.f);
     float c1 = 0.f, c2 = 0.f;
@@ -68,7 +69,8 @@ __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Up
             if (i < p.per_sample) {
                 const int64_t g = base + i;
                 float v = p.x0[g];
-                if (p.x0_u) v = cfg_combine(v, p.x0_u[g], s);
+                if (p.x0_a) v = cfg_combine2(v, p.x0_a[g], p.x0_u[g], s, s2);
+                else if (p.x0_u) v = cfg_combine(v, p.x0_u[g], s);
                 if (p.mask && p.mask[g]) v = p.known[g];
                 if (p.clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised (NaN passes through, as torch.clamp)
                 const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
@@ -250,12 +252,13 @@ int enqueue_update(const afm_loop::Update& p, int32_t B, hipStream_t s) {
 
 __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream) {
     if (!p.x0 || !p.xt || !p.xn || !p.x0_u != !p.scale || !p.known != !p.mask || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
+    if (!p.x0_a != !p.scale2 || (p.x0_a && !p.x0_u)) return AFM_E_BADARG;          // a middle branch: both scales and the unconditioned branch
     if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && p.rd)) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
     if (p.sg && !p.noise && !p.philox) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside their launch)
     if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
     if (B == 0) return 0;
     if (!p.x0_u) return enqueue_update(p, B, (hipStream_t)stream);
-    AfmProf prof(AFM_PROF_MISC, 5.0 * B * p.per_sample, (hipStream_t)stream);          // (profiling records: the guided launches only)
+    AfmProf prof(AFM_PROF_MISC, (p.x0_a ? 6.0 : 5.0) * B * p.per_sample, (hipStream_t)stream);          // (profiling records: the guided launches only)
     return enqueue_update(p, B, (hipStream_t)stream);
 }
 
@@ -293,6 +296,16 @@ extern "C" int afm_cfg_step(const afm_cfg_step_args* a, void* stream) {
     if (!a || !a->x0_c || !a->x0_u || !a->scale) return AFM_E_BADARG;
     afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
     p.x0_u = a->x0_u; p.scale = a->scale; p.clip = a->clip ? 1 : 0;
+    if (a->ddim) set_ddim_rows(&p, a->ddim);
+    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    return afm_sampling_update(p, a->B, stream);
+}
+
+extern "C" int afm_cfg2_step(const afm_cfg2_step_args* a, void* stream) {
+    if (!a || !a->x0_c || !a->x0_a || !a->x0_u || !a->scale_first || !a->scale_second || !a->known != !a->mask) return AFM_E_BADARG;
+    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
+    p.x0_a = a->x0_a; p.x0_u = a->x0_u; p.scale = a->scale_first; p.scale2 = a->scale_second;
+    p.known = a->known; p.mask = a->mask; p.clip = a->clip ? 1 : 0;
     if (a->ddim) set_ddim_rows(&p, a->ddim);
     else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
     return afm_sampling_update(p, a->B, stream);
@@ -378,6 +391,17 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restric
         out[base + i] = cfg_combine(x0c[base + i], x0u[base + i], s);
 }
 
+// x0_guided = cfg_combine2(x0_c, x0_a, x0_u, scale_first[b], scale_second[b]) per element
+__global__ __launch_bounds__(256) void cfg2_combine_kernel(const float* __restrict__ x0c, const float* __restrict__ x0a, const float* __restrict__ x0u,
+                                                           const float* __restrict__ s1, const float* __restrict__ s2, float* __restrict__ out,
+                                                           int64_t per_sample) {
+    const int b = blockIdx.y;
+    const float sa = s1[b], sb = s2[b];
+    const int64_t base = (int64_t)b * per_sample;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * blockDim.x)
+        out[base + i] = cfg_combine2(x0c[base + i], x0a[base + i], x0u[base + i], sa, sb);
+}
+
 }  // namespace
 
 // ---- imputation of an x0 alone (the imputing updates are the sampling update above)
@@ -402,6 +426,17 @@ extern "C" int afm_cfg_combine(const float* x0_c, const float* x0_u, const float
     if (B == 0) return 0;
     AfmProf prof(AFM_PROF_MISC, 3.0 * B * per_sample, (hipStream_t)stream);
     hipLaunchKernelGGL(cfg_combine_kernel, stream_grid(per_sample, 1024, B), dim3(256), 0, (hipStream_t)stream, x0_c, x0_u, scale, out, per_sample);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int afm_cfg2_combine(const float* x0_c, const float* x0_a, const float* x0_u, const float* scale_first, const float* scale_second,
+                                float* out, int32_t B, int64_t per_sample, void* stream) {
+    if (!x0_c || !x0_a || !x0_u || !scale_first || !scale_second || !out || B < 0 || per_sample <= 0) return AFM_E_BADARG;
+    if (B == 0) return 0;
+    AfmProf prof(AFM_PROF_MISC, 4.0 * B * per_sample, (hipStream_t)stream);
+    hipLaunchKernelGGL(cfg2_combine_kernel, stream_grid(per_sample, 1024, B), dim3(256), 0, (hipStream_t)stream, x0_c, x0_a, x0_u, scale_first,
+                       scale_second, out, per_sample);
     AFM_CHECK_LAUNCH();
     return 0;
 }

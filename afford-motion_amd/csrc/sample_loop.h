@@ -12,7 +12,7 @@ __attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tm
 __attribute__((visibility("hidden"))) int afm_randn_steps(float*, int32_t, int64_t, uint64_t, int64_t, int32_t, int32_t, void*);      // [nsteps][B][per_sample]
 namespace afm_loop { struct Update; }
 // checks and enqueues one sampling update over B samples (AFM_E_BADARG: a NULL tensor or row, x0_u without scale or known without mask or
-// the reverse, a noise term without noise unless `philox`, xpad with ldpad < cols; B == 0: nothing to do)
+// the reverse, a middle branch x0_a without both scales and x0_u, a noise term without noise unless `philox`, xpad with ldpad < cols; B == 0: nothing to do)
 __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream);
 
 namespace afm_loop {
@@ -22,6 +22,8 @@ namespace afm_loop {
 struct Update {
     const float* x0;                // pred_xstart (the conditioned branch's when guided)
     const float *x0_u, *scale;      // guided: the unconditioned branch's pred_xstart and scale [B]; both NULL: unguided
+    const float *x0_a, *scale2;     // two-scale guided (cfg_combine2): the middle branch's pred_xstart (only the first condition kept) and the
+                                    //   second condition's scale [B], `scale` being the first's; both NULL: one scale.  Need x0_u and scale.
     const float* known;             // imputation [B][per_sample]: x0 (guided: the combination) := mask ? known : x0, before the clamp;
     const uint8_t* mask;            //   nonzero = known; both NULL: none
     const float* xt;

@@ -736,6 +736,65 @@ int afm_cmdm_impute_loop_range(const afm_cmdm_weights* w, float* x, const float*
                                uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
 
+/* ---- Two-scale guidance of the CMDM: one scale per condition (v7-additive: new structs and entry points, no existing struct changed).
+ * The reference drops text and scene contact independently in training, so a checkpoint is a guidance model for each condition
+ * separately.  (first, second) name the two conditions in the caller's order; three evaluations share x_t, t and the frame mask:
+ *   u: both dropped (the compact unconditioned form of afm_cfg_args, or the masked one with AFM_CFG_FORCE_MASKED),
+ *   a: only `first` kept (the masked partial-drop form: the second condition's tokens key-masked),
+ *   c: nothing dropped (the ordinary forward).
+ * For sample b, in float32, no contraction, this association:
+ *   g1 = u + scale_first[b] * (a - u);      x0_guided = g1 + scale_second[b] * (c - a)
+ * No shortcut for equal or zero scales: equal scales are NOT bit-equal to the single-scale form.  frame_mask is required (a is a masked
+ * form).  Branch streams are not built for three branches. */
+typedef struct {
+    const float* scale_first;              /* device [B]: the first condition's scale per sample                          */
+    const float* scale_second;             /* device [B]: the second condition's                                          */
+    int32_t first;                         /* the first condition: 0 = text, 1 = pc (the second is the other one)         */
+    int32_t flags;                         /* AFM_CFG_FORCE_MASKED: applies to u                                          */
+} afm_cfg2_args;
+
+/* out = (x0_u + scale_first[b] * (x0_a - x0_u)) + scale_second[b] * (x0_c - x0_a), [B][per_sample]; out may alias any input. */
+int afm_cfg2_combine(const float* x0_c, const float* x0_a, const float* x0_u, const float* scale_first, const float* scale_second,
+                     float* out, int32_t B, int64_t per_sample, void* stream);
+
+/* One two-scale sampling update from the three branches' pred_xstart: x0 = the combination above, := known where mask is set (known /
+ * mask: both or neither), clamped to [-1, 1] if `clip`, then the afm_ddpm_step expression (rows c1 / c2 / sigma, ddim == NULL) or the
+ * afm_ddim_step expression (rows *ddim).  Noise as afm_cfg_step.  x_next may alias x_t.  Bit-identical to afm_cfg2_combine ->
+ * afm_impute -> afm_clamp -> afm_ddpm_step / afm_ddim_step. */
+typedef struct {
+    const float* x0_c; const float* x0_a; const float* x0_u;        /* [B][per_sample] x 3      */
+    const float* scale_first; const float* scale_second;            /* [B] x 2                  */
+    const float* known; const uint8_t* mask;                        /* [B][per_sample] or NULL  */
+    const float* x_t; const float* noise; float* x_next;            /* [B][per_sample]          */
+    const float* c1; const float* c2; const float* sigma;           /* DDPM rows [B]            */
+    const afm_ddim_rows* ddim;                                      /* or DDIM rows [B]         */
+    int32_t clip; int32_t B; int64_t per_sample;
+    uint64_t seed; int64_t sample_index0; int32_t step;
+} afm_cfg2_step_args;
+int afm_cfg2_step(const afm_cfg2_step_args* args, void* stream);
+
+/* The three branches of one two-scale evaluation and their combination: x0_c, x0_a, x0_u, x0_guided [B,L,motion_dim] (the branches may
+ * be NULL: the workspace then holds them).  One workspace (afm_cmdm_workspace_bytes plus 3 * B * L * motion_dim floats) serves the three
+ * branches in turn. */
+int64_t afm_cmdm_cfg2_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L);
+int afm_cmdm_cfg2_forward(const afm_cmdm_weights* w, const float* x_t, const int64_t* t, const float* cond_tokens,
+                          const uint8_t* frame_mask, const afm_cfg2_args* cfg, float* x0_c, float* x0_a, float* x0_u, float* x0_guided,
+                          int32_t B, int32_t L, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The two-scale native loop, every form behind one entry, like afm_cmdm_impute_loop_range: both kinds of rows (rows != NULL: DDIM,
+ * d_c1 / d_c2 / d_sigma ignored), known / mask [B][L][motion_dim] optional (both or neither).  Per sub-batch and step, all on the
+ * sub-batch's stream: the conditioned branch, the a branch on a workspace of its own behind it, the u branch behind that, and ONE update
+ * launch (the afm_cfg2_step expression, in place on x, plus the next step's K-padded copy).  The three branches read the same x and the
+ * one K-padded copy.  The motion_layer GEMMs store pred_xstart with the plain epilogue, for DDPM too.  AFM_CMDM_PAIR_LAUNCH and
+ * AFM_CMDM_FUSED_LN are ignored.  workspace >= afm_cmdm_cfg2_loop_workspace_bytes; sched_scratch as the unguided loop of the same rows. */
+int64_t afm_cmdm_cfg2_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg2_args* cfg);
+int afm_cmdm_cfg2_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
+                             const uint8_t* frame_mask, const float* step_noise, const int64_t* d_timestep_map,
+                             const afm_ddim_rows* rows, const float* d_c1, const float* d_c2, const float* d_sigma,
+                             const afm_cfg2_args* cfg, const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step,
+                             uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                             int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
