@@ -333,6 +333,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         self.loop_sub_batches = 0
         if self.arch != "Perceiver":
             self.afm_native_loop = None         # other archs sample step by step
+            self.afm_native_impute_loop = None
         self.sub_batches = 1                    # per-call sub-batches of forward(): >1 costs more host time per step than it hides (measured)
         self._streams = []
         self.no_fold = False            # measurement: the layer-by-layer sampling form (what training-mode forward also runs)
@@ -633,6 +634,22 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         slices the chain (afm_cdm_sample_loop_range) so a tqdm bar can advance, with bit-identical results.  The batch
         runs as `loop_sub_batches` sub-batches on their own stream pairs (see __init__; bit-identical results).  ``snapshots`` =
         {executed step count: None} is filled with clones of x after those steps, as in CMDM.afm_native_loop."""
+        return self._native_loop(diffusion, x, model_kwargs, None, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=progress,
+                                 snapshots=snapshots, clip_denoised=clip_denoised, ddim_eta=ddim_eta)
+
+    def afm_native_impute_loop(self, diffusion, x, model_kwargs, impute, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
+                               clip_denoised=False, ddim_eta: Optional[float] = None):
+        """afm_native_loop with an afm.diffusion.Impute ([B, N, contact_dim], the model's normalised contact space): its known values are
+        written over every step's pred_xstart before the clamp inside the loop (afm_cdm_impute_loop_range) - fused into dec_point's update
+        in the row-less form, one update launch behind the stored pred_xstart in the other two.  Every keyword as afm_native_loop."""
+        if impute is None:
+            raise ValueError("afm_native_impute_loop needs an Impute; afm_native_loop samples without one")
+        impute.check(x)
+        return self._native_loop(diffusion, x, model_kwargs, impute, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=progress,
+                                 snapshots=snapshots, clip_denoised=clip_denoised, ddim_eta=ddim_eta)
+
+    def _native_loop(self, diffusion, x, model_kwargs, impute, *, step_noise, seed, sample_index0, progress, snapshots, clip_denoised, ddim_eta):
+        """the body of both native loops: with ``impute`` the entry is afm_cdm_impute_loop_range and known / mask ride along"""
         if self.arch != "Perceiver":
             raise NotImplementedError("the native loop covers the Perceiver arch")
         lib = ffi.load()
@@ -664,18 +681,22 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if clip_denoised:
                 w.flags |= ffi.CDM_CLIP_X0                   # per call: the next _weights() rewrites the flags
             entry = "afm_cdm_sample_loop_range" if ddim is None else "afm_cdm_ddim_loop_range"
+            if impute is not None:
+                entry = "afm_cdm_impute_loop_range"
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
                 rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
                     (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
+                if impute is not None:      # one entry for both updates: both kinds of rows, then known and mask
+                    rows = ((rows[0], None, None, None) if ddim is not None else (None,) + rows) + (impute.known.data_ptr(), impute.mask.data_ptr())
                 ffi.check(getattr(lib, entry)(
                     C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(), nz, tab.timestep_map[lo:].data_ptr(),
                     *rows, j1 - j0, j0, seed & (2**64 - 1), sample_index0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream),
                     entry)
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
-            self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu, ddim)
+            self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu, ddim, impute)
         return x
 
     # ------------------------------------------------------------------ 'MLP' arch (per-operator composition, inference and training)

@@ -70,16 +70,20 @@ class LossType(enum.Enum):
 
 
 class Impute:
-    """Known motion values imputed into every pred_xstart of a sampling chain (editing: keyframes to in-between, a root trajectory, a
-    prefix to continue): ``x0 = where(mask, known, x0)`` after the denoiser and before the clamp - what the reference's ``denoised_fn``
-    hook of p_mean_variance exists for (gaussian_diffusion.py:289-294).  A select: ``known`` is never read where the mask is 0.
+    """Known values imputed into every pred_xstart of a sampling chain - motion (editing: keyframes to in-between, a root trajectory, a
+    prefix to continue) or contact (steering the first stage: contact pinned on the points of a chosen object, zero contact on a region
+    to keep clear): ``x0 = where(mask, known, x0)`` after the denoiser and before the clamp - what the reference's ``denoised_fn``
+    hook of p_mean_variance exists for (gaussian_diffusion.py:289-294).  A select, never a blend: where the mask is 0 nothing of ``known``
+    reaches the result (a NaN there does not propagate).
 
-    ``known``: float32 [B, L, D] in the model's normalised motion space.  ``mask``: bool or uint8 (nonzero = known), broadcastable to it
-    ([L, D], [B, L, 1], [B, 1, D], ...); expanded ONCE to a contiguous uint8 [B, L, D] on known's device.
+    ``known``: float32 [B, L, D] in the model's normalised motion space, or [B, N, J] in the CDM's sample space (normalised contact,
+    (exp(-d^2 / 2 sigma^2) - mean) / std).  ``mask``: bool or uint8 (nonzero = known), broadcastable to it
+    ([L, D], [B, L, 1], [B, 1, D], ...); expanded ONCE to a contiguous uint8 of known's shape on known's device.
 
     The object is a callable ``imp(x0) -> ops.impute(x0, known, mask)`` (afm_impute, HIP), so it IS a ``denoised_fn`` wherever one is
     accepted - p_sample, ddim_sample, the progressive generators, the CDM; handed to p_sample_loop / ddim_sample_loop of a denoiser whose
-    native loop takes ``impute=`` (CMDM `trans_enc`, GuidedCMDM) the whole chain stays in the native loop (afm_cmdm_impute_loop_range)."""
+    native loop takes ``impute=`` (CMDM `trans_enc`, GuidedCMDM: afm_cmdm_impute_loop_range) or that has an ``afm_native_impute_loop``
+    (the CDM Perceiver: afm_cdm_impute_loop_range) the whole chain stays in the native loop."""
 
     def __init__(self, known: torch.Tensor, mask: torch.Tensor):
         if known.dim() != 3:
@@ -128,7 +132,8 @@ class Impute:
 
 
 def _takes_impute(native) -> bool:
-    """does a denoiser's afm_native_loop accept the ``impute=`` keyword (CMDM trans_enc, GuidedCMDM; not the CDM)"""
+    """does a denoiser's afm_native_loop accept the ``impute=`` keyword (CMDM trans_enc, GuidedCMDM; not the CDM, whose afm_native_loop
+    keeps its signature: its imputing loop is a second method, afm_native_impute_loop, which `_sample_loop` looks for by name)"""
     import inspect
     try:
         return "impute" in inspect.signature(native).parameters
@@ -377,10 +382,12 @@ class GaussianDiffusion:
                      sample_index0, snapshots, ddim_eta: Optional[float]):
         """p_sample_loop (ddim_eta None) / ddim_sample_loop: the native loop when the denoiser has one and nothing needs the host between
         steps, else the progressive generator.  A ``denoised_fn`` that is an `Impute` stays native where the denoiser's loop takes
-        ``impute=``; any other callable samples step by step."""
+        ``impute=`` or the denoiser has an ``afm_native_impute_loop`` (the CDM); any other callable samples step by step."""
         native = getattr(model, "afm_native_loop", None)
         switches = any(k in (model_kwargs or {}) for k in ("c_text_mask", "c_text_erase", "c_pc_mask", "c_pc_erase"))
-        impute = denoised_fn if isinstance(denoised_fn, Impute) and native is not None and _takes_impute(native) else None
+        native_impute = getattr(model, "afm_native_impute_loop", None) if native is not None else None
+        impute = denoised_fn if isinstance(denoised_fn, Impute) and native is not None and \
+            (_takes_impute(native) or native_impute is not None) else None
         if native is not None and (denoised_fn is None or impute is not None) and cond_fn is None and not self.rescale_timesteps and not switches:
             if device is None:
                 device = next(model.parameters()).device
@@ -392,13 +399,16 @@ class GaussianDiffusion:
             extra = {} if snapshots is None else {"snapshots": snapshots}
             if impute is not None:
                 impute.check(x)
-                extra["impute"] = impute
+                if _takes_impute(native):
+                    extra["impute"] = impute
             if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused update
                 extra["clip_denoised"] = True
             if ddim_eta is not None:
                 extra["ddim_eta"] = ddim_eta
-            return native(self, x, model_kwargs or {}, step_noise=step_noise, seed=seed, sample_index0=sample_index0,
-                          progress=bool(progress), **extra)
+            args = (self, x, model_kwargs or {})
+            if impute is not None and "impute" not in extra:      # the CDM: a second method with the Impute as its fourth argument
+                native, args = native_impute, args + (impute,)
+            return native(*args, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=bool(progress), **extra)
         gen = self.p_sample_loop_progressive if ddim_eta is None else \
             (lambda *a, **k: self.ddim_sample_loop_progressive(*a, eta=ddim_eta, **k))
         final, done = None, 0

@@ -21,7 +21,8 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
                      contact_std: float = 1.0, seed: int = 0, sample_index0: int = 0,
                      adm_noise: Optional[Dict[str, torch.Tensor]] = None,
                      amdm_noise: Optional[Dict[str, torch.Tensor]] = None, sampler: str = "ddpm",
-                     eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None) -> Dict[str, torch.Tensor]:
+                     eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None,
+                     contact_impute=None) -> Dict[str, torch.Tensor]:
     """text_feat [B, text_dim], xyz [B, N, 3] (B = scenes x k_sample, already flattened) ->
     {"contact": [B, N, J] ADM sample, "cond": [B, N, J] AMDM condition, "motion": [B, frames, D]}.
 
@@ -31,7 +32,11 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     ``guidance_scale`` (a float or a [B] tensor; None = unguided): classifier-free guidance of the MOTION stage, dropping the conditions named
     in ``guidance_drop`` (afm.cmdm.GuidedCMDM; the CDM of the first stage never reads the condition switches).  A mapping
     ``{"pc": s_pc, "text": s_text}`` (insertion order = first, second) gives every condition a scale of its own; ``guidance_drop`` must
-    then name exactly the mapping's keys."""
+    then name exactly the mapping's keys.
+    ``contact_impute`` / ``motion_impute``: an afm.diffusion.Impute handed to stage 1 / stage 2 as ``denoised_fn`` (both stay in their native
+    loops).  The contact stage is the one to steer: ``contact_impute.known`` [B, N, J] lives in the CDM's own sample space, the
+    normalised contact (exp(-d^2 / 2 sigma^2) - mean) / std - pin it on the points of a chosen object, or to the value of zero contact
+    on a region to keep clear.  ``motion_impute.known`` [B, frames, D] lives in the normalised motion space."""
     if sampler not in ("ddpm", "ddim"):
         raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
     if isinstance(guidance_scale, Mapping):          # (refused before the first stage runs)
@@ -49,7 +54,7 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     adm_kw = dict(c_text_feat=text_feat, c_pc_xyz=xyz)
     an = adm_noise or {}
     contact = loop(adm_diffusion, adm, (B, N, adm.contact_dim), noise=an.get("x_T"), clip_denoised=False,
-                   model_kwargs=adm_kw, step_noise=an.get("steps"), seed=seed, sample_index0=sample_index0)
+                   denoised_fn=contact_impute, model_kwargs=adm_kw, step_noise=an.get("steps"), seed=seed, sample_index0=sample_index0)
     cond = adist.adm_to_amdm_condition(contact, sigma=sigma, mean=contact_mean, std=contact_std)
     if x_mask is None:
         x_mask = torch.zeros(B, frames, dtype=torch.bool, device=dev)

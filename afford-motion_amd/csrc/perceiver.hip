@@ -199,8 +199,11 @@ int cdm_prepare_invariants(const afm_cdm_weights& w, const float* feat, int B, i
 // one denoiser evaluation in the folded (mode 1) or generated (mode 2) form; `prepared` (mode 1): ws.enc_kv / ws.bufB already hold C / D
 int cdm_forward_folded(const afm_cdm_weights& w, const float* feat, const float* x_t, const int64_t* t, const float* text_q0,
                        const float* text_u, const float* text_cu, float* x0_out, const afm_ddpm_args* ddpm, int B, int N, const CdmWs& ws,
-                       bool prepared, hipStream_t s, const CdmChainSide* cs = nullptr) {
+                       bool prepared, hipStream_t s, const CdmChainSide* cs = nullptr, const Update* loop_upd = nullptr) {
     const int M = B * N, dkv = w.dkv, cd = w.contact_dim, mode = cdm_mode(w);
+    // the imputing loops: known / mask of the sub-batch ride in the loop's update description (row-less: fused into dec_point; FOLD: below)
+    const float* known = loop_upd ? loop_upd->known : nullptr;
+    const uint8_t* mask = loop_upd ? loop_upd->mask : nullptr;
     if (mode == 1 && !prepared) AFM_TRY(cdm_prepare_invariants(w, feat, B, N, ws, s));
     if (mode == 3) AFM_TRY(launch_enc_point(w, text_u, text_cu, t, B, N, ws, x_t, feat, s));
     else AFM_TRY(launch_enc_reduce(w, ws.enc_kv, text_u, text_cu, t, B, N, ws, x_t, mode, s));
@@ -212,10 +215,10 @@ int cdm_forward_folded(const afm_cdm_weights& w, const float* feat, const float*
         AFM_TRY(launch_dec_tables(w, B, ws, cs->chain));
         (void)hipEventRecord(cs->joined, cs->chain);
         (void)hipStreamWaitEvent(s, cs->joined, 0);
-        return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false);
+        return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false, known, mask);
     }
     AFM_TRY(cdm_latent_chain(w, text_q0, t, ws, B, s, mode == 3));
-    if (mode == 3) return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s);
+    if (mode == 3) return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s, true, known, mask);
     AFM_TRY(launch_dec_attend(w, B, N, ws, x_t, mode, s));
     afm_linear_args a = {};                 // GELU(linear1 z) . w2 per 64-column group; the hidden activations are never stored
     a.A = ws.z; a.lda = dkv; a.W = w.dec_mlp.fc1.w; a.ldw = dkv; a.M = M; a.N = dkv; a.K = dkv; a.bias = w.dec_mlp.fc1.b; a.act = AFM_ACT_GELU;
@@ -223,6 +226,12 @@ int cdm_forward_folded(const afm_cdm_weights& w, const float* feat, const float*
     a.arith = w.gemm_arith; a.arith_min_n = w.gemm_arith_min_n;
     a.tune = ((w.flags >> AFM_CDM_TILE_SHIFT) & 0xF) << AFM_TUNE_TILE_SHIFT;
     AFM_TRY(afm_linear(&a, s));
+    if (mask) {       // imputing loop, FOLD: pred_xstart to ws.h1 (not used by this form) with the plain output, then the one update launch that selects
+        AFM_TRY(launch_cdm_output(w, B, N, ws, x_t, ws.h1, nullptr, s));
+        Update u = *loop_upd;
+        u.x0 = ws.h1;
+        return afm_sampling_update(u, B, s);
+    }
     return launch_cdm_output(w, B, N, ws, x_t, x0_out, ddpm, s);
 }
 
@@ -232,7 +241,8 @@ static int cdm_forward_impl(const afm_cdm_weights* wp, const float* feat, const 
                             const float* text_q0, const float* text_u, const float* text_cu, float* x0_out,
                             const afm_ddpm_args* ddpm, int32_t B, int32_t N, void* workspace, int64_t workspace_bytes,
                             void* side_stream, void* stream, bool prepared = false, bool rowless_ws = false, const CdmChainSide* cs = nullptr,
-                            const afm_loop::Update* loop_upd = nullptr) {      // loop_upd: the layer-by-layer DDIM loop's update launch, its x0 set here
+                            const afm_loop::Update* loop_upd = nullptr) {      // loop_upd: the update launch of a loop step (the layer-by-layer DDIM loop's;
+                                                                              // an imputing loop's, known / mask set), its x0 set here
     AFM_TRY(validate(wp, B, N));
     if (!feat || !t || !text_q0 || !text_u || !text_cu || !workspace || (!x0_out && !ddpm)) return AFM_E_BADARG;
     if (!wp->time_q0 || !wp->time_u || !wp->time_cu) return AFM_E_BADARG;
@@ -244,7 +254,8 @@ static int cdm_forward_impl(const afm_cdm_weights* wp, const float* feat, const 
     const CdmWs ws = carve(w, B, N, workspace, !rowless_ws);
     if (ws.bytes > workspace_bytes) return AFM_E_WORKSPACE;
     const int M = B * N, dkv = w.dkv;
-    if (cdm_folded(w) && x_t) return cdm_forward_folded(w, feat, x_t, t, text_q0, text_u, text_cu, x0_out, ddpm, B, N, ws, prepared, s, cs);
+    if (loop_upd && loop_upd->mask && !ddpm) return AFM_E_BADARG;
+    if (cdm_folded(w) && x_t) return cdm_forward_folded(w, feat, x_t, t, text_q0, text_u, text_cu, x0_out, ddpm, B, N, ws, prepared, s, cs, loop_upd);
 
     afm_linear_args a = {};
     a.A = feat; a.lda = w.feat_dim; a.W = w.encoder_adapter.w; a.ldw = w.feat_dim; a.C = ws.enc_kv; a.ldc = dkv;
@@ -298,7 +309,8 @@ static int cdm_forward_impl(const afm_cdm_weights* wp, const float* feat, const 
     a.A = ws.z; a.lda = dkv; a.W = w.contact_layer.w; a.ldw = dkv; a.C = x0_out; a.ldc = w.contact_dim;
     a.M = M; a.N = w.contact_dim; a.K = dkv; a.bias = w.contact_layer.b;
     const int upd = ddpm ? cdm_update_bits(w) : 0;
-    if (upd & AFM_UPD_DDIM) {       // native DDIM loop: pred_xstart to bufB (read by nothing after fc2), then the DDIM update in place on x_t
+    if ((upd & AFM_UPD_DDIM) || (loop_upd && loop_upd->mask)) {       // native DDIM loop, and every imputing loop (the fused DDPM epilogue has no
+                                    // place for the select): pred_xstart to bufB (read by nothing after fc2), then the update in place on x_t
         if (dkv < w.contact_dim) return AFM_E_UNSUPPORTED;          // (bufB holds [M][dkv]; pred_xstart needs [M][contact_dim])
         a.C = ws.bufB;
         a.arith = w.gemm_arith; a.arith_min_n = w.gemm_arith_min_n;
@@ -357,6 +369,8 @@ struct LoopCall {
     const float *text_q0, *text_u, *text_cu;
     int N;
     LoopArgs a;                       // (a.streams: a stream pair per sub-batch)
+    const float* known = nullptr;     // imputing loop: [B][N][contact_dim] each, both set (neither: no imputation)
+    const uint8_t* mask = nullptr;
 };
 
 // sub-batch s runs on `stream` (streams[2s]) with `side` (streams[2s+1]) as the side stream of its decoder-adapter GEMM, of its latent chain
@@ -392,7 +406,7 @@ struct LoopPlan {
 int plan_loop(const LoopCall& c, LoopPlan* p) {
     const LoopArgs& a = c.a;
     AFM_TRY(validate(c.w, a.B, c.N));
-    if (!c.x || !c.feat || !c.text_q0 || !c.text_u || !c.text_cu || !a.ok()) return AFM_E_BADARG;
+    if (!c.x || !c.feat || !c.text_q0 || !c.text_u || !c.text_cu || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     p->nsub = 0;
     if (a.B == 0) return 0;
     p->w = *c.w;
@@ -426,6 +440,8 @@ struct Loop {
 
 inline float* sub_x(const Loop& l, const SubBatch& sb) { return l.c.x + (int64_t)sb.start * l.p.per; }
 inline float* sub_feat(const Loop& l, const SubBatch& sb) { return l.c.feat + (int64_t)sb.start * l.c.N * l.p.w.feat_dim; }
+inline const float* sub_known(const Loop& l, const SubBatch& sb) { return l.c.mask ? l.c.known + (int64_t)sb.start * l.p.per : nullptr; }
+inline const uint8_t* sub_mask(const Loop& l, const SubBatch& sb) { return l.c.mask ? l.c.mask + (int64_t)sb.start * l.p.per : nullptr; }
 
 // the events of a loop call, all owned by `ev`: the fork of the sub-batch streams, the chain-side pairs, the pipeline's pairs
 int loop_events(Loop& l, Events& ev) {
@@ -492,7 +508,7 @@ int pipe_dec(const Loop& l, const SubBatch& sb, int j) {
     const float* nz;
     AFM_TRY(step_noise(l.c.a, l.p.per, sb, sb.noise, j, sub_x(l, sb), nullptr, &nz));
     const afm_ddpm_args dd = ddpm_args(l.c.a, l.sched.at(j, sb.start), nz, sub_x(l, sb), sb, j);
-    return launch_dec_point(l.p.w, sb.count, l.c.N, sb.ws, sub_x(l, sb), sub_feat(l, sb), nullptr, &dd, H, false);
+    return launch_dec_point(l.p.w, sb.count, l.c.N, sb.ws, sub_x(l, sb), sub_feat(l, sb), nullptr, &dd, H, false, sub_known(l, sb), sub_mask(l, sb));
 }
 
 int pipelined_steps(const Loop& l) {
@@ -517,7 +533,8 @@ int plain_step(const Loop& l, const SubBatch& sb, int j) {
     AFM_TRY(step_noise(c.a, l.p.per, sb, sb.noise, j, xs, &sb.stream, &nz));
     const StepRows r = l.sched.at(j, sb.start);
     const afm_ddpm_args dd = ddpm_args(c.a, r, nz, xs, sb, j);
-    const Update upd = loop_update(c.a, r, nullptr, xs, nz, l.p.per, w.flags & AFM_CDM_CLIP_X0);
+    Update upd = loop_update(c.a, r, nullptr, xs, nz, l.p.per, w.flags & AFM_CDM_CLIP_X0);
+    upd.known = sub_known(l, sb); upd.mask = sub_mask(l, sb);
     return cdm_forward_impl(&w, fs, xs, r.t, c.text_q0 + (int64_t)sb.start * w.dq, c.text_u + (int64_t)sb.start * w.enc_heads * w.dkv,
                             c.text_cu + (int64_t)sb.start * w.enc_heads, nullptr, &dd, sb.count, c.N, sb.base, sb.ws.bytes, sb.side, sb.stream,
                             l.p.folded, l.p.rowless, l.p.chain_side ? &sb.chain : nullptr, &upd);
@@ -584,4 +601,18 @@ extern "C" int afm_cdm_ddim_loop_range(const afm_cdm_weights* w, float* x, float
     if (first_step < 0 || !rows) return AFM_E_BADARG;
     return cdm_sample_loop_impl({w, x, feat, text_q0, text_u, text_cu, N, {step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, seed, sample_index0, B,
                                  sched_scratch, workspace, workspace_bytes, n_sub, streams, stream}});
+}
+
+// The imputing native loop, DDPM and DDIM behind one entry (rows != NULL: DDIM, d_c1 / d_c2 / d_sigma ignored): known / mask both NULL is
+// the loop without imputation
+extern "C" int afm_cdm_impute_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
+                                         const float* text_cu, const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows,
+                                         const float* d_c1, const float* d_c2, const float* d_sigma, const float* known, const uint8_t* mask,
+                                         int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t N,
+                                         void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream) {
+    if (!known != !mask) return AFM_E_BADARG;
+    if (first_step < 0) return AFM_E_BADARG;
+    if (rows) d_c1 = d_c2 = d_sigma = nullptr;
+    return cdm_sample_loop_impl({w, x, feat, text_q0, text_u, text_cu, N, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
+                                 sched_scratch, workspace, workspace_bytes, n_sub, streams, stream}, known, mask});
 }

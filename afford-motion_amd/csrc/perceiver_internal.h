@@ -67,8 +67,9 @@ int launch_lat_decfold(const afm_cdm_weights& w, const CdmWs& ws, int B, hipStre
 int launch_enc_point(const afm_cdm_weights& w, const float* text_u, const float* text_cu, const int64_t* t, int B, int N, const CdmWs& ws,
                      const float* x_t, const float* feat, hipStream_t s);
 int launch_lat_head(const afm_cdm_weights& w, const float* text_q0, const int64_t* t, const CdmWs& ws, int B, hipStream_t s);
+// known / mask [B][N][contact_dim] (both or neither; the imputing loops): the select fused in front of the in-place update, ddpm->x_next required
 int launch_dec_point(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, const float* x_t, const float* feat, float* x0_out,
-                     const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables = true);
+                     const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables = true, const float* known = nullptr, const uint8_t* mask = nullptr);
 int launch_dec_tables(const afm_cdm_weights& w, int B, const CdmWs& ws, hipStream_t s);      // lat_dectables_kernel alone (chain stream)
 // perceiver_chain.hip - enc_reduce / enc_point partials -> the decoder's view of the two latents (dec_lat records / lat_kv for the row-less form)
 int cdm_latent_chain(const afm_cdm_weights& w, const float* text_q0, const int64_t* t, const CdmWs& ws, int B, hipStream_t s, bool rowless);

@@ -927,6 +927,21 @@ int afm_cdm_ddim_loop_range(const afm_cdm_weights* w, float* x, float* feat, con
                             int32_t n_steps, int32_t first_step, uint64_t seed,
                             int64_t sample_index0, int32_t B, int32_t N, void* sched_scratch, void* workspace,
                             int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream);
+/* The imputing loop slice (v7-additive), DDPM and DDIM behind one entry, as afm_cmdm_impute_loop_range: the arguments of the two entries
+ * above with both kinds of rows (rows != NULL: the DDIM loop, d_c1 / d_c2 / d_sigma ignored; rows == NULL: the DDPM loop) and known / mask
+ * [B][N][contact_dim] (the imputation rule above: a select on pred_xstart in front of the clamp; mask uint8, nonzero = known).  known
+ * without mask or the reverse: AFM_E_BADARG, in front of every other check; both NULL: the loop without imputation.
+ * Row-less form (the default): the select is fused into dec_point in front of its update - no extra launch, no stored pred_xstart - and
+ * the DDPM update is the afm_ddpm_step expression, every operation rounded on its own: the loop is bit-identical to afm_cdm_forward ->
+ * afm_impute -> (afm_clamp ->) afm_ddpm_step / afm_ddim_step per step.  Folded-rows and layer-by-layer forms: pred_xstart stored with the
+ * plain output, then ONE update launch per sub-batch (the afm_impute_step expression, in place on x), for DDPM too.  Workspace, schedule
+ * scratch (afm_ddim_sched_scratch_bytes with rows, afm_cmdm_sched_scratch_bytes without), noise, sub-batches and first_step as above. */
+int afm_cdm_impute_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
+                              const float* text_cu, const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows,
+                              const float* d_c1, const float* d_c2, const float* d_sigma, const float* known, const uint8_t* mask,
+                              int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t N,
+                              void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams,
+                              void* stream);
 
 /* Latent-token precomputation (step-invariant, off the per-step path): for n input rows `in` [n, text_dim] (which = 0,
  * language_adapter) or [n, time_dim] (which = 1, time_embedding_adapter) compute the latent's enc_q0 row
