@@ -344,6 +344,24 @@ def cfg_combine(x0_c: torch.Tensor, x0_u: torch.Tensor, scale: torch.Tensor, *, 
     return out
 
 
+def _step_tail(a, x0, x_t, out, noise, ddpm, ddim, clip, seed, sample_index0, step) -> list:
+    """The fields CfgStepArgs, ImputeStepArgs and Cfg2StepArgs share: x_t, x_next, noise, the DDPM or DDIM rows, clip, the sizes, the Philox
+    key.  -> what must stay alive until the call returns (the contiguous noise and rows, the DdimRows struct ``a.ddim`` points to)."""
+    B = x0.shape[0]
+    nz = None if noise is None else ffi.f32c(noise)
+    a.x_t, a.x_next, a.noise = x_t.data_ptr(), out.data_ptr(), ffi.ptr(nz)
+    keep = [ffi.f32c(r) for r in (ddpm if ddpm is not None else ddim) if r is not None]
+    if ddpm is not None:
+        a.c1, a.c2, a.sigma = (r.data_ptr() for r in keep)
+    else:
+        rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], keep[4].data_ptr() if len(keep) > 4 else None)
+        a.ddim = C.pointer(rows)
+        keep.append(rows)
+    a.clip, a.B, a.per_sample = int(bool(clip)), B, x0.numel() // max(B, 1)
+    a.seed, a.sample_index0, a.step = seed & (2**64 - 1), sample_index0, step
+    return keep + [nz]
+
+
 def cfg_step(x0_c: torch.Tensor, x0_u: torch.Tensor, scale: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor], *,
              ddpm=None, ddim=None, clip: bool = False, seed: int = 0, sample_index0: int = 0, step: int = 0,
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -359,18 +377,8 @@ def cfg_step(x0_c: torch.Tensor, x0_u: torch.Tensor, scale: torch.Tensor, x_t: t
         raise ValueError(f"cfg_step: scale must hold one value per sample ({B}), got {tuple(scale.shape)}")
     out = torch.empty_like(x0_c) if out is None else out
     a = ffi.CfgStepArgs()
-    a.x0_c, a.x0_u, a.scale, a.x_t, a.x_next = x0_c.data_ptr(), x0_u.data_ptr(), scale.data_ptr(), x_t.data_ptr(), out.data_ptr()
-    nz = None if noise is None else ffi.f32c(noise)
-    a.noise = ffi.ptr(nz)
-    keep = [ffi.f32c(r) for r in (ddpm if ddpm is not None else ddim) if r is not None]
-    rows = None
-    if ddpm is not None:
-        a.c1, a.c2, a.sigma = (r.data_ptr() for r in keep)
-    else:
-        rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], keep[4].data_ptr() if len(keep) > 4 else None)
-        a.ddim = C.pointer(rows)
-    a.clip, a.B, a.per_sample = int(bool(clip)), B, x0_c.numel() // max(B, 1)
-    a.seed, a.sample_index0, a.step = seed & (2**64 - 1), sample_index0, step
+    a.x0_c, a.x0_u, a.scale = x0_c.data_ptr(), x0_u.data_ptr(), scale.data_ptr()
+    keep = _step_tail(a, x0_c, x_t, out, noise, ddpm, ddim, clip, seed, sample_index0, step)
     ffi.check(lib.afm_cfg_step(C.byref(a), ffi.stream_of(x0_c)), "afm_cfg_step")
     return out
 
@@ -417,23 +425,13 @@ def impute_step(x0: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, x_t: 
         raise ValueError(f"impute_step: known {tuple(known.shape)} and mask {tuple(mask.shape)} must have x0's shape {tuple(x0.shape)}")
     out = torch.empty_like(x0) if out is None else out
     a = ffi.ImputeStepArgs()
-    a.x0_c, a.known, a.mask, a.x_t, a.x_next = x0.data_ptr(), known.data_ptr(), mask.data_ptr(), x_t.data_ptr(), out.data_ptr()
+    a.x0_c, a.known, a.mask = x0.data_ptr(), known.data_ptr(), mask.data_ptr()
     if x0_u is not None:
         x0_u, scale = ffi.f32c(x0_u), ffi.f32c(scale)
         if scale.numel() != B or x0_u.shape != x0.shape:
             raise ValueError(f"impute_step: scale must hold one value per sample ({B}), got {tuple(scale.shape)}; x0_u {tuple(x0_u.shape)}")
         a.x0_u, a.scale = x0_u.data_ptr(), scale.data_ptr()
-    nz = None if noise is None else ffi.f32c(noise)
-    a.noise = ffi.ptr(nz)
-    keep = [ffi.f32c(r) for r in (ddpm if ddpm is not None else ddim) if r is not None]
-    rows = None
-    if ddpm is not None:
-        a.c1, a.c2, a.sigma = (r.data_ptr() for r in keep)
-    else:
-        rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], keep[4].data_ptr() if len(keep) > 4 else None)
-        a.ddim = C.pointer(rows)
-    a.clip, a.B, a.per_sample = int(bool(clip)), B, x0.numel() // max(B, 1)
-    a.seed, a.sample_index0, a.step = seed & (2**64 - 1), sample_index0, step
+    keep = _step_tail(a, x0, x_t, out, noise, ddpm, ddim, clip, seed, sample_index0, step)
     ffi.check(lib.afm_impute_step(C.byref(a), ffi.stream_of(x0)), "afm_impute_step")
     return out
 
@@ -476,23 +474,12 @@ def cfg2_step(x0_c: torch.Tensor, x0_a: torch.Tensor, x0_u: torch.Tensor, scale_
     out = torch.empty_like(x0_c) if out is None else out
     a = ffi.Cfg2StepArgs()
     a.x0_c, a.x0_a, a.x0_u, a.scale_first, a.scale_second = x0_c.data_ptr(), x0_a.data_ptr(), x0_u.data_ptr(), s1.data_ptr(), s2.data_ptr()
-    a.x_t, a.x_next = x_t.data_ptr(), out.data_ptr()
     if known is not None:
         known, mask = ffi.f32c(known), _mask_u8(mask)
         if known.shape != x0_c.shape or mask.shape != x0_c.shape:
             raise ValueError(f"cfg2_step: known {tuple(known.shape)} and mask {tuple(mask.shape)} must have x0's shape {tuple(x0_c.shape)}")
         a.known, a.mask = known.data_ptr(), mask.data_ptr()
-    nz = None if noise is None else ffi.f32c(noise)
-    a.noise = ffi.ptr(nz)
-    keep = [ffi.f32c(r) for r in (ddpm if ddpm is not None else ddim) if r is not None]
-    rows = None
-    if ddpm is not None:
-        a.c1, a.c2, a.sigma = (r.data_ptr() for r in keep)
-    else:
-        rows = ffi.DdimRows(*[r.data_ptr() for r in keep[:4]], keep[4].data_ptr() if len(keep) > 4 else None)
-        a.ddim = C.pointer(rows)
-    a.clip, a.B, a.per_sample = int(bool(clip)), B, x0_c.numel() // max(B, 1)
-    a.seed, a.sample_index0, a.step = seed & (2**64 - 1), sample_index0, step
+    keep = _step_tail(a, x0_c, x_t, out, noise, ddpm, ddim, clip, seed, sample_index0, step)
     ffi.check(lib.afm_cfg2_step(C.byref(a), ffi.stream_of(x0_c)), "afm_cfg2_step")
     return out
 

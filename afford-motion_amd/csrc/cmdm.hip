@@ -10,9 +10,8 @@
 //   buffer, +bias +positional rows) -> n_layers x { in_proj GEMM, flash MHA, out_proj GEMM(+bias
 //   +residual), LN, FFN1 GEMM(+bias+GELU), FFN2 GEMM(+bias+residual), LN } -> motion_layer GEMM
 //   (gather motion tokens, +bias, fused DDPM posterior update).
-// Classifier-free guided steps (afm_cmdm_cfg_*): this sequence twice - the conditioned branch, then the unconditioned one (struct Branch) -
-// with both motion_layer GEMMs storing pred_xstart, and one elementwise launch for the guided update (afm_sampling_update).
-// Two-scale guided steps (afm_cmdm_cfg2_*): three times - conditioned, the middle branch (only the first condition kept), unconditioned.
+// Classifier-free guided steps (afm_cmdm_cfg_*, afm_cmdm_cfg2_*): this sequence for the conditioned evaluation, then once per branch of the
+// list struct Guidance holds ([middle,] unconditioned), every motion_layer GEMM storing pred_xstart, then one launch that combines them.
 #include <memory>
 
 #include "sample_loop.h"
@@ -167,6 +166,7 @@ int forward_impl(const afm_cmdm_weights& w, const float* x_t, const int64_t* t, 
     const int pos_off = br ? br->pos_off : 1 + w.n_cond;          // positional row of the first motion token
     const bool mask_cond = br && (br->mask_text || br->mask_pc);
     if (mask_cond && (!keymask || w.n_cond < 1 || rec)) return AFM_E_BADARG;
+    if (w.n_cond == 0) cond = nullptr;               // (a compact branch runs on the caller's arguments: no condition rows, none read)
 
     // Steps after the first of a native loop need no prologue launch: the condition tokens and the key mask persist in the workspace, the
     // K-padded copy of x_t was written by the previous step's DDPM update (ddpm_out2), and the time tokens ride on the motion adapter's
@@ -348,26 +348,73 @@ inline afm_cmdm_weights callers_pack(const afm_cmdm_weights& w, uint32_t also = 
     return r;
 }
 
-// the unconditioned branch of a guided evaluation: its copy of the pack and its Branch (compact when every condition is dropped)
-int uncond_setup(const afm_cmdm_weights& w, const afm_cfg_args* cfg, const uint8_t* frame_mask, afm_cmdm_weights* wu, Branch* br) {
-    if (!cfg || !cfg->scale || (!cfg->drop_text && !cfg->drop_pc) || w.n_cond < 1) return AFM_E_BADARG;
-    const bool compact = cfg->drop_text && cfg->drop_pc && !(cfg->flags & AFM_CFG_FORCE_MASKED);
-    if (!compact && !frame_mask) return AFM_E_BADARG;          // (the key mask is built from the frame mask)
-    *wu = w;
-    br->pos_off = 1 + w.n_cond;
-    br->mask_text = compact ? 0 : (cfg->drop_text ? 1 : 0);
-    br->mask_pc = compact ? 0 : (cfg->drop_pc ? 1 : 0);
-    if (compact) wu->n_cond = 0;
+// The extra evaluations of a guided step, in launch order behind the conditioned one: [middle,] unconditioned.
+struct GuideBranch { afm_cmdm_weights w; Branch br; };       // the pack copy an extra evaluation runs on, and its layout
+struct Guidance {                     // n == 0: unguided
+    int n;
+    GuideBranch b[2];
+    const float* scale[2];            // [B] rows: scale[0] = Update::scale, scale[1] = Update::scale2 (two scales only)
+    void* const* branch_streams;      // one extra branch only
+};
+
+inline bool cfg2_ok(const afm_cfg2_args* c) { return c && c->scale_first && c->scale_second && (c->first == 0 || c->first == 1); }
+
+// The list of either public description (`two` wins; neither: AFM_E_BADARG) for the pack `w`.  One scale: the unconditioned branch drops
+// what the caller names.  Two scales: the middle branch keeps the first condition only - always a masked form - and the unconditioned one
+// drops both (scale[0]: the first condition's, the row cfg_combine2's inner cfg_combine reads).  A branch that drops every condition is
+// compact (n_cond = 0 in its pack, the positional rows of the full layout) unless AFM_CFG_FORCE_MASKED.  `to_run`: also refuse a masked
+// form without a frame mask (the key mask is built from it); the workspace sizes do not depend on it.
+int make_guidance(const afm_cmdm_weights& w, const afm_cfg_args* one, const afm_cfg2_args* two, bool to_run, const uint8_t* frame_mask, Guidance* g) {
+    *g = {};
+    if (two ? !cfg2_ok(two) : (!one || !one->scale || (!one->drop_text && !one->drop_pc))) return AFM_E_BADARG;
+    if (w.n_cond < 1) return AFM_E_BADARG;
+    const bool text = two || one->drop_text, pc = two || one->drop_pc;         // what the unconditioned branch drops
+    const bool compact = text && pc && !((two ? two->flags : one->flags) & AFM_CFG_FORCE_MASKED);
+    if (to_run && !frame_mask && (two || !compact)) return AFM_E_BADARG;
+    auto add = [&](bool mask_text, bool mask_pc) { g->b[g->n++] = GuideBranch{w, {1 + w.n_cond, mask_text, mask_pc}}; };
+    if (two) add(two->first == 1, two->first == 0);
+    add(!compact && text, !compact && pc);
+    if (compact) g->b[g->n - 1].w.n_cond = 0;
+    g->scale[0] = two ? two->scale_first : one->scale;
+    g->scale[1] = two ? two->scale_second : nullptr;
+    g->branch_streams = two ? nullptr : one->branch_streams;
     return 0;
 }
 
-// Two-scale guidance as the two single-scale descriptions its extra branches are built from: *u drops both conditions (scale: the first
-// condition's, the row cfg_combine2's inner cfg_combine reads), *a drops the second condition only (always a masked form).
-int cfg2_split(const afm_cfg2_args* c2, afm_cfg_args* u, afm_cfg_args* a) {
-    if (!c2 || !c2->scale_first || !c2->scale_second || (c2->first != 0 && c2->first != 1)) return AFM_E_BADARG;
-    *u = afm_cfg_args{c2->scale_first, 1, 1, c2->flags & AFM_CFG_FORCE_MASKED, nullptr};
-    *a = afm_cfg_args{c2->scale_first, c2->first == 1 ? 1 : 0, c2->first == 0 ? 1 : 0, 0, nullptr};
-    return 0;
+// One guided evaluation: validate, the library's own copy of the pack, the conditioned evaluation and each branch of the list in turn on
+// one workspace (no branch's layout is larger than the conditioned one's), then the combine launch.  outs: pred_xstart of c, [a,] u
+// (NULL: the region behind the workspace, in that order).
+int guided_forward(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, const float* x_t, const int64_t* t,
+                   const float* cond_tokens, const uint8_t* frame_mask, float** outs, float* x0_guided, int B, int L, void* workspace,
+                   int64_t workspace_bytes, hipStream_t s) {
+    AFM_TRY(validate(w, B, L));
+    if (!x_t || !t || !cond_tokens || !workspace || !x0_guided) return AFM_E_BADARG;
+    const afm_cmdm_weights wc = callers_pack(*w, AFM_CMDM_FUSED_LN);         // (the opt-in fused LayerNorm is not built here)
+    Guidance g;
+    AFM_TRY(make_guidance(wc, one, two, true, frame_mask, &g));
+    if (B == 0) return 0;
+    const Workspace ws = carve(wc, B, L, workspace);
+    const int64_t xb = align256((int64_t)B * L * w->motion_dim * 4);
+    if (ws.bytes + (1 + g.n) * xb > workspace_bytes) return AFM_E_WORKSPACE;
+    Workspace wsb[2];
+    for (int i = 0; i < g.n; ++i) {
+        wsb[i] = carve(g.b[i].w, B, L, workspace);
+        if (wsb[i].bytes > ws.bytes) return AFM_E_WORKSPACE;
+    }
+    for (int i = 0; i <= g.n; ++i)
+        if (!outs[i]) outs[i] = (float*)((char*)workspace + ws.bytes + i * xb);
+    AFM_TRY(forward_impl(wc, x_t, t, cond_tokens, frame_mask, outs[0], nullptr, B, L, ws, true, s));
+    for (int i = 0; i < g.n; ++i)
+        AFM_TRY(forward_impl(g.b[i].w, x_t, t, cond_tokens, frame_mask, outs[1 + i], nullptr, B, L, wsb[i], true, s, nullptr, &g.b[i].br));
+    const int64_t per = (int64_t)L * w->motion_dim;
+    if (g.n == 1) return afm_cfg_combine(outs[0], outs[1], g.scale[0], x0_guided, B, per, s);
+    return afm_cfg2_combine(outs[0], outs[1], outs[2], g.scale[0], g.scale[1], x0_guided, B, per, s);
+}
+
+// the workspace of a guided evaluation: the conditioned one's, and a pred_xstart region for it and for each of the n_extra branches
+int64_t guided_workspace_bytes(const afm_cmdm_weights* w, int B, int L, int n_extra) {
+    if (validate(w, B, L) != 0) return AFM_E_BADARG;
+    return carve(*w, B, L, nullptr).bytes + (1 + n_extra) * align256((int64_t)B * L * w->motion_dim * 4);
 }
 
 }  // namespace
@@ -397,61 +444,25 @@ extern "C" int afm_cmdm_forward(const afm_cmdm_weights* w, const float* x_t, con
 }
 
 extern "C" int64_t afm_cmdm_cfg_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L) {
-    if (validate(w, B, L) != 0) return AFM_E_BADARG;
-    return carve(*w, B, L, nullptr).bytes + 2 * align256((int64_t)B * L * w->motion_dim * 4);
+    return guided_workspace_bytes(w, B, L, 1);
 }
 
-// Both branches in turn on one workspace (the unconditioned branch's layout is never larger), then the combine launch.
 extern "C" int afm_cmdm_cfg_forward(const afm_cmdm_weights* w, const float* x_t, const int64_t* t, const float* cond_tokens,
                                     const uint8_t* frame_mask, const afm_cfg_args* cfg, float* x0_c, float* x0_u, float* x0_guided,
                                     int32_t B, int32_t L, void* workspace, int64_t workspace_bytes, void* stream) {
-    AFM_TRY(validate(w, B, L));
-    if (!x_t || !t || !cond_tokens || !workspace || !x0_guided) return AFM_E_BADARG;
-    const afm_cmdm_weights wc = callers_pack(*w, AFM_CMDM_FUSED_LN);         // (the opt-in fused LayerNorm is not built here)
-    afm_cmdm_weights wu;
-    Branch br;
-    AFM_TRY(uncond_setup(wc, cfg, frame_mask, &wu, &br));
-    if (B == 0) return 0;
-    const Workspace ws = carve(wc, B, L, workspace), wsu = carve(wu, B, L, workspace);
-    const int64_t xb = align256((int64_t)B * L * w->motion_dim * 4);
-    if (ws.bytes + 2 * xb > workspace_bytes || wsu.bytes > ws.bytes) return AFM_E_WORKSPACE;
-    if (!x0_c) x0_c = (float*)((char*)workspace + ws.bytes);
-    if (!x0_u) x0_u = (float*)((char*)workspace + ws.bytes + xb);
-    AFM_TRY(forward_impl(wc, x_t, t, cond_tokens, frame_mask, x0_c, nullptr, B, L, ws, true, (hipStream_t)stream));
-    AFM_TRY(forward_impl(wu, x_t, t, wu.n_cond ? cond_tokens : nullptr, frame_mask, x0_u, nullptr, B, L, wsu, true, (hipStream_t)stream, nullptr, &br));
-    return afm_cfg_combine(x0_c, x0_u, cfg->scale, x0_guided, B, (int64_t)L * w->motion_dim, stream);
+    float* outs[] = {x0_c, x0_u};
+    return guided_forward(w, cfg, nullptr, x_t, t, cond_tokens, frame_mask, outs, x0_guided, B, L, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int64_t afm_cmdm_cfg2_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L) {
-    if (validate(w, B, L) != 0) return AFM_E_BADARG;
-    return carve(*w, B, L, nullptr).bytes + 3 * align256((int64_t)B * L * w->motion_dim * 4);
+    return guided_workspace_bytes(w, B, L, 2);
 }
 
-// The three branches in turn on one workspace (no branch's layout is larger than the conditioned one's), then the combine launch.
 extern "C" int afm_cmdm_cfg2_forward(const afm_cmdm_weights* w, const float* x_t, const int64_t* t, const float* cond_tokens,
                                      const uint8_t* frame_mask, const afm_cfg2_args* cfg, float* x0_c, float* x0_a, float* x0_u, float* x0_guided,
                                      int32_t B, int32_t L, void* workspace, int64_t workspace_bytes, void* stream) {
-    AFM_TRY(validate(w, B, L));
-    if (!x_t || !t || !cond_tokens || !frame_mask || !workspace || !x0_guided) return AFM_E_BADARG;
-    const afm_cmdm_weights wc = callers_pack(*w, AFM_CMDM_FUSED_LN);
-    afm_cfg_args cu, ca;
-    afm_cmdm_weights wu, wa;
-    Branch bru, bra;
-    AFM_TRY(cfg2_split(cfg, &cu, &ca));
-    AFM_TRY(uncond_setup(wc, &cu, frame_mask, &wu, &bru));
-    AFM_TRY(uncond_setup(wc, &ca, frame_mask, &wa, &bra));
-    if (B == 0) return 0;
-    const Workspace ws = carve(wc, B, L, workspace), wsu = carve(wu, B, L, workspace);
-    const int64_t xb = align256((int64_t)B * L * w->motion_dim * 4);
-    if (ws.bytes + 3 * xb > workspace_bytes || wsu.bytes > ws.bytes) return AFM_E_WORKSPACE;
-    if (!x0_c) x0_c = (float*)((char*)workspace + ws.bytes);
-    if (!x0_a) x0_a = (float*)((char*)workspace + ws.bytes + xb);
-    if (!x0_u) x0_u = (float*)((char*)workspace + ws.bytes + 2 * xb);
-    const hipStream_t s = (hipStream_t)stream;
-    AFM_TRY(forward_impl(wc, x_t, t, cond_tokens, frame_mask, x0_c, nullptr, B, L, ws, true, s));
-    AFM_TRY(forward_impl(wa, x_t, t, cond_tokens, frame_mask, x0_a, nullptr, B, L, ws, true, s, nullptr, &bra));
-    AFM_TRY(forward_impl(wu, x_t, t, wu.n_cond ? cond_tokens : nullptr, frame_mask, x0_u, nullptr, B, L, wsu, true, s, nullptr, &bru));
-    return afm_cfg2_combine(x0_c, x0_a, x0_u, cfg->scale_first, cfg->scale_second, x0_guided, B, (int64_t)L * w->motion_dim, stream);
+    float* outs[] = {x0_c, x0_a, x0_u};
+    return guided_forward(w, nullptr, cfg, x_t, t, cond_tokens, frame_mask, outs, x0_guided, B, L, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int64_t afm_cmdm_sched_scratch_bytes(int32_t n_steps, int32_t B) {
@@ -477,7 +488,8 @@ namespace {
 constexpr int MAX_SUB = 16;           // sub-batches (streams) of one loop call
 constexpr int NEV = 2 * AFM_MAX_LAYERS;      // events of the paired schedule: two cross-stream edges per layer
 
-// the arguments of the seven loop entry points
+// the arguments of the seven loop entry points: the model's tensors, the guidance as the caller describes it (at most one of cfg / cfg2;
+// neither: unguided), what every loop takes, the imputation
 struct LoopCall {
     const afm_cmdm_weights* w;
     float* x;
@@ -488,14 +500,11 @@ struct LoopCall {
     LoopArgs a;                       // (a.streams: one side stream per sub-batch)
     const float* known = nullptr;     // imputing loop: [B][L][motion_dim] each, both set (neither: no imputation)
     const uint8_t* mask = nullptr;
-    // two-scale guided loop: `cfg` then describes the unconditioned branch (scale: the first condition's row), cfg_a the middle branch
-    // (only the first condition kept), scale2 the second condition's row [B]
-    const afm_cfg_args* cfg_a = nullptr;
-    const float* scale2 = nullptr;
+    const afm_cfg2_args* cfg2 = nullptr;
 };
 
 struct SubBatch : SubRange {
-    Workspace ws, wsa, wsu;           // guided loops: wsa the middle branch's (two scales only) behind ws, wsu the unconditioned branch's behind that
+    Workspace ws, wsb[2];             // guided loops: wsb[i] the workspace of branch i of the list, behind ws in list order
     // guided loop with branch streams: the unconditioned branch runs on `branch`; two events order it against the guided update, the only
     // writer of x and of its K-padded copy (x_ready: x is ready, u_ready: the branch's pred_xstart is ready)
     hipStream_t branch;
@@ -503,36 +512,37 @@ struct SubBatch : SubRange {
 };
 
 // carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
-int64_t carve_sub(const afm_cmdm_weights& w, const afm_cmdm_weights* wa, const afm_cmdm_weights* wu, int L, char* base, SubBatch* sb) {
+int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb) {
     sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
     int64_t off = sb->ws.bytes;
-    // (2 "noise steps": a pred_xstart region of its own, as little noise space as the layout allows)
-    for (int i = 0; i < 2; ++i) {
-        const afm_cmdm_weights* wb = i == 0 ? wa : wu;
-        if (!wb) continue;
-        Workspace& wsb = i == 0 ? sb->wsa : sb->wsu;
-        wsb = carve(*wb, sb->count, L, base ? base + off : nullptr, 2);
-        wsb.xpad = sb->ws.xpad;       // one K-padded copy of x_t serves every branch
-        off += wsb.bytes;
+    for (int i = 0; i < g.n; ++i) {
+        // (2 "noise steps": a pred_xstart region of its own, as little noise space as the layout allows)
+        sb->wsb[i] = carve(g.b[i].w, sb->count, L, base ? base + off : nullptr, 2);
+        sb->wsb[i].xpad = sb->ws.xpad;       // one K-padded copy of x_t serves every branch
+        off += sb->wsb[i].bytes;
     }
     return off;
 }
 
-int64_t loop_workspace_bytes(const afm_cmdm_weights& w, const afm_cmdm_weights* wa, const afm_cmdm_weights* wu, int B, int L, int n_streams) {
+// the loop workspace of either public description of the guidance (neither: the unguided loop's); AFM_E_BADARG as the loop itself
+int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams) {
+    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
+    Guidance g = {};
+    if ((one || two) && make_guidance(*w, one, two, false, nullptr, &g) != 0) return AFM_E_BADARG;
     const int n = sub_count(B, n_streams, MAX_SUB);
     int64_t total = 0;
     for (int s = 0; s < n; ++s) {
         SubBatch sb = {};
         sub_range(B, n, s, &sb.start, &sb.count);
-        total += carve_sub(w, wa, wu, L, nullptr, &sb);
+        total += carve_sub(*w, g, L, nullptr, &sb);
     }
     return total;
 }
 
 // what a loop call fixes before its first launch: the loop's own weight packs, the sub-batches with their streams and workspaces, the form
 struct LoopPlan {
-    afm_cmdm_weights w, wu, wa;       // the loop's copies: flags (private bits, tile code) set here; wu / wa: the unconditioned / middle branch's pack
-    Branch br, bra;
+    afm_cmdm_weights w;               // the loop's copy: flags (private bits, tile code) set here
+    Guidance g;                       // the extra evaluations of a guided loop, the loop's flags on their packs too
     int nsub;                         // 0: an empty batch, nothing to enqueue
     SubBatch sb[MAX_SUB];
     bool paired;                      // AFM_CMDM_PAIR_LAUNCH, two sub-batches: every step after the first is recorded and issued interleaved
@@ -543,30 +553,25 @@ struct LoopPlan {
 int plan_loop(const LoopCall& c, LoopPlan* p) {
     const LoopArgs& a = c.a;
     AFM_TRY(validate(c.w, a.B, c.L));
-    // Guided loop (cfg != NULL): per sub-batch and step the conditioned branch (this loop's step as it is, pred_xstart stored the DDIM
-    // loop's way, for DDPM too), the unconditioned branch on a workspace of its own behind it on the same stream, and ONE update launch
-    // (afm_sampling_update).  Both branches read the same x / K-padded copy; only the update writes them.
-    p->br = {};
-    if (c.cfg) AFM_TRY(uncond_setup(*c.w, c.cfg, c.frame_mask, &p->wu, &p->br));
-    p->bra = {};
-    if (c.cfg_a) {
-        if (!c.cfg || !c.scale2 || !c.frame_mask) return AFM_E_BADARG;
-        if (c.cfg->branch_streams) return AFM_E_UNSUPPORTED;       // (four hardware queues do not fit 2 sub-batches x 3 branches)
-        AFM_TRY(uncond_setup(*c.w, c.cfg_a, c.frame_mask, &p->wa, &p->bra));
-    }
+    // Guided loop (g.n > 0): per sub-batch and step the conditioned evaluation (this loop's step as it is, pred_xstart stored the DDIM
+    // loop's way, for DDPM too), each branch of the list on a workspace of its own behind it on the same stream, and ONE update launch
+    // (afm_sampling_update).  Every evaluation reads the same x / K-padded copy; only the update writes them.
+    Guidance& g = p->g;               // (n == 0 as the caller zeroed the plan)
+    if (c.cfg || c.cfg2) AFM_TRY(make_guidance(*c.w, c.cfg, c.cfg2, true, c.frame_mask, &g));
+    if (g.n > 1 && g.branch_streams) return AFM_E_UNSUPPORTED;       // (four hardware queues do not fit 2 sub-batches x 3 evaluations)
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     p->nsub = 0;
     if (a.B == 0) return 0;
     p->nsub = sub_count(a.B, a.n_streams, MAX_SUB);
-    p->branch_streams = c.cfg && c.cfg->branch_streams;
+    p->branch_streams = g.branch_streams != nullptr;
     int64_t off = 0;
     for (int s = 0; s < p->nsub; ++s) {
         SubBatch& sb = p->sb[s];
         sb = {};
         sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, c.cfg_a ? &p->wa : nullptr, c.cfg ? &p->wu : nullptr, c.L, (char*)a.workspace + off, &sb);
+        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
-        if (p->branch_streams) sb.branch = (hipStream_t)c.cfg->branch_streams[s];
+        if (p->branch_streams) sb.branch = (hipStream_t)g.branch_streams[s];
     }
     if (off > a.workspace_bytes) return AFM_E_WORKSPACE;
 
@@ -582,14 +587,13 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     p->w = *c.w;
     p->w.flags = a.loop_flags(p->w.flags);
     // (an imputing loop likewise: the update fused into the motion_layer epilogue is contracted and has no place for the select)
-    if (c.cfg || c.mask) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
+    if (g.n || c.mask) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
     if (p->nsub >= 2 && ((p->w.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < p->nsub; ++s) big = big && (int64_t)p->sb[s].count * T >= 4096;
         if (big) p->w.flags |= 14 << AFM_CMDM_WIDE_TILE_SHIFT;
     }
-    if (c.cfg) { const int nc_u = p->wu.n_cond; p->wu = p->w; p->wu.n_cond = nc_u; }       // the loop's flags (tile code, private bits) on the branch's pack
-    if (c.cfg_a) p->wa = p->w;                                                             // (a masked form: the full layout)
+    for (int i = 0; i < g.n; ++i) g.b[i].w.flags = p->w.flags;       // the loop's flags (tile code, private bits) on every branch's pack
     p->paired = (p->w.flags & AFM_CMDM_PAIR_LAUNCH) && p->nsub == 2 && p->sb[0].count > 0 && p->sb[1].count > 0;
     p->row = (int64_t)c.L * c.w->motion_dim;
     return 0;
@@ -601,67 +605,64 @@ struct Loop {
     Schedule sched;
 };
 
+// the sub-batch's slices of the call's tensors
 inline float* sub_x(const Loop& l, const SubBatch& sb) { return l.c.x + (int64_t)sb.start * l.p.row; }
+inline const float* sub_cond(const Loop& l, const SubBatch& sb) { return l.c.cond_tokens ? l.c.cond_tokens + (int64_t)sb.start * l.p.w.n_cond * l.p.w.d : nullptr; }
+inline const uint8_t* sub_fmask(const Loop& l, const SubBatch& sb) { return l.c.frame_mask ? l.c.frame_mask + (int64_t)sb.start * l.c.L : nullptr; }
 
 // the conditioned evaluation of (sub-batch, step j) on the sub-batch's stream, or into `rec`; *rows and *dd: what the update launches
 // behind it read (in a DDPM loop the evaluation's own epilogue is the update)
 int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_ddpm_args* dd, Recorder* rec) {
     const LoopCall& c = l.c;
-    const afm_cmdm_weights& w = l.p.w;
     const float* nz;
     AFM_TRY(step_noise(c.a, l.p.row, sb, sb.ws.noise, j, sub_x(l, sb), &sb.stream, &nz));
     *rows = l.sched.at(j, sb.start);
     *dd = ddpm_args(c.a, *rows, nz, sub_x(l, sb), sb, j);
-    return forward_impl(w, sub_x(l, sb), rows->t, c.cond_tokens ? c.cond_tokens + (int64_t)sb.start * w.n_cond * w.d : nullptr,
-                        c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr, nullptr, dd, sb.count, c.L, sb.ws, j == 0, sb.stream, rec);
+    return forward_impl(l.p.w, sub_x(l, sb), rows->t, sub_cond(l, sb), sub_fmask(l, sb), nullptr, dd, sb.count, c.L, sb.ws, j == 0, sb.stream, rec);
 }
 
-// the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and the unconditioned branch's, wsu.x0; two scales: and the middle
-// branch's, wsa.x0), in place on x, with the
-// K-padded copy the next step reads
+// the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and each branch's, wsb[i].x0 - the list's last branch is the
+// unconditioned one, a branch in front of it the middle one), in place on x, with the K-padded copy the next step reads
 int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const float* noise) {
     const afm_cmdm_weights& w = l.p.w;
+    const Guidance& g = l.p.g;
     Update u = loop_update(l.c.a, rows, sb.ws.x0, sub_x(l, sb), noise, l.p.row, w.flags & AFM_CMDM_CLIP_X0);
-    if (l.c.cfg) { u.x0_u = sb.wsu.x0; u.scale = l.c.cfg->scale + sb.start; }
-    if (l.c.cfg_a) { u.x0_a = sb.wsa.x0; u.scale2 = l.c.scale2 + sb.start; }
+    if (g.n > 0) { u.x0_u = sb.wsb[g.n - 1].x0; u.scale = g.scale[0] + sb.start; }
+    if (g.n > 1) { u.x0_a = sb.wsb[0].x0; u.scale2 = g.scale[1] + sb.start; }
     if (l.c.mask) { u.known = l.c.known + (int64_t)sb.start * l.p.row; u.mask = l.c.mask + (int64_t)sb.start * l.p.row; }
     u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
     return afm_sampling_update(u, sb.count, sb.stream);
 }
 
-int unguided_step(const Loop& l, const SubBatch& sb, int j) {
-    StepRows rows;
-    afm_ddpm_args dd;
-    AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
-    return l.c.a.ddim || l.c.mask ? update_launch(l, sb, rows, dd.noise) : 0;
-}
-
-int guided_step(const Loop& l, const SubBatch& sb, int j) {
+// one (sub-batch, step): the conditioned evaluation, each branch of a guided loop's list, the update launch (a plain DDPM loop has none:
+// the conditioned evaluation's own epilogue is the update)
+int loop_step(const Loop& l, const SubBatch& sb, int j) {
     const LoopCall& c = l.c;
-    const afm_cmdm_weights &w = l.p.w, &wu = l.p.wu;
-    const bool bs = l.p.branch_streams;
+    const Guidance& g = l.p.g;
     StepRows rows;
     afm_ddpm_args dd;
     AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
-    const float* conds = c.cond_tokens ? c.cond_tokens + (int64_t)sb.start * w.n_cond * w.d : nullptr;
-    const uint8_t* fmask = c.frame_mask ? c.frame_mask + (int64_t)sb.start * c.L : nullptr;
-    // two scales: the middle branch behind the conditioned one on the sub-batch's stream, on its own workspace
-    if (c.cfg_a) AFM_TRY(forward_impl(l.p.wa, sub_x(l, sb), rows.t, conds, fmask, nullptr, &dd, sb.count, c.L, sb.wsa, j == 0, sb.stream, nullptr, &l.p.bra));
-    // step 0: the branch's prologue rewrites the shared K-padded copy (same values), so it starts behind the conditioned branch;
-    // later steps: behind the previous update, next to the conditioned branch
-    const hipStream_t su = bs ? sb.branch : sb.stream;
-    if (bs) {
-        if (j == 0) (void)hipEventRecord(sb.x_ready, sb.stream);
-        (void)hipStreamWaitEvent(su, sb.x_ready, 0);
+    for (int i = 0; i < g.n; ++i) {
+        // every branch behind the conditioned evaluation on the sub-batch's stream, on its own workspace - but the last one on the branch
+        // stream when there is one.  step 0: the branch's prologue rewrites the shared K-padded copy (same values), so it starts behind
+        // the conditioned evaluation; later steps: behind the previous update, next to the conditioned evaluation
+        const bool bs = l.p.branch_streams && i == g.n - 1;
+        const hipStream_t su = bs ? sb.branch : sb.stream;
+        if (bs) {
+            if (j == 0) (void)hipEventRecord(sb.x_ready, sb.stream);
+            (void)hipStreamWaitEvent(su, sb.x_ready, 0);
+        }
+        const int rc = forward_impl(g.b[i].w, sub_x(l, sb), rows.t, sub_cond(l, sb), sub_fmask(l, sb), nullptr, &dd, sb.count, c.L, sb.wsb[i], j == 0, su,
+                                    nullptr, &g.b[i].br);
+        if (bs) {       // (also behind a failed branch: the sub-batch's stream never runs ahead of its branch stream)
+            (void)hipEventRecord(sb.u_ready, su);
+            (void)hipStreamWaitEvent(sb.stream, sb.u_ready, 0);
+        }
+        AFM_TRY(rc);
     }
-    const int rc = forward_impl(wu, sub_x(l, sb), rows.t, wu.n_cond ? conds : nullptr, fmask, nullptr, &dd, sb.count, c.L, sb.wsu, j == 0, su, nullptr, &l.p.br);
-    if (bs) {       // (also behind a failed branch: the sub-batch's stream never runs ahead of its branch stream)
-        (void)hipEventRecord(sb.u_ready, su);
-        (void)hipStreamWaitEvent(sb.stream, sb.u_ready, 0);
-    }
-    AFM_TRY(rc);
+    if (!(g.n || c.a.ddim || c.mask)) return 0;
     AFM_TRY(update_launch(l, sb, rows, dd.noise));
-    if (bs) (void)hipEventRecord(sb.x_ready, sb.stream);       // x and its padded copy of the next step
+    if (l.p.branch_streams) (void)hipEventRecord(sb.x_ready, sb.stream);       // x and its padded copy of the next step
     return 0;
 }
 
@@ -747,7 +748,7 @@ int sample_loop_impl(const LoopCall& c) {
         if (l.p.paired && j > 0) { rc = paired_step(l, j, recs.get(), pev); continue; }
         for (int s = 0; s < l.p.nsub && rc == 0; ++s) {
             if (l.p.sb[s].count == 0) continue;
-            rc = c.cfg ? guided_step(l, l.p.sb[s], j) : unguided_step(l, l.p.sb[s], j);
+            rc = loop_step(l, l.p.sb[s], j);
         }
     }
     // (every branch stream's last work is joined to its sub-batch's stream before the last update)
@@ -758,28 +759,15 @@ int sample_loop_impl(const LoopCall& c) {
 }  // namespace
 
 extern "C" int64_t afm_cmdm_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams) {
-    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
-    return loop_workspace_bytes(*w, nullptr, nullptr, B, L, n_streams);
+    return loop_workspace_bytes(w, nullptr, nullptr, B, L, n_streams);
 }
 
 extern "C" int64_t afm_cmdm_cfg_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg) {
-    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
-    afm_cmdm_weights wu;
-    Branch br;
-    const uint8_t some_mask = 0;                              // (sizes do not depend on the frame mask)
-    if (uncond_setup(*w, cfg, &some_mask, &wu, &br) != 0) return AFM_E_BADARG;
-    return loop_workspace_bytes(*w, nullptr, &wu, B, L, n_streams);
+    return cfg ? loop_workspace_bytes(w, cfg, nullptr, B, L, n_streams) : AFM_E_BADARG;
 }
 
 extern "C" int64_t afm_cmdm_cfg2_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg2_args* cfg) {
-    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
-    afm_cfg_args cu, ca;
-    afm_cmdm_weights wu, wa;
-    Branch br;
-    const uint8_t some_mask = 0;                              // (sizes do not depend on the frame mask)
-    if (cfg2_split(cfg, &cu, &ca) != 0 || uncond_setup(*w, &cu, &some_mask, &wu, &br) != 0 || uncond_setup(*w, &ca, &some_mask, &wa, &br) != 0)
-        return AFM_E_BADARG;
-    return loop_workspace_bytes(*w, &wa, &wu, B, L, n_streams);
+    return cfg ? loop_workspace_bytes(w, nullptr, cfg, B, L, n_streams) : AFM_E_BADARG;
 }
 
 extern "C" int afm_cmdm_sample_loop(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
@@ -851,10 +839,8 @@ extern "C" int afm_cmdm_cfg2_loop_range(const afm_cmdm_weights* w, float* x, con
                                         const afm_cfg2_args* cfg, const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step,
                                         uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                         int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
-    afm_cfg_args cu, ca;
-    if (first_step < 0 || !frame_mask || !known != !mask) return AFM_E_BADARG;
-    AFM_TRY(cfg2_split(cfg, &cu, &ca));
+    if (first_step < 0 || !frame_mask || !known != !mask || !cfg2_ok(cfg)) return AFM_E_BADARG;
     if (rows) d_c1 = d_c2 = d_sigma = nullptr;
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, &cu, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, &ca, cfg->scale_second});
+    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
+                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg});
 }

@@ -274,6 +274,15 @@ afm_loop::Update step_update(const float* x0, const float* x_t, const float* noi
 void set_ddim_rows(afm_loop::Update* p, const afm_ddim_rows* r) {
     p->ddim = 1; p->ra = r->a; p->rb = r->b; p->rc = r->c; p->rd = r->d; p->sg = r->sigma;
 }
+// what the afm_*_step_args entry points share (A: any of the three structs): step_update, the clamp, either kind of rows
+template <class A>
+afm_loop::Update args_update(const A* a) {
+    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
+    p.clip = a->clip ? 1 : 0;
+    if (a->ddim) set_ddim_rows(&p, a->ddim);
+    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    return p;
+}
 }  // namespace
 
 extern "C" int afm_ddpm_step(const float* x0, const float* x_t, const float* noise, float* x_next, const float* c1,
@@ -294,29 +303,23 @@ extern "C" int afm_ddim_step(const float* x0, const float* x_t, const float* noi
 
 extern "C" int afm_cfg_step(const afm_cfg_step_args* a, void* stream) {
     if (!a || !a->x0_c || !a->x0_u || !a->scale) return AFM_E_BADARG;
-    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
-    p.x0_u = a->x0_u; p.scale = a->scale; p.clip = a->clip ? 1 : 0;
-    if (a->ddim) set_ddim_rows(&p, a->ddim);
-    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    afm_loop::Update p = args_update(a);
+    p.x0_u = a->x0_u; p.scale = a->scale;
     return afm_sampling_update(p, a->B, stream);
 }
 
 extern "C" int afm_cfg2_step(const afm_cfg2_step_args* a, void* stream) {
     if (!a || !a->x0_c || !a->x0_a || !a->x0_u || !a->scale_first || !a->scale_second || !a->known != !a->mask) return AFM_E_BADARG;
-    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
+    afm_loop::Update p = args_update(a);
     p.x0_a = a->x0_a; p.x0_u = a->x0_u; p.scale = a->scale_first; p.scale2 = a->scale_second;
-    p.known = a->known; p.mask = a->mask; p.clip = a->clip ? 1 : 0;
-    if (a->ddim) set_ddim_rows(&p, a->ddim);
-    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    p.known = a->known; p.mask = a->mask;
     return afm_sampling_update(p, a->B, stream);
 }
 
 extern "C" int afm_impute_step(const afm_impute_step_args* a, void* stream) {
     if (!a || !a->x0_c || !a->known || !a->mask) return AFM_E_BADARG;
-    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
-    p.x0_u = a->x0_u; p.scale = a->scale; p.known = a->known; p.mask = a->mask; p.clip = a->clip ? 1 : 0;
-    if (a->ddim) set_ddim_rows(&p, a->ddim);
-    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    afm_loop::Update p = args_update(a);
+    p.x0_u = a->x0_u; p.scale = a->scale; p.known = a->known; p.mask = a->mask;
     return afm_sampling_update(p, a->B, stream);
 }
 

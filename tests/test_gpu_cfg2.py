@@ -258,6 +258,33 @@ def test_one_sub_batch_stream_equals_two_at_an_uneven_split(cmdm):
         d5.p_sample_loop(w, (B, L, 263), clip_denoised=False, model_kwargs=kw, seed=4)
 
 
+@pytest.mark.parametrize("form", ["two_scale", "one_scale_compact", "one_scale_masked"])
+def test_every_guided_form_at_an_uneven_split_and_a_partial_quad(cmdm, form):
+    """B = 3, L = 15 (sub-batches of 2 + 1; 3945 values per sample: the update's last quad and the K-padded row copy end on a partial
+    quad), {DDPM, DDIM eta = 0.5} x {no imputation, Impute}: two sub-batch streams and the step-by-step loop through the same wrapper
+    are the native one-stream loop bit for bit - what a wrong branch order, workspace alias or stream would break."""
+    B, L = 3, 15
+    _, _, kw, scales = _batch3()
+    kw = dict(kw, x_mask=D(synth.frame_mask(B, L, min_len=8)))
+    w = GuidedCMDM(cmdm, scales) if form == "two_scale" else GuidedCMDM(cmdm, scales["text"], force_masked=form == "one_scale_masked")
+    imp = Impute(D(synth.gaussian("cfg2_b3_L15_known", (B, L, 263))), D(synth.gaussian("cfg2_b3_L15_mask", (B, L, 263)) > 0))
+    loops = {"ddpm": (create_gaussian_diffusion(cmdm_cfg(steps=1000, respacing="5")), "p_sample_loop", {}),
+             "ddim": (create_gaussian_diffusion(cmdm_cfg(steps=1000, respacing="ddim5")), "ddim_sample_loop", {"eta": 0.5})}
+    saved = (cmdm.loop_streams, cmdm.loop_streams_auto, cmdm.pair_launch)
+    try:
+        for name, (d, loop, extra) in loops.items():
+            args = dict(noise=D(synth.gaussian(f"cfg2_b3_L15_{name}_xT", (B, L, 263))), clip_denoised=True, model_kwargs=kw,
+                        step_noise=D(torch.stack([synth.gaussian(f"cfg2_b3_L15_{name}_{j}", (B, L, 263)) for j in range(d.num_timesteps)])), **extra)
+            for fn in (None, imp):
+                cmdm.loop_streams, cmdm.loop_streams_auto, cmdm.pair_launch = 1, True, False
+                one = getattr(d, loop)(w, (B, L, 263), denoised_fn=fn, **args)
+                assert torch.equal(one, _last(getattr(d, loop + "_progressive")(w, (B, L, 263), denoised_fn=fn, **args))), (name, fn)
+                cmdm.loop_streams, cmdm.loop_streams_auto = 2, False
+                assert torch.equal(one, getattr(d, loop)(w, (B, L, 263), denoised_fn=fn, **args)), (name, fn)
+    finally:
+        cmdm.loop_streams, cmdm.loop_streams_auto, cmdm.pair_launch = saved
+
+
 def test_a_batch_of_three_equals_its_samples_run_in_shards(cmdm):
     B, L, kw, scales = _batch3()
     d = create_gaussian_diffusion(cmdm_cfg(steps=1000, respacing="5"))
