@@ -29,8 +29,12 @@ def create_gaussian_diffusion(cfg, *args, **kwargs):
         var_type = gd.ModelVarType.LEARNED_RANGE
     else:
         var_type = gd.ModelVarType.FIXED_SMALL if c.sigma_small else gd.ModelVarType.FIXED_LARGE
-    return gd.SpacedDiffusion(use_timesteps=gd.space_timesteps(steps, respacing),
-                              betas=gd.get_named_beta_schedule(c.noise_schedule, steps),
+    betas = gd.get_named_beta_schedule(c.noise_schedule, steps)
+    if isinstance(respacing, str) and respacing.startswith("logsnr"):      # uniform in log-SNR (needs the betas: not space_timesteps')
+        use = gd.logsnr_timesteps(betas, int(respacing[len("logsnr"):]))
+    else:
+        use = gd.space_timesteps(steps, respacing)
+    return gd.SpacedDiffusion(use_timesteps=use, betas=betas,
                               model_mean_type=mean_type, model_var_type=var_type, loss_type=loss_type,
                               rescale_timesteps=c.rescale_timesteps)
 

@@ -541,17 +541,22 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
     # ------------------------------------------------------------------ native sampling loop
     def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                        clip_denoised=False, ddim_eta: Optional[float] = None, impute=None, _guidance=None):
+                        clip_denoised=False, ddim_eta: Optional[float] = None, impute=None, _guidance=None, dpm_order: Optional[int] = None):
         """Whole p_sample_loop on the device: x holds x_T on entry, returns the final sample.  ``clip_denoised``: pred_xstart clamped to
         [-1, 1] inside the fused DDPM update (the reference's default argument; test.py passes False).  ``ddim_eta`` not None: the
         ddim_sample_loop with that eta instead (afm_cmdm_ddim_loop_range: the same launches, the DDIM update in the same epilogue).  ``progress`` (test.py:85 passes
         True) splits the chain into ~50 native slices (afm_cmdm_sample_loop_range) and advances a tqdm bar between them; the
         result is bit-identical to the unsliced loop.  ``impute``: an afm.diffusion.Impute - its known values are written over every step's
-        pred_xstart before the clamp, inside the loop's update launch (afm_cmdm_impute_loop_range, all four forms).  ``_guidance``:
+        pred_xstart before the clamp, inside the loop's update launch (afm_cmdm_impute_loop_range, all four forms).  ``dpm_order`` (1 or
+        2) not None: dpm_solver_sample_loop instead (afm_cmdm_dpm_loop_range, every form: the eta = 0 DDIM loop's launches with the
+        DPM-Solver++ update and one history buffer per sub-batch in the workspace; no noise: ``step_noise`` is refused, ``seed`` unused;
+        sliced chains stay bit-identical because every range call of one chain runs on the same workspace).  ``_guidance``:
         GuidedCMDM's (afm_cfg_args or afm_cfg2_args, branch streams?) (the guided loops; not a caller's argument)."""
         if any(k in model_kwargs for k in COND_SWITCHES):
             raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
                                       "p_sample_loop samples them step by step (p_sample_loop_progressive)")
+        if dpm_order is not None and (ddim_eta is not None or step_noise is not None):
+            raise ValueError("the DPM-Solver++ loop is deterministic: it takes neither ddim_eta nor step_noise")
         lib = ffi.load()
         ffi.require_gpu(x)
         with torch.no_grad():
@@ -563,11 +568,14 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if clip_denoised:
                 w.flags |= ffi.CMDM_CLIP_X0                  # per call: _stamp() rewrites the flags on the next _weights()
             cond = self.condition_tokens(**model_kwargs)
+            if tuple(cond.shape[:2]) != (B, w.n_cond):       # (e.g. a cloud of fewer points than contact_model.num_points: the loop reads n_cond rows per sample)
+                raise ValueError(f"the conditions give {tuple(cond.shape[:2])} tokens, the model's layout has ({B}, {w.n_cond})")
             fm = model_kwargs["x_mask"].to(device=x.device, dtype=torch.uint8).contiguous() if self.mask_motion else None
             tab = diffusion.tables(x.device)
             n = diffusion.num_timesteps
-            sched = ffi.sched_scratch(self, n, B, x.device, ddim=ddim_eta is not None)
+            sched = ffi.sched_scratch(self, n, B, x.device, ddim=ddim_eta is not None or dpm_order is not None)
             ddim = None if ddim_eta is None else diffusion.ddim_tables(x.device, ddim_eta)
+            dpm = None if dpm_order is None else diffusion.dpm_tables(x.device, dpm_order)
             # sub-batch streams fill the wave-quantisation tails of B >= 16 launches; below that every launch is latency-bound and a
             # second stream only adds launches (B = 4: 1311 steps/s on one stream vs 1159 on two, profiles/r02_small_batch.md)
             nsub = max(1, min(int(self.loop_streams), B // 8 if self.loop_streams_auto else B))
@@ -587,7 +595,10 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[:nsub]])
                 branch_handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[nsub:2 * nsub]])
                 cfg.branch_streams = C.cast(branch_handles, C.POINTER(C.c_void_p))
-            if cfg is None:
+            if dpm is not None:
+                nbytes = lib.afm_cmdm_dpm_loop_workspace_bytes(C.byref(w), B, L, nsub, None if cfg is None or two else C.byref(cfg),
+                                                               C.byref(cfg) if two else None)
+            elif cfg is None:
                 nbytes = lib.afm_cmdm_loop_workspace_bytes(C.byref(w), B, L, nsub)
             elif two:
                 nbytes = lib.afm_cmdm_cfg2_loop_workspace_bytes(C.byref(w), B, L, nsub, C.byref(cfg))
@@ -596,6 +607,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if nbytes < 0:
                 ffi.check(int(nbytes), "afm_cmdm_loop_workspace_bytes")
             form = "loop" if cfg is None else ("cfg2_loop", cfg.first, cfg.flags) if two else ("cfg_loop", cfg.drop_text, cfg.drop_pc, cfg.flags)
+            if dpm is not None:         # (a size of its own: the history buffers)
+                form = ("dpm", form)
             key = (form, B, L, nsub, str(x.device))
             if key not in self._ws:
                 self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
@@ -610,6 +623,14 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
+                if dpm is not None:         # one entry for every form; the history of step j0 - 1 is in `ws`
+                    rc = lib.afm_cmdm_dpm_loop_range(
+                        C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), tab.timestep_map[lo:].data_ptr(), C.byref(dpm.rows(lo)),
+                        None if cfg is None or two else C.byref(cfg), C.byref(cfg) if two else None,
+                        None if impute is None else impute.known.data_ptr(), None if impute is None else impute.mask.data_ptr(),
+                        j1 - j0, j0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub if nsub > 1 else 0,
+                        handles if nsub > 1 else None, stream)
+                    return ffi.check(rc, "afm_cmdm_dpm_loop_range")
                 head = (C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), nz, tab.timestep_map[lo:].data_ptr())
                 rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
                     (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
@@ -624,7 +645,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim, _guidance, impute)
+            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim, dpm, _guidance, impute)
         return x
 
 
@@ -759,12 +780,13 @@ class GuidedCMDM(nn.Module):
     def forward(self, x, timesteps, **kwargs):
         return self.branches(x, timesteps, **kwargs)[-1]
 
-    def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, **kw):
+    def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, dpm_order: Optional[int] = None, **kw):
         """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range; with ``impute``: the guided form of
-        afm_cmdm_impute_loop_range; one scale per condition: afm_cmdm_cfg2_loop_range, every form): CMDM.afm_native_loop's arguments."""
+        afm_cmdm_impute_loop_range; one scale per condition: afm_cmdm_cfg2_loop_range, every form; ``dpm_order``: the guided forms of
+        afm_cmdm_dpm_loop_range): CMDM.afm_native_loop's arguments."""
         self._no_switches(model_kwargs)
         if self.model.training:
             raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
         cfg = self._cfg(x.shape[0], x.device)          # (a [B] scale of the wrong length is refused here)
         ffi.require_gpu(x)
-        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams), impute=impute, **kw)
+        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams), impute=impute, dpm_order=dpm_order, **kw)

@@ -151,6 +151,11 @@ class DdimRows(C.Structure):
     _fields_ = [("a", c_f32p), ("b", c_f32p), ("c", c_f32p), ("d", c_f32p), ("sigma", c_f32p)]
 
 
+class DpmRows(C.Structure):
+    """afm_dpm_rows (v7-additive): device pointers of the three DPM-Solver++(2M) rows (a, b, c)."""
+    _fields_ = [("a", c_f32p), ("b", c_f32p), ("c", c_f32p)]
+
+
 class CfgArgs(C.Structure):
     """afm_cfg_args (v7-additive): classifier-free guidance of the CMDM - device [B] scales, the dropped conditions, AFM_CFG_* flags."""
     _fields_ = [("scale", c_f32p), ("drop_text", i32), ("drop_pc", i32), ("flags", i32), ("branch_streams", C.POINTER(C.c_void_p))]
@@ -235,6 +240,11 @@ EXPORTS = {
     "afm_cmdm_cfg2_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
                                            c_f32p, c_f32p, c_f32p, C.POINTER(Cfg2Args), c_f32p, C.c_void_p, i32, i32, u64, i64, i32, i32,
                                            C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_dpm_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(DpmRows), i32, i64, C.c_void_p]),
+    "afm_cmdm_dpm_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args)]),
+    "afm_cmdm_dpm_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.POINTER(DpmRows), C.POINTER(CfgArgs),
+                                          C.POINTER(Cfg2Args), c_f32p, C.c_void_p, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                          C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

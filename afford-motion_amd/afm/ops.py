@@ -329,6 +329,28 @@ def ddim_step(x0: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor]
     return out
 
 
+def dpm_step(x0: torch.Tensor, x_t: torch.Tensor, prev: Optional[torch.Tensor], a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, *,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """DPM-Solver++(2M) update (afm_dpm_step): x_next = a*x_t + b*x0 (``prev`` None: no history) or (a*x_t + b*x0) + c*prev, per-sample
+    rows [B], float32, every operation rounded on its own.  No noise term.  ``out`` may be ``x_t``."""
+    lib = ffi.load()
+    ffi.require_gpu(x0, x_t, prev)
+    x0, x_t = ffi.f32c(x0), ffi.f32c(x_t)
+    pv = None if prev is None else ffi.f32c(prev)
+    if x_t.shape != x0.shape or (pv is not None and pv.shape != x0.shape):
+        raise ValueError(f"dpm_step: x0 {tuple(x0.shape)}, x_t {tuple(x_t.shape)} and prev must have one shape")
+    B = x0.shape[0]
+    per = x0.numel() // max(B, 1)
+    out = torch.empty_like(x0) if out is None else out
+    keep = [ffi.f32c(r) for r in (a, b, c)]
+    if any(r.numel() != B for r in keep):
+        raise ValueError(f"dpm_step: the rows hold one value per sample ({B})")
+    rows = ffi.DpmRows(*[r.data_ptr() for r in keep])
+    ffi.check(lib.afm_dpm_step(x0.data_ptr(), x_t.data_ptr(), ffi.ptr(pv), out.data_ptr(), C.byref(rows), B, per, ffi.stream_of(x0)),
+              "afm_dpm_step")
+    return out
+
+
 def cfg_combine(x0_c: torch.Tensor, x0_u: torch.Tensor, scale: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Classifier-free guidance of an x_start prediction (afm_cfg_combine): x0_u + scale[b] * (x0_c - x0_u), float32, every operation
     rounded on its own; scale [B]."""

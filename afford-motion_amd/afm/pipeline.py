@@ -28,7 +28,10 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
 
     ``*_noise`` = optional {"x_T": ..., "steps": [T, ...]} explicit noise (parity tests); otherwise Philox
     keyed by (seed, sample_index0 + b), stage 2 uses seed + 1.  ``sampler`` = "ddpm" (p_sample_loop) or "ddim" (ddim_sample_loop with
-    ``eta``) for both stages; DDIM runs the spaced process of each diffusion (e.g. timestep_respacing="ddim50").
+    ``eta``) for both stages; DDIM runs the spaced process of each diffusion (e.g. timestep_respacing="ddim50").  ``sampler`` = "dpm++":
+    DPM-Solver++(2M) (dpm_solver_sample_loop, deterministic; ``eta`` must be 0, explicit step noise is refused) on the spaced process of each
+    diffusion (e.g. timestep_respacing="logsnr20"): the motion stage runs in the CMDM's native loop, the contact stage step by step
+    (CDM.forward + afm_dpm_step per step; the CDM has no native form of this sampler).
     ``guidance_scale`` (a float or a [B] tensor; None = unguided): classifier-free guidance of the MOTION stage, dropping the conditions named
     in ``guidance_drop`` (afm.cmdm.GuidedCMDM; the CDM of the first stage never reads the condition switches).  A mapping
     ``{"pc": s_pc, "text": s_text}`` (insertion order = first, second) gives every condition a scale of its own; ``guidance_drop`` must
@@ -37,8 +40,10 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     loops).  The contact stage is the one to steer: ``contact_impute.known`` [B, N, J] lives in the CDM's own sample space, the
     normalised contact (exp(-d^2 / 2 sigma^2) - mean) / std - pin it on the points of a chosen object, or to the value of zero contact
     on a region to keep clear.  ``motion_impute.known`` [B, frames, D] lives in the normalised motion space."""
-    if sampler not in ("ddpm", "ddim"):
-        raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+    if sampler not in ("ddpm", "ddim", "dpm++"):
+        raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpm++', not {sampler!r}")
+    if sampler == "dpm++" and float(eta) != 0.0:
+        raise ValueError(f"sampler 'dpm++' is deterministic: eta must be 0, not {eta!r}")
     if isinstance(guidance_scale, Mapping):          # (refused before the first stage runs)
         dropped = {guidance_drop} if isinstance(guidance_drop, str) else set(guidance_drop)
         if dropped != set(guidance_scale):
@@ -47,6 +52,10 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     def loop(diffusion, *args, **kw):
         if sampler == "ddim":
             return diffusion.ddim_sample_loop(*args, eta=eta, **kw)
+        if sampler == "dpm++":
+            if kw.pop("step_noise") is not None:
+                raise ValueError("sampler 'dpm++' has no noise term: remove the \"steps\" noise")
+            return diffusion.dpm_solver_sample_loop(*args, **kw)
         return diffusion.p_sample_loop(*args, **kw)
 
     B, N = xyz.shape[0], xyz.shape[1]

@@ -481,6 +481,7 @@ extern "C" int64_t afm_ddim_sched_scratch_bytes(int32_t n_steps, int32_t B) {
 // (`ddim` != NULL: motion_layer stores pred_xstart and ONE elementwise launch per sub-batch and step, afm_sampling_update, applies the
 // update), each unguided or guided (`cfg` != NULL).  (The DDIM update fused into the shared GEMM epilogue grew the registers - and on three
 // variants the scratch - of DDPM GEMM kernels that every sampling step runs; a launch of its own leaves them as they were.)
+// The DPM-Solver++(2M) loop (`a.dpm`) is the eta = 0 DDIM loop with the 2M update in that launch and one history buffer per sub-batch.
 // plan_loop decides everything a call fixes before its first launch; the step functions enqueue one (sub-batch, step); sample_loop_impl
 // owns the schedule, the events and the order.  The shared pieces (sub-batches, schedule, noise, events) live in sample_loop.h.
 namespace {
@@ -488,7 +489,7 @@ namespace {
 constexpr int MAX_SUB = 16;           // sub-batches (streams) of one loop call
 constexpr int NEV = 2 * AFM_MAX_LAYERS;      // events of the paired schedule: two cross-stream edges per layer
 
-// the arguments of the seven loop entry points: the model's tensors, the guidance as the caller describes it (at most one of cfg / cfg2;
+// the arguments of the eight loop entry points: the model's tensors, the guidance as the caller describes it (at most one of cfg / cfg2;
 // neither: unguided), what every loop takes, the imputation
 struct LoopCall {
     const afm_cmdm_weights* w;
@@ -509,10 +510,11 @@ struct SubBatch : SubRange {
     // writer of x and of its K-padded copy (x_ready: x is ready, u_ready: the branch's pred_xstart is ready)
     hipStream_t branch;
     hipEvent_t x_ready, u_ready;
+    float* hist;                      // 2M loop only: the previous step's final x0 [count][L * motion_dim], behind every evaluation's workspace
 };
 
 // carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
-int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb) {
+int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist) {
     sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
     int64_t off = sb->ws.bytes;
     for (int i = 0; i < g.n; ++i) {
@@ -521,11 +523,17 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
         sb->wsb[i].xpad = sb->ws.xpad;       // one K-padded copy of x_t serves every branch
         off += sb->wsb[i].bytes;
     }
+    sb->hist = nullptr;
+    if (hist) {                       // (carved for the 2M loop alone: the other forms' sizes stay as they are)
+        sb->hist = base ? (float*)(base + off) : nullptr;
+        off += align256((int64_t)sb->count * L * w.motion_dim * 4);
+    }
     return off;
 }
 
 // the loop workspace of either public description of the guidance (neither: the unguided loop's); AFM_E_BADARG as the loop itself
-int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams) {
+int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams,
+                             bool hist = false) {
     if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
     Guidance g = {};
     if ((one || two) && make_guidance(*w, one, two, false, nullptr, &g) != 0) return AFM_E_BADARG;
@@ -534,7 +542,7 @@ int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one,
     for (int s = 0; s < n; ++s) {
         SubBatch sb = {};
         sub_range(B, n, s, &sb.start, &sb.count);
-        total += carve_sub(*w, g, L, nullptr, &sb);
+        total += carve_sub(*w, g, L, nullptr, &sb, hist);
     }
     return total;
 }
@@ -560,6 +568,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     if (c.cfg || c.cfg2) AFM_TRY(make_guidance(*c.w, c.cfg, c.cfg2, true, c.frame_mask, &g));
     if (g.n > 1 && g.branch_streams) return AFM_E_UNSUPPORTED;       // (four hardware queues do not fit 2 sub-batches x 3 evaluations)
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
+    if (a.dpm && (!a.ddim || a.noise_term() || a.step_noise || a.first_step < 0)) return AFM_E_BADARG;
     p->nsub = 0;
     if (a.B == 0) return 0;
     p->nsub = sub_count(a.B, a.n_streams, MAX_SUB);
@@ -569,7 +578,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         SubBatch& sb = p->sb[s];
         sb = {};
         sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb);
+        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
         if (p->branch_streams) sb.branch = (hipStream_t)g.branch_streams[s];
     }
@@ -622,8 +631,10 @@ int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_d
 }
 
 // the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and each branch's, wsb[i].x0 - the list's last branch is the
-// unconditioned one, a branch in front of it the middle one), in place on x, with the K-padded copy the next step reads
-int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const float* noise) {
+// unconditioned one, a branch in front of it the middle one), in place on x, with the K-padded copy the next step reads.  2M loop: the
+// final x0 of step j is kept in the sub-batch's history, which the next step - of this call or of the next range call on the same
+// workspace - reads; the first executed step of a chain (first_step + j == 0) has no history and takes the two-term form
+int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const float* noise, int j) {
     const afm_cmdm_weights& w = l.p.w;
     const Guidance& g = l.p.g;
     Update u = loop_update(l.c.a, rows, sb.ws.x0, sub_x(l, sb), noise, l.p.row, w.flags & AFM_CMDM_CLIP_X0);
@@ -631,6 +642,7 @@ int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const
     if (g.n > 1) { u.x0_a = sb.wsb[0].x0; u.scale2 = g.scale[1] + sb.start; }
     if (l.c.mask) { u.known = l.c.known + (int64_t)sb.start * l.p.row; u.mask = l.c.mask + (int64_t)sb.start * l.p.row; }
     u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
+    if (l.c.a.dpm) { u.x0_prev = l.c.a.first_step + j > 0 ? sb.hist : nullptr; u.x0_keep = sb.hist; }
     return afm_sampling_update(u, sb.count, sb.stream);
 }
 
@@ -661,7 +673,7 @@ int loop_step(const Loop& l, const SubBatch& sb, int j) {
         AFM_TRY(rc);
     }
     if (!(g.n || c.a.ddim || c.mask)) return 0;
-    AFM_TRY(update_launch(l, sb, rows, dd.noise));
+    AFM_TRY(update_launch(l, sb, rows, dd.noise, j));
     if (l.p.branch_streams) (void)hipEventRecord(sb.x_ready, sb.stream);       // x and its padded copy of the next step
     return 0;
 }
@@ -705,7 +717,7 @@ int paired_step(const Loop& l, int j, Recorder* recs, const hipEvent_t* pev) {
         AFM_TRY(cond_forward(l, l.p.sb[s], j, &rows[s], &dd[s], &recs[s]));
     }
     AFM_TRY(issue_paired(recs[0], recs[1], l.p.sb[0].stream, l.p.sb[1].stream, pev, NEV));
-    for (int s = 0; l.c.a.ddim && s < 2; ++s) AFM_TRY(update_launch(l, l.p.sb[s], rows[s], dd[s].noise));
+    for (int s = 0; l.c.a.ddim && s < 2; ++s) AFM_TRY(update_launch(l, l.p.sb[s], rows[s], dd[s].noise, j));
     return 0;
 }
 
@@ -843,4 +855,26 @@ extern "C" int afm_cmdm_cfg2_loop_range(const afm_cmdm_weights* w, float* x, con
     if (rows) d_c1 = d_c2 = d_sigma = nullptr;
     return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
                              sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg});
+}
+
+// DPM-Solver++(2M): the eta = 0 DDIM loop's launches (pred_xstart stored, one update launch per sub-batch and step) with the 2M update and
+// one history buffer per sub-batch.  The rows travel through the DDIM schedule layout as {a, b, c, unused}.
+extern "C" int64_t afm_cmdm_dpm_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                     const afm_cfg2_args* cfg2) {
+    if (cfg && cfg2) return AFM_E_BADARG;
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true);
+}
+
+extern "C" int afm_cmdm_dpm_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                       const int64_t* d_timestep_map, const afm_dpm_rows* rows, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2,
+                                       const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step, int32_t B, int32_t L,
+                                       void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                       void* stream) {
+    if (first_step < 0 || !rows || !rows->a || !rows->b || !rows->c || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
+    if (cfg2 && (!frame_mask || !cfg2_ok(cfg2))) return AFM_E_BADARG;
+    const afm_ddim_rows as_ddim = {rows->a, rows->b, rows->c, rows->c, nullptr};          // (d: any valid row, never used by dpm_update)
+    LoopCall c = {w, x, cond_tokens, frame_mask, cfg, L, {nullptr, d_timestep_map, nullptr, nullptr, nullptr, &as_ddim, n_steps, first_step, 0, 0, B,
+                  sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2};
+    c.a.dpm = true;
+    return sample_loop_impl(c);
 }

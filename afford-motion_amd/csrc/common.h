@@ -311,6 +311,23 @@ __device__ __forceinline__ float ddim_update(float x0, float xt, const float4& r
     return mean + sn;
 }
 
+// ---- DPM-Solver++(2M) update of one element (Lu et al. 2022, the multistep data-prediction solver; no counterpart in the reference), float32
+// with every operation rounded on its own:  x_next = a * x_t + b * x0  (no history: the first executed step, a caller without a previous
+// prediction), or  x_next = (a * x_t + b * x0) + c * x0_prev.  r = {a, b, c, unused} of the element's sample (afm_dpm_rows, built by the host
+// in float64).  No noise term.  The only place the expression is written: afm_dpm_step and the 2M native loops call this helper.
+__device__ __forceinline__ float dpm_update(float x0, float xt, const float4& r) {
+#pragma clang fp contract(off)
+    const float m1 = r.x * xt;
+    const float m2 = r.y * x0;
+    return m1 + m2;
+}
+__device__ __forceinline__ float dpm_update(float x0, float xt, const float4& r, float x0_prev) {
+#pragma clang fp contract(off)
+    const float two = dpm_update(x0, xt, r);
+    const float m3 = r.z * x0_prev;
+    return two + m3;
+}
+
 // ---- classifier-free guidance of an x_start-predicting denoiser, one element: x0_u + s * (x0_c - x0_u) in float32, this association,
 // every operation rounded on its own (what the float32 torch expression gives).  s = the guidance scale of the element's sample.  Every
 // guided site (afm_cfg_combine, the guided update of afm_cfg_step and of the guided native loops) calls this one helper.

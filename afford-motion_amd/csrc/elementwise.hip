@@ -1,4 +1,4 @@
-// LayerNorm, the sampling update (DDPM, DDIM, guided), Philox normal generator.
+// LayerNorm, the sampling update (DDPM, DDIM, DPM-Solver++(2M), guided), Philox normal generator.
 // All three are HBM/L2-streaming kernels: float4 accesses, one wave per LayerNorm row.
 #include "profile.h"
 #include "sample_loop.h"
@@ -49,6 +49,7 @@ __global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __r
 // sg == NULL: no noise term).  Every operation is one of common.h's individually rounded helpers (the reference's float32 torch expression,
 // bit for bit).  xn may alias xt (one thread reads then writes an element).  noise == NULL with a noise term: Philox keyed by the quad q.
 // xpad: x_next also into rows of ldpad floats (the next motion-adapter GEMM's K-padded A rows; columns >= cols stay zero).
+// dpm: dpm_update on the rows {a, b, c} instead (x0_prev NULL: its two-term form), v - the final x0 - also stored to x0_keep when asked.
 __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Update p) {
     const int b = blockIdx.y;
     const float s = p.x0_u ? p.scale[b] : 0.f;
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Up
     const float sg = p.sg ? p.sg[b] : 0.f;
     float4 r = make_float4(0.f, 1.f, 0.f, 0.f);
     float c1 = 0.f, c2 = 0.f;
-    if (p.ddim) r = p.rec ? p.rec[b] : make_float4(p.ra[b], p.rb[b], p.rc[b], p.rd[b]);
+    if (p.ddim) r = p.rec ? p.rec[b] : make_float4(p.ra[b], p.rb[b], p.rc[b], p.rd ? p.rd[b] : 0.f);
     else { c1 = p.c1[b]; c2 = p.c2[b]; }
     const int64_t base = (int64_t)b * p.per_sample;
     const int64_t nquad = (p.per_sample + 3) >> 2;
@@ -76,7 +77,10 @@ __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Up
                 const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
                 const float vt = p.xt[g];
                 float xn;
-                if (p.ddim) xn = p.sg ? ddim_update(v, vt, r, sg, nz) : ddim_update(v, vt, r);
+                if (p.dpm) {
+                    xn = p.x0_prev ? dpm_update(v, vt, r, p.x0_prev[g]) : dpm_update(v, vt, r);
+                    if (p.x0_keep) p.x0_keep[g] = v;
+                } else if (p.ddim) xn = p.sg ? ddim_update(v, vt, r, sg, nz) : ddim_update(v, vt, r);
                 else xn = ddpm_update(v, vt, c1, c2, sg, nz);
                 p.xn[g] = xn;
                 if (p.xpad) {
@@ -241,7 +245,7 @@ extern "C" int afm_layernorm_rows(const float* x, const float* gamma, const floa
     return 0;
 }
 
-// ---- the sampling update: one launcher behind afm_ddpm_step, afm_ddim_step, afm_cfg_step and the update launch of the native loops
+// ---- the sampling update: one launcher behind afm_ddpm_step, afm_ddim_step, afm_dpm_step, afm_cfg_step and the update launch of the native loops
 namespace {
 int enqueue_update(const afm_loop::Update& p, int32_t B, hipStream_t s) {
     hipLaunchKernelGGL(sampling_update_kernel, stream_grid(quads(p.per_sample), 1024, B), dim3(256), 0, s, p);
@@ -253,7 +257,8 @@ int enqueue_update(const afm_loop::Update& p, int32_t B, hipStream_t s) {
 __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream) {
     if (!p.x0 || !p.xt || !p.xn || !p.x0_u != !p.scale || !p.known != !p.mask || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
     if (!p.x0_a != !p.scale2 || (p.x0_a && !p.x0_u)) return AFM_E_BADARG;          // a middle branch: both scales and the unconditioned branch
-    if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && p.rd)) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
+    if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && (p.rd || p.dpm))) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
+    if (p.dpm ? (!p.ddim || p.sg) : (p.x0_prev || p.x0_keep)) return AFM_E_BADARG;          // 2M: DDIM-layout rows, no noise term; history only there
     if (p.sg && !p.noise && !p.philox) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside their launch)
     if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
     if (B == 0) return 0;
@@ -298,6 +303,15 @@ extern "C" int afm_ddim_step(const float* x0, const float* x_t, const float* noi
     if (!rows) return AFM_E_BADARG;
     afm_loop::Update p = step_update(x0, x_t, noise, x_next, per_sample, seed, sample_index0, step);
     set_ddim_rows(&p, rows);
+    return afm_sampling_update(p, B, stream);
+}
+
+extern "C" int afm_dpm_step(const float* x0, const float* x_t, const float* x0_prev, float* x_next, const afm_dpm_rows* rows, int32_t B,
+                            int64_t per_sample, void* stream) {
+    if (!rows) return AFM_E_BADARG;
+    afm_loop::Update p = {};
+    p.x0 = x0; p.xt = x_t; p.xn = x_next; p.per_sample = per_sample; p.x0_prev = x0_prev;
+    p.ddim = 1; p.dpm = 1; p.ra = rows->a; p.rb = rows->b; p.rc = rows->c;
     return afm_sampling_update(p, B, stream);
 }
 

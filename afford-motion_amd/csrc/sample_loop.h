@@ -12,7 +12,8 @@ __attribute__((visibility("hidden"))) int afm_ddim_expand_rows(const int64_t* tm
 __attribute__((visibility("hidden"))) int afm_randn_steps(float*, int32_t, int64_t, uint64_t, int64_t, int32_t, int32_t, void*);      // [nsteps][B][per_sample]
 namespace afm_loop { struct Update; }
 // checks and enqueues one sampling update over B samples (AFM_E_BADARG: a NULL tensor or row, x0_u without scale or known without mask or
-// the reverse, a middle branch x0_a without both scales and x0_u, a noise term without noise unless `philox`, xpad with ldpad < cols; B == 0: nothing to do)
+// the reverse, a middle branch x0_a without both scales and x0_u, a noise term without noise unless `philox`, xpad with ldpad < cols, `dpm`
+// without DDIM-layout rows or with a noise term, x0_prev / x0_keep without `dpm`; B == 0: nothing to do)
 __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream);
 
 namespace afm_loop {
@@ -31,11 +32,15 @@ struct Update {
     const float* noise;             // NULL with a noise term: drawn in the kernel from (seed, sample0 + b, step) if `philox`, else rejected
     const float *c1, *c2, *sg;      // DDPM rows [B]; sg is also the DDIM noise coefficient (NULL there: no noise term, noise never read)
     const float *ra, *rb, *rc, *rd; // DDIM rows [B] (`ddim` set), or
-    const float4* rec;              //   the same as {a, b, c, d} records [B]
+    const float4* rec;              //   the same as {a, b, c, d} records [B].  With `dpm`: the 2M rows {a, b, c, unused} (rd may be NULL)
     float* xpad;                    // x_next also as rows of `cols` values at row stride ldpad (NULL: none)
     int64_t ldpad, per_sample, sample0;
     uint64_t seed;
     int cols, clip, ddim, philox, step;
+    int dpm;                        // DPM-Solver++(2M) update (dpm_update of common.h) on the DDIM-layout rows; `ddim` set too, no noise term
+    const float* x0_prev;           // `dpm`: the previous step's final x0 [B][per_sample]; NULL: the two-term form (never read then)
+    float* x0_keep;                 // `dpm`: the final x0 (after combine, select and clamp) is also stored here; NULL: not kept.  May alias
+                                    //   x0_prev (one thread reads then writes an element)
 };
 
 inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
@@ -59,6 +64,7 @@ struct LoopArgs {
     int n_streams;
     void* const* streams;
     void* stream;
+    bool dpm = false;               // the 2M loop: `ddim` holds its rows as {a, b, c, d = c (unused), sigma = NULL}; no noise, no seed
 
     bool ok() const {
         const bool rows_ok = ddim ? (ddim->a && ddim->b && ddim->c && ddim->d) : (c1 && c2 && sigma);
@@ -150,6 +156,7 @@ inline Update loop_update(const LoopArgs& a, const StepRows& rows, const float* 
     if (rows.rec) { u.ddim = 1; u.rec = rows.rec; }
     else { u.c1 = rows.c1; u.c2 = rows.c2; }
     if (a.noise_term()) { u.sg = rows.sigma; u.noise = noise; }
+    u.dpm = a.dpm ? 1 : 0;
     return u;
 }
 

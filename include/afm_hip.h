@@ -250,6 +250,23 @@ typedef struct {
 int afm_ddim_step(const float* x0, const float* x_t, const float* noise, float* x_next, const afm_ddim_rows* rows,
                   int32_t B, int64_t per_sample, uint64_t seed, int64_t sample_index0, int32_t step, void* stream);
 
+/* ---- DPM-Solver++(2M) (v7-additive; Lu et al. 2022, the second-order multistep solver for x_start-predicting models; the reference has
+ * no such sampler).  afm_dpm_rows: three float32 rows indexed like the afm_ddim_rows.  With alpha_i = sqrt(abar_i), sigma_i =
+ * sqrt(1 - abar_i), lambda_i = ln(alpha_i / sigma_i) of the (respaced) process, the step from timestep index i to i - 1 has
+ *   h_i = lambda_{i-1} - lambda_i,  a_i = sigma_{i-1} / sigma_i,  k_i = -alpha_{i-1} * expm1(-h_i),  r_i = h_{i+1} / h_i
+ *   (b_i, c_i) = (k_i, 0) at the first executed step i = n - 1 and for order 1; (k_i * (1 + 1 / (2 r_i)), -k_i / (2 r_i)) otherwise;
+ *   (a_0, b_0, c_0) = (0, 1, 0): the last step returns pred_xstart.
+ * The host computes them in float64 and stores float32. */
+typedef struct {
+    const float* a; const float* b; const float* c;
+} afm_dpm_rows;
+
+/* afm_dpm_step: x_next = a[b] * x_t + b[b] * x0 (x0_prev == NULL: no history; x0_prev is never read) or
+ * x_next = (a[b] * x_t + b[b] * x0) + c[b] * x0_prev, float32, this association, every operation rounded on its own.  rows: host struct of
+ * per-sample [B] device arrays.  No noise term: the sampler is deterministic.  x_next may alias x_t. */
+int afm_dpm_step(const float* x0, const float* x_t, const float* x0_prev, float* x_next, const afm_dpm_rows* rows,
+                 int32_t B, int64_t per_sample, void* stream);
+
 /* afm_clamp: x <- min(max(x, lo), hi) in place (NaN propagates, as torch.clamp): `process_xstart` with clip_denoised=True on the
  * step-by-step path (gaussian_diffusion.py:289-294).  ABI v6. */
 int afm_clamp(float* x, int64_t n, float lo, float hi, void* stream);
@@ -794,6 +811,23 @@ int afm_cmdm_cfg2_loop_range(const afm_cmdm_weights* w, float* x, const float* c
                              const afm_cfg2_args* cfg, const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step,
                              uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                              int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream);
+
+/* The DPM-Solver++(2M) native loop, every form behind one entry: `rows` [T] like the DDIM rows, cfg (one scale) or cfg2 (one scale per
+ * condition) or neither (both: AFM_E_BADARG), known / mask [B][L][motion_dim] optional (both or neither).  No noise, no seed.  The
+ * launches are those of the eta = 0 DDIM loop of the same form (AFM_CMDM_PAIR_LAUNCH / AFM_CMDM_FUSED_LN as there; branch streams for one
+ * scale only), the update launch applying the afm_dpm_step expression to the final pred_xstart - after the guidance combine, the
+ * imputation select and the clamp - and keeping that value as the next step's x0_prev in a history buffer [count][L * motion_dim] per
+ * sub-batch, carved from the workspace for this loop alone.  first_step == 0: executed step 0 has no history (two-term form).
+ * first_step > 0: the history is what the previous range call left in the SAME workspace (same B, L, n_streams, guidance) - chained
+ * range calls are bit-identical to one call.  workspace >= afm_cmdm_dpm_loop_workspace_bytes; sched_scratch >=
+ * afm_ddim_sched_scratch_bytes(n_steps, B). */
+int64_t afm_cmdm_dpm_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                          const afm_cfg2_args* cfg2);
+int afm_cmdm_dpm_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                            const int64_t* d_timestep_map, const afm_dpm_rows* rows, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2,
+                            const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step, int32_t B, int32_t L,
+                            void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward

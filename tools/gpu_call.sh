@@ -11,6 +11,8 @@
 #   cdm_check                CDM parity tests + tools/cdm_ab.py + rocprofv3 --stats of the CDM loop (H3D and HUMANISE variants)
 #   points                   configs[3] kernels: timings + PMC passes (FETCH / WRITE / SQ) -> points_summary.md
 #   pk_repro                 the packed-f32 reproducer with its controls
+#   samplers [reps]          tools/bench_samplers.py (DDIM "ddim50" against DPM-Solver++(2M) "logsnr20" / "logsnr10", B = 1 and 32), with the parent
+#                            commit's DDIM loop from tools/ab_libs/libafm_parent.so in the same call when that build is there
 #   validate <rNN>           end-of-round validation: full -m gpu suite, smoke, both bench commands, rocprofv3 stats + PMC passes (CMDM, CDM, points), training benches
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
@@ -136,6 +138,11 @@ points)
 pk_repro)
   ( timeout 600 bash tools/probes/run_pk_repro.sh ) > $O/pk_repro.txt 2>&1
   tail -60 $O/pk_repro.txt
+  ;;
+samplers)
+  PL=tools/ab_libs/libafm_parent.so
+  ( timeout 500 python tools/bench_samplers.py --reps ${1:-5} $( [ -f $PL ] && echo --parent-lib $PL ) ) > $O/bench_samplers.json 2> $O/bench_samplers.err
+  tail -1 $O/bench_samplers.json | cut -c1-6000; tail -3 $O/bench_samplers.err
   ;;
 validate)
   R=${1:-r05}
