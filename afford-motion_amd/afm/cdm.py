@@ -334,6 +334,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         if self.arch != "Perceiver":
             self.afm_native_loop = None         # other archs sample step by step
             self.afm_native_impute_loop = None
+            self.afm_native_dpm_loop = None
         self.sub_batches = 1                    # per-call sub-batches of forward(): >1 costs more host time per step than it hides (measured)
         self._streams = []
         self.no_fold = False            # measurement: the layer-by-layer sampling form (what training-mode forward also runs)
@@ -648,8 +649,23 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         return self._native_loop(diffusion, x, model_kwargs, impute, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=progress,
                                  snapshots=snapshots, clip_denoised=clip_denoised, ddim_eta=ddim_eta)
 
-    def _native_loop(self, diffusion, x, model_kwargs, impute, *, step_noise, seed, sample_index0, progress, snapshots, clip_denoised, ddim_eta):
-        """the body of both native loops: with ``impute`` the entry is afm_cdm_impute_loop_range and known / mask ride along"""
+    def afm_native_dpm_loop(self, diffusion, x, model_kwargs, impute=None, *, seed=0, sample_index0=0, progress=False, snapshots=None,
+                            clip_denoised=False, dpm_order: int = 2):
+        """dpm_solver_sample_loop on the device (afm_cdm_dpm_loop_range): DPM-Solver++(2M), or the first-order solver with ``dpm_order`` 1 -
+        the same loop on the order-1 rows.  x holds x_T on entry, returns the sample; ``impute`` (an afm.diffusion.Impute, [B, N, contact_dim],
+        or None) is applied as in afm_native_impute_loop.  Row-less form: update, select and the history of the previous step's final
+        pred_xstart ride in dec_point, the launches of the eta = 0 DDIM loop; the other two forms add one update launch per step.
+        Deterministic: ``seed`` / ``sample_index0`` keyed x_T only and are not used here.  ``progress`` / ``snapshots`` slice the chain as
+        in afm_native_loop - the history crosses the range calls in the loop's workspace - with bit-identical results."""
+        if impute is not None:
+            impute.check(x)
+        return self._native_loop(diffusion, x, model_kwargs, impute, step_noise=None, seed=seed, sample_index0=sample_index0, progress=progress,
+                                 snapshots=snapshots, clip_denoised=clip_denoised, ddim_eta=None, dpm_order=int(dpm_order))
+
+    def _native_loop(self, diffusion, x, model_kwargs, impute, *, step_noise, seed, sample_index0, progress, snapshots, clip_denoised, ddim_eta,
+                     dpm_order=None):
+        """the body of the native loops: with ``impute`` the entry is afm_cdm_impute_loop_range and known / mask ride along; with
+        ``dpm_order`` it is afm_cdm_dpm_loop_range, with or without them"""
         if self.arch != "Perceiver":
             raise NotImplementedError("the native loop covers the Perceiver arch")
         lib = ffi.load()
@@ -663,17 +679,21 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             tq0, tu, tcu = self._text_latent(w, model_kwargs, dev)
             tab = diffusion.tables(dev)
             n = diffusion.num_timesteps
-            sched = ffi.sched_scratch(self, n, B, dev, ddim=ddim_eta is not None)
+            sched = ffi.sched_scratch(self, n, B, dev, ddim=ddim_eta is not None or dpm_order is not None)
             ddim = None if ddim_eta is None else diffusion.ddim_tables(dev, ddim_eta)
+            dpm = None if dpm_order is None else diffusion.dpm_tables(dev, dpm_order)
             nsub = int(self.loop_sub_batches) or 1
             nsub = max(1, min(nsub, B))
             need = 2 * nsub if nsub > 1 else (1 if self.overlap_streams else 0)
             streams = self._loop_streams(need, dev)
             handles = (C.c_void_p * max(need, 1))(*[s_.cuda_stream for s_ in streams]) if need else None
-            nbytes = lib.afm_cdm_loop_workspace_bytes(C.byref(w), B, N, nsub)
+            sizer = "afm_cdm_loop_workspace_bytes" if dpm is None else "afm_cdm_dpm_loop_workspace_bytes"
+            nbytes = getattr(lib, sizer)(C.byref(w), B, N, nsub)
             if nbytes < 0:
-                ffi.check(int(nbytes), "afm_cdm_loop_workspace_bytes")
-            key = ("loop", B, N, nsub, str(dev))
+                ffi.check(int(nbytes), sizer)
+            # (the 2M loop: a buffer of its own per sampling form - the history of step j0 - 1 lives in it between the slices of a chain, at an
+            # offset that depends on the form)
+            key = ("loop", B, N, nsub, str(dev)) if dpm is None else ("dpm_loop", bool(self.no_gen), bool(self.no_fold), B, N, nsub, str(dev))
             if key not in self._ws or self._ws[key].numel() < nbytes:        # (the row-less form's workspace is smaller than the other forms')
                 self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             ws = self._ws[key]
@@ -686,6 +706,11 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
+                if dpm is not None:         # one entry with and without an Impute; no noise, no seed
+                    return ffi.check(lib.afm_cdm_dpm_loop_range(
+                        C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(), tab.timestep_map[lo:].data_ptr(),
+                        C.byref(dpm.rows(lo)), None if impute is None else impute.known.data_ptr(), None if impute is None else impute.mask.data_ptr(),
+                        j1 - j0, j0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream), "afm_cdm_dpm_loop_range")
                 rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
                     (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
                 if impute is not None:      # one entry for both updates: both kinds of rows, then known and mask
@@ -696,7 +721,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                     entry)
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
-            self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu, ddim, impute)
+            self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu, ddim, dpm, impute)
         return x
 
     # ------------------------------------------------------------------ 'MLP' arch (per-operator composition, inference and training)

@@ -479,9 +479,9 @@ class GaussianDiffusion:
                                sample_index0: int = 0, snapshots: Optional[dict] = None):
         """DPM-Solver++(2M) sampling (``order`` 1: first order, DDIM eta = 0) on this - usually respaced, e.g. "logsnr20" - process: one
         denoiser evaluation per step, deterministic.  ``seed`` / ``sample_index0`` key x_T only; ``step_noise`` is refused.  A denoiser
-        whose ``afm_native_loop`` takes ``dpm_order`` (CMDM `trans_enc`, GuidedCMDM; an `Impute` as ``denoised_fn`` included) runs the whole
-        chain natively under p_sample_loop's conditions; any other (the CDM) samples step by step, an `Impute` applied as the plain
-        ``denoised_fn`` it also is."""
+        whose ``afm_native_loop`` takes ``dpm_order`` (CMDM `trans_enc`, GuidedCMDM) or that has an ``afm_native_dpm_loop`` (the CDM
+        `Perceiver`: afm_cdm_dpm_loop_range), an `Impute` as ``denoised_fn`` included, runs the whole chain natively under p_sample_loop's
+        conditions; any other samples step by step, an `Impute` applied as the plain ``denoised_fn`` it also is."""
         if step_noise is not None:
             raise ValueError("DPM-Solver++ is deterministic: it takes no step_noise")
         if cond_fn is not None:
@@ -495,14 +495,17 @@ class GaussianDiffusion:
         """p_sample_loop (ddim_eta None) / ddim_sample_loop / dpm_solver_sample_loop (dpm_order not None): the native loop when the
         denoiser has one and nothing needs the host between steps, else the progressive generator.  A ``denoised_fn`` that is an `Impute`
         stays native where the denoiser's loop takes ``impute=`` or the denoiser has an ``afm_native_impute_loop`` (the CDM); any other
-        callable samples step by step.  DPM-Solver++ is native only where ``afm_native_loop`` names ``dpm_order`` (never the CDM's loops)."""
+        callable samples step by step.  DPM-Solver++ is native where ``afm_native_loop`` names ``dpm_order`` (the CMDM) or, when it does
+        not, where the denoiser has an ``afm_native_dpm_loop`` (the CDM: a third method with the Impute, or None, as its fourth argument)
+        - found by name, under the same conditions; a denoiser with neither samples step by step."""
         native = getattr(model, "afm_native_loop", None)
-        if dpm_order is not None and native is not None and not _takes(native, "dpm_order"):
-            native = None
+        third = dpm_order is not None and native is not None and not _takes(native, "dpm_order")
+        if third:                                  # the CDM's 2M loop; None (a non-Perceiver CDM, any other denoiser): step by step
+            native = getattr(model, "afm_native_dpm_loop", None)
         switches = any(k in (model_kwargs or {}) for k in ("c_text_mask", "c_text_erase", "c_pc_mask", "c_pc_erase"))
-        native_impute = getattr(model, "afm_native_impute_loop", None) if native is not None else None
+        native_impute = getattr(model, "afm_native_impute_loop", None) if native is not None and not third else None
         impute = denoised_fn if isinstance(denoised_fn, Impute) and native is not None and \
-            (_takes_impute(native) or native_impute is not None) else None
+            (third or _takes_impute(native) or native_impute is not None) else None
         if native is not None and (denoised_fn is None or impute is not None) and cond_fn is None and not self.rescale_timesteps and not switches:
             if device is None:
                 device = next(model.parameters()).device
@@ -514,7 +517,7 @@ class GaussianDiffusion:
             extra = {} if snapshots is None else {"snapshots": snapshots}
             if impute is not None:
                 impute.check(x)
-                if _takes_impute(native):
+                if not third and _takes_impute(native):
                     extra["impute"] = impute
             if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused update
                 extra["clip_denoised"] = True
@@ -523,6 +526,8 @@ class GaussianDiffusion:
             if dpm_order is not None:
                 extra["dpm_order"] = dpm_order
             args = (self, x, model_kwargs or {})
+            if third:                              # the Impute, or None, as the fourth argument; the sampler has no step noise
+                return native(*args, impute, seed=seed, sample_index0=sample_index0, progress=bool(progress), **extra)
             if impute is not None and "impute" not in extra:      # the CDM: a second method with the Impute as its fourth argument
                 native, args = native_impute, args + (impute,)
             return native(*args, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=bool(progress), **extra)

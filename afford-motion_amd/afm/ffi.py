@@ -231,6 +231,9 @@ EXPORTS = {
     "afm_cdm_impute_loop_range": (C.c_int, [C.POINTER(CdmWeights), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
                                             c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                             C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_cdm_dpm_loop_workspace_bytes": (i64, [C.POINTER(CdmWeights), i32, i32, i32]),
+    "afm_cdm_dpm_loop_range": (C.c_int, [C.POINTER(CdmWeights), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(DpmRows), c_f32p,
+                                         C.c_void_p, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, i32, C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_cfg2_combine": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i64, C.c_void_p]),
     "afm_cfg2_step": (C.c_int, [C.POINTER(Cfg2StepArgs), C.c_void_p]),
     "afm_cmdm_cfg2_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32]),

@@ -30,8 +30,8 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     keyed by (seed, sample_index0 + b), stage 2 uses seed + 1.  ``sampler`` = "ddpm" (p_sample_loop) or "ddim" (ddim_sample_loop with
     ``eta``) for both stages; DDIM runs the spaced process of each diffusion (e.g. timestep_respacing="ddim50").  ``sampler`` = "dpm++":
     DPM-Solver++(2M) (dpm_solver_sample_loop, deterministic; ``eta`` must be 0, explicit step noise is refused) on the spaced process of each
-    diffusion (e.g. timestep_respacing="logsnr20"): the motion stage runs in the CMDM's native loop, the contact stage step by step
-    (CDM.forward + afm_dpm_step per step; the CDM has no native form of this sampler).
+    diffusion (e.g. timestep_respacing="logsnr20"): both stages run in their native loops (the motion stage in
+    afm_cmdm_dpm_loop_range, the contact stage in afm_cdm_dpm_loop_range; a non-Perceiver CDM samples step by step).
     ``guidance_scale`` (a float or a [B] tensor; None = unguided): classifier-free guidance of the MOTION stage, dropping the conditions named
     in ``guidance_drop`` (afm.cmdm.GuidedCMDM; the CDM of the first stage never reads the condition switches).  A mapping
     ``{"pc": s_pc, "text": s_text}`` (insertion order = first, second) gives every condition a scale of its own; ``guidance_drop`` must

@@ -1,5 +1,6 @@
-// Body of dec_point_kernel / dec_point_imputing_kernel (perceiver_points.hip), included into each with the kernel's arguments and
-// IMPUTE, known, mask, x0_out in scope (template parameters NKS, NPROD, DDIM).
+// Body of dec_point_kernel / dec_point_imputing_kernel / dec_point_dpm_kernel (perceiver_points.hip), included into each with the kernel's
+// arguments and IMPUTE, known, mask, x0_out, DPM, x0_prev, x0_keep in scope (template parameters NKS, NPROD, DDIM).  IMPUTE and DPM are
+// compile-time constants in the first two kernels; in the 2M kernel IMPUTE is the uniform run-time `mask != NULL`.
     using RL = RowLess<NKS>;
     constexpr int K = RL::K, NT = RL::NT, LDQ = RL::LDQ, XS = RL::XS, NSTEP = RL::NSTEP, NW = RL::NW, NTH = 64 * NW, QEW = 16 * NT;
     extern __shared__ __attribute__((aligned(16))) float dp_sm[];
@@ -75,17 +76,22 @@
         // a tile's work ahead of its use, and without a branch: loaded at the site, a `known` under a test of its mask byte stood behind that
         // byte's round trip at the end of every tile (4.7 % of the kernel).  A lane without an output element reads element 0 and drops it;
         // `known` is read everywhere and selected, never blended.  (x_t here is the lane's own element, which only this lane writes, below.)
+        // DPM (the 2M kernel): x_t and the previous step's final x0 of the lane's own elements are requested here as well - per element, a
+        // sample's base b N cd is not 16-byte aligned in general - and the mask bytes / known values only where there is a mask.
         unsigned km[4] = {0u, 0u, 0u, 0u};
-        float kn[4] = {0.f, 0.f, 0.f, 0.f}, xo[4] = {0.f, 0.f, 0.f, 0.f}, zo[4] = {0.f, 0.f, 0.f, 0.f};
-        if (IMPUTE) {
+        float kn[4] = {0.f, 0.f, 0.f, 0.f}, xo[4] = {0.f, 0.f, 0.f, 0.f}, zo[4] = {0.f, 0.f, 0.f, 0.f}, hp[4] = {0.f, 0.f, 0.f, 0.f};
+        if (IMPUTE || DPM) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = 4 * g + r;
                 const int64_t i = (pvalid && j < cd) ? pt * cd + j : 0;
-                km[r] = mask[i];
-                kn[r] = known[i];
+                if (IMPUTE) {
+                    km[r] = mask[i];
+                    kn[r] = known[i];
+                }
                 xo[r] = xt[i];
-                if (!(clip & AFM_UPD_NO_NOISE)) zo[r] = noise[i];
+                if (!DPM && !(clip & AFM_UPD_NO_NOISE)) zo[r] = noise[i];
+                if (DPM && x0_prev) hp[r] = x0_prev[i];
             }
         }
         // ---- LayerNorm statistics of the (never generated) query row: var_q = x Qd x^T; scores = rstd_q (x . EG) + const; softmax over the
@@ -207,7 +213,11 @@
                     if (IMPUTE) v = km[r] ? kn[r] : v;                                           // the select of afm_impute
                     if (clip & AFM_UPD_CLIP) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);      // clip_denoised
                     if (x0_out) x0_out[i] = v;
-                    if (DDIM && IMPUTE) {
+                    if (DPM) {                       // v is the final x0 of the step: the update, and the next step's history (this lane read hp[r] above)
+                        const float4 rr = reinterpret_cast<const float4*>(c1)[b];
+                        x_next[i] = x0_prev ? dpm_update(v, xo[r], rr, hp[r]) : dpm_update(v, xo[r], rr);
+                        x0_keep[i] = v;
+                    } else if (DDIM && IMPUTE) {
                         const float4 rr = reinterpret_cast<const float4*>(c1)[b];
                         x_next[i] = (clip & AFM_UPD_NO_NOISE) ? ddim_update(v, xo[r], rr) : ddim_update(v, xo[r], rr, sigma[b], zo[r]);
                     } else if (DDIM) {

@@ -204,6 +204,9 @@ int cdm_forward_folded(const afm_cdm_weights& w, const float* feat, const float*
     // the imputing loops: known / mask of the sub-batch ride in the loop's update description (row-less: fused into dec_point; FOLD: below)
     const float* known = loop_upd ? loop_upd->known : nullptr;
     const uint8_t* mask = loop_upd ? loop_upd->mask : nullptr;
+    // the 2M loop: the sub-batch's history rides there too (row-less: fused into dec_point; FOLD: the update launch below)
+    const float* x0_prev = loop_upd ? loop_upd->x0_prev : nullptr;
+    float* x0_keep = loop_upd ? loop_upd->x0_keep : nullptr;
     if (mode == 1 && !prepared) AFM_TRY(cdm_prepare_invariants(w, feat, B, N, ws, s));
     if (mode == 3) AFM_TRY(launch_enc_point(w, text_u, text_cu, t, B, N, ws, x_t, feat, s));
     else AFM_TRY(launch_enc_reduce(w, ws.enc_kv, text_u, text_cu, t, B, N, ws, x_t, mode, s));
@@ -215,10 +218,10 @@ int cdm_forward_folded(const afm_cdm_weights& w, const float* feat, const float*
         AFM_TRY(launch_dec_tables(w, B, ws, cs->chain));
         (void)hipEventRecord(cs->joined, cs->chain);
         (void)hipStreamWaitEvent(s, cs->joined, 0);
-        return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false, known, mask);
+        return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false, known, mask, x0_prev, x0_keep);
     }
     AFM_TRY(cdm_latent_chain(w, text_q0, t, ws, B, s, mode == 3));
-    if (mode == 3) return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s, true, known, mask);
+    if (mode == 3) return launch_dec_point(w, B, N, ws, x_t, feat, x0_out, ddpm, s, true, known, mask, x0_prev, x0_keep);
     AFM_TRY(launch_dec_attend(w, B, N, ws, x_t, mode, s));
     afm_linear_args a = {};                 // GELU(linear1 z) . w2 per 64-column group; the hidden activations are never stored
     a.A = ws.z; a.lda = dkv; a.W = w.dec_mlp.fc1.w; a.ldw = dkv; a.M = M; a.N = dkv; a.K = dkv; a.bias = w.dec_mlp.fc1.b; a.act = AFM_ACT_GELU;
@@ -226,7 +229,8 @@ int cdm_forward_folded(const afm_cdm_weights& w, const float* feat, const float*
     a.arith = w.gemm_arith; a.arith_min_n = w.gemm_arith_min_n;
     a.tune = ((w.flags >> AFM_CDM_TILE_SHIFT) & 0xF) << AFM_TUNE_TILE_SHIFT;
     AFM_TRY(afm_linear(&a, s));
-    if (mask) {       // imputing loop, FOLD: pred_xstart to ws.h1 (not used by this form) with the plain output, then the one update launch that selects
+    if (mask || x0_keep) {       // imputing loop and 2M loop, FOLD: pred_xstart to ws.h1 (not used by this form) with the plain output, then the one update
+                                 // launch that selects (and, 2M, reads and writes the history)
         AFM_TRY(launch_cdm_output(w, B, N, ws, x_t, ws.h1, nullptr, s));
         Update u = *loop_upd;
         u.x0 = ws.h1;
@@ -254,7 +258,7 @@ static int cdm_forward_impl(const afm_cdm_weights* wp, const float* feat, const 
     const CdmWs ws = carve(w, B, N, workspace, !rowless_ws);
     if (ws.bytes > workspace_bytes) return AFM_E_WORKSPACE;
     const int M = B * N, dkv = w.dkv;
-    if (loop_upd && loop_upd->mask && !ddpm) return AFM_E_BADARG;
+    if (loop_upd && (loop_upd->mask || loop_upd->x0_keep) && !ddpm) return AFM_E_BADARG;
     if (cdm_folded(w) && x_t) return cdm_forward_folded(w, feat, x_t, t, text_q0, text_u, text_cu, x0_out, ddpm, B, N, ws, prepared, s, cs, loop_upd);
 
     afm_linear_args a = {};
@@ -384,14 +388,21 @@ struct SubBatch : SubRange {
     // already enqueued on its previous record)
     CdmChainSide chain;
     hipEvent_t enc_done, tables_done; // AFM_CDM_PIPELINE: enc_point -> [enc_done] -> chain + tables -> [tables_done] -> dec_point
+    float* hist;                      // 2M loop only: the previous step's final x0 [count][N * contact_dim], behind the noise
 };
 
 // carves the workspace of a sub-batch whose range is set at `base` (NULL: sizes only); -> its bytes
-int64_t carve_sub(const afm_cdm_weights& w, int N, char* base, SubBatch* sb) {
+int64_t carve_sub(const afm_cdm_weights& w, int N, char* base, SubBatch* sb, bool hist = false) {
     sb->base = base;
     sb->ws = carve(w, sb->count, N, base, cdm_mode(w) != 3);
     sb->noise = base ? (float*)(base + sb->ws.bytes) : nullptr;
-    return sb->ws.bytes + align256((int64_t)NOISE_STEPS * sb->count * N * w.contact_dim * 4);
+    int64_t off = sb->ws.bytes + align256((int64_t)NOISE_STEPS * sb->count * N * w.contact_dim * 4);
+    sb->hist = nullptr;
+    if (hist) {                       // (carved for the 2M loop alone: the other loops' sizes stay as they are)
+        sb->hist = base ? (float*)(base + off) : nullptr;
+        off += align256((int64_t)sb->count * N * w.contact_dim * 4);
+    }
+    return off;
 }
 
 // what a loop call fixes before its first launch
@@ -407,6 +418,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     const LoopArgs& a = c.a;
     AFM_TRY(validate(c.w, a.B, c.N));
     if (!c.x || !c.feat || !c.text_q0 || !c.text_u || !c.text_cu || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
+    if (a.dpm && (!a.ddim || a.noise_term() || a.step_noise || a.first_step < 0)) return AFM_E_BADARG;
     p->nsub = 0;
     if (a.B == 0) return 0;
     p->w = *c.w;
@@ -417,7 +429,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         SubBatch& sb = p->sb[s];
         sb = {};
         sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(p->w, c.N, (char*)a.workspace + off, &sb);
+        off += carve_sub(p->w, c.N, (char*)a.workspace + off, &sb, a.dpm);
         if (p->nsub > 1) { sb.stream = (hipStream_t)a.streams[2 * s]; sb.side = (hipStream_t)a.streams[2 * s + 1]; }
         else { sb.stream = (hipStream_t)a.stream; sb.side = a.streams ? (hipStream_t)a.streams[0] : nullptr; }
     }
@@ -442,6 +454,10 @@ inline float* sub_x(const Loop& l, const SubBatch& sb) { return l.c.x + (int64_t
 inline float* sub_feat(const Loop& l, const SubBatch& sb) { return l.c.feat + (int64_t)sb.start * l.c.N * l.p.w.feat_dim; }
 inline const float* sub_known(const Loop& l, const SubBatch& sb) { return l.c.mask ? l.c.known + (int64_t)sb.start * l.p.per : nullptr; }
 inline const uint8_t* sub_mask(const Loop& l, const SubBatch& sb) { return l.c.mask ? l.c.mask + (int64_t)sb.start * l.p.per : nullptr; }
+// 2M loop: the history step j writes (NULL in every other loop), and the one it reads - what step j - 1 of this call, or the last step of
+// the previous range call on the same workspace, left there; the first executed step of a chain (first_step + j == 0) has none
+inline float* hist_keep(const Loop& l, const SubBatch& sb) { return l.c.a.dpm ? sb.hist : nullptr; }
+inline const float* hist_prev(const Loop& l, const SubBatch& sb, int j) { return l.c.a.dpm && l.c.a.first_step + j > 0 ? sb.hist : nullptr; }
 
 // the events of a loop call, all owned by `ev`: the fork of the sub-batch streams, the chain-side pairs, the pipeline's pairs
 int loop_events(Loop& l, Events& ev) {
@@ -508,7 +524,8 @@ int pipe_dec(const Loop& l, const SubBatch& sb, int j) {
     const float* nz;
     AFM_TRY(step_noise(l.c.a, l.p.per, sb, sb.noise, j, sub_x(l, sb), nullptr, &nz));
     const afm_ddpm_args dd = ddpm_args(l.c.a, l.sched.at(j, sb.start), nz, sub_x(l, sb), sb, j);
-    return launch_dec_point(l.p.w, sb.count, l.c.N, sb.ws, sub_x(l, sb), sub_feat(l, sb), nullptr, &dd, H, false, sub_known(l, sb), sub_mask(l, sb));
+    return launch_dec_point(l.p.w, sb.count, l.c.N, sb.ws, sub_x(l, sb), sub_feat(l, sb), nullptr, &dd, H, false, sub_known(l, sb), sub_mask(l, sb),
+                            hist_prev(l, sb, j), hist_keep(l, sb));
 }
 
 int pipelined_steps(const Loop& l) {
@@ -535,6 +552,7 @@ int plain_step(const Loop& l, const SubBatch& sb, int j) {
     const afm_ddpm_args dd = ddpm_args(c.a, r, nz, xs, sb, j);
     Update upd = loop_update(c.a, r, nullptr, xs, nz, l.p.per, w.flags & AFM_CDM_CLIP_X0);
     upd.known = sub_known(l, sb); upd.mask = sub_mask(l, sb);
+    upd.x0_prev = hist_prev(l, sb, j); upd.x0_keep = hist_keep(l, sb);
     return cdm_forward_impl(&w, fs, xs, r.t, c.text_q0 + (int64_t)sb.start * w.dq, c.text_u + (int64_t)sb.start * w.enc_heads * w.dkv,
                             c.text_cu + (int64_t)sb.start * w.enc_heads, nullptr, &dd, sb.count, c.N, sb.base, sb.ws.bytes, sb.side, sb.stream,
                             l.p.folded, l.p.rowless, l.p.chain_side ? &sb.chain : nullptr, &upd);
@@ -563,16 +581,20 @@ int cdm_sample_loop_impl(const LoopCall& c) {
 
 }  // namespace
 
-extern "C" int64_t afm_cdm_loop_workspace_bytes(const afm_cdm_weights* w, int32_t B, int32_t N, int32_t n_sub) {
+static int64_t cdm_loop_workspace_bytes(const afm_cdm_weights* w, int32_t B, int32_t N, int32_t n_sub, bool hist) {
     if (validate(w, B, N) != 0 || n_sub < 0) return AFM_E_BADARG;
     const int nsub = sub_count(B, n_sub, MAX_SUB);
     int64_t total = 0;
     for (int s = 0; s < nsub; ++s) {
         SubBatch sb = {};
         sub_range(B, nsub, s, &sb.start, &sb.count);
-        total += carve_sub(*w, N, nullptr, &sb);
+        total += carve_sub(*w, N, nullptr, &sb, hist);
     }
     return total;
+}
+
+extern "C" int64_t afm_cdm_loop_workspace_bytes(const afm_cdm_weights* w, int32_t B, int32_t N, int32_t n_sub) {
+    return cdm_loop_workspace_bytes(w, B, N, n_sub, false);
 }
 
 extern "C" int afm_cdm_sample_loop(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
@@ -615,4 +637,24 @@ extern "C" int afm_cdm_impute_loop_range(const afm_cdm_weights* w, float* x, flo
     if (rows) d_c1 = d_c2 = d_sigma = nullptr;
     return cdm_sample_loop_impl({w, x, feat, text_q0, text_u, text_cu, N, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
                                  sched_scratch, workspace, workspace_bytes, n_sub, streams, stream}, known, mask});
+}
+
+// DPM-Solver++(2M): the eta = 0 DDIM loop with dpm_update in its place and one history buffer per sub-batch.  Row-less form: the update and
+// the history ride in dec_point (dec_point_dpm_kernel), with or without known / mask - the launches of the DDIM loop.  Folded-rows and
+// layer-by-layer forms: pred_xstart stored where their imputing loops store it, then one update launch per sub-batch and step.  The rows
+// travel through the DDIM schedule layout as {a, b, c, unused}.
+extern "C" int64_t afm_cdm_dpm_loop_workspace_bytes(const afm_cdm_weights* w, int32_t B, int32_t N, int32_t n_sub) {
+    return cdm_loop_workspace_bytes(w, B, N, n_sub, true);
+}
+
+extern "C" int afm_cdm_dpm_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
+                                      const float* text_cu, const int64_t* d_timestep_map, const afm_dpm_rows* rows, const float* known,
+                                      const uint8_t* mask, int32_t n_steps, int32_t first_step, int32_t B, int32_t N, void* sched_scratch,
+                                      void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream) {
+    if (first_step < 0 || !rows || !rows->a || !rows->b || !rows->c || !known != !mask) return AFM_E_BADARG;
+    const afm_ddim_rows as_ddim = {rows->a, rows->b, rows->c, rows->c, nullptr};          // (d: any valid row, never used by dpm_update)
+    LoopCall c = {w, x, feat, text_q0, text_u, text_cu, N, {nullptr, d_timestep_map, nullptr, nullptr, nullptr, &as_ddim, n_steps, first_step, 0, 0, B,
+                  sched_scratch, workspace, workspace_bytes, n_sub, streams, stream}, known, mask};
+    c.a.dpm = true;
+    return cdm_sample_loop_impl(c);
 }

@@ -68,8 +68,11 @@ int launch_enc_point(const afm_cdm_weights& w, const float* text_u, const float*
                      const float* x_t, const float* feat, hipStream_t s);
 int launch_lat_head(const afm_cdm_weights& w, const float* text_q0, const int64_t* t, const CdmWs& ws, int B, hipStream_t s);
 // known / mask [B][N][contact_dim] (both or neither; the imputing loops): the select fused in front of the in-place update, ddpm->x_next required
+// x0_keep [B][N][contact_dim] (the 2M loop): the update is dpm_update, the step's final x0 is stored there; x0_prev: the previous step's (NULL:
+// the first executed step of a chain; may be x0_keep)
 int launch_dec_point(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, const float* x_t, const float* feat, float* x0_out,
-                     const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables = true, const float* known = nullptr, const uint8_t* mask = nullptr);
+                     const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables = true, const float* known = nullptr, const uint8_t* mask = nullptr,
+                     const float* x0_prev = nullptr, float* x0_keep = nullptr);
 int launch_dec_tables(const afm_cdm_weights& w, int B, const CdmWs& ws, hipStream_t s);      // lat_dectables_kernel alone (chain stream)
 // perceiver_chain.hip - enc_reduce / enc_point partials -> the decoder's view of the two latents (dec_lat records / lat_kv for the row-less form)
 int cdm_latent_chain(const afm_cdm_weights& w, const float* text_q0, const int64_t* t, const CdmWs& ws, int B, hipStream_t s, bool rowless);

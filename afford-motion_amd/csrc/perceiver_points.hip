@@ -357,9 +357,10 @@ void dec_point_kernel(const float* __restrict__ twp, const float* __restrict__ q
                       const float* __restrict__ cvec, const float* __restrict__ w2f, const float* __restrict__ gen_qe, const float* __restrict__ c0, int N, int cd,
                       const float* xt, const float* __restrict__ feat, int fd, float* __restrict__ x0_out, const float* __restrict__ noise, float* x_next,
                       const float* __restrict__ c1, const float* __restrict__ c2, const float* __restrict__ sigma, int clip) {
-    constexpr bool IMPUTE = false;
-    constexpr const float* known = nullptr;
+    constexpr bool IMPUTE = false, DPM = false;
+    constexpr const float *known = nullptr, *x0_prev = nullptr;
     constexpr const uint8_t* mask = nullptr;
+    constexpr float* x0_keep = nullptr;
 #include "dec_point_body.inc"
 }
 
@@ -371,14 +372,33 @@ void dec_point_imputing_kernel(const float* __restrict__ twp, const float* __res
                              const float* xt, const float* __restrict__ feat, int fd, const float* __restrict__ noise, float* x_next,
                              const float* __restrict__ c1, const float* __restrict__ c2, const float* __restrict__ sigma, int clip,
                              const float* __restrict__ known, const uint8_t* __restrict__ mask) {
-    constexpr bool IMPUTE = true;
+    constexpr bool IMPUTE = true, DPM = false;
+    constexpr float *x0_out = nullptr, *x0_keep = nullptr;
+    constexpr const float* x0_prev = nullptr;
+#include "dec_point_body.inc"
+}
+
+// The DPM-Solver++(2M) loop's decoder: always the in-place update, dpm_update (common.h) on the final x0 - after the select and the clamp -
+// with c1 -> the {a, b, c, unused} records.  x0_prev [B][N][cd]: the previous step's final x0 (NULL: the first executed step of a chain, the
+// two-term form); x0_keep: this step's, written to the element the same lane read (the two may be one buffer, like xt and x_next).  One
+// kernel with and without imputation - `mask` is uniform over the launch - so 4 instantiations instead of 8: with the branch the kernel
+// keeps its siblings' occupancy and uses no scratch (NKS = 3: 190 VGPRs, two workgroups per CU; profiles/cdm_dpm_resources.md).
+template <int NKS, int NPROD>
+__global__ __launch_bounds__(64 * RowLess<NKS>::NW, NKS <= 4 ? 2 : 1)
+void dec_point_dpm_kernel(const float* __restrict__ twp, const float* __restrict__ qtab, const float* __restrict__ qdd, const float* __restrict__ twx,
+                          const float* __restrict__ cvec, const float* __restrict__ w2f, const float* __restrict__ gen_qe, const float* __restrict__ c0, int N, int cd,
+                          const float* xt, const float* __restrict__ feat, int fd, float* x_next, const float* __restrict__ c1, int clip,
+                          const float* __restrict__ known, const uint8_t* __restrict__ mask, const float* x0_prev, float* x0_keep) {
+    constexpr bool DDIM = true, DPM = true;
+    const bool IMPUTE = mask != nullptr;
     constexpr float* x0_out = nullptr;
+    constexpr const float *noise = nullptr, *c2 = nullptr, *sigma = nullptr;
 #include "dec_point_body.inc"
 }
 
 template <int NKS>
 int launch_dec_point_t(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, const float* x_t, const float* feat, float* x0_out,
-                       const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask);
+                       const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask, const float* x0_prev, float* x0_keep);
 template <int NKS>
 int launch_dec_tables_t(const afm_cdm_weights& w, int B, const CdmWs& ws, hipStream_t s) {
     hipLaunchKernelGGL(lat_dectables_kernel<NKS>, dim3(B, 4), dim3(1024), 0, s, ws.lat_kv, w.dec_dwq, w.dec_wqb, w.dec_wco, w.dec_wow, w.dec_wog, w.dec_xwo,
@@ -417,11 +437,11 @@ int launch_lat_head(const afm_cdm_weights& w, const float* text_q0, const int64_
 
 // the fused decoder (mode 3): the per-sample tables of the step (one launch), then one kernel over the points
 int launch_dec_point(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, const float* x_t, const float* feat, float* x0_out,
-                     const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask) {
+                     const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask, const float* x0_prev, float* x0_keep) {
     if (with_tables) AFM_TRY(launch_dec_tables(w, B, ws, s));        // (its own profile bracket: the tables belong to the chain's time)
     AfmProf prof(AFM_PROF_CDM_DEC, 0.0, s);
-    return rowless_nks(w.feat_dim) == 3 ? launch_dec_point_t<3>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false, known, mask)
-                                        : launch_dec_point_t<11>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false, known, mask);
+    return rowless_nks(w.feat_dim) == 3 ? launch_dec_point_t<3>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false, known, mask, x0_prev, x0_keep)
+                                        : launch_dec_point_t<11>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, false, known, mask, x0_prev, x0_keep);
 }
 
 int launch_dec_tables(const afm_cdm_weights& w, int B, const CdmWs& ws, hipStream_t s) {
@@ -435,14 +455,15 @@ namespace {
 
 template <int NKS, int NPROD>
 int launch_dec_point_p(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, const float* x_t, const float* feat, float* x0_out,
-                       const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask) {
+                       const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask, const float* x0_prev, float* x0_keep) {
     constexpr int LDS = dp_lds_floats<NKS>() * (int)sizeof(float);
     static_assert(LDS <= 160 * 1024, "dec_point_kernel's tables fit the LDS");
     static const int attr = []() {
         int rc = (int)hipFuncSetAttribute((const void*)dec_point_kernel<NKS, NPROD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (rc == 0) rc = (int)hipFuncSetAttribute((const void*)dec_point_kernel<NKS, NPROD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (rc == 0) rc = (int)hipFuncSetAttribute((const void*)dec_point_imputing_kernel<NKS, NPROD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        return rc ? rc : (int)hipFuncSetAttribute((const void*)dec_point_imputing_kernel<NKS, NPROD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        if (rc == 0) rc = (int)hipFuncSetAttribute((const void*)dec_point_imputing_kernel<NKS, NPROD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        return rc ? rc : (int)hipFuncSetAttribute((const void*)dec_point_dpm_kernel<NKS, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     }();
     if (attr != 0) return attr;
     if (with_tables) AFM_TRY(launch_dec_tables_t<NKS>(w, B, ws, s));
@@ -453,7 +474,13 @@ int launch_dec_point_p(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, 
     if (chunks > (N + 15) / 16) chunks = (N + 15) / 16;
     const int upd = ddpm ? cdm_update_bits(w) : 0;
     if (!known != !mask || (mask && (!ddpm || !ddpm->x_next || x0_out))) return AFM_E_BADARG;      // imputation: both, and only with the in-place update
-    if (mask && (upd & AFM_UPD_DDIM))
+    // the 2M update: only in place, on DDIM-layout records, without a noise term; x0_prev without x0_keep is no form of it
+    if ((x0_prev && !x0_keep) || (x0_keep && (!ddpm || !ddpm->x_next || x0_out || (upd & (AFM_UPD_DDIM | AFM_UPD_NO_NOISE)) != (AFM_UPD_DDIM | AFM_UPD_NO_NOISE))))
+        return AFM_E_BADARG;
+    if (x0_keep)
+        hipLaunchKernelGGL((dec_point_dpm_kernel<NKS, NPROD>), dim3(chunks, B), dim3(64 * RowLess<NKS>::NW), LDS, s, ws.twp, ws.qtab, w.dec_qdd, w.dec_twx, w.dec_c,
+                           w.fold_w2, w.gen_qe, w.fold_c0, N, w.contact_dim, x_t, feat, w.feat_dim, ddpm->x_next, ddpm->c1, upd, known, mask, x0_prev, x0_keep);
+    else if (mask && (upd & AFM_UPD_DDIM))
         hipLaunchKernelGGL((dec_point_imputing_kernel<NKS, NPROD, true>), dim3(chunks, B), dim3(64 * RowLess<NKS>::NW), LDS, s, ws.twp, ws.qtab, w.dec_qdd, w.dec_twx, w.dec_c,
                            w.fold_w2, w.gen_qe, w.fold_c0, N, w.contact_dim, x_t, feat, w.feat_dim, ddpm->noise, ddpm->x_next, ddpm->c1, ddpm->c2, ddpm->sigma, upd,
                            known, mask);
@@ -476,10 +503,10 @@ int launch_dec_point_p(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, 
 
 template <int NKS>
 int launch_dec_point_t(const afm_cdm_weights& w, int B, int N, const CdmWs& ws, const float* x_t, const float* feat, float* x0_out,
-                       const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask) {
+                       const afm_ddpm_args* ddpm, hipStream_t s, bool with_tables, const float* known, const uint8_t* mask, const float* x0_prev, float* x0_keep) {
     // six products for AFM_ARITH_DEFAULT / AFM_ARITH_BF16X6, all nine otherwise: a function of the pack's arithmetic only
-    if (w.gemm_arith == AFM_ARITH_DEFAULT || w.gemm_arith == AFM_ARITH_BF16X6) return launch_dec_point_p<NKS, 6>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, with_tables, known, mask);
-    return launch_dec_point_p<NKS, 9>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, with_tables, known, mask);
+    if (w.gemm_arith == AFM_ARITH_DEFAULT || w.gemm_arith == AFM_ARITH_BF16X6) return launch_dec_point_p<NKS, 6>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, with_tables, known, mask, x0_prev, x0_keep);
+    return launch_dec_point_p<NKS, 9>(w, B, N, ws, x_t, feat, x0_out, ddpm, s, with_tables, known, mask, x0_prev, x0_keep);
 }
 
 }  // namespace

@@ -976,6 +976,22 @@ int afm_cdm_impute_loop_range(const afm_cdm_weights* w, float* x, float* feat, c
                               int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t N,
                               void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams,
                               void* stream);
+/* The DPM-Solver++(2M) loop slice (v7-additive), as afm_cmdm_dpm_loop_range: the arguments of afm_cdm_ddim_loop_range with the 2M rows in
+ * place of the DDIM rows, no step noise and no seed (the sampler has no noise term), and known / mask [B][N][contact_dim] optional (both or
+ * neither; the imputation rule above).  The update is the afm_dpm_step expression on the final pred_xstart - after the select and the
+ * clamp - which is also kept as the next step's x0_prev in a history buffer [count][N * contact_dim] per sub-batch, carved behind the
+ * sub-batch's workspace for this loop alone (afm_cdm_dpm_loop_workspace_bytes; afm_cdm_loop_workspace_bytes stays what it was).
+ * Row-less form (the default): update, select and history ride in dec_point - the launches of the eta = 0 DDIM loop, bit-identical to
+ * afm_cdm_forward -> (afm_impute ->) (afm_clamp ->) afm_dpm_step per step.  Folded-rows and layer-by-layer forms: pred_xstart stored where
+ * their imputing loops store it, then ONE update launch per sub-batch and step.  first_step == 0: executed step 0 has no history (the
+ * two-term form); first_step > 0: the history is what the previous range call left in the SAME workspace (same B, N, n_sub) - chained
+ * range calls are bit-identical to one call.  AFM_E_BADARG: NULL rows (or a NULL row), first_step < 0, known without mask or the
+ * reverse; AFM_E_WORKSPACE: workspace < afm_cdm_dpm_loop_workspace_bytes.  sched_scratch >= afm_ddim_sched_scratch_bytes(n_steps, B). */
+int64_t afm_cdm_dpm_loop_workspace_bytes(const afm_cdm_weights* w, int32_t B, int32_t N, int32_t n_sub);
+int afm_cdm_dpm_loop_range(const afm_cdm_weights* w, float* x, float* feat, const float* text_q0, const float* text_u,
+                           const float* text_cu, const int64_t* d_timestep_map, const afm_dpm_rows* rows, const float* known,
+                           const uint8_t* mask, int32_t n_steps, int32_t first_step, int32_t B, int32_t N, void* sched_scratch,
+                           void* workspace, int64_t workspace_bytes, int32_t n_sub, void* const* streams, void* stream);
 
 /* Latent-token precomputation (step-invariant, off the per-step path): for n input rows `in` [n, text_dim] (which = 0,
  * language_adapter) or [n, time_dim] (which = 1, time_embedding_adapter) compute the latent's enc_q0 row
