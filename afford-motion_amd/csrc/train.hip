@@ -10,6 +10,9 @@
 //     tiny (<= 1536 x 512) while M = B*T is ~10^4, so the split is what fills 256 CUs.
 //   * LayerNorm backward: one wave per row (row in registers, two wave reductions), per-lane dgamma/dbeta
 //     accumulators over a grid-stride row loop, fixed-order two-stage reduction.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include "common.h"
 #include "profile.h"
 
@@ -624,31 +627,52 @@ __global__ __launch_bounds__(256) void rowop_kernel(const float* __restrict__ x,
     }
 }
 
+// The constants of one AdamW step that torch.optim.AdamW forms in double from its Python-float betas: 1 - beta1, 1 - beta2, the bias
+// corrections 1 - beta1^step and sqrt(1 - beta2^step), each rounded to float32 once.  The betas reach the C ABI as floats, and float32
+// arithmetic on them is not the same thing: 1.0f - 0.999f is exact, but it is 1 minus the ROUNDED beta2, 0.00099998713 (1.3e-5 relative from
+// 0.001, a hundred float32 ulps on the second moment).  A hyper-parameter is a short decimal, so the double the caller meant is recovered as
+// the shortest decimal (up to 9 digits) that rounds to the given float: 0.999f -> 0.999, 0.9f -> 0.9; a float that is no short decimal keeps
+// its own value (9 digits identify any float32).
+struct AdamwConsts { float omb1, omb2, bc1, bc2_sqrt; };
+double shortest_decimal(float f) {
+    char buf[32];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof buf, "%.*g", digits, (double)f);
+        const double d = strtod(buf, nullptr);
+        if ((float)d == f) return d;
+    }
+    return (double)f;
+}
+AdamwConsts adamw_consts(float beta1, float beta2, int32_t step) {
+    const double b1 = shortest_decimal(beta1), b2 = shortest_decimal(beta2);
+    return {(float)(1.0 - b1), (float)(1.0 - b2), (float)(1.0 - pow(b1, (double)step)), (float)sqrt(1.0 - pow(b2, (double)step))};
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                    int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+                                                    int64_t n, float lr, float b1, float b2, float eps, float wd, const AdamwConsts k) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float gi = g[i];
         float pi = p[i] * (1.0f - lr * wd);
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+        const float mi = b1 * m[i] + k.omb1 * gi;
+        const float vi = b2 * v[i] + k.omb2 * gi * gi;
         m[i] = mi; v[i] = vi;
-        pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
+        pi -= (lr / k.bc1) * mi / (sqrtf(vi) / k.bc2_sqrt + eps);
         p[i] = pi;
     }
 }
 
 // one launch for every parameter tensor: blockIdx.y = tensor, blockIdx.x = 16K-element chunk of it
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const afm_adamw_tensor* __restrict__ tab, float lr, float b1, float b2, float eps, float wd,
-                                                          float bc1, float bc2_sqrt) {
+                                                          const AdamwConsts k) {
     const afm_adamw_tensor t = tab[blockIdx.y];
     const int64_t lo = (int64_t)blockIdx.x * 16384, hi = min(t.n, lo + 16384);
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
         const float gi = t.g[i];
         float pi = t.p[i] * (1.0f - lr * wd);
-        const float mi = b1 * t.m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * t.v[i] + (1.0f - b2) * gi * gi;
+        const float mi = b1 * t.m[i] + k.omb1 * gi;
+        const float vi = b2 * t.v[i] + k.omb2 * gi * gi;
         t.m[i] = mi; t.v[i] = vi;
-        pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
+        pi -= (lr / k.bc1) * mi / (sqrtf(vi) / k.bc2_sqrt + eps);
         t.p[i] = pi;
     }
 }
@@ -659,9 +683,8 @@ extern "C" int afm_adamw_multi(const afm_adamw_tensor* d_table, int32_t n_tensor
                                float weight_decay, int32_t step, void* stream) {
     if (n_tensors == 0) return 0;
     if (!d_table || n_tensors < 0 || n_tensors > 65535 || max_n <= 0 || step < 1) return AFM_E_BADARG;
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = sqrtf(1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)((max_n + 16383) / 16384), n_tensors), dim3(256), 0, (hipStream_t)stream, d_table, lr, beta1,
-                       beta2, eps, weight_decay, bc1, bc2);
+                       beta2, eps, weight_decay, adamw_consts(beta1, beta2, step));
     AFM_CHECK_LAUNCH();
     return 0;
 }
@@ -860,9 +883,9 @@ extern "C" int afm_adamw(float* p, const float* g, float* m, float* v, int64_t n
                          float weight_decay, int32_t step, void* stream) {
     if (n == 0) return 0;
     if (!p || !g || !m || !v || n < 0 || step < 1) return AFM_E_BADARG;
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = sqrtf(1.0f - powf(beta2, (float)step));
     int64_t gx = (n + 255) / 256; if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2);
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                       adamw_consts(beta1, beta2, step));
     AFM_CHECK_LAUNCH();
     return 0;
 }
