@@ -333,8 +333,6 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         self.loop_sub_batches = 0
         if self.arch != "Perceiver":
             self.afm_native_loop = None         # other archs sample step by step
-            self.afm_native_impute_loop = None
-            self.afm_native_dpm_loop = None
         self.sub_batches = 1                    # per-call sub-batches of forward(): >1 costs more host time per step than it hides (measured)
         self._streams = []
         self.no_fold = False            # measurement: the layer-by-layer sampling form (what training-mode forward also runs)
@@ -607,13 +605,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 fork.record(cur)
             for i, (lo, hi) in enumerate(bounds):
                 n = hi - lo
-                key = (n, N, i, str(x.device))
-                if key not in self._ws:
-                    nbytes = lib.afm_cdm_workspace_bytes(C.byref(w), n, N)
-                    if nbytes < 0:
-                        ffi.check(int(nbytes), "afm_cdm_workspace_bytes")
-                    self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-                ws = self._ws[key]
+                ws = ffi.workspace(self._ws, (n, N, i, str(x.device)), "afm_cdm_workspace_bytes", C.byref(w), n, N, device=x.device)
                 main = cur if nsub == 1 else self._streams[2 * i]
                 if fork is not None:
                     main.wait_event(fork)
@@ -629,45 +621,25 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
     # ------------------------------------------------------------------ native sampling loop
     def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                        clip_denoised=False, ddim_eta: Optional[float] = None):
-        """Whole p_sample_loop of the ADM on the device (afm_cdm_sample_loop): x holds x_T on entry, returns the sample.  ``ddim_eta`` not
-        None: ddim_sample_loop with that eta (afm_cdm_ddim_loop_range, the DDIM update fused where the DDPM update is in every form).  ``progress``
-        slices the chain (afm_cdm_sample_loop_range) so a tqdm bar can advance, with bit-identical results.  The batch
-        runs as `loop_sub_batches` sub-batches on their own stream pairs (see __init__; bit-identical results).  ``snapshots`` =
-        {executed step count: None} is filled with clones of x after those steps, as in CMDM.afm_native_loop."""
-        return self._native_loop(diffusion, x, model_kwargs, None, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=progress,
-                                 snapshots=snapshots, clip_denoised=clip_denoised, ddim_eta=ddim_eta)
-
-    def afm_native_impute_loop(self, diffusion, x, model_kwargs, impute, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                               clip_denoised=False, ddim_eta: Optional[float] = None):
-        """afm_native_loop with an afm.diffusion.Impute ([B, N, contact_dim], the model's normalised contact space): its known values are
-        written over every step's pred_xstart before the clamp inside the loop (afm_cdm_impute_loop_range) - fused into dec_point's update
-        in the row-less form, one update launch behind the stored pred_xstart in the other two.  Every keyword as afm_native_loop."""
-        if impute is None:
-            raise ValueError("afm_native_impute_loop needs an Impute; afm_native_loop samples without one")
-        impute.check(x)
-        return self._native_loop(diffusion, x, model_kwargs, impute, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=progress,
-                                 snapshots=snapshots, clip_denoised=clip_denoised, ddim_eta=ddim_eta)
-
-    def afm_native_dpm_loop(self, diffusion, x, model_kwargs, impute=None, *, seed=0, sample_index0=0, progress=False, snapshots=None,
-                            clip_denoised=False, dpm_order: int = 2):
-        """dpm_solver_sample_loop on the device (afm_cdm_dpm_loop_range): DPM-Solver++(2M), or the first-order solver with ``dpm_order`` 1 -
-        the same loop on the order-1 rows.  x holds x_T on entry, returns the sample; ``impute`` (an afm.diffusion.Impute, [B, N, contact_dim],
-        or None) is applied as in afm_native_impute_loop.  Row-less form: update, select and the history of the previous step's final
-        pred_xstart ride in dec_point, the launches of the eta = 0 DDIM loop; the other two forms add one update launch per step.
-        Deterministic: ``seed`` / ``sample_index0`` keyed x_T only and are not used here.  ``progress`` / ``snapshots`` slice the chain as
-        in afm_native_loop - the history crosses the range calls in the loop's workspace - with bit-identical results."""
-        if impute is not None:
-            impute.check(x)
-        return self._native_loop(diffusion, x, model_kwargs, impute, step_noise=None, seed=seed, sample_index0=sample_index0, progress=progress,
-                                 snapshots=snapshots, clip_denoised=clip_denoised, ddim_eta=None, dpm_order=int(dpm_order))
-
-    def _native_loop(self, diffusion, x, model_kwargs, impute, *, step_noise, seed, sample_index0, progress, snapshots, clip_denoised, ddim_eta,
-                     dpm_order=None):
-        """the body of the native loops: with ``impute`` the entry is afm_cdm_impute_loop_range and known / mask ride along; with
-        ``dpm_order`` it is afm_cdm_dpm_loop_range, with or without them"""
+                        clip_denoised=False, ddim_eta: Optional[float] = None, impute=None, dpm_order: Optional[int] = None):
+        """Whole p_sample_loop of the ADM on the device (afm_cdm_sample_loop_range): x holds x_T on entry, returns the sample.  ``ddim_eta`` not
+        None: ddim_sample_loop with that eta (afm_cdm_ddim_loop_range, the DDIM update fused where the DDPM update is in every form).
+        ``impute``: an afm.diffusion.Impute ([B, N, contact_dim], the model's normalised contact space) - its known values are written over
+        every step's pred_xstart before the clamp inside the loop (afm_cdm_impute_loop_range, both updates) - fused into dec_point's update
+        in the row-less form, one update launch behind the stored pred_xstart in the other two.  ``dpm_order`` (1 or 2) not None:
+        dpm_solver_sample_loop instead (afm_cdm_dpm_loop_range, with or without an Impute): DPM-Solver++(2M), or the first-order solver -
+        the same loop on the order-1 rows.  Row-less form: update, select and the history of the previous step's final pred_xstart ride in
+        dec_point, the launches of the eta = 0 DDIM loop; the other two forms add one update launch per step.  No noise: ``step_noise`` and
+        ``ddim_eta`` are refused, ``seed`` / ``sample_index0`` keyed x_T only and are not used.  ``progress`` slices the chain so a tqdm bar
+        can advance, with bit-identical results (the 2M history crosses the range calls in the loop's workspace).  The batch runs as
+        `loop_sub_batches` sub-batches on their own stream pairs (see __init__; bit-identical results).  ``snapshots`` = {executed step
+        count: None} is filled with clones of x after those steps, as in CMDM.afm_native_loop."""
         if self.arch != "Perceiver":
             raise NotImplementedError("the native loop covers the Perceiver arch")
+        if dpm_order is not None and (ddim_eta is not None or step_noise is not None):
+            raise ValueError("the DPM-Solver++ loop is deterministic: it takes neither ddim_eta nor step_noise")
+        if impute is not None:
+            impute.check(x)
         lib = ffi.load()
         ffi.require_gpu(x)
         with torch.no_grad():
@@ -677,51 +649,45 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             w = self._weights()
             feat = self._features(x, model_kwargs)
             tq0, tu, tcu = self._text_latent(w, model_kwargs, dev)
-            tab = diffusion.tables(dev)
-            n = diffusion.num_timesteps
-            sched = ffi.sched_scratch(self, n, B, dev, ddim=ddim_eta is not None or dpm_order is not None)
-            ddim = None if ddim_eta is None else diffusion.ddim_tables(dev, ddim_eta)
-            dpm = None if dpm_order is None else diffusion.dpm_tables(dev, dpm_order)
+            tables = ffi.LoopTables(self, diffusion, B, dev, ddim_eta, dpm_order)
             nsub = int(self.loop_sub_batches) or 1
             nsub = max(1, min(nsub, B))
             need = 2 * nsub if nsub > 1 else (1 if self.overlap_streams else 0)
             streams = self._loop_streams(need, dev)
             handles = (C.c_void_p * max(need, 1))(*[s_.cuda_stream for s_ in streams]) if need else None
-            sizer = "afm_cdm_loop_workspace_bytes" if dpm is None else "afm_cdm_dpm_loop_workspace_bytes"
-            nbytes = getattr(lib, sizer)(C.byref(w), B, N, nsub)
-            if nbytes < 0:
-                ffi.check(int(nbytes), sizer)
             # (the 2M loop: a buffer of its own per sampling form - the history of step j0 - 1 lives in it between the slices of a chain, at an
-            # offset that depends on the form)
-            key = ("loop", B, N, nsub, str(dev)) if dpm is None else ("dpm_loop", bool(self.no_gen), bool(self.no_fold), B, N, nsub, str(dev))
-            if key not in self._ws or self._ws[key].numel() < nbytes:        # (the row-less form's workspace is smaller than the other forms')
-                self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            ws = self._ws[key]
-            stream = ffi.stream_of(x)
+            # offset that depends on the form; the other loops: one key, the row-less form's workspace is smaller than the other forms')
+            if tables.dpm is None:
+                key, sizer = ("loop", B, N, nsub, str(dev)), "afm_cdm_loop_workspace_bytes"
+            else:
+                key, sizer = ("dpm_loop", bool(self.no_gen), bool(self.no_fold), B, N, nsub, str(dev)), "afm_cdm_dpm_loop_workspace_bytes"
+            ws = ffi.workspace(self._ws, key, sizer, C.byref(w), B, N, nsub, device=dev)
             if clip_denoised:
                 w.flags |= ffi.CDM_CLIP_X0                   # per call: the next _weights() rewrites the flags
-            entry = "afm_cdm_sample_loop_range" if ddim is None else "afm_cdm_ddim_loop_range"
-            if impute is not None:
+            # the entry and what it takes behind its rows: afm_cdm_impute_loop_range runs both updates (both kinds of rows, then known and
+            # mask), afm_cdm_dpm_loop_range takes known and mask or NULLs
+            known_mask = ffi.impute_ptrs(impute) if impute is not None or tables.dpm is not None else ()
+            if tables.dpm is not None:
+                entry = "afm_cdm_dpm_loop_range"
+            elif impute is not None:
                 entry = "afm_cdm_impute_loop_range"
+            else:
+                entry = "afm_cdm_sample_loop_range" if tables.ddim is None else "afm_cdm_ddim_loop_range"
+            head = (C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr())
+            tail = (B, N, tables.sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, ffi.stream_of(x))
+            n = tables.n
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
-                if dpm is not None:         # one entry with and without an Impute; no noise, no seed
-                    return ffi.check(lib.afm_cdm_dpm_loop_range(
-                        C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(), tab.timestep_map[lo:].data_ptr(),
-                        C.byref(dpm.rows(lo)), None if impute is None else impute.known.data_ptr(), None if impute is None else impute.mask.data_ptr(),
-                        j1 - j0, j0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream), "afm_cdm_dpm_loop_range")
-                rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
-                    (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
-                if impute is not None:      # one entry for both updates: both kinds of rows, then known and mask
-                    rows = ((rows[0], None, None, None) if ddim is not None else (None,) + rows) + (impute.known.data_ptr(), impute.mask.data_ptr())
-                ffi.check(getattr(lib, entry)(
-                    C.byref(w), x.data_ptr(), feat.data_ptr(), tq0.data_ptr(), tu.data_ptr(), tcu.data_ptr(), nz, tab.timestep_map[lo:].data_ptr(),
-                    *rows, j1 - j0, j0, seed & (2**64 - 1), sample_index0, B, N, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub, handles, stream),
-                    entry)
+                if tables.dpm is not None:      # no noise, no seed
+                    steps = (tables.tmap(lo), tables.dpm_rows(lo), *known_mask, j1 - j0, j0)
+                else:
+                    steps = (nz, tables.tmap(lo), *tables.rows(lo, impute is not None), *known_mask, j1 - j0, j0, seed & (2**64 - 1),
+                             sample_index0)
+                ffi.check(getattr(lib, entry)(*head, *steps, *tail), entry)
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
-            self._last_loop_scratch = (sched, step_noise, feat, tq0, tu, tcu, ddim, dpm, impute)
+            self._last_loop_scratch = (tables.keep(), step_noise, feat, tq0, tu, tcu, impute)
         return x
 
     # ------------------------------------------------------------------ 'MLP' arch (per-operator composition, inference and training)

@@ -279,15 +279,6 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             (ffi.CMDM_PAIR_LAUNCH if self.pair_launch else 0)
         return w
 
-    def _workspace(self, w: ffi.CmdmWeights, B: int, L: int, device) -> torch.Tensor:
-        key = (B, L, str(device))
-        if key not in self._ws:
-            nbytes = ffi.load().afm_cmdm_workspace_bytes(C.byref(w), B, L)
-            if nbytes < 0:
-                ffi.check(int(nbytes), "afm_cmdm_workspace_bytes")
-            self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=device)}
-        return self._ws[key]
-
     # ------------------------------------------------------------------ step-invariant conditions
     def condition_tokens(self, **kwargs) -> torch.Tensor:
         """[B, 1 + G, d]: language_adapter(text) and contact_adapter(SceneMapEncoder(xyz, contact)),
@@ -338,7 +329,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if self.mask_motion:
                 fm = kwargs["x_mask"].to(device=x.device, dtype=torch.uint8).contiguous()
             out = torch.empty_like(x)
-            ws = self._workspace(w, B, L, x.device)
+            ws = ffi.workspace(self._ws, (B, L, str(x.device)), "afm_cmdm_workspace_bytes", C.byref(w), B, L, device=x.device, single=True)
             t = timesteps.to(device=x.device, dtype=torch.int64).contiguous()
             ffi.check(lib.afm_cmdm_forward(C.byref(w), x.data_ptr(), t.data_ptr(), cond.data_ptr(), ffi.ptr(fm),
                                            out.data_ptr(), None, B, L, ws.data_ptr(), ws.numel(), ffi.stream_of(x)),
@@ -571,11 +562,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if tuple(cond.shape[:2]) != (B, w.n_cond):       # (e.g. a cloud of fewer points than contact_model.num_points: the loop reads n_cond rows per sample)
                 raise ValueError(f"the conditions give {tuple(cond.shape[:2])} tokens, the model's layout has ({B}, {w.n_cond})")
             fm = model_kwargs["x_mask"].to(device=x.device, dtype=torch.uint8).contiguous() if self.mask_motion else None
-            tab = diffusion.tables(x.device)
-            n = diffusion.num_timesteps
-            sched = ffi.sched_scratch(self, n, B, x.device, ddim=ddim_eta is not None or dpm_order is not None)
-            ddim = None if ddim_eta is None else diffusion.ddim_tables(x.device, ddim_eta)
-            dpm = None if dpm_order is None else diffusion.dpm_tables(x.device, dpm_order)
+            tables = ffi.LoopTables(self, diffusion, B, x.device, ddim_eta, dpm_order)
             # sub-batch streams fill the wave-quantisation tails of B >= 16 launches; below that every launch is latency-bound and a
             # second stream only adds launches (B = 4: 1311 steps/s on one stream vs 1159 on two, profiles/r02_small_batch.md)
             nsub = max(1, min(int(self.loop_streams), B // 8 if self.loop_streams_auto else B))
@@ -595,57 +582,44 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[:nsub]])
                 branch_handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[nsub:2 * nsub]])
                 cfg.branch_streams = C.cast(branch_handles, C.POINTER(C.c_void_p))
-            if dpm is not None:
-                nbytes = lib.afm_cmdm_dpm_loop_workspace_bytes(C.byref(w), B, L, nsub, None if cfg is None or two else C.byref(cfg),
-                                                               C.byref(cfg) if two else None)
-            elif cfg is None:
-                nbytes = lib.afm_cmdm_loop_workspace_bytes(C.byref(w), B, L, nsub)
+            cfg_ref = None if cfg is None else C.byref(cfg)
+            # the workspace: its sizer, the sizer's guidance argument and the form that keys the buffer
+            if cfg is None:
+                sizer, size_args, form = "afm_cmdm_loop_workspace_bytes", (), "loop"
             elif two:
-                nbytes = lib.afm_cmdm_cfg2_loop_workspace_bytes(C.byref(w), B, L, nsub, C.byref(cfg))
+                sizer, size_args, form = "afm_cmdm_cfg2_loop_workspace_bytes", (cfg_ref,), ("cfg2_loop", cfg.first, cfg.flags)
             else:
-                nbytes = lib.afm_cmdm_cfg_loop_workspace_bytes(C.byref(w), B, L, nsub, C.byref(cfg))
-            if nbytes < 0:
-                ffi.check(int(nbytes), "afm_cmdm_loop_workspace_bytes")
-            form = "loop" if cfg is None else ("cfg2_loop", cfg.first, cfg.flags) if two else ("cfg_loop", cfg.drop_text, cfg.drop_pc, cfg.flags)
-            if dpm is not None:         # (a size of its own: the history buffers)
-                form = ("dpm", form)
-            key = (form, B, L, nsub, str(x.device))
-            if key not in self._ws:
-                self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
-            ws = self._ws[key]
-            stream = ffi.stream_of(x)
-            entry = {(True, True): "afm_cmdm_sample_loop_range", (True, False): "afm_cmdm_ddim_loop_range",
-                     (False, True): "afm_cmdm_cfg_sample_loop_range", (False, False): "afm_cmdm_cfg_ddim_loop_range"}[(cfg is None, ddim is None)]
-            if impute is not None:
-                entry = "afm_cmdm_impute_loop_range"
-            if two:
-                entry = "afm_cmdm_cfg2_loop_range"
+                sizer, size_args, form = "afm_cmdm_cfg_loop_workspace_bytes", (cfg_ref,), ("cfg_loop", cfg.drop_text, cfg.drop_pc, cfg.flags)
+            # the entry and what it takes behind its rows.  ``every_form``: an entry that runs both updates - both kinds of rows, then cfg or
+            # NULL, known and mask or NULLs
+            every_form = False
+            if tables.dpm is not None:          # every form; a size of its own: the history buffers, which cross the range calls of a chain
+                entry, guide = "afm_cmdm_dpm_loop_range", (None if two else cfg_ref, cfg_ref if two else None) + ffi.impute_ptrs(impute)
+                sizer, size_args, form = "afm_cmdm_dpm_loop_workspace_bytes", guide[:2], ("dpm", form)
+            elif two or impute is not None:
+                entry = "afm_cmdm_cfg2_loop_range" if two else "afm_cmdm_impute_loop_range"
+                guide, every_form = (cfg_ref,) + ffi.impute_ptrs(impute), True
+            elif cfg is None:
+                entry, guide = "afm_cmdm_sample_loop_range" if tables.ddim is None else "afm_cmdm_ddim_loop_range", ()
+            else:
+                entry, guide = "afm_cmdm_cfg_sample_loop_range" if tables.ddim is None else "afm_cmdm_cfg_ddim_loop_range", (cfg_ref,)
+            ws = ffi.workspace(self._ws, (form, B, L, nsub, str(x.device)), sizer, C.byref(w), B, L, nsub, *size_args, device=x.device, single=True)
+            head = (C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm))
+            tail = (B, L, tables.sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub if nsub > 1 else 0, handles if nsub > 1 else None,
+                    ffi.stream_of(x))
+            n = tables.n
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
-                if dpm is not None:         # one entry for every form; the history of step j0 - 1 is in `ws`
-                    rc = lib.afm_cmdm_dpm_loop_range(
-                        C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), tab.timestep_map[lo:].data_ptr(), C.byref(dpm.rows(lo)),
-                        None if cfg is None or two else C.byref(cfg), C.byref(cfg) if two else None,
-                        None if impute is None else impute.known.data_ptr(), None if impute is None else impute.mask.data_ptr(),
-                        j1 - j0, j0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub if nsub > 1 else 0,
-                        handles if nsub > 1 else None, stream)
-                    return ffi.check(rc, "afm_cmdm_dpm_loop_range")
-                head = (C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm), nz, tab.timestep_map[lo:].data_ptr())
-                rows = (C.byref(ddim.rows(lo)),) if ddim is not None else \
-                    (tab.coef1[lo:].data_ptr(), tab.coef2[lo:].data_ptr(), tab.sigma[lo:].data_ptr())
-                guide = () if cfg is None else (C.byref(cfg),)
-                if impute is not None or two:       # one entry for every form: both kinds of rows, cfg or NULL, known and mask (two scales: or NULL)
-                    rows = (rows[0], None, None, None) if ddim is not None else (None,) + rows
-                    guide = (None if cfg is None else C.byref(cfg),) + \
-                        ((None, None) if impute is None else (impute.known.data_ptr(), impute.mask.data_ptr()))
-                tail = (j1 - j0, j0, seed & (2**64 - 1), sample_index0, B, L, sched.data_ptr(), ws.data_ptr(), ws.numel(),
-                        nsub if nsub > 1 else 0, handles if nsub > 1 else None, stream)
-                ffi.check(getattr(lib, entry)(*head, *rows, *guide, *tail), entry)
+                if tables.dpm is not None:      # no noise, no seed
+                    steps = (tables.tmap(lo), tables.dpm_rows(lo), *guide, j1 - j0, j0)
+                else:
+                    steps = (nz, tables.tmap(lo), *tables.rows(lo, every_form), *guide, j1 - j0, j0, seed & (2**64 - 1), sample_index0)
+                ffi.check(getattr(lib, entry)(*head, *steps, *tail), entry)
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (sched, step_noise, cond, fm, ddim, dpm, _guidance, impute)
+            self._last_loop_scratch = (tables.keep(), step_noise, cond, fm, _guidance, impute)
         return x
 
 
@@ -764,13 +738,8 @@ class GuidedCMDM(nn.Module):
             two = self.order is not None
             name = "afm_cmdm_cfg2" if two else "afm_cmdm_cfg"
             out = torch.empty((4 if two else 3,) + tuple(x.shape), dtype=torch.float32, device=x.device)
-            key = ("cfg2" if two else "cfg", B, L, str(x.device))
-            if key not in m._ws:
-                nbytes = getattr(lib, name + "_workspace_bytes")(C.byref(w), B, L)
-                if nbytes < 0:
-                    ffi.check(int(nbytes), name + "_workspace_bytes")
-                m._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
-            ws = m._ws[key]
+            ws = ffi.workspace(m._ws, ("cfg2" if two else "cfg", B, L, str(x.device)), name + "_workspace_bytes", C.byref(w), B, L,
+                               device=x.device, single=True)
             t = timesteps.to(device=x.device, dtype=torch.int64).contiguous()
             ffi.check(getattr(lib, name + "_forward")(C.byref(w), x.data_ptr(), t.data_ptr(), cond.data_ptr(), fm.data_ptr(), C.byref(cfg),
                                                       *[o.data_ptr() for o in out], B, L, ws.data_ptr(), ws.numel(), ffi.stream_of(x)),

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import ffi, ops
+from .cmdm import COND_SWITCHES
 
 
 def betas_for_alpha_bar(num_diffusion_timesteps: int, alpha_bar: Callable[[float], float], max_beta: float = 0.999):
@@ -81,9 +82,9 @@ class Impute:
     ([L, D], [B, L, 1], [B, 1, D], ...); expanded ONCE to a contiguous uint8 of known's shape on known's device.
 
     The object is a callable ``imp(x0) -> ops.impute(x0, known, mask)`` (afm_impute, HIP), so it IS a ``denoised_fn`` wherever one is
-    accepted - p_sample, ddim_sample, the progressive generators, the CDM; handed to p_sample_loop / ddim_sample_loop of a denoiser whose
-    native loop takes ``impute=`` (CMDM `trans_enc`, GuidedCMDM: afm_cmdm_impute_loop_range) or that has an ``afm_native_impute_loop``
-    (the CDM Perceiver: afm_cdm_impute_loop_range) the whole chain stays in the native loop."""
+    accepted - p_sample, ddim_sample, the progressive generators, the CDM; handed to p_sample_loop / ddim_sample_loop /
+    dpm_solver_sample_loop of a denoiser whose ``afm_native_loop`` names ``impute`` (CMDM `trans_enc`, GuidedCMDM:
+    afm_cmdm_impute_loop_range; the CDM Perceiver: afm_cdm_impute_loop_range) the whole chain stays in the native loop."""
 
     def __init__(self, known: torch.Tensor, mask: torch.Tensor):
         if known.dim() != 3:
@@ -129,16 +130,6 @@ class Impute:
         if start < 0 or count < 0 or start + count > self.known.shape[0]:
             raise ValueError(f"Impute.narrow({start}, {count}) of a batch of {self.known.shape[0]}")
         return Impute._of(self.known[start:start + count], self.mask[start:start + count])
-
-
-def _takes_impute(native) -> bool:
-    """does a denoiser's afm_native_loop accept the ``impute=`` keyword (CMDM trans_enc, GuidedCMDM; not the CDM, whose afm_native_loop
-    keeps its signature: its imputing loop is a second method, afm_native_impute_loop, which `_sample_loop` looks for by name)"""
-    import inspect
-    try:
-        return "impute" in inspect.signature(native).parameters
-    except (TypeError, ValueError):
-        return False
 
 
 class _DeviceTables:
@@ -479,8 +470,8 @@ class GaussianDiffusion:
                                sample_index0: int = 0, snapshots: Optional[dict] = None):
         """DPM-Solver++(2M) sampling (``order`` 1: first order, DDIM eta = 0) on this - usually respaced, e.g. "logsnr20" - process: one
         denoiser evaluation per step, deterministic.  ``seed`` / ``sample_index0`` key x_T only; ``step_noise`` is refused.  A denoiser
-        whose ``afm_native_loop`` takes ``dpm_order`` (CMDM `trans_enc`, GuidedCMDM) or that has an ``afm_native_dpm_loop`` (the CDM
-        `Perceiver`: afm_cdm_dpm_loop_range), an `Impute` as ``denoised_fn`` included, runs the whole chain natively under p_sample_loop's
+        whose ``afm_native_loop`` names ``dpm_order`` (CMDM `trans_enc`, GuidedCMDM: afm_cmdm_dpm_loop_range; the CDM `Perceiver`:
+        afm_cdm_dpm_loop_range), an `Impute` as ``denoised_fn`` included, runs the whole chain natively under p_sample_loop's
         conditions; any other samples step by step, an `Impute` applied as the plain ``denoised_fn`` it also is."""
         if step_noise is not None:
             raise ValueError("DPM-Solver++ is deterministic: it takes no step_noise")
@@ -492,21 +483,17 @@ class GaussianDiffusion:
 
     def _sample_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, step_noise, seed,
                      sample_index0, snapshots, ddim_eta: Optional[float], dpm_order: Optional[int] = None):
-        """p_sample_loop (ddim_eta None) / ddim_sample_loop / dpm_solver_sample_loop (dpm_order not None): the native loop when the
-        denoiser has one and nothing needs the host between steps, else the progressive generator.  A ``denoised_fn`` that is an `Impute`
-        stays native where the denoiser's loop takes ``impute=`` or the denoiser has an ``afm_native_impute_loop`` (the CDM); any other
-        callable samples step by step.  DPM-Solver++ is native where ``afm_native_loop`` names ``dpm_order`` (the CMDM) or, when it does
-        not, where the denoiser has an ``afm_native_dpm_loop`` (the CDM: a third method with the Impute, or None, as its fourth argument)
-        - found by name, under the same conditions; a denoiser with neither samples step by step."""
+        """p_sample_loop (ddim_eta None) / ddim_sample_loop / dpm_solver_sample_loop (dpm_order not None): the denoiser's
+        ``afm_native_loop`` when it has one and nothing needs the host between steps - no ``cond_fn``, no rescaled timesteps, no condition
+        switch in ``model_kwargs`` - else the progressive generator.  A ``denoised_fn`` that is an `Impute` stays native where the loop
+        names ``impute``, DPM-Solver++ where it names ``dpm_order``; any other ``denoised_fn``, and a loop that names neither keyword,
+        sample step by step."""
         native = getattr(model, "afm_native_loop", None)
-        third = dpm_order is not None and native is not None and not _takes(native, "dpm_order")
-        if third:                                  # the CDM's 2M loop; None (a non-Perceiver CDM, any other denoiser): step by step
-            native = getattr(model, "afm_native_dpm_loop", None)
-        switches = any(k in (model_kwargs or {}) for k in ("c_text_mask", "c_text_erase", "c_pc_mask", "c_pc_erase"))
-        native_impute = getattr(model, "afm_native_impute_loop", None) if native is not None and not third else None
-        impute = denoised_fn if isinstance(denoised_fn, Impute) and native is not None and \
-            (third or _takes_impute(native) or native_impute is not None) else None
-        if native is not None and (denoised_fn is None or impute is not None) and cond_fn is None and not self.rescale_timesteps and not switches:
+        impute = denoised_fn if isinstance(denoised_fn, Impute) else None
+        if native is not None and cond_fn is None and not self.rescale_timesteps and \
+                not any(k in (model_kwargs or {}) for k in COND_SWITCHES) and \
+                (denoised_fn is None or (impute is not None and _takes(native, "impute"))) and \
+                (dpm_order is None or _takes(native, "dpm_order")):
             if device is None:
                 device = next(model.parameters()).device
             seed = self._fresh_seed("_sample_calls") if seed is None else seed
@@ -517,20 +504,15 @@ class GaussianDiffusion:
             extra = {} if snapshots is None else {"snapshots": snapshots}
             if impute is not None:
                 impute.check(x)
-                if not third and _takes_impute(native):
-                    extra["impute"] = impute
+                extra["impute"] = impute
             if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused update
                 extra["clip_denoised"] = True
             if ddim_eta is not None:
                 extra["ddim_eta"] = ddim_eta
             if dpm_order is not None:
                 extra["dpm_order"] = dpm_order
-            args = (self, x, model_kwargs or {})
-            if third:                              # the Impute, or None, as the fourth argument; the sampler has no step noise
-                return native(*args, impute, seed=seed, sample_index0=sample_index0, progress=bool(progress), **extra)
-            if impute is not None and "impute" not in extra:      # the CDM: a second method with the Impute as its fourth argument
-                native, args = native_impute, args + (impute,)
-            return native(*args, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=bool(progress), **extra)
+            return native(self, x, model_kwargs or {}, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=bool(progress),
+                          **extra)
         gen = self.p_sample_loop_progressive if ddim_eta is None else \
             (lambda *a, **k: self.ddim_sample_loop_progressive(*a, eta=ddim_eta, **k))
         if dpm_order is not None:

@@ -386,6 +386,61 @@ def sched_scratch(owner, n_steps: int, batch: int, device, *, ddim: bool = False
     return buf
 
 
+class LoopTables:
+    """What one native sampling-loop call reads of the schedule: the `_DeviceTables` of ``diffusion`` on ``device``, the DDIM rows of
+    ``ddim_eta`` or None, the DPM-Solver++ rows of ``dpm_order`` or None, and the expanded-schedule scratch (`sched_scratch` on ``owner``,
+    the model).  It knows the ABI's ordering of the row arguments of a range call whose first timestep index is ``lo``, nothing else."""
+
+    def __init__(self, owner, diffusion, B: int, device, ddim_eta=None, dpm_order=None):
+        self.n = diffusion.num_timesteps
+        self.tab = diffusion.tables(device)
+        self.sched = sched_scratch(owner, self.n, B, device, ddim=ddim_eta is not None or dpm_order is not None)
+        self.ddim = None if ddim_eta is None else diffusion.ddim_tables(device, ddim_eta)
+        self.dpm = None if dpm_order is None else diffusion.dpm_tables(device, dpm_order)
+
+    def tmap(self, lo: int) -> int:
+        return self.tab.timestep_map[lo:].data_ptr()
+
+    def rows(self, lo: int, every_form: bool = False) -> tuple:
+        """(c1, c2, sigma) of a DDPM-only entry or (afm_ddim_rows*,) of a DDIM-only one; ``every_form``: the (rows, c1, c2, sigma) of an
+        entry that runs both updates, the other kind NULL."""
+        if self.ddim is not None:
+            rows = C.byref(self.ddim.rows(lo))
+            return (rows, None, None, None) if every_form else (rows,)
+        ddpm = (self.tab.coef1[lo:].data_ptr(), self.tab.coef2[lo:].data_ptr(), self.tab.sigma[lo:].data_ptr())
+        return (None,) + ddpm if every_form else ddpm
+
+    def dpm_rows(self, lo: int):
+        return C.byref(self.dpm.rows(lo))
+
+    def keep(self) -> tuple:
+        """what the caller holds until the stream has consumed the loop"""
+        return (self.sched, self.ddim, self.dpm)
+
+
+def workspace(cache: dict, key, sizer: str, *args, device, single: bool = False) -> torch.Tensor:
+    """The byte buffer ``cache[key]`` of a native call, sized by the library's ``sizer(*args)`` (a negative size is its error code).
+    ``single`` (the CMDM): the key fixes the size, a hit is returned unsized, and a miss replaces whatever the cache held - one buffer per
+    model.  Otherwise (the CDM) every key stays and a cached buffer smaller than this call needs is re-allocated (one key covers the
+    sampling forms, whose sizes differ)."""
+    buf = cache.get(key)
+    if buf is not None and single:
+        return buf
+    nbytes = int(getattr(load(), sizer)(*args))
+    if nbytes < 0:
+        check(nbytes, sizer)
+    if buf is None or buf.numel() < nbytes:
+        if single:
+            cache.clear()
+        buf = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return buf
+
+
+def impute_ptrs(impute) -> tuple:
+    """the (known, mask) pointer pair of an afm.diffusion.Impute, or two NULLs"""
+    return (None, None) if impute is None else (impute.known.data_ptr(), impute.mask.data_ptr())
+
+
 _HIP_RT = None
 
 

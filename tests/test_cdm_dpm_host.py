@@ -1,13 +1,12 @@
 """DPM-Solver++(2M) in the CDM's native loops, on the host (no GPU): the C ABI declares and exports the two new entries and refuses NULL
-rows and a `known` without a `mask`; `dpm_solver_sample_loop` reaches the CDM's third method, `afm_native_dpm_loop`, under the conditions
-of every native loop; the signatures of the two existing methods stay.  The float32 / float64 twins of the loop - the 2M update restated
+rows and a `known` without a `mask`; `dpm_solver_sample_loop` reaches the CDM's `afm_native_loop` with ``dpm_order=``, under the conditions
+of every native loop.  The float32 / float64 twins of the loop - the 2M update restated
 around the CPU oracle's CDM - are built here for tests/test_gpu_cdm_dpm.py to import.
 
     x_next = a x_t + b x0                       the first executed step (no history)
     x_next = (a x_t + b x0) + c x0_prev         x0 / x0_prev: the final predictions (after the imputation select and the clamp)"""
 import ctypes
 import functools
-import inspect
 import os
 import re
 
@@ -16,7 +15,8 @@ import torch
 
 from afm import ffi
 from conftest import ROOT
-from test_cdm_impute_host import SHAPE, contact_known, contact_mask, imputed, loop_inputs, oracle_cdm
+from test_cdm_impute_host import (SHAPE, _NarrowRecorder, _Recorder, check_one_native_loop, contact_known, contact_mask, imputed, loop_inputs,
+                                  oracle_cdm, samples_step_by_step)
 from test_ddim_host import _diffusion
 
 ENTRY, SIZER = "afm_cdm_dpm_loop_range", "afm_cdm_dpm_loop_workspace_bytes"
@@ -71,58 +71,17 @@ def test_entry_refuses_null_rows_and_a_known_without_a_mask():
 
 
 def test_python_surface():
-    from afm.cdm import CDM
-    from afm.diffusion import GaussianDiffusion, _takes, _takes_impute
+    from afm.diffusion import GaussianDiffusion
     from afm.pipeline import two_stage_sample
-    loop, imp, dpm = (inspect.signature(f) for f in (CDM.afm_native_loop, CDM.afm_native_impute_loop, CDM.afm_native_dpm_loop))
-    # the two existing methods are what they were (tests/test_cdm_impute_host.py pins the same lists)
-    assert list(loop.parameters) == ["self", "diffusion", "x", "model_kwargs", "step_noise", "seed", "sample_index0", "progress", "snapshots",
-                                     "clip_denoised", "ddim_eta"]
-    assert list(imp.parameters) == ["self", "diffusion", "x", "model_kwargs", "impute"] + list(loop.parameters)[4:]
-    assert not _takes_impute(CDM.afm_native_loop) and not _takes(CDM.afm_native_loop, "dpm_order") and not _takes(CDM.afm_native_impute_loop, "dpm_order")
-    assert list(dpm.parameters) == ["self", "diffusion", "x", "model_kwargs", "impute", "seed", "sample_index0", "progress", "snapshots",
-                                    "clip_denoised", "dpm_order"]
-    assert dpm.parameters["impute"].default is None and dpm.parameters["impute"].kind is inspect.Parameter.POSITIONAL_OR_KEYWORD
-    for name in list(dpm.parameters)[5:]:
-        assert dpm.parameters[name].kind is inspect.Parameter.KEYWORD_ONLY, name
-    assert "afm_native_dpm_loop" in inspect.getsource(GaussianDiffusion._sample_loop)
+    check_one_native_loop()
     doc = two_stage_sample.__doc__
     assert "normalised contact" in doc and "afm_cdm_dpm_loop_range" in doc and "no native form" not in doc
     assert "never the CDM" not in GaussianDiffusion._sample_loop.__doc__
 
 
-class _Recorder(torch.nn.Module):
-    """a denoiser with the CDM's three native loops, recording which one a sampling call reaches"""
-    def __init__(self, with_dpm_loop=True):
-        super().__init__()
-        self.p = torch.nn.Parameter(torch.zeros(1))
-        self.calls = []
-        if not with_dpm_loop:
-            self.afm_native_dpm_loop = None
-
-    def forward(self, x, t, **kw):
-        self.calls.append("forward")
-        return x
-
-    def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
-                        clip_denoised=False, ddim_eta=None):
-        self.calls.append(("loop", clip_denoised, ddim_eta))
-        return x
-
-    def afm_native_impute_loop(self, diffusion, x, model_kwargs, impute, *, step_noise=None, seed=0, sample_index0=0, progress=False,
-                               snapshots=None, clip_denoised=False, ddim_eta=None):
-        self.calls.append(("impute", impute, clip_denoised, ddim_eta))
-        return x
-
-    def afm_native_dpm_loop(self, diffusion, x, model_kwargs, impute=None, *, seed=0, sample_index0=0, progress=False, snapshots=None,
-                            clip_denoised=False, dpm_order=2):
-        self.calls.append(("dpm", impute, clip_denoised, dpm_order, seed, sample_index0, progress, snapshots))
-        return x
-
-
-def test_dpm_solver_sample_loop_routes_to_the_third_method(monkeypatch):
+def test_dpm_solver_sample_loop_hands_the_order_to_the_native_loop(monkeypatch):
     from afm.diffusion import Impute
-    d = _diffusion(500, "ddim5")
+    d, seeds = _diffusion(500, "ddim5"), _diffusion(500, "ddim5")
     shape = (2, 4, 6)
     imp = Impute(torch.zeros(shape), torch.ones(shape, dtype=torch.bool))
     xT = torch.zeros(shape)
@@ -132,49 +91,37 @@ def test_dpm_solver_sample_loop_routes_to_the_third_method(monkeypatch):
     d.dpm_solver_sample_loop(m, shape, noise=xT, clip_denoised=False, order=1, seed=4, progress=False, snapshots=snaps)
     d.ddim_sample_loop(m, shape, noise=xT, clip_denoised=False, eta=0.0)          # the other samplers go where they went
     d.p_sample_loop(m, shape, noise=xT, clip_denoised=False, denoised_fn=imp)
-    assert m.calls == [("dpm", imp, True, 2, 3, 5, False, None), ("dpm", None, False, 1, 4, 0, False, snaps), ("loop", False, 0.0),
-                       ("impute", imp, False, None)]
+    s = [seeds._fresh_seed("_sample_calls") for _ in range(2)]                  # no seed given: the diffusion's own, call by call
+    assert m.calls == [(imp, True, None, 2, 3, 5, False, None, True), (None, False, None, 1, 4, 0, False, snaps, True),
+                       (None, False, 0.0, None, s[0], 0, False, None, True), (imp, False, None, None, s[1], 0, False, None, True)]
     with pytest.raises(ValueError):               # impute.check(x) first
         d.dpm_solver_sample_loop(m, (2, 5, 6), noise=torch.zeros(2, 5, 6), denoised_fn=imp)
     assert len(m.calls) == 4
-    # a plain callable, rescale_timesteps, a condition switch, and a denoiser whose third method is None sample step by step (stopped at
-    # the first denoiser call)
-    class Stop(Exception):
-        pass
-
-    def stop(*a, **k):
-        raise Stop
+    # a plain callable, rescale_timesteps, a condition switch, and a denoiser whose loop does not name ``dpm_order`` - with and without an
+    # Impute - sample step by step
     rescaled = _diffusion(500, "ddim5")
     rescaled.rescale_timesteps = True
     switch = dict(c_text_mask=torch.zeros(2, 1, dtype=torch.bool))
     for diff, model, fn, kw in ((d, _Recorder(), lambda x0: x0, None), (rescaled, _Recorder(), None, None), (d, _Recorder(), None, switch),
-                                (d, _Recorder(with_dpm_loop=False), imp, None), (d, _Recorder(with_dpm_loop=False), None, None)):
-        monkeypatch.setattr(model, "forward", stop)
-        with pytest.raises(Stop):
-            diff.dpm_solver_sample_loop(model, shape, noise=xT, clip_denoised=False, denoised_fn=fn, model_kwargs=kw)
-        assert model.calls == []
+                                (d, _NarrowRecorder(), imp, None), (d, _NarrowRecorder(), None, None)):
+        samples_step_by_step(monkeypatch, model, lambda: diff.dpm_solver_sample_loop(model, shape, noise=xT, clip_denoised=False, denoised_fn=fn,
+                                                                                     model_kwargs=kw))
 
 
-def test_only_the_perceiver_cdm_has_the_third_method(monkeypatch):
-    """a non-Perceiver CDM has no native loop of any kind, so dpm_solver_sample_loop drives its forward step by step; the Perceiver has
-    all three methods"""
+def test_only_the_perceiver_cdm_has_the_native_loop(monkeypatch):
+    """a non-Perceiver CDM has no native loop, so dpm_solver_sample_loop drives its forward step by step; the Perceiver's names both
+    keywords"""
     from afm import base
     from afm.config import load_config
+    from afm.diffusion import _takes
     cfg = lambda *extra: load_config("text_to_motion_contact_gen", "cdm", ["model.input_feats=6", "model.scene_model.use_scene_model=False", *extra])
     for arch in ("MLP", "PointTrans"):
         m = base.create_model(cfg(f"model.arch={arch}", "task.dataset.num_points=1024"), device="cpu")
-        assert m.arch == arch and m.afm_native_loop is None and m.afm_native_impute_loop is None and m.afm_native_dpm_loop is None
-
-        class Stop(Exception):
-            pass
-
-        def stop(*a, **k):
-            raise Stop
-        monkeypatch.setattr(m, "forward", stop)
-        with pytest.raises(Stop):
-            _diffusion(500, "ddim5").dpm_solver_sample_loop(m, (1, 1024, 6), noise=torch.zeros(1, 1024, 6), clip_denoised=False)
+        assert m.arch == arch and m.afm_native_loop is None
+        samples_step_by_step(monkeypatch, m, lambda: _diffusion(500, "ddim5").dpm_solver_sample_loop(m, (1, 1024, 6), noise=torch.zeros(1, 1024, 6),
+                                                                                                     clip_denoised=False))
     p = base.create_model(cfg("model.arch=Perceiver"), device="cpu")
-    assert all(callable(getattr(p, n)) for n in ("afm_native_loop", "afm_native_impute_loop", "afm_native_dpm_loop"))
+    assert callable(p.afm_native_loop) and _takes(p.afm_native_loop, "impute") and _takes(p.afm_native_loop, "dpm_order")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the twins

@@ -1,5 +1,5 @@
 """Imputation of known contact values in the CDM's native loops, on the host (no GPU): the C ABI declares and exports the new entry and
-refuses a `known` without a `mask`; the Python surface has the second method and `contact_impute`; the reference goldens
+refuses a `known` without a `mask`; the Python surface is the one native loop with ``impute=`` and `contact_impute`; the reference goldens
 (tools/make_goldens_cdm_impute.py) are self-consistent; the CPU oracle's CDM wrapped with the same select reproduces them.  The float64
 twins of those loops are built here for tests/test_gpu_cdm_impute.py to import."""
 import ctypes
@@ -120,51 +120,86 @@ def test_entry_refuses_a_known_without_a_mask():
     assert getattr(lib, ENTRY)(*args) == -1       # neither: the existing loop's checks
 
 
-def test_python_surface():
+LOOP_PARAMS = ["self", "diffusion", "x", "model_kwargs", "step_noise", "seed", "sample_index0", "progress", "snapshots", "clip_denoised",
+               "ddim_eta", "impute", "dpm_order"]
+LOOP_DEFAULTS = dict(step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None, clip_denoised=False, ddim_eta=None, impute=None,
+                     dpm_order=None)
+
+
+def check_one_native_loop():
+    """The CDM's native-loop surface (tests/test_cdm_dpm_host.py pins the same): one method with the CMDM's protocol, found by
+    `_sample_loop` through its keywords, and no second or third one."""
     from afm.cdm import CDM
-    from afm.diffusion import GaussianDiffusion, Impute, _takes_impute
+    from afm.cmdm import CMDM
+    from afm.diffusion import GaussianDiffusion, _takes
+    loop = inspect.signature(CDM.afm_native_loop).parameters
+    assert list(loop) == LOOP_PARAMS                                             # the old eleven names, then impute, dpm_order
+    for name in LOOP_PARAMS[:4]:
+        assert loop[name].kind is inspect.Parameter.POSITIONAL_OR_KEYWORD and loop[name].default is inspect.Parameter.empty, name
+    for name in LOOP_PARAMS[4:]:                  # everything after model_kwargs: keyword-only, with these defaults
+        assert loop[name].kind is inspect.Parameter.KEYWORD_ONLY, name
+        assert repr(loop[name].default) == repr(LOOP_DEFAULTS[name]), name
+    cmdm = {k: v for k, v in inspect.signature(CMDM.afm_native_loop).parameters.items() if k != "_guidance"}
+    assert sorted(loop) == sorted(cmdm)
+    for name, par in cmdm.items():                # name for name, kind for kind, default for default
+        assert loop[name].kind is par.kind and repr(loop[name].default) == repr(par.default), name
+    assert _takes(CDM.afm_native_loop, "impute") and _takes(CDM.afm_native_loop, "dpm_order")
+    src = inspect.getsource(GaussianDiffusion._sample_loop)
+    for gone in ("afm_native_impute_loop", "afm_native_dpm_loop"):
+        assert not hasattr(CDM, gone) and gone not in src, gone
+
+
+def test_python_surface():
+    from afm.diffusion import Impute
     from afm.pipeline import two_stage_sample
-    loop, imp = inspect.signature(CDM.afm_native_loop), inspect.signature(CDM.afm_native_impute_loop)
-    assert list(loop.parameters) == ["self", "diffusion", "x", "model_kwargs", "step_noise", "seed", "sample_index0", "progress", "snapshots",
-                                     "clip_denoised", "ddim_eta"]
-    assert not _takes_impute(CDM.afm_native_loop)
-    assert list(imp.parameters) == ["self", "diffusion", "x", "model_kwargs", "impute"] + list(loop.parameters)[4:]
-    for name in list(loop.parameters)[4:]:        # the same keywords, keyword-only, with the same defaults
-        assert imp.parameters[name].kind is inspect.Parameter.KEYWORD_ONLY and imp.parameters[name].default == loop.parameters[name].default
+    check_one_native_loop()
     ts = inspect.signature(two_stage_sample).parameters
     assert ts["contact_impute"].default is None and ts["motion_impute"].default is None
     assert "normalised contact" in two_stage_sample.__doc__ and "[B, N, J]" in Impute.__doc__
-    assert "afm_native_impute_loop" in inspect.getsource(GaussianDiffusion._sample_loop)
 
 
 class _Recorder(torch.nn.Module):
-    """a denoiser with both native loops, recording which one a sampling call reaches"""
-    def __init__(self, with_impute_loop=True):
+    """a denoiser with the one native loop, recording what a sampling call hands it (tests/test_cdm_dpm_host.py imports it)"""
+    def __init__(self):
         super().__init__()
         self.p = torch.nn.Parameter(torch.zeros(1))
         self.calls = []
-        if not with_impute_loop:
-            self.afm_native_impute_loop = None
 
     def forward(self, x, t, **kw):
         self.calls.append("forward")
         return x
 
     def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
+                        clip_denoised=False, ddim_eta=None, impute=None, dpm_order=None):
+        self.calls.append((impute, clip_denoised, ddim_eta, dpm_order, seed, sample_index0, progress, snapshots, step_noise is None))
+        return x
+
+
+class _NarrowRecorder(_Recorder):
+    """a denoiser whose native loop names neither ``impute`` nor ``dpm_order``"""
+    def afm_native_loop(self, diffusion, x, model_kwargs, *, step_noise=None, seed=0, sample_index0=0, progress=False, snapshots=None,
                         clip_denoised=False, ddim_eta=None):
-        self.calls.append(("loop", clip_denoised, ddim_eta))
-        return x
-
-    def afm_native_impute_loop(self, diffusion, x, model_kwargs, impute, *, step_noise=None, seed=0, sample_index0=0, progress=False,
-                               snapshots=None, clip_denoised=False, ddim_eta=None):
-        self.calls.append(("impute", impute, clip_denoised, ddim_eta))
+        self.calls.append("narrow loop")
         return x
 
 
-def test_sample_loop_routes_an_impute_to_the_second_method(monkeypatch):
-    from afm import ops
+class Stop(Exception):
+    pass
+
+
+def samples_step_by_step(monkeypatch, model, sample):
+    """``sample()`` reaches the denoiser's forward (stopped there) and never its native loop"""
+    def stop(*a, **k):
+        raise Stop
+    monkeypatch.setattr(model, "forward", stop)
+    with pytest.raises(Stop):
+        sample()
+    assert getattr(model, "calls", []) == []
+
+
+def test_sample_loop_hands_an_impute_to_the_native_loop(monkeypatch):
     from afm.diffusion import Impute
-    d = _diffusion(500, "ddim5")
+    d, seeds = _diffusion(500, "ddim5"), _diffusion(500, "ddim5")
     shape = (2, 4, 6)
     imp = Impute(torch.zeros(shape), torch.ones(shape, dtype=torch.bool))
     xT = torch.zeros(shape)
@@ -172,20 +207,34 @@ def test_sample_loop_routes_an_impute_to_the_second_method(monkeypatch):
     d.p_sample_loop(m, shape, noise=xT, clip_denoised=True, denoised_fn=imp)
     d.ddim_sample_loop(m, shape, noise=xT, clip_denoised=False, denoised_fn=imp, eta=0.5)
     d.p_sample_loop(m, shape, noise=xT, clip_denoised=False)
-    assert m.calls == [("impute", imp, True, None), ("impute", imp, False, 0.5), ("loop", False, None)]
+    s = [seeds._fresh_seed("_sample_calls") for _ in range(3)]                  # no seed given: the diffusion's own, call by call
+    assert m.calls == [(imp, True, None, None, s[0], 0, False, None, True), (imp, False, 0.5, None, s[1], 0, False, None, True),
+                       (None, False, None, None, s[2], 0, False, None, True)]
     with pytest.raises(ValueError):               # impute.check(x) first
         d.p_sample_loop(m, (2, 5, 6), noise=torch.zeros(2, 5, 6), denoised_fn=imp)
-    # any other callable, and a denoiser whose second method is None, sample step by step (stopped at the first denoiser call)
-    class Stop(Exception):
-        pass
+    assert len(m.calls) == 3
+    # any other callable, and an Impute on a denoiser whose loop does not name ``impute``, sample step by step
+    for model, fn in ((_Recorder(), lambda x0: x0), (_NarrowRecorder(), imp)):
+        samples_step_by_step(monkeypatch, model, lambda: d.p_sample_loop(model, shape, noise=xT, clip_denoised=False, denoised_fn=fn))
+    narrow = _NarrowRecorder()                    # (which still samples natively without one)
+    d.p_sample_loop(narrow, shape, noise=xT, clip_denoised=False)
+    assert narrow.calls == ["narrow loop"]
 
-    def stop(*a, **k):
-        raise Stop
-    for model, fn in ((_Recorder(), lambda x0: x0), (_Recorder(with_impute_loop=False), imp)):
-        monkeypatch.setattr(model, "forward", stop)
-        with pytest.raises(Stop):
-            d.p_sample_loop(model, shape, noise=xT, clip_denoised=False, denoised_fn=fn)
-        assert model.calls == []
+
+def test_native_loop_refuses_early():
+    """before anything touches the library: on CPU tensors"""
+    from afm import base
+    from afm.config import load_config
+    from afm.diffusion import Impute
+    cdm = base.create_model(load_config("text_to_motion_contact_gen", "cdm", ["model.input_feats=6", "model.scene_model.use_scene_model=False",
+                                                                                "model.arch=Perceiver"]), device="cpu")
+    d, x, kw = _diffusion(500, "ddim5"), torch.zeros(2, 4, 6), {}
+    with pytest.raises(ValueError, match="neither ddim_eta nor step_noise"):
+        cdm.afm_native_loop(d, x, kw, dpm_order=2, ddim_eta=0.0)
+    with pytest.raises(ValueError, match="neither ddim_eta nor step_noise"):
+        cdm.afm_native_loop(d, x, kw, dpm_order=2, step_noise=torch.zeros(5, 2, 4, 6))
+    with pytest.raises(ValueError, match="sample is"):
+        cdm.afm_native_loop(d, x, kw, impute=Impute(torch.zeros(2, 5, 6), torch.ones(2, 5, 6, dtype=torch.bool)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- goldens

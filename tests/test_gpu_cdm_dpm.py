@@ -1,4 +1,4 @@
-"""`-m gpu`: DPM-Solver++(2M) sampling inside the CDM's native loops (CDM.afm_native_dpm_loop, afm_cdm_dpm_loop_range).
+"""`-m gpu`: DPM-Solver++(2M) sampling inside the CDM's native loops (CDM.afm_native_loop with dpm_order=, afm_cdm_dpm_loop_range).
 
 Bit for bit: the default (row-less) form - update, imputation select and the history of the previous step's final pred_xstart fused into
 dec_point (dec_point_dpm_kernel) - against the step-by-step loop (CDM.forward, the Impute, the clamp, afm_dpm_step per step), sliced one

@@ -1,4 +1,4 @@
-"""`-m gpu`: imputation of known contact values inside the CDM's native loops (CDM.afm_native_impute_loop, afm_cdm_impute_loop_range).
+"""`-m gpu`: imputation of known contact values inside the CDM's native loops (CDM.afm_native_loop with impute=, afm_cdm_impute_loop_range).
 
 Bit for bit: the default (row-less) form against the step-by-step loop with the same afm.diffusion.Impute - the select fused into
 dec_point's update, the DDPM update uncontracted - and against itself over sub-batches, the pipelined and chain-side forms, slices and

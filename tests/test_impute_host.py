@@ -241,11 +241,11 @@ def test_sampling_entry_points_take_the_imputation():
     from afm.base import create_gaussian_diffusion, create_model
     from afm.cdm import CDM
     from afm.cmdm import CMDM, GuidedCMDM
-    from afm.diffusion import _takes_impute
+    from afm.diffusion import _takes
     from afm.pipeline import two_stage_sample
     from test_cfg_host import _cfg
     assert inspect.signature(two_stage_sample).parameters["motion_impute"].default is None
-    assert _takes_impute(CMDM.afm_native_loop) and _takes_impute(GuidedCMDM.afm_native_loop) and not _takes_impute(CDM.afm_native_loop)
+    assert all(_takes(cls.afm_native_loop, "impute") for cls in (CMDM, GuidedCMDM, CDM))
     # shape and device are checked against x before the native loop is entered
     m, d = create_model(_cfg(), device="cpu").eval(), create_gaussian_diffusion(_cfg())
     imp = Impute(impute_known(), impute_mask())

@@ -70,7 +70,7 @@ def _models(dev, lib=None):
     synth.fill_module_(cdm)
     cdm = cdm.to(dev).eval()
     if lib:
-        cdm.afm_native_dpm_loop = None            # the parent's route: dpm_solver_sample_loop samples the CDM step by step
+        cdm.afm_native_loop = None                # the parent's route: dpm_solver_sample_loop samples the CDM step by step (this worker runs "dpm++" only)
     cmdm = create_model(mcfg(RESP), device=dev)
     synth.fill_module_(cmdm)
     cmdm = cmdm.to(dev).eval()
