@@ -139,7 +139,9 @@ def linear_pair(first: dict, second: dict) -> Tuple[torch.Tensor, torch.Tensor]:
 # The library itself has no switch and reads no environment (ABI v3).  Two settings:
 #   sampling / inference operators (`linear`, `mha`, the CMDM / CDM weight packs): AFM_GEMM_SPLIT / AFM_GEMM_SPLIT_MIN_N in the environment of the
 #     Python process, else SIX products of the three-way bf16 operand split on every eligible GEMM and in the attention (round 6: the
-#     worst-case comparison of tests/test_gpu_arith.py - six products are never above nine and both sit in the error class of an f32 chain);
+#     worst-case comparison of tests/test_gpu_arith.py for the GEMMs - six products are never above nine and both sit in the error class of
+#     an f32 chain; for the attention the value families of tests/test_gpu_attention_edges.py, profiles/attention_edges_parity.json - large and
+#     near-tied logits, wide-range V, the worst-mantissa operands: six and nine products within 1.7 x the float32 reference's own error);
 #   training operators (afm.autograd: every forward and backward GEMM of the tape): AFM_GEMM_SPLIT_TRAIN, else all NINE products (exact f32
 #     products) - gradients through ~40 serial batch-statistics BatchNorms are ill-conditioned in float32 (the reference's own f32 backward sits
 #     2.8e-2 from its f64 backward on the CDM's PointTrans U-Net), so the tape keeps every bit the operands carry.
