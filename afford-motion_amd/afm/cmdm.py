@@ -541,8 +541,11 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         pred_xstart before the clamp, inside the loop's update launch (afm_cmdm_impute_loop_range, all four forms).  ``dpm_order`` (1 or
         2) not None: dpm_solver_sample_loop instead (afm_cmdm_dpm_loop_range, every form: the eta = 0 DDIM loop's launches with the
         DPM-Solver++ update and one history buffer per sub-batch in the workspace; no noise: ``step_noise`` is refused, ``seed`` unused;
-        sliced chains stay bit-identical because every range call of one chain runs on the same workspace).  ``_guidance``:
-        GuidedCMDM's (afm_cfg_args or afm_cfg2_args, branch streams?) (the guided loops; not a caller's argument)."""
+        sliced chains stay bit-identical because every range call of one chain runs on the same workspace).  ``_guidance``: what only this
+        denoiser's loops take (not a caller's argument; the public keywords are the CDM's, name for name): GuidedCMDM's (afm_cfg_args or
+        afm_cfg2_args or None, branch streams?) and, as an optional third entry, an afm.diffusion.ContactGuidance - its gradient at every guided step's x_t is computed on the sub-batch's stream (two launches) and
+        enters the loop's update launch (afm_cmdm_guide_loop_range, every form; the loop runs in the separate-update form like an
+        imputing one; steps before the guidance starts launch what an imputing loop of that form launches)."""
         if any(k in model_kwargs for k in COND_SWITCHES):
             raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
                                       "p_sample_loop samples them step by step (p_sample_loop_progressive)")
@@ -558,6 +561,13 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             w = self._weights()
             if clip_denoised:
                 w.flags |= ffi.CMDM_CLIP_X0                  # per call: _stamp() rewrites the flags on the next _weights()
+            cfg, branch_streams, contact_guide = (tuple(_guidance) + (None,))[:3] if _guidance is not None else (None, False, None)
+            cguide = guide_keep = None
+            if contact_guide is not None:
+                cguide, guide_fm, guide_keep = contact_guide.describe(x, model_kwargs)
+                cguide.frame_mask = ffi.ptr(guide_fm)          # the guidance masks by x_mask also where the model does not (mask_motion=False)
+                cguide.first_guided = contact_guide.first_guided(diffusion)
+                gk_rows = diffusion.guidance_rows(x.device, "mean" if ddim_eta is None and dpm_order is None else "x0", B)
             cond = self.condition_tokens(**model_kwargs)
             if tuple(cond.shape[:2]) != (B, w.n_cond):       # (e.g. a cloud of fewer points than contact_model.num_points: the loop reads n_cond rows per sample)
                 raise ValueError(f"the conditions give {tuple(cond.shape[:2])} tokens, the model's layout has ({B}, {w.n_cond})")
@@ -569,7 +579,6 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             self._side_streams = ffi.stream_pool(x.device, nsub)          # process-wide pool (hardware queues are few: ffi.stream_pool)
             handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in self._side_streams[:nsub]])
             # _guidance (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)
-            cfg, branch_streams = _guidance if _guidance is not None else (None, False)
             two = isinstance(cfg, ffi.Cfg2Args)             # one scale per condition: three branches (afm_cmdm_cfg2_loop_range)
             if two and branch_streams:
                 raise ValueError("branch streams are not built for the two-scale guided loop (three branches)")
@@ -593,7 +602,12 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             # the entry and what it takes behind its rows.  ``every_form``: an entry that runs both updates - both kinds of rows, then cfg or
             # NULL, known and mask or NULLs
             every_form = False
-            if tables.dpm is not None:          # every form; a size of its own: the history buffers, which cross the range calls of a chain
+            if cguide is not None:              # every form; a size of its own: the gradient buffers (and always a history buffer)
+                entry = "afm_cmdm_guide_loop_range"
+                guide_cfg = (None if two else cfg_ref, cfg_ref if two else None)
+                guide_tail = guide_cfg + ffi.impute_ptrs(impute) + (C.byref(cguide),)
+                sizer, size_args, form = "afm_cmdm_guide_loop_workspace_bytes", guide_cfg + (C.byref(cguide),), ("guide", form, cguide.K, cguide.N)
+            elif tables.dpm is not None:          # every form; a size of its own: the history buffers, which cross the range calls of a chain
                 entry, guide = "afm_cmdm_dpm_loop_range", (None if two else cfg_ref, cfg_ref if two else None) + ffi.impute_ptrs(impute)
                 sizer, size_args, form = "afm_cmdm_dpm_loop_workspace_bytes", guide[:2], ("dpm", form)
             elif two or impute is not None:
@@ -611,7 +625,12 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
-                if tables.dpm is not None:      # no noise, no seed
+                if cguide is not None:          # both kinds of rows and the 2M rows, one of the three set; the gk rows of the slice
+                    cguide.gk = gk_rows[lo:].data_ptr()
+                    rows = (None, tables.dpm_rows(lo), None, None, None) if tables.dpm is not None else \
+                        (lambda r: (r[0], None) + r[1:])(tables.rows(lo, True))
+                    steps = (nz, tables.tmap(lo), *rows, *guide_tail, j1 - j0, j0, seed & (2**64 - 1), sample_index0)
+                elif tables.dpm is not None:      # no noise, no seed
                     steps = (tables.tmap(lo), tables.dpm_rows(lo), *guide, j1 - j0, j0)
                 else:
                     steps = (nz, tables.tmap(lo), *tables.rows(lo, every_form), *guide, j1 - j0, j0, seed & (2**64 - 1), sample_index0)
@@ -619,7 +638,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (tables.keep(), step_noise, cond, fm, _guidance, impute)
+            self._last_loop_scratch = (tables.keep(), step_noise, cond, fm, _guidance, impute, guide_keep)
         return x
 
 
@@ -749,13 +768,14 @@ class GuidedCMDM(nn.Module):
     def forward(self, x, timesteps, **kwargs):
         return self.branches(x, timesteps, **kwargs)[-1]
 
-    def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, dpm_order: Optional[int] = None, **kw):
+    def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, dpm_order: Optional[int] = None, contact_guide=None, **kw):
         """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range; with ``impute``: the guided form of
         afm_cmdm_impute_loop_range; one scale per condition: afm_cmdm_cfg2_loop_range, every form; ``dpm_order``: the guided forms of
-        afm_cmdm_dpm_loop_range): CMDM.afm_native_loop's arguments."""
+        afm_cmdm_dpm_loop_range; ``contact_guide``: the guided forms of afm_cmdm_guide_loop_range): CMDM.afm_native_loop's arguments."""
         self._no_switches(model_kwargs)
         if self.model.training:
             raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
         cfg = self._cfg(x.shape[0], x.device)          # (a [B] scale of the wrong length is refused here)
         ffi.require_gpu(x)
-        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams), impute=impute, dpm_order=dpm_order, **kw)
+        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams, contact_guide), impute=impute,
+                                          dpm_order=dpm_order, **kw)

@@ -188,6 +188,25 @@ class Cfg2StepArgs(C.Structure):
                 ("ddim", C.POINTER(DdimRows)), ("clip", i32), ("B", i32), ("per_sample", i64), ("seed", u64), ("sample_index0", i64), ("step", i32)]
 
 
+class GuideStepArgs(C.Structure):
+    """afm_guide_step_args (v7-additive): one sampling update with every optional ingredient - branches, known / mask, grad / gk."""
+    _fields_ = [("x0_c", c_f32p), ("x0_a", c_f32p), ("x0_u", c_f32p), ("scale", c_f32p), ("scale2", c_f32p), ("known", c_f32p),
+                ("mask", C.c_void_p), ("grad", c_f32p), ("gk", c_f32p), ("x_t", c_f32p), ("noise", c_f32p), ("x_next", c_f32p),
+                ("x0_out", c_f32p), ("c1", c_f32p), ("c2", c_f32p), ("sigma", c_f32p), ("ddim", C.POINTER(DdimRows)),
+                ("dpm", C.POINTER(DpmRows)), ("x0_prev", c_f32p), ("clip", i32), ("B", i32), ("per_sample", i64), ("seed", u64),
+                ("sample_index0", i64), ("step", i32)]
+
+
+GUIDE_MAX_JOINTS = 16
+
+
+class ContactGuide(C.Structure):
+    """afm_contact_guide (v7-additive): the contact-guidance description - scene points, target map, columns, de-normalisation, scale, and
+    for the loops the gk rows [T][B] and the first guided executed step."""
+    _fields_ = [("q", c_f32p), ("c", c_f32p), ("mean", c_f32p), ("std", c_f32p), ("scale", c_f32p), ("gk", c_f32p),
+                ("frame_mask", C.c_void_p), ("cols", i32 * GUIDE_MAX_JOINTS), ("K", i32), ("N", i32), ("sigma", C.c_double), ("first_guided", i32), ("t_start", i64)]
+
+
 CFG_FORCE_MASKED = 0x1
 
 EXPORTS = {
@@ -248,6 +267,16 @@ EXPORTS = {
     "afm_cmdm_dpm_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.POINTER(DpmRows), C.POINTER(CfgArgs),
                                           C.POINTER(Cfg2Args), c_f32p, C.c_void_p, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                           C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_guide_step": (C.c_int, [C.POINTER(GuideStepArgs), C.c_void_p]),
+    "afm_contact_guidance_workspace_bytes": (i64, [i32, i32, i32]),
+    "afm_contact_guidance": (C.c_int, [C.POINTER(ContactGuide), c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, i32, i32, i32, C.c_void_p, i64,
+                                       C.c_void_p]),
+    "afm_cmdm_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
+                                                  C.POINTER(ContactGuide)]),
+    "afm_cmdm_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                            C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p, C.c_void_p,
+                                            C.POINTER(ContactGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                            C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

@@ -460,6 +460,100 @@ def impute_step(x0: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, x_t: 
     return out
 
 
+def guide_step(x0: torch.Tensor, x_t: torch.Tensor, noise: Optional[torch.Tensor], *, grad: Optional[torch.Tensor] = None,
+               gk: Optional[torch.Tensor] = None, x0_a: Optional[torch.Tensor] = None, x0_u: Optional[torch.Tensor] = None,
+               scale: Optional[torch.Tensor] = None, scale2: Optional[torch.Tensor] = None, known: Optional[torch.Tensor] = None,
+               mask: Optional[torch.Tensor] = None, ddpm=None, ddim=None, dpm=None, prev: Optional[torch.Tensor] = None, clip: bool = False,
+               seed: int = 0, sample_index0: int = 0, step: int = 0, out: Optional[torch.Tensor] = None,
+               x0_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One sampling update with a cond_fn gradient (afm_guide_step): x0 (with ``x0_u`` / ``scale``: cfg_combine; with ``x0_a`` / ``scale2``
+    too: cfg2_combine), impute with ``known`` / ``mask``, the clamp to [-1, 1] if ``clip``, then with ``grad`` [B, ...] and its per-sample
+    coefficient ``gk`` [B] (both or neither), in float32 with every operation rounded on its own:
+
+        ddim= (a, b, c, d, sigma | None) or dpm= (a, b, c) with ``prev``:   m = gk[b] * grad;  x0' = x0 + m;  the ddim_step / dpm_step
+                                                                             expression on x0' (``x0_out``, if given, receives x0')
+        ddpm= (c1, c2, sigma):                                              m = gk[b] * grad;  x_next = ((c1*x0 + c2*x_t) + m) + sigma*noise
+
+    Without ``grad`` nothing of it is read and the result is cfg_step / impute_step / cfg2_step / ddpm_step / ddim_step / dpm_step of
+    the same arguments, bit for bit.  noise None: Philox.  ``out`` may be ``x_t``."""
+    if sum(r is not None for r in (ddpm, ddim, dpm)) != 1:
+        raise ValueError("guide_step: exactly one of ddpm= / ddim= / dpm= rows")
+    if (known is None) != (mask is None):
+        raise ValueError("guide_step: known= and mask= go together")
+    lib = ffi.load()
+    ffi.require_gpu(x0, x_t, grad, prev)
+    x0, x_t = ffi.f32c(x0), ffi.f32c(x_t)
+    B = x0.shape[0]
+    out = torch.empty_like(x0) if out is None else out
+    a = ffi.GuideStepArgs()
+    keep = []
+
+    def same(name, t):
+        t = ffi.f32c(t)
+        if t.shape != x0.shape:
+            raise ValueError(f"guide_step: {name} {tuple(t.shape)} must have x0's shape {tuple(x0.shape)}")
+        keep.append(t)
+        return t.data_ptr()
+
+    def row(name, t):
+        t = ffi.f32c(t)
+        if t.numel() != B:
+            raise ValueError(f"guide_step: {name} must hold one value per sample ({B}), got {tuple(t.shape)}")
+        keep.append(t)
+        return t.data_ptr()
+    a.x0_c = x0.data_ptr()
+    if x_t.shape != x0.shape:
+        raise ValueError(f"guide_step: x_t {tuple(x_t.shape)} must have x0's shape {tuple(x0.shape)}")
+    for name, t in (("x0_a", x0_a), ("x0_u", x0_u), ("known", known), ("grad", grad), ("x0_prev", prev)):
+        if t is not None:
+            setattr(a, name, same(name, t))
+    for name, t in (("scale", scale), ("scale2", scale2), ("gk", gk)):
+        if t is not None:
+            setattr(a, name, row(name, t))
+    if mask is not None:
+        mask = _mask_u8(mask)
+        if mask.shape != x0.shape:
+            raise ValueError(f"guide_step: mask {tuple(mask.shape)} must have x0's shape {tuple(x0.shape)}")
+        a.mask = mask.data_ptr()
+    if x0_out is not None:
+        if x0_out.dtype != torch.float32 or x0_out.shape != x0.shape or not x0_out.is_contiguous() or x0_out.device != x0.device:
+            raise ValueError(f"guide_step: x0_out must be a contiguous float32 tensor of x0's shape {tuple(x0.shape)} on {x0.device}")
+        a.x0_out = x0_out.data_ptr()
+    if dpm is not None:
+        rows = [ffi.f32c(r) for r in dpm]
+        drows = ffi.DpmRows(*[r.data_ptr() for r in rows])
+        a.dpm = C.pointer(drows)
+        keep += rows + [drows]
+        a.x_t, a.x_next = x_t.data_ptr(), out.data_ptr()
+        a.clip, a.B, a.per_sample = int(bool(clip)), B, x0.numel() // max(B, 1)
+    else:
+        keep += _step_tail(a, x0, x_t, out, noise, ddpm, ddim, clip, seed, sample_index0, step)
+    ffi.check(lib.afm_guide_step(C.byref(a), ffi.stream_of(x0)), "afm_guide_step")
+    return out
+
+
+def contact_guidance(guide: "ffi.ContactGuide", x: torch.Tensor, frame_mask: Optional[torch.Tensor], t: Optional[torch.Tensor] = None, *,
+                     grad: bool = True, energy: bool = False):
+    """afm_contact_guidance of a filled description (afm.diffusion.ContactGuidance builds it): -> (grad [B, L, D] or None, energy [B] or
+    None) of x [B, L, D]; ``frame_mask`` [B, L] (True / nonzero = padded) or None; ``t`` [B] int64 (samples with t >= guide.t_start get a
+    zero gradient) or None.  Two launches, no atomics; the workspace is allocated per call."""
+    lib = ffi.load()
+    ffi.require_gpu(x, frame_mask, t)
+    x = ffi.f32c(x)
+    B, L, D = x.shape
+    fm = None if frame_mask is None else _mask_u8(frame_mask.reshape(B, L))
+    tt = None if t is None else t.to(dtype=torch.int64).contiguous()
+    g = torch.empty_like(x) if grad else None
+    e = torch.empty(B, dtype=torch.float32, device=x.device) if energy else None
+    nbytes = int(lib.afm_contact_guidance_workspace_bytes(B, guide.N, guide.K))
+    if nbytes < 0:
+        ffi.check(nbytes, "afm_contact_guidance_workspace_bytes")
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ffi.check(lib.afm_contact_guidance(C.byref(guide), x.data_ptr(), ffi.ptr(fm), ffi.ptr(tt), ffi.ptr(g), ffi.ptr(e), B, L, D, ws.data_ptr(),
+                                       ws.numel(), ffi.stream_of(x)), "afm_contact_guidance")
+    return g, e
+
+
 def cfg2_combine(x0_c: torch.Tensor, x0_a: torch.Tensor, x0_u: torch.Tensor, scale_first: torch.Tensor, scale_second: torch.Tensor, *,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Two-scale guidance of an x_start prediction (afm_cfg2_combine): (x0_u + scale_first[b] * (x0_a - x0_u)) + scale_second[b] *

@@ -22,7 +22,7 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
                      adm_noise: Optional[Dict[str, torch.Tensor]] = None,
                      amdm_noise: Optional[Dict[str, torch.Tensor]] = None, sampler: str = "ddpm",
                      eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None,
-                     contact_impute=None) -> Dict[str, torch.Tensor]:
+                     contact_impute=None, contact_guidance=None) -> Dict[str, torch.Tensor]:
     """text_feat [B, text_dim], xyz [B, N, 3] (B = scenes x k_sample, already flattened) ->
     {"contact": [B, N, J] ADM sample, "cond": [B, N, J] AMDM condition, "motion": [B, frames, D]}.
 
@@ -39,7 +39,9 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     ``contact_impute`` / ``motion_impute``: an afm.diffusion.Impute handed to stage 1 / stage 2 as ``denoised_fn`` (both stay in their native
     loops).  The contact stage is the one to steer: ``contact_impute.known`` [B, N, J] lives in the CDM's own sample space, the
     normalised contact (exp(-d^2 / 2 sigma^2) - mean) / std - pin it on the points of a chosen object, or to the value of zero contact
-    on a region to keep clear.  ``motion_impute.known`` [B, frames, D] lives in the normalised motion space."""
+    on a region to keep clear.  ``motion_impute.known`` [B, frames, D] lives in the normalised motion space.
+    ``contact_guidance``: an afm.diffusion.ContactGuidance handed to the motion stage as ``cond_fn`` (the stage stays in its native loop):
+    the ``c_pc_contact`` it reads is the stage's own ``cond``, so the generated joints are pulled to the points the first stage marked."""
     if sampler not in ("ddpm", "ddim", "dpm++"):
         raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpm++', not {sampler!r}")
     if sampler == "dpm++" and float(eta) != 0.0:
@@ -73,5 +75,5 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
         from .cmdm import GuidedCMDM
         amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
     motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
-                  denoised_fn=motion_impute, model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
+                  denoised_fn=motion_impute, cond_fn=contact_guidance, model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
     return {"contact": contact, "cond": cond, "motion": motion}

@@ -502,6 +502,7 @@ struct LoopCall {
     const float* known = nullptr;     // imputing loop: [B][L][motion_dim] each, both set (neither: no imputation)
     const uint8_t* mask = nullptr;
     const afm_cfg2_args* cfg2 = nullptr;
+    const afm_contact_guide* guide = nullptr;      // contact-guided loop: the description of the whole batch (NULL: none)
 };
 
 struct SubBatch : SubRange {
@@ -511,10 +512,13 @@ struct SubBatch : SubRange {
     hipStream_t branch;
     hipEvent_t x_ready, u_ready;
     float* hist;                      // 2M loop only: the previous step's final x0 [count][L * motion_dim], behind every evaluation's workspace
+    float* ggrad;                     // contact-guided loop only: the step's gradient [count][L * motion_dim], behind the history, and the
+    char* gws;                        //   workspace of afm_contact_guidance for `count` samples behind it
+    int64_t gws_bytes;
 };
 
 // carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
-int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist) {
+int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist, const afm_contact_guide* guide = nullptr) {
     sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
     int64_t off = sb->ws.bytes;
     for (int i = 0; i < g.n; ++i) {
@@ -528,13 +532,22 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
         sb->hist = base ? (float*)(base + off) : nullptr;
         off += align256((int64_t)sb->count * L * w.motion_dim * 4);
     }
+    sb->ggrad = nullptr; sb->gws = nullptr; sb->gws_bytes = 0;
+    if (guide) {                      // (carved for the contact-guided loop alone)
+        sb->ggrad = base ? (float*)(base + off) : nullptr;
+        off += align256((int64_t)sb->count * L * w.motion_dim * 4);
+        sb->gws = base ? base + off : nullptr;
+        sb->gws_bytes = afm_contact_guidance_workspace_bytes(sb->count, guide->N, guide->K);
+        off += align256(sb->gws_bytes);
+    }
     return off;
 }
 
 // the loop workspace of either public description of the guidance (neither: the unguided loop's); AFM_E_BADARG as the loop itself
 int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams,
-                             bool hist = false) {
+                             bool hist = false, const afm_contact_guide* guide = nullptr) {
     if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
+    if (guide && afm_contact_guidance_workspace_bytes(B, guide->N, guide->K) < 0) return AFM_E_BADARG;
     Guidance g = {};
     if ((one || two) && make_guidance(*w, one, two, false, nullptr, &g) != 0) return AFM_E_BADARG;
     const int n = sub_count(B, n_streams, MAX_SUB);
@@ -542,7 +555,7 @@ int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one,
     for (int s = 0; s < n; ++s) {
         SubBatch sb = {};
         sub_range(B, n, s, &sb.start, &sb.count);
-        total += carve_sub(*w, g, L, nullptr, &sb, hist);
+        total += carve_sub(*w, g, L, nullptr, &sb, hist, guide);
     }
     return total;
 }
@@ -569,6 +582,10 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     if (g.n > 1 && g.branch_streams) return AFM_E_UNSUPPORTED;       // (four hardware queues do not fit 2 sub-batches x 3 evaluations)
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     if (a.dpm && (!a.ddim || a.noise_term() || a.step_noise || a.first_step < 0)) return AFM_E_BADARG;
+    if (c.guide) {
+        AFM_TRY(afm_contact_guide_check(c.guide, c.L, c.w->motion_dim));
+        if (!c.guide->gk || c.guide->first_guided < 0) return AFM_E_BADARG;
+    }
     p->nsub = 0;
     if (a.B == 0) return 0;
     p->nsub = sub_count(a.B, a.n_streams, MAX_SUB);
@@ -578,7 +595,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         SubBatch& sb = p->sb[s];
         sb = {};
         sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm);
+        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guide, c.guide);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
         if (p->branch_streams) sb.branch = (hipStream_t)g.branch_streams[s];
     }
@@ -596,7 +613,8 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     p->w = *c.w;
     p->w.flags = a.loop_flags(p->w.flags);
     // (an imputing loop likewise: the update fused into the motion_layer epilogue is contracted and has no place for the select)
-    if (g.n || c.mask) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
+    // (a contact-guided loop too: no place for the gradient term either)
+    if (g.n || c.mask || c.guide) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
     if (p->nsub >= 2 && ((p->w.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < p->nsub; ++s) big = big && (int64_t)p->sb[s].count * T >= 4096;
@@ -630,6 +648,18 @@ int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_d
     return forward_impl(l.p.w, sub_x(l, sb), rows->t, sub_cond(l, sb), sub_fmask(l, sb), nullptr, dd, sb.count, c.L, sb.ws, j == 0, sb.stream, rec);
 }
 
+// does executed step j of the call carry the contact-guidance term (a contact-guided loop, at or behind its first guided step)
+inline bool guided_step(const Loop& l, int j) { return l.c.guide && l.c.a.first_step + j >= l.c.guide->first_guided; }
+
+// the gradient of (sub-batch, step j) at the x the step's evaluations read, on the sub-batch's stream: the two launches of
+// afm_contact_guidance into the sub-batch's gradient buffer
+int guide_launch(const Loop& l, const SubBatch& sb) {
+    // (the guidance's own mask: the denoiser's frame_mask is NULL for a model that does not mask its motion tokens)
+    const uint8_t* fm = l.c.guide->frame_mask ? l.c.guide->frame_mask + (int64_t)sb.start * l.c.L : nullptr;
+    return afm_contact_guidance_sub(l.c.guide, sb.start, sub_x(l, sb), fm, nullptr, sb.ggrad, nullptr, sb.count, l.c.L, l.p.w.motion_dim,
+                                    sb.gws, sb.gws_bytes, sb.stream);
+}
+
 // the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and each branch's, wsb[i].x0 - the list's last branch is the
 // unconditioned one, a branch in front of it the middle one), in place on x, with the K-padded copy the next step reads.  2M loop: the
 // final x0 of step j is kept in the sub-batch's history, which the next step - of this call or of the next range call on the same
@@ -643,6 +673,7 @@ int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const
     if (l.c.mask) { u.known = l.c.known + (int64_t)sb.start * l.p.row; u.mask = l.c.mask + (int64_t)sb.start * l.p.row; }
     u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
     if (l.c.a.dpm) { u.x0_prev = l.c.a.first_step + j > 0 ? sb.hist : nullptr; u.x0_keep = sb.hist; }
+    if (guided_step(l, j)) { u.grad = sb.ggrad; u.gk = l.c.guide->gk + ((int64_t)(l.c.a.n_steps - 1 - j) * l.c.a.B + sb.start); }
     return afm_sampling_update(u, sb.count, sb.stream);
 }
 
@@ -653,6 +684,7 @@ int loop_step(const Loop& l, const SubBatch& sb, int j) {
     const Guidance& g = l.p.g;
     StepRows rows;
     afm_ddpm_args dd;
+    if (guided_step(l, j)) AFM_TRY(guide_launch(l, sb));
     AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
     for (int i = 0; i < g.n; ++i) {
         // every branch behind the conditioned evaluation on the sub-batch's stream, on its own workspace - but the last one on the branch
@@ -672,7 +704,7 @@ int loop_step(const Loop& l, const SubBatch& sb, int j) {
         }
         AFM_TRY(rc);
     }
-    if (!(g.n || c.a.ddim || c.mask)) return 0;
+    if (!(g.n || c.a.ddim || c.mask || c.guide)) return 0;
     AFM_TRY(update_launch(l, sb, rows, dd.noise, j));
     if (l.p.branch_streams) (void)hipEventRecord(sb.x_ready, sb.stream);       // x and its padded copy of the next step
     return 0;
@@ -876,5 +908,33 @@ extern "C" int afm_cmdm_dpm_loop_range(const afm_cmdm_weights* w, float* x, cons
     LoopCall c = {w, x, cond_tokens, frame_mask, cfg, L, {nullptr, d_timestep_map, nullptr, nullptr, nullptr, &as_ddim, n_steps, first_step, 0, 0, B,
                   sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2};
     c.a.dpm = true;
+    return sample_loop_impl(c);
+}
+
+// The contact-guided loop, every form behind one entry: the separate-update loop of the form the rows and the guidance name, with the two
+// gradient launches in front of a guided step's evaluations and grad / gk in its update launch.  A 2M history buffer is always carved, so
+// every form shares one workspace layout.
+extern "C" int64_t afm_cmdm_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                       const afm_cfg2_args* cfg2, const afm_contact_guide* guide) {
+    if ((cfg && cfg2) || !guide) return AFM_E_BADARG;
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, guide);
+}
+
+extern "C" int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                         const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                         const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                         const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_contact_guide* guide,
+                                         int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                         void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                         void* stream) {
+    if (first_step < 0 || !guide || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
+    if ((rows != nullptr) + (dpm != nullptr) + (d_c1 || d_c2 || d_sigma ? 1 : 0) != 1) return AFM_E_BADARG;          // one kind of rows
+    if (dpm && (!dpm->a || !dpm->b || !dpm->c || step_noise)) return AFM_E_BADARG;
+    if (cfg2 && (!frame_mask || !cfg2_ok(cfg2))) return AFM_E_BADARG;
+    afm_ddim_rows as_ddim = {};
+    if (dpm) { as_ddim = {dpm->a, dpm->b, dpm->c, dpm->c, nullptr}; rows = &as_ddim; }          // (d: any valid row, never used by dpm_update)
+    LoopCall c = {w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, dpm ? 0 : seed,
+                  dpm ? 0 : sample_index0, B, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2, guide};
+    c.a.dpm = dpm != nullptr;
     return sample_loop_impl(c);
 }

@@ -50,11 +50,29 @@ __global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __r
 // bit for bit).  xn may alias xt (one thread reads then writes an element).  noise == NULL with a noise term: Philox keyed by the quad q.
 // xpad: x_next also into rows of ldpad floats (the next motion-adapter GEMM's K-padded A rows; columns >= cols stay zero).
 // dpm: dpm_update on the rows {a, b, c} instead (x0_prev NULL: its two-term form), v - the final x0 - also stored to x0_keep when asked.
+// grad (cond_fn guidance, with its per-sample coefficient gk), float32, each operation rounded on its own:
+//   DDIM / 2M:  m = gk[b] * grad;  v = v + m          after the clamp; this shifted v enters the update and is what x0_keep stores
+//   DDPM:       m = gk[b] * grad;  x_next = ((c1 * v + c2 * x_t) + m) + sg * noise          (guided_ddpm_update)
+// grad == NULL: the kernel computes what it computed without the term, and grad is never read.
+__device__ __forceinline__ float guided_x0(float v, float gk, float grad) {
+#pragma clang fp contract(off)
+    const float m = gk * grad;
+    return v + m;
+}
+__device__ __forceinline__ float guided_ddpm_update(float x0, float xt, float c1, float c2, float sg, float nz, float gk, float grad) {
+#pragma clang fp contract(off)
+    const float m1 = c1 * x0;
+    const float m2 = c2 * xt;
+    const float mean = guided_x0(m1 + m2, gk, grad);
+    const float sn = sg * nz;
+    return mean + sn;
+}
 __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Update p) {
     const int b = blockIdx.y;
     const float s = p.x0_u ? p.scale[b] : 0.f;
     const float s2 = p.x0_a ? p.scale2[b] : 0.f;
     const float sg = p.sg ? p.sg[b] : 0.f;
+    const float gk = p.grad ? p.gk[b] : 0.f;
     float4 r = make_float4(0.f, 1.f, 0.f, 0.f);
     float c1 = 0.f, c2 = 0.f;
     if (p.ddim) r = p.rec ? p.rec[b] : make_float4(p.ra[b], p.rb[b], p.rc[b], p.rd ? p.rd[b] : 0.f);
@@ -77,10 +95,15 @@ __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Up
                 const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
                 const float vt = p.xt[g];
                 float xn;
+                if (p.grad && p.ddim) v = guided_x0(v, gk, p.grad[g]);
                 if (p.dpm) {
                     xn = p.x0_prev ? dpm_update(v, vt, r, p.x0_prev[g]) : dpm_update(v, vt, r);
                     if (p.x0_keep) p.x0_keep[g] = v;
-                } else if (p.ddim) xn = p.sg ? ddim_update(v, vt, r, sg, nz) : ddim_update(v, vt, r);
+                } else if (p.ddim) {
+                    xn = p.sg ? ddim_update(v, vt, r, sg, nz) : ddim_update(v, vt, r);
+                    if (p.x0_keep) p.x0_keep[g] = v;
+                }
+                else if (p.grad) xn = guided_ddpm_update(v, vt, c1, c2, sg, nz, gk, p.grad[g]);
                 else xn = ddpm_update(v, vt, c1, c2, sg, nz);
                 p.xn[g] = xn;
                 if (p.xpad) {
@@ -258,7 +281,8 @@ __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Up
     if (!p.x0 || !p.xt || !p.xn || !p.x0_u != !p.scale || !p.known != !p.mask || B < 0 || p.per_sample <= 0) return AFM_E_BADARG;
     if (!p.x0_a != !p.scale2 || (p.x0_a && !p.x0_u)) return AFM_E_BADARG;          // a middle branch: both scales and the unconditioned branch
     if (p.ddim ? !(p.rec || (p.ra && p.rb && p.rc && (p.rd || p.dpm))) : !(p.c1 && p.c2 && p.sg)) return AFM_E_BADARG;
-    if (p.dpm ? (!p.ddim || p.sg) : (p.x0_prev || p.x0_keep)) return AFM_E_BADARG;          // 2M: DDIM-layout rows, no noise term; history only there
+    if (p.dpm ? (!p.ddim || p.sg) : (p.x0_prev || (p.x0_keep && !(p.ddim && p.grad)))) return AFM_E_BADARG;          // 2M: DDIM-layout rows, no noise term; history only there
+    if (!p.grad != !p.gk) return AFM_E_BADARG;          // cond_fn guidance: the gradient and its coefficient row go together
     if (p.sg && !p.noise && !p.philox) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside their launch)
     if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
     if (B == 0) return 0;
@@ -334,6 +358,21 @@ extern "C" int afm_impute_step(const afm_impute_step_args* a, void* stream) {
     if (!a || !a->x0_c || !a->known || !a->mask) return AFM_E_BADARG;
     afm_loop::Update p = args_update(a);
     p.x0_u = a->x0_u; p.scale = a->scale; p.known = a->known; p.mask = a->mask;
+    return afm_sampling_update(p, a->B, stream);
+}
+
+extern "C" int afm_guide_step(const afm_guide_step_args* a, void* stream) {
+    if (!a || !a->x0_c || !a->known != !a->mask) return AFM_E_BADARG;
+    if ((a->ddim != nullptr) + (a->dpm != nullptr) + (a->c1 || a->c2 || a->sigma ? 1 : 0) != 1) return AFM_E_BADARG;          // one kind of rows
+    if (a->dpm && !(a->dpm->a && a->dpm->b && a->dpm->c)) return AFM_E_BADARG;
+    afm_loop::Update p = step_update(a->x0_c, a->x_t, a->noise, a->x_next, a->per_sample, a->seed, a->sample_index0, a->step);
+    p.clip = a->clip ? 1 : 0;
+    if (a->ddim) set_ddim_rows(&p, a->ddim);
+    else if (a->dpm) { p.ddim = 1; p.dpm = 1; p.ra = a->dpm->a; p.rb = a->dpm->b; p.rc = a->dpm->c; p.x0_prev = a->x0_prev; p.noise = nullptr; }
+    else { p.c1 = a->c1; p.c2 = a->c2; p.sg = a->sigma; }
+    if (a->x0_prev && !a->dpm) return AFM_E_BADARG;
+    p.x0_a = a->x0_a; p.x0_u = a->x0_u; p.scale = a->scale; p.scale2 = a->scale2;
+    p.known = a->known; p.mask = a->mask; p.grad = a->grad; p.gk = a->gk; p.x0_keep = a->x0_out;
     return afm_sampling_update(p, a->B, stream);
 }
 

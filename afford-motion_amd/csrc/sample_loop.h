@@ -13,8 +13,17 @@ __attribute__((visibility("hidden"))) int afm_randn_steps(float*, int32_t, int64
 namespace afm_loop { struct Update; }
 // checks and enqueues one sampling update over B samples (AFM_E_BADARG: a NULL tensor or row, x0_u without scale or known without mask or
 // the reverse, a middle branch x0_a without both scales and x0_u, a noise term without noise unless `philox`, xpad with ldpad < cols, `dpm`
-// without DDIM-layout rows or with a noise term, x0_prev / x0_keep without `dpm`; B == 0: nothing to do)
+// without DDIM-layout rows or with a noise term, x0_prev without `dpm`, x0_keep without `dpm` or `ddim` with `grad`, grad without gk or
+// the reverse; B == 0: nothing to do)
 __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream);
+
+// guidance.hip: afm_contact_guidance on the samples [start, start + count) of the description's batch (x, frame_mask, t, grad, energy
+// already point at sample `start`; the workspace: afm_contact_guidance_workspace_bytes(count, N, K))
+__attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_contact_guide* g, int32_t start, const float* x, const uint8_t* frame_mask,
+                                                                   const int64_t* t, float* grad, float* energy, int32_t count, int32_t L, int32_t D,
+                                                                   void* workspace, int64_t workspace_bytes, void* stream);
+
+__attribute__((visibility("hidden"))) int afm_contact_guide_check(const afm_contact_guide* g, int32_t L, int32_t D);
 
 namespace afm_loop {
 
@@ -40,7 +49,10 @@ struct Update {
     int dpm;                        // DPM-Solver++(2M) update (dpm_update of common.h) on the DDIM-layout rows; `ddim` set too, no noise term
     const float* x0_prev;           // `dpm`: the previous step's final x0 [B][per_sample]; NULL: the two-term form (never read then)
     float* x0_keep;                 // `dpm`: the final x0 (after combine, select and clamp) is also stored here; NULL: not kept.  May alias
-                                    //   x0_prev (one thread reads then writes an element)
+                                    //   x0_prev (one thread reads then writes an element).  Also taken with `ddim` and `grad`: the shifted x0
+    const float *grad, *gk;         // cond_fn guidance: grad [B][per_sample] = grad log p(y | x_t), gk [B] its coefficient (DDPM: the
+                                    //   posterior variance, mean += gk * grad; DDIM / 2M: (1 - abar) / sqrt(abar), x0 += gk * grad after the
+                                    //   clamp - the shifted x0 is what x0_keep stores); both NULL: none, grad is never read
 };
 
 inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }

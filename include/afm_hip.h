@@ -830,6 +830,86 @@ int afm_cmdm_dpm_loop_range(const afm_cmdm_weights* w, float* x, const float* co
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cond_fn guidance (v7-additive).  The reference's condition_mean / condition_score (gaussian_diffusion.py:357-394): a gradient
+ * grad = d log p(y | x_t) / d x_t steers the sample.  Both rules are  target += gk[b] * grad  in the sampling update:
+ *   DDPM (condition_mean):       gk = posterior_variance[t] (unclipped, 0 at t == 0);  the target is the posterior mean:
+ *                                x_next = ((c1 * x0 + c2 * x_t) + gk * grad) + sigma * noise
+ *   DDIM / 2M (condition_score): gk = (1 - abar_t) / sqrt(abar_t);  the target is the final pred_xstart, after the guidance combine, the
+ *                                imputation select and the clamp:  x0' = x0 + gk * grad,  then the afm_ddim_step / afm_dpm_step expression
+ *                                on x0'.  x0' is what a 2M chain keeps as its history.
+ * float32, m = gk * grad rounded, then the addition rounded (no contraction).  The host builds gk in float64 and rounds it once.
+ * ------------------------------------------------------------------------------------------ */
+
+/* One sampling update with every optional ingredient: the branches of afm_cfg_step (x0_u / scale) or afm_cfg2_step (x0_a / scale2 too),
+ * known / mask of afm_impute_step, grad / gk [B][per_sample] / [B] (both or neither: AFM_E_BADARG otherwise; without them grad is never
+ * read and the result is the unguided entry's, bit for bit).  Rows: DDPM (c1, c2, sigma), or ddim, or dpm (with x0_prev or NULL) -
+ * exactly one kind.  x0_out (optional, ddim with grad or dpm only): the final pred_xstart x0'.  x_next may alias x_t. */
+typedef struct {
+    const float* x0_c; const float* x0_a; const float* x0_u;        /* [B][per_sample]; x0_a, x0_u optional                */
+    const float* scale; const float* scale2;                        /* [B]: with x0_u; scale2 with x0_a                    */
+    const float* known; const uint8_t* mask;                        /* [B][per_sample] or NULL                             */
+    const float* grad; const float* gk;                             /* [B][per_sample], [B]; both or neither               */
+    const float* x_t; const float* noise; float* x_next;            /* [B][per_sample]                                     */
+    float* x0_out;                                                  /* [B][per_sample] or NULL                             */
+    const float* c1; const float* c2; const float* sigma;           /* DDPM rows [B]                                       */
+    const afm_ddim_rows* ddim;                                      /* or DDIM rows [B]                                    */
+    const afm_dpm_rows* dpm; const float* x0_prev;                  /* or 2M rows [B] and the history (NULL: two-term)     */
+    int32_t clip; int32_t B; int64_t per_sample;
+    uint64_t seed; int64_t sample_index0; int32_t step;
+} afm_guide_step_args;
+int afm_guide_step(const afm_guide_step_args* args, void* stream);
+
+/* Contact guidance: the analytic gradient of the energy between the contact map a motion implies and the map it was given.
+ *   p[b,f,k,a] = x[b,f,cols[k]+a] * std[cols[k]+a] + mean[cols[k]+a]           (a = 0..2; absolute joint positions)
+ *   d2[b,n,k]  = min over frames f with frame_mask[b,f] == 0 of ((dx*dx + dy*dy) + dz*dz), d = p[b,f,k,:] - q[b,n,:]; f* the FIRST such f
+ *   chat       = exp(-d2 / (2 sigma^2)) (no valid frame: chat = 0);   w[b,n,k] = (chat - c[b,n,k]) * chat
+ *   energy[b]  = (sum_{n,k} (chat - c)^2) / (N K)
+ *   grad[b,f,cols[k]+a] = (scale[b] * coef * std[cols[k]+a]) * S,   S = sum_{n: f*(b,n,k) == f} w * (p_a - q_a),   coef = 2 / (N K sigma^2)
+ * which is -scale[b] * dE/dx.  grad is zero in every other column, in masked frames, in a sample without a valid frame and (t != NULL) in
+ * a sample with t[b] >= t_start.  Two launches: pass 1 per (b, k, n) with the sample's joint positions in LDS, pass 2 one wave per
+ * (b, f, k) summing its points in a fixed order (lane l takes n = l, l + 64, ...; then a fixed butterfly) - no atomics, bit-identical
+ * run to run, and a function of the sample alone (no value depends on B or on the sample's place in the batch).  The column triples must
+ * lie inside D and must not overlap; K <= AFM_GUIDE_MAX_JOINTS; K * L * 3 floats must fit the LDS (AFM_E_UNSUPPORTED). */
+#define AFM_GUIDE_MAX_JOINTS 16
+typedef struct {
+    const float* q;                        /* device [B][N][3]: the scene points                                          */
+    const float* c;                        /* device [B][N][K]: the target contact map, un-normalised exp(-d^2 / 2 sigma^2) */
+    const float* mean; const float* std;   /* device [D]: de-normalisation of the motion                                  */
+    const float* scale;                    /* device [B]                                                                  */
+    const float* gk;                       /* loops only: device [T][B], row i = the coefficient of spaced timestep i     */
+    const uint8_t* frame_mask;             /* loops only: device [B][L], nonzero = padded frame, or NULL - the guidance's own mask (x_mask),
+                                              whether or not the denoiser masks its motion tokens                          */
+    int32_t cols[AFM_GUIDE_MAX_JOINTS];    /* column of x of joint k (y, z: the next two)                                 */
+    int32_t K; int32_t N;
+    double sigma;                          /* of the contact map; 2 sigma^2 and the coefficient are formed in float64 and rounded once */
+    int32_t first_guided;                  /* loops only: executed steps (first_step + j) below it run unguided - no gradient launch */
+    int64_t t_start;                       /* afm_contact_guidance with t: samples with t[b] >= t_start get a zero gradient */
+} afm_contact_guide;
+
+/* grad [B][L][D] and / or energy [B] (either may be NULL) of x [B][L][D]; frame_mask [B][L] (nonzero = padded) or NULL; t [B] or NULL. */
+int64_t afm_contact_guidance_workspace_bytes(int32_t B, int32_t N, int32_t K);
+int afm_contact_guidance(const afm_contact_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                         float* energy, int32_t B, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The contact-guided native loop, every form behind one entry: DDPM (d_c1 / d_c2 / d_sigma), DDIM (rows) or 2M (dpm; no noise) - exactly
+ * one kind of rows; cfg or cfg2 or neither; known / mask optional (both or neither); guide required.  The loop runs in the
+ * separate-update form (as an imputing loop: the update fused into the motion_layer epilogue has no place for the term).  Per sub-batch
+ * and executed step first_step + j >= guide->first_guided, on the sub-batch's stream and in front of the evaluations, the two launches
+ * of afm_contact_guidance on the x the evaluations read, with guide->frame_mask (not the denoiser's frame_mask, which a model
+ * without motion masking does not have); the update launch takes grad and gk row n_steps - 1 - j.  Earlier steps launch
+ * what an imputing loop of the same form launches (grad NULL).  guide->q / c / scale / gk cover the whole batch.  A 2M history buffer is
+ * always carved, so chained range calls share one layout.  workspace >= afm_cmdm_guide_loop_workspace_bytes. */
+int64_t afm_cmdm_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                            const afm_cfg2_args* cfg2, const afm_contact_guide* guide);
+int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                              const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                              const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                              const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_contact_guide* guide,
+                              int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                              void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
  * CrossAttentionLayer, SelfAttentionBlock, MLP, Residual; pad mask / rotary / kv-cache never used).
