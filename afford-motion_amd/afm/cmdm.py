@@ -606,7 +606,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 entry = "afm_cmdm_guide_loop_range"
                 guide_cfg = (None if two else cfg_ref, cfg_ref if two else None)
                 guide_tail = guide_cfg + ffi.impute_ptrs(impute) + (C.byref(cguide),)
-                sizer, size_args, form = "afm_cmdm_guide_loop_workspace_bytes", guide_cfg + (C.byref(cguide),), ("guide", form, cguide.K, cguide.N)
+                sizer, size_args, form = "afm_cmdm_guide_loop_workspace_bytes", guide_cfg + (C.byref(cguide),), ("guide", form, cguide.K, cguide.N, bool(cguide.h3d))
             elif tables.dpm is not None:          # every form; a size of its own: the history buffers, which cross the range calls of a chain
                 entry, guide = "afm_cmdm_dpm_loop_range", (None if two else cfg_ref, cfg_ref if two else None) + ffi.impute_ptrs(impute)
                 sizer, size_args, form = "afm_cmdm_dpm_loop_workspace_bytes", guide[:2], ("dpm", form)

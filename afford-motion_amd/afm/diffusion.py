@@ -19,6 +19,7 @@ MI355X-first differences (results unchanged):
 """
 from __future__ import annotations
 
+import ctypes as C
 import enum
 import math
 from typing import Callable, Dict, Iterable, List, Optional, Sequence
@@ -146,8 +147,9 @@ class ContactGuidance:
     of an energy between the map the motion implies and the map it was given (afm_contact_guidance, HIP; no second network, no autograd).
 
     ``cols``: K ints (K <= 16), each the column of the x coordinate of one contact joint in the motion vector, y and z the next two
-    columns.  The columns must hold ABSOLUTE joint positions (``data_repr`` "pos" / "pos_rot": ``3 * j`` for joint j); "h3d" integrates
-    root velocities over the frames and has no such columns - it is not special-cased.  The triples lie inside D and do not overlap.
+    columns.  The columns must hold ABSOLUTE joint positions (``data_repr`` "pos" / "pos_rot": ``3 * j`` for joint j).  "h3d" has no such
+    columns - it integrates root velocities over the frames: ``ContactGuidance.h3d(joints, mean, std)`` builds the guidance for it, the
+    same energy on the joints the features imply (below).  The triples lie inside D and do not overlap.
     ``mean`` / ``std`` [D] de-normalise the motion.  ``sigma``: the contact map's.  ``scale``: a float or a [B] tensor.  ``t_start``: only
     steps whose model timestep is < t_start are guided (None: all).
 
@@ -171,7 +173,22 @@ class ContactGuidance:
     ``contact_guide`` (GuidedCMDM) or takes it in its private ``_guidance`` bundle (CMDM `trans_enc`, whose public keywords stay the
     CDM's) - afm_cmdm_guide_loop_range - the whole chain stays in the native loop; any other
     denoiser samples step by step through ``__call__``.  A skipped step natively launches no gradient kernel; step by step it adds a
-    gradient of zeros (the same values)."""
+    gradient of zeros (the same values).
+
+    HumanML3D features: ``ContactGuidance.h3d(joints, mean, std, to_scene=None, ...)`` with ``joints`` the K joint indices 0..21.  With
+    u = x * std + mean (columns 0..66 are read) and the velocity columns 0..2 of a padded frame counted as zero, p is the reference's
+    recover_from_ric placed in the scene:
+
+        th_f = sum_{g<f} u[g,0];  c_f, s_f = cos, sin(2 th_f);  X_f = sum_{1<=h<=f} (u[h-1,1] c_h - u[h-1,2] s_h),  Z_f likewise with
+        (u[h-1,1] s_h + u[h-1,2] c_h);  joint 0: P = (X_f, u[f,3], Z_f);  joint j, l = u[f, 4+3(j-1):7+3(j-1)]:
+        P = (l_x c_f - l_z s_f + X_f, l_y, l_x s_f + l_z c_f + Z_f);  p = A P + t,  to_scene = [A|t]
+
+    ``to_scene`` is a float32 [3, 4] or [B, 3, 4] tensor (None: identity).  The reference does not fix how an h3d motion is placed in
+    its scene, so the transform is an argument and not a constant; y-up to z-up is A = [[1, 0, 0], [0, 0, -1], [0, 1, 0]], t = 0.  The
+    energy is the one above on these p; the gradient is its exact adjoint through the recovery (afm_contact_guidance with an
+    afm_h3d_layout: four launches - recovery, the two passes, adjoint - every scan over the frames one lane's serial chain in frame order,
+    no atomics), nonzero only in columns 0..66 of valid frames.  Everything else - ``__call__``, ``energy``, ``first_guided``, the
+    native loops of GuidedCMDM and the plain CMDM, ``two_stage_sample(contact_guidance=...)`` - works as for the column form."""
 
     def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, sigma: float = 0.8, scale=1.0, t_start: Optional[int] = None):
         cols = [int(c) for c in cols]
@@ -197,6 +214,24 @@ class ContactGuidance:
         self.mean, self.std = ffi.f32c(mean.detach()), ffi.f32c(std.detach())
         self.t_start = None if t_start is None else int(t_start)
         self._dev: Dict[tuple, tuple] = {}
+        self.joints, self.to_scene = None, None            # (set by ContactGuidance.h3d alone)
+
+    @classmethod
+    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, to_scene: Optional[torch.Tensor] = None, sigma: float = 0.8, scale=1.0,
+            t_start: Optional[int] = None) -> "ContactGuidance":
+        """The guidance of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67): ``joints`` are joint indices 0..21, ``to_scene`` a
+        float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity).  See the class docstring."""
+        who = "ContactGuidance.h3d"
+        joints = ops.h3d_joint_list([int(j) for j in joints], ffi.GUIDE_MAX_JOINTS, who)
+        if mean.dim() != 1 or std.shape != mean.shape:
+            raise ValueError(f"{who}: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
+        if mean.shape[0] < ffi.H3D_COLS:
+            raise ValueError(f"{who}: the joint recovery reads columns 0..{ffi.H3D_COLS - 1}, the motion vector has {mean.shape[0]}")
+        to_scene = ops.h3d_to_scene(to_scene, who)
+        # (the column checks of __init__ do not apply: the layout names joints, `cols` is not read)
+        self = cls([0], mean, std, sigma=sigma, scale=scale, t_start=t_start)
+        self.cols, self.joints, self.to_scene = [], joints, to_scene
+        return self
 
     def _scale_row(self, B: int, device) -> torch.Tensor:
         if isinstance(self.scale, torch.Tensor):
@@ -212,11 +247,18 @@ class ContactGuidance:
         for name in ("c_pc_xyz", "c_pc_contact"):
             if name not in model_kwargs:
                 raise ValueError(f"ContactGuidance reads {name} from model_kwargs")
-        B, K = x.shape[0], len(self.cols)
+        B, K = x.shape[0], len(self.cols if self.joints is None else self.joints)
         q, c = model_kwargs["c_pc_xyz"], model_kwargs["c_pc_contact"]
         if q.dim() != 3 or q.shape[0] != B or q.shape[2] != 3 or tuple(c.shape) != (B, q.shape[1], K):
             raise ValueError(f"ContactGuidance: c_pc_xyz must be [{B}, N, 3] and c_pc_contact [{B}, N, {K}], got {tuple(q.shape)} and {tuple(c.shape)}")
         scale = self._scale_row(B, x.device)
+        lay = ts = None
+        if self.joints is not None:
+            ts, stride = ops.h3d_to_scene_on(self.to_scene, B, x.device, "ContactGuidance.h3d")
+            lay = ffi.H3dLayout()
+            for k, j in enumerate(self.joints):
+                lay.joints[k] = j
+            lay.to_scene, lay.to_scene_stride = ffi.ptr(ts), stride
         ffi.require_gpu(x, q, c)
         q, c = ffi.f32c(q), ffi.f32c(c)
         key = str(x.device)
@@ -235,7 +277,9 @@ class ContactGuidance:
             g.cols[k] = col
         g.K, g.N, g.sigma = K, q.shape[1], self.sigma
         g.t_start = 2**62 if self.t_start is None else self.t_start
-        return g, fm, (q, c, mean, std, scale, fm)
+        if lay is not None:
+            g.h3d = C.pointer(lay)
+        return g, fm, (q, c, mean, std, scale, fm, lay, ts)
 
     def first_guided(self, diffusion: "GaussianDiffusion") -> int:
         """the first executed step of a chain on ``diffusion`` that is guided: the count of its timesteps >= t_start"""

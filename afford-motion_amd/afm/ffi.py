@@ -198,13 +198,22 @@ class GuideStepArgs(C.Structure):
 
 
 GUIDE_MAX_JOINTS = 16
+H3D_JOINTS = 22                   # joints of the HumanML3D skeleton
+H3D_COLS = 67                     # the feature columns the joint recovery reads: 0..66
+
+
+class H3dLayout(C.Structure):
+    """afm_h3d_layout (v7-additive): the motion vector holds HumanML3D features - the joint index 0..21 of each guided joint and the
+    scene transform [3][4] (NULL: identity) with its batch stride in floats (0: one shared matrix, 12: one per sample)."""
+    _fields_ = [("joints", i32 * GUIDE_MAX_JOINTS), ("to_scene", c_f32p), ("to_scene_stride", i32)]
 
 
 class ContactGuide(C.Structure):
     """afm_contact_guide (v7-additive): the contact-guidance description - scene points, target map, columns, de-normalisation, scale, and
-    for the loops the gk rows [T][B] and the first guided executed step."""
+    for the loops the gk rows [T][B] and the first guided executed step; ``h3d``: NULL, or the layout of a HumanML3D-feature motion."""
     _fields_ = [("q", c_f32p), ("c", c_f32p), ("mean", c_f32p), ("std", c_f32p), ("scale", c_f32p), ("gk", c_f32p),
-                ("frame_mask", C.c_void_p), ("cols", i32 * GUIDE_MAX_JOINTS), ("K", i32), ("N", i32), ("sigma", C.c_double), ("first_guided", i32), ("t_start", i64)]
+                ("frame_mask", C.c_void_p), ("cols", i32 * GUIDE_MAX_JOINTS), ("K", i32), ("N", i32), ("sigma", C.c_double), ("first_guided", i32), ("t_start", i64),
+                ("h3d", C.POINTER(H3dLayout))]
 
 
 CFG_FORCE_MASKED = 0x1
@@ -271,6 +280,8 @@ EXPORTS = {
     "afm_contact_guidance_workspace_bytes": (i64, [i32, i32, i32]),
     "afm_contact_guidance": (C.c_int, [C.POINTER(ContactGuide), c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, i32, i32, i32, C.c_void_p, i64,
                                        C.c_void_p]),
+    "afm_contact_guidance_h3d_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "afm_h3d_joints": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(i32), i32, c_f32p, i32, c_f32p, i32, i32, i32, C.c_void_p]),
     "afm_cmdm_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
                                                   C.POINTER(ContactGuide)]),
     "afm_cmdm_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),

@@ -536,7 +536,7 @@ def contact_guidance(guide: "ffi.ContactGuide", x: torch.Tensor, frame_mask: Opt
                      grad: bool = True, energy: bool = False):
     """afm_contact_guidance of a filled description (afm.diffusion.ContactGuidance builds it): -> (grad [B, L, D] or None, energy [B] or
     None) of x [B, L, D]; ``frame_mask`` [B, L] (True / nonzero = padded) or None; ``t`` [B] int64 (samples with t >= guide.t_start get a
-    zero gradient) or None.  Two launches, no atomics; the workspace is allocated per call."""
+    zero gradient) or None.  Two launches (an h3d description: four), no atomics; the workspace is allocated per call."""
     lib = ffi.load()
     ffi.require_gpu(x, frame_mask, t)
     x = ffi.f32c(x)
@@ -545,13 +545,79 @@ def contact_guidance(guide: "ffi.ContactGuide", x: torch.Tensor, frame_mask: Opt
     tt = None if t is None else t.to(dtype=torch.int64).contiguous()
     g = torch.empty_like(x) if grad else None
     e = torch.empty(B, dtype=torch.float32, device=x.device) if energy else None
-    nbytes = int(lib.afm_contact_guidance_workspace_bytes(B, guide.N, guide.K))
+    if guide.h3d:
+        sizer, nbytes = "afm_contact_guidance_h3d_workspace_bytes", int(lib.afm_contact_guidance_h3d_workspace_bytes(B, L, guide.N, guide.K))
+    else:
+        sizer, nbytes = "afm_contact_guidance_workspace_bytes", int(lib.afm_contact_guidance_workspace_bytes(B, guide.N, guide.K))
     if nbytes < 0:
-        ffi.check(nbytes, "afm_contact_guidance_workspace_bytes")
+        ffi.check(nbytes, sizer)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
     ffi.check(lib.afm_contact_guidance(C.byref(guide), x.data_ptr(), ffi.ptr(fm), ffi.ptr(tt), ffi.ptr(g), ffi.ptr(e), B, L, D, ws.data_ptr(),
                                        ws.numel(), ffi.stream_of(x)), "afm_contact_guidance")
     return g, e
+
+
+def h3d_joint_list(joints, limit: int, who: str):
+    """the joint list of a HumanML3D-feature motion as ints (None: all 22), checked: 1..limit joints, each 0..21, none twice"""
+    joints = list(range(ffi.H3D_JOINTS)) if joints is None else [int(j) for j in joints]
+    if not 1 <= len(joints) <= limit:
+        raise ValueError(f"{who}: 1 to {limit} joints, got {len(joints)}")
+    for i, j in enumerate(joints):
+        if not 0 <= j < ffi.H3D_JOINTS:
+            raise ValueError(f"{who}: joint {j} is outside 0..{ffi.H3D_JOINTS - 1}")
+        if j in joints[:i]:
+            raise ValueError(f"{who}: joint {j} is named twice")
+    return joints
+
+
+def h3d_to_scene(to_scene: Optional[torch.Tensor], who: str):
+    """``to_scene`` checked apart from its device and batch: None, or a float32 [3, 4] / [B, 3, 4] tensor"""
+    if to_scene is None:
+        return None
+    if not isinstance(to_scene, torch.Tensor) or to_scene.dtype != torch.float32 or to_scene.dim() not in (2, 3) or tuple(to_scene.shape[-2:]) != (3, 4):
+        what = f"{tuple(to_scene.shape)} {to_scene.dtype}" if isinstance(to_scene, torch.Tensor) else type(to_scene).__name__
+        raise ValueError(f"{who}: to_scene must be a float32 [3, 4] or [B, 3, 4] tensor, got {what}")
+    return to_scene.detach()
+
+
+def h3d_to_scene_on(to_scene: Optional[torch.Tensor], B: int, device, who: str):
+    """(contiguous tensor or None, batch stride in floats) of a checked ``to_scene`` against a batch on ``device``"""
+    if to_scene is None:
+        return None, 0
+    if to_scene.device != device:
+        raise ValueError(f"{who}: to_scene is on {to_scene.device}, the sample on {device}")
+    if to_scene.dim() == 3 and to_scene.shape[0] != B:
+        raise ValueError(f"{who}: to_scene holds {to_scene.shape[0]} matrices for a batch of {B}")
+    return to_scene.contiguous(), (12 if to_scene.dim() == 3 else 0)
+
+
+def h3d_joints(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, *, x_mask: Optional[torch.Tensor] = None, joints=None,
+               to_scene: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Joint positions [B, L, J, 3] of a HumanML3D-feature motion x [B, L, D >= 67] (afm_h3d_joints: the reference's recover_from_ric on
+    the device, one launch).  ``mean`` / ``std`` [D] de-normalise x; ``joints``: the joint indices 0..21 wanted (None: all 22);
+    ``x_mask`` [B, L] (True = padded): a padded frame's rotation and root velocities count as zero, so with valid frames first the valid
+    frames come out as without a mask; ``to_scene`` [3, 4] or [B, 3, 4] float32 = [A|t] places the motion in the scene, p = A P + t
+    (None: identity; y-up to z-up is A = [[1, 0, 0], [0, 0, -1], [0, 1, 0]])."""
+    who = "h3d_joints"
+    if x.dim() != 3 or x.shape[-1] < ffi.H3D_COLS:
+        raise ValueError(f"{who}: x must be [B, L, D] with D >= {ffi.H3D_COLS} HumanML3D feature columns, got {tuple(x.shape)}")
+    B, L, D = x.shape
+    if mean.dim() != 1 or mean.shape[0] != D or std.shape != mean.shape:
+        raise ValueError(f"{who}: mean and std must be [{D}], got {tuple(mean.shape)} and {tuple(std.shape)}")
+    joints = h3d_joint_list(joints, ffi.H3D_JOINTS, who)
+    ts, stride = h3d_to_scene_on(h3d_to_scene(to_scene, who), B, x.device, who)
+    ffi.require_gpu(x, x_mask)
+    lib = ffi.load()
+    x = ffi.f32c(x)
+    mean, std = ffi.f32c(mean.detach().to(x.device)), ffi.f32c(std.detach().to(x.device))
+    fm = None if x_mask is None else _mask_u8(x_mask.reshape(B, L))
+    out = torch.empty((B, L, len(joints), 3), dtype=torch.float32, device=x.device)
+    if L == 0:
+        return out
+    jl = (C.c_int32 * len(joints))(*joints)
+    ffi.check(lib.afm_h3d_joints(x.data_ptr(), mean.data_ptr(), std.data_ptr(), ffi.ptr(fm), jl, len(joints), ffi.ptr(ts), stride, out.data_ptr(),
+                                 B, L, D, ffi.stream_of(x)), "afm_h3d_joints")
+    return out
 
 
 def cfg2_combine(x0_c: torch.Tensor, x0_a: torch.Tensor, x0_u: torch.Tensor, scale_first: torch.Tensor, scale_second: torch.Tensor, *,

@@ -41,7 +41,8 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     normalised contact (exp(-d^2 / 2 sigma^2) - mean) / std - pin it on the points of a chosen object, or to the value of zero contact
     on a region to keep clear.  ``motion_impute.known`` [B, frames, D] lives in the normalised motion space.
     ``contact_guidance``: an afm.diffusion.ContactGuidance handed to the motion stage as ``cond_fn`` (the stage stays in its native loop):
-    the ``c_pc_contact`` it reads is the stage's own ``cond``, so the generated joints are pulled to the points the first stage marked."""
+    the ``c_pc_contact`` it reads is the stage's own ``cond``, so the generated joints are pulled to the points the first stage marked.  A motion model on HumanML3D features (``data_repr`` "h3d",
+    D = 263) takes ``ContactGuidance.h3d(joints, mean, std, to_scene=...)``, one on absolute positions ``ContactGuidance(cols, mean, std)``."""
     if sampler not in ("ddpm", "ddim", "dpm++"):
         raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpm++', not {sampler!r}")
     if sampler == "dpm++" and float(eta) != 0.0:

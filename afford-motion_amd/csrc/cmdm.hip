@@ -537,7 +537,7 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
         sb->ggrad = base ? (float*)(base + off) : nullptr;
         off += align256((int64_t)sb->count * L * w.motion_dim * 4);
         sb->gws = base ? base + off : nullptr;
-        sb->gws_bytes = afm_contact_guidance_workspace_bytes(sb->count, guide->N, guide->K);
+        sb->gws_bytes = afm_contact_guide_workspace_bytes(guide, sb->count, L);
         off += align256(sb->gws_bytes);
     }
     return off;
@@ -652,7 +652,7 @@ int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_d
 inline bool guided_step(const Loop& l, int j) { return l.c.guide && l.c.a.first_step + j >= l.c.guide->first_guided; }
 
 // the gradient of (sub-batch, step j) at the x the step's evaluations read, on the sub-batch's stream: the two launches of
-// afm_contact_guidance into the sub-batch's gradient buffer
+// afm_contact_guidance (h3d description: four) into the sub-batch's gradient buffer
 int guide_launch(const Loop& l, const SubBatch& sb) {
     // (the guidance's own mask: the denoiser's frame_mask is NULL for a model that does not mask its motion tokens)
     const uint8_t* fm = l.c.guide->frame_mask ? l.c.guide->frame_mask + (int64_t)sb.start * l.c.L : nullptr;

@@ -1,6 +1,11 @@
 // Contact guidance (afm_contact_guidance): the analytic gradient and value of the energy between the contact map a motion implies and the
 // map it was given - a cond_fn of the samplers without a second network and without autograd.  Two launches, no atomics: every sum has a
 // fixed order and reads one sample's data only, so a sample's result does not depend on the batch it is computed in.
+//
+// HumanML3D features (`h3d`, afm_h3d_layout): the joints are not columns of x but a function of it - the root's rotation and planar velocities
+// integrated over the frames (the reference's recover_from_ric).  A recovery kernel in front of the two passes writes the guided joints'
+// scene-frame positions to the workspace, the passes read them from there, pass 2 leaves S[b,f,k,:] in the workspace, and an adjoint kernel
+// behind them carries S through the transposed recovery into complete grad rows: four launches, every scan one lane's serial chain.
 #include "sample_loop.h"
 
 namespace {
@@ -14,6 +19,113 @@ struct GuideDev {
     float two_s2, coef;             // 2 sigma^2 and 2 / (N K sigma^2), rounded once from float64
     int64_t t_start;
 };
+
+constexpr int H3D_JOINTS = 22;                       // joints of the HumanML3D skeleton
+constexpr int H3D_COLS = 4 + 3 * (H3D_JOINTS - 1);   // 67: rotation velocity, two planar velocities, root height, 21 local triples
+constexpr int H3D_SCAN_ROWS = 7;                     // per-frame LDS rows of the recovery and of the adjoint
+
+// what the recovery kernel takes: positions of J joints to pos[b * out_b + k * out_j + f * 3]
+struct H3dDev {
+    const float *mean, *std, *to_scene;              // to_scene: the first sample's [3][4], sample b at b * ts_stride (NULL: identity)
+    int joints[H3D_JOINTS];
+    int J, L, D, ts_stride;
+    int64_t out_b, out_j, out_f;
+};
+
+struct H3dAdjDev {
+    const float *mean, *std, *scale, *to_scene;
+    int joints[AFM_GUIDE_MAX_JOINTS];
+    int K, L, D, ts_stride;
+    float coef;
+    int64_t t_start;
+};
+
+// u = x * std + mean of one feature column, each operation rounded on its own: the recovery and the adjoint see the same features
+__device__ __forceinline__ float h3d_u(const float* __restrict__ xrow, const float* __restrict__ mean, const float* __restrict__ std, int col) {
+#pragma clang fp contract(off)
+    const float m = xrow[col] * std[col];
+    return m + mean[col];
+}
+
+// [A|t] of sample b into LDS (row-major 3 x 4; NULL: the identity)
+__device__ __forceinline__ void stage_to_scene(const float* __restrict__ to_scene, int64_t off, float* sA) {
+    if (threadIdx.x < 12) sA[threadIdx.x] = to_scene ? to_scene[off + threadIdx.x] : (threadIdx.x % 5 == 0 ? 1.f : 0.f);
+}
+
+// The recovery, one block per sample.  With w, vx, vz = u[f, 0..2] (zero in a padded frame):
+//   th_f = sum_{g<f} w_g;  c_f = cosf(2 th_f), s_f = sinf(2 th_f);  dX_f = vx_{f-1} c_f - vz_{f-1} s_f, dZ_f = vx_{f-1} s_f + vz_{f-1} c_f (f >= 1)
+//   X_f = sum_{h<=f} dX_h, Z_f likewise;  joint 0: P = (X, u[f,3], Z);  joint j: P = (lx c - lz s + X, ly, lx s + lz c + Z), l = u[f, 4+3(j-1)..]
+//   p = (A_r0 P_x + A_r1 P_y) + A_r2 P_z + t_r
+// The three scans are serial chains in frame order, f = 0, 1, ..., each on one lane (th on lane 0; then X on lane 0 and Z on lane 64):
+// the order depends on nothing at all, not on L, B or the sample's place.  c, s go to cs[b][f][2] (if given) for the adjoint to read back.
+__global__ __launch_bounds__(256) void h3d_recover_kernel(const H3dDev h, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                          float* __restrict__ pos, float* __restrict__ cs) {
+#pragma clang fp contract(off)
+    extern __shared__ float sh[];                   // [H3D_SCAN_ROWS][L]
+    __shared__ int sj[H3D_JOINTS];
+    __shared__ float sA[12];
+    const int b = blockIdx.x, L = h.L;
+    float *sth = sh, *sc = sh + L, *ss = sh + 2 * L, *sX = sh + 3 * L, *sZ = sh + 4 * L, *svx = sh + 5 * L, *svz = sh + 6 * L;
+#pragma unroll
+    for (int k = 0; k < H3D_JOINTS; ++k)
+        if (threadIdx.x == k) sj[k] = h.joints[k];
+    stage_to_scene(h.to_scene, (int64_t)b * h.ts_stride, sA);
+    const float* xb = x + (int64_t)b * L * h.D;
+    for (int f = threadIdx.x; f < L; f += 256) {
+        const float* xrow = xb + (int64_t)f * h.D;
+        const bool pad = fmask && fmask[(int64_t)b * L + f];
+        sth[f] = pad ? 0.f : h3d_u(xrow, h.mean, h.std, 0);
+        svx[f] = pad ? 0.f : h3d_u(xrow, h.mean, h.std, 1);
+        svz[f] = pad ? 0.f : h3d_u(xrow, h.mean, h.std, 2);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float acc = 0.f;
+        for (int f = 0; f < L; ++f) { const float w = sth[f]; sth[f] = acc; acc = acc + w; }
+    }
+    __syncthreads();
+    for (int f = threadIdx.x; f < L; f += 256) {
+        const float a = 2.f * sth[f];
+        const float c = cosf(a), s = sinf(a);
+        float dX = 0.f, dZ = 0.f;
+        if (f > 0) {
+            const float vx = svx[f - 1], vz = svz[f - 1];
+            dX = vx * c - vz * s;
+            dZ = vx * s + vz * c;
+        }
+        sc[f] = c; ss[f] = s; sX[f] = dX; sZ[f] = dZ;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 || threadIdx.x == 64) {
+        float* v = threadIdx.x == 0 ? sX : sZ;
+        float acc = 0.f;
+        for (int f = 0; f < L; ++f) { acc = acc + v[f]; v[f] = acc; }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < h.J * L; i += 256) {
+        const int k = i / L, f = i - k * L, j = sj[k];
+        const float* xrow = xb + (int64_t)f * h.D;
+        float Px, Py, Pz;
+        if (j == 0) {
+            Px = sX[f]; Py = h3d_u(xrow, h.mean, h.std, 3); Pz = sZ[f];
+        } else {
+            const int col = 4 + 3 * (j - 1);
+            const float lx = h3d_u(xrow, h.mean, h.std, col), ly = h3d_u(xrow, h.mean, h.std, col + 1), lz = h3d_u(xrow, h.mean, h.std, col + 2);
+            const float c = sc[f], s = ss[f];
+            Px = (lx * c - lz * s) + sX[f];
+            Py = ly;
+            Pz = (lx * s + lz * c) + sZ[f];
+        }
+        float* o = pos + (int64_t)b * h.out_b + (int64_t)k * h.out_j + (int64_t)f * h.out_f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) o[r] = ((sA[4 * r] * Px + sA[4 * r + 1] * Py) + sA[4 * r + 2] * Pz) + sA[4 * r + 3];
+    }
+    if (cs)
+        for (int f = threadIdx.x; f < L; f += 256) {
+            cs[((int64_t)b * L + f) * 2] = sc[f];
+            cs[((int64_t)b * L + f) * 2 + 1] = ss[f];
+        }
+}
 
 // the column list into LDS with static indices (a dynamic index into the by-value argument would put the array in scratch)
 __device__ __forceinline__ void stage_cols(const GuideDev& g, int* scols) {
@@ -130,7 +242,179 @@ __global__ __launch_bounds__(256) void guide_gather_kernel(const GuideDev g, con
     }
 }
 
+// Pass 1 of the h3d form: guide_nearest_kernel with the positions taken from the recovery kernel's pos[b][K][L][3] - the very order staged
+// here - in place of the columns of x.  A kernel of its own (as pass 2 below), so that the code of the two kernels above stays what it was.
+__global__ __launch_bounds__(256) void guide_nearest_h3d_kernel(const GuideDev g, const float* __restrict__ pos, const uint8_t* __restrict__ fmask,
+                                                                int* __restrict__ fstar, float* __restrict__ w, float* __restrict__ partial) {
+#pragma clang fp contract(off)
+    extern __shared__ float sp[];                   // [K][L][3] positions, then [L] validity
+    __shared__ float red[4];
+    const int b = blockIdx.y, K = g.K, N = g.N, L = g.L;
+    int* sval = reinterpret_cast<int*>(sp + (size_t)K * L * 3);
+    const float* pb = pos + (int64_t)b * K * L * 3;
+    for (int i = threadIdx.x; i < K * L * 3; i += 256) sp[i] = pb[i];
+    for (int f = threadIdx.x; f < L; f += 256) sval[f] = !(fmask && fmask[(int64_t)b * L + f]);
+    __syncthreads();
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    float sq = 0.f;
+    if (e < K * N) {
+        const int k = e / N, n = e - k * N;
+        const float* qp = g.q + ((int64_t)b * N + n) * 3;
+        const float qx = qp[0], qy = qp[1], qz = qp[2];
+        const float* pk = sp + (size_t)k * L * 3;
+        float best = INFINITY;
+        int bf = -1;
+        for (int f = 0; f < L; ++f) {
+            if (!sval[f]) continue;
+            const float dx = pk[f * 3] - qx, dy = pk[f * 3 + 1] - qy, dz = pk[f * 3 + 2] - qz;
+            const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+            const float d2 = (xx + yy) + zz;
+            if (d2 < best) { best = d2; bf = f; }
+        }
+        const float chat = bf >= 0 ? expf(-best / g.two_s2) : 0.f;
+        const float df = chat - g.c[((int64_t)b * N + n) * K + k];
+        const int64_t o = ((int64_t)b * K + k) * N + n;
+        fstar[o] = bf;
+        w[o] = df * chat;
+        sq = df * df;
+    }
+    sq = wave_sum(sq);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(int64_t)b * g.nblk + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Pass 2 of the h3d form, guide_gather_kernel's blocks, waves and sums: p is the recovery kernel's, and the bare sums go to S[b][f][k][3] for the adjoint (a
+// padded frame is nobody's nearest frame, so its sums are zero; scale, t_start and the mask are the adjoint's business).  S == NULL:
+// the energy alone, one block per sample.
+__global__ __launch_bounds__(256) void guide_sums_h3d_kernel(const GuideDev g, const float* __restrict__ pos, const int* __restrict__ fstar,
+                                                             const float* __restrict__ w, const float* __restrict__ partial,
+                                                             float* __restrict__ S, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y, f = blockIdx.x, K = g.K, N = g.N;
+    if (f == 0 && energy && threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < g.nblk; ++i) s += partial[(int64_t)b * g.nblk + i];
+        energy[b] = s / (float)((int64_t)N * K);
+    }
+    if (!S) return;
+    const int lane = threadIdx.x & 63;
+    for (int k = threadIdx.x >> 6; k < K; k += 4) {
+        const float* pp = pos + (((int64_t)b * K + k) * g.L + f) * 3;
+        const float p0 = pp[0], p1 = pp[1], p2 = pp[2];
+        const int64_t o = ((int64_t)b * K + k) * N;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+        for (int n = lane; n < N; n += 64) {
+            if (fstar[o + n] != f) continue;
+            const float ww = w[o + n];
+            const float* qp = g.q + ((int64_t)b * N + n) * 3;
+            const float m0 = ww * (p0 - qp[0]), m1 = ww * (p1 - qp[1]), m2 = ww * (p2 - qp[2]);
+            s0 = s0 + m0; s1 = s1 + m1; s2 = s2 + m2;
+        }
+        s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
+        if (lane < 3) S[(((int64_t)b * g.L + f) * K + k) * 3 + lane] = lane == 0 ? s0 : (lane == 1 ? s1 : s2);
+    }
+}
+
+// The adjoint of the recovery, one block per sample: S[b][f][k][3] -> complete grad rows of the sample, the zeros included.  Per frame
+// (one thread each), G_k = A^T S_k, the local-coordinate and root-height terms written at once, gX_f = sum_k G_x, gZ_f likewise and the
+// rotation term of the joints, in joint order; then SX, SZ = inclusive suffix sums of gX, gZ (lane 0 and lane 64, f = L-1 down to 0);
+// per frame the velocity terms and T_f; then dw = the exclusive suffix sum of T (lane 0, f = L-1 down to 0).  c_f, s_f are read back from
+// what the recovery stored.  A padded frame's row, and every row of a sample with t[b] >= t_start, stays zero.  No atomics.
+__global__ __launch_bounds__(256) void h3d_adjoint_kernel(const H3dAdjDev a, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                          const int64_t* __restrict__ t, const float* __restrict__ cs, const float* __restrict__ S,
+                                                          float* __restrict__ grad) {
+#pragma clang fp contract(off)
+    extern __shared__ float sh[];                   // [H3D_SCAN_ROWS][L]
+    __shared__ int sj[AFM_GUIDE_MAX_JOINTS];
+    __shared__ float sA[12];
+    const int b = blockIdx.x, L = a.L, D = a.D, K = a.K;
+    float *sgX = sh, *sgZ = sh + L, *sT = sh + 2 * L, *sc = sh + 3 * L, *ss = sh + 4 * L, *svx = sh + 5 * L, *svz = sh + 6 * L;
+    float* gb = grad + (int64_t)b * L * D;
+    for (int64_t i = threadIdx.x; i < (int64_t)L * D; i += 256) gb[i] = 0.f;
+    if (t && t[b] >= a.t_start) return;
+#pragma unroll
+    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
+        if (threadIdx.x == k) sj[k] = a.joints[k];
+    stage_to_scene(a.to_scene, (int64_t)b * a.ts_stride, sA);
+    __syncthreads();                                // (the zeros above are in place before any thread writes a term over them)
+    const float* xb = x + (int64_t)b * L * D;
+    const uint8_t* mb = fmask ? fmask + (int64_t)b * L : nullptr;
+    const float ks = a.scale[b] * a.coef;
+    for (int f = threadIdx.x; f < L; f += 256) {
+        const float* xrow = xb + (int64_t)f * D;
+        float* row = gb + (int64_t)f * D;
+        const bool pad = mb && mb[f];
+        const float c = cs[((int64_t)b * L + f) * 2], s = cs[((int64_t)b * L + f) * 2 + 1];
+        sc[f] = c; ss[f] = s;
+        svx[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 1);
+        svz[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 2);
+        float gX = 0.f, gZ = 0.f, T = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const float* Sp = S + (((int64_t)b * L + f) * K + k) * 3;
+            const float S0 = Sp[0], S1 = Sp[1], S2 = Sp[2];
+            const float Gx = (sA[0] * S0 + sA[4] * S1) + sA[8] * S2;
+            const float Gy = (sA[1] * S0 + sA[5] * S1) + sA[9] * S2;
+            const float Gz = (sA[2] * S0 + sA[6] * S1) + sA[10] * S2;
+            gX = gX + Gx; gZ = gZ + Gz;
+            const int j = sj[k];
+            if (j == 0) {
+                if (!pad) row[3] = (ks * a.std[3]) * Gy;
+                continue;
+            }
+            const int col = 4 + 3 * (j - 1);
+            const float lx = h3d_u(xrow, a.mean, a.std, col), lz = h3d_u(xrow, a.mean, a.std, col + 2);
+            T = T + (Gx * (-lx * s - lz * c) + Gz * (lx * c - lz * s));
+            if (!pad) {
+                row[col] = (ks * a.std[col]) * (Gx * c + Gz * s);
+                row[col + 1] = (ks * a.std[col + 1]) * Gy;
+                row[col + 2] = (ks * a.std[col + 2]) * (Gz * c - Gx * s);
+            }
+        }
+        sgX[f] = gX; sgZ[f] = gZ; sT[f] = T;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 || threadIdx.x == 64) {
+        float* v = threadIdx.x == 0 ? sgX : sgZ;
+        float acc = 0.f;
+        for (int f = L - 1; f >= 0; --f) { acc = acc + v[f]; v[f] = acc; }
+    }
+    __syncthreads();
+    for (int f = threadIdx.x; f < L; f += 256) {
+        if (f == 0) { sT[0] = 2.f * sT[0]; continue; }            // (never read: dw_g sums the frames behind g)
+        const float SX = sgX[f], SZ = sgZ[f], c = sc[f], s = ss[f], vx = svx[f - 1], vz = svz[f - 1];
+        sT[f] = 2.f * ((sT[f] + SX * (-vx * s - vz * c)) + SZ * (vx * c - vz * s));
+        if (!(mb && mb[f - 1])) {
+            float* row = gb + (int64_t)(f - 1) * D;
+            row[1] = (ks * a.std[1]) * (SX * c + SZ * s);
+            row[2] = (ks * a.std[2]) * (SZ * c - SX * s);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float acc = 0.f;
+        for (int f = L - 1; f >= 0; --f) { const float v = sT[f]; sT[f] = acc; acc = acc + v; }
+    }
+    __syncthreads();
+    for (int f = threadIdx.x; f < L; f += 256)
+        if (!(mb && mb[f])) gb[(int64_t)f * D] = (ks * a.std[0]) * sT[f];
+}
+
 int64_t guide_nblk(int N, int K) { return ((int64_t)N * K + 255) / 256; }
+
+// the h3d form's buffers behind the three of the absolute form: positions [B][K][L][3], c / s [B][L][2], S [B][L][K][3]
+int64_t h3d_extra_bytes(int64_t B, int64_t L, int64_t K) {
+    return 2 * afm_loop::align256(B * K * L * 3 * 4) + afm_loop::align256(B * L * 2 * 4);
+}
+
+bool h3d_joint_list_ok(const int32_t* joints, int n) {
+    for (int k = 0; k < n; ++k) {
+        if (joints[k] < 0 || joints[k] >= H3D_JOINTS) return false;
+        for (int j = 0; j < k; ++j)
+            if (joints[j] == joints[k]) return false;
+    }
+    return true;
+}
 
 }  // namespace
 
@@ -140,16 +424,33 @@ extern "C" int64_t afm_contact_guidance_workspace_bytes(int32_t B, int32_t N, in
     return 2 * afm_loop::align256(nk * 4) + afm_loop::align256((int64_t)B * guide_nblk(N, K) * 4);
 }
 
+extern "C" int64_t afm_contact_guidance_h3d_workspace_bytes(int32_t B, int32_t L, int32_t N, int32_t K) {
+    const int64_t base = afm_contact_guidance_workspace_bytes(B, N, K);
+    if (base < 0 || L <= 0) return AFM_E_BADARG;
+    return afm_loop::align256(base) + h3d_extra_bytes(B, L, K);
+}
+
+// the workspace of `count` samples of a description, either form
+__attribute__((visibility("hidden"))) int64_t afm_contact_guide_workspace_bytes(const afm_contact_guide* a, int32_t count, int32_t L) {
+    return a->h3d ? afm_contact_guidance_h3d_workspace_bytes(count, L, a->N, a->K) : afm_contact_guidance_workspace_bytes(count, a->N, a->K);
+}
+
 // what a description must satisfy before anything is enqueued (L, D: the motion's)
 __attribute__((visibility("hidden"))) int afm_contact_guide_check(const afm_contact_guide* a, int32_t L, int32_t D) {
     if (!a || !a->q || !a->c || !a->mean || !a->std || !a->scale || L <= 0 || D <= 0) return AFM_E_BADARG;
     if (a->K <= 0 || a->K > AFM_GUIDE_MAX_JOINTS || a->N <= 0 || !(a->sigma > 0.0) || (int64_t)a->N * a->K > (int64_t)1 << 30) return AFM_E_BADARG;
-    for (int k = 0; k < a->K; ++k) {
-        if (a->cols[k] < 0 || a->cols[k] + 3 > D) return AFM_E_BADARG;
-        for (int j = 0; j < k; ++j)
-            if (a->cols[k] < a->cols[j] + 3 && a->cols[j] < a->cols[k] + 3) return AFM_E_BADARG;          // overlapping triples
+    if (a->h3d) {
+        if (D < H3D_COLS || !h3d_joint_list_ok(a->h3d->joints, a->K)) return AFM_E_BADARG;
+        if (a->h3d->to_scene_stride != 0 && a->h3d->to_scene_stride != 12) return AFM_E_BADARG;
+    } else {
+        for (int k = 0; k < a->K; ++k) {
+            if (a->cols[k] < 0 || a->cols[k] + 3 > D) return AFM_E_BADARG;
+            for (int j = 0; j < k; ++j)
+                if (a->cols[k] < a->cols[j] + 3 && a->cols[j] < a->cols[k] + 3) return AFM_E_BADARG;          // overlapping triples
+        }
     }
     if (((size_t)a->K * L * 3 + L) * 4 > (size_t)GUIDE_LDS_BYTES || L > 65535) return AFM_E_UNSUPPORTED;
+    if (a->h3d && (size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
     return 0;
 }
 
@@ -163,7 +464,7 @@ __attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_con
     if (count > 65535) return AFM_E_UNSUPPORTED;
     const size_t lds = ((size_t)a->K * L * 3 + L) * 4;
     if (count == 0) return 0;
-    const int64_t need = afm_contact_guidance_workspace_bytes(count, a->N, a->K);
+    const int64_t need = afm_contact_guide_workspace_bytes(a, count, L);
     if (!workspace || workspace_bytes < need) return AFM_E_WORKSPACE;
     GuideDev g = {};
     g.q = a->q + (int64_t)start * a->N * 3; g.c = a->c + (int64_t)start * a->N * a->K; g.mean = a->mean; g.std = a->std; g.scale = a->scale + start;
@@ -178,6 +479,36 @@ __attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_con
     float* w = (float*)wp; wp += afm_loop::align256(nk * 4);
     float* partial = (float*)wp;
     hipStream_t s = (hipStream_t)stream;
+    if (a->h3d) {
+        const afm_h3d_layout& lay = *a->h3d;
+        wp = (char*)workspace + afm_loop::align256(afm_contact_guidance_workspace_bytes(count, a->N, a->K));
+        const int64_t klb = afm_loop::align256((int64_t)count * a->K * L * 3 * 4);
+        float* pos = (float*)wp; wp += klb;
+        float* S = (float*)wp; wp += klb;
+        float* cs = (float*)wp;
+        const float* to_scene = lay.to_scene ? lay.to_scene + (int64_t)start * lay.to_scene_stride : nullptr;
+        const size_t scan_lds = (size_t)H3D_SCAN_ROWS * L * 4;
+        H3dDev h = {};
+        h.mean = a->mean; h.std = a->std; h.to_scene = to_scene; h.ts_stride = lay.to_scene_stride;
+        for (int k = 0; k < a->K; ++k) h.joints[k] = lay.joints[k];
+        h.J = a->K; h.L = L; h.D = D;
+        h.out_b = (int64_t)a->K * L * 3; h.out_j = (int64_t)L * 3; h.out_f = 3;
+        hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, h, x, frame_mask, pos, grad ? cs : nullptr);
+        AFM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(guide_nearest_h3d_kernel, dim3((unsigned)g.nblk, (unsigned)count), dim3(256), lds, s, g, pos, frame_mask, fstar, w, partial);
+        AFM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(guide_sums_h3d_kernel, dim3(grad ? (unsigned)L : 1u, (unsigned)count), dim3(256), 0, s, g, pos, fstar, w, partial,
+                           grad ? S : nullptr, energy);
+        AFM_CHECK_LAUNCH();
+        if (!grad) return 0;
+        H3dAdjDev ad = {};
+        ad.mean = a->mean; ad.std = a->std; ad.scale = g.scale; ad.to_scene = to_scene; ad.ts_stride = lay.to_scene_stride;
+        for (int k = 0; k < a->K; ++k) ad.joints[k] = lay.joints[k];
+        ad.K = a->K; ad.L = L; ad.D = D; ad.coef = g.coef; ad.t_start = a->t_start;
+        hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, ad, x, frame_mask, t, cs, S, grad);
+        AFM_CHECK_LAUNCH();
+        return 0;
+    }
     hipLaunchKernelGGL(guide_nearest_kernel, dim3((unsigned)g.nblk, (unsigned)count), dim3(256), lds, s, g, x, frame_mask, fstar, w, partial);
     AFM_CHECK_LAUNCH();
     hipLaunchKernelGGL(guide_gather_kernel, dim3(grad ? (unsigned)L : 1u, (unsigned)count), dim3(256), 0, s, g, x, frame_mask, t, fstar, w, partial, grad,
@@ -189,4 +520,23 @@ __attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_con
 extern "C" int afm_contact_guidance(const afm_contact_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
                                     float* energy, int32_t B, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes, void* stream) {
     return afm_contact_guidance_sub(g, 0, x, frame_mask, t, grad, energy, B, L, D, workspace, workspace_bytes, stream);
+}
+
+extern "C" int afm_h3d_joints(const float* x, const float* mean, const float* std, const uint8_t* frame_mask, const int32_t* joints, int32_t J,
+                              const float* to_scene, int32_t to_scene_stride, float* out, int32_t B, int32_t L, int32_t D, void* stream) {
+    if (!x || !mean || !std || !out || B < 0 || L <= 0 || D < H3D_COLS) return AFM_E_BADARG;
+    if (to_scene_stride != 0 && to_scene_stride != 12) return AFM_E_BADARG;
+    if (!joints) J = H3D_JOINTS;
+    if (J <= 0 || J > H3D_JOINTS || (joints && !h3d_joint_list_ok(joints, J))) return AFM_E_BADARG;
+    if ((size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES || B > 65535) return AFM_E_UNSUPPORTED;
+    if (B == 0) return 0;
+    H3dDev h = {};
+    h.mean = mean; h.std = std; h.to_scene = to_scene; h.ts_stride = to_scene_stride;
+    for (int k = 0; k < J; ++k) h.joints[k] = joints ? joints[k] : k;
+    h.J = J; h.L = L; h.D = D;
+    h.out_b = (int64_t)L * J * 3; h.out_j = 3; h.out_f = (int64_t)J * 3;
+    hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)B), dim3(256), (size_t)H3D_SCAN_ROWS * L * 4, (hipStream_t)stream, h, x, frame_mask, out,
+                       (float*)nullptr);
+    AFM_CHECK_LAUNCH();
+    return 0;
 }

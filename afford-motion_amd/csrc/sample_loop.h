@@ -18,7 +18,9 @@ namespace afm_loop { struct Update; }
 __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Update& p, int32_t B, void* stream);
 
 // guidance.hip: afm_contact_guidance on the samples [start, start + count) of the description's batch (x, frame_mask, t, grad, energy
-// already point at sample `start`; the workspace: afm_contact_guidance_workspace_bytes(count, N, K))
+// already point at sample `start`; the workspace: afm_contact_guide_workspace_bytes(g, count, L) - the public size function of the
+// description's form, absolute columns or h3d)
+__attribute__((visibility("hidden"))) int64_t afm_contact_guide_workspace_bytes(const afm_contact_guide* g, int32_t count, int32_t L);
 __attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_contact_guide* g, int32_t start, const float* x, const uint8_t* frame_mask,
                                                                    const int64_t* t, float* grad, float* energy, int32_t count, int32_t L, int32_t D,
                                                                    void* workspace, int64_t workspace_bytes, void* stream);

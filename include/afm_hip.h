@@ -869,10 +869,30 @@ int afm_guide_step(const afm_guide_step_args* args, void* stream);
  * a sample with t[b] >= t_start.  Two launches: pass 1 per (b, k, n) with the sample's joint positions in LDS, pass 2 one wave per
  * (b, f, k) summing its points in a fixed order (lane l takes n = l, l + 64, ...; then a fixed butterfly) - no atomics, bit-identical
  * run to run, and a function of the sample alone (no value depends on B or on the sample's place in the batch).  The column triples must
- * lie inside D and must not overlap; K <= AFM_GUIDE_MAX_JOINTS; K * L * 3 floats must fit the LDS (AFM_E_UNSUPPORTED). */
+ * lie inside D and must not overlap; K <= AFM_GUIDE_MAX_JOINTS; K * L * 3 floats must fit the LDS (AFM_E_UNSUPPORTED).
+ *
+ * HumanML3D features (`h3d`, D = 263; v7-additive: afm_contact_guide.h3d, NULL = the absolute columns above).  The motion vector holds no
+ * joint positions: with u = x * std + mean (columns 0..66 are read; D >= 67) and the velocity columns 0..2 of a padded frame taken as zero,
+ *   th_f = sum_{g<f} u[g,0]  (the reference's HALF angle);  c_f = cos(2 th_f), s_f = sin(2 th_f)
+ *   X_f = sum_{1<=h<=f} (u[h-1,1] c_h - u[h-1,2] s_h),   Z_f = sum_{1<=h<=f} (u[h-1,1] s_h + u[h-1,2] c_h),   Y_f = u[f,3]
+ *   joint 0: P = (X_f, Y_f, Z_f);   joint j = 1..21, l = u[f, 4+3(j-1) ..]: P = (l_x c_f - l_z s_f + X_f, l_y, l_x s_f + l_z c_f + Z_f)
+ *   p = A P + t,  to_scene = [A|t] (3 x 4 row-major; the reference does not fix how an h3d motion lies in its scene, e.g. y-up to z-up:
+ *   A = [[1,0,0],[0,0,-1],[0,1,0]], t = 0)
+ * which is recover_from_ric(data, 22) of the reference's utils/visualize.py on valid-frames-first masks.  Everything behind p is the
+ * guidance above; grad is the adjoint of the recovery applied to A^T S, scaled per column as above: nonzero only in columns 0..66 of valid
+ * frames.  Four launches: the recovery (one block per sample; positions [K][L][3], c and s to the workspace), passes 1 and 2 reading those
+ * positions (pass 2 leaves S[b,f,k,:] in the workspace), the adjoint (one block per sample, reads c and s back, writes complete rows).
+ * Every scan over the frames is one lane's serial chain in frame order: no value depends on B, on the sample's place or on L's wave shape.
+ * 7 * L floats must fit the LDS too (AFM_E_UNSUPPORTED). */
 #define AFM_GUIDE_MAX_JOINTS 16
+#define AFM_H3D_JOINTS 22
 typedef struct {
-    const float* q;                        /* device [B][N][3]: the scene points                                          */
+    int32_t joints[AFM_GUIDE_MAX_JOINTS];  /* joint index 0..21 of guided joint k (K of afm_contact_guide; no joint twice)  */
+    const float* to_scene;                 /* device [3][4], or [B][3][4] with to_scene_stride 12; NULL: the identity      */
+    int32_t to_scene_stride;               /* floats between two samples' matrices: 0 (one shared) or 12                   */
+} afm_h3d_layout;
+typedef struct {
+    const float* q;                       /* device [B][N][3]: the scene points                                          */
     const float* c;                        /* device [B][N][K]: the target contact map, un-normalised exp(-d^2 / 2 sigma^2) */
     const float* mean; const float* std;   /* device [D]: de-normalisation of the motion                                  */
     const float* scale;                    /* device [B]                                                                  */
@@ -884,12 +904,24 @@ typedef struct {
     double sigma;                          /* of the contact map; 2 sigma^2 and the coefficient are formed in float64 and rounded once */
     int32_t first_guided;                  /* loops only: executed steps (first_step + j) below it run unguided - no gradient launch */
     int64_t t_start;                       /* afm_contact_guidance with t: samples with t[b] >= t_start get a zero gradient */
+    const afm_h3d_layout* h3d;             /* NULL: `cols` name absolute positions; set: x holds HumanML3D features, `cols` is ignored */
 } afm_contact_guide;
 
-/* grad [B][L][D] and / or energy [B] (either may be NULL) of x [B][L][D]; frame_mask [B][L] (nonzero = padded) or NULL; t [B] or NULL. */
+/* grad [B][L][D] and / or energy [B] (either may be NULL) of x [B][L][D]; frame_mask [B][L] (nonzero = padded) or NULL; t [B] or NULL.
+ * The workspace: afm_contact_guidance_workspace_bytes (absolute columns), afm_contact_guidance_h3d_workspace_bytes (g->h3d set: the
+ * positions, c / s and S scale with B * L * K). */
 int64_t afm_contact_guidance_workspace_bytes(int32_t B, int32_t N, int32_t K);
+int64_t afm_contact_guidance_h3d_workspace_bytes(int32_t B, int32_t L, int32_t N, int32_t K);
 int afm_contact_guidance(const afm_contact_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
                          float* energy, int32_t B, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The joint positions of a HumanML3D-feature motion (the reference's recover_from_ric, on the device): out [B][L][J][3] of x [B][L][D] for
+ * the joint list `joints` [J] (host; NULL: all 22 in order, J ignored), with mean / std device [D], frame_mask [B][L] or NULL (a padded
+ * frame's velocities count as zero; its own row still gives its height and local coordinates) and to_scene as in afm_h3d_layout.  One
+ * launch of the recovery kernel the guidance uses.  AFM_E_BADARG: D < 67, J outside 1..22, a joint outside 0..21 or named twice, a stride
+ * other than 0 / 12; AFM_E_UNSUPPORTED: 7 * L floats beyond the LDS. */
+int afm_h3d_joints(const float* x, const float* mean, const float* std, const uint8_t* frame_mask, const int32_t* joints, int32_t J,
+                   const float* to_scene, int32_t to_scene_stride, float* out, int32_t B, int32_t L, int32_t D, void* stream);
 
 /* The contact-guided native loop, every form behind one entry: DDPM (d_c1 / d_c2 / d_sigma), DDIM (rows) or 2M (dpm; no noise) - exactly
  * one kind of rows; cfg or cfg2 or neither; known / mask optional (both or neither); guide required.  The loop runs in the
@@ -898,7 +930,8 @@ int afm_contact_guidance(const afm_contact_guide* g, const float* x, const uint8
  * of afm_contact_guidance on the x the evaluations read, with guide->frame_mask (not the denoiser's frame_mask, which a model
  * without motion masking does not have); the update launch takes grad and gk row n_steps - 1 - j.  Earlier steps launch
  * what an imputing loop of the same form launches (grad NULL).  guide->q / c / scale / gk cover the whole batch.  A 2M history buffer is
- * always carved, so chained range calls share one layout.  workspace >= afm_cmdm_guide_loop_workspace_bytes. */
+ * always carved, so chained range calls share one layout.  workspace >= afm_cmdm_guide_loop_workspace_bytes.  A description with
+ * guide->h3d set runs through the same entry: four gradient launches per guided step in place of two, the workspace sized for them. */
 int64_t afm_cmdm_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
                                             const afm_cfg2_args* cfg2, const afm_contact_guide* guide);
 int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,

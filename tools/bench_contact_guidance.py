@@ -1,6 +1,6 @@
 """Cost of contact guidance in the CMDM's sampling loops on one MI355X, printed as ONE JSON line (and as a markdown table with --md).
 
-    python tools/bench_contact_guidance.py [--reps 5] [--parent-lib PATH] [--md PATH]
+    python tools/bench_contact_guidance.py [--repr pos|h3d] [--reps 5] [--parent-lib PATH] [--md PATH]
 
 L = 196, N = 8192 contact points, K = 6 contact joints, the benchmark's synthetic weights, at B = 1 and at B = 32, for DDIM (eta = 0) at
 "ddim50" and DPM-Solver++(2M) at "logsnr20".  Arms, ms per sample call (the loop call and the final synchronise):
@@ -9,6 +9,12 @@ L = 196, N = 8192 contact points, K = 6 contact joints, the benchmark's syntheti
     native_guided   the same loop with a ContactGuidance as cond_fn (afm_cmdm_guide_loop_range)
     step_guided     the step-by-step loop with the same ContactGuidance (the progressive generator, consumed)
     parent          --parent-lib: the unguided loop of a libafm_hip.so built from the parent commit, in a fresh child process
+
+--repr pos (the default) guides absolute-position columns (two gradient launches a step).  --repr h3d guides the same D = 263 vector as
+HumanML3D features with ContactGuidance.h3d and the y-up to z-up transform (four launches: recovery, the two passes, adjoint), the same
+L, N, K and batches, and adds the arm
+
+    pos_guided      the native loop with the absolute-column ContactGuidance of --repr pos, for the cost of the two extra launches
 
 A timed window is as many back-to-back loop calls as fill 100 ms (a single B = 1 call of 7 - 27 ms is too short a window), reported per
 call.  The arms alternate inside every repetition and every repetition is kept (median, best, spread (max - min) / median), as the other
@@ -37,7 +43,7 @@ BATCHES = (1, 32)
 SAMPLERS = {"ddim50": ("ddim50", "ddim"), "dpm2m_logsnr20": ("logsnr20", "dpm")}
 JOINTS = [0, 10, 11, 12, 20, 21]
 NEW = ("afm_guide_step", "afm_contact_guidance", "afm_contact_guidance_workspace_bytes", "afm_cmdm_guide_loop_range",
-       "afm_cmdm_guide_loop_workspace_bytes")
+       "afm_cmdm_guide_loop_workspace_bytes", "afm_contact_guidance_h3d_workspace_bytes", "afm_h3d_joints")
 
 
 def _setup(dev, lib=None):
@@ -119,8 +125,9 @@ def _stats(ts, steps):
 
 
 def _markdown(out):
-    lines = ["# Contact guidance in the CMDM sampling loops", "",
-             f"`tools/bench_contact_guidance.py`, {out['device']}, L = {L}, N = {N}, K = {len(JOINTS)}, {out['reps']} repetitions, arms alternating "
+    h3d = out.get("repr") == "h3d"
+    lines = ["# Contact guidance in the CMDM sampling loops" + (" on HumanML3D features" if h3d else ""), "",
+             f"`tools/bench_contact_guidance.py{' --repr h3d' if h3d else ''}`, {out['device']}, L = {L}, N = {N}, K = {len(JOINTS)}, {out['reps']} repetitions, arms alternating "
              "inside every repetition, a timed window = the loop calls that fill 100 ms.  ms per sample call (median; spread = (max - min) / median).", "",
              "| sampler | B | arm | ms / call | ms / step | spread |", "|---|---|---|---|---|---|"]
     for s in SAMPLERS:
@@ -128,17 +135,21 @@ def _markdown(out):
             for arm, v in out[s][f"B{b}"].items():
                 if isinstance(v, dict):
                     lines.append(f"| {s} | {b} | {arm} | {v['ms_per_sample_call']} | {v['ms_per_step']} | {v['spread']} |")
-    lines += ["", "| sampler | B | guided step / unguided step | step-by-step guided / native guided | unguided / parent unguided |", "|---|---|---|---|---|"]
+    extra = ("guided step / pos-guided step | ", "---|") if h3d else ("", "")
+    lines += ["", f"| sampler | B | guided step / unguided step | {extra[0]}step-by-step guided / native guided | unguided / parent unguided |",
+              f"|---|---|---|{extra[1]}---|---|"]
     for s in SAMPLERS:
         for b in BATCHES:
             o = out[s][f"B{b}"]
-            lines.append(f"| {s} | {b} | {o['guided_over_unguided']} | {o['step_over_native']} | {o.get('unguided_over_parent', 'n/a')} |")
+            mid = f"{o['guided_over_pos_guided']} | " if h3d else ""
+            lines.append(f"| {s} | {b} | {o['guided_over_unguided']} | {mid}{o['step_over_native']} | {o.get('unguided_over_parent', 'n/a')} |")
     return "\n".join(lines) + "\n"
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--repr", choices=("pos", "h3d"), default="pos", help="what the motion vector holds: absolute positions or HumanML3D features")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--md", default=None, help="also write the table as markdown to this path")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
@@ -148,8 +159,13 @@ def main():
     dev = torch.device("cuda:0")
     model, diffs, kws = _setup(dev)
     from afm.diffusion import ContactGuidance
-    guide = ContactGuidance([3 * j for j in JOINTS], torch.zeros(D), torch.ones(D), sigma=0.8, scale=1.0)
+    guide = pos_guide = ContactGuidance([3 * j for j in JOINTS], torch.zeros(D), torch.ones(D), sigma=0.8, scale=1.0)
+    if args.repr == "h3d":
+        zup = torch.tensor([[1.0, 0.0, 0.0, 0.0], [0.0, 0.0, -1.0, 0.0], [0.0, 1.0, 0.0, 0.0]], device=dev)
+        guide = ContactGuidance.h3d(JOINTS, torch.zeros(D), torch.ones(D), to_scene=zup, sigma=0.8, scale=1.0)
     arms = {"unguided": dict(), "native_guided": dict(guide=guide), "step_guided": dict(guide=guide, step_by_step=True)}
+    if args.repr == "h3d":
+        arms["pos_guided"] = dict(guide=pos_guide)
     runs = {(s, b, arm): _runner(model, diffs, kws, s, b, **kw) for s in SAMPLERS for b in BATCHES for arm, kw in arms.items()}
     calls = {k: _calls(fn) for k, fn in runs.items()}
     times = {k: [] for k in runs}
@@ -169,7 +185,7 @@ def main():
             for s in SAMPLERS:
                 for arm in arms:
                     times[(s, b, arm)].append(_timed(runs[(s, b, arm)], calls[(s, b, arm)]))
-    out = {"tool": "bench_contact_guidance", "device": torch.cuda.get_device_name(0), "L": L, "N": N, "reps": args.reps}
+    out = {"tool": "bench_contact_guidance", "repr": args.repr, "device": torch.cuda.get_device_name(0), "L": L, "N": N, "reps": args.reps}
     ok = True
     for s in SAMPLERS:
         out[s] = {}
@@ -181,6 +197,8 @@ def main():
                 o["unguided_over_parent"] = round(o["unguided"]["ms_per_sample_call"] / o["parent"]["ms_per_sample_call"], 4)
             o["guided_over_unguided"] = round(o["native_guided"]["ms_per_sample_call"] / o["unguided"]["ms_per_sample_call"], 4)
             o["step_over_native"] = round(o["step_guided"]["ms_per_sample_call"] / o["native_guided"]["ms_per_sample_call"], 4)
+            if "pos_guided" in o:
+                o["guided_over_pos_guided"] = round(o["native_guided"]["ms_per_sample_call"] / o["pos_guided"]["ms_per_sample_call"], 4)
             ok = ok and o["step_over_native"] > 1.0
             out[s][f"B{b}"] = o
     print(json.dumps(out))
