@@ -543,7 +543,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         DPM-Solver++ update and one history buffer per sub-batch in the workspace; no noise: ``step_noise`` is refused, ``seed`` unused;
         sliced chains stay bit-identical because every range call of one chain runs on the same workspace).  ``_guidance``: what only this
         denoiser's loops take (not a caller's argument; the public keywords are the CDM's, name for name): GuidedCMDM's (afm_cfg_args or
-        afm_cfg2_args or None, branch streams?) and, as an optional third entry, an afm.diffusion.ContactGuidance - its gradient at every guided step's x_t is computed on the sub-batch's stream (two launches) and
+        afm_cfg2_args or None, branch streams?) and, as an optional third entry, an afm.diffusion.ContactGuidance (afm_cmdm_guide_loop_range), JointTargets or MotionGuidance (afm_cmdm_motion_guide_loop_range: the same loop, the step's gradient the sum of the terms that have started) - its gradient at every guided step's x_t is computed on the sub-batch's stream (two launches) and
         enters the loop's update launch (afm_cmdm_guide_loop_range, every form; the loop runs in the separate-update form like an
         imputing one; steps before the guidance starts launch what an imputing loop of that form launches)."""
         if any(k in model_kwargs for k in COND_SWITCHES):
@@ -564,9 +564,20 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             cfg, branch_streams, contact_guide = (tuple(_guidance) + (None,))[:3] if _guidance is not None else (None, False, None)
             cguide = guide_keep = None
             if contact_guide is not None:
-                cguide, guide_fm, guide_keep = contact_guide.describe(x, model_kwargs)
+                from .diffusion import ContactGuidance, JointTargets, MotionGuidance
+                if isinstance(contact_guide, ContactGuidance):      # a bare contact term keeps its own entry
+                    guide_names = ("afm_cmdm_guide_loop_range", "afm_cmdm_guide_loop_workspace_bytes")
+                    cguide, guide_fm, guide_keep = contact_guide.describe(x, model_kwargs)
+                    cguide.first_guided = contact_guide.first_guided(diffusion)
+                    guide_form = ("guide", cguide.K, cguide.N, bool(cguide.h3d))
+                else:                                                # anything that carries targets: the sum's entry
+                    guide_names = ("afm_cmdm_motion_guide_loop_range", "afm_cmdm_motion_guide_loop_workspace_bytes")
+                    both = MotionGuidance(targets=contact_guide) if isinstance(contact_guide, JointTargets) else contact_guide
+                    cguide, guide_fm, guide_keep = both.describe(x, model_kwargs, diffusion)
+                    ct, tg = both.contact, both.targets
+                    guide_form = ("motion_guide", None if ct is None else (len(ct.joints or ct.cols), model_kwargs["c_pc_xyz"].shape[1]),
+                                  None if tg is None else tg.K, bool((ct or tg).joints is not None))
                 cguide.frame_mask = ffi.ptr(guide_fm)          # the guidance masks by x_mask also where the model does not (mask_motion=False)
-                cguide.first_guided = contact_guide.first_guided(diffusion)
                 gk_rows = diffusion.guidance_rows(x.device, "mean" if ddim_eta is None and dpm_order is None else "x0", B)
             cond = self.condition_tokens(**model_kwargs)
             if tuple(cond.shape[:2]) != (B, w.n_cond):       # (e.g. a cloud of fewer points than contact_model.num_points: the loop reads n_cond rows per sample)
@@ -603,10 +614,10 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             # NULL, known and mask or NULLs
             every_form = False
             if cguide is not None:              # every form; a size of its own: the gradient buffers (and always a history buffer)
-                entry = "afm_cmdm_guide_loop_range"
+                entry = guide_names[0]
                 guide_cfg = (None if two else cfg_ref, cfg_ref if two else None)
                 guide_tail = guide_cfg + ffi.impute_ptrs(impute) + (C.byref(cguide),)
-                sizer, size_args, form = "afm_cmdm_guide_loop_workspace_bytes", guide_cfg + (C.byref(cguide),), ("guide", form, cguide.K, cguide.N, bool(cguide.h3d))
+                sizer, size_args, form = guide_names[1], guide_cfg + (C.byref(cguide),), (guide_form[0], form) + guide_form[1:]
             elif tables.dpm is not None:          # every form; a size of its own: the history buffers, which cross the range calls of a chain
                 entry, guide = "afm_cmdm_dpm_loop_range", (None if two else cfg_ref, cfg_ref if two else None) + ffi.impute_ptrs(impute)
                 sizer, size_args, form = "afm_cmdm_dpm_loop_workspace_bytes", guide[:2], ("dpm", form)

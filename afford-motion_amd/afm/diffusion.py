@@ -294,6 +294,221 @@ class ContactGuidance:
         return ops.contact_guidance(g, x, fm, grad=False, energy=True)[1]
 
 
+def _guide_mask(x: torch.Tensor, model_kwargs, who: str):
+    """x_mask of ``model_kwargs`` as the guidance kernels take it: uint8 [B, L] on x's device, or None"""
+    fm = model_kwargs.get("x_mask")
+    if fm is None:
+        return None
+    fm = fm.to(device=x.device).reshape(x.shape[0], -1)
+    if fm.shape[1] != x.shape[1]:
+        raise ValueError(f"{who}: x_mask covers {fm.shape[1]} frames, the sample has {x.shape[1]}")
+    return (fm.view(torch.uint8) if fm.dtype == torch.bool else fm.to(torch.uint8)).contiguous()
+
+
+class JointTargets:
+    """A ``cond_fn`` that pulls named joints to given places in the scene at given frames: a root path through the room, a hand on a handle
+    at frame 120, a pose at the last frame (afm_motion_guidance, HIP; no network, no autograd).
+
+    ``cols``: K ints (K <= 16), the column of the x coordinate of each guided joint in a motion vector of ABSOLUTE positions (``data_repr``
+    "pos" / "pos_rot"), as for `ContactGuidance`; ``JointTargets.h3d(joints, mean, std, ...)`` names joints 0..21 of a HumanML3D-feature
+    motion instead (joint 0 is the root) and takes the ``to_scene`` of `ContactGuidance.h3d`.  ``target`` [B, L, K, 3] float32 holds scene
+    coordinates, ``weight`` [B, L, K] their weights: 0 means no target, and the target value there is never read (it may be NaN).
+    ``scale``: a float or a [B] tensor.  ``t_start``: only steps whose model timestep is < t_start are guided (None: all).  ``x_mask`` is
+    read from ``model_kwargs`` as `ContactGuidance` reads it; nothing else is.
+
+    With p[b,f,k,:] the positions `ContactGuidance` computes (x * std rounded, + mean rounded; h3d: the recovery kernel's output):
+
+        E[b] = sum over valid frames f and joints k of  w * ((dx*dx + dy*dy) + dz*dz),   d = p - target
+
+    not normalised - the weights are the caller's.  Order of the sum: the items e = f * K + k of a sample are dealt to the 256 threads of one
+    block, thread i adds e = i, i + 256, ... in that order, then a fixed wave butterfly and ((r0 + r1) + r2) + r3 over the four waves: a
+    function of the sample alone.  ``guide(x, t, **model_kwargs)`` returns -scale[b] * dE/dx:
+
+        columns:  d = target_a - p_a;  m = w * d;  grad[b,f,cols[k]+a] = ((scale[b] * 2) * std_a) * m                       (one launch)
+        h3d:      S[b,f,k,:] = w * (target - p), carried through the adjoint of the recovery with coef = 2 - the kernel and the six
+                  serial scans `ContactGuidance.h3d` uses (three launches: recovery, targets, adjoint)
+
+    exactly zero in every other column, in padded frames, where w == 0 and in samples with t >= t_start.  ``guide.energy(x, **model_kwargs)``
+    returns E [B].  Handed as ``cond_fn`` it stays in the native loops wherever a `ContactGuidance` does (afm_cmdm_motion_guide_loop_range);
+    `MotionGuidance` sums it with a `ContactGuidance`."""
+
+    def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, target: torch.Tensor, weight: torch.Tensor, scale=1.0,
+                 t_start: Optional[int] = None, _who: str = "JointTargets"):
+        cols = [int(c) for c in cols]
+        if not 1 <= len(cols) <= ffi.GUIDE_MAX_JOINTS:
+            raise ValueError(f"{_who}: 1 to {ffi.GUIDE_MAX_JOINTS} guided joints, got {len(cols)}")
+        if mean.dim() != 1 or std.shape != mean.shape:
+            raise ValueError(f"{_who}: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
+        D = mean.shape[0]
+        for i, c in enumerate(cols):
+            if c < 0 or c + 3 > D:
+                raise ValueError(f"{_who}: the column triple {c}..{c + 2} leaves the motion vector of {D} columns")
+            if any(abs(c - o) < 3 for o in cols[:i]):
+                raise ValueError(f"{_who}: the column triple at {c} overlaps another one")
+        K = len(cols)
+        if not isinstance(target, torch.Tensor) or not isinstance(weight, torch.Tensor) or target.dim() != 4 or target.shape[2:] != (K, 3) or \
+                tuple(weight.shape) != tuple(target.shape[:3]) or not target.is_floating_point() or not weight.is_floating_point():
+            raise ValueError(f"{_who}: target must be a floating [B, L, {K}, 3] tensor and weight [B, L, {K}], got "
+                             f"{tuple(getattr(target, 'shape', ()))} and {tuple(getattr(weight, 'shape', ()))}")
+        if isinstance(scale, torch.Tensor):
+            if scale.dim() > 1 or not scale.is_floating_point():
+                raise ValueError(f"{_who}: `scale` must be a float or a floating [B] tensor, got {tuple(scale.shape)} {scale.dtype}")
+            scale = scale.detach().clone().float().reshape(-1)
+        else:
+            scale = float(scale)
+        self.cols, self.D, self.scale = cols, D, scale
+        self.mean, self.std = ffi.f32c(mean.detach()), ffi.f32c(std.detach())
+        self.target, self.weight = ffi.f32c(target.detach()), ffi.f32c(weight.detach())
+        self.t_start = None if t_start is None else int(t_start)
+        self._dev: Dict[str, tuple] = {}
+        self.joints, self.to_scene = None, None            # (set by JointTargets.h3d alone)
+
+    @classmethod
+    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, target: torch.Tensor, weight: torch.Tensor,
+            to_scene: Optional[torch.Tensor] = None, scale=1.0, t_start: Optional[int] = None) -> "JointTargets":
+        """The targets of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67): ``joints`` are joint indices 0..21 (0: the root),
+        ``to_scene`` a float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity).  See the class docstring."""
+        who = "JointTargets.h3d"
+        joints = ops.h3d_joint_list([int(j) for j in joints], ffi.GUIDE_MAX_JOINTS, who)
+        if mean.dim() != 1 or std.shape != mean.shape:
+            raise ValueError(f"{who}: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
+        if mean.shape[0] < ffi.H3D_COLS:
+            raise ValueError(f"{who}: the joint recovery reads columns 0..{ffi.H3D_COLS - 1}, the motion vector has {mean.shape[0]}")
+        to_scene = ops.h3d_to_scene(to_scene, who)
+        # (the column checks of __init__ run on stand-in triples: the layout names joints, `cols` is not read)
+        self = cls([3 * k for k in range(len(joints))], mean, std, target=target, weight=weight, scale=scale, t_start=t_start, _who=who)
+        self.cols, self.joints, self.to_scene = [], joints, to_scene
+        return self
+
+    @property
+    def K(self) -> int:
+        return len(self.cols if self.joints is None else self.joints)
+
+    def describe(self, x: torch.Tensor, model_kwargs, *, shared=None) -> tuple:
+        """(afm_joint_targets of this sample tensor, x_mask as uint8 or None, what must stay alive with it).  ``shared``: the (mean, std,
+        to_scene, stride) device tensors of the contact term this one is summed with - a sum names one set of them."""
+        who = "JointTargets" if self.joints is None else "JointTargets.h3d"
+        if x.dim() != 3 or x.shape[-1] != self.D:
+            raise ValueError(f"{who}: mean / std describe {self.D} columns, the sample is {tuple(x.shape)}")
+        B, L, K = x.shape[0], x.shape[1], self.K
+        if tuple(self.target.shape) != (B, L, K, 3):
+            raise ValueError(f"{who}: target is {tuple(self.target.shape)} and weight {tuple(self.weight.shape)}, the sample needs "
+                             f"[{B}, {L}, {K}, 3] and [{B}, {L}, {K}]")
+        if isinstance(self.scale, torch.Tensor) and self.scale.numel() != B:
+            raise ValueError(f"{who}: `scale` holds {self.scale.numel()} values for a batch of {B}")
+        fm = _guide_mask(x, model_kwargs, who)
+        if self.joints is not None:                            # (checked against the batch before anything touches the device)
+            ops.h3d_to_scene_on(self.to_scene, B, x.device, who)
+        ffi.require_gpu(x)
+        key = str(x.device)
+        if key not in self._dev:
+            self._dev[key] = (self.mean.to(x.device), self.std.to(x.device), self.target.to(x.device).contiguous(),
+                              self.weight.to(x.device).contiguous())
+        mean, std, target, weight = self._dev[key]
+        scale = self.scale.to(x.device).contiguous() if isinstance(self.scale, torch.Tensor) else \
+            torch.full((B,), self.scale, dtype=torch.float32, device=x.device)
+        lay = ts = None
+        if self.joints is not None:
+            ts, stride = ops.h3d_to_scene_on(self.to_scene, B, x.device, who)
+        if shared is not None:
+            mean, std = shared[0], shared[1]
+            if self.joints is not None:
+                ts, stride = shared[2], shared[3]
+        if self.joints is not None:
+            lay = ffi.H3dLayout()
+            for k, j in enumerate(self.joints):
+                lay.joints[k] = j
+            lay.to_scene, lay.to_scene_stride = ffi.ptr(ts), stride
+        g = ffi.JointTargets()
+        g.target, g.weight, g.scale, g.mean, g.std = target.data_ptr(), weight.data_ptr(), scale.data_ptr(), mean.data_ptr(), std.data_ptr()
+        for k, col in enumerate(self.cols):
+            g.cols[k] = col
+        g.K = K
+        g.t_start = 2**62 if self.t_start is None else self.t_start
+        if lay is not None:
+            g.h3d = C.pointer(lay)
+        return g, fm, (target, weight, mean, std, scale, fm, lay, ts)
+
+    def first_guided(self, diffusion: "GaussianDiffusion") -> int:
+        """the first executed step of a chain on ``diffusion`` that carries this term: the count of its timesteps >= t_start"""
+        return 0 if self.t_start is None else sum(1 for t in diffusion.timestep_map if t >= self.t_start)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        return MotionGuidance(targets=self)(x, t, **model_kwargs)
+
+    def energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        return MotionGuidance(targets=self).energies(x, **model_kwargs)[1]
+
+
+class MotionGuidance:
+    """The sum of a `ContactGuidance` and a `JointTargets` as one ``cond_fn`` (either may be None, not both):
+    grad = grad_contact + grad_targets, each term the float32 result of that guidance alone, joined by one rounded addition per element -
+    ``MotionGuidance(contact, targets)(x, t, **kw)`` equals ``contact(x, t, **kw) + targets(x, t, **kw)`` bit for bit.  Each term keeps its
+    own ``scale`` and ``t_start``: a sample (step by step) or a step (native loops) a term does not guide gets exactly zero from it.  The two
+    terms describe one motion: the same ``mean`` / ``std``, both on columns or both on HumanML3D features, the same ``to_scene`` -
+    ValueError otherwise.  The joint lists may differ; an h3d motion is recovered once per term.  Launches per guided step: the contact
+    term's 2 (h3d: 4) plus the targets' 1 (h3d: 3).  ``energies(x, **kw)`` returns (E_contact or None, E_targets or None)."""
+
+    def __init__(self, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None):
+        if contact is None and targets is None:
+            raise ValueError("MotionGuidance: at least one of contact / targets")
+        if contact is not None and not isinstance(contact, ContactGuidance):
+            raise TypeError(f"MotionGuidance: contact must be a ContactGuidance, not {type(contact).__name__}")
+        if targets is not None and not isinstance(targets, JointTargets):
+            raise TypeError(f"MotionGuidance: targets must be a JointTargets, not {type(targets).__name__}")
+        if contact is not None and targets is not None:
+            if contact.D != targets.D or not torch.equal(contact.mean.cpu(), targets.mean.cpu()) or not torch.equal(contact.std.cpu(), targets.std.cpu()):
+                raise ValueError("MotionGuidance: the two terms de-normalise the motion with different mean / std")
+            if (contact.joints is None) != (targets.joints is None):
+                raise ValueError("MotionGuidance: one term names columns of absolute positions, the other joints of HumanML3D features")
+            a, b = contact.to_scene, targets.to_scene
+            if (a is None) != (b is None) or (a is not None and a is not b and (a.shape != b.shape or a.device != b.device or not torch.equal(a.cpu(), b.cpu()))):          # (compared on the host: no device arithmetic)
+                raise ValueError("MotionGuidance: the two terms place the motion in the scene with different to_scene transforms")
+        self.contact, self.targets = contact, targets
+
+    @property
+    def t_start(self):
+        """None if any term guides every step, else the latest start"""
+        ts = [g.t_start for g in (self.contact, self.targets) if g is not None]
+        return None if any(t is None for t in ts) else max(ts)
+
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion: Optional["GaussianDiffusion"] = None) -> tuple:
+        """(afm_motion_guide of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).  With
+        ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
+        cg = tg = fm = shared = None
+        keep = []
+        if self.contact is not None:
+            cg, fm, ck = self.contact.describe(x, model_kwargs)
+            keep.append((cg, ck))
+            shared = (ck[2], ck[3], ck[7], cg.h3d.contents.to_scene_stride if cg.h3d else 0)
+            if diffusion is not None:
+                cg.first_guided = self.contact.first_guided(diffusion)
+        if self.targets is not None:
+            tg, fm, tk = self.targets.describe(x, model_kwargs, shared=shared)
+            keep.append((tg, tk))
+            if diffusion is not None:
+                tg.first_guided = self.targets.first_guided(diffusion)
+        g = ffi.MotionGuide()
+        if cg is not None:
+            g.contact = C.pointer(cg)
+        if tg is not None:
+            g.targets = C.pointer(tg)
+        return g, fm, keep
+
+    def first_guided(self, diffusion: "GaussianDiffusion") -> int:
+        """the first executed step of a chain on ``diffusion`` that carries any term"""
+        return min(g.first_guided(diffusion) for g in (self.contact, self.targets) if g is not None)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        g, fm, keep = self.describe(x, model_kwargs)
+        timed = any(q is not None and q.t_start is not None for q in (self.contact, self.targets))
+        return ops.motion_guidance(g, x, fm, t.to(x.device) if timed else None)[0]
+
+    def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
+        g, fm, keep = self.describe(x, model_kwargs)
+        return ops.motion_guidance(g, x, fm, grad=False, energy=True)[1:]
+
+
 class _DeviceTables:
     """float32 schedule rows on one device (cast exactly like `_extract_into_tensor(...).float()`)."""
 
@@ -711,11 +926,11 @@ class GaussianDiffusion:
         """p_sample_loop (ddim_eta None) / ddim_sample_loop / dpm_solver_sample_loop (dpm_order not None): the denoiser's
         ``afm_native_loop`` when it has one and nothing needs the host between steps - no generic ``cond_fn``, no rescaled timesteps, no
         condition switch in ``model_kwargs`` - else the progressive generator.  A ``denoised_fn`` that is an `Impute` stays native where
-        the loop names ``impute``, DPM-Solver++ where it names ``dpm_order``, a ``cond_fn`` that is a `ContactGuidance` where it names
+        the loop names ``impute``, DPM-Solver++ where it names ``dpm_order``, a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets` or a `MotionGuidance` where it names
         ``contact_guide`` (GuidedCMDM) or, the plain CMDM, takes it in its private ``_guidance`` bundle; any other ``denoised_fn`` or ``cond_fn``, and a loop that does not name the keyword, sample step by step."""
         native = getattr(model, "afm_native_loop", None)
         impute = denoised_fn if isinstance(denoised_fn, Impute) else None
-        guide = cond_fn if isinstance(cond_fn, ContactGuidance) else None
+        guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance)) else None
         guide_kw = None                    # how the loop takes the guidance: by name, or (the CMDM) inside its private bundle
         if guide is not None and native is not None:
             if _takes(native, "contact_guide"):

@@ -216,6 +216,19 @@ class ContactGuide(C.Structure):
                 ("h3d", C.POINTER(H3dLayout))]
 
 
+class JointTargets(C.Structure):
+    """afm_joint_targets (v7-additive): the joint-target description - target positions [B][L][K][3], weights [B][L][K], scale,
+    de-normalisation, the columns (or ``h3d``: the layout of a HumanML3D-feature motion), and for the loops the term's own first guided step."""
+    _fields_ = [("target", c_f32p), ("weight", c_f32p), ("scale", c_f32p), ("mean", c_f32p), ("std", c_f32p), ("cols", i32 * GUIDE_MAX_JOINTS),
+                ("K", i32), ("first_guided", i32), ("t_start", i64), ("h3d", C.POINTER(H3dLayout))]
+
+
+class MotionGuide(C.Structure):
+    """afm_motion_guide (v7-additive): the sum of the contact and the joint-target guidance (either may be NULL, not both) and, for the
+    loops, the gk rows [T][B] and the guidance's frame mask."""
+    _fields_ = [("contact", C.POINTER(ContactGuide)), ("targets", C.POINTER(JointTargets)), ("gk", c_f32p), ("frame_mask", C.c_void_p)]
+
+
 CFG_FORCE_MASKED = 0x1
 
 EXPORTS = {
@@ -282,6 +295,15 @@ EXPORTS = {
                                        C.c_void_p]),
     "afm_contact_guidance_h3d_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "afm_h3d_joints": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(i32), i32, c_f32p, i32, c_f32p, i32, i32, i32, C.c_void_p]),
+    "afm_motion_guidance_workspace_bytes": (i64, [C.POINTER(MotionGuide), i32, i32, i32]),
+    "afm_motion_guidance": (C.c_int, [C.POINTER(MotionGuide), c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, i32, i32, i32, C.c_void_p, i64,
+                                      C.c_void_p]),
+    "afm_cmdm_motion_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
+                                                         C.POINTER(MotionGuide)]),
+    "afm_cmdm_motion_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                                   C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p,
+                                                   C.c_void_p, C.POINTER(MotionGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                                   C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_cmdm_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
                                                   C.POINTER(ContactGuide)]),
     "afm_cmdm_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),

@@ -22,7 +22,7 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
                      adm_noise: Optional[Dict[str, torch.Tensor]] = None,
                      amdm_noise: Optional[Dict[str, torch.Tensor]] = None, sampler: str = "ddpm",
                      eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None,
-                     contact_impute=None, contact_guidance=None) -> Dict[str, torch.Tensor]:
+                     contact_impute=None, contact_guidance=None, joint_targets=None) -> Dict[str, torch.Tensor]:
     """text_feat [B, text_dim], xyz [B, N, 3] (B = scenes x k_sample, already flattened) ->
     {"contact": [B, N, J] ADM sample, "cond": [B, N, J] AMDM condition, "motion": [B, frames, D]}.
 
@@ -42,7 +42,10 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     on a region to keep clear.  ``motion_impute.known`` [B, frames, D] lives in the normalised motion space.
     ``contact_guidance``: an afm.diffusion.ContactGuidance handed to the motion stage as ``cond_fn`` (the stage stays in its native loop):
     the ``c_pc_contact`` it reads is the stage's own ``cond``, so the generated joints are pulled to the points the first stage marked.  A motion model on HumanML3D features (``data_repr`` "h3d",
-    D = 263) takes ``ContactGuidance.h3d(joints, mean, std, to_scene=...)``, one on absolute positions ``ContactGuidance(cols, mean, std)``."""
+    D = 263) takes ``ContactGuidance.h3d(joints, mean, std, to_scene=...)``, one on absolute positions ``ContactGuidance(cols, mean, std)``.
+    ``joint_targets``: an afm.diffusion.JointTargets (or ``JointTargets.h3d``) - joints pulled to given scene positions at given frames - as
+    the motion stage's ``cond_fn``; with ``contact_guidance`` too the stage is guided by their sum (afm.diffusion.MotionGuidance), still in
+    its native loop."""
     if sampler not in ("ddpm", "ddim", "dpm++"):
         raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpm++', not {sampler!r}")
     if sampler == "dpm++" and float(eta) != 0.0:
@@ -72,9 +75,13 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
         x_mask = torch.zeros(B, frames, dtype=torch.bool, device=dev)
     amdm_kw = dict(c_text_feat=text_feat, c_pc_xyz=xyz, c_pc_contact=cond, x_mask=x_mask)
     mn = amdm_noise or {}
+    cond_fn = contact_guidance
+    if joint_targets is not None:
+        from .diffusion import MotionGuidance
+        cond_fn = joint_targets if contact_guidance is None else MotionGuidance(contact_guidance, joint_targets)
     if guidance_scale is not None:
         from .cmdm import GuidedCMDM
         amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
     motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
-                  denoised_fn=motion_impute, cond_fn=contact_guidance, model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
+                  denoised_fn=motion_impute, cond_fn=cond_fn, model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
     return {"contact": contact, "cond": cond, "motion": motion}

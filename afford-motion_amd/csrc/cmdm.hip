@@ -502,7 +502,8 @@ struct LoopCall {
     const float* known = nullptr;     // imputing loop: [B][L][motion_dim] each, both set (neither: no imputation)
     const uint8_t* mask = nullptr;
     const afm_cfg2_args* cfg2 = nullptr;
-    const afm_contact_guide* guide = nullptr;      // contact-guided loop: the description of the whole batch (NULL: none)
+    afm_motion_guide guide = {};      // guided loop: the terms' descriptions of the whole batch (neither term set: none)
+    bool guided() const { return guide.contact || guide.targets; }
 };
 
 struct SubBatch : SubRange {
@@ -512,13 +513,13 @@ struct SubBatch : SubRange {
     hipStream_t branch;
     hipEvent_t x_ready, u_ready;
     float* hist;                      // 2M loop only: the previous step's final x0 [count][L * motion_dim], behind every evaluation's workspace
-    float* ggrad;                     // contact-guided loop only: the step's gradient [count][L * motion_dim], behind the history, and the
-    char* gws;                        //   workspace of afm_contact_guidance for `count` samples behind it
+    float* ggrad;                     // guided loop only: the step's gradient [count][L * motion_dim], behind the history, and the
+    char* gws;                        //   workspace of afm_motion_guidance for `count` samples behind it
     int64_t gws_bytes;
 };
 
 // carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
-int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist, const afm_contact_guide* guide = nullptr) {
+int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist, const afm_motion_guide* guide = nullptr) {
     sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
     int64_t off = sb->ws.bytes;
     for (int i = 0; i < g.n; ++i) {
@@ -533,11 +534,11 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
         off += align256((int64_t)sb->count * L * w.motion_dim * 4);
     }
     sb->ggrad = nullptr; sb->gws = nullptr; sb->gws_bytes = 0;
-    if (guide) {                      // (carved for the contact-guided loop alone)
+    if (guide) {                      // (carved for the guided loops alone)
         sb->ggrad = base ? (float*)(base + off) : nullptr;
         off += align256((int64_t)sb->count * L * w.motion_dim * 4);
         sb->gws = base ? base + off : nullptr;
-        sb->gws_bytes = afm_contact_guide_workspace_bytes(guide, sb->count, L);
+        sb->gws_bytes = afm_motion_guide_workspace_bytes(guide, sb->count, L, w.motion_dim);
         off += align256(sb->gws_bytes);
     }
     return off;
@@ -545,9 +546,11 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
 
 // the loop workspace of either public description of the guidance (neither: the unguided loop's); AFM_E_BADARG as the loop itself
 int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams,
-                             bool hist = false, const afm_contact_guide* guide = nullptr) {
+                             bool hist = false, const afm_motion_guide* guide = nullptr) {
     if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
-    if (guide && afm_contact_guidance_workspace_bytes(B, guide->N, guide->K) < 0) return AFM_E_BADARG;
+    if (guide && !guide->contact && !guide->targets) return AFM_E_BADARG;
+    if (guide && guide->contact && afm_contact_guidance_workspace_bytes(B, guide->contact->N, guide->contact->K) < 0) return AFM_E_BADARG;
+    if (guide && guide->targets && (guide->targets->K <= 0 || guide->targets->K > AFM_GUIDE_MAX_JOINTS)) return AFM_E_BADARG;
     Guidance g = {};
     if ((one || two) && make_guidance(*w, one, two, false, nullptr, &g) != 0) return AFM_E_BADARG;
     const int n = sub_count(B, n_streams, MAX_SUB);
@@ -582,9 +585,9 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     if (g.n > 1 && g.branch_streams) return AFM_E_UNSUPPORTED;       // (four hardware queues do not fit 2 sub-batches x 3 evaluations)
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     if (a.dpm && (!a.ddim || a.noise_term() || a.step_noise || a.first_step < 0)) return AFM_E_BADARG;
-    if (c.guide) {
-        AFM_TRY(afm_contact_guide_check(c.guide, c.L, c.w->motion_dim));
-        if (!c.guide->gk || c.guide->first_guided < 0) return AFM_E_BADARG;
+    if (c.guided()) {
+        AFM_TRY(afm_motion_guide_check(&c.guide, c.L, c.w->motion_dim));
+        if (!c.guide.gk || (c.guide.contact && c.guide.contact->first_guided < 0) || (c.guide.targets && c.guide.targets->first_guided < 0)) return AFM_E_BADARG;
     }
     p->nsub = 0;
     if (a.B == 0) return 0;
@@ -595,7 +598,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         SubBatch& sb = p->sb[s];
         sb = {};
         sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guide, c.guide);
+        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guided(), c.guided() ? &c.guide : nullptr);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
         if (p->branch_streams) sb.branch = (hipStream_t)g.branch_streams[s];
     }
@@ -613,8 +616,8 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     p->w = *c.w;
     p->w.flags = a.loop_flags(p->w.flags);
     // (an imputing loop likewise: the update fused into the motion_layer epilogue is contracted and has no place for the select)
-    // (a contact-guided loop too: no place for the gradient term either)
-    if (g.n || c.mask || c.guide) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
+    // (a contact- or target-guided loop too: no place for the gradient term either)
+    if (g.n || c.mask || c.guided()) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
     if (p->nsub >= 2 && ((p->w.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < p->nsub; ++s) big = big && (int64_t)p->sb[s].count * T >= 4096;
@@ -648,16 +651,18 @@ int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_d
     return forward_impl(l.p.w, sub_x(l, sb), rows->t, sub_cond(l, sb), sub_fmask(l, sb), nullptr, dd, sb.count, c.L, sb.ws, j == 0, sb.stream, rec);
 }
 
-// does executed step j of the call carry the contact-guidance term (a contact-guided loop, at or behind its first guided step)
-inline bool guided_step(const Loop& l, int j) { return l.c.guide && l.c.a.first_step + j >= l.c.guide->first_guided; }
+// the terms of the guidance executed step j of the call carries: each one at or behind its own first guided step
+inline bool contact_step(const Loop& l, int j) { return l.c.guide.contact && l.c.a.first_step + j >= l.c.guide.contact->first_guided; }
+inline bool targets_step(const Loop& l, int j) { return l.c.guide.targets && l.c.a.first_step + j >= l.c.guide.targets->first_guided; }
+inline bool guided_step(const Loop& l, int j) { return contact_step(l, j) || targets_step(l, j); }
 
-// the gradient of (sub-batch, step j) at the x the step's evaluations read, on the sub-batch's stream: the two launches of
-// afm_contact_guidance (h3d description: four) into the sub-batch's gradient buffer
-int guide_launch(const Loop& l, const SubBatch& sb) {
+// the gradient of (sub-batch, step j) at the x the step's evaluations read, on the sub-batch's stream: the launches of afm_motion_guidance
+// for the step's terms (contact: two, h3d four; targets: one, h3d three) into the sub-batch's gradient buffer
+int guide_launch(const Loop& l, const SubBatch& sb, int j) {
     // (the guidance's own mask: the denoiser's frame_mask is NULL for a model that does not mask its motion tokens)
-    const uint8_t* fm = l.c.guide->frame_mask ? l.c.guide->frame_mask + (int64_t)sb.start * l.c.L : nullptr;
-    return afm_contact_guidance_sub(l.c.guide, sb.start, sub_x(l, sb), fm, nullptr, sb.ggrad, nullptr, sb.count, l.c.L, l.p.w.motion_dim,
-                                    sb.gws, sb.gws_bytes, sb.stream);
+    const uint8_t* fm = l.c.guide.frame_mask ? l.c.guide.frame_mask + (int64_t)sb.start * l.c.L : nullptr;
+    return afm_motion_guidance_sub(&l.c.guide, contact_step(l, j), targets_step(l, j), sb.start, sub_x(l, sb), fm, nullptr, sb.ggrad, nullptr, nullptr,
+                                   sb.count, l.c.L, l.p.w.motion_dim, sb.gws, sb.gws_bytes, sb.stream);
 }
 
 // the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and each branch's, wsb[i].x0 - the list's last branch is the
@@ -673,7 +678,7 @@ int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const
     if (l.c.mask) { u.known = l.c.known + (int64_t)sb.start * l.p.row; u.mask = l.c.mask + (int64_t)sb.start * l.p.row; }
     u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
     if (l.c.a.dpm) { u.x0_prev = l.c.a.first_step + j > 0 ? sb.hist : nullptr; u.x0_keep = sb.hist; }
-    if (guided_step(l, j)) { u.grad = sb.ggrad; u.gk = l.c.guide->gk + ((int64_t)(l.c.a.n_steps - 1 - j) * l.c.a.B + sb.start); }
+    if (guided_step(l, j)) { u.grad = sb.ggrad; u.gk = l.c.guide.gk + ((int64_t)(l.c.a.n_steps - 1 - j) * l.c.a.B + sb.start); }
     return afm_sampling_update(u, sb.count, sb.stream);
 }
 
@@ -684,7 +689,7 @@ int loop_step(const Loop& l, const SubBatch& sb, int j) {
     const Guidance& g = l.p.g;
     StepRows rows;
     afm_ddpm_args dd;
-    if (guided_step(l, j)) AFM_TRY(guide_launch(l, sb));
+    if (guided_step(l, j)) AFM_TRY(guide_launch(l, sb, j));
     AFM_TRY(cond_forward(l, sb, j, &rows, &dd, nullptr));
     for (int i = 0; i < g.n; ++i) {
         // every branch behind the conditioned evaluation on the sub-batch's stream, on its own workspace - but the last one on the branch
@@ -704,7 +709,7 @@ int loop_step(const Loop& l, const SubBatch& sb, int j) {
         }
         AFM_TRY(rc);
     }
-    if (!(g.n || c.a.ddim || c.mask || c.guide)) return 0;
+    if (!(g.n || c.a.ddim || c.mask || c.guided())) return 0;
     AFM_TRY(update_launch(l, sb, rows, dd.noise, j));
     if (l.p.branch_streams) (void)hipEventRecord(sb.x_ready, sb.stream);       // x and its padded copy of the next step
     return 0;
@@ -917,17 +922,20 @@ extern "C" int afm_cmdm_dpm_loop_range(const afm_cmdm_weights* w, float* x, cons
 extern "C" int64_t afm_cmdm_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
                                                        const afm_cfg2_args* cfg2, const afm_contact_guide* guide) {
     if ((cfg && cfg2) || !guide) return AFM_E_BADARG;
-    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, guide);
+    const afm_motion_guide sum = {guide, nullptr, nullptr, nullptr};
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, &sum);
 }
 
-extern "C" int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
-                                         const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
-                                         const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
-                                         const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_contact_guide* guide,
-                                         int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
-                                         void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
-                                         void* stream) {
-    if (first_step < 0 || !guide || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
+namespace {
+
+// both guided entries: the separate-update loop of the form the rows and the guidance name, with the terms' gradient launches in front of
+// a guided step's evaluations and grad / gk in its update launch
+int guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask, const float* step_noise,
+                     const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm, const float* d_c1, const float* d_c2,
+                     const float* d_sigma, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
+                     const afm_motion_guide& guide, int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                     void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
+    if (first_step < 0 || (!guide.contact && !guide.targets) || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
     if ((rows != nullptr) + (dpm != nullptr) + (d_c1 || d_c2 || d_sigma ? 1 : 0) != 1) return AFM_E_BADARG;          // one kind of rows
     if (dpm && (!dpm->a || !dpm->b || !dpm->c || step_noise)) return AFM_E_BADARG;
     if (cfg2 && (!frame_mask || !cfg2_ok(cfg2))) return AFM_E_BADARG;
@@ -937,4 +945,39 @@ extern "C" int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, co
                   dpm ? 0 : sample_index0, B, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2, guide};
     c.a.dpm = dpm != nullptr;
     return sample_loop_impl(c);
+}
+
+}  // namespace
+
+extern "C" int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                         const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                         const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                         const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_contact_guide* guide,
+                                         int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                         void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                         void* stream) {
+    if (!guide) return AFM_E_BADARG;
+    return guide_loop_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask,
+                            afm_motion_guide{guide, nullptr, guide->gk, guide->frame_mask}, n_steps, first_step, seed, sample_index0, B, L, sched_scratch,
+                            workspace, workspace_bytes, n_streams, side_streams, stream);
+}
+
+// The same loop with the sum of the contact and the joint-target guidance as its description (afm_motion_guide): the terms a step has
+// reached are computed into the one gradient buffer, the targets' launch adding to what the contact term wrote.
+extern "C" int64_t afm_cmdm_motion_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                              const afm_cfg2_args* cfg2, const afm_motion_guide* guide) {
+    if ((cfg && cfg2) || !guide) return AFM_E_BADARG;
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, guide);
+}
+
+extern "C" int afm_cmdm_motion_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                                const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows,
+                                                const afm_dpm_rows* dpm, const float* d_c1, const float* d_c2, const float* d_sigma,
+                                                const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
+                                                const afm_motion_guide* guide, int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0,
+                                                int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
+                                                void* const* side_streams, void* stream) {
+    if (!guide) return AFM_E_BADARG;
+    return guide_loop_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask, *guide,
+                            n_steps, first_step, seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
 }

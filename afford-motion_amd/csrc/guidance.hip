@@ -400,6 +400,200 @@ __global__ __launch_bounds__(256) void h3d_adjoint_kernel(const H3dAdjDev a, con
         if (!(mb && mb[f])) gb[(int64_t)f * D] = (ks * a.std[0]) * sT[f];
 }
 
+// ---- joint-position targets (afm_joint_targets): E = sum over valid (f, k) of w * |p - g|^2 on the positions p the kernels above compute.
+struct TargetDev {
+    const float *target, *weight, *mean, *std, *scale;
+    int cols[AFM_GUIDE_MAX_JOINTS];
+    int K, L, D;
+    int64_t t_start;
+};
+
+// the block's sum of one value per thread in a fixed order: the wave butterfly, then ((r0 + r1) + r2) + r3; valid in thread 0
+__device__ __forceinline__ float target_block_sum(float v, float* red) {
+#pragma clang fp contract(off)
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one item's energy term w * ((dx*dx + dy*dy) + dz*dz), d = p - g
+__device__ __forceinline__ float target_term(float w, float p0, float p1, float p2, const float* __restrict__ gp) {
+#pragma clang fp contract(off)
+    const float dx = p0 - gp[0], dy = p1 - gp[1], dz = p2 - gp[2];
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    return w * ((xx + yy) + zz);
+}
+
+// The column form, one block per (frame blockIdx.x, sample blockIdx.y): thread i < 3 K the coordinate a = i % 3 of joint k = i / 3,
+// d = g_a - p_a, m = w * d, term = ((scale[b] * 2) * std_a) * m; every other column of the row, a joint with w == 0 (its target is not
+// read), a padded frame and a sample with t[b] >= t_start give the term 0.  ACC: row[d] = row[d] + term for EVERY column of the row (one
+// rounded addition per element on what the contact term wrote), else row[d] = term.  Block 0 of a sample adds its energy: thread i the
+// items e = f * K + k = i, i + 256, ... in that order, then target_block_sum.
+template <bool ACC>
+__global__ __launch_bounds__(256) void target_cols_kernel(const TargetDev g, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                          const int64_t* __restrict__ t, float* __restrict__ grad, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
+    __shared__ float red[4];
+    const int b = blockIdx.y, f = blockIdx.x, K = g.K, L = g.L, D = g.D;
+#pragma unroll
+    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
+        if (threadIdx.x == k) scols[k] = g.cols[k];
+    __syncthreads();
+    if (f == 0 && energy) {
+        float acc = 0.f;
+        for (int e = threadIdx.x; e < L * K; e += 256) {
+            const int ff = e / K, k = e - ff * K;
+            if (fmask && fmask[(int64_t)b * L + ff]) continue;
+            const int64_t o = ((int64_t)b * L + ff) * K + k;
+            const float w = g.weight[o];
+            if (w == 0.f) continue;
+            const float* xrow = x + ((int64_t)b * L + ff) * D;
+            const int col = scols[k];
+            const float p0 = h3d_u(xrow, g.mean, g.std, col), p1 = h3d_u(xrow, g.mean, g.std, col + 1), p2 = h3d_u(xrow, g.mean, g.std, col + 2);
+            acc = acc + target_term(w, p0, p1, p2, g.target + o * 3);
+        }
+        acc = target_block_sum(acc, red);
+        if (threadIdx.x == 0) energy[b] = acc;
+    }
+    if (!grad) return;
+    float* row = grad + ((int64_t)b * L + f) * D;
+    const float* xrow = x + ((int64_t)b * L + f) * D;
+    const bool guided = !(fmask && fmask[(int64_t)b * L + f]) && !(t && t[b] >= g.t_start);
+    const float ks = g.scale[b] * 2.f;
+    for (int d = threadIdx.x; d < D; d += 256) {
+        float term = 0.f;
+        if (guided)
+            for (int k = 0; k < K; ++k) {
+                const int a = d - scols[k];
+                if (a < 0 || a >= 3) continue;
+                const int64_t o = ((int64_t)b * L + f) * K + k;
+                const float w = g.weight[o];
+                if (w == 0.f) break;
+                const float dd = g.target[o * 3 + a] - h3d_u(xrow, g.mean, g.std, d);
+                const float m = w * dd;
+                term = (ks * g.std[d]) * m;
+                break;
+            }
+        row[d] = ACC ? row[d] + term : term;
+    }
+}
+
+// The h3d form, one block per sample: the recovery's positions pos[b][f][k][3] (the targets' own order) -> S[b][f][k][3] = w * (g - p),
+// zero where w == 0 (the target is not read) or the frame is padded, for the adjoint; scale, t_start and the rows are the adjoint's
+// business.  The energy as in the column form: thread i the items e = i, i + 256, ... in that order, then target_block_sum.
+__global__ __launch_bounds__(256) void target_h3d_kernel(const TargetDev g, const float* __restrict__ pos, const uint8_t* __restrict__ fmask,
+                                                         float* __restrict__ S, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    __shared__ float red[4];
+    const int b = blockIdx.x, K = g.K, L = g.L;
+    float acc = 0.f;
+    for (int e = threadIdx.x; e < L * K; e += 256) {
+        const int f = e / K;
+        const int64_t o = (int64_t)b * L * K + e;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+        const float w = (fmask && fmask[(int64_t)b * L + f]) ? 0.f : g.weight[o];
+        if (w != 0.f) {
+            const float* pp = pos + o * 3;
+            const float* gp = g.target + o * 3;
+            const float p0 = pp[0], p1 = pp[1], p2 = pp[2];
+            s0 = w * (gp[0] - p0); s1 = w * (gp[1] - p1); s2 = w * (gp[2] - p2);
+            acc = acc + target_term(w, p0, p1, p2, gp);
+        }
+        if (S) { S[o * 3] = s0; S[o * 3 + 1] = s1; S[o * 3 + 2] = s2; }
+    }
+    if (!energy) return;
+    acc = target_block_sum(acc, red);
+    if (threadIdx.x == 0) energy[b] = acc;
+}
+
+// h3d_adjoint_kernel's result ADDED to the rows the contact term wrote, one launch: the adjoint's passes, scans and expressions repeated
+// (that kernel keeps its code) with the sample's rows going to tmp[b][L][D], then grad = grad + tmp, one rounded addition per element -
+// the zeros of a padded frame, of the other columns and of a sample with t[b] >= t_start included.
+__global__ __launch_bounds__(256) void h3d_adjoint_add_kernel(const H3dAdjDev a, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                              const int64_t* __restrict__ t, const float* __restrict__ cs, const float* __restrict__ S,
+                                                              float* __restrict__ tmp, float* __restrict__ grad) {
+#pragma clang fp contract(off)
+    extern __shared__ float sh[];                   // [H3D_SCAN_ROWS][L]
+    __shared__ int sj[AFM_GUIDE_MAX_JOINTS];
+    __shared__ float sA[12];
+    const int b = blockIdx.x, L = a.L, D = a.D, K = a.K;
+    float *sgX = sh, *sgZ = sh + L, *sT = sh + 2 * L, *sc = sh + 3 * L, *ss = sh + 4 * L, *svx = sh + 5 * L, *svz = sh + 6 * L;
+    float* gb = tmp + (int64_t)b * L * D;
+    float* out = grad + (int64_t)b * L * D;
+    for (int64_t i = threadIdx.x; i < (int64_t)L * D; i += 256) gb[i] = 0.f;
+    if (!(t && t[b] >= a.t_start)) {                // (uniform over the block)
+#pragma unroll
+        for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
+            if (threadIdx.x == k) sj[k] = a.joints[k];
+        stage_to_scene(a.to_scene, (int64_t)b * a.ts_stride, sA);
+        __syncthreads();
+        const float* xb = x + (int64_t)b * L * D;
+        const uint8_t* mb = fmask ? fmask + (int64_t)b * L : nullptr;
+        const float ks = a.scale[b] * a.coef;
+        for (int f = threadIdx.x; f < L; f += 256) {
+            const float* xrow = xb + (int64_t)f * D;
+            float* row = gb + (int64_t)f * D;
+            const bool pad = mb && mb[f];
+            const float c = cs[((int64_t)b * L + f) * 2], s = cs[((int64_t)b * L + f) * 2 + 1];
+            sc[f] = c; ss[f] = s;
+            svx[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 1);
+            svz[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 2);
+            float gX = 0.f, gZ = 0.f, T = 0.f;
+            for (int k = 0; k < K; ++k) {
+                const float* Sp = S + (((int64_t)b * L + f) * K + k) * 3;
+                const float S0 = Sp[0], S1 = Sp[1], S2 = Sp[2];
+                const float Gx = (sA[0] * S0 + sA[4] * S1) + sA[8] * S2;
+                const float Gy = (sA[1] * S0 + sA[5] * S1) + sA[9] * S2;
+                const float Gz = (sA[2] * S0 + sA[6] * S1) + sA[10] * S2;
+                gX = gX + Gx; gZ = gZ + Gz;
+                const int j = sj[k];
+                if (j == 0) {
+                    if (!pad) row[3] = (ks * a.std[3]) * Gy;
+                    continue;
+                }
+                const int col = 4 + 3 * (j - 1);
+                const float lx = h3d_u(xrow, a.mean, a.std, col), lz = h3d_u(xrow, a.mean, a.std, col + 2);
+                T = T + (Gx * (-lx * s - lz * c) + Gz * (lx * c - lz * s));
+                if (!pad) {
+                    row[col] = (ks * a.std[col]) * (Gx * c + Gz * s);
+                    row[col + 1] = (ks * a.std[col + 1]) * Gy;
+                    row[col + 2] = (ks * a.std[col + 2]) * (Gz * c - Gx * s);
+                }
+            }
+            sgX[f] = gX; sgZ[f] = gZ; sT[f] = T;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0 || threadIdx.x == 64) {
+            float* v = threadIdx.x == 0 ? sgX : sgZ;
+            float acc = 0.f;
+            for (int f = L - 1; f >= 0; --f) { acc = acc + v[f]; v[f] = acc; }
+        }
+        __syncthreads();
+        for (int f = threadIdx.x; f < L; f += 256) {
+            if (f == 0) { sT[0] = 2.f * sT[0]; continue; }
+            const float SX = sgX[f], SZ = sgZ[f], c = sc[f], s = ss[f], vx = svx[f - 1], vz = svz[f - 1];
+            sT[f] = 2.f * ((sT[f] + SX * (-vx * s - vz * c)) + SZ * (vx * c - vz * s));
+            if (!(mb && mb[f - 1])) {
+                float* row = gb + (int64_t)(f - 1) * D;
+                row[1] = (ks * a.std[1]) * (SX * c + SZ * s);
+                row[2] = (ks * a.std[2]) * (SZ * c - SX * s);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float acc = 0.f;
+            for (int f = L - 1; f >= 0; --f) { const float v = sT[f]; sT[f] = acc; acc = acc + v; }
+        }
+        __syncthreads();
+        for (int f = threadIdx.x; f < L; f += 256)
+            if (!(mb && mb[f])) gb[(int64_t)f * D] = (ks * a.std[0]) * sT[f];
+    }
+    __syncthreads();                                // (the block's own global writes to tmp are visible to it behind the barrier)
+    for (int64_t i = threadIdx.x; i < (int64_t)L * D; i += 256) out[i] = out[i] + gb[i];
+}
+
 int64_t guide_nblk(int N, int K) { return ((int64_t)N * K + 255) / 256; }
 
 // the h3d form's buffers behind the three of the absolute form: positions [B][K][L][3], c / s [B][L][2], S [B][L][K][3]
@@ -520,6 +714,143 @@ __attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_con
 extern "C" int afm_contact_guidance(const afm_contact_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
                                     float* energy, int32_t B, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes, void* stream) {
     return afm_contact_guidance_sub(g, 0, x, frame_mask, t, grad, energy, B, L, D, workspace, workspace_bytes, stream);
+}
+
+// ---- joint targets and the sum of the two guidances (afm_motion_guide)
+namespace {
+
+int64_t targets_workspace_bytes(const afm_joint_targets* a, bool add, int64_t count, int64_t L, int64_t D) {
+    if (!a->h3d) return 0;
+    // positions [count][L][K][3], S likewise, c / s [count][L][2]; added to a contact term: the adjoint's own rows [count][L][D]
+    return h3d_extra_bytes(count, L, a->K) + (add ? afm_loop::align256(count * L * D * 4) : 0);
+}
+
+int targets_check(const afm_joint_targets* a, int32_t L, int32_t D) {
+    if (!a->target || !a->weight || !a->mean || !a->std || !a->scale || L <= 0 || D <= 0) return AFM_E_BADARG;
+    if (a->K <= 0 || a->K > AFM_GUIDE_MAX_JOINTS) return AFM_E_BADARG;
+    if (a->h3d) {
+        if (D < H3D_COLS || !h3d_joint_list_ok(a->h3d->joints, a->K)) return AFM_E_BADARG;
+        if (a->h3d->to_scene_stride != 0 && a->h3d->to_scene_stride != 12) return AFM_E_BADARG;
+        if ((size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
+    } else {
+        for (int k = 0; k < a->K; ++k) {
+            if (a->cols[k] < 0 || a->cols[k] + 3 > D) return AFM_E_BADARG;
+            for (int j = 0; j < k; ++j)
+                if (a->cols[k] < a->cols[j] + 3 && a->cols[j] < a->cols[k] + 3) return AFM_E_BADARG;          // overlapping triples
+        }
+    }
+    if (L > 65535 || (int64_t)L * a->K > (int64_t)1 << 30) return AFM_E_UNSUPPORTED;
+    return 0;
+}
+
+// the targets' launches on the samples [start, start + count); add: grad holds the contact term's result, the sum goes there
+int targets_sub(const afm_joint_targets* a, bool add, int32_t start, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                float* energy, int32_t count, int32_t L, int32_t D, char* wp, hipStream_t s) {
+    TargetDev g = {};
+    g.target = a->target + (int64_t)start * L * a->K * 3; g.weight = a->weight + (int64_t)start * L * a->K;
+    g.mean = a->mean; g.std = a->std; g.scale = a->scale + start;
+    for (int k = 0; k < a->K; ++k) g.cols[k] = a->h3d ? 0 : a->cols[k];
+    g.K = a->K; g.L = L; g.D = D; g.t_start = a->t_start;
+    if (!a->h3d) {
+        const dim3 grid(grad ? (unsigned)L : 1u, (unsigned)count);
+        if (add) hipLaunchKernelGGL(target_cols_kernel<true>, grid, dim3(256), 0, s, g, x, frame_mask, t, grad, energy);
+        else hipLaunchKernelGGL(target_cols_kernel<false>, grid, dim3(256), 0, s, g, x, frame_mask, t, grad, energy);
+        AFM_CHECK_LAUNCH();
+        return 0;
+    }
+    const afm_h3d_layout& lay = *a->h3d;
+    const int64_t klb = afm_loop::align256((int64_t)count * a->K * L * 3 * 4);
+    float* pos = (float*)wp; wp += klb;
+    float* S = (float*)wp; wp += klb;
+    float* cs = (float*)wp; wp += afm_loop::align256((int64_t)count * L * 2 * 4);
+    float* tmp = (float*)wp;
+    const float* to_scene = lay.to_scene ? lay.to_scene + (int64_t)start * lay.to_scene_stride : nullptr;
+    const size_t scan_lds = (size_t)H3D_SCAN_ROWS * L * 4;
+    H3dDev h = {};
+    h.mean = a->mean; h.std = a->std; h.to_scene = to_scene; h.ts_stride = lay.to_scene_stride;
+    for (int k = 0; k < a->K; ++k) h.joints[k] = lay.joints[k];
+    h.J = a->K; h.L = L; h.D = D;
+    h.out_b = (int64_t)L * a->K * 3; h.out_j = 3; h.out_f = (int64_t)a->K * 3;          // [count][L][K][3]: the targets' own order
+    hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, h, x, frame_mask, pos, grad ? cs : nullptr);
+    AFM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(target_h3d_kernel, dim3((unsigned)count), dim3(256), 0, s, g, pos, frame_mask, grad ? S : nullptr, energy);
+    AFM_CHECK_LAUNCH();
+    if (!grad) return 0;
+    H3dAdjDev ad = {};
+    ad.mean = a->mean; ad.std = a->std; ad.scale = g.scale; ad.to_scene = to_scene; ad.ts_stride = lay.to_scene_stride;
+    for (int k = 0; k < a->K; ++k) ad.joints[k] = lay.joints[k];
+    ad.K = a->K; ad.L = L; ad.D = D; ad.coef = 2.f; ad.t_start = a->t_start;
+    if (add) hipLaunchKernelGGL(h3d_adjoint_add_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, ad, x, frame_mask, t, cs, S, tmp, grad);
+    else hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, ad, x, frame_mask, t, cs, S, grad);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+// what a sum must satisfy before anything is enqueued (L, D: the motion's)
+__attribute__((visibility("hidden"))) int afm_motion_guide_check(const afm_motion_guide* g, int32_t L, int32_t D) {
+    if (!g || (!g->contact && !g->targets)) return AFM_E_BADARG;
+    if (g->contact) {
+        const int rc = afm_contact_guide_check(g->contact, L, D);
+        if (rc != 0) return rc;
+    }
+    if (g->targets) {
+        const int rc = targets_check(g->targets, L, D);
+        if (rc != 0) return rc;
+    }
+    if (g->contact && g->targets) {
+        const afm_contact_guide* c = g->contact;
+        const afm_joint_targets* a = g->targets;
+        if (c->mean != a->mean || c->std != a->std || !c->h3d != !a->h3d) return AFM_E_BADARG;
+        if (c->h3d && (c->h3d->to_scene != a->h3d->to_scene || c->h3d->to_scene_stride != a->h3d->to_scene_stride)) return AFM_E_BADARG;
+    }
+    return 0;
+}
+
+// the workspace of `count` samples of a checked sum: the contact term's, then the targets'
+__attribute__((visibility("hidden"))) int64_t afm_motion_guide_workspace_bytes(const afm_motion_guide* g, int32_t count, int32_t L, int32_t D) {
+    int64_t n = g->contact ? afm_loop::align256(afm_contact_guide_workspace_bytes(g->contact, count, L)) : 0;
+    if (g->targets) n += targets_workspace_bytes(g->targets, g->contact != nullptr, count, L, D);
+    return n;
+}
+
+// the samples [start, start + count) of the sum's batch; x, frame_mask, t, grad and the energies already point at sample `start`.
+// run_contact / run_targets: the terms this call computes (a loop step in front of a term's first_guided leaves it out)
+__attribute__((visibility("hidden"))) int afm_motion_guidance_sub(const afm_motion_guide* g, bool run_contact, bool run_targets, int32_t start, const float* x,
+                                                                  const uint8_t* frame_mask, const int64_t* t, float* grad, float* energy_contact,
+                                                                  float* energy_targets, int32_t count, int32_t L, int32_t D, void* workspace,
+                                                                  int64_t workspace_bytes, void* stream) {
+    const int rc = afm_motion_guide_check(g, L, D);
+    if (rc != 0) return rc;
+    run_contact = run_contact && g->contact;
+    run_targets = run_targets && g->targets;
+    if (!x || (!grad && !energy_contact && !energy_targets) || start < 0 || count < 0 || (energy_contact && !run_contact) ||
+        (energy_targets && !run_targets) || (!run_contact && !run_targets)) return AFM_E_BADARG;
+    if (count > 65535) return AFM_E_UNSUPPORTED;
+    if (count == 0) return 0;
+    if (!workspace || workspace_bytes < afm_motion_guide_workspace_bytes(g, count, L, D)) return AFM_E_WORKSPACE;
+    const int64_t cbytes = g->contact ? afm_loop::align256(afm_contact_guide_workspace_bytes(g->contact, count, L)) : 0;
+    if (run_contact && (grad || energy_contact))
+    {
+        const int rcc = afm_contact_guidance_sub(g->contact, start, x, frame_mask, t, grad, energy_contact, count, L, D, workspace, cbytes, stream);
+        if (rcc != 0) return rcc;
+    }
+    if (run_targets && (grad || energy_targets))
+        return targets_sub(g->targets, run_contact && grad, start, x, frame_mask, t, grad, energy_targets, count, L, D, (char*)workspace + cbytes,
+                           (hipStream_t)stream);
+    return 0;
+}
+
+extern "C" int64_t afm_motion_guidance_workspace_bytes(const afm_motion_guide* g, int32_t B, int32_t L, int32_t D) {
+    if (B < 0 || afm_motion_guide_check(g, L, D) != 0) return AFM_E_BADARG;
+    return afm_motion_guide_workspace_bytes(g, B, L, D) + 256;          // (never zero: the column-form targets alone need none)
+}
+
+extern "C" int afm_motion_guidance(const afm_motion_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                                   float* energy_contact, float* energy_targets, int32_t B, int32_t L, int32_t D, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    return afm_motion_guidance_sub(g, true, true, 0, x, frame_mask, t, grad, energy_contact, energy_targets, B, L, D, workspace, workspace_bytes, stream);
 }
 
 extern "C" int afm_h3d_joints(const float* x, const float* mean, const float* std, const uint8_t* frame_mask, const int32_t* joints, int32_t J,

@@ -27,6 +27,15 @@ __attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_con
 
 __attribute__((visibility("hidden"))) int afm_contact_guide_check(const afm_contact_guide* g, int32_t L, int32_t D);
 
+// guidance.hip: the sum of the contact and the joint-target guidance (afm_motion_guide; either term may be missing) - its checks, the
+// workspace of `count` samples of a checked sum, and afm_motion_guidance on the samples [start, start + count), computing the terms named
+__attribute__((visibility("hidden"))) int afm_motion_guide_check(const afm_motion_guide* g, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int64_t afm_motion_guide_workspace_bytes(const afm_motion_guide* g, int32_t count, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int afm_motion_guidance_sub(const afm_motion_guide* g, bool run_contact, bool run_targets, int32_t start, const float* x,
+                                                                  const uint8_t* frame_mask, const int64_t* t, float* grad, float* energy_contact,
+                                                                  float* energy_targets, int32_t count, int32_t L, int32_t D, void* workspace,
+                                                                  int64_t workspace_bytes, void* stream);
+
 namespace afm_loop {
 
 // ---- the sampling update x_t -> x_next of one launch, [B][per_sample] floats: every DDPM, DDIM and guided update outside the fused GEMM /

@@ -942,6 +942,64 @@ int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* 
                               void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
                               void* stream);
 
+/* Joint-position targets (v7-additive): "joint k is at target[b,f,k,:] in the scene at frame f", a second energy on the joint positions
+ * p[b,f,k,:] the contact guidance computes - the columns of x (cols; p = x * std rounded, + mean rounded) or, with `h3d` set, the output
+ * of the recovery kernel for the layout's joints.  float32, every operation rounded on its own:
+ *   E[b] = sum over valid frames f and joints k of  w * ((dx*dx + dy*dy) + dz*dz),   d = p - target,   w = weight[b,f,k]
+ * not normalised.  The sum's order: the items e = f * K + k of a sample are dealt to the 256 threads of one block, thread i adds
+ * e = i, i + 256, ... in that order to 0, then the fixed butterfly of a wave and ((r0 + r1) + r2) + r3 over the four waves - a function of
+ * the sample alone.  An item with w == 0 or in a padded frame adds exactly 0, and its target is NOT READ (it may be NaN).
+ *   column form:  d = target_a - p_a;  m = w * d;  grad[b,f,cols[k]+a] = ((scale[b] * 2) * std_a) * m       (one launch)
+ *   h3d form:     S[b,f,k,:] = w * (target - p) (zero where w == 0 or the frame is padded), carried through the adjoint of the recovery with
+ *                 coef = 2 exactly as the contact guidance carries its S: three launches - recovery, targets, adjoint.  Joint 0 is the root.
+ * which is -scale[b] * dE/dx.  grad is exactly zero in every other column, in padded frames, where w == 0 and (t != NULL) in a sample with
+ * t[b] >= t_start.  No atomics. */
+typedef struct {
+    const float* target;                   /* device [B][L][K][3]: scene coordinates                                      */
+    const float* weight;                   /* device [B][L][K]: 0 = no target (the target value is not read)              */
+    const float* scale;                    /* device [B]                                                                  */
+    const float* mean; const float* std;   /* device [D]: de-normalisation of the motion                                  */
+    int32_t cols[AFM_GUIDE_MAX_JOINTS];    /* column of x of joint k (y, z: the next two); ignored with `h3d`             */
+    int32_t K;
+    int32_t first_guided;                  /* loops only: executed steps (first_step + j) below it do not carry this term */
+    int64_t t_start;                       /* with t: samples with t[b] >= t_start get a zero gradient                    */
+    const afm_h3d_layout* h3d;             /* NULL: `cols` name absolute positions; set: x holds HumanML3D features       */
+} afm_joint_targets;
+
+/* The sum of the two guidances: grad = grad_contact + grad_targets, each term the float32 result of that guidance alone, joined by one
+ * rounded addition per element (the targets' launch - the column kernel, or the adjoint - adds its complete result to what the contact
+ * term wrote; a sample with t[b] >= a term's t_start gets zeros from that term).  At least one of contact / targets is set; both set: they
+ * name the same mean / std, the same form, and the same to_scene (pointer and stride).  Through this struct contact->gk and
+ * contact->frame_mask are not read.  The recovery of an h3d motion runs once per term (the two joint lists may differ).  Launches: the
+ * contact term's 2 (h3d: 4), plus the targets' 1 (h3d: 3). */
+typedef struct {
+    const afm_contact_guide* contact;      /* or NULL                                                                     */
+    const afm_joint_targets* targets;      /* or NULL                                                                     */
+    const float* gk;                       /* loops only: device [T][B], row i = the coefficient of spaced timestep i     */
+    const uint8_t* frame_mask;             /* loops only: device [B][L], nonzero = padded frame, or NULL                  */
+} afm_motion_guide;
+
+/* grad [B][L][D] and / or the two energies [B] (each may be NULL; an energy of a term that is not set must be NULL) of x [B][L][D];
+ * frame_mask [B][L] or NULL; t [B] or NULL.  AFM_E_BADARG before anything is enqueued: neither term set, K outside 1..16, column triples
+ * that overlap or leave D, a joint outside 0..21 or named twice, D < 67 with h3d, terms that disagree (above). */
+int64_t afm_motion_guidance_workspace_bytes(const afm_motion_guide* g, int32_t B, int32_t L, int32_t D);
+int afm_motion_guidance(const afm_motion_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                        float* energy_contact, float* energy_targets, int32_t B, int32_t L, int32_t D, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
+/* afm_cmdm_guide_loop_range with the description swapped: the same loop body, the step's gradient the sum above over the terms whose own
+ * first_guided the executed step has reached (a term not yet reached launches nothing and contributes exactly zero; no term reached: the
+ * step launches what an imputing loop launches).  Also AFM_E_BADARG: g->gk missing, a negative first_guided. */
+int64_t afm_cmdm_motion_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                   const afm_cfg2_args* cfg2, const afm_motion_guide* guide);
+int afm_cmdm_motion_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                     const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                     const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                     const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_motion_guide* guide,
+                                     int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                     void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                     void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:

@@ -1,6 +1,6 @@
 """Cost of contact guidance in the CMDM's sampling loops on one MI355X, printed as ONE JSON line (and as a markdown table with --md).
 
-    python tools/bench_contact_guidance.py [--repr pos|h3d] [--reps 5] [--parent-lib PATH] [--md PATH]
+    python tools/bench_contact_guidance.py [--repr pos|h3d] [--targets] [--reps 5] [--parent-lib PATH] [--md PATH]
 
 L = 196, N = 8192 contact points, K = 6 contact joints, the benchmark's synthetic weights, at B = 1 and at B = 32, for DDIM (eta = 0) at
 "ddim50" and DPM-Solver++(2M) at "logsnr20".  Arms, ms per sample call (the loop call and the final synchronise):
@@ -15,6 +15,16 @@ HumanML3D features with ContactGuidance.h3d and the y-up to z-up transform (four
 L, N, K and batches, and adds the arm
 
     pos_guided      the native loop with the absolute-column ContactGuidance of --repr pos, for the cost of the two extra launches
+
+--targets measures joint-position targets (afm.diffusion.JointTargets, K = 6 joints, every second frame of every joint weighted) at
+"ddim50" alone, pos or h3d, with the arms
+
+    unguided, contact_guided                    the native loops without a cond_fn and with the ContactGuidance of the plain mode
+    targets_guided, both_guided                 the native loops with the JointTargets and with MotionGuidance(contact, targets)
+    step_targets, step_both                     the step-by-step loops with the same two guidances
+    parent_unguided, parent_contact_guided      --parent-lib: the first two arms on the parent commit's library, in a fresh child process
+
+and the ratios guided step / unguided step, native / step by step, and this build / the parent's for the two arms the parent has.
 
 A timed window is as many back-to-back loop calls as fill 100 ms (a single B = 1 call of 7 - 27 ms is too short a window), reported per
 call.  The arms alternate inside every repetition and every repetition is kept (median, best, spread (max - min) / median), as the other
@@ -42,15 +52,17 @@ L, N, D = 196, 8192, 263
 BATCHES = (1, 32)
 SAMPLERS = {"ddim50": ("ddim50", "ddim"), "dpm2m_logsnr20": ("logsnr20", "dpm")}
 JOINTS = [0, 10, 11, 12, 20, 21]
+NEW_TARGETS = ("afm_motion_guidance", "afm_motion_guidance_workspace_bytes", "afm_cmdm_motion_guide_loop_range",
+               "afm_cmdm_motion_guide_loop_workspace_bytes")
 NEW = ("afm_guide_step", "afm_contact_guidance", "afm_contact_guidance_workspace_bytes", "afm_cmdm_guide_loop_range",
        "afm_cmdm_guide_loop_workspace_bytes", "afm_contact_guidance_h3d_workspace_bytes", "afm_h3d_joints")
 
 
-def _setup(dev, lib=None):
+def _setup(dev, lib=None, targets=False):
     from afm import ffi
     if lib:
         ffi._LIB_PATH = os.path.abspath(lib)          # (before the first load(): the parent build has none of the guidance entry points)
-        for name in NEW:
+        for name in NEW_TARGETS + (() if targets else NEW):          # (--targets: the parent has the contact guidance, not the targets)
             ffi.EXPORTS.pop(name, None)
     from afm import synth
     from afm.base import create_gaussian_diffusion, create_model
@@ -104,18 +116,124 @@ def _runner(model, diffs, kws, sampler, b, guide=None, step_by_step=False):
     return consume
 
 
-def worker(lib, reps):
-    """Child process: the unguided loops of another build's library, `reps` timed runs per cell -> one JSON line of seconds."""
+def worker(lib, reps, targets=False, repr_="pos"):
+    """Child process: the unguided loops of another build's library, `reps` timed runs per cell -> one JSON line of seconds.
+    `targets`: "ddim50" alone, and the contact-guided loop of that library too."""
     dev = torch.device("cuda:0")
-    model, diffs, kws = _setup(dev, lib)
+    model, diffs, kws = _setup(dev, lib, targets)
     out = {}
     for b in BATCHES:
-        for s in SAMPLERS:
+        for s in (TARGET_SAMPLERS if targets else SAMPLERS):
             run = _runner(model, diffs, kws, s, b)
             n = _calls(run)
             model.condition_tokens(**kws[b])
             out[f"{s}/{b}"] = [_timed(run, n) for _ in range(reps)]
+            if targets:
+                run = _runner(model, diffs, kws, s, b, guide=_guides(repr_, dev, b)["contact_guided"])
+                n = _calls(run)
+                out[f"{s}/{b}/contact"] = [_timed(run, n) for _ in range(reps)]
     print("WORKER " + json.dumps(out), flush=True)
+
+
+TARGET_SAMPLERS = ("ddim50",)
+TARGET_SCALE = 1e-3
+
+
+def _guides(repr_, dev, b):
+    """the guidances of the --targets arms for a batch of b: contact, targets, both (K = 6 joints each, the same mean / std and transform).
+    The targets' scale is small on purpose: the un-normalised energy times the early steps' coefficient (gk is about 20 at t = 980) would
+    otherwise drive the synthetic model's samples to inf, and a chip at its power limit runs non-finite data faster than real data - every
+    guided arm's final sample is checked to be finite ("finite" in the JSON line)."""
+    from afm import synth
+    from afm.diffusion import ContactGuidance, JointTargets, MotionGuidance
+    mean, std = torch.zeros(D), torch.ones(D)
+    K = len(JOINTS)
+    target = 1.5 * synth.gaussian(f"bench_targets_{b}", (b, L, K, 3))
+    weight = torch.zeros(b, L, K)
+    weight[:, ::2] = 0.01
+    if repr_ == "h3d":
+        zup = torch.tensor([[1.0, 0.0, 0.0, 0.0], [0.0, 0.0, -1.0, 0.0], [0.0, 1.0, 0.0, 0.0]], device=dev)
+        contact = ContactGuidance.h3d(JOINTS, mean, std, to_scene=zup, sigma=0.8, scale=1.0)
+        targets = JointTargets.h3d(JOINTS, mean, std, to_scene=zup, target=target, weight=weight, scale=TARGET_SCALE)
+    else:
+        contact = ContactGuidance([3 * j for j in JOINTS], mean, std, sigma=0.8, scale=1.0)
+        targets = JointTargets([3 * j for j in JOINTS], mean, std, target=target, weight=weight, scale=TARGET_SCALE)
+    return {"contact_guided": contact, "targets_guided": targets, "both_guided": MotionGuidance(contact, targets)}
+
+
+def _markdown_targets(out):
+    lines = [f"# Joint-position targets in the CMDM sampling loops ({out['repr']})", "",
+             f"`tools/bench_contact_guidance.py --targets --repr {out['repr']}`, {out['device']}, L = {L}, N = {N}, K = {len(JOINTS)}, ddim50, {out['reps']} "
+             "repetitions, arms alternating inside every repetition, a timed window = the loop calls that fill 100 ms.  ms per sample call "
+             "(median; spread = (max - min) / median).  "
+             f"Every guided arm's final sample finite: {all(out['finite'].values())}.", "", "| B | arm | ms / call | ms / step | spread |", "|---|---|---|---|---|"]
+    for b in BATCHES:
+        for arm, v in out["ddim50"][f"B{b}"].items():
+            if isinstance(v, dict):
+                lines.append(f"| {b} | {arm} | {v['ms_per_sample_call']} | {v['ms_per_step']} | {v['spread']} |")
+    names = ("targets_over_unguided", "both_over_unguided", "contact_over_unguided", "step_over_native_targets", "step_over_native_both",
+             "unguided_over_parent", "contact_over_parent")
+    lines += ["", "| B | " + " | ".join(names) + " |", "|---|" + "---|" * len(names)]
+    for b in BATCHES:
+        o = out["ddim50"][f"B{b}"]
+        lines.append(f"| {b} | " + " | ".join(str(o.get(n, "n/a")) for n in names) + " |")
+    return "\n".join(lines) + "\n"
+
+
+def main_targets(args):
+    dev = torch.device("cuda:0")
+    model, diffs, kws = _setup(dev)
+    s = TARGET_SAMPLERS[0]
+    runs = {}
+    for b in BATCHES:
+        g = _guides(args.repr, dev, b)
+        runs[(b, "unguided")] = _runner(model, diffs, kws, s, b)
+        for arm, guide in g.items():
+            runs[(b, arm)] = _runner(model, diffs, kws, s, b, guide=guide)
+        runs[(b, "step_targets")] = _runner(model, diffs, kws, s, b, guide=g["targets_guided"], step_by_step=True)
+        runs[(b, "step_both")] = _runner(model, diffs, kws, s, b, guide=g["both_guided"], step_by_step=True)
+    calls = {k: _calls(fn) for k, fn in runs.items()}
+    finite = {f"B{b}/{arm}": bool(torch.isfinite(fn()).all()) for (b, arm), fn in runs.items() if arm.endswith("_guided")}
+    times = {k: [] for k in runs}
+    parent = {}
+    for _ in range(args.reps):
+        if args.parent_lib:                                   # a fresh process (this one has the GPU open; it idles meanwhile)
+            torch.cuda.synchronize()
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", args.parent_lib, "--reps", "1", "--targets", "--repr", args.repr],
+                               capture_output=True, text=True, timeout=300)
+            line = [l for l in r.stdout.splitlines() if l.startswith("WORKER ")]
+            if r.returncode != 0 or not line:
+                raise RuntimeError(f"parent-library worker failed ({r.returncode}): {r.stderr[-800:]}")
+            for key, ts in json.loads(line[0][7:]).items():
+                parent.setdefault(key, []).extend(ts)
+        for b in BATCHES:
+            model.condition_tokens(**kws[b])
+            for (bb, arm), fn in runs.items():
+                if bb == b:
+                    times[(b, arm)].append(_timed(fn, calls[(b, arm)]))
+    out = {"tool": "bench_contact_guidance --targets", "repr": args.repr, "device": torch.cuda.get_device_name(0), "L": L, "N": N, "reps": args.reps,
+           "finite": finite, s: {}}
+    steps = diffs[s].num_timesteps
+    ok = all(finite.values())
+    for b in BATCHES:
+        o = {arm: _stats(ts, steps) for (bb, arm), ts in times.items() if bb == b}
+        ms = lambda arm: o[arm]["ms_per_sample_call"]
+        if f"{s}/{b}" in parent:
+            o["parent_unguided"], o["parent_contact_guided"] = _stats(parent[f"{s}/{b}"], steps), _stats(parent[f"{s}/{b}/contact"], steps)
+            o["unguided_over_parent"] = round(ms("unguided") / ms("parent_unguided"), 4)
+            o["contact_over_parent"] = round(ms("contact_guided") / ms("parent_contact_guided"), 4)
+        for arm in ("targets", "both", "contact"):
+            o[f"{arm}_over_unguided"] = round(ms(f"{arm}_guided") / ms("unguided"), 4)
+        o["step_over_native_targets"] = round(ms("step_targets") / ms("targets_guided"), 4)
+        o["step_over_native_both"] = round(ms("step_both") / ms("both_guided"), 4)
+        ok = ok and o["step_over_native_targets"] > 1.0 and o["step_over_native_both"] > 1.0
+        out[s][f"B{b}"] = o
+    print(json.dumps(out))
+    if args.md:
+        os.makedirs(os.path.dirname(os.path.abspath(args.md)), exist_ok=True)
+        with open(args.md, "w") as f:
+            f.write(_markdown_targets(out))
+    return 0 if ok else 1
 
 
 def _stats(ts, steps):
@@ -150,12 +268,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--repr", choices=("pos", "h3d"), default="pos", help="what the motion vector holds: absolute positions or HumanML3D features")
+    ap.add_argument("--targets", action="store_true", help="measure joint-position targets, alone and summed with the contact guidance (ddim50)")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--md", default=None, help="also write the table as markdown to this path")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.worker:
-        return worker(args.worker, args.reps)
+        return worker(args.worker, args.reps, args.targets, args.repr)
+    if args.targets:
+        return main_targets(args)
     dev = torch.device("cuda:0")
     model, diffs, kws = _setup(dev)
     from afm.diffusion import ContactGuidance
