@@ -545,7 +545,24 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         denoiser's loops take (not a caller's argument; the public keywords are the CDM's, name for name): GuidedCMDM's (afm_cfg_args or
         afm_cfg2_args or None, branch streams?) and, as an optional third entry, an afm.diffusion.ContactGuidance (afm_cmdm_guide_loop_range), JointTargets or MotionGuidance (afm_cmdm_motion_guide_loop_range: the same loop, the step's gradient the sum of the terms that have started) - its gradient at every guided step's x_t is computed on the sub-batch's stream (two launches) and
         enters the loop's update launch (afm_cmdm_guide_loop_range, every form; the loop runs in the separate-update form like an
-        imputing one; steps before the guidance starts launch what an imputing loop of that form launches)."""
+        imputing one; steps before the guidance starts launch what an imputing loop of that form launches).  A fourth entry of
+        ``_guidance`` (the public keywords stay the CDM's; GuidedCMDM names it ``stitch``): an afm.diffusion.Stitch - the batch rows are overlapping windows of long motions and every step's update launch gives the frames two
+        windows share one pred_xstart (afm_cmdm_stitch_loop_range, every deterministic form: ``ddim_eta`` 0 or ``dpm_order``, plain / one
+        scale / two scales, with or without ``impute``; the separate-update form; sub-batches are cut over long motions).  Refused with a
+        ValueError: the ancestral loop, ``ddim_eta`` != 0, a ``step_noise``, a guidance term, a batch that is no multiple of the windows."""
+        stitch = tuple(_guidance)[3] if _guidance is not None and len(tuple(_guidance)) > 3 else None
+        if stitch is not None:
+            if ddim_eta is None and dpm_order is None:
+                raise ValueError("stitched windows need a deterministic update: the ancestral loop draws noise at every step, and the noise of "
+                                 "the frames two windows share would have to be shared (ddim_eta=0 or dpm_order)")
+            if ddim_eta is not None and float(ddim_eta) != 0.0:
+                raise ValueError(f"stitched windows need a deterministic update: with ddim_eta = {ddim_eta!r} the step noise of the frames two "
+                                 "windows share would have to be shared")
+            if step_noise is not None:
+                raise ValueError("stitched windows take no step_noise: the noise of the frames two windows share would have to be shared")
+            if _guidance is not None and len(tuple(_guidance)) > 2 and tuple(_guidance)[2] is not None:
+                raise ValueError("a cond_fn guidance with stitch= is not built: per-window gradients disagree in the overlaps")
+            stitch.check(x.shape[0], x.shape[1])          # (B % S, 2 * ov <= L, the frames)
         if any(k in model_kwargs for k in COND_SWITCHES):
             raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
                                       "p_sample_loop samples them step by step (p_sample_loop_progressive)")
@@ -587,6 +604,10 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             # sub-batch streams fill the wave-quantisation tails of B >= 16 launches; below that every launch is latency-bound and a
             # second stream only adds launches (B = 4: 1311 steps/s on one stream vs 1159 on two, profiles/r02_small_batch.md)
             nsub = max(1, min(int(self.loop_streams), B // 8 if self.loop_streams_auto else B))
+            st = st_keep = None
+            if stitch is not None:          # sub-batches are cut over long motions: a window and its neighbour share one
+                st, st_keep = stitch.describe(x.device)
+                nsub = max(1, min(nsub, B // stitch.windows))
             self._side_streams = ffi.stream_pool(x.device, nsub)          # process-wide pool (hardware queues are few: ffi.stream_pool)
             handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in self._side_streams[:nsub]])
             # _guidance (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)
@@ -618,6 +639,11 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 guide_cfg = (None if two else cfg_ref, cfg_ref if two else None)
                 guide_tail = guide_cfg + ffi.impute_ptrs(impute) + (C.byref(cguide),)
                 sizer, size_args, form = guide_names[1], guide_cfg + (C.byref(cguide),), (guide_form[0], form) + guide_form[1:]
+            elif st is not None:                # every deterministic form; a size of its own: always a history buffer, sub-batches over long motions
+                entry = "afm_cmdm_stitch_loop_range"
+                guide_cfg = (None if two else cfg_ref, cfg_ref if two else None)
+                guide_tail = guide_cfg + ffi.impute_ptrs(impute) + (C.byref(st),)
+                sizer, size_args, form = "afm_cmdm_stitch_loop_workspace_bytes", guide_cfg + (C.byref(st),), ("stitch", form, st.windows, st.overlap)
             elif tables.dpm is not None:          # every form; a size of its own: the history buffers, which cross the range calls of a chain
                 entry, guide = "afm_cmdm_dpm_loop_range", (None if two else cfg_ref, cfg_ref if two else None) + ffi.impute_ptrs(impute)
                 sizer, size_args, form = "afm_cmdm_dpm_loop_workspace_bytes", guide[:2], ("dpm", form)
@@ -636,8 +662,9 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
-                if cguide is not None:          # both kinds of rows and the 2M rows, one of the three set; the gk rows of the slice
-                    cguide.gk = gk_rows[lo:].data_ptr()
+                if cguide is not None or st is not None:          # both kinds of rows and the 2M rows, one of the three set; the gk rows of the slice
+                    if cguide is not None:
+                        cguide.gk = gk_rows[lo:].data_ptr()
                     rows = (None, tables.dpm_rows(lo), None, None, None) if tables.dpm is not None else \
                         (lambda r: (r[0], None) + r[1:])(tables.rows(lo, True))
                     steps = (nz, tables.tmap(lo), *rows, *guide_tail, j1 - j0, j0, seed & (2**64 - 1), sample_index0)
@@ -649,7 +676,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (tables.keep(), step_noise, cond, fm, _guidance, impute, guide_keep)
+            self._last_loop_scratch = (tables.keep(), step_noise, cond, fm, _guidance, impute, guide_keep, st, st_keep)
         return x
 
 
@@ -779,14 +806,16 @@ class GuidedCMDM(nn.Module):
     def forward(self, x, timesteps, **kwargs):
         return self.branches(x, timesteps, **kwargs)[-1]
 
-    def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, dpm_order: Optional[int] = None, contact_guide=None, **kw):
+    def afm_native_loop(self, diffusion, x, model_kwargs, *, impute=None, dpm_order: Optional[int] = None, contact_guide=None, stitch=None,
+                        **kw):
         """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range; with ``impute``: the guided form of
         afm_cmdm_impute_loop_range; one scale per condition: afm_cmdm_cfg2_loop_range, every form; ``dpm_order``: the guided forms of
-        afm_cmdm_dpm_loop_range; ``contact_guide``: the guided forms of afm_cmdm_guide_loop_range): CMDM.afm_native_loop's arguments."""
+        afm_cmdm_dpm_loop_range; ``contact_guide``: the guided forms of afm_cmdm_guide_loop_range; ``stitch``: the guided forms of
+        afm_cmdm_stitch_loop_range, each window combined with its own scales): CMDM.afm_native_loop's arguments."""
         self._no_switches(model_kwargs)
         if self.model.training:
             raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
         cfg = self._cfg(x.shape[0], x.device)          # (a [B] scale of the wrong length is refused here)
         ffi.require_gpu(x)
-        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams, contact_guide), impute=impute,
+        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams, contact_guide, stitch), impute=impute,
                                           dpm_order=dpm_order, **kw)

@@ -133,6 +133,161 @@ class Impute:
         return Impute._of(self.known[start:start + count], self.mask[start:start + count])
 
 
+class Stitch:
+    """G long motions sampled as ``B = G * S`` overlapping windows, batch row ``g * S + w`` window ``w`` of motion ``g`` (DoubleTake /
+    DiffCollage / MultiDiffusion style): the windows are denoised side by side, each with its own text and contact map, and at every
+    step the frames two windows share get one common pred_xstart.  Window ``w`` holds the long frames ``w * (L - ov) .. w * (L - ov) + L -
+    1``; ``2 * ov <= L``, so a frame lies in at most two windows.  ``windows == 1`` or ``overlap == 0``: no blend.
+
+    ``frames`` = F is the long motion's length, ``(S-1)(L-ov) + ov < F <= S*L - (S-1)*ov``; None: the full length.  A shorter F leaves
+    a padded tail in the LAST window only, never inside an overlap - `x_mask` builds the mask for it (the model must have
+    ``mask_motion=True``).  The window length L is the sample's; given ``frames`` it is known up front, ``ov + ceil((F - ov) / S)``
+    (``length=`` states it where neither is given).
+
+    The blend, for f = 0 .. ov-1, of the left element (w, L - ov + f) and the right element (w + 1, f):
+
+        wr[f] = (f + 1) / (ov + 1),  wl[f] = 1 - wr[f]        float64 on the host, rounded to float32 once (a device row [2][ov])
+        v = (wl[f] * x0_left) + (wr[f] * x0_right)            float32, three roundings, this order, no contraction
+
+    Both windows evaluate the same expression on the same operands and get the same bits: with shared frames starting from shared noise
+    (`x_T`) and a deterministic update (DDIM eta = 0, DPM-Solver++(2M)) the shared frames stay bit-identical in both windows at every
+    step, and `join` of the result is the long motion read from either side.  Order inside a step: the guidance combine (each window its
+    own scales) -> blend -> ``denoised_fn`` / `Impute` -> clamp -> update.
+
+    ``ddim_sample_loop(..., stitch=)`` and ``dpm_solver_sample_loop(..., stitch=)`` take it; a CMDM `trans_enc` or a GuidedCMDM runs the
+    whole chain natively (afm_cmdm_stitch_loop_range).  A per-window `Impute` built by hand that disagrees in an overlap is the caller's
+    error - `impute` builds a consistent one from the long form."""
+
+    def __init__(self, windows: int, overlap: int, frames: Optional[int] = None, *, length: Optional[int] = None):
+        S, ov = int(windows), int(overlap)
+        if S < 1:
+            raise ValueError(f"Stitch: at least one window, got {windows!r}")
+        if ov < 0:
+            raise ValueError(f"Stitch: overlap must be >= 0, got {overlap!r}")
+        self.windows, self.overlap = S, ov
+        self.frames = None if frames is None else int(frames)
+        self.length = None if length is None else int(length)
+        if self.length is None and self.frames is not None:
+            if self.frames <= (ov if S > 1 else 0):
+                raise ValueError(f"Stitch: {self.frames} frames do not reach past the first overlap of {ov}")
+            self.length = self.frames if S == 1 else ov + -(-(self.frames - ov) // S)
+        if self.length is not None:
+            self._geometry(self.length)
+        self._w: Dict[str, torch.Tensor] = {}
+
+    # ---- geometry
+    def _geometry(self, L: int) -> int:
+        """checks the geometry at window length L; -> the long motion's frames"""
+        S, ov = self.windows, self.overlap
+        if L <= 0 or 2 * ov > L:
+            raise ValueError(f"Stitch: 2 * overlap <= L - a frame lies in at most two windows - but overlap = {ov}, L = {L}")
+        full = S * L - (S - 1) * ov
+        F = full if self.frames is None else self.frames
+        lo = (S - 1) * (L - ov) + (ov if S > 1 else 0)
+        if not lo < F <= full:
+            raise ValueError(f"Stitch: {S} windows of {L} frames sharing {ov} hold long motions of {lo + 1}..{full} frames (a padded tail "
+                             f"in the last window only), not {F}")
+        return F
+
+    def full(self, L: int) -> int:
+        """the long frames S windows of L frames cover"""
+        return self.windows * L - (self.windows - 1) * self.overlap
+
+    def check(self, B: int, L: int) -> int:
+        """a batch of B windows of L frames against the geometry (ValueError); -> the long motion's frames F"""
+        if B % self.windows != 0:
+            raise ValueError(f"Stitch: the batch holds whole long motions - {B} rows are no multiple of {self.windows} windows")
+        if self.length is not None and L != self.length:
+            raise ValueError(f"Stitch: the windows have {self.length} frames, the sample has {L}")
+        return self._geometry(L)
+
+    def _resolve(self, length: Optional[int], F: Optional[int] = None) -> int:
+        L = self.length if self.length is not None else length
+        if L is None and F is not None:          # a full-length long motion names its window length
+            S, ov = self.windows, self.overlap
+            if (F - ov) % S == 0 and F > ov:
+                L = ov + (F - ov) // S
+        if L is None:
+            raise ValueError("Stitch: the window length is not known - pass length= (or frames= to the constructor)")
+        return int(L)
+
+    # ---- the weight row
+    def weights64(self) -> np.ndarray:
+        """[2, ov] float64: wl then wr"""
+        wr = (np.arange(self.overlap, dtype=np.float64) + 1.0) / (self.overlap + 1.0)
+        return np.stack([1.0 - wr, wr], 0)
+
+    def weights(self, device) -> torch.Tensor:
+        """the float32 row [2, ov] on ``device``: `weights64` rounded once"""
+        key = str(torch.device(device))
+        if key not in self._w:
+            self._w[key] = torch.from_numpy(self.weights64()).float().contiguous().to(device)
+        return self._w[key]
+
+    def describe(self, device) -> tuple:
+        """(afm_stitch on ``device``, what must stay alive with it)"""
+        w = self.weights(device)
+        return ffi.Stitch(self.windows, self.overlap, w.data_ptr() if self.overlap > 0 else None), w
+
+    # ---- long form <-> windows (copies; float32 on the GPU: afm_stitch_windows / afm_stitch_join)
+    def windows_of(self, long: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
+        """[G, F, D] -> [G * S, L, D]; frames at or behind F (the padded tail) are zero.  F: the long motion's frames or the full length."""
+        if long.dim() != 3:
+            raise ValueError(f"Stitch.windows_of: the long form is [G, F, D], got {tuple(long.shape)}")
+        G, F, D = long.shape
+        S, ov = self.windows, self.overlap
+        L = self._resolve(length, F)
+        self._geometry(L)
+        lo = (S - 1) * (L - ov) + (ov if S > 1 else 0)
+        if not lo < F <= self.full(L):
+            raise ValueError(f"Stitch.windows_of: {F} frames do not fill {S} windows of {L} sharing {ov}")
+        if long.is_cuda and long.dtype == torch.float32:
+            return ops.stitch_windows(long, S, ov, L)
+        out = long.new_zeros(G, S, L, D)
+        for w in range(S):
+            a = w * (L - ov)
+            n = max(0, min(L, F - a))
+            out[:, w, :n] = long[:, a:a + n]
+        return out.reshape(G * S, L, D)
+
+    def join(self, windows: torch.Tensor) -> torch.Tensor:
+        """[G * S, L, D] -> [G, F, D]; a shared frame is read from the later window (after a stitched chain both hold the same bits)"""
+        if windows.dim() != 3:
+            raise ValueError(f"Stitch.join: the windows are [G * S, L, D], got {tuple(windows.shape)}")
+        B, L, D = windows.shape
+        F = self.check(B, L)
+        S, ov = self.windows, self.overlap
+        if windows.is_cuda and windows.dtype == torch.float32:
+            return ops.stitch_join(windows, S, ov, F)
+        v = windows.reshape(B // S, S, L, D)
+        parts = [v[:, w, :(L - ov if w + 1 < S else F - w * (L - ov))] for w in range(S)]
+        return torch.cat(parts, 1)
+
+    def x_mask(self, G: int, device, length: Optional[int] = None, model=None) -> torch.Tensor:
+        """bool [G * S, L], True = padded frame: the tail of every long motion's last window.  ``model``: checked for mask_motion."""
+        L = self._resolve(length)
+        F = self._geometry(L)
+        pad = self.full(L) - F
+        if pad > 0 and model is not None and not getattr(getattr(model, "model", model), "mask_motion", True):
+            raise ValueError("Stitch: a long motion shorter than its windows pads the last window, which needs a model with mask_motion=True")
+        m = torch.zeros(G, self.windows, L, dtype=torch.bool)
+        if pad > 0:
+            m[:, -1, L - pad:] = True
+        return m.reshape(G * self.windows, L).to(device)
+
+    def impute(self, known_long: torch.Tensor, mask_long: torch.Tensor, length: Optional[int] = None) -> Impute:
+        """the `Impute` over the windows of a long-form known [G, F, D] / mask (broadcastable to it): consistent in the overlaps by
+        construction (padded frames know nothing)"""
+        imp = Impute(known_long, mask_long)          # (the long form checked and expanded like any other)
+        return Impute._of(self.windows_of(imp.known, length), self.windows_of(imp.mask, length))
+
+    def x_T(self, B: int, L: int, D: int, device, seed: int, sample_index0: int = 0) -> torch.Tensor:
+        """x_T of a stitched chain: the windows of ONE Philox draw [G, S*L - (S-1)*ov, D] keyed (seed, sample_index0 + g) - shared frames
+        start from shared noise, and a long motion's noise does not depend on the batch around it"""
+        self.check(B, L)
+        return self.windows_of(ops.randn((B // self.windows, self.full(L), D), device, seed=seed, sample_index0=sample_index0, step=-1), L)
+
+
 class CondFnError(ValueError, NotImplementedError):
     """A ``cond_fn`` that does not implement the protocol ``cond_fn(x, t, **model_kwargs) -> float32 tensor of x's shape on x's device``: it
     cannot be called that way, or what it returns does not fit.  It is a ValueError, which is what such a callable deserves.  The second
@@ -767,12 +922,12 @@ class GaussianDiffusion:
                                      dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs))
 
     def _progressive(self, step_fn, model, shape, noise, device, progress, step_noise, seed, sample_index0, step_kwargs):
-        """The loop of both progressive generators: x_T (``noise`` or Philox step -1), then ``step_fn`` (p_sample / ddim_sample) per
-        executed step j at timestep index T - 1 - j, each output yielded and its sample fed to the next step."""
+        """The loop of both progressive generators: x_T (``noise`` or Philox step -1; stitched: `Stitch.x_T`), then ``step_fn`` (p_sample /
+        ddim_sample) per executed step j at timestep index T - 1 - j, each output yielded and its sample fed to the next step."""
         if device is None:
             device = next(model.parameters()).device
         seed = self._fresh_seed("_sample_calls") if seed is None else seed
-        img = noise if noise is not None else ops.randn(tuple(shape), device, seed=seed, sample_index0=sample_index0, step=-1)
+        img = noise if noise is not None else self._x_T(shape, device, seed, sample_index0, step_kwargs.get("stitch"))
         tvec = self.tables(device).timesteps(shape[0])
         steps: Iterable[int] = range(self.num_timesteps - 1, -1, -1)
         if progress:
@@ -786,21 +941,57 @@ class GaussianDiffusion:
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, *,
-                      step_noise=None, seed: Optional[int] = None, sample_index0: int = 0, snapshots: Optional[dict] = None):
-        """Full ancestral sampling (reference gaussian_diffusion.py:442-486).
+                      step_noise=None, seed: Optional[int] = None, sample_index0: int = 0, snapshots: Optional[dict] = None, stitch=None):
+        """Full ancestral sampling (reference gaussian_diffusion.py:442-486).  ``stitch`` is refused (ValueError): every ancestral step
+        draws noise, and the noise of the frames two windows share would have to be shared - use ddim_sample_loop (eta = 0) or
+        dpm_solver_sample_loop.
 
         Extra keyword-only arguments: ``step_noise`` ([T, *shape] tensor or list, row j = j-th
         executed step) replaces the `randn_like` draws; otherwise Philox noise keyed by
         (seed, sample_index0 + b, step).  Denoisers exposing ``afm_native_loop`` (our CMDM / CDM)
         run the whole loop natively without host synchronisation.  ``snapshots`` = {executed-step count: None} is filled with
         clones of x after those steps (what iterating p_sample_loop_progressive would have shown)."""
+        if stitch is not None:
+            raise ValueError("p_sample_loop: stitched windows need a deterministic update - every ancestral step draws noise, and the noise of "
+                             "the frames two windows share would have to be shared; use ddim_sample_loop (eta = 0) or dpm_solver_sample_loop")
         return self._sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
                                  step_noise, seed, sample_index0, snapshots, ddim_eta=None)
 
     # ------------------------------------------------------------------ DDIM
-    def _pred_xstart(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, tab):
-        """p_mean_variance's pred_xstart for START_X models (gaussian_diffusion.py:289-294), for p_sample and the DDIM steps."""
+    @staticmethod
+    def _x_T(shape, device, seed, sample_index0, stitch=None):
+        """x_T of a chain without a caller's ``noise``: Philox step -1 keyed (seed, sample_index0 + b); stitched: `Stitch.x_T`"""
+        if stitch is not None:
+            return stitch.x_T(shape[0], shape[1], shape[2], device, seed, sample_index0)
+        return ops.randn(tuple(shape), device, seed=seed, sample_index0=sample_index0, step=-1)
+
+    @staticmethod
+    def _check_stitch(stitch, model, shape, cond_fn=None, step_noise=None, eta=None, who: str = "stitch") -> None:
+        """what a stitched chain refuses (ValueError, each with its reason), before anything runs"""
+        if not isinstance(stitch, Stitch):
+            raise ValueError(f"{who}: stitch= takes an afm.diffusion.Stitch, not {type(stitch).__name__}")
+        if eta is not None and float(eta) != 0.0:
+            raise ValueError(f"{who}: stitched windows need a deterministic update - with eta = {eta!r} the step noise of the frames two "
+                             "windows share would have to be shared")
+        if step_noise is not None:
+            raise ValueError(f"{who}: stitched windows take no step_noise - the noise of the frames two windows share would have to be shared")
+        if cond_fn is not None:
+            raise ValueError(f"{who}: cond_fn with stitch= is not built - a gradient through the h3d recovery integrates from each window's "
+                             "own origin, so per-window gradients disagree in the overlaps")
+        if getattr(getattr(model, "model", model), "arch", None) == "trans_dec":
+            raise ValueError(f"{who}: stitched windows are built for arch='trans_enc' only, not 'trans_dec'")
+        if len(shape) != 3:
+            raise ValueError(f"{who}: stitched windows are [B, L, D] samples, got shape {tuple(shape)}")
+        F = stitch.check(shape[0], shape[1])
+        if F < stitch.full(shape[1]) and not getattr(getattr(model, "model", model), "mask_motion", True):
+            raise ValueError(f"{who}: a long motion shorter than its windows pads the last window, which needs a model with mask_motion=True")
+
+    def _pred_xstart(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, tab, stitch=None):
+        """p_mean_variance's pred_xstart for START_X models (gaussian_diffusion.py:289-294), for p_sample and the DDIM steps.  ``stitch``:
+        the frames neighbouring windows share are blended (ops.stitch_blend) in the model's output, before ``denoised_fn`` and the clamp."""
         x0 = model(x, self._model_timesteps(t, tab), **(model_kwargs or {}))
+        if stitch is not None:
+            x0 = ops.stitch_blend(x0, stitch)
         if denoised_fn is not None:
             x0 = denoised_fn(x0)
         if clip_denoised:
@@ -811,15 +1002,17 @@ class GaussianDiffusion:
         return x0
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0, *,
-                    noise: Optional[torch.Tensor] = None, seed: int = 0, sample_index0: int = 0, step: int = 0):
+                    noise: Optional[torch.Tensor] = None, seed: int = 0, sample_index0: int = 0, step: int = 0, stitch=None):
         """One DDIM step x_t -> x_{t-1} (reference gaussian_diffusion.py:538-586): the update is afm_ddim_step with the cached rows of eta.
         ``noise`` replaces the `randn_like` draw, otherwise Philox keyed by (seed, sample_index0 + b, step).  ``cond_fn``: condition_score
         (:372-394), which is a shift of the final pred_xstart - after ``denoised_fn`` and the clamp - x0' = x0 + ((1 - abar_t) /
         sqrt(abar_t)) * grad (ops.guide_step's float32 order); the update runs on x0', which is the returned "pred_xstart"."""
+        if stitch is not None:          # (``stitch``: an afm.diffusion.Stitch - x holds windows; eta = 0 only, no cond_fn, no noise)
+            self._check_stitch(stitch, model, x.shape, cond_fn, noise, eta, "ddim_sample")
         tab = self.tables(x.device)
         rows = self.ddim_tables(x.device, eta)
         with torch.no_grad():
-            x0 = self._pred_xstart(model, x, t, clip_denoised, denoised_fn, model_kwargs, tab)
+            x0 = self._pred_xstart(model, x, t, clip_denoised, denoised_fn, model_kwargs, tab, stitch)
             sg = None if rows.sigma is None else rows.sigma[t]
             if cond_fn is not None:
                 grad = self._cond_grad(cond_fn, x, t, tab, model_kwargs)
@@ -845,33 +1038,41 @@ class GaussianDiffusion:
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, *,
                                      step_noise: Optional[Sequence[torch.Tensor]] = None, seed: Optional[int] = None,
-                                     sample_index0: int = 0):
-        """Generator over the DDIM steps (reference gaussian_diffusion.py:672-710); noise keyed as p_sample_loop_progressive."""
+                                     sample_index0: int = 0, stitch=None):
+        """Generator over the DDIM steps (reference gaussian_diffusion.py:672-710); noise keyed as p_sample_loop_progressive.  ``stitch``
+        (an afm.diffusion.Stitch): the batch is windows of long motions - x_T is `Stitch.x_T`, every step blends the shared frames."""
         assert isinstance(shape, (tuple, list))
-        yield from self._progressive(self.ddim_sample, model, shape, noise, device, progress, step_noise, seed, sample_index0,
-                                     dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta))
+        kw = dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta)
+        if stitch is not None:
+            self._check_stitch(stitch, model, shape, cond_fn, step_noise, eta, "ddim_sample_loop")
+            kw["stitch"] = stitch
+        yield from self._progressive(self.ddim_sample, model, shape, noise, device, progress, step_noise, seed, sample_index0, kw)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, eta=0.0, *, step_noise=None, seed: Optional[int] = None, sample_index0: int = 0,
-                         snapshots: Optional[dict] = None):
+                         snapshots: Optional[dict] = None, stitch=None):
         """DDIM sampling (reference gaussian_diffusion.py:626-670).  The keyword-only extras are p_sample_loop's; denoisers exposing
-        ``afm_native_loop`` run the whole chain natively (the DDIM update fused where the DDPM update is) under the same conditions."""
+        ``afm_native_loop`` run the whole chain natively (the DDIM update fused where the DDPM update is) under the same conditions.
+        ``stitch`` (an afm.diffusion.Stitch): the batch rows are overlapping windows of long motions; eta must be 0, ``step_noise`` and
+        ``cond_fn`` are refused; a loop that names ``stitch`` (CMDM `trans_enc`, GuidedCMDM: afm_cmdm_stitch_loop_range) stays native."""
         return self._sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
-                                 step_noise, seed, sample_index0, snapshots, ddim_eta=float(eta))
+                                 step_noise, seed, sample_index0, snapshots, ddim_eta=float(eta), stitch=stitch)
 
     # ------------------------------------------------------------------ DPM-Solver++(2M)
     def dpm_solver_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, *,
-                          prev_xstart: Optional[torch.Tensor] = None, order: int = 2):
+                          prev_xstart: Optional[torch.Tensor] = None, order: int = 2, stitch=None):
         """One DPM-Solver++ step x_t -> x_{t-1} (no counterpart in the reference): the update is afm_dpm_step with the cached rows of
         ``order``.  ``prev_xstart``: the previous step's "pred_xstart" (None: no history - the first executed step - the two-term update).
         Deterministic: no noise, no seed.  The returned "pred_xstart" is what the next step takes as ``prev_xstart``.  ``cond_fn`` (not
         in the reference for this sampler): defined as ddim_sample's rule - x0' = x0 + ((1 - abar_t) / sqrt(abar_t)) * grad after
         ``denoised_fn`` and the clamp, the update on x0', and x0' is the returned "pred_xstart": the shifted prediction is what the 2M
         history keeps."""
+        if stitch is not None:          # (``stitch``: an afm.diffusion.Stitch - x holds windows; the history keeps the blended value)
+            self._check_stitch(stitch, model, x.shape, cond_fn, None, None, "dpm_solver_sample")
         tab = self.tables(x.device)
         rows = self.dpm_tables(x.device, order)
         with torch.no_grad():
-            x0 = self._pred_xstart(model, x, t, clip_denoised, denoised_fn, model_kwargs, tab)
+            x0 = self._pred_xstart(model, x, t, clip_denoised, denoised_fn, model_kwargs, tab, stitch)
             if cond_fn is not None:
                 grad = self._cond_grad(cond_fn, x, t, tab, model_kwargs)
                 shifted = torch.empty_like(ffi.f32c(x0))
@@ -883,17 +1084,19 @@ class GaussianDiffusion:
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                            model_kwargs=None, device=None, progress=False, *, order: int = 2, step_noise=None,
-                                           seed: Optional[int] = None, sample_index0: int = 0):
+                                           seed: Optional[int] = None, sample_index0: int = 0, stitch=None):
         """Generator over the DPM-Solver++ steps, each step's pred_xstart handed to the next as its history.  ``seed`` / ``sample_index0``
         key x_T only; a ``step_noise`` is refused (the sampler has no noise term)."""
         assert isinstance(shape, (tuple, list))
         if step_noise is not None:
             raise ValueError("DPM-Solver++ is deterministic: it takes no step_noise")
         self.dpm_tables("cpu", order)          # (order checked before anything runs)
+        if stitch is not None:
+            self._check_stitch(stitch, model, shape, cond_fn, None, None, "dpm_solver_sample_loop")
         if device is None:
             device = next(model.parameters()).device
         seed = self._fresh_seed("_sample_calls") if seed is None else seed
-        img = noise if noise is not None else ops.randn(tuple(shape), device, seed=seed, sample_index0=sample_index0, step=-1)
+        img = noise if noise is not None else self._x_T(shape, device, seed, sample_index0, stitch)
         tvec = self.tables(device).timesteps(shape[0])
         steps: Iterable[int] = range(self.num_timesteps - 1, -1, -1)
         if progress:
@@ -902,13 +1105,13 @@ class GaussianDiffusion:
         prev = None
         for i in steps:
             out = self.dpm_solver_sample(model, img, tvec[i], clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                         model_kwargs=model_kwargs, prev_xstart=prev, order=order)
+                                         model_kwargs=model_kwargs, prev_xstart=prev, order=order, stitch=stitch)
             yield out
             img, prev = out["sample"], out["pred_xstart"]
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                                device=None, progress=False, *, order: int = 2, step_noise=None, seed: Optional[int] = None,
-                               sample_index0: int = 0, snapshots: Optional[dict] = None):
+                               sample_index0: int = 0, snapshots: Optional[dict] = None, stitch=None):
         """DPM-Solver++(2M) sampling (``order`` 1: first order, DDIM eta = 0) on this - usually respaced, e.g. "logsnr20" - process: one
         denoiser evaluation per step, deterministic.  ``seed`` / ``sample_index0`` key x_T only; ``step_noise`` is refused.  A denoiser
         whose ``afm_native_loop`` names ``dpm_order`` (CMDM `trans_enc`, GuidedCMDM: afm_cmdm_dpm_loop_range; the CDM `Perceiver`:
@@ -919,16 +1122,18 @@ class GaussianDiffusion:
             raise ValueError("DPM-Solver++ is deterministic: it takes no step_noise")
         self.dpm_tables("cpu", order)
         return self._sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
-                                 None, seed, sample_index0, snapshots, ddim_eta=None, dpm_order=int(order))
+                                 None, seed, sample_index0, snapshots, ddim_eta=None, dpm_order=int(order), stitch=stitch)
 
     def _sample_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, step_noise, seed,
-                     sample_index0, snapshots, ddim_eta: Optional[float], dpm_order: Optional[int] = None):
+                     sample_index0, snapshots, ddim_eta: Optional[float], dpm_order: Optional[int] = None, stitch=None):
         """p_sample_loop (ddim_eta None) / ddim_sample_loop / dpm_solver_sample_loop (dpm_order not None): the denoiser's
         ``afm_native_loop`` when it has one and nothing needs the host between steps - no generic ``cond_fn``, no rescaled timesteps, no
         condition switch in ``model_kwargs`` - else the progressive generator.  A ``denoised_fn`` that is an `Impute` stays native where
         the loop names ``impute``, DPM-Solver++ where it names ``dpm_order``, a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets` or a `MotionGuidance` where it names
         ``contact_guide`` (GuidedCMDM) or, the plain CMDM, takes it in its private ``_guidance`` bundle; any other ``denoised_fn`` or ``cond_fn``, and a loop that does not name the keyword, sample step by step."""
         native = getattr(model, "afm_native_loop", None)
+        if stitch is not None:          # a stitched chain (ddim_sample_loop / dpm_solver_sample_loop): native where the loop names ``stitch``
+            self._check_stitch(stitch, model, shape, cond_fn, step_noise, ddim_eta, "dpm_solver_sample_loop" if dpm_order is not None else "ddim_sample_loop")
         impute = denoised_fn if isinstance(denoised_fn, Impute) else None
         guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance)) else None
         guide_kw = None                    # how the loop takes the guidance: by name, or (the CMDM) inside its private bundle
@@ -941,12 +1146,12 @@ class GaussianDiffusion:
                 not self.rescale_timesteps and \
                 not any(k in (model_kwargs or {}) for k in COND_SWITCHES) and \
                 (denoised_fn is None or (impute is not None and _takes(native, "impute"))) and \
-                (dpm_order is None or _takes(native, "dpm_order")):
+                (dpm_order is None or _takes(native, "dpm_order")) and \
+                (stitch is None or _takes(native, "stitch") or _takes(native, "_guidance")):
             if device is None:
                 device = next(model.parameters()).device
             seed = self._fresh_seed("_sample_calls") if seed is None else seed
-            x = noise.clone() if noise is not None else ops.randn(tuple(shape), device, seed=seed,
-                                                                   sample_index0=sample_index0, step=-1)
+            x = noise.clone() if noise is not None else self._x_T(shape, device, seed, sample_index0, stitch)
             if isinstance(step_noise, (list, tuple)):
                 step_noise = torch.stack(list(step_noise), 0)
             extra = {} if snapshots is None else {"snapshots": snapshots}
@@ -961,12 +1166,19 @@ class GaussianDiffusion:
                 extra["ddim_eta"] = ddim_eta
             if dpm_order is not None:
                 extra["dpm_order"] = dpm_order
+            if stitch is not None:          # by name (GuidedCMDM), or (the CMDM) as the fourth entry of its private bundle
+                if _takes(native, "stitch"):
+                    extra["stitch"] = stitch
+                else:
+                    extra["_guidance"] = (None, False, None, stitch)
             return native(self, x, model_kwargs or {}, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=bool(progress),
                           **extra)
         gen = self.p_sample_loop_progressive if ddim_eta is None else \
             (lambda *a, **k: self.ddim_sample_loop_progressive(*a, eta=ddim_eta, **k))
         if dpm_order is not None:
             gen = lambda *a, **k: self.dpm_solver_sample_loop_progressive(*a, order=dpm_order, **k)
+        if stitch is not None:
+            gen = (lambda g: lambda *a, **k: g(*a, stitch=stitch, **k))(gen)
         final, done = None, 0
         for final in gen(model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
                          model_kwargs=model_kwargs, device=device, progress=progress, step_noise=step_noise, seed=seed,

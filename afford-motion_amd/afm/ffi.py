@@ -229,6 +229,20 @@ class MotionGuide(C.Structure):
     _fields_ = [("contact", C.POINTER(ContactGuide)), ("targets", C.POINTER(JointTargets)), ("gk", c_f32p), ("frame_mask", C.c_void_p)]
 
 
+class Stitch(C.Structure):
+    """afm_stitch (v7-additive): a batch of G * S overlapping windows of G long motions - windows per motion, shared frames of two
+    neighbours, the device weight row [2][overlap] (wl then wr)."""
+    _fields_ = [("windows", i32), ("overlap", i32), ("weights", c_f32p)]
+
+
+class StitchStepArgs(C.Structure):
+    """afm_stitch_step_args (v7-additive): one stitched sampling update - branches, known / mask, DDIM (eta = 0) or 2M rows."""
+    _fields_ = [("x0_c", c_f32p), ("x0_a", c_f32p), ("x0_u", c_f32p), ("scale", c_f32p), ("scale2", c_f32p), ("known", c_f32p),
+                ("mask", C.c_void_p), ("x_t", c_f32p), ("x_next", c_f32p), ("x0_out", c_f32p), ("ddim", C.POINTER(DdimRows)),
+                ("dpm", C.POINTER(DpmRows)), ("x0_prev", c_f32p), ("stitch", C.POINTER(Stitch)), ("clip", i32), ("B", i32), ("L", i32),
+                ("D", i32)]
+
+
 CFG_FORCE_MASKED = 0x1
 
 EXPORTS = {
@@ -310,6 +324,16 @@ EXPORTS = {
                                             C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p, C.c_void_p,
                                             C.POINTER(ContactGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                             C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_stitch_blend": (C.c_int, [c_f32p, c_f32p, C.POINTER(Stitch), i32, i32, i32, C.c_void_p]),
+    "afm_stitch_windows": (C.c_int, [c_f32p, c_f32p, i32, i32, i32, i32, i32, i32, C.c_void_p]),
+    "afm_stitch_join": (C.c_int, [c_f32p, c_f32p, i32, i32, i32, i32, i32, i32, C.c_void_p]),
+    "afm_stitch_step": (C.c_int, [C.POINTER(StitchStepArgs), C.c_void_p]),
+    "afm_cmdm_stitch_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
+                                                   C.POINTER(Stitch)]),
+    "afm_cmdm_stitch_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                             C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p, C.c_void_p,
+                                             C.POINTER(Stitch), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                             C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

@@ -715,3 +715,122 @@ def masked_mse(target: torch.Tensor, pred: torch.Tensor, frame_mask: Optional[to
     ffi.check(lib.afm_masked_mse(target.data_ptr(), pred.data_ptr(), ffi.ptr(km), out.data_ptr(), B, L, D,
                                  ffi.stream_of(target)), "afm_masked_mse")
     return out
+
+
+# ---------------------------------------------------------------------- long motions as overlapping windows (afm.diffusion.Stitch)
+def _stitch_desc(stitch, x: torch.Tensor, who: str):
+    """(afm_stitch of ``stitch`` on x's device, what must stay alive with it), x [B, L, D] checked against the geometry"""
+    if x.dim() != 3:
+        raise ValueError(f"{who}: the windows are [B, L, D], got {tuple(x.shape)}")
+    stitch.check(x.shape[0], x.shape[1])
+    return stitch.describe(x.device)
+
+
+def stitch_blend(x0: torch.Tensor, stitch, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The blend of the frames neighbouring windows share (afm_stitch_blend): x0 [G * S, L, D]; for f < overlap, window w's frame
+    L - overlap + f and window w + 1's frame f both become (wl[f] * left) + (wr[f] * right), float32, each operation rounded on its
+    own; everything else is copied.  ``stitch``: an afm.diffusion.Stitch.  ``out`` may be x0.  No blend (one window, no overlap): the
+    input's bits."""
+    lib = ffi.load()
+    ffi.require_gpu(x0)
+    x0 = ffi.f32c(x0)
+    st, keep = _stitch_desc(stitch, x0, "stitch_blend")
+    out = torch.empty_like(x0) if out is None else out
+    if out.shape != x0.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x0.device:
+        raise ValueError(f"stitch_blend: out must be a contiguous float32 tensor of x0's shape {tuple(x0.shape)} on {x0.device}")
+    B, L, D = x0.shape
+    ffi.check(lib.afm_stitch_blend(x0.data_ptr(), out.data_ptr(), C.byref(st), B, L, D, ffi.stream_of(x0)), "afm_stitch_blend")
+    return out
+
+
+def stitch_windows(long_motion: torch.Tensor, windows: int, overlap: int, length: int) -> torch.Tensor:
+    """[G, F, D] -> the windows [G * S, L, D] (afm_stitch_windows): window w holds the long frames w * (L - overlap) ..; frames at or
+    behind F are zero.  Copies."""
+    lib = ffi.load()
+    ffi.require_gpu(long_motion)
+    x = ffi.f32c(long_motion)
+    if x.dim() != 3:
+        raise ValueError(f"stitch_windows: the long motions are [G, F, D], got {tuple(x.shape)}")
+    G, F, D = x.shape
+    out = torch.empty(G * windows, length, D, dtype=torch.float32, device=x.device)
+    ffi.check(lib.afm_stitch_windows(x.data_ptr(), out.data_ptr(), G, windows, overlap, length, D, F, ffi.stream_of(x)), "afm_stitch_windows")
+    return out
+
+
+def stitch_join(windows_: torch.Tensor, windows: int, overlap: int, frames: int) -> torch.Tensor:
+    """The windows [G * S, L, D] -> [G, F, D] (afm_stitch_join): a shared frame is read from the later window.  Copies."""
+    lib = ffi.load()
+    ffi.require_gpu(windows_)
+    x = ffi.f32c(windows_)
+    if x.dim() != 3 or x.shape[0] % windows != 0:
+        raise ValueError(f"stitch_join: the windows are [G * {windows}, L, D], got {tuple(x.shape)}")
+    B, L, D = x.shape
+    out = torch.empty(B // windows, frames, D, dtype=torch.float32, device=x.device)
+    ffi.check(lib.afm_stitch_join(x.data_ptr(), out.data_ptr(), B // windows, windows, overlap, L, D, frames, ffi.stream_of(x)), "afm_stitch_join")
+    return out
+
+
+def stitch_step(x0: torch.Tensor, x_t: torch.Tensor, stitch, *, x0_a: Optional[torch.Tensor] = None, x0_u: Optional[torch.Tensor] = None,
+                scale: Optional[torch.Tensor] = None, scale2: Optional[torch.Tensor] = None, known: Optional[torch.Tensor] = None,
+                mask: Optional[torch.Tensor] = None, ddim=None, dpm=None, prev: Optional[torch.Tensor] = None, clip: bool = False,
+                out: Optional[torch.Tensor] = None, x0_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One stitched sampling update in one launch (afm_stitch_step): x0 (with ``x0_u`` / ``scale``: cfg_combine; with ``x0_a`` /
+    ``scale2`` too: cfg2_combine - each window with its own scales), the blend of `stitch_blend` - the neighbour window's branches combined
+    with the neighbour's scales - impute with ``known`` / ``mask``, the clamp to [-1, 1] if ``clip``, then the ddim_step expression with
+    ``ddim`` = (a, b, c, d) (no noise term) or the dpm_step expression with ``dpm`` = (a, b, c) and ``prev``; ``x0_out`` (dpm only)
+    receives the final x0.  Equal, bit for bit, to the chain of separate launches.  ``out`` may be ``x_t``."""
+    if (ddim is None) == (dpm is None):
+        raise ValueError("stitch_step: exactly one of ddim= / dpm= rows")
+    if (known is None) != (mask is None):
+        raise ValueError("stitch_step: known= and mask= go together")
+    if ddim is not None and len(ddim) > 4 and ddim[4] is not None:
+        raise ValueError("stitch_step: rows with a noise term are refused - the step noise of shared frames would have to be shared")
+    lib = ffi.load()
+    ffi.require_gpu(x0, x_t, prev)
+    x0, x_t = ffi.f32c(x0), ffi.f32c(x_t)
+    st, keep = _stitch_desc(stitch, x0, "stitch_step")
+    keep = [keep]
+    B, L, D = x0.shape
+    if x_t.shape != x0.shape:
+        raise ValueError(f"stitch_step: x_t {tuple(x_t.shape)} must have x0's shape {tuple(x0.shape)}")
+    out = torch.empty_like(x0) if out is None else out
+    a = ffi.StitchStepArgs()
+    a.x0_c, a.x_t, a.x_next, a.stitch = x0.data_ptr(), x_t.data_ptr(), out.data_ptr(), C.pointer(st)
+    for name, t in (("x0_a", x0_a), ("x0_u", x0_u), ("known", known), ("x0_prev", prev)):
+        if t is not None:
+            t = ffi.f32c(t)
+            if t.shape != x0.shape:
+                raise ValueError(f"stitch_step: {name} {tuple(t.shape)} must have x0's shape {tuple(x0.shape)}")
+            keep.append(t)
+            setattr(a, name, t.data_ptr())
+    for name, t in (("scale", scale), ("scale2", scale2)):
+        if t is not None:
+            t = ffi.f32c(t)
+            if t.numel() != B:
+                raise ValueError(f"stitch_step: {name} must hold one value per sample ({B}), got {tuple(t.shape)}")
+            keep.append(t)
+            setattr(a, name, t.data_ptr())
+    if mask is not None:
+        mask = _mask_u8(mask)
+        if mask.shape != x0.shape:
+            raise ValueError(f"stitch_step: mask {tuple(mask.shape)} must have x0's shape {tuple(x0.shape)}")
+        a.mask = mask.data_ptr()
+    if x0_out is not None:
+        if dpm is None:
+            raise ValueError("stitch_step: x0_out goes with dpm= rows")
+        if x0_out.dtype != torch.float32 or x0_out.shape != x0.shape or not x0_out.is_contiguous() or x0_out.device != x0.device:
+            raise ValueError(f"stitch_step: x0_out must be a contiguous float32 tensor of x0's shape {tuple(x0.shape)} on {x0.device}")
+        a.x0_out = x0_out.data_ptr()
+    rows = [ffi.f32c(r) for r in (ddim[:4] if ddim is not None else dpm)]
+    if any(r.numel() != B for r in rows):
+        raise ValueError(f"stitch_step: the rows hold one value per sample ({B})")
+    if ddim is not None:
+        rr = ffi.DdimRows(*[r.data_ptr() for r in rows], None)
+        a.ddim = C.pointer(rr)
+    else:
+        rr = ffi.DpmRows(*[r.data_ptr() for r in rows])
+        a.dpm = C.pointer(rr)
+    keep += rows + [rr]
+    a.clip, a.B, a.L, a.D = int(bool(clip)), B, L, D
+    ffi.check(lib.afm_stitch_step(C.byref(a), ffi.stream_of(x0)), "afm_stitch_step")
+    return out

@@ -85,3 +85,56 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
                   denoised_fn=motion_impute, cond_fn=cond_fn, model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
     return {"contact": contact, "cond": cond, "motion": motion}
+
+
+def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: torch.Tensor, xyz: torch.Tensor, frames: int, overlap: int,
+                       sampler: str = "dpm++", guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None, sigma: float = 0.8,
+                       contact_mean: float = 0.0, contact_std: float = 1.0, seed: int = 0,
+                       sample_index0: int = 0) -> Dict[str, torch.Tensor]:
+    """One scene, one thing after another: G long motions of ``frames`` frames, each S windows with a text of its own, sampled as
+    ``G * S`` overlapping windows stitched inside the native loop (afm.diffusion.Stitch; "walk to the sofa, sit down, stand up again" is
+    S = 3).  text_feat [G, S, text_dim], xyz [G, N, 3] ->
+    {"contact": [G, S, N, J] ADM samples, "cond": [G * S, N, J] the motion stage's condition, "motion": [G, frames, D] the long motions,
+    "windows": [G * S, L, D] the windows they were joined from}.
+
+    Stage 1 runs as `two_stage_sample`'s on G * S rows - each window's text on its group's cloud - and the hand-off is unchanged.
+    Stage 2 is stitched: window length ``L = overlap + ceil((frames - overlap) / S)``, neighbouring windows share ``overlap`` frames
+    (``2 * overlap <= L``), x_T is the windows of one Philox draw per long motion keyed (seed + 1, sample_index0 + g), and the padded tail
+    of a last window, if any, is masked.  ``sampler``: "dpm++" (dpm_solver_sample_loop) or "ddim" (ddim_sample_loop, eta = 0) on the spaced
+    process of each diffusion - both deterministic, which is what keeps shared frames bit-identical in both windows.
+    ``guidance_scale``: as `two_stage_sample`'s, a [G * S] tensor giving every window a scale of its own.  ``motion_impute``: an
+    afm.diffusion.Impute in the LONG form ([G, frames, D]); it is cut into windows consistently (`Stitch.impute`)."""
+    from .diffusion import Stitch
+    if sampler not in ("dpm++", "ddim"):
+        raise ValueError(f"long_motion_sample: sampler must be 'dpm++' or 'ddim' (a deterministic update), not {sampler!r}")
+    if text_feat.dim() != 3 or xyz.dim() != 3 or xyz.shape[0] != text_feat.shape[0] or xyz.shape[2] != 3:
+        raise ValueError(f"long_motion_sample: text_feat is [G, S, text_dim] and xyz [G, N, 3], got {tuple(text_feat.shape)} and {tuple(xyz.shape)}")
+    if isinstance(guidance_scale, Mapping):
+        dropped = {guidance_drop} if isinstance(guidance_drop, str) else set(guidance_drop)
+        if dropped != set(guidance_scale):
+            raise ValueError(f"guidance_drop {sorted(dropped)} contradicts the conditions of the guidance_scale mapping {list(guidance_scale)}")
+    G, S, N = text_feat.shape[0], text_feat.shape[1], xyz.shape[1]
+    stitch = Stitch(S, overlap, frames)
+    L, B, dev = stitch.length, G * S, xyz.device
+    if motion_impute is not None and tuple(motion_impute.shape[:2]) != (G, frames):          # (refused before the first stage runs)
+        raise ValueError(f"long_motion_sample: motion_impute is the long form [{G}, {frames}, D], got {motion_impute.shape}")
+    x_mask = stitch.x_mask(G, dev, model=amdm)
+    text = text_feat.reshape(B, text_feat.shape[2])
+    cloud = xyz[:, None].expand(G, S, N, 3).reshape(B, N, 3)
+
+    def loop(diffusion, *args, **kw):
+        if sampler == "ddim":
+            return diffusion.ddim_sample_loop(*args, eta=0.0, **kw)
+        return diffusion.dpm_solver_sample_loop(*args, **kw)
+
+    contact = loop(adm_diffusion, adm, (B, N, adm.contact_dim), clip_denoised=False, model_kwargs=dict(c_text_feat=text, c_pc_xyz=cloud),
+                   seed=seed, sample_index0=sample_index0 * S)
+    cond = adist.adm_to_amdm_condition(contact, sigma=sigma, mean=contact_mean, std=contact_std)
+    amdm_kw = dict(c_text_feat=text, c_pc_xyz=cloud, c_pc_contact=cond, x_mask=x_mask)
+    imp = None if motion_impute is None else stitch.impute(motion_impute.known, motion_impute.mask)
+    if guidance_scale is not None:
+        from .cmdm import GuidedCMDM
+        amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
+    windows = loop(amdm_diffusion, amdm, (B, L, amdm.motion_dim), clip_denoised=False, denoised_fn=imp, model_kwargs=amdm_kw, seed=seed + 1,
+                   sample_index0=sample_index0, stitch=stitch)
+    return {"contact": contact.reshape(G, S, N, -1), "cond": cond, "motion": stitch.join(windows), "windows": windows}

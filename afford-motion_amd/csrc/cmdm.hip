@@ -504,7 +504,17 @@ struct LoopCall {
     const afm_cfg2_args* cfg2 = nullptr;
     afm_motion_guide guide = {};      // guided loop: the terms' descriptions of the whole batch (neither term set: none)
     bool guided() const { return guide.contact || guide.targets; }
+    afm_stitch stitch = {};           // stitched loop: the batch is windows of long motions (windows == 0: not stitched)
+    bool stitched() const { return stitch.windows > 0; }
 };
+
+// the sample range of sub-batch s of n over a batch of B cut in units of `unit` samples (a stitched loop: the windows of one long motion,
+// so a window and its neighbour share a sub-batch and a stream; 1: single samples): the one rule of the loops and of their sizers
+inline int unit_sub_count(int B, int unit, int n_streams) { return sub_count(B / unit, n_streams, MAX_SUB); }
+inline void unit_sub_range(int B, int unit, int n, int s, int* start, int* count) {
+    sub_range(B / unit, n, s, start, count);
+    *start *= unit; *count *= unit;
+}
 
 struct SubBatch : SubRange {
     Workspace ws, wsb[2];             // guided loops: wsb[i] the workspace of branch i of the list, behind ws in list order
@@ -546,18 +556,18 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
 
 // the loop workspace of either public description of the guidance (neither: the unguided loop's); AFM_E_BADARG as the loop itself
 int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams,
-                             bool hist = false, const afm_motion_guide* guide = nullptr) {
-    if (validate(w, B, L) != 0 || n_streams < 0) return AFM_E_BADARG;
+                             bool hist = false, const afm_motion_guide* guide = nullptr, int unit = 1) {
+    if (validate(w, B, L) != 0 || n_streams < 0 || unit < 1 || B % unit != 0) return AFM_E_BADARG;
     if (guide && !guide->contact && !guide->targets) return AFM_E_BADARG;
     if (guide && guide->contact && afm_contact_guidance_workspace_bytes(B, guide->contact->N, guide->contact->K) < 0) return AFM_E_BADARG;
     if (guide && guide->targets && (guide->targets->K <= 0 || guide->targets->K > AFM_GUIDE_MAX_JOINTS)) return AFM_E_BADARG;
     Guidance g = {};
     if ((one || two) && make_guidance(*w, one, two, false, nullptr, &g) != 0) return AFM_E_BADARG;
-    const int n = sub_count(B, n_streams, MAX_SUB);
+    const int n = unit_sub_count(B, unit, n_streams);
     int64_t total = 0;
     for (int s = 0; s < n; ++s) {
         SubBatch sb = {};
-        sub_range(B, n, s, &sb.start, &sb.count);
+        unit_sub_range(B, unit, n, s, &sb.start, &sb.count);
         total += carve_sub(*w, g, L, nullptr, &sb, hist, guide);
     }
     return total;
@@ -589,16 +599,22 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         AFM_TRY(afm_motion_guide_check(&c.guide, c.L, c.w->motion_dim));
         if (!c.guide.gk || (c.guide.contact && c.guide.contact->first_guided < 0) || (c.guide.targets && c.guide.targets->first_guided < 0)) return AFM_E_BADARG;
     }
+    const int unit = c.stitched() ? c.stitch.windows : 1;
+    if (c.stitched()) {               // whole long motions, a frame in at most two windows, a deterministic update, no gradient term
+        const afm_stitch& st = c.stitch;
+        if (st.overlap < 0 || 2 * (int64_t)st.overlap > c.L || a.B % st.windows != 0 || !a.ddim || a.noise_term() || a.step_noise || c.guided()) return AFM_E_BADARG;
+        if (st.windows > 1 && st.overlap > 0 && !st.weights) return AFM_E_BADARG;
+    }
     p->nsub = 0;
     if (a.B == 0) return 0;
-    p->nsub = sub_count(a.B, a.n_streams, MAX_SUB);
+    p->nsub = unit_sub_count(a.B, unit, a.n_streams);
     p->branch_streams = g.branch_streams != nullptr;
     int64_t off = 0;
     for (int s = 0; s < p->nsub; ++s) {
         SubBatch& sb = p->sb[s];
         sb = {};
-        sub_range(a.B, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guided(), c.guided() ? &c.guide : nullptr);
+        unit_sub_range(a.B, unit, p->nsub, s, &sb.start, &sb.count);
+        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guided() || c.stitched(), c.guided() ? &c.guide : nullptr);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
         if (p->branch_streams) sb.branch = (hipStream_t)g.branch_streams[s];
     }
@@ -617,7 +633,8 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     p->w.flags = a.loop_flags(p->w.flags);
     // (an imputing loop likewise: the update fused into the motion_layer epilogue is contracted and has no place for the select)
     // (a contact- or target-guided loop too: no place for the gradient term either)
-    if (g.n || c.mask || c.guided()) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
+    // (a stitched loop too: the blend reads the neighbour window's pred_xstart, which only a launch behind the evaluation can)
+    if (g.n || c.mask || c.guided() || c.stitched()) p->w.flags = (p->w.flags | AFM_PRIV_DDIM) & ~(AFM_CMDM_PAIR_LAUNCH | AFM_CMDM_FUSED_LN);
     if (p->nsub >= 2 && ((p->w.flags >> AFM_CMDM_WIDE_TILE_SHIFT) & 0xF) == 0) {
         bool big = true;
         for (int s = 0; s < p->nsub; ++s) big = big && (int64_t)p->sb[s].count * T >= 4096;
@@ -678,6 +695,9 @@ int update_launch(const Loop& l, const SubBatch& sb, const StepRows& rows, const
     if (l.c.mask) { u.known = l.c.known + (int64_t)sb.start * l.p.row; u.mask = l.c.mask + (int64_t)sb.start * l.p.row; }
     u.xpad = sb.ws.xpad; u.ldpad = w.motion_adapter_kpad; u.cols = w.motion_dim;
     if (l.c.a.dpm) { u.x0_prev = l.c.a.first_step + j > 0 ? sb.hist : nullptr; u.x0_keep = sb.hist; }
+    if (l.c.stitched()) {             // (sb.start is a multiple of the windows: the kernel's b % st_S is the window's place)
+        u.st_S = l.c.stitch.windows; u.st_ov = l.c.stitch.overlap; u.st_L = l.c.L; u.st_D = w.motion_dim; u.st_w = l.c.stitch.weights;
+    }
     if (guided_step(l, j)) { u.grad = sb.ggrad; u.gk = l.c.guide.gk + ((int64_t)(l.c.a.n_steps - 1 - j) * l.c.a.B + sb.start); }
     return afm_sampling_update(u, sb.count, sb.stream);
 }
@@ -980,4 +1000,38 @@ extern "C" int afm_cmdm_motion_guide_loop_range(const afm_cmdm_weights* w, float
     if (!guide) return AFM_E_BADARG;
     return guide_loop_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask, *guide,
                             n_steps, first_step, seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
+}
+
+// The stitched loop (afm_stitch: the batch is G * S windows of G long motions), every form behind one entry: the separate-update loop of
+// the form the rows and the guidance name, its update launch the stitched one (the frames two windows share get one pred_xstart between
+// the combine and the select).  Sub-batches are cut over long motions.  A 2M history buffer is always carved, so every form shares one
+// workspace layout.
+extern "C" int64_t afm_cmdm_stitch_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                        const afm_cfg2_args* cfg2, const afm_stitch* stitch) {
+    if ((cfg && cfg2) || !stitch || stitch->windows < 1 || stitch->overlap < 0 || 2 * (int64_t)stitch->overlap > L) return AFM_E_BADARG;
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, nullptr, stitch->windows);
+}
+
+extern "C" int afm_cmdm_stitch_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                          const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                          const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                          const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_stitch* stitch,
+                                          int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                          void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                          void* stream) {
+    (void)seed; (void)sample_index0;          // (no noise is drawn)
+    if (first_step < 0 || !stitch || stitch->windows < 1 || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
+    if (d_c1 || d_c2 || d_sigma || step_noise) return AFM_E_BADARG;          // DDPM rows, explicit step noise: the noise of shared frames would have to be shared
+    if ((rows != nullptr) + (dpm != nullptr) != 1) return AFM_E_BADARG;          // one kind of rows
+    if (rows && rows->sigma) return AFM_E_BADARG;          // a noise term (eta != 0)
+    if (dpm && (!dpm->a || !dpm->b || !dpm->c)) return AFM_E_BADARG;
+    if (B < 0 || B % stitch->windows != 0 || stitch->overlap < 0 || 2 * (int64_t)stitch->overlap > L) return AFM_E_BADARG;
+    if (cfg2 && (!frame_mask || !cfg2_ok(cfg2))) return AFM_E_BADARG;
+    afm_ddim_rows as_ddim = {};
+    if (dpm) { as_ddim = {dpm->a, dpm->b, dpm->c, dpm->c, nullptr}; rows = &as_ddim; }          // (d: any valid row, never used by dpm_update)
+    LoopCall c = {w, x, cond_tokens, frame_mask, cfg, L, {nullptr, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, 0, 0, B,
+                  sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2};
+    c.a.dpm = dpm != nullptr;
+    c.stitch = *stitch;
+    return sample_loop_impl(c);
 }

@@ -349,6 +349,17 @@ __device__ __forceinline__ float cfg_combine2(float x0_c, float x0_a, float x0_u
     const float m = s2 * df;
     return g1 + m;
 }
+// ---- the blend of a frame two overlapping windows of one long motion share (afm_stitch), one element: (wl * x0_left) + (wr * x0_right) in
+// float32, this order, every operation rounded on its own.  x0_left: the element of the earlier window (its last `overlap` frames),
+// x0_right: the same long frame in the later window (its first `overlap` frames); wl / wr: the weight row's entries of the frame's place
+// in the overlap.  Both windows evaluate it on the same operands and get the same bits.  The only place the expression is written:
+// afm_stitch_blend, afm_stitch_step and the update of the stitched native loop call this helper.
+__device__ __forceinline__ float stitch_blend(float x0_left, float x0_right, float wl, float wr) {
+#pragma clang fp contract(off)
+    const float ml = wl * x0_left;
+    const float mr = wr * x0_right;
+    return ml + mr;
+}
 // the ancestral (DDPM) update of one element: (c1 * x0 + c2 * x_t) + sigma * noise, every operation rounded on its own (the reference's
 // float32 torch expression).  The sampling update kernel (afm_ddpm_step, the guided updates) calls this helper.  The fused DDPM updates of
 // the GEMM epilogue and the CDM output kernels spell the expression inline with contraction allowed ("Contraction at the fused

@@ -67,10 +67,35 @@ __device__ __forceinline__ float guided_ddpm_update(float x0, float xt, float c1
     const float sn = sg * nz;
     return mean + sn;
 }
+// the combined pred_xstart of element g of a sample with the scales s / s2: x0, or cfg_combine / cfg_combine2 of the branches
+__device__ __forceinline__ float combined_x0(const afm_loop::Update& p, int64_t g, float s, float s2) {
+    const float v = p.x0[g];
+    if (p.x0_a) return cfg_combine2(v, p.x0_a[g], p.x0_u[g], s, s2);
+    if (p.x0_u) return cfg_combine(v, p.x0_u[g], s);
+    return v;
+}
+// STITCH (afm_loop::Update: st_*): between the combine and the select, the elements of a frame two windows share become stitch_blend of
+// the two windows' combined x0, the neighbour's read st_ov * st_D values further on in its own sample (the later window's first frames)
+// or back (the earlier window's last frames), with the neighbour's scales - decided per element (per_sample need not be a multiple of
+// 4: a quad may straddle the edge of an overlap).  The unstitched instantiation is the kernel as it was.
+template <bool STITCH>
 __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Update p) {
     const int b = blockIdx.y;
     const float s = p.x0_u ? p.scale[b] : 0.f;
     const float s2 = p.x0_a ? p.scale2[b] : 0.f;
+    // stitched: the edges of the window's two overlaps inside the sample [0, st_lo) and [st_hi, per_sample), the neighbours' scales
+    int64_t st_lo = 0, st_hi = 0;
+    bool has_left = false, has_right = false;
+    float sl = 0.f, sl2 = 0.f, sr = 0.f, sr2 = 0.f;
+    if constexpr (STITCH) {
+        const int w = b % p.st_S;
+        has_left = w > 0;                    // an earlier window shares this one's first st_ov frames
+        has_right = w + 1 < p.st_S;          // a later window shares this one's last st_ov frames
+        st_lo = (int64_t)p.st_ov * p.st_D;
+        st_hi = p.per_sample - st_lo;
+        if (has_left) { sl = p.x0_u ? p.scale[b - 1] : 0.f; sl2 = p.x0_a ? p.scale2[b - 1] : 0.f; }
+        if (has_right) { sr = p.x0_u ? p.scale[b + 1] : 0.f; sr2 = p.x0_a ? p.scale2[b + 1] : 0.f; }
+    }
     const float sg = p.sg ? p.sg[b] : 0.f;
     const float gk = p.grad ? p.gk[b] : 0.f;
     float4 r = make_float4(0.f, 1.f, 0.f, 0.f);
@@ -90,6 +115,15 @@ __global__ __launch_bounds__(256) void sampling_update_kernel(const afm_loop::Up
                 float v = p.x0[g];
                 if (p.x0_a) v = cfg_combine2(v, p.x0_a[g], p.x0_u[g], s, s2);
                 else if (p.x0_u) v = cfg_combine(v, p.x0_u[g], s);
+                if constexpr (STITCH) {
+                    if (has_right && i >= st_hi) {               // this window is the left one of the pair
+                        const int k = (int)((i - st_hi) / p.st_D);
+                        v = stitch_blend(v, combined_x0(p, g + st_lo, sr, sr2), p.st_w[k], p.st_w[p.st_ov + k]);
+                    } else if (has_left && i < st_lo) {          // the right one
+                        const int k = (int)(i / p.st_D);
+                        v = stitch_blend(combined_x0(p, g - st_lo, sl, sl2), v, p.st_w[k], p.st_w[p.st_ov + k]);
+                    }
+                }
                 if (p.mask && p.mask[g]) v = p.known[g];
                 if (p.clip) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);          // clip_denoised (NaN passes through, as torch.clamp)
                 const float nz = p.sg ? (p.noise ? p.noise[g] : z[e]) : 0.f;
@@ -271,7 +305,8 @@ extern "C" int afm_layernorm_rows(const float* x, const float* gamma, const floa
 // ---- the sampling update: one launcher behind afm_ddpm_step, afm_ddim_step, afm_dpm_step, afm_cfg_step and the update launch of the native loops
 namespace {
 int enqueue_update(const afm_loop::Update& p, int32_t B, hipStream_t s) {
-    hipLaunchKernelGGL(sampling_update_kernel, stream_grid(quads(p.per_sample), 1024, B), dim3(256), 0, s, p);
+    if (p.stitched()) hipLaunchKernelGGL(sampling_update_kernel<true>, stream_grid(quads(p.per_sample), 1024, B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(sampling_update_kernel<false>, stream_grid(quads(p.per_sample), 1024, B), dim3(256), 0, s, p);
     AFM_CHECK_LAUNCH();
     return 0;
 }
@@ -285,6 +320,12 @@ __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Up
     if (!p.grad != !p.gk) return AFM_E_BADARG;          // cond_fn guidance: the gradient and its coefficient row go together
     if (p.sg && !p.noise && !p.philox) return AFM_E_BADARG;          // (the loops hand their noise in: no Philox draw inside their launch)
     if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
+    if (p.st_S != 0 || p.st_ov != 0) {          // stitched windows: whole long motions, a frame in at most two windows, a deterministic update
+        if (p.st_S < 1 || p.st_ov < 0 || p.st_L <= 0 || p.st_D <= 0 || (int64_t)p.st_L * p.st_D != p.per_sample || 2 * (int64_t)p.st_ov > p.st_L ||
+            B % p.st_S != 0 || !p.ddim || p.sg || p.grad || (p.stitched() && !p.st_w)) return AFM_E_BADARG;
+        if (p.x0_keep && (p.x0_keep == p.x0 || p.x0_keep == p.x0_u || p.x0_keep == p.x0_a)) return AFM_E_BADARG;
+        if (p.xn == p.x0 || p.xn == p.x0_u || p.xn == p.x0_a) return AFM_E_BADARG;          // (the neighbour's x0 is read by another thread)
+    }
     if (B == 0) return 0;
     if (!p.x0_u) return enqueue_update(p, B, (hipStream_t)stream);
     AfmProf prof(AFM_PROF_MISC, (p.x0_a ? 6.0 : 5.0) * B * p.per_sample, (hipStream_t)stream);          // (profiling records: the guided launches only)
@@ -495,4 +536,113 @@ extern "C" int afm_cfg2_combine(const float* x0_c, const float* x0_a, const floa
                        scale_second, out, per_sample);
     AFM_CHECK_LAUNCH();
     return 0;
+}
+
+// ---- stitched windows of long motions (afm_stitch): B = G * S samples [B][L][D], sample g * S + w window w of long motion g, holding the
+// long frames w * (L - ov) .. w * (L - ov) + L - 1.  The same elementwise family as above: no atomics, one writer per element.
+namespace {
+
+// the blend of an x0 alone.  One thread owns BOTH elements of a shared frame (it runs over the earlier window's copy, reads the two, writes
+// the one value to both), an element outside every overlap is copied: out may be x0.
+__global__ __launch_bounds__(256) void stitch_blend_kernel(const float* x0, float* out, const float* __restrict__ wrow, int S, int ov, int D,
+                                                           int64_t per_sample) {
+    const int b = blockIdx.y;
+    const int w = b % S;
+    const int64_t lo = (int64_t)ov * D, hi = per_sample - lo;
+    const int64_t base = (int64_t)b * per_sample;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t g = base + i;
+        if (w + 1 < S && i >= hi) {
+            const int k = (int)((i - hi) / D);
+            const float v = stitch_blend(x0[g], x0[g + lo], wrow[k], wrow[ov + k]);
+            out[g] = v;
+            out[g + lo] = v;
+        } else if (!(w > 0 && i < lo)) {
+            out[g] = x0[g];
+        }
+    }
+}
+
+// windows [G * S][L][D] of long [G][F][D]: copies; a frame at or behind F (the padded tail of the last window) is zero
+__global__ __launch_bounds__(256) void stitch_windows_kernel(const float* __restrict__ lng, float* __restrict__ win, int S, int ov, int L, int D, int F) {
+    const int b = blockIdx.y;
+    const int g = b / S, w = b % S;
+    const int64_t per = (int64_t)L * D;
+    const int64_t first = (int64_t)w * (L - ov);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = first + i / D;
+        win[(int64_t)b * per + i] = f < F ? lng[((int64_t)g * F) * D + first * D + i] : 0.f;
+    }
+}
+
+// long [G][F][D] of windows [G * S][L][D]: copies; a shared frame is read from the later window (both hold the same bits after a
+// stitched chain)
+__global__ __launch_bounds__(256) void stitch_join_kernel(const float* __restrict__ win, float* __restrict__ lng, int S, int ov, int L, int D, int F) {
+    const int g = blockIdx.y;
+    const int64_t per = (int64_t)F * D;
+    const int P = L - ov;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = i / D;
+        int64_t w = f / P;
+        if (w > S - 1) w = S - 1;
+        lng[(int64_t)g * per + i] = win[(((int64_t)g * S + w) * L) * D + (i - w * P * D)];
+    }
+}
+
+// the geometry of a stitch description against a batch: whole long motions, a frame in at most two windows
+inline bool stitch_ok(int S, int ov, int L, int D) { return S >= 1 && ov >= 0 && L > 0 && D > 0 && 2 * (int64_t)ov <= L; }
+
+}  // namespace
+
+extern "C" int afm_stitch_blend(const float* x0, float* out, const afm_stitch* st, int32_t B, int32_t L, int32_t D, void* stream) {
+    if (!st || !stitch_ok(st->windows, st->overlap, L, D) || B < 0 || B % st->windows != 0) return AFM_E_BADARG;
+    if (B == 0) return 0;
+    if (!x0 || !out) return AFM_E_BADARG;
+    const int64_t per = (int64_t)L * D;
+    if (st->windows == 1 || st->overlap == 0) {          // no blend: the input's bits
+        if (out != x0 && hipMemcpyAsync(out, x0, (size_t)B * per * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
+        return 0;
+    }
+    if (!st->weights) return AFM_E_BADARG;
+    hipLaunchKernelGGL(stitch_blend_kernel, stream_grid(per, 1024, B), dim3(256), 0, (hipStream_t)stream, x0, out, st->weights, st->windows, st->overlap, D, per);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int afm_stitch_windows(const float* long_motion, float* windows, int32_t G, int32_t S, int32_t overlap, int32_t L, int32_t D, int32_t F,
+                                  void* stream) {
+    if (!stitch_ok(S, overlap, L, D) || G < 0 || F <= (int64_t)(S - 1) * (L - overlap) + (S > 1 ? overlap : 0) || F > (int64_t)S * L - (int64_t)(S - 1) * overlap) return AFM_E_BADARG;
+    if (G == 0) return 0;
+    if (!long_motion || !windows || (int64_t)G * S > 65535) return AFM_E_BADARG;
+    hipLaunchKernelGGL(stitch_windows_kernel, stream_grid((int64_t)L * D, 1024, G * S), dim3(256), 0, (hipStream_t)stream, long_motion, windows, S, overlap, L, D, F);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int afm_stitch_join(const float* windows, float* long_motion, int32_t G, int32_t S, int32_t overlap, int32_t L, int32_t D, int32_t F,
+                               void* stream) {
+    if (!stitch_ok(S, overlap, L, D) || G < 0 || F <= (int64_t)(S - 1) * (L - overlap) + (S > 1 ? overlap : 0) || F > (int64_t)S * L - (int64_t)(S - 1) * overlap) return AFM_E_BADARG;
+    if (G == 0) return 0;
+    if (!long_motion || !windows || G > 65535) return AFM_E_BADARG;
+    hipLaunchKernelGGL(stitch_join_kernel, stream_grid((int64_t)F * D, 1024, G), dim3(256), 0, (hipStream_t)stream, windows, long_motion, S, overlap, L, D, F);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int afm_stitch_step(const afm_stitch_step_args* a, void* stream) {
+    if (!a || !a->x0_c || !a->stitch || !a->known != !a->mask) return AFM_E_BADARG;
+    if ((a->ddim != nullptr) + (a->dpm != nullptr) != 1) return AFM_E_BADARG;          // one kind of rows, both deterministic
+    if (a->ddim && a->ddim->sigma) return AFM_E_BADARG;          // (the step noise of shared frames would have to be shared)
+    if (a->dpm && !(a->dpm->a && a->dpm->b && a->dpm->c)) return AFM_E_BADARG;
+    if (a->x0_prev && !a->dpm) return AFM_E_BADARG;
+    if (a->L <= 0 || a->D <= 0) return AFM_E_BADARG;
+    afm_loop::Update p = {};
+    p.x0 = a->x0_c; p.xt = a->x_t; p.xn = a->x_next; p.per_sample = (int64_t)a->L * a->D; p.clip = a->clip ? 1 : 0;
+    if (a->ddim) set_ddim_rows(&p, a->ddim);
+    else { p.ddim = 1; p.dpm = 1; p.ra = a->dpm->a; p.rb = a->dpm->b; p.rc = a->dpm->c; p.x0_prev = a->x0_prev; p.x0_keep = a->x0_out; }
+    p.x0_a = a->x0_a; p.x0_u = a->x0_u; p.scale = a->scale; p.scale2 = a->scale2;
+    p.known = a->known; p.mask = a->mask;
+    if (a->x0_out && !a->dpm) return AFM_E_BADARG;
+    p.st_S = a->stitch->windows; p.st_ov = a->stitch->overlap; p.st_L = a->L; p.st_D = a->D; p.st_w = a->stitch->weights;
+    return afm_sampling_update(p, a->B, stream);
 }

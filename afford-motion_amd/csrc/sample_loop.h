@@ -64,6 +64,16 @@ struct Update {
     const float *grad, *gk;         // cond_fn guidance: grad [B][per_sample] = grad log p(y | x_t), gk [B] its coefficient (DDPM: the
                                     //   posterior variance, mean += gk * grad; DDIM / 2M: (1 - abar) / sqrt(abar), x0 += gk * grad after the
                                     //   clamp - the shifted x0 is what x0_keep stores); both NULL: none, grad is never read
+    // stitched windows (afm_stitch): sample b is window b % st_S of long motion b / st_S, per_sample == st_L * st_D.  Between the combine
+    // and the select, an element of the last st_ov frames of a window with a later neighbour, or of the first st_ov frames of one with an
+    // earlier neighbour, becomes stitch_blend (common.h) of its own combined x0 and the neighbour sample's - read from the x0 buffers at
+    // +- st_ov * st_D and combined with the NEIGHBOUR's scales.  Only the x0 buffers are read across samples and only the
+    // element's own x_next / xpad / x0_keep are written, so the in-place update stays race-free (x0_keep must not alias an x0 buffer).
+    // st_w: the weight row [2][st_ov], wl then wr.  st_S <= 1 or st_ov == 0: no blend (the unstitched kernel).  DDIM without a noise
+    // term or 2M only, no grad.
+    int st_S, st_ov, st_L, st_D;
+    const float* st_w;
+    bool stitched() const { return st_S > 1 && st_ov > 0; }
 };
 
 inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }

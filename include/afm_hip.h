@@ -1001,6 +1001,73 @@ int afm_cmdm_motion_guide_loop_range(const afm_cmdm_weights* w, float* x, const 
                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Long motions as overlapping windows (v7-additive).  G long motions are B = G * S samples [B][L][D]: sample g * S + w is window w of
+ * motion g and holds the long frames w * (L - overlap) .. w * (L - overlap) + L - 1, so neighbouring windows share `overlap` frames and,
+ * with 2 * overlap <= L, a frame lies in at most two windows.  The windows are denoised side by side; at every step the frames two
+ * windows share get ONE pred_xstart: for f = 0 .. overlap - 1, the earlier window's frame L - overlap + f ("left") and the later
+ * window's frame f ("right") both become
+ *     v = (wl[f] * x0_left) + (wr[f] * x0_right)          float32, each product rounded, then the sum (no contraction)
+ * with the weight row `weights` = device [2][overlap], wl then wr; the host forms wr[f] = (f + 1) / (overlap + 1), wl[f] = 1 - wr[f] in
+ * float64 and rounds once.  Both windows evaluate the same expression on the same operands: with a deterministic update (DDIM eta = 0,
+ * DPM-Solver++(2M)) and shared frames that start from the same noise, the shared frames stay bit-identical in both windows at every
+ * step.  Order inside a sampling update: guidance combine (each window with its own scales) -> blend -> imputation select -> clamp ->
+ * update; a 2M history keeps the blended value.  windows == 1 or overlap == 0: no blend.  A long motion of F frames,
+ * (S - 1) * (L - overlap) + overlap < F <= S * L - (S - 1) * overlap, leaves a padded tail in the last window only, outside every overlap.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t windows;          /* S >= 1: windows per long motion; the batch is a multiple of it                 */
+    int32_t overlap;          /* frames two neighbouring windows share; 2 * overlap <= L                        */
+    const float* weights;     /* device [2][overlap]: wl then wr (may be NULL when nothing is blended)          */
+} afm_stitch;
+
+/* The blend of an x0 [B][L][D] alone; out may be x0 (one thread owns both copies of a shared element).  No blend: out = x0's bits.
+ * AFM_E_BADARG: B % windows != 0, 2 * overlap > L, a NULL tensor, weights missing where something is blended. */
+int afm_stitch_blend(const float* x0, float* out, const afm_stitch* stitch, int32_t B, int32_t L, int32_t D, void* stream);
+
+/* windows [G * S][L][D] of long_motion [G][F][D] (a frame at or behind F: zeros) and back (a shared frame is read from the later
+ * window).  Copies.  AFM_E_BADARG: F outside the range above, 2 * overlap > L, more than 65535 samples. */
+int afm_stitch_windows(const float* long_motion, float* windows, int32_t G, int32_t S, int32_t overlap, int32_t L, int32_t D, int32_t F,
+                       void* stream);
+int afm_stitch_join(const float* windows, float* long_motion, int32_t G, int32_t S, int32_t overlap, int32_t L, int32_t D, int32_t F,
+                    void* stream);
+
+/* One stitched sampling update in ONE launch, the order above: the branches of afm_cfg_step (x0_u / scale) or afm_cfg2_step (x0_a /
+ * scale2 too), the blend - in an overlap the kernel also reads the neighbour sample's x0 buffers, overlap * D values on or back, and
+ * combines them with the neighbour's scales - known / mask, the clamp, then the afm_ddim_step expression (ddim, sigma NULL) or the
+ * afm_dpm_step expression (dpm, with x0_prev or NULL; x0_out, optional, receives the final blended x0).  Exactly one kind of rows;
+ * rows with a noise term are refused (the step noise of shared frames would have to be shared).  x_next may alias x_t; neither x_next
+ * nor x0_out may alias an x0 buffer. */
+typedef struct {
+    const float* x0_c; const float* x0_a; const float* x0_u;        /* [B][L][D]; x0_a, x0_u optional                      */
+    const float* scale; const float* scale2;                        /* [B]: with x0_u; scale2 with x0_a                    */
+    const float* known; const uint8_t* mask;                        /* [B][L][D] or NULL                                   */
+    const float* x_t; float* x_next;                                /* [B][L][D]                                           */
+    float* x0_out;                                                  /* dpm only: [B][L][D] or NULL                         */
+    const afm_ddim_rows* ddim;                                      /* DDIM rows [B], sigma NULL                           */
+    const afm_dpm_rows* dpm; const float* x0_prev;                  /* or 2M rows [B] and the history (NULL: two-term)     */
+    const afm_stitch* stitch;
+    int32_t clip; int32_t B; int32_t L; int32_t D;
+} afm_stitch_step_args;
+int afm_stitch_step(const afm_stitch_step_args* args, void* stream);
+
+/* The stitched native loop: afm_cmdm_guide_loop_range's signature with the stitch description in the guidance's place, built the same
+ * way (the separate-update form of an imputing loop; a 2M history buffer is always carved).  rows (eta = 0: sigma NULL) or dpm - exactly
+ * one; cfg or cfg2 or neither; known / mask or neither (they must agree in the overlaps: a description that does not is the caller's
+ * error).  The update launch of every step is the stitched one above, in place on x.  Sub-batches are cut over long motions - a window and
+ * its neighbour always share a sub-batch and a stream - n_streams > 1: at most one sub-batch per long motion; the sizer uses the same rule.
+ * AFM_E_BADARG: DDPM rows (d_c1 / d_c2 / d_sigma), rows with a noise term, a step_noise, B % windows != 0, 2 * overlap > L.  seed and
+ * sample_index0 are unused (no noise is drawn).  Chained range calls on one workspace are bit-identical to one call. */
+int64_t afm_cmdm_stitch_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                             const afm_cfg2_args* cfg2, const afm_stitch* stitch);
+int afm_cmdm_stitch_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                               const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                               const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                               const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_stitch* stitch,
+                               int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                               void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
  * CrossAttentionLayer, SelfAttentionBlock, MLP, Residual; pad mask / rotary / kv-cache never used).

@@ -1,0 +1,156 @@
+"""What stitching costs: long motions sampled as overlapping windows in the native loop (afm.diffusion.Stitch, afm_cmdm_stitch_loop_range).
+
+    python tools/bench_stitch.py [--reps 5] [--parent-lib PATH] [--bench-steps 200] [--md PATH]
+
+Cells: DPM-Solver++(2M) on "logsnr20" and DDIM (eta = 0) on "ddim50", G = 1 and G = 8 long motions of S = 4 windows, L = 196, ov = 20
+(724 frames each), N = 8192 scene points, D = 263.  Per cell two arms on the same G * S rows, from the same x_T, alternated inside one
+process:
+
+    stitched        ddim_sample_loop / dpm_solver_sample_loop(..., stitch=Stitch(4, 20))
+    imputing_form   the same rows in the imputing-form loop (an `Impute` that knows nothing) without stitching: the same launches - stored
+                    pred_xstart, one update launch per sub-batch and step - minus the blend, which isolates the blend's cost
+
+reported as ms per long motion and ms per step (median of --reps windows, with the spread), and their ratio.  A timed window holds as many
+loop calls as fill 0.1 s.  With --parent-lib (a libafm_hip.so built from the parent commit) `bench.py --gpus 1 --steps K --warmup 20` runs
+on this build and on the parent's, alternated, each in a fresh child process while this one idles: bench.py's loops are untouched, so its
+figure should lie inside the parent's own call-to-call spread.  One JSON line at the end; --md also writes the table as markdown."""
+import argparse
+import json
+import math
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "afford-motion_amd"))
+
+S, L, OV, N, D = 4, 196, 20, 8192, 263
+GROUPS = (1, 8)
+SAMPLERS = {"dpm2m_logsnr20": ("logsnr20", "dpm"), "ddim50": ("ddim50", "ddim")}
+NEW = ("afm_stitch_blend", "afm_stitch_windows", "afm_stitch_join", "afm_stitch_step", "afm_cmdm_stitch_loop_workspace_bytes",
+       "afm_cmdm_stitch_loop_range")
+MIN_WINDOW_S = 0.1
+
+
+def _timed(fn, calls=1):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / calls
+
+
+def _stats(ts, steps, groups):
+    med = statistics.median(ts)
+    return {"ms_per_long_motion": round(med * 1e3 / groups, 3), "ms_per_step": round(med * 1e3 / steps, 4),
+            "spread_pct": round(100.0 * (max(ts) - min(ts)) / med, 2), "windows": len(ts)}
+
+
+def bench_child(lib):
+    """Child process: bench.py on another build's library (the entry points it lacks are not bound)."""
+    from afm import ffi
+    ffi._LIB_PATH = os.path.abspath(lib)
+    for name in NEW:
+        ffi.EXPORTS.pop(name, None)
+    import runpy
+    runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")
+
+
+def _bench_once(lib, steps):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] if lib is None else [sys.executable, os.path.abspath(__file__), "--bench-child", lib]
+    r = subprocess.run(cmd + ["--gpus", "1", "--steps", str(steps), "--warmup", "20"], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    if r.returncode != 0:
+        raise RuntimeError(f"bench.py failed ({r.returncode}): {r.stderr[-800:]}")
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+    return json.loads(line)["value"]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--bench-steps", type=int, default=200)
+    ap.add_argument("--bench-rounds", type=int, default=3)
+    ap.add_argument("--md", default=None)
+    ap.add_argument("--bench-child", default=None, help=argparse.SUPPRESS)
+    args, rest = ap.parse_known_args()
+    if args.bench_child:
+        sys.argv = [os.path.join(ROOT, "bench.py")] + rest
+        return bench_child(args.bench_child)
+
+    from afm import synth
+    from afm.base import create_gaussian_diffusion, create_model
+    from afm.config import load_config
+    from afm.diffusion import Impute, Stitch
+    dev = torch.device("cuda:0")
+    cfg = lambda resp: load_config("text_to_motion_contact_motion_gen", "cmdm", ["model.data_repr=h3d", "model.input_feats=263",
+                                                                                "model.text_model.max_length=20", "diffusion.steps=1000",
+                                                                                f"diffusion.timestep_respacing='{resp}'"])
+    model = create_model(cfg("ddim50"), device=dev)
+    synth.fill_module_(model)
+    model = model.to(dev).eval()
+    st = Stitch(S, OV, length=L)
+    out = {"shape": {"S": S, "L": L, "overlap": OV, "frames": st.full(L), "N": N, "D": D}, "device": torch.cuda.get_device_name(0), "cells": {}}
+    for name, (resp, kind) in SAMPLERS.items():
+        d = create_gaussian_diffusion(cfg(resp))
+        steps = d.num_timesteps
+        loop = d.ddim_sample_loop if kind == "ddim" else d.dpm_solver_sample_loop
+        for G in GROUPS:
+            B = G * S
+            kw = dict(c_text_feat=synth.text_feature(B).to(dev), c_pc_xyz=synth.scene_cloud(B, N).to(dev),
+                      c_pc_contact=synth.contact_map(B, N).to(dev), x_mask=torch.zeros(B, L, dtype=torch.bool, device=dev))
+            x_T = st.x_T(B, L, D, dev, 1)
+            nothing = Impute(torch.zeros(B, L, D, device=dev), torch.zeros(B, L, D, dtype=torch.bool, device=dev))
+            arms = {"stitched": lambda: loop(model, (B, L, D), noise=x_T, clip_denoised=False, model_kwargs=kw, stitch=st),
+                    "imputing_form": lambda: loop(model, (B, L, D), noise=x_T, clip_denoised=False, denoised_fn=nothing, model_kwargs=kw)}
+            calls = {}
+            for arm, fn in arms.items():          # warm-up (weight packs, condition tokens, workspaces, rows), then the calls per window
+                fn()
+                fn()
+                calls[arm] = max(1, math.ceil(MIN_WINDOW_S / _timed(fn)))
+            ts = {arm: [] for arm in arms}
+            for _ in range(args.reps):             # alternated: a drift of the chip's clocks lands on both arms
+                for arm, fn in arms.items():
+                    ts[arm].append(_timed(fn, calls[arm]))
+            cell = {arm: _stats(ts[arm], steps, G) for arm in arms}
+            cell["steps"], cell["rows"] = steps, B
+            cell["stitched_over_imputing_form"] = round(statistics.median(ts["stitched"]) / statistics.median(ts["imputing_form"]), 4)
+            out["cells"][f"{name}/G{G}"] = cell
+            print(f"[stitch bench] {name} G={G}: {cell}", flush=True)
+    if args.parent_lib:
+        this, parent = [], []
+        for _ in range(args.bench_rounds):
+            this.append(_bench_once(None, args.bench_steps))
+            parent.append(_bench_once(args.parent_lib, args.bench_steps))
+        spread = lambda v: round(100.0 * (max(v) - min(v)) / statistics.median(v), 2)
+        out["bench_py"] = {"steps_per_s_this": this, "steps_per_s_parent": parent, "median_this": statistics.median(this),
+                           "median_parent": statistics.median(parent), "this_over_parent": round(statistics.median(this) / statistics.median(parent), 4),
+                           "spread_pct_this": spread(this), "spread_pct_parent": spread(parent)}
+        print(f"[stitch bench] bench.py: {out['bench_py']}", flush=True)
+    if args.md:
+        lines = [f"# Stitched long motions: S = {S}, L = {L}, ov = {OV} ({st.full(L)} frames), N = {N}, {out['device']}", "",
+                 "| sampler | G | rows | steps | stitched ms / long motion | stitched ms / step | imputing-form ms / step | stitched / imputing-form | spread % (stitched, imputing-form) |",
+                 "|---|---|---|---|---|---|---|---|---|"]
+        for key, c in out["cells"].items():
+            s, g = key.split("/G")
+            lines.append(f"| {s} | {g} | {c['rows']} | {c['steps']} | {c['stitched']['ms_per_long_motion']} | {c['stitched']['ms_per_step']} | "
+                         f"{c['imputing_form']['ms_per_step']} | {c['stitched_over_imputing_form']} | {c['stitched']['spread_pct']}, {c['imputing_form']['spread_pct']} |")
+        if "bench_py" in out:
+            b = out["bench_py"]
+            lines += ["", f"`bench.py --gpus 1 --steps {args.bench_steps} --warmup 20`, this build and the parent's library alternated in fresh processes:", "",
+                      f"* this build: {b['steps_per_s_this']} steps/s (median {b['median_this']}, spread {b['spread_pct_this']} %)",
+                      f"* parent: {b['steps_per_s_parent']} steps/s (median {b['median_parent']}, spread {b['spread_pct_parent']} %)",
+                      f"* this / parent = {b['this_over_parent']}"]
+        with open(args.md, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
