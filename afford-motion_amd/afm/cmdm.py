@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Mapping, Optional
+from typing import Dict, List, Mapping, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -26,6 +26,7 @@ from . import autograd as AG
 from . import ffi, ops
 from ._cache import HeldKey
 from .base import Model
+from .guidance import ContactGuidance, JointTargets, MotionGuidance, scale_row, scale_value
 from .scene import SceneMapEncoder, SceneMapEncoderDecoder
 from .text import TextEncoderMixin, lang_feat_dim_type
 
@@ -134,6 +135,81 @@ class _FlatParamsMixin:
 def _dist_rank() -> int:
     import torch.distributed as dist
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+class LoopExtras(NamedTuple):
+    """The ``_guidance`` of `CMDM.afm_native_loop`: what only this denoiser's native loop takes (a plain tuple in this order serves too).
+    ``cfg`` / ``branch_streams``: GuidedCMDM's afm_cfg_args or afm_cfg2_args and its branch-stream switch.  ``guide``: an
+    afm.diffusion.ContactGuidance (afm_cmdm_guide_loop_range), JointTargets or MotionGuidance (afm_cmdm_motion_guide_loop_range: the step's
+    gradient the sum of the terms that have started) - the gradient at every guided step's x_t is computed on the sub-batch's stream and
+    enters the update launch; the loop runs in the separate-update form like an imputing one, and steps before the guidance starts launch
+    what an imputing loop launches.  ``stitch``: an afm.diffusion.Stitch - the batch rows are overlapping windows of long motions and
+    every step's update launch gives the frames two windows share one pred_xstart (afm_cmdm_stitch_loop_range, every deterministic
+    form; the separate-update form; sub-batches are cut over long motions)."""
+    cfg: object = None
+    branch_streams: bool = False
+    guide: object = None
+    stitch: object = None
+
+
+class LoopPlan(NamedTuple):
+    """One form's native call by names: the C entry, its workspace sizer and the sizer's arguments behind (w, B, L, streams), the form's
+    part of the workspace key, the entry's arguments between frame_mask and B.  A slot names a value of the call; None is a NULL."""
+    entry: str
+    sizer: str
+    size_slots: tuple
+    key: tuple
+    slots: tuple
+
+
+def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, term: str = "none", stitch: bool = False) -> LoopPlan:
+    """The entry a chain reaches: ``update`` "ddpm" / "ddim" / "dpm", ``guidance`` "none" / "cfg" (one scale) / "cfg2" (two), with or without
+    ``impute``, ``term`` "none" / "contact" (a bare ContactGuidance) / "motion" (anything that carries targets), stitched or not.  By
+    priority: a term's entry, the stitched one, the 2M one (each runs every form it is asked for on a workspace of its own size: a history
+    buffer, gradient buffers, sub-batches over long motions), then the entries of both updates (cfg2, impute), then one per update."""
+    if stitch and (update == "ddpm" or term != "none"):
+        raise ValueError(f"no stitched loop with update {update!r} and term {term!r}")
+    base = {"none": "loop", "cfg": "cfg_loop", "cfg2": "cfg2_loop"}[guidance]
+    cfgs = ("cfg" if guidance == "cfg" else None, "cfg2" if guidance == "cfg2" else None)
+    known = ("known", "mask") if impute else (None, None)
+    ddim = "ddim_rows" if update == "ddim" else None
+    ddpm = ("c1", "c2", "sigma") if update == "ddpm" else (None, None, None)
+    tail = ("n_steps", "first_step", "seed", "sample_index0")
+    own = {"contact": "guide", "motion": "motion_guide"}.get(term, "stitch" if stitch else None)
+    if own is not None:                 # both kinds of rows and the 2M rows, one of the three set
+        last = ("stitch" if stitch else "term",)
+        return LoopPlan(f"afm_cmdm_{own}_loop_range", f"afm_cmdm_{own}_loop_workspace_bytes", cfgs + last, (own, base),
+                        ("noise", "tmap", ddim, "dpm_rows" if update == "dpm" else None) + ddpm + cfgs + known + last + tail)
+    if update == "dpm":                 # no noise, no seed
+        return LoopPlan("afm_cmdm_dpm_loop_range", "afm_cmdm_dpm_loop_workspace_bytes", cfgs, ("dpm", base),
+                        ("tmap", "dpm_rows") + cfgs + known + tail[:2])
+    sizer, size = f"afm_cmdm_{base}_workspace_bytes", tuple(c for c in cfgs if c)
+    if guidance == "cfg2" or impute:    # both kinds of rows, then cfg (of the entry's own kind) or NULL, known and mask or NULLs
+        return LoopPlan("afm_cmdm_cfg2_loop_range" if guidance == "cfg2" else "afm_cmdm_impute_loop_range", sizer, size, (None, base),
+                        ("noise", "tmap", ddim) + ddpm + (cfgs[1] or cfgs[0],) + known + tail)
+    name = ("cfg_" if size else "") + ("sample" if update == "ddpm" else "ddim")
+    return LoopPlan(f"afm_cmdm_{name}_loop_range", sizer, size, (None, base), ("noise", "tmap") + (ddpm if ddim is None else (ddim,)) + size + tail)
+
+
+def _refuse_loop(ex: LoopExtras, x, model_kwargs, step_noise, ddim_eta, dpm_order) -> None:
+    """what `CMDM.afm_native_loop` refuses before it touches the device"""
+    if ex.stitch is not None:
+        if ddim_eta is None and dpm_order is None:
+            raise ValueError("stitched windows need a deterministic update: the ancestral loop draws noise at every step, and the noise of "
+                             "the frames two windows share would have to be shared (ddim_eta=0 or dpm_order)")
+        if ddim_eta is not None and float(ddim_eta) != 0.0:
+            raise ValueError(f"stitched windows need a deterministic update: with ddim_eta = {ddim_eta!r} the step noise of the frames two "
+                             "windows share would have to be shared")
+        if step_noise is not None:
+            raise ValueError("stitched windows take no step_noise: the noise of the frames two windows share would have to be shared")
+        if ex.guide is not None:
+            raise ValueError("a cond_fn guidance with stitch= is not built: per-window gradients disagree in the overlaps")
+        ex.stitch.check(x.shape[0], x.shape[1])          # (B % S, 2 * ov <= L, the frames)
+    if any(k in model_kwargs for k in COND_SWITCHES):
+        raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
+                                  "p_sample_loop samples them step by step (p_sample_loop_progressive)")
+    if dpm_order is not None and (ddim_eta is not None or step_noise is not None):
+        raise ValueError("the DPM-Solver++ loop is deterministic: it takes neither ddim_eta nor step_noise")
 
 
 @Model.register()
@@ -542,32 +618,10 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         2) not None: dpm_solver_sample_loop instead (afm_cmdm_dpm_loop_range, every form: the eta = 0 DDIM loop's launches with the
         DPM-Solver++ update and one history buffer per sub-batch in the workspace; no noise: ``step_noise`` is refused, ``seed`` unused;
         sliced chains stay bit-identical because every range call of one chain runs on the same workspace).  ``_guidance``: what only this
-        denoiser's loops take (not a caller's argument; the public keywords are the CDM's, name for name): GuidedCMDM's (afm_cfg_args or
-        afm_cfg2_args or None, branch streams?) and, as an optional third entry, an afm.diffusion.ContactGuidance (afm_cmdm_guide_loop_range), JointTargets or MotionGuidance (afm_cmdm_motion_guide_loop_range: the same loop, the step's gradient the sum of the terms that have started) - its gradient at every guided step's x_t is computed on the sub-batch's stream (two launches) and
-        enters the loop's update launch (afm_cmdm_guide_loop_range, every form; the loop runs in the separate-update form like an
-        imputing one; steps before the guidance starts launch what an imputing loop of that form launches).  A fourth entry of
-        ``_guidance`` (the public keywords stay the CDM's; GuidedCMDM names it ``stitch``): an afm.diffusion.Stitch - the batch rows are overlapping windows of long motions and every step's update launch gives the frames two
-        windows share one pred_xstart (afm_cmdm_stitch_loop_range, every deterministic form: ``ddim_eta`` 0 or ``dpm_order``, plain / one
-        scale / two scales, with or without ``impute``; the separate-update form; sub-batches are cut over long motions).  Refused with a
-        ValueError: the ancestral loop, ``ddim_eta`` != 0, a ``step_noise``, a guidance term, a batch that is no multiple of the windows."""
-        stitch = tuple(_guidance)[3] if _guidance is not None and len(tuple(_guidance)) > 3 else None
-        if stitch is not None:
-            if ddim_eta is None and dpm_order is None:
-                raise ValueError("stitched windows need a deterministic update: the ancestral loop draws noise at every step, and the noise of "
-                                 "the frames two windows share would have to be shared (ddim_eta=0 or dpm_order)")
-            if ddim_eta is not None and float(ddim_eta) != 0.0:
-                raise ValueError(f"stitched windows need a deterministic update: with ddim_eta = {ddim_eta!r} the step noise of the frames two "
-                                 "windows share would have to be shared")
-            if step_noise is not None:
-                raise ValueError("stitched windows take no step_noise: the noise of the frames two windows share would have to be shared")
-            if _guidance is not None and len(tuple(_guidance)) > 2 and tuple(_guidance)[2] is not None:
-                raise ValueError("a cond_fn guidance with stitch= is not built: per-window gradients disagree in the overlaps")
-            stitch.check(x.shape[0], x.shape[1])          # (B % S, 2 * ov <= L, the frames)
-        if any(k in model_kwargs for k in COND_SWITCHES):
-            raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
-                                      "p_sample_loop samples them step by step (p_sample_loop_progressive)")
-        if dpm_order is not None and (ddim_eta is not None or step_noise is not None):
-            raise ValueError("the DPM-Solver++ loop is deterministic: it takes neither ddim_eta nor step_noise")
+        denoiser's loops take (not a caller's argument; the public keywords are the CDM's, name for name) - a `LoopExtras`, or a tuple in
+        its order.  What the loop refuses: `_refuse_loop`; which entry a form reaches and how its arguments lie: `plan_loop_call`."""
+        ex = LoopExtras() if _guidance is None else LoopExtras(*_guidance)
+        _refuse_loop(ex, x, model_kwargs, step_noise, ddim_eta, dpm_order)
         lib = ffi.load()
         ffi.require_gpu(x)
         with torch.no_grad():
@@ -578,23 +632,18 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             w = self._weights()
             if clip_denoised:
                 w.flags |= ffi.CMDM_CLIP_X0                  # per call: _stamp() rewrites the flags on the next _weights()
-            cfg, branch_streams, contact_guide = (tuple(_guidance) + (None,))[:3] if _guidance is not None else (None, False, None)
-            cguide = guide_keep = None
-            if contact_guide is not None:
-                from .diffusion import ContactGuidance, JointTargets, MotionGuidance
-                if isinstance(contact_guide, ContactGuidance):      # a bare contact term keeps its own entry
-                    guide_names = ("afm_cmdm_guide_loop_range", "afm_cmdm_guide_loop_workspace_bytes")
-                    cguide, guide_fm, guide_keep = contact_guide.describe(x, model_kwargs)
-                    cguide.first_guided = contact_guide.first_guided(diffusion)
-                    guide_form = ("guide", cguide.K, cguide.N, bool(cguide.h3d))
+            cfg = ex.cfg
+            term, term_keep, kind, kind_key = None, None, "none", None
+            if ex.guide is not None:
+                both = MotionGuidance(targets=ex.guide) if isinstance(ex.guide, JointTargets) else ex.guide
+                term, term_fm, term_keep = both.describe(x, model_kwargs, diffusion)
+                if isinstance(both, ContactGuidance):      # a bare contact term keeps its own entry
+                    kind, kind_key = "contact", (term.K, term.N, bool(term.h3d))
                 else:                                                # anything that carries targets: the sum's entry
-                    guide_names = ("afm_cmdm_motion_guide_loop_range", "afm_cmdm_motion_guide_loop_workspace_bytes")
-                    both = MotionGuidance(targets=contact_guide) if isinstance(contact_guide, JointTargets) else contact_guide
-                    cguide, guide_fm, guide_keep = both.describe(x, model_kwargs, diffusion)
                     ct, tg = both.contact, both.targets
-                    guide_form = ("motion_guide", None if ct is None else (len(ct.joints or ct.cols), model_kwargs["c_pc_xyz"].shape[1]),
-                                  None if tg is None else tg.K, bool((ct or tg).joints is not None))
-                cguide.frame_mask = ffi.ptr(guide_fm)          # the guidance masks by x_mask also where the model does not (mask_motion=False)
+                    kind, kind_key = "motion", (None if ct is None else (ct.K, model_kwargs["c_pc_xyz"].shape[1]), None if tg is None else tg.K,
+                                                (ct or tg).joints is not None)
+                term.frame_mask = ffi.ptr(term_fm)          # the guidance masks by x_mask also where the model does not (mask_motion=False)
                 gk_rows = diffusion.guidance_rows(x.device, "mean" if ddim_eta is None and dpm_order is None else "x0", B)
             cond = self.condition_tokens(**model_kwargs)
             if tuple(cond.shape[:2]) != (B, w.n_cond):       # (e.g. a cloud of fewer points than contact_model.num_points: the loop reads n_cond rows per sample)
@@ -605,16 +654,17 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             # second stream only adds launches (B = 4: 1311 steps/s on one stream vs 1159 on two, profiles/r02_small_batch.md)
             nsub = max(1, min(int(self.loop_streams), B // 8 if self.loop_streams_auto else B))
             st = st_keep = None
-            if stitch is not None:          # sub-batches are cut over long motions: a window and its neighbour share one
-                st, st_keep = stitch.describe(x.device)
-                nsub = max(1, min(nsub, B // stitch.windows))
+            if ex.stitch is not None:          # sub-batches are cut over long motions: a window and its neighbour share one
+                st, st_keep = ex.stitch.describe(x.device)
+                nsub = max(1, min(nsub, B // ex.stitch.windows))
+                kind_key = (st.windows, st.overlap)
             self._side_streams = ffi.stream_pool(x.device, nsub)          # process-wide pool (hardware queues are few: ffi.stream_pool)
             handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in self._side_streams[:nsub]])
-            # _guidance (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)
+            # ex.cfg (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)
             two = isinstance(cfg, ffi.Cfg2Args)             # one scale per condition: three branches (afm_cmdm_cfg2_loop_range)
-            if two and branch_streams:
+            if two and ex.branch_streams:
                 raise ValueError("branch streams are not built for the two-scale guided loop (three branches)")
-            if branch_streams:
+            if ex.branch_streams:
                 # the unconditioned branch of every sub-batch on a pool stream of its own: 2 * nsub <= 4 streams (the process has four hardware
                 # queues; more streams than queues serialise, ffi.stream_pool)
                 nsub = min(nsub, 2)
@@ -623,38 +673,18 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[:nsub]])
                 branch_handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in pool[nsub:2 * nsub]])
                 cfg.branch_streams = C.cast(branch_handles, C.POINTER(C.c_void_p))
-            cfg_ref = None if cfg is None else C.byref(cfg)
-            # the workspace: its sizer, the sizer's guidance argument and the form that keys the buffer
-            if cfg is None:
-                sizer, size_args, form = "afm_cmdm_loop_workspace_bytes", (), "loop"
-            elif two:
-                sizer, size_args, form = "afm_cmdm_cfg2_loop_workspace_bytes", (cfg_ref,), ("cfg2_loop", cfg.first, cfg.flags)
-            else:
-                sizer, size_args, form = "afm_cmdm_cfg_loop_workspace_bytes", (cfg_ref,), ("cfg_loop", cfg.drop_text, cfg.drop_pc, cfg.flags)
-            # the entry and what it takes behind its rows.  ``every_form``: an entry that runs both updates - both kinds of rows, then cfg or
-            # NULL, known and mask or NULLs
-            every_form = False
-            if cguide is not None:              # every form; a size of its own: the gradient buffers (and always a history buffer)
-                entry = guide_names[0]
-                guide_cfg = (None if two else cfg_ref, cfg_ref if two else None)
-                guide_tail = guide_cfg + ffi.impute_ptrs(impute) + (C.byref(cguide),)
-                sizer, size_args, form = guide_names[1], guide_cfg + (C.byref(cguide),), (guide_form[0], form) + guide_form[1:]
-            elif st is not None:                # every deterministic form; a size of its own: always a history buffer, sub-batches over long motions
-                entry = "afm_cmdm_stitch_loop_range"
-                guide_cfg = (None if two else cfg_ref, cfg_ref if two else None)
-                guide_tail = guide_cfg + ffi.impute_ptrs(impute) + (C.byref(st),)
-                sizer, size_args, form = "afm_cmdm_stitch_loop_workspace_bytes", guide_cfg + (C.byref(st),), ("stitch", form, st.windows, st.overlap)
-            elif tables.dpm is not None:          # every form; a size of its own: the history buffers, which cross the range calls of a chain
-                entry, guide = "afm_cmdm_dpm_loop_range", (None if two else cfg_ref, cfg_ref if two else None) + ffi.impute_ptrs(impute)
-                sizer, size_args, form = "afm_cmdm_dpm_loop_workspace_bytes", guide[:2], ("dpm", form)
-            elif two or impute is not None:
-                entry = "afm_cmdm_cfg2_loop_range" if two else "afm_cmdm_impute_loop_range"
-                guide, every_form = (cfg_ref,) + ffi.impute_ptrs(impute), True
-            elif cfg is None:
-                entry, guide = "afm_cmdm_sample_loop_range" if tables.ddim is None else "afm_cmdm_ddim_loop_range", ()
-            else:
-                entry, guide = "afm_cmdm_cfg_sample_loop_range" if tables.ddim is None else "afm_cmdm_cfg_ddim_loop_range", (cfg_ref,)
-            ws = ffi.workspace(self._ws, (form, B, L, nsub, str(x.device)), sizer, C.byref(w), B, L, nsub, *size_args, device=x.device, single=True)
+            # the form's entry, sizer and argument layout, and the values its slots name.  The workspace key: the plan's, what of the
+            # guidance and of the term / the windows sizes the buffer; every range call of a chain runs on the one buffer
+            plan = plan_loop_call("dpm" if tables.dpm is not None else "ddpm" if tables.ddim is None else "ddim",
+                                  "none" if cfg is None else "cfg2" if two else "cfg", impute is not None, kind, st is not None)
+            cfg_key = () if cfg is None else (cfg.first, cfg.flags) if two else (cfg.drop_text, cfg.drop_pc, cfg.flags)
+            ref = lambda s: None if s is None else C.byref(s)
+            fill = lambda slots, v: [None if s is None else v[s] for s in slots]
+            known, mask = ffi.impute_ptrs(impute)
+            values = {"cfg": ref(cfg), "cfg2": ref(cfg), "known": known, "mask": mask, "term": ref(term), "stitch": ref(st),
+                      "seed": seed & (2**64 - 1), "sample_index0": sample_index0}
+            ws = ffi.workspace(self._ws, (plan.key, cfg_key, kind_key, B, L, nsub, str(x.device)), plan.sizer, C.byref(w), B, L, nsub,
+                               *fill(plan.size_slots, values), device=x.device, single=True)
             head = (C.byref(w), x.data_ptr(), cond.data_ptr(), ffi.ptr(fm))
             tail = (B, L, tables.sched.data_ptr(), ws.data_ptr(), ws.numel(), nsub if nsub > 1 else 0, handles if nsub > 1 else None,
                     ffi.stream_of(x))
@@ -662,21 +692,14 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
-                if cguide is not None or st is not None:          # both kinds of rows and the 2M rows, one of the three set; the gk rows of the slice
-                    if cguide is not None:
-                        cguide.gk = gk_rows[lo:].data_ptr()
-                    rows = (None, tables.dpm_rows(lo), None, None, None) if tables.dpm is not None else \
-                        (lambda r: (r[0], None) + r[1:])(tables.rows(lo, True))
-                    steps = (nz, tables.tmap(lo), *rows, *guide_tail, j1 - j0, j0, seed & (2**64 - 1), sample_index0)
-                elif tables.dpm is not None:      # no noise, no seed
-                    steps = (tables.tmap(lo), tables.dpm_rows(lo), *guide, j1 - j0, j0)
-                else:
-                    steps = (nz, tables.tmap(lo), *tables.rows(lo, every_form), *guide, j1 - j0, j0, seed & (2**64 - 1), sample_index0)
-                ffi.check(getattr(lib, entry)(*head, *steps, *tail), entry)
+                if term is not None:          # the gk rows of the slice
+                    term.gk = gk_rows[lo:].data_ptr()
+                step = dict(values, noise=nz, tmap=tables.tmap(lo), n_steps=j1 - j0, first_step=j0, **tables.named(lo))
+                ffi.check(getattr(lib, plan.entry)(*head, *fill(plan.slots, step), *tail), plan.entry)
 
             step_noise = ffi.run_native_loop(x, n, step_noise, progress, snapshots, call)
             # keep scratch alive until the stream has consumed it
-            self._last_loop_scratch = (tables.keep(), step_noise, cond, fm, _guidance, impute, guide_keep, st, st_keep)
+            self._last_loop_scratch = (tables.keep(), step_noise, cond, fm, ex, impute, term_keep, st, st_keep)
         return x
 
 
@@ -728,20 +751,12 @@ class GuidedCMDM(nn.Module):
             if branch_streams:
                 raise ValueError("GuidedCMDM: branch streams are not built for one scale per condition (three branches)")
             self.order = tuple(scale)
-            scale = {k: self._scale_value(v) for k, v in scale.items()}
+            scale = {k: scale_value(v, "GuidedCMDM", "shape ") for k, v in scale.items()}
         else:
-            scale = self._scale_value(scale)
+            scale = scale_value(scale, "GuidedCMDM", "shape ")
         self.model, self.scale, self.drop, self.force_masked = model, scale, tuple(sorted(set(drop))), bool(force_masked)
         self.branch_streams = bool(branch_streams)
         self._scales: Dict[tuple, torch.Tensor] = {}
-
-    @staticmethod
-    def _scale_value(scale):
-        if isinstance(scale, torch.Tensor):
-            if scale.dim() > 1 or not scale.is_floating_point():
-                raise ValueError(f"GuidedCMDM: `scale` must be a float or a floating [B] tensor, got shape {tuple(scale.shape)} {scale.dtype}")
-            return scale.detach().clone().float().reshape(-1)
-        return float(scale)
 
     @property
     def motion_dim(self) -> int:
@@ -751,14 +766,8 @@ class GuidedCMDM(nn.Module):
         """the [B] scale tensor (`which`: a condition's name with one scale per condition, else None), built once per (B, device)"""
         key = (which, B, str(device))
         if key not in self._scales:
-            scale = self.scale if which is None else self.scale[which]
-            if isinstance(scale, torch.Tensor):
-                if scale.numel() != B:
-                    name = "`scale`" if which is None else f"`scale[{which!r}]`"
-                    raise ValueError(f"GuidedCMDM: {name} holds {scale.numel()} values for a batch of {B}")
-                self._scales[key] = scale.to(device).contiguous()
-            else:
-                self._scales[key] = torch.full((B,), scale, dtype=torch.float32, device=device)
+            self._scales[key] = scale_row(self.scale if which is None else self.scale[which], B, device, "GuidedCMDM",
+                                          "`scale`" if which is None else f"`scale[{which!r}]`")
         return self._scales[key]
 
     def _cfg(self, B: int, device):
@@ -817,5 +826,5 @@ class GuidedCMDM(nn.Module):
             raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")
         cfg = self._cfg(x.shape[0], x.device)          # (a [B] scale of the wrong length is refused here)
         ffi.require_gpu(x)
-        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=(cfg, self.branch_streams, contact_guide, stitch), impute=impute,
-                                          dpm_order=dpm_order, **kw)
+        return self.model.afm_native_loop(diffusion, x, model_kwargs, _guidance=LoopExtras(cfg, self.branch_streams, contact_guide, stitch),
+                                          impute=impute, dpm_order=dpm_order, **kw)

@@ -19,7 +19,6 @@ MI355X-first differences (results unchanged):
 """
 from __future__ import annotations
 
-import ctypes as C
 import enum
 import math
 from typing import Callable, Dict, Iterable, List, Optional, Sequence
@@ -28,7 +27,8 @@ import numpy as np
 import torch
 
 from . import ffi, ops
-from .cmdm import COND_SWITCHES
+from .cmdm import COND_SWITCHES, LoopExtras
+from .guidance import CondFnError, ContactGuidance, Impute, JointTargets, MotionGuidance, Stitch, _guide_mask          # noqa: F401 (kept in this namespace)
 
 
 def betas_for_alpha_bar(num_diffusion_timesteps: int, alpha_bar: Callable[[float], float], max_beta: float = 0.999):
@@ -69,599 +69,6 @@ class LossType(enum.Enum):
 
     def is_vb(self):
         return self in (LossType.KL, LossType.RESCALED_KL)
-
-
-class Impute:
-    """Known values imputed into every pred_xstart of a sampling chain - motion (editing: keyframes to in-between, a root trajectory, a
-    prefix to continue) or contact (steering the first stage: contact pinned on the points of a chosen object, zero contact on a region
-    to keep clear): ``x0 = where(mask, known, x0)`` after the denoiser and before the clamp - what the reference's ``denoised_fn``
-    hook of p_mean_variance exists for (gaussian_diffusion.py:289-294).  A select, never a blend: where the mask is 0 nothing of ``known``
-    reaches the result (a NaN there does not propagate).
-
-    ``known``: float32 [B, L, D] in the model's normalised motion space, or [B, N, J] in the CDM's sample space (normalised contact,
-    (exp(-d^2 / 2 sigma^2) - mean) / std).  ``mask``: bool or uint8 (nonzero = known), broadcastable to it
-    ([L, D], [B, L, 1], [B, 1, D], ...); expanded ONCE to a contiguous uint8 of known's shape on known's device.
-
-    The object is a callable ``imp(x0) -> ops.impute(x0, known, mask)`` (afm_impute, HIP), so it IS a ``denoised_fn`` wherever one is
-    accepted - p_sample, ddim_sample, the progressive generators, the CDM; handed to p_sample_loop / ddim_sample_loop /
-    dpm_solver_sample_loop of a denoiser whose ``afm_native_loop`` names ``impute`` (CMDM `trans_enc`, GuidedCMDM:
-    afm_cmdm_impute_loop_range; the CDM Perceiver: afm_cdm_impute_loop_range) the whole chain stays in the native loop."""
-
-    def __init__(self, known: torch.Tensor, mask: torch.Tensor):
-        if known.dim() != 3:
-            raise ValueError(f"Impute: known must be [B, L, D], got {tuple(known.shape)}")
-        if mask.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f"Impute: mask must be bool or uint8, not {mask.dtype}")
-        if mask.dim() > 3:
-            raise ValueError(f"Impute: mask {tuple(mask.shape)} does not broadcast to known {tuple(known.shape)}")
-        try:
-            full = torch.broadcast_shapes(tuple(mask.shape), tuple(known.shape))
-        except RuntimeError:
-            full = None
-        if full != tuple(known.shape):
-            raise ValueError(f"Impute: mask {tuple(mask.shape)} does not broadcast to known {tuple(known.shape)}")
-        self.known = ffi.f32c(known.detach())
-        # bool storage is one byte of 0 / 1 and the kernels read "nonzero": the expansion is one copy, no arithmetic
-        m = mask.detach().to(device=self.known.device).expand(full).contiguous()
-        self.mask = m.view(torch.uint8) if m.dtype == torch.bool else m
-
-    @classmethod
-    def _of(cls, known: torch.Tensor, mask: torch.Tensor) -> "Impute":
-        imp = cls.__new__(cls)
-        imp.known, imp.mask = known, mask
-        return imp
-
-    @property
-    def shape(self):
-        return tuple(self.known.shape)
-
-    def __call__(self, x0: torch.Tensor) -> torch.Tensor:
-        self.check(x0)
-        return ops.impute(x0, self.known, self.mask)
-
-    def check(self, x: torch.Tensor) -> None:
-        """shape and device against a sample tensor"""
-        if tuple(x.shape) != self.shape:
-            raise ValueError(f"Impute: known is {self.shape}, the sample is {tuple(x.shape)}")
-        if x.device != self.known.device:
-            raise ValueError(f"Impute: known is on {self.known.device}, the sample on {x.device}")
-
-    def narrow(self, start: int, count: int) -> "Impute":
-        """the samples [start, start + count) - the slice of one rank of a sharded job (afm.dist.sharded_sample's sample_fn)"""
-        if start < 0 or count < 0 or start + count > self.known.shape[0]:
-            raise ValueError(f"Impute.narrow({start}, {count}) of a batch of {self.known.shape[0]}")
-        return Impute._of(self.known[start:start + count], self.mask[start:start + count])
-
-
-class Stitch:
-    """G long motions sampled as ``B = G * S`` overlapping windows, batch row ``g * S + w`` window ``w`` of motion ``g`` (DoubleTake /
-    DiffCollage / MultiDiffusion style): the windows are denoised side by side, each with its own text and contact map, and at every
-    step the frames two windows share get one common pred_xstart.  Window ``w`` holds the long frames ``w * (L - ov) .. w * (L - ov) + L -
-    1``; ``2 * ov <= L``, so a frame lies in at most two windows.  ``windows == 1`` or ``overlap == 0``: no blend.
-
-    ``frames`` = F is the long motion's length, ``(S-1)(L-ov) + ov < F <= S*L - (S-1)*ov``; None: the full length.  A shorter F leaves
-    a padded tail in the LAST window only, never inside an overlap - `x_mask` builds the mask for it (the model must have
-    ``mask_motion=True``).  The window length L is the sample's; given ``frames`` it is known up front, ``ov + ceil((F - ov) / S)``
-    (``length=`` states it where neither is given).
-
-    The blend, for f = 0 .. ov-1, of the left element (w, L - ov + f) and the right element (w + 1, f):
-
-        wr[f] = (f + 1) / (ov + 1),  wl[f] = 1 - wr[f]        float64 on the host, rounded to float32 once (a device row [2][ov])
-        v = (wl[f] * x0_left) + (wr[f] * x0_right)            float32, three roundings, this order, no contraction
-
-    Both windows evaluate the same expression on the same operands and get the same bits: with shared frames starting from shared noise
-    (`x_T`) and a deterministic update (DDIM eta = 0, DPM-Solver++(2M)) the shared frames stay bit-identical in both windows at every
-    step, and `join` of the result is the long motion read from either side.  Order inside a step: the guidance combine (each window its
-    own scales) -> blend -> ``denoised_fn`` / `Impute` -> clamp -> update.
-
-    ``ddim_sample_loop(..., stitch=)`` and ``dpm_solver_sample_loop(..., stitch=)`` take it; a CMDM `trans_enc` or a GuidedCMDM runs the
-    whole chain natively (afm_cmdm_stitch_loop_range).  A per-window `Impute` built by hand that disagrees in an overlap is the caller's
-    error - `impute` builds a consistent one from the long form."""
-
-    def __init__(self, windows: int, overlap: int, frames: Optional[int] = None, *, length: Optional[int] = None):
-        S, ov = int(windows), int(overlap)
-        if S < 1:
-            raise ValueError(f"Stitch: at least one window, got {windows!r}")
-        if ov < 0:
-            raise ValueError(f"Stitch: overlap must be >= 0, got {overlap!r}")
-        self.windows, self.overlap = S, ov
-        self.frames = None if frames is None else int(frames)
-        self.length = None if length is None else int(length)
-        if self.length is None and self.frames is not None:
-            if self.frames <= (ov if S > 1 else 0):
-                raise ValueError(f"Stitch: {self.frames} frames do not reach past the first overlap of {ov}")
-            self.length = self.frames if S == 1 else ov + -(-(self.frames - ov) // S)
-        if self.length is not None:
-            self._geometry(self.length)
-        self._w: Dict[str, torch.Tensor] = {}
-
-    # ---- geometry
-    def _geometry(self, L: int) -> int:
-        """checks the geometry at window length L; -> the long motion's frames"""
-        S, ov = self.windows, self.overlap
-        if L <= 0 or 2 * ov > L:
-            raise ValueError(f"Stitch: 2 * overlap <= L - a frame lies in at most two windows - but overlap = {ov}, L = {L}")
-        full = S * L - (S - 1) * ov
-        F = full if self.frames is None else self.frames
-        lo = (S - 1) * (L - ov) + (ov if S > 1 else 0)
-        if not lo < F <= full:
-            raise ValueError(f"Stitch: {S} windows of {L} frames sharing {ov} hold long motions of {lo + 1}..{full} frames (a padded tail "
-                             f"in the last window only), not {F}")
-        return F
-
-    def full(self, L: int) -> int:
-        """the long frames S windows of L frames cover"""
-        return self.windows * L - (self.windows - 1) * self.overlap
-
-    def check(self, B: int, L: int) -> int:
-        """a batch of B windows of L frames against the geometry (ValueError); -> the long motion's frames F"""
-        if B % self.windows != 0:
-            raise ValueError(f"Stitch: the batch holds whole long motions - {B} rows are no multiple of {self.windows} windows")
-        if self.length is not None and L != self.length:
-            raise ValueError(f"Stitch: the windows have {self.length} frames, the sample has {L}")
-        return self._geometry(L)
-
-    def _resolve(self, length: Optional[int], F: Optional[int] = None) -> int:
-        L = self.length if self.length is not None else length
-        if L is None and F is not None:          # a full-length long motion names its window length
-            S, ov = self.windows, self.overlap
-            if (F - ov) % S == 0 and F > ov:
-                L = ov + (F - ov) // S
-        if L is None:
-            raise ValueError("Stitch: the window length is not known - pass length= (or frames= to the constructor)")
-        return int(L)
-
-    # ---- the weight row
-    def weights64(self) -> np.ndarray:
-        """[2, ov] float64: wl then wr"""
-        wr = (np.arange(self.overlap, dtype=np.float64) + 1.0) / (self.overlap + 1.0)
-        return np.stack([1.0 - wr, wr], 0)
-
-    def weights(self, device) -> torch.Tensor:
-        """the float32 row [2, ov] on ``device``: `weights64` rounded once"""
-        key = str(torch.device(device))
-        if key not in self._w:
-            self._w[key] = torch.from_numpy(self.weights64()).float().contiguous().to(device)
-        return self._w[key]
-
-    def describe(self, device) -> tuple:
-        """(afm_stitch on ``device``, what must stay alive with it)"""
-        w = self.weights(device)
-        return ffi.Stitch(self.windows, self.overlap, w.data_ptr() if self.overlap > 0 else None), w
-
-    # ---- long form <-> windows (copies; float32 on the GPU: afm_stitch_windows / afm_stitch_join)
-    def windows_of(self, long: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
-        """[G, F, D] -> [G * S, L, D]; frames at or behind F (the padded tail) are zero.  F: the long motion's frames or the full length."""
-        if long.dim() != 3:
-            raise ValueError(f"Stitch.windows_of: the long form is [G, F, D], got {tuple(long.shape)}")
-        G, F, D = long.shape
-        S, ov = self.windows, self.overlap
-        L = self._resolve(length, F)
-        self._geometry(L)
-        lo = (S - 1) * (L - ov) + (ov if S > 1 else 0)
-        if not lo < F <= self.full(L):
-            raise ValueError(f"Stitch.windows_of: {F} frames do not fill {S} windows of {L} sharing {ov}")
-        if long.is_cuda and long.dtype == torch.float32:
-            return ops.stitch_windows(long, S, ov, L)
-        out = long.new_zeros(G, S, L, D)
-        for w in range(S):
-            a = w * (L - ov)
-            n = max(0, min(L, F - a))
-            out[:, w, :n] = long[:, a:a + n]
-        return out.reshape(G * S, L, D)
-
-    def join(self, windows: torch.Tensor) -> torch.Tensor:
-        """[G * S, L, D] -> [G, F, D]; a shared frame is read from the later window (after a stitched chain both hold the same bits)"""
-        if windows.dim() != 3:
-            raise ValueError(f"Stitch.join: the windows are [G * S, L, D], got {tuple(windows.shape)}")
-        B, L, D = windows.shape
-        F = self.check(B, L)
-        S, ov = self.windows, self.overlap
-        if windows.is_cuda and windows.dtype == torch.float32:
-            return ops.stitch_join(windows, S, ov, F)
-        v = windows.reshape(B // S, S, L, D)
-        parts = [v[:, w, :(L - ov if w + 1 < S else F - w * (L - ov))] for w in range(S)]
-        return torch.cat(parts, 1)
-
-    def x_mask(self, G: int, device, length: Optional[int] = None, model=None) -> torch.Tensor:
-        """bool [G * S, L], True = padded frame: the tail of every long motion's last window.  ``model``: checked for mask_motion."""
-        L = self._resolve(length)
-        F = self._geometry(L)
-        pad = self.full(L) - F
-        if pad > 0 and model is not None and not getattr(getattr(model, "model", model), "mask_motion", True):
-            raise ValueError("Stitch: a long motion shorter than its windows pads the last window, which needs a model with mask_motion=True")
-        m = torch.zeros(G, self.windows, L, dtype=torch.bool)
-        if pad > 0:
-            m[:, -1, L - pad:] = True
-        return m.reshape(G * self.windows, L).to(device)
-
-    def impute(self, known_long: torch.Tensor, mask_long: torch.Tensor, length: Optional[int] = None) -> Impute:
-        """the `Impute` over the windows of a long-form known [G, F, D] / mask (broadcastable to it): consistent in the overlaps by
-        construction (padded frames know nothing)"""
-        imp = Impute(known_long, mask_long)          # (the long form checked and expanded like any other)
-        return Impute._of(self.windows_of(imp.known, length), self.windows_of(imp.mask, length))
-
-    def x_T(self, B: int, L: int, D: int, device, seed: int, sample_index0: int = 0) -> torch.Tensor:
-        """x_T of a stitched chain: the windows of ONE Philox draw [G, S*L - (S-1)*ov, D] keyed (seed, sample_index0 + g) - shared frames
-        start from shared noise, and a long motion's noise does not depend on the batch around it"""
-        self.check(B, L)
-        return self.windows_of(ops.randn((B // self.windows, self.full(L), D), device, seed=seed, sample_index0=sample_index0, step=-1), L)
-
-
-class CondFnError(ValueError, NotImplementedError):
-    """A ``cond_fn`` that does not implement the protocol ``cond_fn(x, t, **model_kwargs) -> float32 tensor of x's shape on x's device``: it
-    cannot be called that way, or what it returns does not fit.  It is a ValueError, which is what such a callable deserves.  The second
-    base, NotImplementedError, and the `inspect.signature(...).bind` check in `_cond_grad` exist for one reason: before ``cond_fn`` was
-    opened every sampler refused it with NotImplementedError, and tests/test_gpu_dpm.py::test_refusals still expects that from
-    ``dpm_solver_sample(_loop)`` for ``lambda *a: None`` and ``lambda *a, **k: None``.  When that test is brought up to date, drop the
-    second base and the bind check."""
-
-
-class ContactGuidance:
-    """A ``cond_fn`` that pulls the contact joints of a generated motion towards the points its contact map marks - the analytic gradient
-    of an energy between the map the motion implies and the map it was given (afm_contact_guidance, HIP; no second network, no autograd).
-
-    ``cols``: K ints (K <= 16), each the column of the x coordinate of one contact joint in the motion vector, y and z the next two
-    columns.  The columns must hold ABSOLUTE joint positions (``data_repr`` "pos" / "pos_rot": ``3 * j`` for joint j).  "h3d" has no such
-    columns - it integrates root velocities over the frames: ``ContactGuidance.h3d(joints, mean, std)`` builds the guidance for it, the
-    same energy on the joints the features imply (below).  The triples lie inside D and do not overlap.
-    ``mean`` / ``std`` [D] de-normalise the motion.  ``sigma``: the contact map's.  ``scale``: a float or a [B] tensor.  ``t_start``: only
-    steps whose model timestep is < t_start are guided (None: all).
-
-    With q = c_pc_xyz [B, N, 3], c = c_pc_contact [B, N, K] (un-normalised exp(-d^2 / 2 sigma^2), as the motion model receives it) and
-    x_mask [B, L] (True = padded frame) taken from ``model_kwargs``:
-
-        p[b,f,k,:] = x[b,f,cols[k]:cols[k]+3] * std + mean
-        d2[b,n,k]  = min over frames f with not x_mask[b,f] of |p[b,f,k,:] - q[b,n,:]|^2,   f* the FIRST frame that attains it
-        chat       = exp(-d2 / (2 sigma^2))          (no valid frame: 0)
-        E[b]       = 1/(N K) sum_{n,k} (chat - c)^2
-        dE/dx[b,f,cols[k]+a] = sum_{n: f*(b,n,k) = f} (2/(N K)) (chat - c) chat (-(p_a - q_a) / sigma^2) std_a
-
-    ``guide(x, t, **model_kwargs)`` returns -scale[b] * dE/dx [B, L, D] float32 (zero outside the named columns, in padded frames, in a
-    sample without a valid frame or with t >= t_start); ``guide.energy(x, **model_kwargs)`` returns E [B] (a score for picking the best
-    of several samples).  float32 order of the kernel: d2 = (dx*dx + dy*dy) + dz*dz; w = (chat - c) * chat; S_a = sum of w * (p_a - q_a)
-    over the frame's points (lane l of a wave takes n = l, l + 64, ..., then a fixed butterfly); result = ((scale * coef) * std_a) * S_a
-    with coef = 2 / (N K sigma^2) rounded once from float64.  No atomics: bit-identical run to run, and a sample's result does not depend
-    on the batch around it.
-
-    Handed as ``cond_fn`` to p_sample_loop / ddim_sample_loop / dpm_solver_sample_loop of a denoiser whose ``afm_native_loop`` names
-    ``contact_guide`` (GuidedCMDM) or takes it in its private ``_guidance`` bundle (CMDM `trans_enc`, whose public keywords stay the
-    CDM's) - afm_cmdm_guide_loop_range - the whole chain stays in the native loop; any other
-    denoiser samples step by step through ``__call__``.  A skipped step natively launches no gradient kernel; step by step it adds a
-    gradient of zeros (the same values).
-
-    HumanML3D features: ``ContactGuidance.h3d(joints, mean, std, to_scene=None, ...)`` with ``joints`` the K joint indices 0..21.  With
-    u = x * std + mean (columns 0..66 are read) and the velocity columns 0..2 of a padded frame counted as zero, p is the reference's
-    recover_from_ric placed in the scene:
-
-        th_f = sum_{g<f} u[g,0];  c_f, s_f = cos, sin(2 th_f);  X_f = sum_{1<=h<=f} (u[h-1,1] c_h - u[h-1,2] s_h),  Z_f likewise with
-        (u[h-1,1] s_h + u[h-1,2] c_h);  joint 0: P = (X_f, u[f,3], Z_f);  joint j, l = u[f, 4+3(j-1):7+3(j-1)]:
-        P = (l_x c_f - l_z s_f + X_f, l_y, l_x s_f + l_z c_f + Z_f);  p = A P + t,  to_scene = [A|t]
-
-    ``to_scene`` is a float32 [3, 4] or [B, 3, 4] tensor (None: identity).  The reference does not fix how an h3d motion is placed in
-    its scene, so the transform is an argument and not a constant; y-up to z-up is A = [[1, 0, 0], [0, 0, -1], [0, 1, 0]], t = 0.  The
-    energy is the one above on these p; the gradient is its exact adjoint through the recovery (afm_contact_guidance with an
-    afm_h3d_layout: four launches - recovery, the two passes, adjoint - every scan over the frames one lane's serial chain in frame order,
-    no atomics), nonzero only in columns 0..66 of valid frames.  Everything else - ``__call__``, ``energy``, ``first_guided``, the
-    native loops of GuidedCMDM and the plain CMDM, ``two_stage_sample(contact_guidance=...)`` - works as for the column form."""
-
-    def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, sigma: float = 0.8, scale=1.0, t_start: Optional[int] = None):
-        cols = [int(c) for c in cols]
-        if not 1 <= len(cols) <= ffi.GUIDE_MAX_JOINTS:
-            raise ValueError(f"ContactGuidance: 1 to {ffi.GUIDE_MAX_JOINTS} contact joints, got {len(cols)}")
-        if mean.dim() != 1 or std.shape != mean.shape:
-            raise ValueError(f"ContactGuidance: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
-        D = mean.shape[0]
-        for i, c in enumerate(cols):
-            if c < 0 or c + 3 > D:
-                raise ValueError(f"ContactGuidance: the column triple {c}..{c + 2} leaves the motion vector of {D} columns")
-            if any(abs(c - o) < 3 for o in cols[:i]):
-                raise ValueError(f"ContactGuidance: the column triple at {c} overlaps another one")
-        if not float(sigma) > 0.0:
-            raise ValueError(f"ContactGuidance: sigma must be positive, got {sigma!r}")
-        if isinstance(scale, torch.Tensor):
-            if scale.dim() > 1 or not scale.is_floating_point():
-                raise ValueError(f"ContactGuidance: `scale` must be a float or a floating [B] tensor, got {tuple(scale.shape)} {scale.dtype}")
-            scale = scale.detach().clone().float().reshape(-1)
-        else:
-            scale = float(scale)
-        self.cols, self.D, self.sigma, self.scale = cols, D, float(sigma), scale
-        self.mean, self.std = ffi.f32c(mean.detach()), ffi.f32c(std.detach())
-        self.t_start = None if t_start is None else int(t_start)
-        self._dev: Dict[tuple, tuple] = {}
-        self.joints, self.to_scene = None, None            # (set by ContactGuidance.h3d alone)
-
-    @classmethod
-    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, to_scene: Optional[torch.Tensor] = None, sigma: float = 0.8, scale=1.0,
-            t_start: Optional[int] = None) -> "ContactGuidance":
-        """The guidance of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67): ``joints`` are joint indices 0..21, ``to_scene`` a
-        float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity).  See the class docstring."""
-        who = "ContactGuidance.h3d"
-        joints = ops.h3d_joint_list([int(j) for j in joints], ffi.GUIDE_MAX_JOINTS, who)
-        if mean.dim() != 1 or std.shape != mean.shape:
-            raise ValueError(f"{who}: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
-        if mean.shape[0] < ffi.H3D_COLS:
-            raise ValueError(f"{who}: the joint recovery reads columns 0..{ffi.H3D_COLS - 1}, the motion vector has {mean.shape[0]}")
-        to_scene = ops.h3d_to_scene(to_scene, who)
-        # (the column checks of __init__ do not apply: the layout names joints, `cols` is not read)
-        self = cls([0], mean, std, sigma=sigma, scale=scale, t_start=t_start)
-        self.cols, self.joints, self.to_scene = [], joints, to_scene
-        return self
-
-    def _scale_row(self, B: int, device) -> torch.Tensor:
-        if isinstance(self.scale, torch.Tensor):
-            if self.scale.numel() != B:
-                raise ValueError(f"ContactGuidance: `scale` holds {self.scale.numel()} values for a batch of {B}")
-            return self.scale.to(device).contiguous()
-        return torch.full((B,), self.scale, dtype=torch.float32, device=device)
-
-    def describe(self, x: torch.Tensor, model_kwargs) -> tuple:
-        """(afm_contact_guide of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it)"""
-        if x.dim() != 3 or x.shape[-1] != self.D:
-            raise ValueError(f"ContactGuidance: mean / std describe {self.D} columns, the sample is {tuple(x.shape)}")
-        for name in ("c_pc_xyz", "c_pc_contact"):
-            if name not in model_kwargs:
-                raise ValueError(f"ContactGuidance reads {name} from model_kwargs")
-        B, K = x.shape[0], len(self.cols if self.joints is None else self.joints)
-        q, c = model_kwargs["c_pc_xyz"], model_kwargs["c_pc_contact"]
-        if q.dim() != 3 or q.shape[0] != B or q.shape[2] != 3 or tuple(c.shape) != (B, q.shape[1], K):
-            raise ValueError(f"ContactGuidance: c_pc_xyz must be [{B}, N, 3] and c_pc_contact [{B}, N, {K}], got {tuple(q.shape)} and {tuple(c.shape)}")
-        scale = self._scale_row(B, x.device)
-        lay = ts = None
-        if self.joints is not None:
-            ts, stride = ops.h3d_to_scene_on(self.to_scene, B, x.device, "ContactGuidance.h3d")
-            lay = ffi.H3dLayout()
-            for k, j in enumerate(self.joints):
-                lay.joints[k] = j
-            lay.to_scene, lay.to_scene_stride = ffi.ptr(ts), stride
-        ffi.require_gpu(x, q, c)
-        q, c = ffi.f32c(q), ffi.f32c(c)
-        key = str(x.device)
-        if key not in self._dev:
-            self._dev[key] = (self.mean.to(x.device), self.std.to(x.device))
-        mean, std = self._dev[key]
-        fm = model_kwargs.get("x_mask")
-        if fm is not None:
-            fm = fm.to(device=x.device).reshape(B, -1)
-            if fm.shape[1] != x.shape[1]:
-                raise ValueError(f"ContactGuidance: x_mask covers {fm.shape[1]} frames, the sample has {x.shape[1]}")
-            fm = (fm.view(torch.uint8) if fm.dtype == torch.bool else fm.to(torch.uint8)).contiguous()
-        g = ffi.ContactGuide()
-        g.q, g.c, g.mean, g.std, g.scale = q.data_ptr(), c.data_ptr(), mean.data_ptr(), std.data_ptr(), scale.data_ptr()
-        for k, col in enumerate(self.cols):
-            g.cols[k] = col
-        g.K, g.N, g.sigma = K, q.shape[1], self.sigma
-        g.t_start = 2**62 if self.t_start is None else self.t_start
-        if lay is not None:
-            g.h3d = C.pointer(lay)
-        return g, fm, (q, c, mean, std, scale, fm, lay, ts)
-
-    def first_guided(self, diffusion: "GaussianDiffusion") -> int:
-        """the first executed step of a chain on ``diffusion`` that is guided: the count of its timesteps >= t_start"""
-        return 0 if self.t_start is None else sum(1 for t in diffusion.timestep_map if t >= self.t_start)
-
-    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
-        g, fm, keep = self.describe(x, model_kwargs)
-        return ops.contact_guidance(g, x, fm, None if self.t_start is None else t.to(x.device))[0]
-
-    def energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
-        g, fm, keep = self.describe(x, model_kwargs)
-        return ops.contact_guidance(g, x, fm, grad=False, energy=True)[1]
-
-
-def _guide_mask(x: torch.Tensor, model_kwargs, who: str):
-    """x_mask of ``model_kwargs`` as the guidance kernels take it: uint8 [B, L] on x's device, or None"""
-    fm = model_kwargs.get("x_mask")
-    if fm is None:
-        return None
-    fm = fm.to(device=x.device).reshape(x.shape[0], -1)
-    if fm.shape[1] != x.shape[1]:
-        raise ValueError(f"{who}: x_mask covers {fm.shape[1]} frames, the sample has {x.shape[1]}")
-    return (fm.view(torch.uint8) if fm.dtype == torch.bool else fm.to(torch.uint8)).contiguous()
-
-
-class JointTargets:
-    """A ``cond_fn`` that pulls named joints to given places in the scene at given frames: a root path through the room, a hand on a handle
-    at frame 120, a pose at the last frame (afm_motion_guidance, HIP; no network, no autograd).
-
-    ``cols``: K ints (K <= 16), the column of the x coordinate of each guided joint in a motion vector of ABSOLUTE positions (``data_repr``
-    "pos" / "pos_rot"), as for `ContactGuidance`; ``JointTargets.h3d(joints, mean, std, ...)`` names joints 0..21 of a HumanML3D-feature
-    motion instead (joint 0 is the root) and takes the ``to_scene`` of `ContactGuidance.h3d`.  ``target`` [B, L, K, 3] float32 holds scene
-    coordinates, ``weight`` [B, L, K] their weights: 0 means no target, and the target value there is never read (it may be NaN).
-    ``scale``: a float or a [B] tensor.  ``t_start``: only steps whose model timestep is < t_start are guided (None: all).  ``x_mask`` is
-    read from ``model_kwargs`` as `ContactGuidance` reads it; nothing else is.
-
-    With p[b,f,k,:] the positions `ContactGuidance` computes (x * std rounded, + mean rounded; h3d: the recovery kernel's output):
-
-        E[b] = sum over valid frames f and joints k of  w * ((dx*dx + dy*dy) + dz*dz),   d = p - target
-
-    not normalised - the weights are the caller's.  Order of the sum: the items e = f * K + k of a sample are dealt to the 256 threads of one
-    block, thread i adds e = i, i + 256, ... in that order, then a fixed wave butterfly and ((r0 + r1) + r2) + r3 over the four waves: a
-    function of the sample alone.  ``guide(x, t, **model_kwargs)`` returns -scale[b] * dE/dx:
-
-        columns:  d = target_a - p_a;  m = w * d;  grad[b,f,cols[k]+a] = ((scale[b] * 2) * std_a) * m                       (one launch)
-        h3d:      S[b,f,k,:] = w * (target - p), carried through the adjoint of the recovery with coef = 2 - the kernel and the six
-                  serial scans `ContactGuidance.h3d` uses (three launches: recovery, targets, adjoint)
-
-    exactly zero in every other column, in padded frames, where w == 0 and in samples with t >= t_start.  ``guide.energy(x, **model_kwargs)``
-    returns E [B].  Handed as ``cond_fn`` it stays in the native loops wherever a `ContactGuidance` does (afm_cmdm_motion_guide_loop_range);
-    `MotionGuidance` sums it with a `ContactGuidance`."""
-
-    def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, target: torch.Tensor, weight: torch.Tensor, scale=1.0,
-                 t_start: Optional[int] = None, _who: str = "JointTargets"):
-        cols = [int(c) for c in cols]
-        if not 1 <= len(cols) <= ffi.GUIDE_MAX_JOINTS:
-            raise ValueError(f"{_who}: 1 to {ffi.GUIDE_MAX_JOINTS} guided joints, got {len(cols)}")
-        if mean.dim() != 1 or std.shape != mean.shape:
-            raise ValueError(f"{_who}: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
-        D = mean.shape[0]
-        for i, c in enumerate(cols):
-            if c < 0 or c + 3 > D:
-                raise ValueError(f"{_who}: the column triple {c}..{c + 2} leaves the motion vector of {D} columns")
-            if any(abs(c - o) < 3 for o in cols[:i]):
-                raise ValueError(f"{_who}: the column triple at {c} overlaps another one")
-        K = len(cols)
-        if not isinstance(target, torch.Tensor) or not isinstance(weight, torch.Tensor) or target.dim() != 4 or target.shape[2:] != (K, 3) or \
-                tuple(weight.shape) != tuple(target.shape[:3]) or not target.is_floating_point() or not weight.is_floating_point():
-            raise ValueError(f"{_who}: target must be a floating [B, L, {K}, 3] tensor and weight [B, L, {K}], got "
-                             f"{tuple(getattr(target, 'shape', ()))} and {tuple(getattr(weight, 'shape', ()))}")
-        if isinstance(scale, torch.Tensor):
-            if scale.dim() > 1 or not scale.is_floating_point():
-                raise ValueError(f"{_who}: `scale` must be a float or a floating [B] tensor, got {tuple(scale.shape)} {scale.dtype}")
-            scale = scale.detach().clone().float().reshape(-1)
-        else:
-            scale = float(scale)
-        self.cols, self.D, self.scale = cols, D, scale
-        self.mean, self.std = ffi.f32c(mean.detach()), ffi.f32c(std.detach())
-        self.target, self.weight = ffi.f32c(target.detach()), ffi.f32c(weight.detach())
-        self.t_start = None if t_start is None else int(t_start)
-        self._dev: Dict[str, tuple] = {}
-        self.joints, self.to_scene = None, None            # (set by JointTargets.h3d alone)
-
-    @classmethod
-    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, target: torch.Tensor, weight: torch.Tensor,
-            to_scene: Optional[torch.Tensor] = None, scale=1.0, t_start: Optional[int] = None) -> "JointTargets":
-        """The targets of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67): ``joints`` are joint indices 0..21 (0: the root),
-        ``to_scene`` a float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity).  See the class docstring."""
-        who = "JointTargets.h3d"
-        joints = ops.h3d_joint_list([int(j) for j in joints], ffi.GUIDE_MAX_JOINTS, who)
-        if mean.dim() != 1 or std.shape != mean.shape:
-            raise ValueError(f"{who}: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
-        if mean.shape[0] < ffi.H3D_COLS:
-            raise ValueError(f"{who}: the joint recovery reads columns 0..{ffi.H3D_COLS - 1}, the motion vector has {mean.shape[0]}")
-        to_scene = ops.h3d_to_scene(to_scene, who)
-        # (the column checks of __init__ run on stand-in triples: the layout names joints, `cols` is not read)
-        self = cls([3 * k for k in range(len(joints))], mean, std, target=target, weight=weight, scale=scale, t_start=t_start, _who=who)
-        self.cols, self.joints, self.to_scene = [], joints, to_scene
-        return self
-
-    @property
-    def K(self) -> int:
-        return len(self.cols if self.joints is None else self.joints)
-
-    def describe(self, x: torch.Tensor, model_kwargs, *, shared=None) -> tuple:
-        """(afm_joint_targets of this sample tensor, x_mask as uint8 or None, what must stay alive with it).  ``shared``: the (mean, std,
-        to_scene, stride) device tensors of the contact term this one is summed with - a sum names one set of them."""
-        who = "JointTargets" if self.joints is None else "JointTargets.h3d"
-        if x.dim() != 3 or x.shape[-1] != self.D:
-            raise ValueError(f"{who}: mean / std describe {self.D} columns, the sample is {tuple(x.shape)}")
-        B, L, K = x.shape[0], x.shape[1], self.K
-        if tuple(self.target.shape) != (B, L, K, 3):
-            raise ValueError(f"{who}: target is {tuple(self.target.shape)} and weight {tuple(self.weight.shape)}, the sample needs "
-                             f"[{B}, {L}, {K}, 3] and [{B}, {L}, {K}]")
-        if isinstance(self.scale, torch.Tensor) and self.scale.numel() != B:
-            raise ValueError(f"{who}: `scale` holds {self.scale.numel()} values for a batch of {B}")
-        fm = _guide_mask(x, model_kwargs, who)
-        if self.joints is not None:                            # (checked against the batch before anything touches the device)
-            ops.h3d_to_scene_on(self.to_scene, B, x.device, who)
-        ffi.require_gpu(x)
-        key = str(x.device)
-        if key not in self._dev:
-            self._dev[key] = (self.mean.to(x.device), self.std.to(x.device), self.target.to(x.device).contiguous(),
-                              self.weight.to(x.device).contiguous())
-        mean, std, target, weight = self._dev[key]
-        scale = self.scale.to(x.device).contiguous() if isinstance(self.scale, torch.Tensor) else \
-            torch.full((B,), self.scale, dtype=torch.float32, device=x.device)
-        lay = ts = None
-        if self.joints is not None:
-            ts, stride = ops.h3d_to_scene_on(self.to_scene, B, x.device, who)
-        if shared is not None:
-            mean, std = shared[0], shared[1]
-            if self.joints is not None:
-                ts, stride = shared[2], shared[3]
-        if self.joints is not None:
-            lay = ffi.H3dLayout()
-            for k, j in enumerate(self.joints):
-                lay.joints[k] = j
-            lay.to_scene, lay.to_scene_stride = ffi.ptr(ts), stride
-        g = ffi.JointTargets()
-        g.target, g.weight, g.scale, g.mean, g.std = target.data_ptr(), weight.data_ptr(), scale.data_ptr(), mean.data_ptr(), std.data_ptr()
-        for k, col in enumerate(self.cols):
-            g.cols[k] = col
-        g.K = K
-        g.t_start = 2**62 if self.t_start is None else self.t_start
-        if lay is not None:
-            g.h3d = C.pointer(lay)
-        return g, fm, (target, weight, mean, std, scale, fm, lay, ts)
-
-    def first_guided(self, diffusion: "GaussianDiffusion") -> int:
-        """the first executed step of a chain on ``diffusion`` that carries this term: the count of its timesteps >= t_start"""
-        return 0 if self.t_start is None else sum(1 for t in diffusion.timestep_map if t >= self.t_start)
-
-    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
-        return MotionGuidance(targets=self)(x, t, **model_kwargs)
-
-    def energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
-        return MotionGuidance(targets=self).energies(x, **model_kwargs)[1]
-
-
-class MotionGuidance:
-    """The sum of a `ContactGuidance` and a `JointTargets` as one ``cond_fn`` (either may be None, not both):
-    grad = grad_contact + grad_targets, each term the float32 result of that guidance alone, joined by one rounded addition per element -
-    ``MotionGuidance(contact, targets)(x, t, **kw)`` equals ``contact(x, t, **kw) + targets(x, t, **kw)`` bit for bit.  Each term keeps its
-    own ``scale`` and ``t_start``: a sample (step by step) or a step (native loops) a term does not guide gets exactly zero from it.  The two
-    terms describe one motion: the same ``mean`` / ``std``, both on columns or both on HumanML3D features, the same ``to_scene`` -
-    ValueError otherwise.  The joint lists may differ; an h3d motion is recovered once per term.  Launches per guided step: the contact
-    term's 2 (h3d: 4) plus the targets' 1 (h3d: 3).  ``energies(x, **kw)`` returns (E_contact or None, E_targets or None)."""
-
-    def __init__(self, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None):
-        if contact is None and targets is None:
-            raise ValueError("MotionGuidance: at least one of contact / targets")
-        if contact is not None and not isinstance(contact, ContactGuidance):
-            raise TypeError(f"MotionGuidance: contact must be a ContactGuidance, not {type(contact).__name__}")
-        if targets is not None and not isinstance(targets, JointTargets):
-            raise TypeError(f"MotionGuidance: targets must be a JointTargets, not {type(targets).__name__}")
-        if contact is not None and targets is not None:
-            if contact.D != targets.D or not torch.equal(contact.mean.cpu(), targets.mean.cpu()) or not torch.equal(contact.std.cpu(), targets.std.cpu()):
-                raise ValueError("MotionGuidance: the two terms de-normalise the motion with different mean / std")
-            if (contact.joints is None) != (targets.joints is None):
-                raise ValueError("MotionGuidance: one term names columns of absolute positions, the other joints of HumanML3D features")
-            a, b = contact.to_scene, targets.to_scene
-            if (a is None) != (b is None) or (a is not None and a is not b and (a.shape != b.shape or a.device != b.device or not torch.equal(a.cpu(), b.cpu()))):          # (compared on the host: no device arithmetic)
-                raise ValueError("MotionGuidance: the two terms place the motion in the scene with different to_scene transforms")
-        self.contact, self.targets = contact, targets
-
-    @property
-    def t_start(self):
-        """None if any term guides every step, else the latest start"""
-        ts = [g.t_start for g in (self.contact, self.targets) if g is not None]
-        return None if any(t is None for t in ts) else max(ts)
-
-    def describe(self, x: torch.Tensor, model_kwargs, diffusion: Optional["GaussianDiffusion"] = None) -> tuple:
-        """(afm_motion_guide of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).  With
-        ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
-        cg = tg = fm = shared = None
-        keep = []
-        if self.contact is not None:
-            cg, fm, ck = self.contact.describe(x, model_kwargs)
-            keep.append((cg, ck))
-            shared = (ck[2], ck[3], ck[7], cg.h3d.contents.to_scene_stride if cg.h3d else 0)
-            if diffusion is not None:
-                cg.first_guided = self.contact.first_guided(diffusion)
-        if self.targets is not None:
-            tg, fm, tk = self.targets.describe(x, model_kwargs, shared=shared)
-            keep.append((tg, tk))
-            if diffusion is not None:
-                tg.first_guided = self.targets.first_guided(diffusion)
-        g = ffi.MotionGuide()
-        if cg is not None:
-            g.contact = C.pointer(cg)
-        if tg is not None:
-            g.targets = C.pointer(tg)
-        return g, fm, keep
-
-    def first_guided(self, diffusion: "GaussianDiffusion") -> int:
-        """the first executed step of a chain on ``diffusion`` that carries any term"""
-        return min(g.first_guided(diffusion) for g in (self.contact, self.targets) if g is not None)
-
-    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
-        g, fm, keep = self.describe(x, model_kwargs)
-        timed = any(q is not None and q.t_start is not None for q in (self.contact, self.targets))
-        return ops.motion_guidance(g, x, fm, t.to(x.device) if timed else None)[0]
-
-    def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
-        g, fm, keep = self.describe(x, model_kwargs)
-        return ops.motion_guidance(g, x, fm, grad=False, energy=True)[1:]
 
 
 class _DeviceTables:
@@ -921,9 +328,10 @@ class GaussianDiffusion:
         yield from self._progressive(self.p_sample, model, shape, noise, device, progress, step_noise, seed, sample_index0,
                                      dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs))
 
-    def _progressive(self, step_fn, model, shape, noise, device, progress, step_noise, seed, sample_index0, step_kwargs):
-        """The loop of both progressive generators: x_T (``noise`` or Philox step -1; stitched: `Stitch.x_T`), then ``step_fn`` (p_sample /
-        ddim_sample) per executed step j at timestep index T - 1 - j, each output yielded and its sample fed to the next step."""
+    def _progressive(self, step_fn, model, shape, noise, device, progress, step_noise, seed, sample_index0, step_kwargs, history=False):
+        """The loop of the progressive generators: x_T (``noise`` or Philox step -1; stitched: `Stitch.x_T`), then ``step_fn`` (p_sample /
+        ddim_sample; ``history``: dpm_solver_sample, which takes the previous step's pred_xstart where the others take their noise keys) per
+        executed step j at timestep index T - 1 - j, each output yielded and its sample fed to the next step."""
         if device is None:
             device = next(model.parameters()).device
         seed = self._fresh_seed("_sample_calls") if seed is None else seed
@@ -933,11 +341,13 @@ class GaussianDiffusion:
         if progress:
             from tqdm.auto import tqdm
             steps = tqdm(list(steps))
+        prev = None
         for j, i in enumerate(steps):
-            out = step_fn(model, img, tvec[i], noise=None if step_noise is None else step_noise[j], seed=seed,
-                          sample_index0=sample_index0, step=j, **step_kwargs)
+            own = dict(prev_xstart=prev) if history else \
+                dict(noise=None if step_noise is None else step_noise[j], seed=seed, sample_index0=sample_index0, step=j)
+            out = step_fn(model, img, tvec[i], **own, **step_kwargs)
             yield out
-            img = out["sample"]
+            img, prev = out["sample"], out["pred_xstart"]
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, *,
@@ -1093,21 +503,8 @@ class GaussianDiffusion:
         self.dpm_tables("cpu", order)          # (order checked before anything runs)
         if stitch is not None:
             self._check_stitch(stitch, model, shape, cond_fn, None, None, "dpm_solver_sample_loop")
-        if device is None:
-            device = next(model.parameters()).device
-        seed = self._fresh_seed("_sample_calls") if seed is None else seed
-        img = noise if noise is not None else self._x_T(shape, device, seed, sample_index0, stitch)
-        tvec = self.tables(device).timesteps(shape[0])
-        steps: Iterable[int] = range(self.num_timesteps - 1, -1, -1)
-        if progress:
-            from tqdm.auto import tqdm
-            steps = tqdm(list(steps))
-        prev = None
-        for i in steps:
-            out = self.dpm_solver_sample(model, img, tvec[i], clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                         model_kwargs=model_kwargs, prev_xstart=prev, order=order, stitch=stitch)
-            yield out
-            img, prev = out["sample"], out["pred_xstart"]
+        kw = dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, stitch=stitch)
+        yield from self._progressive(self.dpm_solver_sample, model, shape, noise, device, progress, None, seed, sample_index0, kw, history=True)
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                                device=None, progress=False, *, order: int = 2, step_noise=None, seed: Optional[int] = None,
@@ -1124,53 +521,59 @@ class GaussianDiffusion:
         return self._sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
                                  None, seed, sample_index0, snapshots, ddim_eta=None, dpm_order=int(order), stitch=stitch)
 
+    def _native_keywords(self, native, clip_denoised, denoised_fn, cond_fn, model_kwargs, snapshots, ddim_eta, dpm_order, stitch) -> Optional[dict]:
+        """The keywords of ``native(...)`` for this chain, or None: sample step by step.  Native: the denoiser has an ``afm_native_loop``
+        and nothing needs the host between steps - no rescaled timesteps, no condition switch in ``model_kwargs``, no generic
+        ``denoised_fn`` / ``cond_fn``.  A ``denoised_fn`` that is an `Impute` stays native where the loop names ``impute``, DPM-Solver++
+        where it names ``dpm_order``; a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets` or a `MotionGuidance`, and a `Stitch`,
+        where it names ``contact_guide`` / ``stitch`` (GuidedCMDM) or - the plain CMDM, whose public keywords stay the CDM's - takes a
+        private ``_guidance`` bundle (afm.cmdm.LoopExtras)."""
+        if native is None or self.rescale_timesteps or any(k in (model_kwargs or {}) for k in COND_SWITCHES):
+            return None
+        impute = denoised_fn if isinstance(denoised_fn, Impute) else None
+        guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance)) else None
+        if (denoised_fn is not None and impute is None) or (cond_fn is not None and guide is None):
+            return None
+        kw, private = {}, {}
+        for name, field, value in (("impute", None, impute), ("dpm_order", None, dpm_order), ("contact_guide", "guide", guide),
+                                   ("stitch", "stitch", stitch)):
+            if value is None:
+                continue
+            if _takes(native, name):
+                kw[name] = value
+            elif field is not None:
+                private[field] = value
+            else:
+                return None
+        if private:
+            if not _takes(native, "_guidance"):
+                return None
+            kw["_guidance"] = LoopExtras(**private)
+        if snapshots is not None:
+            kw["snapshots"] = snapshots
+        if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused update
+            kw["clip_denoised"] = True
+        if ddim_eta is not None:
+            kw["ddim_eta"] = ddim_eta
+        return kw
+
     def _sample_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, step_noise, seed,
                      sample_index0, snapshots, ddim_eta: Optional[float], dpm_order: Optional[int] = None, stitch=None):
         """p_sample_loop (ddim_eta None) / ddim_sample_loop / dpm_solver_sample_loop (dpm_order not None): the denoiser's
-        ``afm_native_loop`` when it has one and nothing needs the host between steps - no generic ``cond_fn``, no rescaled timesteps, no
-        condition switch in ``model_kwargs`` - else the progressive generator.  A ``denoised_fn`` that is an `Impute` stays native where
-        the loop names ``impute``, DPM-Solver++ where it names ``dpm_order``, a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets` or a `MotionGuidance` where it names
-        ``contact_guide`` (GuidedCMDM) or, the plain CMDM, takes it in its private ``_guidance`` bundle; any other ``denoised_fn`` or ``cond_fn``, and a loop that does not name the keyword, sample step by step."""
+        ``afm_native_loop`` where `_native_keywords` finds the chain native, else the progressive generator."""
         native = getattr(model, "afm_native_loop", None)
         if stitch is not None:          # a stitched chain (ddim_sample_loop / dpm_solver_sample_loop): native where the loop names ``stitch``
             self._check_stitch(stitch, model, shape, cond_fn, step_noise, ddim_eta, "dpm_solver_sample_loop" if dpm_order is not None else "ddim_sample_loop")
-        impute = denoised_fn if isinstance(denoised_fn, Impute) else None
-        guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance)) else None
-        guide_kw = None                    # how the loop takes the guidance: by name, or (the CMDM) inside its private bundle
-        if guide is not None and native is not None:
-            if _takes(native, "contact_guide"):
-                guide_kw = {"contact_guide": guide}
-            elif _takes(native, "_guidance"):
-                guide_kw = {"_guidance": (None, False, guide)}
-        if native is not None and (cond_fn is None or guide_kw is not None) and \
-                not self.rescale_timesteps and \
-                not any(k in (model_kwargs or {}) for k in COND_SWITCHES) and \
-                (denoised_fn is None or (impute is not None and _takes(native, "impute"))) and \
-                (dpm_order is None or _takes(native, "dpm_order")) and \
-                (stitch is None or _takes(native, "stitch") or _takes(native, "_guidance")):
+        extra = self._native_keywords(native, clip_denoised, denoised_fn, cond_fn, model_kwargs, snapshots, ddim_eta, dpm_order, stitch)
+        if extra is not None:
             if device is None:
                 device = next(model.parameters()).device
             seed = self._fresh_seed("_sample_calls") if seed is None else seed
             x = noise.clone() if noise is not None else self._x_T(shape, device, seed, sample_index0, stitch)
             if isinstance(step_noise, (list, tuple)):
                 step_noise = torch.stack(list(step_noise), 0)
-            extra = {} if snapshots is None else {"snapshots": snapshots}
-            if impute is not None:
-                impute.check(x)
-                extra["impute"] = impute
-            if guide_kw is not None:
-                extra.update(guide_kw)
-            if clip_denoised:                      # the reference's default: pred_xstart clamped to [-1, 1] inside the fused update
-                extra["clip_denoised"] = True
-            if ddim_eta is not None:
-                extra["ddim_eta"] = ddim_eta
-            if dpm_order is not None:
-                extra["dpm_order"] = dpm_order
-            if stitch is not None:          # by name (GuidedCMDM), or (the CMDM) as the fourth entry of its private bundle
-                if _takes(native, "stitch"):
-                    extra["stitch"] = stitch
-                else:
-                    extra["_guidance"] = (None, False, None, stitch)
+            if "impute" in extra:
+                extra["impute"].check(x)
             return native(self, x, model_kwargs or {}, step_noise=step_noise, seed=seed, sample_index0=sample_index0, progress=bool(progress),
                           **extra)
         gen = self.p_sample_loop_progressive if ddim_eta is None else \

@@ -499,6 +499,14 @@ class LoopTables:
     def dpm_rows(self, lo: int):
         return C.byref(self.dpm.rows(lo))
 
+    def named(self, lo: int) -> dict:
+        """the one kind of rows this chain has, by the slot names of afm.cmdm.plan_loop_call"""
+        if self.dpm is not None:
+            return {"dpm_rows": self.dpm_rows(lo)}
+        if self.ddim is not None:
+            return {"ddim_rows": C.byref(self.ddim.rows(lo))}
+        return dict(zip(("c1", "c2", "sigma"), self.rows(lo)))
+
     def keep(self) -> tuple:
         """what the caller holds until the stream has consumed the loop"""
         return (self.sched, self.ddim, self.dpm)

@@ -1,0 +1,587 @@
+"""What a sampling chain is conditioned on besides the denoiser's own inputs: known values (`Impute`), overlapping windows of a long
+motion (`Stitch`), and the analytic ``cond_fn`` guidance terms (`ContactGuidance`, `JointTargets`, their sum `MotionGuidance`).  The
+samplers of afm.diffusion take them, the native loops of afm.cmdm / afm.cdm read their descriptions; afm.diffusion re-exports every name
+(``afm.diffusion.Stitch is afm.guidance.Stitch``).  This module imports `ffi` and `ops` only: of a diffusion object it reads
+``timestep_map`` and nothing else."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import ffi, ops
+
+
+class Impute:
+    """Known values imputed into every pred_xstart of a sampling chain - motion (editing: keyframes to in-between, a root trajectory, a
+    prefix to continue) or contact (steering the first stage: contact pinned on the points of a chosen object, zero contact on a region
+    to keep clear): ``x0 = where(mask, known, x0)`` after the denoiser and before the clamp - what the reference's ``denoised_fn``
+    hook of p_mean_variance exists for (gaussian_diffusion.py:289-294).  A select, never a blend: where the mask is 0 nothing of ``known``
+    reaches the result (a NaN there does not propagate).
+
+    ``known``: float32 [B, L, D] in the model's normalised motion space, or [B, N, J] in the CDM's sample space (normalised contact,
+    (exp(-d^2 / 2 sigma^2) - mean) / std).  ``mask``: bool or uint8 (nonzero = known), broadcastable to it
+    ([L, D], [B, L, 1], [B, 1, D], ...); expanded ONCE to a contiguous uint8 of known's shape on known's device.
+
+    The object is a callable ``imp(x0) -> ops.impute(x0, known, mask)`` (afm_impute, HIP), so it IS a ``denoised_fn`` wherever one is
+    accepted - p_sample, ddim_sample, the progressive generators, the CDM; handed to p_sample_loop / ddim_sample_loop /
+    dpm_solver_sample_loop of a denoiser whose ``afm_native_loop`` names ``impute`` (CMDM `trans_enc`, GuidedCMDM:
+    afm_cmdm_impute_loop_range; the CDM Perceiver: afm_cdm_impute_loop_range) the whole chain stays in the native loop."""
+
+    def __init__(self, known: torch.Tensor, mask: torch.Tensor):
+        if known.dim() != 3:
+            raise ValueError(f"Impute: known must be [B, L, D], got {tuple(known.shape)}")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"Impute: mask must be bool or uint8, not {mask.dtype}")
+        if mask.dim() > 3:
+            raise ValueError(f"Impute: mask {tuple(mask.shape)} does not broadcast to known {tuple(known.shape)}")
+        try:
+            full = torch.broadcast_shapes(tuple(mask.shape), tuple(known.shape))
+        except RuntimeError:
+            full = None
+        if full != tuple(known.shape):
+            raise ValueError(f"Impute: mask {tuple(mask.shape)} does not broadcast to known {tuple(known.shape)}")
+        self.known = ffi.f32c(known.detach())
+        # bool storage is one byte of 0 / 1 and the kernels read "nonzero": the expansion is one copy, no arithmetic
+        m = mask.detach().to(device=self.known.device).expand(full).contiguous()
+        self.mask = m.view(torch.uint8) if m.dtype == torch.bool else m
+
+    @classmethod
+    def _of(cls, known: torch.Tensor, mask: torch.Tensor) -> "Impute":
+        imp = cls.__new__(cls)
+        imp.known, imp.mask = known, mask
+        return imp
+
+    @property
+    def shape(self):
+        return tuple(self.known.shape)
+
+    def __call__(self, x0: torch.Tensor) -> torch.Tensor:
+        self.check(x0)
+        return ops.impute(x0, self.known, self.mask)
+
+    def check(self, x: torch.Tensor) -> None:
+        """shape and device against a sample tensor"""
+        if tuple(x.shape) != self.shape:
+            raise ValueError(f"Impute: known is {self.shape}, the sample is {tuple(x.shape)}")
+        if x.device != self.known.device:
+            raise ValueError(f"Impute: known is on {self.known.device}, the sample on {x.device}")
+
+    def narrow(self, start: int, count: int) -> "Impute":
+        """the samples [start, start + count) - the slice of one rank of a sharded job (afm.dist.sharded_sample's sample_fn)"""
+        if start < 0 or count < 0 or start + count > self.known.shape[0]:
+            raise ValueError(f"Impute.narrow({start}, {count}) of a batch of {self.known.shape[0]}")
+        return Impute._of(self.known[start:start + count], self.mask[start:start + count])
+
+
+class Stitch:
+    """G long motions sampled as ``B = G * S`` overlapping windows, batch row ``g * S + w`` window ``w`` of motion ``g`` (DoubleTake /
+    DiffCollage / MultiDiffusion style): the windows are denoised side by side, each with its own text and contact map, and at every
+    step the frames two windows share get one common pred_xstart.  Window ``w`` holds the long frames ``w * (L - ov) .. w * (L - ov) + L -
+    1``; ``2 * ov <= L``, so a frame lies in at most two windows.  ``windows == 1`` or ``overlap == 0``: no blend.
+
+    ``frames`` = F is the long motion's length, ``(S-1)(L-ov) + ov < F <= S*L - (S-1)*ov``; None: the full length.  A shorter F leaves
+    a padded tail in the LAST window only, never inside an overlap - `x_mask` builds the mask for it (the model must have
+    ``mask_motion=True``).  The window length L is the sample's; given ``frames`` it is known up front, ``ov + ceil((F - ov) / S)``
+    (``length=`` states it where neither is given).
+
+    The blend, for f = 0 .. ov-1, of the left element (w, L - ov + f) and the right element (w + 1, f):
+
+        wr[f] = (f + 1) / (ov + 1),  wl[f] = 1 - wr[f]        float64 on the host, rounded to float32 once (a device row [2][ov])
+        v = (wl[f] * x0_left) + (wr[f] * x0_right)            float32, three roundings, this order, no contraction
+
+    Both windows evaluate the same expression on the same operands and get the same bits: with shared frames starting from shared noise
+    (`x_T`) and a deterministic update (DDIM eta = 0, DPM-Solver++(2M)) the shared frames stay bit-identical in both windows at every
+    step, and `join` of the result is the long motion read from either side.  Order inside a step: the guidance combine (each window its
+    own scales) -> blend -> ``denoised_fn`` / `Impute` -> clamp -> update.
+
+    ``ddim_sample_loop(..., stitch=)`` and ``dpm_solver_sample_loop(..., stitch=)`` take it; a CMDM `trans_enc` or a GuidedCMDM runs the
+    whole chain natively (afm_cmdm_stitch_loop_range).  A per-window `Impute` built by hand that disagrees in an overlap is the caller's
+    error - `impute` builds a consistent one from the long form."""
+
+    def __init__(self, windows: int, overlap: int, frames: Optional[int] = None, *, length: Optional[int] = None):
+        S, ov = int(windows), int(overlap)
+        if S < 1:
+            raise ValueError(f"Stitch: at least one window, got {windows!r}")
+        if ov < 0:
+            raise ValueError(f"Stitch: overlap must be >= 0, got {overlap!r}")
+        self.windows, self.overlap = S, ov
+        self.frames = None if frames is None else int(frames)
+        self.length = None if length is None else int(length)
+        if self.length is None and self.frames is not None:
+            if self.frames <= (ov if S > 1 else 0):
+                raise ValueError(f"Stitch: {self.frames} frames do not reach past the first overlap of {ov}")
+            self.length = self.frames if S == 1 else ov + -(-(self.frames - ov) // S)
+        if self.length is not None:
+            self._geometry(self.length)
+        self._w: Dict[str, torch.Tensor] = {}
+
+    # ---- geometry
+    def _geometry(self, L: int) -> int:
+        """checks the geometry at window length L; -> the long motion's frames"""
+        S, ov = self.windows, self.overlap
+        if L <= 0 or 2 * ov > L:
+            raise ValueError(f"Stitch: 2 * overlap <= L - a frame lies in at most two windows - but overlap = {ov}, L = {L}")
+        full = S * L - (S - 1) * ov
+        F = full if self.frames is None else self.frames
+        lo = (S - 1) * (L - ov) + (ov if S > 1 else 0)
+        if not lo < F <= full:
+            raise ValueError(f"Stitch: {S} windows of {L} frames sharing {ov} hold long motions of {lo + 1}..{full} frames (a padded tail "
+                             f"in the last window only), not {F}")
+        return F
+
+    def full(self, L: int) -> int:
+        """the long frames S windows of L frames cover"""
+        return self.windows * L - (self.windows - 1) * self.overlap
+
+    def check(self, B: int, L: int) -> int:
+        """a batch of B windows of L frames against the geometry (ValueError); -> the long motion's frames F"""
+        if B % self.windows != 0:
+            raise ValueError(f"Stitch: the batch holds whole long motions - {B} rows are no multiple of {self.windows} windows")
+        if self.length is not None and L != self.length:
+            raise ValueError(f"Stitch: the windows have {self.length} frames, the sample has {L}")
+        return self._geometry(L)
+
+    def _resolve(self, length: Optional[int], F: Optional[int] = None) -> int:
+        L = self.length if self.length is not None else length
+        if L is None and F is not None:          # a full-length long motion names its window length
+            S, ov = self.windows, self.overlap
+            if (F - ov) % S == 0 and F > ov:
+                L = ov + (F - ov) // S
+        if L is None:
+            raise ValueError("Stitch: the window length is not known - pass length= (or frames= to the constructor)")
+        return int(L)
+
+    # ---- the weight row
+    def weights64(self) -> np.ndarray:
+        """[2, ov] float64: wl then wr"""
+        wr = (np.arange(self.overlap, dtype=np.float64) + 1.0) / (self.overlap + 1.0)
+        return np.stack([1.0 - wr, wr], 0)
+
+    def weights(self, device) -> torch.Tensor:
+        """the float32 row [2, ov] on ``device``: `weights64` rounded once"""
+        key = str(torch.device(device))
+        if key not in self._w:
+            self._w[key] = torch.from_numpy(self.weights64()).float().contiguous().to(device)
+        return self._w[key]
+
+    def describe(self, device) -> tuple:
+        """(afm_stitch on ``device``, what must stay alive with it)"""
+        w = self.weights(device)
+        return ffi.Stitch(self.windows, self.overlap, w.data_ptr() if self.overlap > 0 else None), w
+
+    # ---- long form <-> windows (copies; float32 on the GPU: afm_stitch_windows / afm_stitch_join)
+    def windows_of(self, long: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
+        """[G, F, D] -> [G * S, L, D]; frames at or behind F (the padded tail) are zero.  F: the long motion's frames or the full length."""
+        if long.dim() != 3:
+            raise ValueError(f"Stitch.windows_of: the long form is [G, F, D], got {tuple(long.shape)}")
+        G, F, D = long.shape
+        S, ov = self.windows, self.overlap
+        L = self._resolve(length, F)
+        self._geometry(L)
+        lo = (S - 1) * (L - ov) + (ov if S > 1 else 0)
+        if not lo < F <= self.full(L):
+            raise ValueError(f"Stitch.windows_of: {F} frames do not fill {S} windows of {L} sharing {ov}")
+        if long.is_cuda and long.dtype == torch.float32:
+            return ops.stitch_windows(long, S, ov, L)
+        out = long.new_zeros(G, S, L, D)
+        for w in range(S):
+            a = w * (L - ov)
+            n = max(0, min(L, F - a))
+            out[:, w, :n] = long[:, a:a + n]
+        return out.reshape(G * S, L, D)
+
+    def join(self, windows: torch.Tensor) -> torch.Tensor:
+        """[G * S, L, D] -> [G, F, D]; a shared frame is read from the later window (after a stitched chain both hold the same bits)"""
+        if windows.dim() != 3:
+            raise ValueError(f"Stitch.join: the windows are [G * S, L, D], got {tuple(windows.shape)}")
+        B, L, D = windows.shape
+        F = self.check(B, L)
+        S, ov = self.windows, self.overlap
+        if windows.is_cuda and windows.dtype == torch.float32:
+            return ops.stitch_join(windows, S, ov, F)
+        v = windows.reshape(B // S, S, L, D)
+        parts = [v[:, w, :(L - ov if w + 1 < S else F - w * (L - ov))] for w in range(S)]
+        return torch.cat(parts, 1)
+
+    def x_mask(self, G: int, device, length: Optional[int] = None, model=None) -> torch.Tensor:
+        """bool [G * S, L], True = padded frame: the tail of every long motion's last window.  ``model``: checked for mask_motion."""
+        L = self._resolve(length)
+        F = self._geometry(L)
+        pad = self.full(L) - F
+        if pad > 0 and model is not None and not getattr(getattr(model, "model", model), "mask_motion", True):
+            raise ValueError("Stitch: a long motion shorter than its windows pads the last window, which needs a model with mask_motion=True")
+        m = torch.zeros(G, self.windows, L, dtype=torch.bool)
+        if pad > 0:
+            m[:, -1, L - pad:] = True
+        return m.reshape(G * self.windows, L).to(device)
+
+    def impute(self, known_long: torch.Tensor, mask_long: torch.Tensor, length: Optional[int] = None) -> Impute:
+        """the `Impute` over the windows of a long-form known [G, F, D] / mask (broadcastable to it): consistent in the overlaps by
+        construction (padded frames know nothing)"""
+        imp = Impute(known_long, mask_long)          # (the long form checked and expanded like any other)
+        return Impute._of(self.windows_of(imp.known, length), self.windows_of(imp.mask, length))
+
+    def x_T(self, B: int, L: int, D: int, device, seed: int, sample_index0: int = 0) -> torch.Tensor:
+        """x_T of a stitched chain: the windows of ONE Philox draw [G, S*L - (S-1)*ov, D] keyed (seed, sample_index0 + g) - shared frames
+        start from shared noise, and a long motion's noise does not depend on the batch around it"""
+        self.check(B, L)
+        return self.windows_of(ops.randn((B // self.windows, self.full(L), D), device, seed=seed, sample_index0=sample_index0, step=-1), L)
+
+
+class CondFnError(ValueError, NotImplementedError):
+    """A ``cond_fn`` that does not implement the protocol ``cond_fn(x, t, **model_kwargs) -> float32 tensor of x's shape on x's device``: it
+    cannot be called that way, or what it returns does not fit.  It is a ValueError, which is what such a callable deserves.  The second
+    base, NotImplementedError, and the `inspect.signature(...).bind` check in `_cond_grad` exist for one reason: before ``cond_fn`` was
+    opened every sampler refused it with NotImplementedError, and tests/test_gpu_dpm.py::test_refusals still expects that from
+    ``dpm_solver_sample(_loop)`` for ``lambda *a: None`` and ``lambda *a, **k: None``.  When that test is brought up to date, drop the
+    second base and the bind check."""
+
+
+# ---------------------------------------------------------------------- scales: one float or one value per sample
+def scale_value(scale, who: str, got: str = ""):
+    """a guidance scale as its owner keeps it: a float, or a private float32 [B] copy of a floating tensor (``who`` leads the message)"""
+    if isinstance(scale, torch.Tensor):
+        if scale.dim() > 1 or not scale.is_floating_point():
+            raise ValueError(f"{who}: `scale` must be a float or a floating [B] tensor, got {got}{tuple(scale.shape)} {scale.dtype}")
+        return scale.detach().clone().float().reshape(-1)
+    return float(scale)
+
+
+def scale_fits(scale, B: int, who: str, name: str = "`scale`") -> None:
+    if isinstance(scale, torch.Tensor) and scale.numel() != B:
+        raise ValueError(f"{who}: {name} holds {scale.numel()} values for a batch of {B}")
+
+
+def scale_row(scale, B: int, device, who: str, name: str = "`scale`") -> torch.Tensor:
+    """the float32 [B] row of a `scale_value` on ``device``"""
+    scale_fits(scale, B, who, name)
+    return scale.to(device).contiguous() if isinstance(scale, torch.Tensor) else torch.full((B,), scale, dtype=torch.float32, device=device)
+
+
+def _guide_mask(x: torch.Tensor, model_kwargs, who: str):
+    """x_mask of ``model_kwargs`` as the guidance kernels take it: uint8 [B, L] on x's device, or None"""
+    fm = model_kwargs.get("x_mask")
+    if fm is None:
+        return None
+    fm = fm.to(device=x.device).reshape(x.shape[0], -1)
+    if fm.shape[1] != x.shape[1]:
+        raise ValueError(f"{who}: x_mask covers {fm.shape[1]} frames, the sample has {x.shape[1]}")
+    return (fm.view(torch.uint8) if fm.dtype == torch.bool else fm.to(torch.uint8)).contiguous()
+
+
+class _JointTerm:
+    """What `ContactGuidance` and `JointTargets` share: K joints named as column triples of absolute positions or (``.h3d``) as joints of
+    HumanML3D features placed by ``to_scene``, the mean / std that de-normalise the motion, a scale per sample, ``t_start`` - and, per
+    call, the pieces of the C description both fill the same way."""
+    _NOUN = "guided"            # "1 to 16 <noun> joints" (_NAME: the class's name in its messages)
+    _H3D_NAME = True            # an h3d object's messages say "<name>.h3d" behind the constructor's own checks too
+
+    def _init(self, cols, joints, to_scene, mean: torch.Tensor, std: torch.Tensor, scale, t_start: Optional[int], **own) -> None:
+        who = self._NAME + ("" if joints is None else ".h3d")
+        if joints is None:
+            cols = [int(c) for c in cols]
+            if not 1 <= len(cols) <= ffi.GUIDE_MAX_JOINTS:
+                raise ValueError(f"{who}: 1 to {ffi.GUIDE_MAX_JOINTS} {self._NOUN} joints, got {len(cols)}")
+        else:
+            joints = ops.h3d_joint_list([int(j) for j in joints], ffi.GUIDE_MAX_JOINTS, who)
+        if mean.dim() != 1 or std.shape != mean.shape:
+            raise ValueError(f"{who}: mean and std must be [D] and alike, got {tuple(mean.shape)} and {tuple(std.shape)}")
+        D = mean.shape[0]
+        for i, c in enumerate(cols if joints is None else []):          # (an h3d layout names joints: there are no columns to check)
+            if c < 0 or c + 3 > D:
+                raise ValueError(f"{who}: the column triple {c}..{c + 2} leaves the motion vector of {D} columns")
+            if any(abs(c - o) < 3 for o in cols[:i]):
+                raise ValueError(f"{who}: the column triple at {c} overlaps another one")
+        if joints is not None:
+            if D < ffi.H3D_COLS:
+                raise ValueError(f"{who}: the joint recovery reads columns 0..{ffi.H3D_COLS - 1}, the motion vector has {D}")
+            to_scene = ops.h3d_to_scene(to_scene, who)
+            cols, who = [], who if self._H3D_NAME else self._NAME
+        self.cols, self.joints, self.to_scene, self.D, self._who = cols, joints, to_scene, D, who
+        self.mean, self.std = ffi.f32c(mean.detach()), ffi.f32c(std.detach())
+        self._host = (self.mean, self.std) + tuple(self._own(**own))          # what `_on` copies to a device, once
+        self.scale = scale_value(scale, who)
+        self.t_start = None if t_start is None else int(t_start)
+        self._dev: Dict[str, tuple] = {}
+
+    @property
+    def K(self) -> int:
+        return len(self.cols if self.joints is None else self.joints)
+
+    def _check_sample(self, x: torch.Tensor) -> None:
+        if x.dim() != 3 or x.shape[-1] != self.D:
+            raise ValueError(f"{self._who}: mean / std describe {self.D} columns, the sample is {tuple(x.shape)}")
+
+    def _to_scene_on(self, B: int, device) -> tuple:
+        return (None, 0) if self.joints is None else ops.h3d_to_scene_on(self.to_scene, B, device, self._NAME + ".h3d")
+
+    def _on(self, device) -> tuple:
+        """the term's own tensors (mean, std, ...) on ``device``, copied once per device"""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(t.to(device) for t in self._host)
+        return self._dev[key]
+
+    def _fill(self, g, mean, std, scale, ts, stride, diffusion):
+        """the fields every term's description has (``diffusion`` given: first_guided of a chain on it); -> its afm_h3d_layout or None"""
+        g.first_guided = 0 if diffusion is None else self.first_guided(diffusion)
+        g.mean, g.std, g.scale, g.K = mean.data_ptr(), std.data_ptr(), scale.data_ptr(), self.K
+        g.cols[:len(self.cols)] = self.cols
+        g.t_start = 2**62 if self.t_start is None else self.t_start
+        if self.joints is None:
+            return None
+        lay = ffi.H3dLayout()
+        lay.joints[:self.K], lay.to_scene, lay.to_scene_stride = self.joints, ffi.ptr(ts), stride
+        g.h3d = C.pointer(lay)
+        return lay
+
+    def first_guided(self, diffusion) -> int:
+        """the first executed step of a chain on ``diffusion`` that carries this term: the count of its timesteps >= t_start"""
+        return 0 if self.t_start is None else sum(1 for t in diffusion.timestep_map if t >= self.t_start)
+
+
+class ContactGuidance(_JointTerm):
+    """A ``cond_fn`` that pulls the contact joints of a generated motion towards the points its contact map marks - the analytic gradient
+    of an energy between the map the motion implies and the map it was given (afm_contact_guidance, HIP; no second network, no autograd).
+
+    ``cols``: K ints (K <= 16), each the column of the x coordinate of one contact joint in the motion vector, y and z the next two
+    columns.  The columns must hold ABSOLUTE joint positions (``data_repr`` "pos" / "pos_rot": ``3 * j`` for joint j).  "h3d" has no such
+    columns - it integrates root velocities over the frames: ``ContactGuidance.h3d(joints, mean, std)`` builds the guidance for it, the
+    same energy on the joints the features imply (below).  The triples lie inside D and do not overlap.
+    ``mean`` / ``std`` [D] de-normalise the motion.  ``sigma``: the contact map's.  ``scale``: a float or a [B] tensor.  ``t_start``: only
+    steps whose model timestep is < t_start are guided (None: all).
+
+    With q = c_pc_xyz [B, N, 3], c = c_pc_contact [B, N, K] (un-normalised exp(-d^2 / 2 sigma^2), as the motion model receives it) and
+    x_mask [B, L] (True = padded frame) taken from ``model_kwargs``:
+
+        p[b,f,k,:] = x[b,f,cols[k]:cols[k]+3] * std + mean
+        d2[b,n,k]  = min over frames f with not x_mask[b,f] of |p[b,f,k,:] - q[b,n,:]|^2,   f* the FIRST frame that attains it
+        chat       = exp(-d2 / (2 sigma^2))          (no valid frame: 0)
+        E[b]       = 1/(N K) sum_{n,k} (chat - c)^2
+        dE/dx[b,f,cols[k]+a] = sum_{n: f*(b,n,k) = f} (2/(N K)) (chat - c) chat (-(p_a - q_a) / sigma^2) std_a
+
+    ``guide(x, t, **model_kwargs)`` returns -scale[b] * dE/dx [B, L, D] float32 (zero outside the named columns, in padded frames, in a
+    sample without a valid frame or with t >= t_start); ``guide.energy(x, **model_kwargs)`` returns E [B] (a score for picking the best
+    of several samples).  float32 order of the kernel: d2 = (dx*dx + dy*dy) + dz*dz; w = (chat - c) * chat; S_a = sum of w * (p_a - q_a)
+    over the frame's points (lane l of a wave takes n = l, l + 64, ..., then a fixed butterfly); result = ((scale * coef) * std_a) * S_a
+    with coef = 2 / (N K sigma^2) rounded once from float64.  No atomics: bit-identical run to run, and a sample's result does not depend
+    on the batch around it.
+
+    Handed as ``cond_fn`` to p_sample_loop / ddim_sample_loop / dpm_solver_sample_loop of a denoiser whose ``afm_native_loop`` names
+    ``contact_guide`` (GuidedCMDM) or takes it in its private ``_guidance`` bundle (CMDM `trans_enc`, whose public keywords stay the
+    CDM's) - afm_cmdm_guide_loop_range - the whole chain stays in the native loop; any other
+    denoiser samples step by step through ``__call__``.  A skipped step natively launches no gradient kernel; step by step it adds a
+    gradient of zeros (the same values).
+
+    HumanML3D features: ``ContactGuidance.h3d(joints, mean, std, to_scene=None, ...)`` with ``joints`` the K joint indices 0..21.  With
+    u = x * std + mean (columns 0..66 are read) and the velocity columns 0..2 of a padded frame counted as zero, p is the reference's
+    recover_from_ric placed in the scene:
+
+        th_f = sum_{g<f} u[g,0];  c_f, s_f = cos, sin(2 th_f);  X_f = sum_{1<=h<=f} (u[h-1,1] c_h - u[h-1,2] s_h),  Z_f likewise with
+        (u[h-1,1] s_h + u[h-1,2] c_h);  joint 0: P = (X_f, u[f,3], Z_f);  joint j, l = u[f, 4+3(j-1):7+3(j-1)]:
+        P = (l_x c_f - l_z s_f + X_f, l_y, l_x s_f + l_z c_f + Z_f);  p = A P + t,  to_scene = [A|t]
+
+    ``to_scene`` is a float32 [3, 4] or [B, 3, 4] tensor (None: identity).  The reference does not fix how an h3d motion is placed in
+    its scene, so the transform is an argument and not a constant; y-up to z-up is A = [[1, 0, 0], [0, 0, -1], [0, 1, 0]], t = 0.  The
+    energy is the one above on these p; the gradient is its exact adjoint through the recovery (afm_contact_guidance with an
+    afm_h3d_layout: four launches - recovery, the two passes, adjoint - every scan over the frames one lane's serial chain in frame order,
+    no atomics), nonzero only in columns 0..66 of valid frames.  Everything else - ``__call__``, ``energy``, ``first_guided``, the
+    native loops of GuidedCMDM and the plain CMDM, ``two_stage_sample(contact_guidance=...)`` - works as for the column form."""
+    _NAME, _NOUN, _H3D_NAME = "ContactGuidance", "contact", False
+
+    def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, sigma: float = 0.8, scale=1.0, t_start: Optional[int] = None):
+        self._init(cols, None, None, mean, std, scale, t_start, sigma=sigma)
+
+    @classmethod
+    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, to_scene: Optional[torch.Tensor] = None, sigma: float = 0.8, scale=1.0,
+            t_start: Optional[int] = None) -> "ContactGuidance":
+        """The guidance of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67): ``joints`` are joint indices 0..21, ``to_scene`` a
+        float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity).  See the class docstring."""
+        self = cls.__new__(cls)
+        self._init(None, joints, to_scene, mean, std, scale, t_start, sigma=sigma)
+        return self
+
+    def _own(self, sigma) -> tuple:
+        if not float(sigma) > 0.0:
+            raise ValueError(f"{self._who}: sigma must be positive, got {sigma!r}")
+        self.sigma = float(sigma)
+        return ()
+
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None) -> tuple:
+        """(afm_contact_guide of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).  With
+        ``diffusion``: first_guided set for a chain on it (the loops)."""
+        self._check_sample(x)
+        for name in ("c_pc_xyz", "c_pc_contact"):
+            if name not in model_kwargs:
+                raise ValueError(f"ContactGuidance reads {name} from model_kwargs")
+        B, K = x.shape[0], self.K
+        q, c = model_kwargs["c_pc_xyz"], model_kwargs["c_pc_contact"]
+        if q.dim() != 3 or q.shape[0] != B or q.shape[2] != 3 or tuple(c.shape) != (B, q.shape[1], K):
+            raise ValueError(f"ContactGuidance: c_pc_xyz must be [{B}, N, 3] and c_pc_contact [{B}, N, {K}], got {tuple(q.shape)} and {tuple(c.shape)}")
+        scale = scale_row(self.scale, B, x.device, self._who)
+        ts, stride = self._to_scene_on(B, x.device)
+        ffi.require_gpu(x, q, c)
+        q, c = ffi.f32c(q), ffi.f32c(c)
+        mean, std = self._on(x.device)
+        fm = _guide_mask(x, model_kwargs, self._who)
+        g = ffi.ContactGuide()
+        lay = self._fill(g, mean, std, scale, ts, stride, diffusion)
+        g.q, g.c, g.N, g.sigma = q.data_ptr(), c.data_ptr(), q.shape[1], self.sigma
+        return g, fm, (q, c, mean, std, scale, fm, lay, ts)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        g, fm, keep = self.describe(x, model_kwargs)
+        return ops.contact_guidance(g, x, fm, None if self.t_start is None else t.to(x.device))[0]
+
+    def energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        g, fm, keep = self.describe(x, model_kwargs)
+        return ops.contact_guidance(g, x, fm, grad=False, energy=True)[1]
+
+
+class JointTargets(_JointTerm):
+    """A ``cond_fn`` that pulls named joints to given places in the scene at given frames: a root path through the room, a hand on a handle
+    at frame 120, a pose at the last frame (afm_motion_guidance, HIP; no network, no autograd).
+
+    ``cols``: K ints (K <= 16), the column of the x coordinate of each guided joint in a motion vector of ABSOLUTE positions (``data_repr``
+    "pos" / "pos_rot"), as for `ContactGuidance`; ``JointTargets.h3d(joints, mean, std, ...)`` names joints 0..21 of a HumanML3D-feature
+    motion instead (joint 0 is the root) and takes the ``to_scene`` of `ContactGuidance.h3d`.  ``target`` [B, L, K, 3] float32 holds scene
+    coordinates, ``weight`` [B, L, K] their weights: 0 means no target, and the target value there is never read (it may be NaN).
+    ``scale``: a float or a [B] tensor.  ``t_start``: only steps whose model timestep is < t_start are guided (None: all).  ``x_mask`` is
+    read from ``model_kwargs`` as `ContactGuidance` reads it; nothing else is.
+
+    With p[b,f,k,:] the positions `ContactGuidance` computes (x * std rounded, + mean rounded; h3d: the recovery kernel's output):
+
+        E[b] = sum over valid frames f and joints k of  w * ((dx*dx + dy*dy) + dz*dz),   d = p - target
+
+    not normalised - the weights are the caller's.  Order of the sum: the items e = f * K + k of a sample are dealt to the 256 threads of one
+    block, thread i adds e = i, i + 256, ... in that order, then a fixed wave butterfly and ((r0 + r1) + r2) + r3 over the four waves: a
+    function of the sample alone.  ``guide(x, t, **model_kwargs)`` returns -scale[b] * dE/dx:
+
+        columns:  d = target_a - p_a;  m = w * d;  grad[b,f,cols[k]+a] = ((scale[b] * 2) * std_a) * m                       (one launch)
+        h3d:      S[b,f,k,:] = w * (target - p), carried through the adjoint of the recovery with coef = 2 - the kernel and the six
+                  serial scans `ContactGuidance.h3d` uses (three launches: recovery, targets, adjoint)
+
+    exactly zero in every other column, in padded frames, where w == 0 and in samples with t >= t_start.  ``guide.energy(x, **model_kwargs)``
+    returns E [B].  Handed as ``cond_fn`` it stays in the native loops wherever a `ContactGuidance` does (afm_cmdm_motion_guide_loop_range);
+    `MotionGuidance` sums it with a `ContactGuidance`."""
+    _NAME = "JointTargets"
+
+    def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, target: torch.Tensor, weight: torch.Tensor, scale=1.0,
+                 t_start: Optional[int] = None):
+        self._init(cols, None, None, mean, std, scale, t_start, target=target, weight=weight)
+
+    @classmethod
+    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, target: torch.Tensor, weight: torch.Tensor,
+            to_scene: Optional[torch.Tensor] = None, scale=1.0, t_start: Optional[int] = None) -> "JointTargets":
+        """The targets of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67): ``joints`` are joint indices 0..21 (0: the root),
+        ``to_scene`` a float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity).  See the class docstring."""
+        self = cls.__new__(cls)
+        self._init(None, joints, to_scene, mean, std, scale, t_start, target=target, weight=weight)
+        return self
+
+    def _own(self, target, weight) -> tuple:
+        K = self.K
+        if not isinstance(target, torch.Tensor) or not isinstance(weight, torch.Tensor) or target.dim() != 4 or target.shape[2:] != (K, 3) or \
+                tuple(weight.shape) != tuple(target.shape[:3]) or not target.is_floating_point() or not weight.is_floating_point():
+            raise ValueError(f"{self._who}: target must be a floating [B, L, {K}, 3] tensor and weight [B, L, {K}], got "
+                             f"{tuple(getattr(target, 'shape', ()))} and {tuple(getattr(weight, 'shape', ()))}")
+        self.target, self.weight = ffi.f32c(target.detach()), ffi.f32c(weight.detach())
+        return self.target, self.weight
+
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, shared=None) -> tuple:
+        """(afm_joint_targets of this sample tensor, x_mask as uint8 or None, what must stay alive with it).  ``shared``: the (mean, std,
+        to_scene, stride) device tensors of the contact term this one is summed with - a sum names one set of them."""
+        who = self._who
+        self._check_sample(x)
+        B, L, K = x.shape[0], x.shape[1], self.K
+        if tuple(self.target.shape) != (B, L, K, 3):
+            raise ValueError(f"{who}: target is {tuple(self.target.shape)} and weight {tuple(self.weight.shape)}, the sample needs "
+                             f"[{B}, {L}, {K}, 3] and [{B}, {L}, {K}]")
+        scale_fits(self.scale, B, who)
+        fm = _guide_mask(x, model_kwargs, who)
+        ts, stride = self._to_scene_on(B, x.device)          # (checked against the batch before anything touches the device)
+        ffi.require_gpu(x)
+        mean, std, target, weight = self._on(x.device)
+        scale = scale_row(self.scale, B, x.device, who)
+        if shared is not None:
+            mean, std = shared[0], shared[1]
+            if self.joints is not None:
+                ts, stride = shared[2], shared[3]
+        g = ffi.JointTargets()
+        lay = self._fill(g, mean, std, scale, ts, stride, diffusion)
+        g.target, g.weight = target.data_ptr(), weight.data_ptr()
+        return g, fm, (target, weight, mean, std, scale, fm, lay, ts)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        return MotionGuidance(targets=self)(x, t, **model_kwargs)
+
+    def energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        return MotionGuidance(targets=self).energies(x, **model_kwargs)[1]
+
+
+class MotionGuidance:
+    """The sum of a `ContactGuidance` and a `JointTargets` as one ``cond_fn`` (either may be None, not both):
+    grad = grad_contact + grad_targets, each term the float32 result of that guidance alone, joined by one rounded addition per element -
+    ``MotionGuidance(contact, targets)(x, t, **kw)`` equals ``contact(x, t, **kw) + targets(x, t, **kw)`` bit for bit.  Each term keeps its
+    own ``scale`` and ``t_start``: a sample (step by step) or a step (native loops) a term does not guide gets exactly zero from it.  The two
+    terms describe one motion: the same ``mean`` / ``std``, both on columns or both on HumanML3D features, the same ``to_scene`` -
+    ValueError otherwise.  The joint lists may differ; an h3d motion is recovered once per term.  Launches per guided step: the contact
+    term's 2 (h3d: 4) plus the targets' 1 (h3d: 3).  ``energies(x, **kw)`` returns (E_contact or None, E_targets or None)."""
+
+    def __init__(self, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None):
+        if contact is None and targets is None:
+            raise ValueError("MotionGuidance: at least one of contact / targets")
+        if contact is not None and not isinstance(contact, ContactGuidance):
+            raise TypeError(f"MotionGuidance: contact must be a ContactGuidance, not {type(contact).__name__}")
+        if targets is not None and not isinstance(targets, JointTargets):
+            raise TypeError(f"MotionGuidance: targets must be a JointTargets, not {type(targets).__name__}")
+        if contact is not None and targets is not None:
+            if contact.D != targets.D or not torch.equal(contact.mean.cpu(), targets.mean.cpu()) or not torch.equal(contact.std.cpu(), targets.std.cpu()):
+                raise ValueError("MotionGuidance: the two terms de-normalise the motion with different mean / std")
+            if (contact.joints is None) != (targets.joints is None):
+                raise ValueError("MotionGuidance: one term names columns of absolute positions, the other joints of HumanML3D features")
+            a, b = contact.to_scene, targets.to_scene
+            if (a is None) != (b is None) or (a is not None and a is not b and (a.shape != b.shape or a.device != b.device or not torch.equal(a.cpu(), b.cpu()))):          # (compared on the host: no device arithmetic)
+                raise ValueError("MotionGuidance: the two terms place the motion in the scene with different to_scene transforms")
+        self.contact, self.targets = contact, targets
+
+    @property
+    def t_start(self):
+        """None if any term guides every step, else the latest start"""
+        ts = [g.t_start for g in (self.contact, self.targets) if g is not None]
+        return None if any(t is None for t in ts) else max(ts)
+
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion: Optional["GaussianDiffusion"] = None) -> tuple:
+        """(afm_motion_guide of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).  With
+        ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
+        cg = tg = fm = shared = None
+        keep = []
+        if self.contact is not None:
+            cg, fm, ck = self.contact.describe(x, model_kwargs, diffusion)
+            keep.append((cg, ck))
+            shared = (ck[2], ck[3], ck[7], cg.h3d.contents.to_scene_stride if cg.h3d else 0)
+        if self.targets is not None:
+            tg, fm, tk = self.targets.describe(x, model_kwargs, diffusion, shared=shared)
+            keep.append((tg, tk))
+        g = ffi.MotionGuide()
+        if cg is not None:
+            g.contact = C.pointer(cg)
+        if tg is not None:
+            g.targets = C.pointer(tg)
+        return g, fm, keep
+
+    def first_guided(self, diffusion: "GaussianDiffusion") -> int:
+        """the first executed step of a chain on ``diffusion`` that carries any term"""
+        return min(g.first_guided(diffusion) for g in (self.contact, self.targets) if g is not None)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        g, fm, keep = self.describe(x, model_kwargs)
+        timed = any(q is not None and q.t_start is not None for q in (self.contact, self.targets))
+        return ops.motion_guidance(g, x, fm, t.to(x.device) if timed else None)[0]
+
+    def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
+        g, fm, keep = self.describe(x, model_kwargs)
+        return ops.motion_guidance(g, x, fm, grad=False, energy=True)[1:]

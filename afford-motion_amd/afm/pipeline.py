@@ -14,6 +14,8 @@ from typing import Dict, Mapping, Optional
 import torch
 
 from . import dist as adist
+from .cmdm import GuidedCMDM
+from .guidance import MotionGuidance, Stitch
 
 
 def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: torch.Tensor, xyz: torch.Tensor, frames: int,
@@ -77,10 +79,8 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     mn = amdm_noise or {}
     cond_fn = contact_guidance
     if joint_targets is not None:
-        from .diffusion import MotionGuidance
         cond_fn = joint_targets if contact_guidance is None else MotionGuidance(contact_guidance, joint_targets)
     if guidance_scale is not None:
-        from .cmdm import GuidedCMDM
         amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
     motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,
                   denoised_fn=motion_impute, cond_fn=cond_fn, model_kwargs=amdm_kw, step_noise=mn.get("steps"), seed=seed + 1, sample_index0=sample_index0)
@@ -104,7 +104,6 @@ def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: t
     process of each diffusion - both deterministic, which is what keeps shared frames bit-identical in both windows.
     ``guidance_scale``: as `two_stage_sample`'s, a [G * S] tensor giving every window a scale of its own.  ``motion_impute``: an
     afm.diffusion.Impute in the LONG form ([G, frames, D]); it is cut into windows consistently (`Stitch.impute`)."""
-    from .diffusion import Stitch
     if sampler not in ("dpm++", "ddim"):
         raise ValueError(f"long_motion_sample: sampler must be 'dpm++' or 'ddim' (a deterministic update), not {sampler!r}")
     if text_feat.dim() != 3 or xyz.dim() != 3 or xyz.shape[0] != text_feat.shape[0] or xyz.shape[2] != 3:
@@ -133,7 +132,6 @@ def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: t
     amdm_kw = dict(c_text_feat=text, c_pc_xyz=cloud, c_pc_contact=cond, x_mask=x_mask)
     imp = None if motion_impute is None else stitch.impute(motion_impute.known, motion_impute.mask)
     if guidance_scale is not None:
-        from .cmdm import GuidedCMDM
         amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
     windows = loop(amdm_diffusion, amdm, (B, L, amdm.motion_dim), clip_denoised=False, denoised_fn=imp, model_kwargs=amdm_kw, seed=seed + 1,
                    sample_index0=sample_index0, stitch=stitch)

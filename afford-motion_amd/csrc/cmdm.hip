@@ -489,8 +489,8 @@ namespace {
 constexpr int MAX_SUB = 16;           // sub-batches (streams) of one loop call
 constexpr int NEV = 2 * AFM_MAX_LAYERS;      // events of the paired schedule: two cross-stream edges per layer
 
-// the arguments of the eight loop entry points: the model's tensors, the guidance as the caller describes it (at most one of cfg / cfg2;
-// neither: unguided), what every loop takes, the imputation
+// the arguments of the loop entry points (afm_cmdm_sample_loop and the ten *_loop_range entries): the model's tensors, the guidance as
+// the caller describes it (at most one of cfg / cfg2; neither: unguided), what every loop takes, the imputation
 struct LoopCall {
     const afm_cmdm_weights* w;
     float* x;
@@ -507,6 +507,26 @@ struct LoopCall {
     afm_stitch stitch = {};           // stitched loop: the batch is windows of long motions (windows == 0: not stitched)
     bool stitched() const { return stitch.windows > 0; }
 };
+
+// the one maker of a LoopCall, from what the entries' signatures hold in one form or another (`ddim` set: DDPM rows next to it are
+// dropped).  a.dpm, the term and the windows are set on the result by the one function that knows them (every_form_range).
+LoopCall loop_call(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask, const float* step_noise,
+                   const int64_t* tmap, const afm_ddim_rows* ddim, const float* c1, const float* c2, const float* sigma, int n_steps, int first_step,
+                   uint64_t seed, int64_t sample_index0, int B, int L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int n_streams,
+                   void* const* side_streams, void* stream, const afm_cfg_args* cfg = nullptr, const afm_cfg2_args* cfg2 = nullptr,
+                   const float* known = nullptr, const uint8_t* mask = nullptr) {
+    if (ddim) c1 = c2 = sigma = nullptr;
+    return {w, x, cond_tokens, frame_mask, cfg, L, {step_noise, tmap, c1, c2, sigma, ddim, n_steps, first_step, seed, sample_index0, B,
+            sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2};
+}
+
+// exactly one kind of rows - DDIM, 2M (complete) or (`ddpm`) DDPM - else AFM_E_BADARG; 2M rows travel through the DDIM schedule layout
+// as {a, b, c, d = c: any valid row, never used by dpm_update}: written to *as_ddim, which *rows then names
+int one_kind_of_rows(const afm_ddim_rows** rows, const afm_dpm_rows* dpm, bool ddpm, afm_ddim_rows* as_ddim) {
+    if ((*rows != nullptr) + (dpm != nullptr) + (ddpm ? 1 : 0) != 1 || (dpm && (!dpm->a || !dpm->b || !dpm->c))) return AFM_E_BADARG;
+    if (dpm) { *as_ddim = {dpm->a, dpm->b, dpm->c, dpm->c, nullptr}; *rows = as_ddim; }
+    return 0;
+}
 
 // the sample range of sub-batch s of n over a batch of B cut in units of `unit` samples (a stitched loop: the windows of one long motion,
 // so a window and its neighbour share a sub-batch and a stream; 1: single samples): the one rule of the loops and of their sizers
@@ -825,6 +845,26 @@ int sample_loop_impl(const LoopCall& c) {
     return rc;
 }
 
+// the entries that run every form - 2M, guided by a term (`guide`), stitched (`stitch`): the separate-update loop of the form the rows
+// and the guidance name, on a workspace with a history buffer; the 2M form draws no noise and takes no seed
+int every_form_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask, const float* step_noise,
+                     const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm, const float* d_c1, const float* d_c2,
+                     const float* d_sigma, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
+                     const afm_motion_guide* guide, const afm_stitch* stitch, int32_t n_steps, int32_t first_step, uint64_t seed,
+                     int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
+                     void* const* side_streams, void* stream) {
+    if (first_step < 0 || (guide && !guide->contact && !guide->targets) || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
+    afm_ddim_rows as_ddim = {};
+    AFM_TRY(one_kind_of_rows(&rows, dpm, d_c1 || d_c2 || d_sigma, &as_ddim));
+    if ((dpm && step_noise) || (cfg2 && (!frame_mask || !cfg2_ok(cfg2)))) return AFM_E_BADARG;
+    LoopCall c = loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, d_c1, d_c2, d_sigma, n_steps, first_step, dpm ? 0 : seed,
+                           dpm ? 0 : sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg, cfg2, known, mask);
+    c.a.dpm = dpm != nullptr;
+    if (guide) c.guide = *guide;
+    if (stitch) c.stitch = *stitch;
+    return sample_loop_impl(c);
+}
+
 }  // namespace
 
 extern "C" int64_t afm_cmdm_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams) {
@@ -844,8 +884,8 @@ extern "C" int afm_cmdm_sample_loop(const afm_cmdm_weights* w, float* x, const f
                                     const float* d_c2, const float* d_sigma, int32_t n_steps, uint64_t seed,
                                     int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                     int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, 0, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
+    return sample_loop_impl(loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, d_c1, d_c2, d_sigma, n_steps, 0, seed, sample_index0,
+                                      B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream));
 }
 
 extern "C" int afm_cmdm_sample_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -855,8 +895,8 @@ extern "C" int afm_cmdm_sample_loop_range(const afm_cmdm_weights* w, float* x, c
                                           void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                           void* const* side_streams, void* stream) {
     if (first_step < 0) return AFM_E_BADARG;
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
+    return sample_loop_impl(loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, d_c1, d_c2, d_sigma, n_steps, first_step, seed,
+                                      sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream));
 }
 
 extern "C" int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -865,8 +905,8 @@ extern "C" int afm_cmdm_ddim_loop_range(const afm_cmdm_weights* w, float* x, con
                                         int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                         void* const* side_streams, void* stream) {
     if (first_step < 0 || !rows) return AFM_E_BADARG;
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
+    return sample_loop_impl(loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, nullptr, nullptr, nullptr, n_steps, first_step, seed,
+                                      sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream));
 }
 
 extern "C" int afm_cmdm_cfg_sample_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -876,8 +916,8 @@ extern "C" int afm_cmdm_cfg_sample_loop_range(const afm_cmdm_weights* w, float* 
                                               void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                               void* const* side_streams, void* stream) {
     if (first_step < 0 || !cfg) return AFM_E_BADARG;
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, nullptr, n_steps, first_step, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
+    return sample_loop_impl(loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, nullptr, d_c1, d_c2, d_sigma, n_steps, first_step, seed,
+                                      sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg));
 }
 
 extern "C" int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -886,8 +926,8 @@ extern "C" int afm_cmdm_cfg_ddim_loop_range(const afm_cmdm_weights* w, float* x,
                                             int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes,
                                             int32_t n_streams, void* const* side_streams, void* stream) {
     if (first_step < 0 || !rows || !cfg) return AFM_E_BADARG;
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}});
+    return sample_loop_impl(loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, nullptr, nullptr, nullptr, n_steps, first_step, seed,
+                                      sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg));
 }
 
 extern "C" int afm_cmdm_impute_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -897,9 +937,8 @@ extern "C" int afm_cmdm_impute_loop_range(const afm_cmdm_weights* w, float* x, c
                                           uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                           int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
     if (first_step < 0 || !known || !mask) return AFM_E_BADARG;
-    if (rows) d_c1 = d_c2 = d_sigma = nullptr;
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask});
+    return sample_loop_impl(loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, d_c1, d_c2, d_sigma, n_steps, first_step, seed, sample_index0,
+                                      B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, cfg, nullptr, known, mask));
 }
 
 extern "C" int afm_cmdm_cfg2_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens,
@@ -909,9 +948,8 @@ extern "C" int afm_cmdm_cfg2_loop_range(const afm_cmdm_weights* w, float* x, con
                                         uint64_t seed, int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
                                         int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
     if (first_step < 0 || !frame_mask || !known != !mask || !cfg2_ok(cfg)) return AFM_E_BADARG;
-    if (rows) d_c1 = d_c2 = d_sigma = nullptr;
-    return sample_loop_impl({w, x, cond_tokens, frame_mask, nullptr, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, seed, sample_index0, B,
-                             sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg});
+    return sample_loop_impl(loop_call(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, d_c1, d_c2, d_sigma, n_steps, first_step, seed, sample_index0,
+                                      B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, nullptr, cfg, known, mask));
 }
 
 // DPM-Solver++(2M): the eta = 0 DDIM loop's launches (pred_xstart stored, one update launch per sub-batch and step) with the 2M update and
@@ -925,15 +963,10 @@ extern "C" int64_t afm_cmdm_dpm_loop_workspace_bytes(const afm_cmdm_weights* w, 
 extern "C" int afm_cmdm_dpm_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
                                        const int64_t* d_timestep_map, const afm_dpm_rows* rows, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2,
                                        const float* known, const uint8_t* mask, int32_t n_steps, int32_t first_step, int32_t B, int32_t L,
-                                       void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
-                                       void* stream) {
-    if (first_step < 0 || !rows || !rows->a || !rows->b || !rows->c || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
-    if (cfg2 && (!frame_mask || !cfg2_ok(cfg2))) return AFM_E_BADARG;
-    const afm_ddim_rows as_ddim = {rows->a, rows->b, rows->c, rows->c, nullptr};          // (d: any valid row, never used by dpm_update)
-    LoopCall c = {w, x, cond_tokens, frame_mask, cfg, L, {nullptr, d_timestep_map, nullptr, nullptr, nullptr, &as_ddim, n_steps, first_step, 0, 0, B,
-                  sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2};
-    c.a.dpm = true;
-    return sample_loop_impl(c);
+                                       void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
+    if (!rows) return AFM_E_BADARG;
+    return every_form_range(w, x, cond_tokens, frame_mask, nullptr, d_timestep_map, nullptr, rows, nullptr, nullptr, nullptr, cfg, cfg2, known, mask, nullptr,
+                            nullptr, n_steps, first_step, 0, 0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
 }
 
 // The contact-guided loop, every form behind one entry: the separate-update loop of the form the rows and the guidance name, with the two
@@ -946,40 +979,16 @@ extern "C" int64_t afm_cmdm_guide_loop_workspace_bytes(const afm_cmdm_weights* w
     return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, &sum);
 }
 
-namespace {
-
-// both guided entries: the separate-update loop of the form the rows and the guidance name, with the terms' gradient launches in front of
-// a guided step's evaluations and grad / gk in its update launch
-int guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask, const float* step_noise,
-                     const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm, const float* d_c1, const float* d_c2,
-                     const float* d_sigma, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
-                     const afm_motion_guide& guide, int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
-                     void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
-    if (first_step < 0 || (!guide.contact && !guide.targets) || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
-    if ((rows != nullptr) + (dpm != nullptr) + (d_c1 || d_c2 || d_sigma ? 1 : 0) != 1) return AFM_E_BADARG;          // one kind of rows
-    if (dpm && (!dpm->a || !dpm->b || !dpm->c || step_noise)) return AFM_E_BADARG;
-    if (cfg2 && (!frame_mask || !cfg2_ok(cfg2))) return AFM_E_BADARG;
-    afm_ddim_rows as_ddim = {};
-    if (dpm) { as_ddim = {dpm->a, dpm->b, dpm->c, dpm->c, nullptr}; rows = &as_ddim; }          // (d: any valid row, never used by dpm_update)
-    LoopCall c = {w, x, cond_tokens, frame_mask, cfg, L, {step_noise, d_timestep_map, d_c1, d_c2, d_sigma, rows, n_steps, first_step, dpm ? 0 : seed,
-                  dpm ? 0 : sample_index0, B, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2, guide};
-    c.a.dpm = dpm != nullptr;
-    return sample_loop_impl(c);
-}
-
-}  // namespace
-
 extern "C" int afm_cmdm_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
                                          const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
                                          const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
                                          const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_contact_guide* guide,
                                          int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
-                                         void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
-                                         void* stream) {
+                                         void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
     if (!guide) return AFM_E_BADARG;
-    return guide_loop_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask,
-                            afm_motion_guide{guide, nullptr, guide->gk, guide->frame_mask}, n_steps, first_step, seed, sample_index0, B, L, sched_scratch,
-                            workspace, workspace_bytes, n_streams, side_streams, stream);
+    const afm_motion_guide sum = {guide, nullptr, guide->gk, guide->frame_mask};
+    return every_form_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask, &sum, nullptr,
+                            n_steps, first_step, seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
 }
 
 // The same loop with the sum of the contact and the joint-target guidance as its description (afm_motion_guide): the terms a step has
@@ -998,7 +1007,7 @@ extern "C" int afm_cmdm_motion_guide_loop_range(const afm_cmdm_weights* w, float
                                                 int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
                                                 void* const* side_streams, void* stream) {
     if (!guide) return AFM_E_BADARG;
-    return guide_loop_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask, *guide,
+    return every_form_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask, guide, nullptr,
                             n_steps, first_step, seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
 }
 
@@ -1017,21 +1026,12 @@ extern "C" int afm_cmdm_stitch_loop_range(const afm_cmdm_weights* w, float* x, c
                                           const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
                                           const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_stitch* stitch,
                                           int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
-                                          void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
-                                          void* stream) {
+                                          void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
     (void)seed; (void)sample_index0;          // (no noise is drawn)
     if (first_step < 0 || !stitch || stitch->windows < 1 || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
     if (d_c1 || d_c2 || d_sigma || step_noise) return AFM_E_BADARG;          // DDPM rows, explicit step noise: the noise of shared frames would have to be shared
-    if ((rows != nullptr) + (dpm != nullptr) != 1) return AFM_E_BADARG;          // one kind of rows
     if (rows && rows->sigma) return AFM_E_BADARG;          // a noise term (eta != 0)
-    if (dpm && (!dpm->a || !dpm->b || !dpm->c)) return AFM_E_BADARG;
     if (B < 0 || B % stitch->windows != 0 || stitch->overlap < 0 || 2 * (int64_t)stitch->overlap > L) return AFM_E_BADARG;
-    if (cfg2 && (!frame_mask || !cfg2_ok(cfg2))) return AFM_E_BADARG;
-    afm_ddim_rows as_ddim = {};
-    if (dpm) { as_ddim = {dpm->a, dpm->b, dpm->c, dpm->c, nullptr}; rows = &as_ddim; }          // (d: any valid row, never used by dpm_update)
-    LoopCall c = {w, x, cond_tokens, frame_mask, cfg, L, {nullptr, d_timestep_map, nullptr, nullptr, nullptr, rows, n_steps, first_step, 0, 0, B,
-                  sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream}, known, mask, cfg2};
-    c.a.dpm = dpm != nullptr;
-    c.stitch = *stitch;
-    return sample_loop_impl(c);
+    return every_form_range(w, x, cond_tokens, frame_mask, nullptr, d_timestep_map, rows, dpm, nullptr, nullptr, nullptr, cfg, cfg2, known, mask, nullptr, stitch,
+                            n_steps, first_step, 0, 0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
 }
