@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from . import autograd as AG
 from . import autograd_points as AP
-from . import ffi, ops
+from . import ffi, fold, ops
 from .base import Model
 from ._cache import HeldKey
 from .cmdm import TimestepEmbedder, _FlatParamsMixin, _param_version
@@ -164,9 +164,25 @@ class ContactPointTrans(nn.Module):
         h = ops.linear(y, l.linear1.weight, l.linear1.bias, act=ffi.ACT_RELU)
         return ops.layernorm(ops.linear(h, l.linear2.weight, l.linear2.bias, residual=y), l.norm2.weight, l.norm2.bias, l.norm2.eps).view(B, G, d)
 
-    def run(self, x, point_feat, language_feat, time_embedding, xyz):
-        """x [B,N,J], point_feat [B,N,F] | None, language_feat [B,Ft], time_embedding [B,Te], xyz [B,N,3] -> [B,N,64]."""
+    # ---- training (cdm.py:190-410 under autograd): the same graph from differentiable HIP operators, BatchNorm per `self.training`
+    @staticmethod
+    def _ctx_train(seq: nn.Sequential, x, context, batch: int):
+        n = x.shape[0] // batch
+        cat = torch.cat((x, AP.broadcast_rows(context, n)), 1)
+        h = AP.batch_norm(AG.linear(cat, seq[0].weight, seq[0].bias), seq[1], relu=True)
+        return AG.linear(h, seq[3].weight, seq[3].bias)
+
+    def _encoder_layer_relu_train(self, x, drop_seed: int):
+        l = self.self_attn_layers.layers[0]
+        p = float(l.dropout.p) if self.training else 0.0
+        return AG.encoder_layer(x, l, None, l.self_attn.num_heads, (p, drop_seed, 0), act=ffi.ACT_RELU)
+
+    def _traverse(self, train: bool, x, point_feat, language_feat, time_embedding, xyz, drop_seed: int = 0):
+        """The U-Net, once for both modes: `train` picks the `*_train` method of every level (and of the context MLPs and the V2
+        bottleneck layer) in place of the fused eval-mode one; the neighbour search is index work without a gradient in either."""
         from . import pointops
+        sfx = "_train" if train else ""
+        ctx = self._ctx_train if train else self._ctx
         B, N, _ = x.shape
         if point_feat is not None:
             x = torch.cat([x, point_feat], dim=-1)
@@ -176,67 +192,33 @@ class ContactPointTrans(nn.Module):
         ps, xs, knns = [], [], []
         for lvl in range(4):
             enc = getattr(self, f"enc{lvl + 1}")
-            p0, x0 = enc[0].run(p0, x0, B)
-            n = p0.shape[0] // B
-            ki, _ = pointops.knn(self.nsamples[lvl], p0, p0, B, n, n)
-            for blk in list(enc)[1:]:
-                x0 = blk.run(p0, x0, ki)
-            ps.append(p0); xs.append(x0); knns.append(ki)
-        if self.v2:
-            x4 = self._encoder_layer_relu(xs[3].view(B, -1, xs[3].shape[-1])).reshape(xs[3].shape)
-            x4 = self._ctx(self.ctx4, x4, context, B)
-        else:
-            x4 = self._ctx(self.ctx, xs[3], context, B)
-        y = self.dec4[1].run(ps[3], self.dec4[0].run_head(x4, B), knns[3])
-        for lvl in (2, 1, 0):
-            dec = getattr(self, f"dec{lvl + 1}")
-            xl = xs[lvl]
-            if self.v2 and lvl in (2, 1):
-                xl = self._ctx(self.ctx3 if lvl == 2 else self.ctx2, xl, context, B)
-            y = dec[1].run(ps[lvl], dec[0].run_fuse(ps[lvl], xl, ps[lvl + 1], y, B), knns[lvl])
-        return y.view(B, N, -1)
-
-    # ---- training (cdm.py:190-410 under autograd): the same graph from differentiable HIP operators, BatchNorm per `self.training`
-    @staticmethod
-    def _ctx_train(seq: nn.Sequential, x, context, batch: int):
-        n = x.shape[0] // batch
-        cat = torch.cat((x, AP.broadcast_rows(context, n)), 1)
-        h = AP.batch_norm(AG.linear(cat, seq[0].weight, seq[0].bias), seq[1], relu=True)
-        return AG.linear(h, seq[3].weight, seq[3].bias)
-
-    def run_train(self, x, point_feat, language_feat, time_embedding, xyz, drop_seed: int = 0):
-        from . import pointops
-        B, N, _ = x.shape
-        if point_feat is not None:
-            x = torch.cat([x, point_feat], dim=-1)
-        context = torch.cat([language_feat, time_embedding], dim=-1)
-        p0 = ffi.f32c(xyz).reshape(B * N, 3)
-        x0 = torch.cat((p0, ffi.f32c(x).reshape(B * N, -1)), 1)
-        ps, xs, knns = [], [], []
-        for lvl in range(4):
-            enc = getattr(self, f"enc{lvl + 1}")
-            p0, x0 = enc[0].run_train(p0, x0, B)
+            p0, x0 = getattr(enc[0], "run" + sfx)(p0, x0, B)
             n = p0.shape[0] // B
             with torch.no_grad():
                 ki, _ = pointops.knn(self.nsamples[lvl], p0, p0, B, n, n)
             for blk in list(enc)[1:]:
-                x0 = blk.run_train(p0, x0, ki)
+                x0 = getattr(blk, "run" + sfx)(p0, x0, ki)
             ps.append(p0); xs.append(x0); knns.append(ki)
+        x4 = xs[3]
         if self.v2:
-            l = self.self_attn_layers.layers[0]
-            p = float(l.dropout.p) if self.training else 0.0
-            x4 = AG.encoder_layer(xs[3].view(B, -1, xs[3].shape[-1]), l, None, l.self_attn.num_heads, (p, drop_seed, 0), act=ffi.ACT_RELU)
-            x4 = self._ctx_train(self.ctx4, x4.reshape(xs[3].shape), context, B)
-        else:
-            x4 = self._ctx_train(self.ctx, xs[3], context, B)
-        y = self.dec4[1].run_train(ps[3], self.dec4[0].run_head_train(x4, B), knns[3])
+            tokens = x4.view(B, -1, x4.shape[-1])
+            x4 = (self._encoder_layer_relu_train(tokens, drop_seed) if train else self._encoder_layer_relu(tokens)).reshape(x4.shape)
+        x4 = ctx(self.ctx4 if self.v2 else self.ctx, x4, context, B)
+        y = getattr(self.dec4[1], "run" + sfx)(ps[3], getattr(self.dec4[0], "run_head" + sfx)(x4, B), knns[3])
         for lvl in (2, 1, 0):
             dec = getattr(self, f"dec{lvl + 1}")
             xl = xs[lvl]
             if self.v2 and lvl in (2, 1):
-                xl = self._ctx_train(self.ctx3 if lvl == 2 else self.ctx2, xl, context, B)
-            y = dec[1].run_train(ps[lvl], dec[0].run_fuse_train(ps[lvl], xl, ps[lvl + 1], y, B), knns[lvl])
+                xl = ctx(self.ctx3 if lvl == 2 else self.ctx2, xl, context, B)
+            y = getattr(dec[1], "run" + sfx)(ps[lvl], getattr(dec[0], "run_fuse" + sfx)(ps[lvl], xl, ps[lvl + 1], y, B), knns[lvl])
         return y.view(B, N, -1)
+
+    def run(self, x, point_feat, language_feat, time_embedding, xyz):
+        """x [B,N,J], point_feat [B,N,F] | None, language_feat [B,Ft], time_embedding [B,Te], xyz [B,N,3] -> [B,N,64]."""
+        return self._traverse(False, x, point_feat, language_feat, time_embedding, xyz)
+
+    def run_train(self, x, point_feat, language_feat, time_embedding, xyz, drop_seed: int = 0):
+        return self._traverse(True, x, point_feat, language_feat, time_embedding, xyz, drop_seed)
 
 
 class ContactPerceiver(nn.Module):
@@ -396,94 +378,20 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         q0, u, cu = self._latent_tokens(w, 1, table)
         keep += [table, q0, u, cu]
         w.time_q0, w.time_u, w.time_cu = q0.data_ptr(), u.data_ptr(), cu.data_ptr()
-        if not self.training and not self.no_fold and self.contact_dim <= 8 and cm.feat_dim > self.contact_dim and cm.dkv % 64 == 0:
-            # eval: weight products of the folded sampling form (afm_cdm_weights.fold_*; float64 products, rounded once).  Only the
-            # contact columns of the encoder input change between steps, and encoder_adapter -> decoder_adapter as well as
-            # linear2 (+ residual) -> contact_layer are linear chains (cdm.py:176-186,509-510).
-            cd = self.contact_dim
-            f64 = lambda t: t.detach().double().cpu()        # a few 256 x 256 products: on the host, exactly reproducible
-            we, wd = f64(cm.encoder_adapter.weight), f64(cm.decoder_adapter.weight)
-            fc2, cl = cm.decoder_cross_attn[1].module[3], self.contact_layer
-            wc = f64(cl.weight)
-            xu = we[:, :cd].t().contiguous()                                       # [cd, dkv]
-            xv = (wd @ we[:, :cd]).t().contiguous()                                # [cd, dkv]
-            bo = f64(cm.decoder_cross_attn[0].module.attention.o_proj.bias)
-            folds = dict(fold_xu=xu, fold_xv=xv, fold_w2=wc @ f64(fc2.weight), fold_q=wc @ xv.t(),
-                         fold_c0=wc @ (f64(fc2.bias) + bo) + f64(cl.bias))
-            if cm.feat_dim + 1 <= 44:
-                K = 12 if cm.feat_dim + 1 <= 12 else 44                           # inputs of the row-less kernels, padded (RowLess<3> / RowLess<11> in perceiver.hip)
-                # generator tables (afm_cdm_weights.gen_*): both adapters as maps of the K = feat_dim + 1 inputs [x_t | features | 1]
-                F_, be, bd = cm.feat_dim, f64(cm.encoder_adapter.bias), f64(cm.decoder_adapter.bias)
-                gen_enc = torch.zeros(K, cm.dkv, dtype=torch.float64)
-                gen_enc[:F_] = we.t(); gen_enc[F_] = be
-                gen_dec = torch.zeros(K, cm.dkv, dtype=torch.float64)
-                gen_dec[:F_] = (wd @ we).t(); gen_dec[F_] = wd @ be + bd
-                folds.update(gen_qe=wc @ gen_dec.t())
-                # the decoder of a point in one kernel (afm_cdm_weights.dec_*): everything between the attention weights and linear1 is linear
-                # in [a | inputs]; rows of the inputs (step-invariant) here, rows of the attention weights per step on the device
-                mlp_m = cm.decoder_cross_attn[1].module
-                g2, b2, w1, b1 = f64(mlp_m[0].weight), f64(mlp_m[0].bias), f64(mlp_m[1].weight), f64(mlp_m[1].bias)
-                tx = gen_dec.clone()
-                tx[F_] += bo                                                       # the attention's output bias rides on the constant input
-                xc = tx - tx.mean(1, keepdim=True)
-                w1g = w1 * g2[None, :]
-                dc = gen_dec - gen_dec.mean(1, keepdim=True)                       # the query row's LayerNorm: var = x Qd x^T, in MFMA operand order
-                def operand_order(q):                                              # [K, K] -> [K, 16 NT]: entry (k, 16 t + i) = q[4 (4 t + (i & 3)) + (i >> 2)][k]
-                    nt = (K + 15) // 16
-                    o = torch.zeros(K, 16 * nt, dtype=torch.float64)
-                    for c in range(16 * nt):
-                        t, i = divmod(c, 16)
-                        src = 4 * (4 * t + (i & 3)) + (i >> 2)
-                        if src < K:
-                            o[:, c] = q[src, :]
-                    return o
-                qdd = operand_order(dc @ dc.t() / cm.dkv)
-                ec = gen_enc - gen_enc.mean(1, keepdim=True)                       # the encoder side: rows the latents attend over
-                folds.update(enc_ec=ec, enc_qee=operand_order(ec @ ec.t() / cm.dkv))
-                # head of the latent chain: x1 = q0 + o_proj(v_proj(LayerNorm_kv-weighted sums)) is linear in the 8 x K numbers enc_point_kernel accumulates
-                ea = cm.encoder_cross_attn[0].module
-                gk, bk = f64(ea.kv_norm.weight), f64(ea.kv_norm.bias)
-                wv, bv, wo, bo_e = f64(ea.attention.v_proj.weight), f64(ea.attention.v_proj.bias), f64(ea.attention.o_proj.weight), f64(ea.attention.o_proj.bias)
-                hd = cm.dq // 8                                                    # the kernel is written for the reference's 8 encoder heads
-                wve = (ec * gk[None, :]) @ wv.t()                                  # [K, dq]: v_proj of gamma * Ec[k]
-                wove = torch.zeros(8 * K, cm.dq, dtype=torch.float64)
-                for h in range(8):
-                    blk = slice(h * hd, (h + 1) * hd)
-                    wove[K * h:K * h + K] = wve[:, blk] @ wo[:, blk].t()
-                folds.update(enc_wove=wove, enc_c1=bo_e + wo @ (wv @ bk + bv))
-                # tail of the chain: the fused decoder's per-sample tables are linear / bilinear in the latents' decoder keys and values
-                da_m = cm.decoder_cross_attn[0].module
-                gq, bq_n = f64(da_m.q_norm.weight), f64(da_m.q_norm.bias)
-                wq_d, bq_d, wo_d = f64(da_m.attention.q_proj.weight), f64(da_m.attention.q_proj.bias), f64(da_m.attention.o_proj.weight)
-                woc = wo_d - wo_d.mean(0, keepdim=True)
-                wco = torch.zeros(8, cm.dkv, dtype=torch.float64)
-                wco[:cd] = wc @ wo_d
-                folds.update(dec_dwq=(dc * gq[None, :]) @ wq_d.t(), dec_wqb=wq_d @ bq_n + bq_d, dec_wco=wco, dec_wow=woc.t() @ w1g.t(),
-                             dec_wog=woc.t() @ woc / cm.dkv, dec_xwo=xc @ woc / cm.dkv)
-                folds.update(dec_c=b1 + w1 @ b2, dec_twx=xc @ w1g.t(), dec_qxx=xc @ xc.t() / cm.dkv, dec_qdd=qdd)
-            dev = cl.weight.device
-            for name, t in folds.items():
-                setattr(w, name, P(t.float().contiguous().to(dev)))
-            # LayerNorm folded into the latent-chain stages that follow one (afm_cdm_weights.lat_fold: 19 slots of (W * gamma, row sums, b + W beta))
-            slots = [None] * 19
-
-            def fold_ln(slot, lin_m, ln_m):
-                wl, bl, gl, btl = f64(lin_m.weight), f64(lin_m.bias), f64(ln_m.weight), f64(ln_m.bias)
-                wg = wl * gl[None, :]
-                slots[slot] = (wg, wg.sum(1), bl + wl @ btl)
-            fold_ln(0, cm.encoder_cross_attn[1].module[1], cm.encoder_cross_attn[1].module[0])
-            for li, layer in enumerate(cm.encoder_self_attn):
-                sa_m, mlp_l = layer[0].module, layer[1].module
-                fold_ln(1 + 4 * li, sa_m.attention.q_proj, sa_m.norm); fold_ln(2 + 4 * li, sa_m.attention.k_proj, sa_m.norm)
-                fold_ln(3 + 4 * li, sa_m.attention.v_proj, sa_m.norm); fold_ln(4 + 4 * li, mlp_l[1], mlp_l[0])
-            da_kv = cm.decoder_cross_attn[0].module
-            fold_ln(17, da_kv.attention.k_proj, da_kv.kv_norm); fold_ln(18, da_kv.attention.v_proj, da_kv.kv_norm)
-            table = (C.c_void_p * (3 * 19))()
-            for si, trip in enumerate(slots):
-                for j in range(3):
-                    table[3 * si + j] = P(trip[j].float().contiguous().to(dev)) if trip is not None else None
-            keep.append(table)
-            w.lat_fold = C.cast(table, C.c_void_p)
+        if not self.training and not self.no_fold:
+            # eval: the weight products of the folded and row-less sampling forms (afm.fold: float64 on the host, rounded once here)
+            up = lambda t: P(t.float().contiguous().to(self.contact_layer.weight.device))
+            tables = fold.cdm_tables(cm, self.contact_layer, self.contact_dim)
+            slots = tables.pop("lat_fold", None)
+            for name, t in tables.items():
+                setattr(w, name, up(t))
+            if slots is not None:
+                ptrs = (C.c_void_p * (3 * len(slots)))()
+                for si, trip in enumerate(slots):
+                    for j in range(3):
+                        ptrs[3 * si + j] = up(trip[j]) if trip is not None else None
+                keep.append(ptrs)
+                w.lat_fold = C.cast(ptrs, C.c_void_p)
         self._pack = (ver, w, keep)
         self._text_cache = None
         w.gemm_arith, w.gemm_arith_min_n = ops.gemm_arith()
@@ -558,16 +466,21 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             self._scene_cache = (HeldKey((xyz, col), ver), self.scene_model((xyz.to(like), None if col is None else col.to(like))))
         return self._scene_cache[1]
 
-    def _features(self, x, kwargs) -> torch.Tensor:
-        """cat(x_t, per-point features, xyz) exactly as cdm.py:495-505 + ContactPerceiver.forward :167-171."""
-        parts = [x]
+    def _point_features(self, x, kwargs):
+        """pc_emb of CDM.forward (cdm.py:495-508): frozen scene backbone output, given per-point features, or None."""
         if hasattr(self, "scene_model"):
             # step-invariant: the reference re-runs the frozen backbone in every step (cdm.py:508); cache per scene batch
             xyz, col = kwargs["c_pc_xyz"], kwargs.get("c_pc_feat")
-            parts.append(self._scene_features(xyz, col, x))
-        elif self.point_feat_dim > 0:
+            return self._scene_features(xyz, col, x)
+        if self.point_feat_dim > 0:
             pf = kwargs["c_pc_feat"]
-            parts.append(self._text_similarity(pf, kwargs, x) if (self.point_feat_dim == 1 and pf.shape[-1] != 1) else pf.to(x))
+            return self._text_similarity(pf, kwargs, x) if (self.point_feat_dim == 1 and pf.shape[-1] != 1) else pf.to(x)
+        return None
+
+    def _features(self, x, kwargs) -> torch.Tensor:
+        """cat(x_t, per-point features, xyz) exactly as cdm.py:495-505 + ContactPerceiver.forward :167-171."""
+        pf = self._point_features(x, kwargs)
+        parts = [x] if pf is None else [x, pf]
         if self.contact_model.point_pos_emb:
             parts.append(kwargs["c_pc_xyz"].to(x))
         return torch.cat(parts, dim=-1).contiguous()
@@ -691,16 +604,6 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         return x
 
     # ------------------------------------------------------------------ 'MLP' arch (per-operator composition, inference and training)
-    def _point_features(self, x, kwargs):
-        """pc_emb of CDM.forward (cdm.py:495-508): frozen scene backbone output, given per-point features, or None."""
-        if hasattr(self, "scene_model"):
-            xyz, col = kwargs["c_pc_xyz"], kwargs.get("c_pc_feat")
-            return self._scene_features(xyz, col, x)
-        if self.point_feat_dim > 0:
-            pf = kwargs["c_pc_feat"]
-            return self._text_similarity(pf, kwargs, x) if (self.point_feat_dim == 1 and pf.shape[-1] != 1) else pf.to(x)
-        return None
-
     def forward_mlp(self, x, timesteps, **kwargs):
         """CDM.forward with ContactMLP (cdm.py:41-85,474-513): every op is a (differentiable) HIP operator; runs under
         torch.no_grad() for sampling and with the tape for training."""
@@ -708,10 +611,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         x = ffi.f32c(x)
         B, N, _ = x.shape
         dev = x.device
-        te = self.timestep_embedder
-        t_idx = timesteps.to(device=dev, dtype=torch.int64)
-        time_emb = AG.linear(AG.linear(te.pe[t_idx, 0, :], te.time_embed[0].weight, te.time_embed[0].bias, act=ffi.ACT_SILU),
-                             te.time_embed[2].weight, te.time_embed[2].bias).view(B, 1, -1)
+        time_emb = self.timestep_embedder.run(timesteps.to(device=dev, dtype=torch.int64)).view(B, 1, -1)
         text = ffi.f32c(self.encode_text(kwargs).to(dev)).view(B, 1, -1)
         h = self.contact_model.run(x, self._point_features(x, kwargs), text, time_emb)
         return AG.linear(h, self.contact_layer.weight, self.contact_layer.bias)
@@ -723,10 +623,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             x = ffi.f32c(x)
             dev = x.device
-            te = self.timestep_embedder
-            t_idx = timesteps.to(device=dev, dtype=torch.int64)
-            time_emb = AG.linear(AG.linear(te.pe[t_idx, 0, :], te.time_embed[0].weight, te.time_embed[0].bias, act=ffi.ACT_SILU),
-                                 te.time_embed[2].weight, te.time_embed[2].bias)                                 # [B, te]
+            time_emb = self.timestep_embedder.run(timesteps.to(device=dev, dtype=torch.int64))                  # [B, te]
             text = ffi.f32c(self.encode_text(kwargs).to(dev))
             self._train_calls = getattr(self, "_train_calls", 0) + 1
             h = self.contact_model.run_train(x, self._point_features(x, kwargs), text, time_emb, kwargs["c_pc_xyz"].to(x),
@@ -778,10 +675,7 @@ class CDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         p_dec = float(a.decoder_dropout) if self.training else 0.0
         self._drop_calls = getattr(self, "_drop_calls", 0) + 1
         seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._drop_calls + 0xD1B54A32D192ED03 * _dist_rank()) & (2**64 - 1)   # per call, per rank
-        te = self.timestep_embedder
-        t_idx = timesteps.to(device=dev, dtype=torch.int64)
-        time_emb = AG.linear(AG.linear(te.pe[t_idx, 0, :], te.time_embed[0].weight, te.time_embed[0].bias, act=ffi.ACT_SILU),
-                             te.time_embed[2].weight, te.time_embed[2].bias)                                # [B, te]
+        time_emb = self.timestep_embedder.run(timesteps.to(device=dev, dtype=torch.int64))                 # [B, te]
         text = ffi.f32c(self.encode_text(kwargs).to(dev))
         feat = self._features(x, kwargs)                                                                     # [B, N, feat]
         enc_kv = AG.linear(feat, cm.encoder_adapter.weight, cm.encoder_adapter.bias)                         # [B, N, dkv]

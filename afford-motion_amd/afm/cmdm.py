@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import autograd as AG
-from . import ffi, ops
+from . import ffi, fold, ops
 from ._cache import HeldKey
 from .base import Model
 from .guidance import ContactGuidance, JointTargets, MotionGuidance, scale_row, scale_value
@@ -64,6 +64,11 @@ class TimestepEmbedder(nn.Module):
         """Embedding of every timestep, [max_len, d_model], two HIP GEMMs (SiLU fused in the first)."""
         h = ops.linear(self.pe[:, 0, :], self.time_embed[0].weight, self.time_embed[0].bias, act=ffi.ACT_SILU)
         return ops.linear(h, self.time_embed[2].weight, self.time_embed[2].bias)
+
+    def run(self, t_idx: torch.Tensor) -> torch.Tensor:
+        """Embedding of the timesteps t_idx [B] (int64, on the device) -> [B, d_model] on the differentiable HIP operators."""
+        h = AG.linear(self.pe[t_idx, 0, :], self.time_embed[0].weight, self.time_embed[0].bias, act=ffi.ACT_SILU)
+        return AG.linear(h, self.time_embed[2].weight, self.time_embed[2].bias)
 
     def forward(self, timesteps):
         return self.table()[timesteps].unsqueeze(1)
@@ -327,22 +332,16 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             lw.norm1_w, lw.norm1_b, lw.norm2_w, lw.norm2_b = P(l.norm1.weight), P(l.norm1.bias), P(l.norm2.weight), P(l.norm2.bias)
         if not self.training:
             # eval: LayerNorm folded into the linears it feeds (afm_encoder_layer_weights.lin1_wg ...): W' = W * gamma, g = row sums of W',
-            # c = b + W beta - float64 products rounded once, on the HOST in numpy (as afm/cdm.py builds the CDM's tables; once per weight
+            # c = b + W beta (afm.fold.ln_fold, the CDM's lat_fold as well) - float64 products rounded once, on the HOST (once per weight
             # version: ~12 MB down, the same up - no eager ATen arithmetic and no vendor BLAS call in a sampling job)
-            import numpy as np
-
-            def fold(lin_w, lin_b, norm):
-                wd = lin_w.detach().cpu().numpy().astype(np.float64)
-                gam, bet = norm.weight.detach().cpu().numpy().astype(np.float64), norm.bias.detach().cpu().numpy().astype(np.float64)
-                wg = wd * gam[None, :]
-                up = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.float32))).to(dev)
-                return P(up(wg)), P(up(wg.sum(1))), P(up(lin_b.detach().cpu().numpy().astype(np.float64) + wd @ bet))
+            def ln_fold(lin_w, lin_b, norm):
+                return tuple(P(t.float().contiguous().to(dev)) for t in fold.ln_fold(lin_w, lin_b, norm.weight, norm.bias))
             for i, l in enumerate(layers):
                 lw = w.layer[i]
-                lw.lin1_wg, lw.lin1_g, lw.lin1_c = fold(l.linear1.weight, l.linear1.bias, l.norm1)
+                lw.lin1_wg, lw.lin1_g, lw.lin1_c = ln_fold(l.linear1.weight, l.linear1.bias, l.norm1)
                 if i > 0:
-                    lw.in_proj_wg, lw.in_proj_g, lw.in_proj_c = fold(l.self_attn.in_proj_weight, l.self_attn.in_proj_bias, layers[i - 1].norm2)
-            w.motion_layer_wg, w.motion_layer_g, w.motion_layer_c = fold(self.motion_layer.weight, self.motion_layer.bias, layers[-1].norm2)
+                    lw.in_proj_wg, lw.in_proj_g, lw.in_proj_c = ln_fold(l.self_attn.in_proj_weight, l.self_attn.in_proj_bias, layers[i - 1].norm2)
+            w.motion_layer_wg, w.motion_layer_g, w.motion_layer_c = ln_fold(self.motion_layer.weight, self.motion_layer.bias, layers[-1].norm2)
         self._pack = (ver, w, keep)
         return self._stamp(w)
 
@@ -520,10 +519,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             Bm, n, c = mem.shape
             mems.append(AG.layer_norm(AG.linear(mem.reshape(Bm * n, c), km[0].weight, km[0].bias), km[1]).view(Bm, n, d))
         # tokens [time | text | motion] + positional encoding (+ dropout)
-        te = self.timestep_embedder
-        t_idx = timesteps.to(device=dev, dtype=torch.int64)
-        time_emb = AG.linear(AG.linear(te.pe[t_idx, 0, :], te.time_embed[0].weight, te.time_embed[0].bias, act=ffi.ACT_SILU),
-                             te.time_embed[2].weight, te.time_embed[2].bias).view(B, 1, d)
+        time_emb = self.timestep_embedder.run(timesteps.to(device=dev, dtype=torch.int64)).view(B, 1, d)
         text = self.encode_text(kwargs)
         if "c_text_erase" in kwargs:
             text = text * (1.0 - kwargs["c_text_erase"].to(dev).float().reshape(B, 1))
@@ -566,10 +562,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._drop_calls + 0xD1B54A32D192ED03 * _dist_rank()) & (2**64 - 1)   # per call, per rank
 
         # time token: pe[t] -> Linear -> SiLU -> Linear (modules.py:48-53)
-        te = self.timestep_embedder
-        t_idx = timesteps.to(device=dev, dtype=torch.int64)
-        time_emb = AG.linear(AG.linear(te.pe[t_idx, 0, :], te.time_embed[0].weight, te.time_embed[0].bias, act=ffi.ACT_SILU),
-                             te.time_embed[2].weight, te.time_embed[2].bias).view(B, 1, d)
+        time_emb = self.timestep_embedder.run(timesteps.to(device=dev, dtype=torch.int64)).view(B, 1, d)
         masks = [torch.zeros(B, 1, dtype=torch.bool, device=dev)]
         # text token (cmdm.py:134-146)
         text_feat = self.encode_text(kwargs)

@@ -486,6 +486,43 @@ def test_batched_latent_chain_with_more_than_one_token_block(cdm):
     assert torch.equal(parts, got), "a sample's result must not depend on which batch it is computed in"
 
 
+def test_eval_pack_carries_the_fold_tables_bit_for_bit():
+    """Every table afm.fold.cdm_tables names is in the default eval pack, behind its field's pointer, as the float32 rounding of the host's
+    float64 table (tests/test_cdm_fold_host.py pins those to their identities); a training-mode pack and a no_fold pack carry none."""
+    import ctypes as C
+    from afm import fold
+    m = create_model(cdm_cfg(num_points=64), device=dev())
+    load_named_weights(m)
+    m = m.to(dev()).eval()
+    tables = fold.cdm_tables(m.contact_model, m.contact_layer, m.contact_dim)
+    slots = tables.pop("lat_fold")
+    assert len(tables) == 20 and len(slots) == 19
+    w = m._weights()
+    by_ptr = {t.data_ptr(): t for t in m._pack[2] if isinstance(t, torch.Tensor)}
+
+    def same(ptr, want, what):
+        got = by_ptr[ptr]
+        assert got.dtype == torch.float32 and got.shape == want.shape and torch.equal(got.cpu(), want.float()), what
+    for name, t in tables.items():
+        same(getattr(w, name), t, name)
+    ptrs = C.cast(w.lat_fold, C.POINTER(C.c_void_p))
+    for s, trip in enumerate(slots):
+        for j in range(3):
+            if trip is None:
+                assert not ptrs[3 * s + j], f"lat_fold slot {s} of a layer the model does not have"
+            else:
+                same(ptrs[3 * s + j], trip[j], f"lat_fold[{3 * s + j}]")
+    try:
+        for training, no_fold in ((True, False), (False, True)):
+            m.train(training)
+            m.no_fold = no_fold
+            w = m._weights()
+            assert not any(getattr(w, name) for name in tables) and not w.lat_fold, f"training={training} no_fold={no_fold}: a table is set"
+    finally:
+        m.eval()
+        m.no_fold = False
+
+
 def test_zz_write_parity_table():
     """Not a check: stores the [parity-f32] figures measured so far (gpu_util.write_parity_table -> profiles/r07_parity_f32_class.json)."""
     write_parity_table()
