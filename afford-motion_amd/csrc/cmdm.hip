@@ -646,7 +646,8 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     // six-product arithmetic, 128 x 128 on EVERY GEMM with N >= 512 measured 588-590 against 568-574 steps/s at 16 + 16 samples in the same
     // calls, but 853 against 995 at 8 + 8 and 1168 against 1470 at 4 + 4 (profiles/r06_tile_rule.md) - so: sub-batches of >= 4096 rows only.
     // Round 7: the same 128 x 128 tile on 512 threads (tile code 14: two of the tile's waves per SIMD) - 611-612 against 580 steps/s for code 5
-    // in one call (profiles/r07_gemm128_timeline.md); code 5 stays reachable through the override.
+    // in one call (profiles/r07_gemm128_timeline.md); code 5 stays reachable through the override.  Code 14's epilogue is the streamed one
+    // (csrc/gemm_epilogue.h; 633-638 against 612-618 steps/s for code 15, the same tile with the shared epilogue: profiles/gemm128_epilogue.md).
     // Tile shapes of one arithmetic are bit-identical; a caller's explicit AFM_CMDM_WIDE_TILE code wins.
     const int T = 1 + c.w->n_cond + c.L;
     p->w = *c.w;

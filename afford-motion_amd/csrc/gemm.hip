@@ -474,7 +474,8 @@ extern "C" int afm_linear(const afm_linear_args* args, void* stream) {
         case 3: return launch_dma<2, 2, 1, 1>(a, AFM_PROF_GEMM64_DMA, s);
         case 4: return launch_dma<2, 2, 1, 2>(a, AFM_PROF_GEMM64x128_DMA, s);
         case 5:
-        case 14: return launch_dma<2, 2, 2, 2>(a, AFM_PROF_GEMM128_DMA, s);      // (14: the bf16-split kernels' 128 x 128 tile on 512 threads, which the sampling loop forces on its
+        case 14:
+        case 15: return launch_dma<2, 2, 2, 2>(a, AFM_PROF_GEMM128_DMA, s);      // (14, 15: the bf16-split kernels' 128 x 128 tile on 512 threads, which the sampling loop forces on its
                                                                                   // wide GEMMs; a GEMM that runs natively - f32 arithmetic, unaligned operands - takes the native 128 x 128)
         default: return AFM_E_BADARG;
     }

@@ -315,6 +315,145 @@ __device__ __forceinline__ void gemm_epilogue(const afm_linear_args& p, const fl
     }
 }
 
+// ---- Streamed epilogue of the 512-thread 128 x 128 tile (tile code 14).  gemm_epilogue's 16-byte branches walk the tile in eight trips, and
+// every trip is a memory round trip of its own: residual load -> arithmetic -> store, with the next trip's load queued behind this trip's
+// stores (on gfx9 stores count in vmcnt and retire in order with loads).  That tile program holds two workgroups per CU, so nothing hides
+// the ~1 us per trip (profiles/r07_gemm128_timeline.md: epilogue 6.8 - 8.0 us of a 33 - 37 us tile).  Here the work is split in three:
+// gemm_epilogue_streamed_prefetch runs BEFORE the accumulators are staged in LDS - the K loop's operand registers are dead by then - and
+// requests every global input of the tile: the per-column vectors, which are the same on every trip, and the eight residual float4s.  The
+// addresses are clamped (row to M - 1, column quad to the last valid one), never predicated.  Behind the staging barrier
+// gemm_epilogue_streamed first rewrites the staged tile in place with what needs no memory (folded LayerNorm of A, bias, activation: a
+// rolled loop), then runs the eight trips unrolled, behind ONE vmcnt(0): no load and no wait between the stores, only the stores are
+// predicated.  An output element's arithmetic is gemm_epilogue's, expression for expression, in the same conditional blocks: bit-identical
+// (tests/test_gpu_gemm128_epilogue.py).  profiles/gemm128_epilogue.md: epilogue 6.7 - 8.0 -> 3.7 - 3.8 us with a residual, 5.4 - 5.9 us
+// with GELU (its arithmetic); the two-stream loop +3.4 %.
+// Served: the 16-byte (vec_out) case with a_stat + a_fold_g, bias, act, residual (+ res_stat), rowtab, stat_out and the row maps - what the
+// sampling step puts on its wide GEMMs.  Anything else (scale, preact, dropout, dact, act_post, row-dot, ln_out, the scalar / DDPM branch,
+// unaligned pointers or strides) leaves `on` false and the tile program calls gemm_epilogue.
+template <int TRIPS>
+struct StreamedEpilogue {
+    bool on;                                    // wave-uniform: this launch is served here
+    int64_t orow[TRIPS];                        // output row of trip t (row clamped to M - 1) through the C row map
+    float4 res[TRIPS];                          // residual of trip t
+    float4 bias, fold_g, res_g, res_b;          // the thread's column quad of the per-column vectors
+};
+
+template <int BM, int BN, int NT>
+__device__ __forceinline__ void gemm_epilogue_streamed_prefetch(const afm_linear_args& p, int bm, int bn, int tid, StreamedEpilogue<BM * BN / 4 / NT>& se) {
+    constexpr int TRIPS = BM * BN / 4 / NT, RSTEP = NT / (BN / 4);
+    static_assert(BM * BN / 4 / 512 == 8 && NT == 512 && TRIPS == 8, "streamed epilogue: the 128 x 128 tile on 512 threads, eight trips");
+    static_assert((BN / 4) % 16 == 0 && NT % (BN / 4) == 0, "a thread keeps its column quad; a 64-column group is 16 consecutive lanes");
+    const bool vec_out = ((p.N & 3) == 0) && ((p.ldc & 3) == 0) && ((p.ldr & 3) == 0) && ((p.ldp & 3) == 0) && ((p.ldz & 3) == 0) && !p.ddpm_out &&
+                         ((((uintptr_t)p.C) | ((uintptr_t)p.residual) | ((uintptr_t)p.bias) | ((uintptr_t)p.scale) | ((uintptr_t)p.rowtab) |
+                           ((uintptr_t)p.preact) | ((uintptr_t)p.dact_z)) & 15) == 0;
+    se.on = vec_out && !p.rowdot_w && !p.scale && !p.preact && !(p.drop_p > 0.0f) && !p.dact && !p.act_post && !p.ln_out;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    se.bias = se.fold_g = se.res_g = se.res_b = zero;
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) { se.orow[t] = 0; se.res[t] = zero; }
+    if (!se.on) return;
+    const RowMap cmap{p.c_grp, p.c_stride, p.c_off, p.c_skip_after, p.c_skip};
+    const int row0 = tid / (BN / 4);
+    const int gc = min(bn * BN + (tid % (BN / 4)) * 4, p.N - 4);
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) se.orow[t] = cmap(min(bm * BM + row0 + t * RSTEP, p.M - 1));
+    if (p.a_stat) se.fold_g = *reinterpret_cast<const float4*>(p.a_fold_g + gc);
+    if (p.bias) se.bias = *reinterpret_cast<const float4*>(p.bias + gc);
+    if (p.residual) {
+        if (p.res_stat) { se.res_g = *reinterpret_cast<const float4*>(p.res_gamma + gc); se.res_b = *reinterpret_cast<const float4*>(p.res_beta + gc); }
+#pragma unroll
+        for (int t = 0; t < TRIPS; ++t) se.res[t] = *reinterpret_cast<const float4*>(p.residual + se.orow[t] * p.ldr + gc);
+    }
+}
+
+// What an output element needs before its residual: folded LayerNorm of the A rows, bias, activation - no global memory, so this part stays a
+// ROLLED loop over the trips that rewrites the staged tile in place (a thread touches its own float4s only: no barrier).  Unrolled with the
+// trips, the activations alone (apply_act's switch, four per trip) were ~3/4 of 35 KB of straight-line code per tile, and the kernel ran 6 us
+// per launch SLOWER inside the sampling loop than the shared epilogue while isolated launches were 1 - 3 us faster (profiles/gemm128_epilogue.md).
+template <int BM, int BN, int NT, int LDC>
+__device__ __forceinline__ void gemm_epilogue_streamed_act(const afm_linear_args& p, float* lds, int tid, const float* rowst,
+                                                           const StreamedEpilogue<BM * BN / 4 / NT>& se) {
+    constexpr int TRIPS = BM * BN / 4 / NT, RSTEP = NT / (BN / 4);
+    if (!p.a_stat && !p.bias && !p.act) return;                 // uniform
+    const int row0 = tid / (BN / 4), cq = (tid % (BN / 4)) * 4;
+#pragma unroll 1
+    for (int i = 0; i < TRIPS; ++i) {
+        const int row = row0 + i * RSTEP;
+        float4 v = *reinterpret_cast<const float4*>(lds + row * LDC + cq);
+        if (p.a_stat) {
+            const float mu = rowst[2 * row], rs = rowst[2 * row + 1];
+            const float4 g = se.fold_g;
+            v.x = rs * (v.x - mu * g.x); v.y = rs * (v.y - mu * g.y); v.z = rs * (v.z - mu * g.z); v.w = rs * (v.w - mu * g.w);
+        }
+        if (p.bias) { const float4 t = se.bias; v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
+        if (p.act) { v.x = apply_act(v.x, p.act); v.y = apply_act(v.y, p.act); v.z = apply_act(v.z, p.act); v.w = apply_act(v.w, p.act); }
+        *reinterpret_cast<float4*>(lds + row * LDC + cq) = v;
+    }
+}
+
+// The eight trips, unrolled: staged value, residual (LayerNorm on the fly), row table, store, statistics.  TAB: the launch adds a row table (gemm_epilogue's plain 16-byte branch; the folded-LayerNorm inputs are absent then), `rt`
+// holds its rows.  Two instantiations because the row table's 32 registers and the fold vectors never live together.
+template <int BM, int BN, int NT, int LDC, bool TAB>
+__device__ __forceinline__ void gemm_epilogue_streamed_trips(const afm_linear_args& p, const float* lds, int bm, int bn, int tid, const float* rowst,
+                                                             const StreamedEpilogue<BM * BN / 4 / NT>& se, const float4* rt) {
+    constexpr int TRIPS = BM * BN / 4 / NT, RSTEP = NT / (BN / 4);
+    const int row0 = tid / (BN / 4), cq = (tid % (BN / 4)) * 4;
+    const int gcol = bn * BN + cq;
+    const bool col_ok = gcol < p.N;
+    const int ngrp = p.N / 64;
+    // Every load of the epilogue has landed before the first store (s_waitcnt vmcnt(0); they were requested a staging phase and a barrier
+    // ago).  Without it hipcc waits per trip for "the loads younger than this trip's residual", and since stores count in vmcnt and retire
+    // in order with loads, that wait also drains the previous trips' stores - down to vmcnt(0) in front of the last trip's store.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i) {
+        const int row = row0 + i * RSTEP, grow = bm * BM + row;
+        const bool valid = grow < p.M && col_ok;
+        const int64_t orow = se.orow[i];
+        float4 v = *reinterpret_cast<const float4*>(lds + row * LDC + cq);
+        if (p.residual) {
+            float4 t = se.res[i];
+            if (!TAB && p.res_stat) {
+                const float mu = rowst[2 * (BM + row)], rs = rowst[2 * (BM + row) + 1];
+                const float4 g = se.res_g, b = se.res_b;
+                t.x = (t.x - mu) * rs * g.x + b.x; t.y = (t.y - mu) * rs * g.y + b.y; t.z = (t.z - mu) * rs * g.z + b.z; t.w = (t.w - mu) * rs * g.w + b.w;
+            }
+            v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+        }
+        if (TAB) { const float4 t = rt[i]; v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
+        if (valid) *reinterpret_cast<float4*>(p.C + orow * p.ldc + gcol) = v;
+        if (!TAB && p.stat_out) {                   // uniform; every lane stays in the butterflies (clamped rows carry values that are never stored)
+            float sm = (v.x + v.y) + (v.z + v.w);
+            sm += lane_xor<1>(sm); sm += lane_xor<2>(sm); sm += lane_xor<4>(sm); sm += lane_xor<8>(sm);
+            const float mu = sm * (1.0f / 64.0f);
+            const float a = v.x - mu, b = v.y - mu, c = v.z - mu, d = v.w - mu;
+            float m2 = (a * a + b * b) + (c * c + d * d);
+            m2 += lane_xor<1>(m2); m2 += lane_xor<2>(m2); m2 += lane_xor<4>(m2); m2 += lane_xor<8>(m2);
+            if (valid && (cq & 63) == 0) *reinterpret_cast<float2*>(p.stat_out + (orow * ngrp + gcol / 64) * 2) = make_float2(mu, m2);
+        }
+    }
+}
+
+template <int BM, int BN, int NT, int LDC = BN + 4>
+__device__ __forceinline__ void gemm_epilogue_streamed(const afm_linear_args& p, float* lds, int bm, int bn, int tid, const float* rowst,
+                                                       const StreamedEpilogue<BM * BN / 4 / NT>& se) {
+    constexpr int TRIPS = BM * BN / 4 / NT, RSTEP = NT / (BN / 4);
+    const bool fold = p.stat_out || p.a_stat || p.res_stat;         // gemm_epilogue's folded-LayerNorm branch (afm_linear refuses a row table there)
+    if (!fold && p.rowtab) {
+        // the row table's rows: requested behind the staging barrier (the accumulators' registers are free from here on), in front of every store
+        float4 rt[TRIPS];
+        const int row0 = tid / (BN / 4), gc = min(bn * BN + (tid % (BN / 4)) * 4, p.N - 4);
+#pragma unroll
+        for (int t = 0; t < TRIPS; ++t)
+            rt[t] = *reinterpret_cast<const float4*>(p.rowtab + (int64_t)(min(bm * BM + row0 + t * RSTEP, p.M - 1) % p.rowtab_period) * p.N + gc);
+        gemm_epilogue_streamed_act<BM, BN, NT, LDC>(p, lds, tid, rowst, se);
+        gemm_epilogue_streamed_trips<BM, BN, NT, LDC, true>(p, lds, bm, bn, tid, rowst, se, rt);
+    } else {
+        gemm_epilogue_streamed_act<BM, BN, NT, LDC>(p, lds, tid, rowst, se);
+        gemm_epilogue_streamed_trips<BM, BN, NT, LDC, false>(p, lds, bm, bn, tid, rowst, se, nullptr);
+    }
+}
+
 // Fused LayerNorm of the output rows ("last arriver", afm_linear_args.ln_*): called by EVERY thread of the workgroup after its tile's
 // epilogue.  The tile is published with the placement-independent hand-off of cdna_hip_programming.md section 6 Guideline 16 (R1 with a
 // ticket counter): the tile was stored write-through (sc1), every storing wave drains its stores, ONE lane takes a ticket on the row

@@ -112,11 +112,15 @@ __global__ __launch_bounds__(256, AFM_WALK_LB) void gemm_f32_split_bf16_walk(con
 //   tile code 5; what changes is that each SIMD now holds two of the tile's waves, so one wave's split VALU, LDS traffic and barrier wait can
 //   issue while the other's MFMAs run.  Two workgroups per CU are four waves per SIMD: <= 128 VGPRs (the second launch bound is hipcc's
 //   amdgpu_waves_per_eu, i.e. waves per SIMD, not workgroups per CU; build_hip.py rejects spills).
+//   tile code 15 (MEASUREMENT): code 14's tile program and K loop with the shared gemm_epilogue (STREAM = false) instead of the streamed
+//   epilogue of gemm_epilogue.h - the baseline arm of profiles/gemm128_epilogue.md and the bit reference of tests/test_gpu_gemm128_epilogue.py.
 // Same tile program text, same products in the same order: bit-identical to every other tile shape.
-template <int BM, int NPROD>
+template <int BM, int NPROD, bool STREAM = (BM == 128)>
 __global__ __launch_bounds__(512, BM == 128 ? 4 : 1) void gemm_f32_split_bf16_wide(const afm_linear_args p, int nbm, int nbn) {
     constexpr int BN = 128, BKS = 16, KG = 1, RING = 2, GSEG = 1;
+    static_assert(!STREAM || BM == 128, "the streamed epilogue exists for the 128 x 128 tile");
 #define AFM_BODY_WM 4
+#define AFM_BODY_STREAMED STREAM
 #define AFM_WG ((int)blockIdx.x)
 #define AFM_TIDX threadIdx.x
 #define AFM_TIMELINE_SLOT blockIdx.x
@@ -124,6 +128,7 @@ __global__ __launch_bounds__(512, BM == 128 ? 4 : 1) void gemm_f32_split_bf16_wi
 #undef AFM_WG
 #undef AFM_TIDX
 #undef AFM_TIMELINE_SLOT
+#undef AFM_BODY_STREAMED
 #undef AFM_BODY_WM
 }
 
@@ -138,7 +143,7 @@ inline bool split_offsets_fit_u32(const afm_linear_args& a) {
 template <int BM, int BN, int BKS, int NPROD, int KG = 1, int RING = 2, int GSEG = 1>
 int launch_split(const afm_linear_args& a, hipStream_t s);
 
-template <int BM, int NPROD>
+template <int BM, int NPROD, bool STREAM = (BM == 128)>
 int launch_split_wide(const afm_linear_args& a, hipStream_t s) {
     static_assert(BM == 128 || BM == 256, "512-thread tiles: 128 x 128 or 256 x 128");
     constexpr int BN = 128, BKS = 16;
@@ -150,12 +155,12 @@ int launch_split_wide(const afm_linear_args& a, hipStream_t s) {
     if (BM == 128 && !split_offsets_fit_u32(a)) return launch_split<128, 128, 16, NPROD, 1, 2, 1>(a, s);      // the 256-thread form: same tile, same bits
     if (a.aux_dst && a.aux_rows > (int64_t)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)) return AFM_E_UNSUPPORTED;      // one rider row per workgroup
     static const int attr = []() {
-        return (int)hipFuncSetAttribute((const void*)gemm_f32_split_bf16_wide<BM, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        return (int)hipFuncSetAttribute((const void*)gemm_f32_split_bf16_wide<BM, NPROD, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     }();
     if (attr != 0) return attr;
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
     AfmProf prof(AFM_PROF_GEMM_SPLIT128, 2.0 * a.M * a.N * a.K, s);
-    hipLaunchKernelGGL((gemm_f32_split_bf16_wide<BM, NPROD>), dim3(nbm * nbn), dim3(512), LDS_BYTES, s, a, nbm, nbn);
+    hipLaunchKernelGGL((gemm_f32_split_bf16_wide<BM, NPROD, STREAM>), dim3(nbm * nbn), dim3(512), LDS_BYTES, s, a, nbm, nbn);
     AFM_CHECK_LAUNCH();
     return 0;
 }
@@ -248,7 +253,7 @@ int launch_split_walk(const afm_linear_args& a, hipStream_t s) {
 
 template <int NPROD>
 int dispatch_split(const afm_linear_args& a, hipStream_t s) {
-    const int tile = (a.tune & AFM_TUNE_TILE_MASK) >> AFM_TUNE_TILE_SHIFT;      // 3 = 64x64, 5 = 128x128, 7 = 64x64 split-K, 8 = weight-stationary slabs, 0 = heuristic
+    const int tile = (a.tune & AFM_TUNE_TILE_MASK) >> AFM_TUNE_TILE_SHIFT;      // 3 = 64x64, 5 = 128x128, 7 = 64x64 split-K, 8 = weight-stationary slabs, 14 / 15 = 128x128 on 512 threads, 0 = heuristic
     // Row-dot launches with K = 256 (the CDM's linear1): the weight-stationary form (gemm_slab.hip) whatever M is
     if ((NPROD == 9 || NPROD == 6) && (tile == 0 || tile == 8) && afm_linear_rowdot_slab_ok(a)) return afm_linear_rowdot_slab(a, NPROD, s);
     if (tile == 8) return AFM_E_UNSUPPORTED;
@@ -294,7 +299,8 @@ int dispatch_split(const afm_linear_args& a, hipStream_t s) {
     const bool full_rounds = tiles128 * 10 >= rounds * resident * 9 && a.K > KSEG;      // >= 90 % of the resident slots used over all rounds
     if (tile == 12) return launch_split_walk<NPROD>(a, s);          // measurement: force the walking form
     if (tile == 13) return launch_split_wide<256, NPROD>(a, s);     // measurement: the 256 x 128 tile on 512 threads
-    if (tile == 14) return launch_split_wide<128, NPROD>(a, s);     // the 128 x 128 tile on 512 threads (two waves per SIMD)
+    if (tile == 14) return launch_split_wide<128, NPROD>(a, s);     // the 128 x 128 tile on 512 threads (two waves per SIMD), streamed epilogue
+    if (tile == 15) return launch_split_wide<128, NPROD, false>(a, s);      // measurement: the same tile with the shared epilogue
     if (tile == 3 || (tile != 5 && !full_rounds)) {
         const int64_t tiles64w = (int64_t)((a.M + 63) / 64) * ((a.N + 63) / 64);
         if (tile != 3 && AFM_WALK_GRID > 0 && tiles64w > AFM_WALK_GRID) return launch_split_walk<NPROD>(a, s);      // (A/B builds only: AFM_WALK_GRID is 0 in the library)

@@ -2,7 +2,8 @@
 // one-tile-per-workgroup kernel stays instruction for instruction what rounds 2-4 tuned while the walking kernels (round 5) run the very same
 // program per tile.  Expects in scope: template parameters BM, BN, BKS, NPROD, KG, RING, GSEG; `const afm_linear_args& p`, `int nbm, nbn`;
 // macros AFM_WG (the tile's linear index in its launch), AFM_TIDX (threadIdx.x, or an opaque per-tile copy of it) and AFM_TIMELINE_SLOT;
-// optionally AFM_BODY_WM = waves along M of one K group (default 2: a 256-thread group of 2 x 2 waves; 4: the 512-thread 256 x 128 tile of round 6).
+// optionally AFM_BODY_WM = waves along M of one K group (default 2: a 256-thread group of 2 x 2 waves; 4: the 512-thread 256 x 128 tile of round 6)
+// and AFM_BODY_STREAMED = a constant expression, true where the tile runs the streamed epilogue (gemm_epilogue.h: the 512-thread 128 x 128 tile).
     static_assert(BKS == 16, "one K16 MFMA step per K-tile");
     static_assert(RING == 2 || RING == 3, "two or three LDS stages");
     static_assert(GSEG == 1 || (GSEG == 2 && KG > 1), "two segments per group: split-K forms only");
@@ -13,6 +14,11 @@
     constexpr int WMv = AFM_BODY_WM;
 #else
     constexpr int WMv = 2;
+#endif
+#ifdef AFM_BODY_STREAMED
+    constexpr bool STREAMED = AFM_BODY_STREAMED;
+#else
+    constexpr bool STREAMED = false;
 #endif
     constexpr int GT = WMv * 2 * 64;                  // threads of one K group: WMv x 2 waves, each a (BM / WMv) x (BN / 2) wave tile
     static_assert(WMv == 2 || KG == 1, "groups of more than 256 threads: one K group only");
@@ -392,6 +398,11 @@
             }
         }
     }
+    // streamed epilogue: every global input of the tile's epilogue is requested here - the operand and fragment registers and the banked
+    // segment sums are dead - and flies while the accumulators are staged in LDS, across the barrier below
+    static_assert(!STREAMED || (GT == 512 && BM == 128 && BN == 128 && KG == 1), "streamed epilogue: the 512-thread 128 x 128 tile");
+    [[maybe_unused]] StreamedEpilogue<STREAMED ? 8 : 1> se;
+    if constexpr (STREAMED) gemm_epilogue_streamed_prefetch<BM, BN, GT>(p, bm, bn, tid, se);
     float* ldsf = reinterpret_cast<float*>(lds_raw);
     if (grp == 0) {
 #pragma unroll
@@ -410,7 +421,17 @@
     // a small launch has nothing else to hide the trips' memory round trips behind; profiles/r04_gemm_timeline_small.txt: epilogue 3.5 of
     // 14.8 us).  An output element's arithmetic does not depend on which thread handles it: bit-identical.
     constexpr int ENT = (KG == 2 || KG == 4) ? 256 * KG : GT;
-    if (ENT > 256) gemm_epilogue<BM, BN, ENT>(p, ldsf, bm, bn, (int)AFM_TIDX, rowst);
+    if constexpr (STREAMED) {
+        // Two tests in this order, the second on an opaque copy of the flag: written as if / else, hipcc lays the shared epilogue out first
+        // and runs into the streamed one behind it, which keeps the 64 prefetched registers alive across the shared epilogue (104 B of scratch).
+        // (the copy is made opaque in a VGPR and read back with the builtin: a v_readfirstlane written out in inline assembly is invisible to
+        // hipcc's hazard recognizer and read its source one instruction behind the VALU write - both epilogues ran)
+        int shared = (int)!se.on;
+        asm volatile("" : "+v"(shared));
+        shared = __builtin_amdgcn_readfirstlane(shared);
+        if (se.on) gemm_epilogue_streamed<BM, BN, GT>(p, ldsf, bm, bn, tid, rowst, se);
+        if (shared) gemm_epilogue<BM, BN, ENT>(p, ldsf, bm, bn, (int)AFM_TIDX, rowst);
+    } else if (ENT > 256) gemm_epilogue<BM, BN, ENT>(p, ldsf, bm, bn, (int)AFM_TIDX, rowst);
     else if (grp == 0) gemm_epilogue<BM, BN>(p, ldsf, bm, bn, tid, rowst);
     gemm_ln_tail<BM>(p, bm, nbn, reinterpret_cast<int*>(ldsf));
     if (p.aux_dst && AFM_WG < p.aux_rows) {          // rider: one row copy (+ add) per workgroup, behind its own tile
