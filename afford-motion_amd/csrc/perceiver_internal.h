@@ -18,8 +18,8 @@ inline int cdm_update_bits(const afm_cdm_weights& w) {
 
 namespace afm_cdm {
 
-constexpr int NSPLIT = 16;          // workgroups per sample in enc_reduce (x4 waves = 64 partials per sample)
-constexpr int NPART = NSPLIT * 4;
+constexpr int NSPLIT = 16;          // (the first enc_reduce split a sample over 16 workgroups x 4 waves; only the product below is still used)
+constexpr int NPART = NSPLIT * 4;   // partials per sample of the encoder reductions: enc_point_kernel and enc_reduce_mfma_kernel both run 8 workgroups x 8 waves
 constexpr int MAXD = 512;           // dq upper bound for the latent kernels' LDS vectors
 constexpr int TL_TOK = 16, TL_OB = 16;      // toklin_kernel: one wave per 16 tokens x 16 outputs
 // per-sample record written by lat_decfold_kernel: G [njh][256] | P [njh][256] | cb [njh] | WP [8][njh] (contact_layer.w . P, folded form)

@@ -104,14 +104,17 @@ def cmdm_forward(sd: SD, x, t, text_feat, c_pc_xyz=None, c_pc_contact=None, x_ma
 
 # ------------------------------------------------------------------ CDM / Perceiver
 
-def _mha(sd, pre, x_q, x_kv, nhead):
-    """modules.py:301-381 (no mask / rotary / cache / causal - never used by this repo)."""
+def _mha(sd, pre, x_q, x_kv, nhead, tap=None):
+    """modules.py:301-381 (no mask / rotary / cache / causal - never used by this repo).  ``tap``: a dict that receives the attention
+    probabilities [B, H, Nq, Nk] under the key ``pre`` (cdm_attention_probs)."""
     q, k, v = _lin(sd, pre + ".q_proj", x_q), _lin(sd, pre + ".k_proj", x_kv), _lin(sd, pre + ".v_proj", x_kv)
     B, Nq, C = q.shape
     split = lambda z: z.view(z.shape[0], z.shape[1], nhead, z.shape[2] // nhead).transpose(1, 2)
     q, k, v = split(q), split(k), split(v)
     q = q * ((C // nhead) ** -0.5)
     a = torch.softmax(torch.einsum("bhic,bhjc->bhij", q, k), dim=-1)
+    if tap is not None:
+        tap[pre] = a
     o = torch.einsum("bhij,bhjc->bhic", a, v).transpose(1, 2).reshape(B, Nq, -1)
     return _lin(sd, pre + ".o_proj", o)
 
@@ -121,10 +124,10 @@ def _mlp(sd, pre, x):
     return _lin(sd, pre + ".3", F.gelu(_lin(sd, pre + ".1", _ln(sd, pre + ".0", x))))
 
 
-def cross_attention_layer(sd, pre, x_q, x_kv, nhead):
+def cross_attention_layer(sd, pre, x_q, x_kv, nhead, tap=None):
     """modules.py:504-541 + Residual (:222-231): pre-LN on q and kv, residual adds the raw q."""
     a = pre + ".0.module"
-    h = _mha(sd, a + ".attention", _ln(sd, a + ".q_norm", x_q), _ln(sd, a + ".kv_norm", x_kv), nhead) + x_q
+    h = _mha(sd, a + ".attention", _ln(sd, a + ".q_norm", x_q), _ln(sd, a + ".kv_norm", x_kv), nhead, tap) + x_q
     return _mlp(sd, pre + ".1.module", h) + h
 
 
@@ -137,7 +140,7 @@ def self_attention_layer(sd, pre, x, nhead):
 
 
 def cdm_forward(sd: SD, x, t, text_feat, c_pc_xyz, pc_emb=None, *, time_emb_dim: int = 128,
-                enc_heads: int = 8, dec_heads: int = 8, self_layers: int = 2, point_pos_emb: bool = True):
+                enc_heads: int = 8, dec_heads: int = 8, self_layers: int = 2, point_pos_emb: bool = True, tap=None):
     """CDM.forward + ContactPerceiver.forward (cdm.py:474-513, 155-188).
 
     ``pc_emb`` = optional per-point scene feature [B, N, F] (the frozen scene model's
@@ -152,12 +155,24 @@ def cdm_forward(sd: SD, x, t, text_feat, c_pc_xyz, pc_emb=None, *, time_emb_dim:
     enc_kv = _lin(sd, cm + ".encoder_adapter", feat)                               # [B,N,256]
     enc_q = torch.cat([_lin(sd, cm + ".language_adapter", text),
                        _lin(sd, cm + ".time_embedding_adapter", time_emb)], dim=1)  # [B,2,512]
-    enc_q = cross_attention_layer(sd, cm + ".encoder_cross_attn", enc_q, enc_kv, enc_heads)
+    enc_q = cross_attention_layer(sd, cm + ".encoder_cross_attn", enc_q, enc_kv, enc_heads, tap)
+    if tap is not None and tap.get("encoder_only"):
+        return None
     for l in range(self_layers):
         enc_q = self_attention_layer(sd, f"{cm}.encoder_self_attn.{l}", enc_q, enc_heads)
     dec_q = _lin(sd, cm + ".decoder_adapter", enc_kv)                              # [B,N,256]
-    dec_q = cross_attention_layer(sd, cm + ".decoder_cross_attn", dec_q, enc_q, dec_heads)
+    dec_q = cross_attention_layer(sd, cm + ".decoder_cross_attn", dec_q, enc_q, dec_heads, tap)
     return _lin(sd, "contact_layer", dec_q)
+
+
+def cdm_attention_probs(sd: SD, x, t, text_feat, c_pc_xyz, pc_emb=None, encoder_only: bool = False, **kw):
+    """The softmax probabilities of the two cross-attentions of the SAME computation cdm_forward runs (its arguments): the encoder's
+    [B, H, 2, N] (the two latents over the points) and the decoder's [B, H, N, 2] (a point over the two latents).  For use in float64
+    (a float64 state dict and inputs): what the edge tests measure peakedness with.  ``encoder_only``: stop behind the encoder's
+    cross-attention and return (encoder probabilities, None)."""
+    tap = {"encoder_only": True} if encoder_only else {}
+    cdm_forward(sd, x, t, text_feat, c_pc_xyz, pc_emb, tap=tap, **kw)
+    return (tap["contact_model.encoder_cross_attn.0.module.attention"], tap.get("contact_model.decoder_cross_attn.0.module.attention"))
 
 
 def cdm_mlp_forward(sd: SD, x, t, text_feat, pc_emb=None, *, time_emb_dim: int = 128, n_layers: int = 2):

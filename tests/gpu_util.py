@@ -72,7 +72,9 @@ def report_f32_class(name, got, want32, want64, old_tol, margin=4.0, select=None
     max_ref, max_got = e_ref.abs().max().item(), e_got.abs().max().item()
     rms_ref, rms_got = e_ref.pow(2).mean().sqrt().item(), e_got.pow(2).mean().sqrt().item()
     floor = ULP32 * want64.abs().max().item()
-    ratio_max, ratio_rms = max_got / (max_ref + floor / margin), rms_got / (rms_ref + floor / margin)
+    # (an exactly zero reference - a gradient under a saturated softmax - has no error and no floor: only an exactly zero result is in its class)
+    ratio = lambda e, d: e / d if d > 0.0 else (0.0 if e == 0.0 else float("inf"))
+    ratio_max, ratio_rms = ratio(max_got, max_ref + floor / margin), ratio(rms_got, rms_ref + floor / margin)
     print(f"[parity-f32] {name}: ref max {max_ref:.3e} rms {rms_ref:.3e} | hip max {max_got:.3e} rms {rms_got:.3e} | "
           f"ratio max {ratio_max:.2f} rms {ratio_rms:.2f} (margin {margin:g}, floor {floor:.1e}, old tol {old_tol:.1e})")
     if record:

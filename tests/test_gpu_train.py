@@ -677,7 +677,63 @@ def _xattn_ref(q, k, v, H, keep=None):
     return (a @ vh).transpose(1, 2).reshape(B, Tq, C), a
 
 
-@pytest.mark.parametrize("B,N,H,C", [(2, 8192, 8, 512), (3, 300, 8, 512), (2, 1000, 8, 256)])
+# Shape edges of the two kernel families (csrc/perceiver_train.hip).  Few-query: N = 8200 is the first size where xq_dots_kernel's 2048
+# workgroups of 4 points take a second grid-stride trip and where xq_chunks caps at 64 (129 points per chunk); N = 1 and 3 leave waves of the
+# one workgroup without a point; N = 129 is the first size with two chunks (65 + 64 points).  Few-key: N = 1 and 3 likewise; N = 4100 is
+# past the forward's 1024 workgroups and the backward's cap of 64 partial sums.
+XQ_EDGE_SHAPES = [(1, 8200, 8, 256), (2, 1, 8, 512), (2, 3, 8, 256), (1, 129, 8, 256)]
+XK_EDGE_SHAPES = [(2, 1, 8, 256), (2, 3, 8, 512), (1, 4100, 8, 256)]
+PEAKED = (8.0, 30.0)              # factors of q: the few-query softmax over N concentrates on one key, the few-key softmax saturates to {1, 0}
+
+
+def xattn_inputs(kind, B, N, H, C, qscale=1.0):
+    """q, k, v, dO of a few-query ("fq": 2 queries over N keys) or few-key ("fk": N queries over 2 keys) case, float32 on the host"""
+    if kind == "fq":
+        return g("fq_q", (B, 2, C)) * qscale, g("fq_k", (B, N, C)) * 0.5, g("fq_v", (B, N, C)), g("fq_do", (B, 2, C))
+    return g("fk_q", (B, N, C)) * qscale, g("fk_k", (B, 2, C)), g("fk_v", (B, 2, C)), g("fk_do", (B, N, C))
+
+
+def xattn_reference(q, k, v, dO, H, dtype):
+    """(out, dQ, dK, dV) of _xattn_ref under torch autograd in `dtype` on the host"""
+    qr, kr, vr = (t.detach().to(dtype).clone().requires_grad_(True) for t in (q, k, v))
+    o, _ = _xattn_ref(qr, kr, vr, H)
+    (o * dO.to(dtype)).sum().backward()
+    return o.detach(), qr.grad, kr.grad, vr.grad
+
+
+def xattn_tolerances(want64):
+    """The existing absolute figures (2e-5 on the output, 5e-5 on the gradients) times max(1, max|want64|)"""
+    return [base * max(1.0, w.abs().max().item()) for base, w in zip((2e-5, 5e-5, 5e-5, 5e-5), want64)]
+
+
+def _peaked_xattn(kind, fn, B, N, H, C, qscale):
+    q, k, v, dO = xattn_inputs(kind, B, N, H, C, qscale)
+    want32, want64 = xattn_reference(q, k, v, dO, H, torch.float32), xattn_reference(q, k, v, dO, H, torch.float64)
+    G = lambda t: t.to(dev()).requires_grad_(True)
+    qg, kg, vg = G(q), G(k), G(v)
+    o = fn(qg, kg, vg, H)
+    (o * dO.to(dev())).sum().backward()
+    name = "few-query" if kind == "fq" else "few-key"
+    for what, got, w32, w64, tol in zip(("out", "dQ", "dK", "dV"), (o, qg.grad, kg.grad, vg.grad), want32, want64, xattn_tolerances(want64)):
+        report_f32_class(f"{name} attention q x {qscale:g} B={B} N={N} C={C} {what}", got, w32, w64, tol)
+
+
+@pytest.mark.parametrize("qscale", PEAKED)
+@pytest.mark.parametrize("B,N,H,C", XQ_EDGE_SHAPES)
+def test_few_query_attention_peaked_fwd_bwd(B, N, H, C, qscale):
+    """q x 8 and x 30 at the shape edges: forward, dQ, dK and dV within 4 x the float32 reference's own error against float64 autograd."""
+    _peaked_xattn("fq", AG.few_query_attention, B, N, H, C, qscale)
+
+
+@pytest.mark.parametrize("qscale", PEAKED)
+@pytest.mark.parametrize("B,N,H,C", XK_EDGE_SHAPES)
+def test_few_key_attention_peaked_fwd_bwd(B, N, H, C, qscale):
+    """Where a probability saturates to exactly 0 or 1 a gradient is exactly zero: the floor of the bound (one ulp of the largest value,
+    0 for a zero tensor) carries it."""
+    _peaked_xattn("fk", AG.few_key_attention, B, N, H, C, qscale)
+
+
+@pytest.mark.parametrize("B,N,H,C", [(2, 8192, 8, 512), (3, 300, 8, 512), (2, 1000, 8, 256)] + XQ_EDGE_SHAPES)
 def test_few_query_attention_fwd_bwd(B, N, H, C):
     q, k, v, dO = g("fq_q", (B, 2, C)), g("fq_k", (B, N, C)) * 0.5, g("fq_v", (B, N, C)), g("fq_do", (B, 2, C))
     T = lambda t: t.double().requires_grad_(True)
@@ -694,7 +750,7 @@ def test_few_query_attention_fwd_bwd(B, N, H, C):
     rel("few-query dV", vg.grad, vr.grad, 5e-5)
 
 
-@pytest.mark.parametrize("B,N,H,C", [(2, 8192, 8, 256), (3, 301, 8, 256), (2, 500, 8, 512)])
+@pytest.mark.parametrize("B,N,H,C", [(2, 8192, 8, 256), (3, 301, 8, 256), (2, 500, 8, 512)] + XK_EDGE_SHAPES)
 def test_few_key_attention_fwd_bwd(B, N, H, C):
     q, k, v, dO = g("fk_q", (B, N, C)), g("fk_k", (B, 2, C)), g("fk_v", (B, 2, C)), g("fk_do", (B, N, C))
     T = lambda t: t.double().requires_grad_(True)
