@@ -40,11 +40,30 @@ struct H3dAdjDev {
     int64_t t_start;
 };
 
-// u = x * std + mean of one feature column, each operation rounded on its own: the recovery and the adjoint see the same features
-__device__ __forceinline__ float h3d_u(const float* __restrict__ xrow, const float* __restrict__ mean, const float* __restrict__ std, int col) {
+// u = x * std + mean of one column, each operation rounded on its own.  Every kernel of this file de-normalises through this, so the
+// recovery, the passes, the adjoint and the targets see the same features and the same positions.
+__device__ __forceinline__ float denorm(const float* __restrict__ xrow, const float* __restrict__ mean, const float* __restrict__ std, int col) {
 #pragma clang fp contract(off)
     const float m = xrow[col] * std[col];
     return m + mean[col];
+}
+
+// the column or joint list of a by-value kernel argument into LDS with static indices (a dynamic index into the argument would put the
+// array in scratch)
+__device__ __forceinline__ void stage_index(const int (&src)[AFM_GUIDE_MAX_JOINTS], int* dst) {
+#pragma unroll
+    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
+        if (threadIdx.x == k) dst[k] = src[k];
+}
+
+// the block's sum of one value per thread in a fixed order: the wave butterfly, then ((r0 + r1) + r2) + r3 over the four waves, read and
+// added by thread 0 alone, which gets the sum (the others get 0)
+__device__ __forceinline__ float block_sum(float v, float* red) {
+#pragma clang fp contract(off)
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return threadIdx.x == 0 ? ((red[0] + red[1]) + red[2]) + red[3] : 0.f;
 }
 
 // [A|t] of sample b into LDS (row-major 3 x 4; NULL: the identity)
@@ -74,9 +93,9 @@ __global__ __launch_bounds__(256) void h3d_recover_kernel(const H3dDev h, const 
     for (int f = threadIdx.x; f < L; f += 256) {
         const float* xrow = xb + (int64_t)f * h.D;
         const bool pad = fmask && fmask[(int64_t)b * L + f];
-        sth[f] = pad ? 0.f : h3d_u(xrow, h.mean, h.std, 0);
-        svx[f] = pad ? 0.f : h3d_u(xrow, h.mean, h.std, 1);
-        svz[f] = pad ? 0.f : h3d_u(xrow, h.mean, h.std, 2);
+        sth[f] = pad ? 0.f : denorm(xrow, h.mean, h.std, 0);
+        svx[f] = pad ? 0.f : denorm(xrow, h.mean, h.std, 1);
+        svz[f] = pad ? 0.f : denorm(xrow, h.mean, h.std, 2);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -107,10 +126,10 @@ __global__ __launch_bounds__(256) void h3d_recover_kernel(const H3dDev h, const 
         const float* xrow = xb + (int64_t)f * h.D;
         float Px, Py, Pz;
         if (j == 0) {
-            Px = sX[f]; Py = h3d_u(xrow, h.mean, h.std, 3); Pz = sZ[f];
+            Px = sX[f]; Py = denorm(xrow, h.mean, h.std, 3); Pz = sZ[f];
         } else {
             const int col = 4 + 3 * (j - 1);
-            const float lx = h3d_u(xrow, h.mean, h.std, col), ly = h3d_u(xrow, h.mean, h.std, col + 1), lz = h3d_u(xrow, h.mean, h.std, col + 2);
+            const float lx = denorm(xrow, h.mean, h.std, col), ly = denorm(xrow, h.mean, h.std, col + 1), lz = denorm(xrow, h.mean, h.std, col + 2);
             const float c = sc[f], s = ss[f];
             Px = (lx * c - lz * s) + sX[f];
             Py = ly;
@@ -127,39 +146,16 @@ __global__ __launch_bounds__(256) void h3d_recover_kernel(const H3dDev h, const 
         }
 }
 
-// the column list into LDS with static indices (a dynamic index into the by-value argument would put the array in scratch)
-__device__ __forceinline__ void stage_cols(const GuideDev& g, int* scols) {
-#pragma unroll
-    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
-        if (threadIdx.x == k) scols[k] = g.cols[k];
-}
-
-// p = x * std + mean of one coordinate, each operation rounded on its own: both passes call this, so they see the same positions
-__device__ __forceinline__ float joint_coord(const float* __restrict__ xrow, const GuideDev& g, int col) {
+// Pass 1 behind its staging, for sample blockIdx.y with the positions in sp[K][L][3] (the [L] validity flags go behind them here), one
+// thread per (k, n) (e = k * N + n: a wave shares k but for one boundary): the minimum of d2 = (dx*dx + dy*dy) + dz*dz over the valid
+// frames and the FIRST frame that attains it (strict <), chat = exp(-d2 / two_s2) (no valid frame: f* = -1, chat = 0),
+// w = (chat - c) * chat; the block's sum of (chat - c)^2 in a fixed order into partial[b][block].  Both forms' pass 1 is this on their p.
+__device__ __forceinline__ void nearest_of_staged(const GuideDev& g, float* sp, const uint8_t* __restrict__ fmask, int* __restrict__ fstar,
+                                                  float* __restrict__ w, float* __restrict__ partial) {
 #pragma clang fp contract(off)
-    const float m = xrow[col] * g.std[col];
-    return m + g.mean[col];
-}
-
-// Pass 1, one thread per (k, n) of sample blockIdx.y (e = k * N + n: a wave shares k but for one boundary): the minimum of
-// d2 = (dx*dx + dy*dy) + dz*dz over the valid frames and the FIRST frame that attains it (strict <), chat = exp(-d2 / two_s2) (no valid
-// frame: f* = -1, chat = 0), w = (chat - c) * chat; the block's sum of (chat - c)^2 in a fixed order into partial[b][block].
-__global__ __launch_bounds__(256) void guide_nearest_kernel(const GuideDev g, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
-                                                            int* __restrict__ fstar, float* __restrict__ w, float* __restrict__ partial) {
-#pragma clang fp contract(off)
-    extern __shared__ float sp[];                   // [K][L][3] positions, then [L] validity
-    __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
     __shared__ float red[4];
     const int b = blockIdx.y, K = g.K, N = g.N, L = g.L;
     int* sval = reinterpret_cast<int*>(sp + (size_t)K * L * 3);
-    stage_cols(g, scols);
-    __syncthreads();
-    for (int i = threadIdx.x; i < K * L; i += 256) {
-        const int k = i / L, f = i - k * L;
-        const float* xrow = x + ((int64_t)b * L + f) * g.D;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) sp[i * 3 + a] = joint_coord(xrow, g, scols[k] + a);
-    }
     for (int f = threadIdx.x; f < L; f += 256) sval[f] = !(fmask && fmask[(int64_t)b * L + f]);
     __syncthreads();
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -185,30 +181,80 @@ __global__ __launch_bounds__(256) void guide_nearest_kernel(const GuideDev g, co
         w[o] = df * chat;
         sq = df * df;
     }
-    sq = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[(int64_t)b * g.nblk + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    sq = block_sum(sq, red);
+    if (threadIdx.x == 0) partial[(int64_t)b * g.nblk + blockIdx.x] = sq;
 }
 
-// Pass 2, one block per (frame blockIdx.x, sample blockIdx.y), wave v the joints k = v, v + 4, ...: S_a = sum over the points n with
-// f*(b, n, k) == f of w * (p_a - q_a) - lane l adds n = l, l + 64, ... in that order, then the fixed butterfly of wave_sum - and
+// pass 1 of the column form: p = the de-normalised columns of x
+__global__ __launch_bounds__(256) void guide_nearest_kernel(const GuideDev g, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                            int* __restrict__ fstar, float* __restrict__ w, float* __restrict__ partial) {
+    extern __shared__ float sp[];                   // [K][L][3] positions, then [L] validity
+    __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
+    const int b = blockIdx.y, L = g.L;
+    stage_index(g.cols, scols);
+    __syncthreads();
+    for (int i = threadIdx.x; i < g.K * L; i += 256) {
+        const int k = i / L, f = i - k * L;
+        const float* xrow = x + ((int64_t)b * L + f) * g.D;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) sp[i * 3 + a] = denorm(xrow, g.mean, g.std, scols[k] + a);
+    }
+    nearest_of_staged(g, sp, fmask, fstar, w, partial);
+}
+
+// pass 1 of the h3d form: p = the recovery kernel's pos[b][K][L][3], the very order staged
+__global__ __launch_bounds__(256) void guide_nearest_h3d_kernel(const GuideDev g, const float* __restrict__ pos, const uint8_t* __restrict__ fmask,
+                                                                int* __restrict__ fstar, float* __restrict__ w, float* __restrict__ partial) {
+    extern __shared__ float sp[];                   // [K][L][3] positions, then [L] validity
+    const int n = g.K * g.L * 3;
+    const float* pb = pos + (int64_t)blockIdx.y * n;
+    for (int i = threadIdx.x; i < n; i += 256) sp[i] = pb[i];
+    nearest_of_staged(g, sp, fmask, fstar, w, partial);
+}
+
+// Pass 2's energy: block 0 of sample blockIdx.y adds the sample's partials in order, energy[b] = sum / (N K)
+__device__ __forceinline__ void sample_energy(const GuideDev& g, const float* __restrict__ partial, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    if (blockIdx.x == 0 && energy && threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < g.nblk; ++i) s += partial[(int64_t)b * g.nblk + i];
+        energy[b] = s / (float)((int64_t)g.N * g.K);
+    }
+}
+
+// Pass 2's sums for (frame blockIdx.x, sample blockIdx.y, joint k) on one wave: S_a = sum over the points n with f*(b, n, k) == f of
+// w * (p_a - q_a) - lane l adds n = l, l + 64, ... in that order, then the fixed butterfly of wave_sum.  Lane a < 3 gets S_a.
+__device__ __forceinline__ float frame_sum(const GuideDev& g, const int* __restrict__ fstar, const float* __restrict__ w, int k, float p0,
+                                           float p1, float p2) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y, f = blockIdx.x, N = g.N, lane = threadIdx.x & 63;
+    const int64_t o = ((int64_t)b * g.K + k) * N;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int n = lane; n < N; n += 64) {
+        if (fstar[o + n] != f) continue;
+        const float ww = w[o + n];
+        const float* qp = g.q + ((int64_t)b * N + n) * 3;
+        const float m0 = ww * (p0 - qp[0]), m1 = ww * (p1 - qp[1]), m2 = ww * (p2 - qp[2]);
+        s0 = s0 + m0; s1 = s1 + m1; s2 = s2 + m2;
+    }
+    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
+    return lane == 0 ? s0 : (lane == 1 ? s1 : s2);
+}
+
+// Pass 2 of the column form, one block per (frame blockIdx.x, sample blockIdx.y), wave v the joints k = v, v + 4, ...:
 // grad[b, f, cols[k] + a] = ((scale[b] * coef) * std_a) * S_a.  Every other column of the row, and the whole row of a masked frame or of a
-// sample with t[b] >= t_start, is written as zero.  Block 0 of a sample adds its energy partials in order: energy[b] = sum / (N K).
+// sample with t[b] >= t_start, is written as zero.
 __global__ __launch_bounds__(256) void guide_gather_kernel(const GuideDev g, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
                                                            const int64_t* __restrict__ t, const int* __restrict__ fstar,
                                                            const float* __restrict__ w, const float* __restrict__ partial,
                                                            float* __restrict__ grad, float* __restrict__ energy) {
 #pragma clang fp contract(off)
     __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
-    const int b = blockIdx.y, f = blockIdx.x, K = g.K, N = g.N;
-    stage_cols(g, scols);
+    const int b = blockIdx.y, f = blockIdx.x, K = g.K;
+    stage_index(g.cols, scols);
     __syncthreads();
-    if (f == 0 && energy && threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < g.nblk; ++i) s += partial[(int64_t)b * g.nblk + i];
-        energy[b] = s / (float)((int64_t)N * K);
-    }
+    sample_energy(g, partial, energy);
     if (!grad) return;
     float* row = grad + ((int64_t)b * g.L + f) * g.D;
     const bool guided = !(fmask && fmask[(int64_t)b * g.L + f]) && !(t && t[b] >= g.t_start);
@@ -223,119 +269,50 @@ __global__ __launch_bounds__(256) void guide_gather_kernel(const GuideDev g, con
     const float ks = g.scale[b] * g.coef;
     for (int k = threadIdx.x >> 6; k < K; k += 4) {
         const int col = scols[k];
-        const float p0 = joint_coord(xrow, g, col), p1 = joint_coord(xrow, g, col + 1), p2 = joint_coord(xrow, g, col + 2);
-        const int64_t o = ((int64_t)b * K + k) * N;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-        for (int n = lane; n < N; n += 64) {
-            if (fstar[o + n] != f) continue;
-            const float ww = w[o + n];
-            const float* qp = g.q + ((int64_t)b * N + n) * 3;
-            const float m0 = ww * (p0 - qp[0]), m1 = ww * (p1 - qp[1]), m2 = ww * (p2 - qp[2]);
-            s0 = s0 + m0; s1 = s1 + m1; s2 = s2 + m2;
-        }
-        s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
+        const float s = frame_sum(g, fstar, w, k, denorm(xrow, g.mean, g.std, col), denorm(xrow, g.mean, g.std, col + 1),
+                                  denorm(xrow, g.mean, g.std, col + 2));
         if (lane < 3) {
-            const float s = lane == 0 ? s0 : (lane == 1 ? s1 : s2);
             const float kss = ks * g.std[col + lane];
             row[col + lane] = kss * s;
         }
     }
 }
 
-// Pass 1 of the h3d form: guide_nearest_kernel with the positions taken from the recovery kernel's pos[b][K][L][3] - the very order staged
-// here - in place of the columns of x.  A kernel of its own (as pass 2 below), so that the code of the two kernels above stays what it was.
-__global__ __launch_bounds__(256) void guide_nearest_h3d_kernel(const GuideDev g, const float* __restrict__ pos, const uint8_t* __restrict__ fmask,
-                                                                int* __restrict__ fstar, float* __restrict__ w, float* __restrict__ partial) {
-#pragma clang fp contract(off)
-    extern __shared__ float sp[];                   // [K][L][3] positions, then [L] validity
-    __shared__ float red[4];
-    const int b = blockIdx.y, K = g.K, N = g.N, L = g.L;
-    int* sval = reinterpret_cast<int*>(sp + (size_t)K * L * 3);
-    const float* pb = pos + (int64_t)b * K * L * 3;
-    for (int i = threadIdx.x; i < K * L * 3; i += 256) sp[i] = pb[i];
-    for (int f = threadIdx.x; f < L; f += 256) sval[f] = !(fmask && fmask[(int64_t)b * L + f]);
-    __syncthreads();
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    float sq = 0.f;
-    if (e < K * N) {
-        const int k = e / N, n = e - k * N;
-        const float* qp = g.q + ((int64_t)b * N + n) * 3;
-        const float qx = qp[0], qy = qp[1], qz = qp[2];
-        const float* pk = sp + (size_t)k * L * 3;
-        float best = INFINITY;
-        int bf = -1;
-        for (int f = 0; f < L; ++f) {
-            if (!sval[f]) continue;
-            const float dx = pk[f * 3] - qx, dy = pk[f * 3 + 1] - qy, dz = pk[f * 3 + 2] - qz;
-            const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-            const float d2 = (xx + yy) + zz;
-            if (d2 < best) { best = d2; bf = f; }
-        }
-        const float chat = bf >= 0 ? expf(-best / g.two_s2) : 0.f;
-        const float df = chat - g.c[((int64_t)b * N + n) * K + k];
-        const int64_t o = ((int64_t)b * K + k) * N + n;
-        fstar[o] = bf;
-        w[o] = df * chat;
-        sq = df * df;
-    }
-    sq = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[(int64_t)b * g.nblk + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// Pass 2 of the h3d form, guide_gather_kernel's blocks, waves and sums: p is the recovery kernel's, and the bare sums go to S[b][f][k][3] for the adjoint (a
-// padded frame is nobody's nearest frame, so its sums are zero; scale, t_start and the mask are the adjoint's business).  S == NULL:
-// the energy alone, one block per sample.
+// Pass 2 of the h3d form, the column form's blocks, waves and sums: p is the recovery kernel's, and the bare sums go to S[b][f][k][3] for
+// the adjoint (a padded frame is nobody's nearest frame, so its sums are zero; scale, t_start and the mask are the adjoint's business).
+// S == NULL: the energy alone, one block per sample.
 __global__ __launch_bounds__(256) void guide_sums_h3d_kernel(const GuideDev g, const float* __restrict__ pos, const int* __restrict__ fstar,
                                                              const float* __restrict__ w, const float* __restrict__ partial,
                                                              float* __restrict__ S, float* __restrict__ energy) {
-#pragma clang fp contract(off)
-    const int b = blockIdx.y, f = blockIdx.x, K = g.K, N = g.N;
-    if (f == 0 && energy && threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < g.nblk; ++i) s += partial[(int64_t)b * g.nblk + i];
-        energy[b] = s / (float)((int64_t)N * K);
-    }
+    const int b = blockIdx.y, f = blockIdx.x, K = g.K, lane = threadIdx.x & 63;
+    sample_energy(g, partial, energy);
     if (!S) return;
-    const int lane = threadIdx.x & 63;
     for (int k = threadIdx.x >> 6; k < K; k += 4) {
         const float* pp = pos + (((int64_t)b * K + k) * g.L + f) * 3;
-        const float p0 = pp[0], p1 = pp[1], p2 = pp[2];
-        const int64_t o = ((int64_t)b * K + k) * N;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-        for (int n = lane; n < N; n += 64) {
-            if (fstar[o + n] != f) continue;
-            const float ww = w[o + n];
-            const float* qp = g.q + ((int64_t)b * N + n) * 3;
-            const float m0 = ww * (p0 - qp[0]), m1 = ww * (p1 - qp[1]), m2 = ww * (p2 - qp[2]);
-            s0 = s0 + m0; s1 = s1 + m1; s2 = s2 + m2;
-        }
-        s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
-        if (lane < 3) S[(((int64_t)b * g.L + f) * K + k) * 3 + lane] = lane == 0 ? s0 : (lane == 1 ? s1 : s2);
+        const float s = frame_sum(g, fstar, w, k, pp[0], pp[1], pp[2]);
+        if (lane < 3) S[(((int64_t)b * g.L + f) * K + k) * 3 + lane] = s;
     }
 }
 
-// The adjoint of the recovery, one block per sample: S[b][f][k][3] -> complete grad rows of the sample, the zeros included.  Per frame
-// (one thread each), G_k = A^T S_k, the local-coordinate and root-height terms written at once, gX_f = sum_k G_x, gZ_f likewise and the
-// rotation term of the joints, in joint order; then SX, SZ = inclusive suffix sums of gX, gZ (lane 0 and lane 64, f = L-1 down to 0);
-// per frame the velocity terms and T_f; then dw = the exclusive suffix sum of T (lane 0, f = L-1 down to 0).  c_f, s_f are read back from
-// what the recovery stored.  A padded frame's row, and every row of a sample with t[b] >= t_start, stays zero.  No atomics.
-__global__ __launch_bounds__(256) void h3d_adjoint_kernel(const H3dAdjDev a, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
-                                                          const int64_t* __restrict__ t, const float* __restrict__ cs, const float* __restrict__ S,
-                                                          float* __restrict__ grad) {
+// The adjoint of the recovery for sample blockIdx.x: S[b][f][k][3] -> the sample's complete rows in `rows` [B][L][D], the zeros included.
+// Per frame (one thread each), G_k = A^T S_k, the local-coordinate and root-height terms written at once, gX_f = sum_k G_x, gZ_f likewise
+// and the rotation term of the joints, in joint order; then SX, SZ = inclusive suffix sums of gX, gZ (lane 0 and lane 64, f = L-1 down
+// to 0); per frame the velocity terms and T_f; then dw = the exclusive suffix sum of T (lane 0, f = L-1 down to 0).  c_f, s_f are read back
+// from what the recovery stored.  A padded frame's row, and every row of a sample with t[b] >= t_start (the return below, uniform over
+// the block), stays zero.  No atomics.
+__device__ __forceinline__ void h3d_adjoint_rows(const H3dAdjDev& a, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                 const int64_t* __restrict__ t, const float* __restrict__ cs, const float* __restrict__ S,
+                                                 float* __restrict__ rows) {
 #pragma clang fp contract(off)
     extern __shared__ float sh[];                   // [H3D_SCAN_ROWS][L]
     __shared__ int sj[AFM_GUIDE_MAX_JOINTS];
     __shared__ float sA[12];
     const int b = blockIdx.x, L = a.L, D = a.D, K = a.K;
     float *sgX = sh, *sgZ = sh + L, *sT = sh + 2 * L, *sc = sh + 3 * L, *ss = sh + 4 * L, *svx = sh + 5 * L, *svz = sh + 6 * L;
-    float* gb = grad + (int64_t)b * L * D;
+    float* gb = rows + (int64_t)b * L * D;
     for (int64_t i = threadIdx.x; i < (int64_t)L * D; i += 256) gb[i] = 0.f;
     if (t && t[b] >= a.t_start) return;
-#pragma unroll
-    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
-        if (threadIdx.x == k) sj[k] = a.joints[k];
+    stage_index(a.joints, sj);
     stage_to_scene(a.to_scene, (int64_t)b * a.ts_stride, sA);
     __syncthreads();                                // (the zeros above are in place before any thread writes a term over them)
     const float* xb = x + (int64_t)b * L * D;
@@ -347,8 +324,8 @@ __global__ __launch_bounds__(256) void h3d_adjoint_kernel(const H3dAdjDev a, con
         const bool pad = mb && mb[f];
         const float c = cs[((int64_t)b * L + f) * 2], s = cs[((int64_t)b * L + f) * 2 + 1];
         sc[f] = c; ss[f] = s;
-        svx[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 1);
-        svz[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 2);
+        svx[f] = pad ? 0.f : denorm(xrow, a.mean, a.std, 1);
+        svz[f] = pad ? 0.f : denorm(xrow, a.mean, a.std, 2);
         float gX = 0.f, gZ = 0.f, T = 0.f;
         for (int k = 0; k < K; ++k) {
             const float* Sp = S + (((int64_t)b * L + f) * K + k) * 3;
@@ -363,7 +340,7 @@ __global__ __launch_bounds__(256) void h3d_adjoint_kernel(const H3dAdjDev a, con
                 continue;
             }
             const int col = 4 + 3 * (j - 1);
-            const float lx = h3d_u(xrow, a.mean, a.std, col), lz = h3d_u(xrow, a.mean, a.std, col + 2);
+            const float lx = denorm(xrow, a.mean, a.std, col), lz = denorm(xrow, a.mean, a.std, col + 2);
             T = T + (Gx * (-lx * s - lz * c) + Gz * (lx * c - lz * s));
             if (!pad) {
                 row[col] = (ks * a.std[col]) * (Gx * c + Gz * s);
@@ -400,6 +377,25 @@ __global__ __launch_bounds__(256) void h3d_adjoint_kernel(const H3dAdjDev a, con
         if (!(mb && mb[f])) gb[(int64_t)f * D] = (ks * a.std[0]) * sT[f];
 }
 
+// the adjoint, one block per sample: the rows are the gradient
+__global__ __launch_bounds__(256) void h3d_adjoint_kernel(const H3dAdjDev a, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                          const int64_t* __restrict__ t, const float* __restrict__ cs, const float* __restrict__ S,
+                                                          float* __restrict__ grad) {
+    h3d_adjoint_rows(a, x, fmask, t, cs, S, grad);
+}
+
+// The adjoint ADDED to the rows the contact term wrote, one launch: the sample's rows go to tmp[b][L][D], then grad = grad + tmp, one
+// rounded addition per element - the zeros of a padded frame, of the other columns and of a sample with t[b] >= t_start included.
+__global__ __launch_bounds__(256) void h3d_adjoint_add_kernel(const H3dAdjDev a, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
+                                                              const int64_t* __restrict__ t, const float* __restrict__ cs, const float* __restrict__ S,
+                                                              float* __restrict__ tmp, float* __restrict__ grad) {
+#pragma clang fp contract(off)
+    h3d_adjoint_rows(a, x, fmask, t, cs, S, tmp);
+    __syncthreads();                                // (the block's own global writes to tmp are visible to it behind the barrier)
+    const int64_t n = (int64_t)a.L * a.D, o = blockIdx.x * n;
+    for (int64_t i = threadIdx.x; i < n; i += 256) grad[o + i] = grad[o + i] + tmp[o + i];
+}
+
 // ---- joint-position targets (afm_joint_targets): E = sum over valid (f, k) of w * |p - g|^2 on the positions p the kernels above compute.
 struct TargetDev {
     const float *target, *weight, *mean, *std, *scale;
@@ -407,15 +403,6 @@ struct TargetDev {
     int K, L, D;
     int64_t t_start;
 };
-
-// the block's sum of one value per thread in a fixed order: the wave butterfly, then ((r0 + r1) + r2) + r3; valid in thread 0
-__device__ __forceinline__ float target_block_sum(float v, float* red) {
-#pragma clang fp contract(off)
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // one item's energy term w * ((dx*dx + dy*dy) + dz*dz), d = p - g
 __device__ __forceinline__ float target_term(float w, float p0, float p1, float p2, const float* __restrict__ gp) {
@@ -429,7 +416,7 @@ __device__ __forceinline__ float target_term(float w, float p0, float p1, float 
 // d = g_a - p_a, m = w * d, term = ((scale[b] * 2) * std_a) * m; every other column of the row, a joint with w == 0 (its target is not
 // read), a padded frame and a sample with t[b] >= t_start give the term 0.  ACC: row[d] = row[d] + term for EVERY column of the row (one
 // rounded addition per element on what the contact term wrote), else row[d] = term.  Block 0 of a sample adds its energy: thread i the
-// items e = f * K + k = i, i + 256, ... in that order, then target_block_sum.
+// items e = f * K + k = i, i + 256, ... in that order, then block_sum.
 template <bool ACC>
 __global__ __launch_bounds__(256) void target_cols_kernel(const TargetDev g, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
                                                           const int64_t* __restrict__ t, float* __restrict__ grad, float* __restrict__ energy) {
@@ -437,9 +424,7 @@ __global__ __launch_bounds__(256) void target_cols_kernel(const TargetDev g, con
     __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
     __shared__ float red[4];
     const int b = blockIdx.y, f = blockIdx.x, K = g.K, L = g.L, D = g.D;
-#pragma unroll
-    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
-        if (threadIdx.x == k) scols[k] = g.cols[k];
+    stage_index(g.cols, scols);
     __syncthreads();
     if (f == 0 && energy) {
         float acc = 0.f;
@@ -451,10 +436,10 @@ __global__ __launch_bounds__(256) void target_cols_kernel(const TargetDev g, con
             if (w == 0.f) continue;
             const float* xrow = x + ((int64_t)b * L + ff) * D;
             const int col = scols[k];
-            const float p0 = h3d_u(xrow, g.mean, g.std, col), p1 = h3d_u(xrow, g.mean, g.std, col + 1), p2 = h3d_u(xrow, g.mean, g.std, col + 2);
+            const float p0 = denorm(xrow, g.mean, g.std, col), p1 = denorm(xrow, g.mean, g.std, col + 1), p2 = denorm(xrow, g.mean, g.std, col + 2);
             acc = acc + target_term(w, p0, p1, p2, g.target + o * 3);
         }
-        acc = target_block_sum(acc, red);
+        acc = block_sum(acc, red);
         if (threadIdx.x == 0) energy[b] = acc;
     }
     if (!grad) return;
@@ -471,7 +456,7 @@ __global__ __launch_bounds__(256) void target_cols_kernel(const TargetDev g, con
                 const int64_t o = ((int64_t)b * L + f) * K + k;
                 const float w = g.weight[o];
                 if (w == 0.f) break;
-                const float dd = g.target[o * 3 + a] - h3d_u(xrow, g.mean, g.std, d);
+                const float dd = g.target[o * 3 + a] - denorm(xrow, g.mean, g.std, d);
                 const float m = w * dd;
                 term = (ks * g.std[d]) * m;
                 break;
@@ -482,7 +467,7 @@ __global__ __launch_bounds__(256) void target_cols_kernel(const TargetDev g, con
 
 // The h3d form, one block per sample: the recovery's positions pos[b][f][k][3] (the targets' own order) -> S[b][f][k][3] = w * (g - p),
 // zero where w == 0 (the target is not read) or the frame is padded, for the adjoint; scale, t_start and the rows are the adjoint's
-// business.  The energy as in the column form: thread i the items e = i, i + 256, ... in that order, then target_block_sum.
+// business.  The energy as in the column form: thread i the items e = i, i + 256, ... in that order, then block_sum.
 __global__ __launch_bounds__(256) void target_h3d_kernel(const TargetDev g, const float* __restrict__ pos, const uint8_t* __restrict__ fmask,
                                                          float* __restrict__ S, float* __restrict__ energy) {
 #pragma clang fp contract(off)
@@ -504,94 +489,8 @@ __global__ __launch_bounds__(256) void target_h3d_kernel(const TargetDev g, cons
         if (S) { S[o * 3] = s0; S[o * 3 + 1] = s1; S[o * 3 + 2] = s2; }
     }
     if (!energy) return;
-    acc = target_block_sum(acc, red);
+    acc = block_sum(acc, red);
     if (threadIdx.x == 0) energy[b] = acc;
-}
-
-// h3d_adjoint_kernel's result ADDED to the rows the contact term wrote, one launch: the adjoint's passes, scans and expressions repeated
-// (that kernel keeps its code) with the sample's rows going to tmp[b][L][D], then grad = grad + tmp, one rounded addition per element -
-// the zeros of a padded frame, of the other columns and of a sample with t[b] >= t_start included.
-__global__ __launch_bounds__(256) void h3d_adjoint_add_kernel(const H3dAdjDev a, const float* __restrict__ x, const uint8_t* __restrict__ fmask,
-                                                              const int64_t* __restrict__ t, const float* __restrict__ cs, const float* __restrict__ S,
-                                                              float* __restrict__ tmp, float* __restrict__ grad) {
-#pragma clang fp contract(off)
-    extern __shared__ float sh[];                   // [H3D_SCAN_ROWS][L]
-    __shared__ int sj[AFM_GUIDE_MAX_JOINTS];
-    __shared__ float sA[12];
-    const int b = blockIdx.x, L = a.L, D = a.D, K = a.K;
-    float *sgX = sh, *sgZ = sh + L, *sT = sh + 2 * L, *sc = sh + 3 * L, *ss = sh + 4 * L, *svx = sh + 5 * L, *svz = sh + 6 * L;
-    float* gb = tmp + (int64_t)b * L * D;
-    float* out = grad + (int64_t)b * L * D;
-    for (int64_t i = threadIdx.x; i < (int64_t)L * D; i += 256) gb[i] = 0.f;
-    if (!(t && t[b] >= a.t_start)) {                // (uniform over the block)
-#pragma unroll
-        for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
-            if (threadIdx.x == k) sj[k] = a.joints[k];
-        stage_to_scene(a.to_scene, (int64_t)b * a.ts_stride, sA);
-        __syncthreads();
-        const float* xb = x + (int64_t)b * L * D;
-        const uint8_t* mb = fmask ? fmask + (int64_t)b * L : nullptr;
-        const float ks = a.scale[b] * a.coef;
-        for (int f = threadIdx.x; f < L; f += 256) {
-            const float* xrow = xb + (int64_t)f * D;
-            float* row = gb + (int64_t)f * D;
-            const bool pad = mb && mb[f];
-            const float c = cs[((int64_t)b * L + f) * 2], s = cs[((int64_t)b * L + f) * 2 + 1];
-            sc[f] = c; ss[f] = s;
-            svx[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 1);
-            svz[f] = pad ? 0.f : h3d_u(xrow, a.mean, a.std, 2);
-            float gX = 0.f, gZ = 0.f, T = 0.f;
-            for (int k = 0; k < K; ++k) {
-                const float* Sp = S + (((int64_t)b * L + f) * K + k) * 3;
-                const float S0 = Sp[0], S1 = Sp[1], S2 = Sp[2];
-                const float Gx = (sA[0] * S0 + sA[4] * S1) + sA[8] * S2;
-                const float Gy = (sA[1] * S0 + sA[5] * S1) + sA[9] * S2;
-                const float Gz = (sA[2] * S0 + sA[6] * S1) + sA[10] * S2;
-                gX = gX + Gx; gZ = gZ + Gz;
-                const int j = sj[k];
-                if (j == 0) {
-                    if (!pad) row[3] = (ks * a.std[3]) * Gy;
-                    continue;
-                }
-                const int col = 4 + 3 * (j - 1);
-                const float lx = h3d_u(xrow, a.mean, a.std, col), lz = h3d_u(xrow, a.mean, a.std, col + 2);
-                T = T + (Gx * (-lx * s - lz * c) + Gz * (lx * c - lz * s));
-                if (!pad) {
-                    row[col] = (ks * a.std[col]) * (Gx * c + Gz * s);
-                    row[col + 1] = (ks * a.std[col + 1]) * Gy;
-                    row[col + 2] = (ks * a.std[col + 2]) * (Gz * c - Gx * s);
-                }
-            }
-            sgX[f] = gX; sgZ[f] = gZ; sT[f] = T;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0 || threadIdx.x == 64) {
-            float* v = threadIdx.x == 0 ? sgX : sgZ;
-            float acc = 0.f;
-            for (int f = L - 1; f >= 0; --f) { acc = acc + v[f]; v[f] = acc; }
-        }
-        __syncthreads();
-        for (int f = threadIdx.x; f < L; f += 256) {
-            if (f == 0) { sT[0] = 2.f * sT[0]; continue; }
-            const float SX = sgX[f], SZ = sgZ[f], c = sc[f], s = ss[f], vx = svx[f - 1], vz = svz[f - 1];
-            sT[f] = 2.f * ((sT[f] + SX * (-vx * s - vz * c)) + SZ * (vx * c - vz * s));
-            if (!(mb && mb[f - 1])) {
-                float* row = gb + (int64_t)(f - 1) * D;
-                row[1] = (ks * a.std[1]) * (SX * c + SZ * s);
-                row[2] = (ks * a.std[2]) * (SZ * c - SX * s);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float acc = 0.f;
-            for (int f = L - 1; f >= 0; --f) { const float v = sT[f]; sT[f] = acc; acc = acc + v; }
-        }
-        __syncthreads();
-        for (int f = threadIdx.x; f < L; f += 256)
-            if (!(mb && mb[f])) gb[(int64_t)f * D] = (ks * a.std[0]) * sT[f];
-    }
-    __syncthreads();                                // (the block's own global writes to tmp are visible to it behind the barrier)
-    for (int64_t i = threadIdx.x; i < (int64_t)L * D; i += 256) out[i] = out[i] + gb[i];
 }
 
 int64_t guide_nblk(int N, int K) { return ((int64_t)N * K + 255) / 256; }
@@ -608,6 +507,51 @@ bool h3d_joint_list_ok(const int32_t* joints, int n) {
             if (joints[j] == joints[k]) return false;
     }
     return true;
+}
+
+// the K joints of a description, either term's: h3d joints 0..21, none twice, in a motion that holds the feature columns, placed by one
+// matrix or one per sample; else column triples inside D that do not overlap
+int joints_check(const int32_t* cols, const afm_h3d_layout* h3d, int K, int D) {
+    if (h3d) {
+        if (D < H3D_COLS || !h3d_joint_list_ok(h3d->joints, K)) return AFM_E_BADARG;
+        if (h3d->to_scene_stride != 0 && h3d->to_scene_stride != 12) return AFM_E_BADARG;
+        return 0;
+    }
+    for (int k = 0; k < K; ++k) {
+        if (cols[k] < 0 || cols[k] + 3 > D) return AFM_E_BADARG;
+        for (int j = 0; j < k; ++j)
+            if (cols[k] < cols[j] + 3 && cols[j] < cols[k] + 3) return AFM_E_BADARG;          // overlapping triples
+    }
+    return 0;
+}
+
+// What an h3d term launches around its own kernels: the recovery's and the adjoint's descriptions of the samples [start, start + count)
+// and their buffers, carved from wp - positions and S, [count][K][L][3] (k_major: the order pass 1 stages) or [count][L][K][3] (the
+// targets' own), then c / s [count][L][2]; `end` is the byte behind them.  `scale` already points at sample `start`.
+struct H3dPlan {
+    H3dDev rec;
+    H3dAdjDev adj;
+    float *pos, *S, *cs;
+    char* end;
+    size_t scan_lds;
+};
+
+H3dPlan h3d_plan(const float* mean, const float* std, const float* scale, const afm_h3d_layout& lay, int K, int L, int D, int start, int count,
+                 bool k_major, float coef, int64_t t_start, char* wp) {
+    H3dPlan p = {};
+    const int64_t klb = afm_loop::align256((int64_t)count * K * L * 3 * 4);
+    p.pos = (float*)wp; wp += klb;
+    p.S = (float*)wp; wp += klb;
+    p.cs = (float*)wp; p.end = wp + afm_loop::align256((int64_t)count * L * 2 * 4);
+    p.scan_lds = (size_t)H3D_SCAN_ROWS * L * 4;
+    p.rec.mean = p.adj.mean = mean; p.rec.std = p.adj.std = std;
+    p.rec.to_scene = p.adj.to_scene = lay.to_scene ? lay.to_scene + (int64_t)start * lay.to_scene_stride : nullptr;
+    p.rec.ts_stride = p.adj.ts_stride = lay.to_scene_stride;
+    for (int k = 0; k < K; ++k) p.rec.joints[k] = p.adj.joints[k] = lay.joints[k];
+    p.rec.J = p.adj.K = K; p.rec.L = p.adj.L = L; p.rec.D = p.adj.D = D;
+    p.rec.out_b = (int64_t)K * L * 3; p.rec.out_j = k_major ? (int64_t)L * 3 : 3; p.rec.out_f = k_major ? 3 : (int64_t)K * 3;
+    p.adj.scale = scale; p.adj.coef = coef; p.adj.t_start = t_start;
+    return p;
 }
 
 }  // namespace
@@ -633,16 +577,7 @@ __attribute__((visibility("hidden"))) int64_t afm_contact_guide_workspace_bytes(
 __attribute__((visibility("hidden"))) int afm_contact_guide_check(const afm_contact_guide* a, int32_t L, int32_t D) {
     if (!a || !a->q || !a->c || !a->mean || !a->std || !a->scale || L <= 0 || D <= 0) return AFM_E_BADARG;
     if (a->K <= 0 || a->K > AFM_GUIDE_MAX_JOINTS || a->N <= 0 || !(a->sigma > 0.0) || (int64_t)a->N * a->K > (int64_t)1 << 30) return AFM_E_BADARG;
-    if (a->h3d) {
-        if (D < H3D_COLS || !h3d_joint_list_ok(a->h3d->joints, a->K)) return AFM_E_BADARG;
-        if (a->h3d->to_scene_stride != 0 && a->h3d->to_scene_stride != 12) return AFM_E_BADARG;
-    } else {
-        for (int k = 0; k < a->K; ++k) {
-            if (a->cols[k] < 0 || a->cols[k] + 3 > D) return AFM_E_BADARG;
-            for (int j = 0; j < k; ++j)
-                if (a->cols[k] < a->cols[j] + 3 && a->cols[j] < a->cols[k] + 3) return AFM_E_BADARG;          // overlapping triples
-        }
-    }
+    if (joints_check(a->cols, a->h3d, a->K, D) != 0) return AFM_E_BADARG;
     if (((size_t)a->K * L * 3 + L) * 4 > (size_t)GUIDE_LDS_BYTES || L > 65535) return AFM_E_UNSUPPORTED;
     if (a->h3d && (size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
     return 0;
@@ -674,32 +609,17 @@ __attribute__((visibility("hidden"))) int afm_contact_guidance_sub(const afm_con
     float* partial = (float*)wp;
     hipStream_t s = (hipStream_t)stream;
     if (a->h3d) {
-        const afm_h3d_layout& lay = *a->h3d;
         wp = (char*)workspace + afm_loop::align256(afm_contact_guidance_workspace_bytes(count, a->N, a->K));
-        const int64_t klb = afm_loop::align256((int64_t)count * a->K * L * 3 * 4);
-        float* pos = (float*)wp; wp += klb;
-        float* S = (float*)wp; wp += klb;
-        float* cs = (float*)wp;
-        const float* to_scene = lay.to_scene ? lay.to_scene + (int64_t)start * lay.to_scene_stride : nullptr;
-        const size_t scan_lds = (size_t)H3D_SCAN_ROWS * L * 4;
-        H3dDev h = {};
-        h.mean = a->mean; h.std = a->std; h.to_scene = to_scene; h.ts_stride = lay.to_scene_stride;
-        for (int k = 0; k < a->K; ++k) h.joints[k] = lay.joints[k];
-        h.J = a->K; h.L = L; h.D = D;
-        h.out_b = (int64_t)a->K * L * 3; h.out_j = (int64_t)L * 3; h.out_f = 3;
-        hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, h, x, frame_mask, pos, grad ? cs : nullptr);
+        const H3dPlan p = h3d_plan(a->mean, a->std, g.scale, *a->h3d, a->K, L, D, start, count, true, g.coef, a->t_start, wp);
+        hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.rec, x, frame_mask, p.pos, grad ? p.cs : nullptr);
         AFM_CHECK_LAUNCH();
-        hipLaunchKernelGGL(guide_nearest_h3d_kernel, dim3((unsigned)g.nblk, (unsigned)count), dim3(256), lds, s, g, pos, frame_mask, fstar, w, partial);
+        hipLaunchKernelGGL(guide_nearest_h3d_kernel, dim3((unsigned)g.nblk, (unsigned)count), dim3(256), lds, s, g, p.pos, frame_mask, fstar, w, partial);
         AFM_CHECK_LAUNCH();
-        hipLaunchKernelGGL(guide_sums_h3d_kernel, dim3(grad ? (unsigned)L : 1u, (unsigned)count), dim3(256), 0, s, g, pos, fstar, w, partial,
-                           grad ? S : nullptr, energy);
+        hipLaunchKernelGGL(guide_sums_h3d_kernel, dim3(grad ? (unsigned)L : 1u, (unsigned)count), dim3(256), 0, s, g, p.pos, fstar, w, partial,
+                           grad ? p.S : nullptr, energy);
         AFM_CHECK_LAUNCH();
         if (!grad) return 0;
-        H3dAdjDev ad = {};
-        ad.mean = a->mean; ad.std = a->std; ad.scale = g.scale; ad.to_scene = to_scene; ad.ts_stride = lay.to_scene_stride;
-        for (int k = 0; k < a->K; ++k) ad.joints[k] = lay.joints[k];
-        ad.K = a->K; ad.L = L; ad.D = D; ad.coef = g.coef; ad.t_start = a->t_start;
-        hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, ad, x, frame_mask, t, cs, S, grad);
+        hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, x, frame_mask, t, p.cs, p.S, grad);
         AFM_CHECK_LAUNCH();
         return 0;
     }
@@ -728,17 +648,8 @@ int64_t targets_workspace_bytes(const afm_joint_targets* a, bool add, int64_t co
 int targets_check(const afm_joint_targets* a, int32_t L, int32_t D) {
     if (!a->target || !a->weight || !a->mean || !a->std || !a->scale || L <= 0 || D <= 0) return AFM_E_BADARG;
     if (a->K <= 0 || a->K > AFM_GUIDE_MAX_JOINTS) return AFM_E_BADARG;
-    if (a->h3d) {
-        if (D < H3D_COLS || !h3d_joint_list_ok(a->h3d->joints, a->K)) return AFM_E_BADARG;
-        if (a->h3d->to_scene_stride != 0 && a->h3d->to_scene_stride != 12) return AFM_E_BADARG;
-        if ((size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
-    } else {
-        for (int k = 0; k < a->K; ++k) {
-            if (a->cols[k] < 0 || a->cols[k] + 3 > D) return AFM_E_BADARG;
-            for (int j = 0; j < k; ++j)
-                if (a->cols[k] < a->cols[j] + 3 && a->cols[j] < a->cols[k] + 3) return AFM_E_BADARG;          // overlapping triples
-        }
-    }
+    if (joints_check(a->cols, a->h3d, a->K, D) != 0) return AFM_E_BADARG;
+    if (a->h3d && (size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
     if (L > 65535 || (int64_t)L * a->K > (int64_t)1 << 30) return AFM_E_UNSUPPORTED;
     return 0;
 }
@@ -758,30 +669,15 @@ int targets_sub(const afm_joint_targets* a, bool add, int32_t start, const float
         AFM_CHECK_LAUNCH();
         return 0;
     }
-    const afm_h3d_layout& lay = *a->h3d;
-    const int64_t klb = afm_loop::align256((int64_t)count * a->K * L * 3 * 4);
-    float* pos = (float*)wp; wp += klb;
-    float* S = (float*)wp; wp += klb;
-    float* cs = (float*)wp; wp += afm_loop::align256((int64_t)count * L * 2 * 4);
-    float* tmp = (float*)wp;
-    const float* to_scene = lay.to_scene ? lay.to_scene + (int64_t)start * lay.to_scene_stride : nullptr;
-    const size_t scan_lds = (size_t)H3D_SCAN_ROWS * L * 4;
-    H3dDev h = {};
-    h.mean = a->mean; h.std = a->std; h.to_scene = to_scene; h.ts_stride = lay.to_scene_stride;
-    for (int k = 0; k < a->K; ++k) h.joints[k] = lay.joints[k];
-    h.J = a->K; h.L = L; h.D = D;
-    h.out_b = (int64_t)L * a->K * 3; h.out_j = 3; h.out_f = (int64_t)a->K * 3;          // [count][L][K][3]: the targets' own order
-    hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, h, x, frame_mask, pos, grad ? cs : nullptr);
+    const H3dPlan p = h3d_plan(a->mean, a->std, g.scale, *a->h3d, a->K, L, D, start, count, false, 2.f, a->t_start, wp);
+    float* tmp = (float*)p.end;                     // (add: the adjoint's own rows [count][L][D])
+    hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.rec, x, frame_mask, p.pos, grad ? p.cs : nullptr);
     AFM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(target_h3d_kernel, dim3((unsigned)count), dim3(256), 0, s, g, pos, frame_mask, grad ? S : nullptr, energy);
+    hipLaunchKernelGGL(target_h3d_kernel, dim3((unsigned)count), dim3(256), 0, s, g, p.pos, frame_mask, grad ? p.S : nullptr, energy);
     AFM_CHECK_LAUNCH();
     if (!grad) return 0;
-    H3dAdjDev ad = {};
-    ad.mean = a->mean; ad.std = a->std; ad.scale = g.scale; ad.to_scene = to_scene; ad.ts_stride = lay.to_scene_stride;
-    for (int k = 0; k < a->K; ++k) ad.joints[k] = lay.joints[k];
-    ad.K = a->K; ad.L = L; ad.D = D; ad.coef = 2.f; ad.t_start = a->t_start;
-    if (add) hipLaunchKernelGGL(h3d_adjoint_add_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, ad, x, frame_mask, t, cs, S, tmp, grad);
-    else hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), scan_lds, s, ad, x, frame_mask, t, cs, S, grad);
+    if (add) hipLaunchKernelGGL(h3d_adjoint_add_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, x, frame_mask, t, p.cs, p.S, tmp, grad);
+    else hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, x, frame_mask, t, p.cs, p.S, grad);
     AFM_CHECK_LAUNCH();
     return 0;
 }

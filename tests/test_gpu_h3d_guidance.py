@@ -109,6 +109,31 @@ def test_h3d_contact_guidance_kernels_vs_float64(case):
     assert not part[0].any() and torch.equal(part[1:], got[1:])
 
 
+@pytest.mark.parametrize("L,N,K", [(7, 300, 2), (1, 1, 1)])
+def test_the_h3d_energy_is_the_column_energy_of_the_recovered_positions(L, N, K):
+    """The two forms' pass 1 is one computation on the positions: the h3d energy of x equals, bit for bit, the column-form energy (mean 0,
+    std 1: x * 1 + 0 is exact) of the motion whose 3 K columns hold ops.h3d_joints(x) - the same [K][L][3] tile staged, the same search,
+    partials and serial sum.  N K = 600: three blocks, the last part-filled; a padded tail frame in sample 0 (L = 7); sample 2 has no
+    valid frame."""
+    Bn, joints, tag = 3, JOINTS[:K], f"h3d_one_body_L{L}_N{N}_K{K}"
+    x = D(synth.gaussian(tag + "_x", (Bn, L, 263)))
+    mean, std = 0.3 * synth.gaussian(tag + "_mean", (263,)), 0.5 + synth.gaussian(tag + "_std", (263,)).abs()
+    std[0], std[1:3] = 0.05, 0.1
+    ts = D(ZUP.repeat(Bn, 1, 1) + 0.2 * synth.gaussian(tag + "_to_scene", (Bn, 3, 4)))
+    mask = torch.zeros(Bn, L, dtype=torch.bool)
+    mask[0, max(L - 1, 1):] = True
+    mask[2] = True
+    c = torch.rand((Bn, N, K), generator=torch.Generator().manual_seed(N * 100 + K)) * 0.999 + 0.001
+    kw = dict(c_pc_xyz=D(1.5 * synth.gaussian(tag + "_q", (Bn, N, 3))), c_pc_contact=D(c), x_mask=D(mask))
+    pos = ops.h3d_joints(x, mean, std, x_mask=kw["x_mask"], joints=joints, to_scene=ts)
+    assert pos.shape == (Bn, L, K, 3)
+    h3d = ContactGuidance.h3d(joints, mean, std, to_scene=ts, sigma=SIGMA)
+    cols = ContactGuidance([3 * k for k in range(K)], torch.zeros(3 * K), torch.ones(3 * K), sigma=SIGMA)
+    e_h3d, e_cols = h3d.energy(x, **kw), cols.energy(pos.reshape(Bn, L, 3 * K), **kw)
+    print(f"[h3d one body] L={L} N={N} K={K}: h3d {e_h3d.tolist()}, columns {e_cols.tolist()}")
+    assert torch.isfinite(e_h3d).all() and (e_h3d > 0).all() and torch.equal(e_h3d, e_cols)
+
+
 # ---------------------------------------------------------------------------------------------------------------- native loops, exact
 def _guide(**kw):
     mean, std = 0.3 * synth.gaussian("h3d_loop_mean", (263,)), 0.5 + synth.gaussian("h3d_loop_std", (263,)).abs()
