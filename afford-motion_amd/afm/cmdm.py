@@ -26,7 +26,7 @@ from . import autograd as AG
 from . import ffi, fold, ops
 from ._cache import HeldKey
 from .base import Model
-from .guidance import ContactGuidance, JointTargets, MotionGuidance, scale_row, scale_value
+from .guidance import ContactGuidance, JointTargets, LongGuidance, MotionGuidance, scale_row, scale_value
 from .scene import SceneMapEncoder, SceneMapEncoderDecoder
 from .text import TextEncoderMixin, lang_feat_dim_type
 
@@ -150,7 +150,8 @@ class LoopExtras(NamedTuple):
     enters the update launch; the loop runs in the separate-update form like an imputing one, and steps before the guidance starts launch
     what an imputing loop launches.  ``stitch``: an afm.diffusion.Stitch - the batch rows are overlapping windows of long motions and
     every step's update launch gives the frames two windows share one pred_xstart (afm_cmdm_stitch_loop_range, every deterministic
-    form; the separate-update form; sub-batches are cut over long motions)."""
+    form; the separate-update form; sub-batches are cut over long motions).  With ``stitch`` the one ``guide`` taken is an
+    afm.diffusion.LongGuidance on the same geometry (afm_cmdm_long_guide_loop_range: the terms on the joined long motions)."""
     cfg: object = None
     branch_streams: bool = False
     guide: object = None
@@ -169,10 +170,13 @@ class LoopPlan(NamedTuple):
 
 def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, term: str = "none", stitch: bool = False) -> LoopPlan:
     """The entry a chain reaches: ``update`` "ddpm" / "ddim" / "dpm", ``guidance`` "none" / "cfg" (one scale) / "cfg2" (two), with or without
-    ``impute``, ``term`` "none" / "contact" (a bare ContactGuidance) / "motion" (anything that carries targets), stitched or not.  By
+    ``impute``, ``term`` "none" / "contact" (a bare ContactGuidance) / "motion" (anything that carries targets) / "long" (a LongGuidance:
+    only stitched, only with a deterministic update; the long description takes the guidance's slot and carries the stitch), stitched or not.  By
     priority: a term's entry, the stitched one, the 2M one (each runs every form it is asked for on a workspace of its own size: a history
     buffer, gradient buffers, sub-batches over long motions), then the entries of both updates (cfg2, impute), then one per update."""
-    if stitch and (update == "ddpm" or term != "none"):
+    if term == "long" and not stitch:
+        raise ValueError("term 'long' guides stitched windows: no such loop with stitch=False")
+    if stitch and (update == "ddpm" or term not in ("none", "long")):
         raise ValueError(f"no stitched loop with update {update!r} and term {term!r}")
     base = {"none": "loop", "cfg": "cfg_loop", "cfg2": "cfg2_loop"}[guidance]
     cfgs = ("cfg" if guidance == "cfg" else None, "cfg2" if guidance == "cfg2" else None)
@@ -180,9 +184,9 @@ def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, te
     ddim = "ddim_rows" if update == "ddim" else None
     ddpm = ("c1", "c2", "sigma") if update == "ddpm" else (None, None, None)
     tail = ("n_steps", "first_step", "seed", "sample_index0")
-    own = {"contact": "guide", "motion": "motion_guide"}.get(term, "stitch" if stitch else None)
+    own = {"contact": "guide", "motion": "motion_guide", "long": "long_guide"}.get(term, "stitch" if stitch else None)
     if own is not None:                 # both kinds of rows and the 2M rows, one of the three set
-        last = ("stitch" if stitch else "term",)
+        last = ("stitch" if own == "stitch" else "term",)
         return LoopPlan(f"afm_cmdm_{own}_loop_range", f"afm_cmdm_{own}_loop_workspace_bytes", cfgs + last, (own, base),
                         ("noise", "tmap", ddim, "dpm_rows" if update == "dpm" else None) + ddpm + cfgs + known + last + tail)
     if update == "dpm":                 # no noise, no seed
@@ -207,9 +211,14 @@ def _refuse_loop(ex: LoopExtras, x, model_kwargs, step_noise, ddim_eta, dpm_orde
                              "windows share would have to be shared")
         if step_noise is not None:
             raise ValueError("stitched windows take no step_noise: the noise of the frames two windows share would have to be shared")
-        if ex.guide is not None:
-            raise ValueError("a cond_fn guidance with stitch= is not built: per-window gradients disagree in the overlaps")
+        if ex.guide is not None and not isinstance(ex.guide, LongGuidance):
+            raise ValueError("a cond_fn guidance with stitch= is not built: per-window gradients disagree in the overlaps (LongGuidance "
+                             "evaluates the terms on the joined long motion)")
         ex.stitch.check(x.shape[0], x.shape[1])          # (B % S, 2 * ov <= L, the frames)
+        if ex.guide is not None and not ex.guide.same_geometry(ex.stitch):
+            raise ValueError("the LongGuidance was built on another Stitch than the chain's (windows, overlap, frames, length)")
+    elif isinstance(ex.guide, LongGuidance):
+        raise ValueError("LongGuidance guides the windows of a stitched chain: pass its Stitch as stitch=")
     if any(k in model_kwargs for k in COND_SWITCHES):
         raise NotImplementedError("condition switches (c_*_mask / c_*_erase) are training-time augmentations; "
                                   "p_sample_loop samples them step by step (p_sample_loop_progressive)")
@@ -627,16 +636,21 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 w.flags |= ffi.CMDM_CLIP_X0                  # per call: _stamp() rewrites the flags on the next _weights()
             cfg = ex.cfg
             term, term_keep, kind, kind_key = None, None, "none", None
+            gk_of = None                    # the description whose gk rows a range call sets
             if ex.guide is not None:
                 both = MotionGuidance(targets=ex.guide) if isinstance(ex.guide, JointTargets) else ex.guide
                 term, term_fm, term_keep = both.describe(x, model_kwargs, diffusion)
+                gk_of = term
                 if isinstance(both, ContactGuidance):      # a bare contact term keeps its own entry
                     kind, kind_key = "contact", (term.K, term.N, bool(term.h3d))
-                else:                                                # anything that carries targets: the sum's entry
+                else:                                                # anything that carries targets: the sum's entry (a LongGuidance: its own)
                     ct, tg = both.contact, both.targets
                     kind, kind_key = "motion", (None if ct is None else (ct.K, model_kwargs["c_pc_xyz"].shape[1]), None if tg is None else tg.K,
                                                 (ct or tg).joints is not None)
-                term.frame_mask = ffi.ptr(term_fm)          # the guidance masks by x_mask also where the model does not (mask_motion=False)
+                if isinstance(both, LongGuidance):         # no frame mask: validity is the geometry; gk rows per window, on its terms
+                    kind, gk_of, long_key = "long", term.terms.contents, kind_key + (term.frames,)
+                else:
+                    term.frame_mask = ffi.ptr(term_fm)      # the guidance masks by x_mask also where the model does not (mask_motion=False)
                 gk_rows = diffusion.guidance_rows(x.device, "mean" if ddim_eta is None and dpm_order is None else "x0", B)
             cond = self.condition_tokens(**model_kwargs)
             if tuple(cond.shape[:2]) != (B, w.n_cond):       # (e.g. a cloud of fewer points than contact_model.num_points: the loop reads n_cond rows per sample)
@@ -650,7 +664,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if ex.stitch is not None:          # sub-batches are cut over long motions: a window and its neighbour share one
                 st, st_keep = ex.stitch.describe(x.device)
                 nsub = max(1, min(nsub, B // ex.stitch.windows))
-                kind_key = (st.windows, st.overlap)
+                kind_key = (st.windows, st.overlap) + (long_key if kind == "long" else ())
             self._side_streams = ffi.stream_pool(x.device, nsub)          # process-wide pool (hardware queues are few: ffi.stream_pool)
             handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in self._side_streams[:nsub]])
             # ex.cfg (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)
@@ -685,8 +699,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
 
             def call(j0, j1, nz):       # executed steps j0..j1-1 = timestep indices n-j1 .. n-1-j0
                 lo = n - j1
-                if term is not None:          # the gk rows of the slice
-                    term.gk = gk_rows[lo:].data_ptr()
+                if gk_of is not None:         # the gk rows of the slice
+                    gk_of.gk = gk_rows[lo:].data_ptr()
                 step = dict(values, noise=nz, tmap=tables.tmap(lo), n_steps=j1 - j0, first_step=j0, **tables.named(lo))
                 ffi.check(getattr(lib, plan.entry)(*head, *fill(plan.slots, step), *tail), plan.entry)
 
@@ -813,7 +827,8 @@ class GuidedCMDM(nn.Module):
         """The guided native loop (afm_cmdm_cfg_sample_loop_range / afm_cmdm_cfg_ddim_loop_range; with ``impute``: the guided form of
         afm_cmdm_impute_loop_range; one scale per condition: afm_cmdm_cfg2_loop_range, every form; ``dpm_order``: the guided forms of
         afm_cmdm_dpm_loop_range; ``contact_guide``: the guided forms of afm_cmdm_guide_loop_range; ``stitch``: the guided forms of
-        afm_cmdm_stitch_loop_range, each window combined with its own scales): CMDM.afm_native_loop's arguments."""
+        afm_cmdm_stitch_loop_range, each window combined with its own scales; with a LongGuidance as ``contact_guide``:
+        afm_cmdm_long_guide_loop_range): CMDM.afm_native_loop's arguments."""
         self._no_switches(model_kwargs)
         if self.model.training:
             raise RuntimeError("GuidedCMDM samples in eval mode: call model.eval() first")

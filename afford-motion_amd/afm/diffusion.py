@@ -28,7 +28,7 @@ import torch
 
 from . import ffi, ops
 from .cmdm import COND_SWITCHES, LoopExtras
-from .guidance import CondFnError, ContactGuidance, Impute, JointTargets, MotionGuidance, Stitch, _guide_mask          # noqa: F401 (kept in this namespace)
+from .guidance import CondFnError, ContactGuidance, Impute, JointTargets, LongGuidance, MotionGuidance, Stitch, _guide_mask          # noqa: F401 (kept in this namespace)
 
 
 def betas_for_alpha_bar(num_diffusion_timesteps: int, alpha_bar: Callable[[float], float], max_beta: float = 0.999):
@@ -385,9 +385,12 @@ class GaussianDiffusion:
                              "windows share would have to be shared")
         if step_noise is not None:
             raise ValueError(f"{who}: stitched windows take no step_noise - the noise of the frames two windows share would have to be shared")
-        if cond_fn is not None:
+        if cond_fn is not None and not isinstance(cond_fn, LongGuidance):
             raise ValueError(f"{who}: cond_fn with stitch= is not built - a gradient through the h3d recovery integrates from each window's "
-                             "own origin, so per-window gradients disagree in the overlaps")
+                             "own origin, so per-window gradients disagree in the overlaps (LongGuidance evaluates the terms on the joined "
+                             "long motion)")
+        if cond_fn is not None and not cond_fn.same_geometry(stitch):
+            raise ValueError(f"{who}: the LongGuidance was built on another Stitch than the chain's (windows, overlap, frames, length)")
         if getattr(getattr(model, "model", model), "arch", None) == "trans_dec":
             raise ValueError(f"{who}: stitched windows are built for arch='trans_enc' only, not 'trans_dec'")
         if len(shape) != 3:
@@ -417,7 +420,7 @@ class GaussianDiffusion:
         ``noise`` replaces the `randn_like` draw, otherwise Philox keyed by (seed, sample_index0 + b, step).  ``cond_fn``: condition_score
         (:372-394), which is a shift of the final pred_xstart - after ``denoised_fn`` and the clamp - x0' = x0 + ((1 - abar_t) /
         sqrt(abar_t)) * grad (ops.guide_step's float32 order); the update runs on x0', which is the returned "pred_xstart"."""
-        if stitch is not None:          # (``stitch``: an afm.diffusion.Stitch - x holds windows; eta = 0 only, no cond_fn, no noise)
+        if stitch is not None:          # (``stitch``: an afm.diffusion.Stitch - x holds windows; eta = 0 only, no cond_fn but a LongGuidance, no noise)
             self._check_stitch(stitch, model, x.shape, cond_fn, noise, eta, "ddim_sample")
         tab = self.tables(x.device)
         rows = self.ddim_tables(x.device, eta)
@@ -464,7 +467,8 @@ class GaussianDiffusion:
         """DDIM sampling (reference gaussian_diffusion.py:626-670).  The keyword-only extras are p_sample_loop's; denoisers exposing
         ``afm_native_loop`` run the whole chain natively (the DDIM update fused where the DDPM update is) under the same conditions.
         ``stitch`` (an afm.diffusion.Stitch): the batch rows are overlapping windows of long motions; eta must be 0, ``step_noise`` and
-        ``cond_fn`` are refused; a loop that names ``stitch`` (CMDM `trans_enc`, GuidedCMDM: afm_cmdm_stitch_loop_range) stays native."""
+        every ``cond_fn`` but a `LongGuidance` on the same geometry are refused; a loop that names ``stitch`` (CMDM `trans_enc`, GuidedCMDM:
+        afm_cmdm_stitch_loop_range; with a `LongGuidance`: afm_cmdm_long_guide_loop_range) stays native."""
         return self._sample_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
                                  step_noise, seed, sample_index0, snapshots, ddim_eta=float(eta), stitch=stitch)
 
@@ -525,13 +529,13 @@ class GaussianDiffusion:
         """The keywords of ``native(...)`` for this chain, or None: sample step by step.  Native: the denoiser has an ``afm_native_loop``
         and nothing needs the host between steps - no rescaled timesteps, no condition switch in ``model_kwargs``, no generic
         ``denoised_fn`` / ``cond_fn``.  A ``denoised_fn`` that is an `Impute` stays native where the loop names ``impute``, DPM-Solver++
-        where it names ``dpm_order``; a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets` or a `MotionGuidance`, and a `Stitch`,
+        where it names ``dpm_order``; a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets`, a `MotionGuidance` or (stitched) a `LongGuidance`, and a `Stitch`,
         where it names ``contact_guide`` / ``stitch`` (GuidedCMDM) or - the plain CMDM, whose public keywords stay the CDM's - takes a
         private ``_guidance`` bundle (afm.cmdm.LoopExtras)."""
         if native is None or self.rescale_timesteps or any(k in (model_kwargs or {}) for k in COND_SWITCHES):
             return None
         impute = denoised_fn if isinstance(denoised_fn, Impute) else None
-        guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance)) else None
+        guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance, LongGuidance)) else None
         if (denoised_fn is not None and impute is None) or (cond_fn is not None and guide is None):
             return None
         kw, private = {}, {}
@@ -562,6 +566,8 @@ class GaussianDiffusion:
         """p_sample_loop (ddim_eta None) / ddim_sample_loop / dpm_solver_sample_loop (dpm_order not None): the denoiser's
         ``afm_native_loop`` where `_native_keywords` finds the chain native, else the progressive generator."""
         native = getattr(model, "afm_native_loop", None)
+        if stitch is None and isinstance(cond_fn, LongGuidance):
+            raise ValueError("LongGuidance guides the windows of a stitched chain: pass its Stitch as stitch=")
         if stitch is not None:          # a stitched chain (ddim_sample_loop / dpm_solver_sample_loop): native where the loop names ``stitch``
             self._check_stitch(stitch, model, shape, cond_fn, step_noise, ddim_eta, "dpm_solver_sample_loop" if dpm_order is not None else "ddim_sample_loop")
         extra = self._native_keywords(native, clip_denoised, denoised_fn, cond_fn, model_kwargs, snapshots, ddim_eta, dpm_order, stitch)

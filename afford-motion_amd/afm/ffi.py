@@ -200,6 +200,8 @@ class GuideStepArgs(C.Structure):
 GUIDE_MAX_JOINTS = 16
 H3D_JOINTS = 22                   # joints of the HumanML3D skeleton
 H3D_COLS = 67                     # the feature columns the joint recovery reads: 0..66
+H3D_SCAN_ROWS = 7                 # per-frame LDS rows of the joint recovery and of its adjoint
+GUIDE_LDS_BYTES = 60 * 1024       # the LDS the guidance kernels stage into
 
 
 class H3dLayout(C.Structure):
@@ -241,6 +243,12 @@ class StitchStepArgs(C.Structure):
                 ("mask", C.c_void_p), ("x_t", c_f32p), ("x_next", c_f32p), ("x0_out", c_f32p), ("ddim", C.POINTER(DdimRows)),
                 ("dpm", C.POINTER(DpmRows)), ("x0_prev", c_f32p), ("stitch", C.POINTER(Stitch)), ("clip", i32), ("B", i32), ("L", i32),
                 ("D", i32)]
+
+
+class LongGuide(C.Structure):
+    """afm_long_guide (v7-additive): the guidance of stitched long motions - the terms (scale rows [G], long-form targets, q / c per window),
+    the stitch and the long motion's frames F."""
+    _fields_ = [("terms", C.POINTER(MotionGuide)), ("stitch", Stitch), ("frames", i32)]
 
 
 CFG_FORCE_MASKED = 0x1
@@ -334,6 +342,15 @@ EXPORTS = {
                                              C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p, C.c_void_p,
                                              C.POINTER(Stitch), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                              C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_long_guidance_workspace_bytes": (i64, [C.POINTER(LongGuide), i32, i32, i32]),
+    "afm_long_guidance": (C.c_int, [C.POINTER(LongGuide), c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, i32, i32, i32, C.c_void_p, i64, C.c_void_p]),
+    "afm_stitch_guide_step": (C.c_int, [C.POINTER(StitchStepArgs), c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "afm_cmdm_long_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
+                                                       C.POINTER(LongGuide)]),
+    "afm_cmdm_long_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                                 C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p, C.c_void_p,
+                                                 C.POINTER(LongGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                                 C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

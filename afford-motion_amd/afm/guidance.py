@@ -1,5 +1,6 @@
 """What a sampling chain is conditioned on besides the denoiser's own inputs: known values (`Impute`), overlapping windows of a long
-motion (`Stitch`), and the analytic ``cond_fn`` guidance terms (`ContactGuidance`, `JointTargets`, their sum `MotionGuidance`).  The
+motion (`Stitch`), and the analytic ``cond_fn`` guidance terms (`ContactGuidance`, `JointTargets`, their sum `MotionGuidance`, and
+`LongGuidance`, the terms on the joined long motion of a stitched chain).  The
 samplers of afm.diffusion take them, the native loops of afm.cmdm / afm.cdm read their descriptions; afm.diffusion re-exports every name
 (``afm.diffusion.Stitch is afm.guidance.Stitch``).  This module imports `ffi` and `ops` only: of a diffusion object it reads
 ``timestep_map`` and nothing else."""
@@ -95,7 +96,7 @@ class Stitch:
     Both windows evaluate the same expression on the same operands and get the same bits: with shared frames starting from shared noise
     (`x_T`) and a deterministic update (DDIM eta = 0, DPM-Solver++(2M)) the shared frames stay bit-identical in both windows at every
     step, and `join` of the result is the long motion read from either side.  Order inside a step: the guidance combine (each window its
-    own scales) -> blend -> ``denoised_fn`` / `Impute` -> clamp -> update.
+    own scales) -> blend -> ``denoised_fn`` / `Impute` -> clamp -> ``x0 += gk * grad`` (a `LongGuidance` as ``cond_fn``) -> update.
 
     ``ddim_sample_loop(..., stitch=)`` and ``dpm_solver_sample_loop(..., stitch=)`` take it; a CMDM `trans_enc` or a GuidedCMDM runs the
     whole chain natively (afm_cmdm_stitch_loop_range).  A per-window `Impute` built by hand that disagrees in an overlap is the caller's
@@ -410,9 +411,10 @@ class ContactGuidance(_JointTerm):
         self.sigma = float(sigma)
         return ()
 
-    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None) -> tuple:
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, long=None) -> tuple:
         """(afm_contact_guide of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).  With
-        ``diffusion``: first_guided set for a chain on it (the loops)."""
+        ``diffusion``: first_guided set for a chain on it (the loops).  ``long`` = (G, F), `LongGuidance`'s: x holds the windows of G long
+        motions - q / c stay per window, scale and to_scene are per long motion, x_mask is not read."""
         self._check_sample(x)
         for name in ("c_pc_xyz", "c_pc_contact"):
             if name not in model_kwargs:
@@ -421,12 +423,14 @@ class ContactGuidance(_JointTerm):
         q, c = model_kwargs["c_pc_xyz"], model_kwargs["c_pc_contact"]
         if q.dim() != 3 or q.shape[0] != B or q.shape[2] != 3 or tuple(c.shape) != (B, q.shape[1], K):
             raise ValueError(f"ContactGuidance: c_pc_xyz must be [{B}, N, 3] and c_pc_contact [{B}, N, {K}], got {tuple(q.shape)} and {tuple(c.shape)}")
-        scale = scale_row(self.scale, B, x.device, self._who)
-        ts, stride = self._to_scene_on(B, x.device)
+        rows = B if long is None else long[0]
+        scale_fits(self.scale, rows, self._who)
+        ts, stride = self._to_scene_on(rows, x.device)
         ffi.require_gpu(x, q, c)
+        scale = scale_row(self.scale, rows, x.device, self._who)
         q, c = ffi.f32c(q), ffi.f32c(c)
         mean, std = self._on(x.device)
-        fm = _guide_mask(x, model_kwargs, self._who)
+        fm = _guide_mask(x, model_kwargs, self._who) if long is None else None
         g = ffi.ContactGuide()
         lay = self._fill(g, mean, std, scale, ts, stride, diffusion)
         g.q, g.c, g.N, g.sigma = q.data_ptr(), c.data_ptr(), q.shape[1], self.sigma
@@ -491,17 +495,19 @@ class JointTargets(_JointTerm):
         self.target, self.weight = ffi.f32c(target.detach()), ffi.f32c(weight.detach())
         return self.target, self.weight
 
-    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, shared=None) -> tuple:
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, shared=None, long=None) -> tuple:
         """(afm_joint_targets of this sample tensor, x_mask as uint8 or None, what must stay alive with it).  ``shared``: the (mean, std,
-        to_scene, stride) device tensors of the contact term this one is summed with - a sum names one set of them."""
+        to_scene, stride) device tensors of the contact term this one is summed with - a sum names one set of them.  ``long`` = (G, F),
+        `LongGuidance`'s: x holds the windows of G long motions of F frames, which is what target / weight / scale / to_scene describe;
+        x_mask is not read."""
         who = self._who
         self._check_sample(x)
-        B, L, K = x.shape[0], x.shape[1], self.K
+        B, L, K = (x.shape[0], x.shape[1], self.K) if long is None else (long[0], long[1], self.K)
         if tuple(self.target.shape) != (B, L, K, 3):
             raise ValueError(f"{who}: target is {tuple(self.target.shape)} and weight {tuple(self.weight.shape)}, the sample needs "
                              f"[{B}, {L}, {K}, 3] and [{B}, {L}, {K}]")
         scale_fits(self.scale, B, who)
-        fm = _guide_mask(x, model_kwargs, who)
+        fm = _guide_mask(x, model_kwargs, who) if long is None else None
         ts, stride = self._to_scene_on(B, x.device)          # (checked against the batch before anything touches the device)
         ffi.require_gpu(x)
         mean, std, target, weight = self._on(x.device)
@@ -585,3 +591,126 @@ class MotionGuidance:
     def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
         g, fm, keep = self.describe(x, model_kwargs)
         return ops.motion_guidance(g, x, fm, grad=False, energy=True)[1:]
+
+
+class LongGuidance:
+    """A ``cond_fn`` for chains that run with ``stitch=``: a `ContactGuidance` and / or a `JointTargets` evaluated on the JOINED long motion
+    (afm_long_guidance, HIP), so a long motion is pulled to its own contact maps, and a root path or a target may lie beyond the first
+    window - on HumanML3D features the root is integrated from long frame 0, not from each window's own origin.  In a stitched chain the
+    shared frames are bit-identical in both windows at every step, so the windows join into one long x_t; the gradient goes back to the
+    windows as one value per long frame, both copies of a shared frame receive the same bits and the stitching invariant survives.
+
+    ``stitch``: a `Stitch` with S windows, overlap ov and F frames; hop = L - ov.  Window w of long motion g is batch row b = g * S + w and
+    holds the long frames a_w = w * hop .. a_w + L - 1, clipped to < F.  ``contact``: a `ContactGuidance`, column form or ``.h3d``.
+    ``targets``: a `JointTargets` whose ``target`` / ``weight`` are in the long form [G, F, K, 3] / [G, F, K].  The two terms must agree as
+    `MotionGuidance` requires (same mean / std, same form, same ``to_scene``).  ``scale`` of each term is a float or a [G] tensor, one per
+    long motion - a [G * S] tensor is a ValueError.  ``to_scene`` is [3, 4] or [G, 3, 4].  ``x_mask`` is not read: validity is the geometry
+    - long frames 0 .. F-1 are valid, and the padded tail of a last window does not exist in the long form.  ``c_pc_xyz`` [G * S, N, 3] and
+    ``c_pc_contact`` [G * S, N, K] are read from ``model_kwargs`` per window: each window keeps its own map.
+
+    ``guide(x, t, **model_kwargs)`` takes x [G * S, L, D] and returns grad [G * S, L, D] float32:
+
+      1. long = `Stitch.join` (x) [G, F, D]; the join rule stands: a shared frame is read from the later window.
+      2. P[g,f,k,:] are the positions of ``long`` exactly as the existing kernels compute them - the de-normalised columns, or the h3d
+         recovery over all F frames.  float32, every operation in its present order.
+      3. Targets term: the existing afm_motion_guidance targets launches on (long, B = G, L = F) - by definition ``targets(long, ...)``.
+      4. Contact term, for each window b: d2[b,n,k] = min over the window's long frames f of |P[g,f,k] - q[b,n]|^2, summed
+         (dx*dx + dy*dy) + dz*dz; f* the first such frame, stored as a long frame index; chat and w as `ContactGuidance`;
+         E_b = sum (chat - c)^2 / (N K) with the existing partial and serial sums; S_b[f,k,:] = sum over {n: f*(b,n,k) = f} of w * (p - q)
+         in the existing frame_sum order.
+      5. Per long frame the windows' sums are joined: a frame in one window takes that window's sum as is, a frame in two windows takes
+         S_earlier + S_later - one rounded addition, earlier window first.
+      6. Column form: grad_long[g,f,col+a] = ((scale[g] * coef) * std_a) * S.  h3d form: the joined S goes through the existing adjoint
+         kernel on (B = G, L = F) with scale[g].
+      7. The targets' launch adds its complete result to what the contact term wrote, as `MotionGuidance` does.
+      8. grad = `Stitch.windows_of` (grad_long): the padded tail is exact zeros, both copies of a shared frame hold the same bits.
+
+    ``energies(x, **kw)`` returns (E_contact [G], E_targets [G]) (None for a term that is not set); E_contact[g] is the serial sum of its
+    windows' E_b in window order.  ``t_start`` and ``first_guided`` work per term as in `MotionGuidance`; t of long motion g is t[g * S].
+    ValueError before anything runs: a batch or L that does not match ``stitch``, long-form shapes that do not match, F beyond what 7 * F
+    floats of LDS allow for the h3d recovery, a term with a per-window scale.
+
+    Handed as ``cond_fn`` to ``ddim_sample_loop(..., stitch=)`` / ``dpm_solver_sample_loop(..., stitch=)`` with the same `Stitch` geometry; a
+    CMDM `trans_enc` or a GuidedCMDM runs the whole chain natively (afm_cmdm_long_guide_loop_range).  Launches per guided step: join + the
+    contact term's 2 (h3d: 4) + the targets' 1 (h3d: 3) + windows."""
+
+    def __init__(self, stitch: Stitch, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None):
+        if not isinstance(stitch, Stitch):
+            raise TypeError(f"LongGuidance: stitch must be a Stitch, not {type(stitch).__name__}")
+        self.stitch = stitch
+        self._sum = MotionGuidance(contact, targets)          # (the terms' types and their agreement, checked once)
+        self.contact, self.targets = contact, targets
+
+    @property
+    def t_start(self):
+        return self._sum.t_start
+
+    def first_guided(self, diffusion) -> int:
+        return self._sum.first_guided(diffusion)
+
+    def same_geometry(self, stitch: Stitch) -> bool:
+        """whether a chain's `Stitch` cuts the long motions as this guidance's does"""
+        a, b = self.stitch, stitch
+        return a is b or (a.windows, a.overlap, a.frames, a.length) == (b.windows, b.overlap, b.frames, b.length)
+
+    def check(self, x: torch.Tensor) -> tuple:
+        """the windows x [G * S, L, D] against the stitch and the terms, on the host (ValueError); -> (G, F)"""
+        who = "LongGuidance"
+        if x.dim() != 3:
+            raise ValueError(f"{who}: the windows are [G * S, L, D], got {tuple(x.shape)}")
+        B, L, _ = x.shape
+        F = self.stitch.check(B, L)
+        S = self.stitch.windows
+        G = B // S
+        for term in (self.contact, self.targets):
+            if term is None:
+                continue
+            term._check_sample(x)
+            if isinstance(term.scale, torch.Tensor) and term.scale.numel() != G:
+                if S > 1 and term.scale.numel() == B:
+                    raise ValueError(f"{who}: the {term._NAME}'s `scale` holds one value per window ({B}); a long motion has one scale, [{G}]")
+                raise ValueError(f"{who}: the {term._NAME}'s `scale` holds {term.scale.numel()} values for {G} long motions")
+            if term.joints is not None and ffi.H3D_SCAN_ROWS * F * 4 > ffi.GUIDE_LDS_BYTES:
+                raise ValueError(f"{who}: the joint recovery keeps {ffi.H3D_SCAN_ROWS} * F floats in LDS - {F} frames are beyond "
+                                 f"{ffi.GUIDE_LDS_BYTES // (4 * ffi.H3D_SCAN_ROWS)}")
+            if term.to_scene is not None and term.to_scene.dim() == 3 and term.to_scene.shape[0] != G:
+                raise ValueError(f"{who}: to_scene holds {term.to_scene.shape[0]} matrices for {G} long motions")
+        tg = self.targets
+        if tg is not None and tuple(tg.target.shape) != (G, F, tg.K, 3):
+            raise ValueError(f"{who}: the targets are long-form - target [{G}, {F}, {tg.K}, 3] and weight [{G}, {F}, {tg.K}], got "
+                             f"{tuple(tg.target.shape)} and {tuple(tg.weight.shape)}")
+        return G, F
+
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None) -> tuple:
+        """(afm_long_guide of these windows and conditions, None - no frame mask is read -, what must stay alive with it).  With
+        ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
+        long = self.check(x)
+        cg = tg = shared = None
+        keep = []
+        if self.contact is not None:
+            cg, _, ck = self.contact.describe(x, model_kwargs, diffusion, long=long)
+            keep.append((cg, ck))
+            shared = (ck[2], ck[3], ck[7], cg.h3d.contents.to_scene_stride if cg.h3d else 0)
+        if self.targets is not None:
+            tg, _, tk = self.targets.describe(x, model_kwargs, diffusion, shared=shared, long=long)
+            keep.append((tg, tk))
+        m = ffi.MotionGuide()
+        if cg is not None:
+            m.contact = C.pointer(cg)
+        if tg is not None:
+            m.targets = C.pointer(tg)
+        st, st_keep = self.stitch.describe(x.device)
+        g = ffi.LongGuide()
+        g.terms, g.stitch, g.frames = C.pointer(m), st, long[1]
+        return g, None, (m, keep, st_keep)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        g, _, keep = self.describe(x, model_kwargs)
+        return ops.long_guidance(g, x, t.to(x.device) if self._timed() else None)[0]
+
+    def _timed(self) -> bool:
+        return any(q is not None and q.t_start is not None for q in (self.contact, self.targets))
+
+    def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
+        g, _, keep = self.describe(x, model_kwargs)
+        return ops.long_guidance(g, x, grad=False, energy=True)[1:]

@@ -779,51 +779,77 @@ def stitch_step(x0: torch.Tensor, x_t: torch.Tensor, stitch, *, x0_a: Optional[t
     with the neighbour's scales - impute with ``known`` / ``mask``, the clamp to [-1, 1] if ``clip``, then the ddim_step expression with
     ``ddim`` = (a, b, c, d) (no noise term) or the dpm_step expression with ``dpm`` = (a, b, c) and ``prev``; ``x0_out`` (dpm only)
     receives the final x0.  Equal, bit for bit, to the chain of separate launches.  ``out`` may be ``x_t``."""
+    return _stitch_update("stitch_step", x0, x_t, stitch, x0_a, x0_u, scale, scale2, known, mask, ddim, dpm, prev, clip, out, x0_out)
+
+
+def stitch_guide_step(x0: torch.Tensor, x_t: torch.Tensor, stitch, *, grad: torch.Tensor, gk: torch.Tensor, x0_a: Optional[torch.Tensor] = None,
+                      x0_u: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None, scale2: Optional[torch.Tensor] = None,
+                      known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, ddim=None, dpm=None,
+                      prev: Optional[torch.Tensor] = None, clip: bool = False, out: Optional[torch.Tensor] = None,
+                      x0_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`stitch_step` with a cond_fn gradient term, one launch (afm_stitch_guide_step): combine -> blend -> select -> clamp ->
+    ``x0 += gk[b] * grad`` (the product rounded, then the sum) -> update.  ``grad`` [B, L, D] and ``gk`` [B] are both required; ``x0_out``
+    (DDIM rows too) receives the shifted x0.  Equal, bit for bit, to `stitch_blend` -> `impute` -> clamp -> `guide_step`."""
+    if grad is None or gk is None:
+        raise ValueError("stitch_guide_step: grad= and gk= are both required")
+    return _stitch_update("stitch_guide_step", x0, x_t, stitch, x0_a, x0_u, scale, scale2, known, mask, ddim, dpm, prev, clip, out, x0_out, grad, gk)
+
+
+def _stitch_update(who, x0, x_t, stitch, x0_a, x0_u, scale, scale2, known, mask, ddim, dpm, prev, clip, out, x0_out, grad=None, gk=None):
+    """what `stitch_step` and `stitch_guide_step` share: the checks, the afm_stitch_step_args and the launch"""
     if (ddim is None) == (dpm is None):
-        raise ValueError("stitch_step: exactly one of ddim= / dpm= rows")
+        raise ValueError(f"{who}: exactly one of ddim= / dpm= rows")
     if (known is None) != (mask is None):
-        raise ValueError("stitch_step: known= and mask= go together")
+        raise ValueError(f"{who}: known= and mask= go together")
     if ddim is not None and len(ddim) > 4 and ddim[4] is not None:
-        raise ValueError("stitch_step: rows with a noise term are refused - the step noise of shared frames would have to be shared")
+        raise ValueError(f"{who}: rows with a noise term are refused - the step noise of shared frames would have to be shared")
     lib = ffi.load()
-    ffi.require_gpu(x0, x_t, prev)
+    ffi.require_gpu(x0, x_t, prev, grad)
     x0, x_t = ffi.f32c(x0), ffi.f32c(x_t)
-    st, keep = _stitch_desc(stitch, x0, "stitch_step")
+    st, keep = _stitch_desc(stitch, x0, who)
     keep = [keep]
     B, L, D = x0.shape
     if x_t.shape != x0.shape:
-        raise ValueError(f"stitch_step: x_t {tuple(x_t.shape)} must have x0's shape {tuple(x0.shape)}")
+        raise ValueError(f"{who}: x_t {tuple(x_t.shape)} must have x0's shape {tuple(x0.shape)}")
     out = torch.empty_like(x0) if out is None else out
     a = ffi.StitchStepArgs()
     a.x0_c, a.x_t, a.x_next, a.stitch = x0.data_ptr(), x_t.data_ptr(), out.data_ptr(), C.pointer(st)
-    for name, t in (("x0_a", x0_a), ("x0_u", x0_u), ("known", known), ("x0_prev", prev)):
+    extra = {}                      # grad / gk: arguments of afm_stitch_guide_step, not fields of the struct
+    for name, t in (("x0_a", x0_a), ("x0_u", x0_u), ("known", known), ("x0_prev", prev), ("grad", grad)):
         if t is not None:
             t = ffi.f32c(t)
             if t.shape != x0.shape:
-                raise ValueError(f"stitch_step: {name} {tuple(t.shape)} must have x0's shape {tuple(x0.shape)}")
+                raise ValueError(f"{who}: {name} {tuple(t.shape)} must have x0's shape {tuple(x0.shape)}")
             keep.append(t)
-            setattr(a, name, t.data_ptr())
-    for name, t in (("scale", scale), ("scale2", scale2)):
+            if name == "grad":
+                extra[name] = t.data_ptr()
+            else:
+                setattr(a, name, t.data_ptr())
+    for name, t in (("scale", scale), ("scale2", scale2), ("gk", gk)):
         if t is not None:
             t = ffi.f32c(t)
             if t.numel() != B:
-                raise ValueError(f"stitch_step: {name} must hold one value per sample ({B}), got {tuple(t.shape)}")
+                raise ValueError(f"{who}: {name} must hold one value per sample ({B}), got {tuple(t.shape)}")
             keep.append(t)
-            setattr(a, name, t.data_ptr())
+            if name == "gk":
+                extra[name] = t.data_ptr()
+            else:
+                setattr(a, name, t.data_ptr())
     if mask is not None:
         mask = _mask_u8(mask)
         if mask.shape != x0.shape:
-            raise ValueError(f"stitch_step: mask {tuple(mask.shape)} must have x0's shape {tuple(x0.shape)}")
+            raise ValueError(f"{who}: mask {tuple(mask.shape)} must have x0's shape {tuple(x0.shape)}")
         a.mask = mask.data_ptr()
     if x0_out is not None:
-        if dpm is None:
-            raise ValueError("stitch_step: x0_out goes with dpm= rows")
+        if dpm is None and grad is None:
+            raise ValueError(f"{who}: x0_out goes with dpm= rows")
         if x0_out.dtype != torch.float32 or x0_out.shape != x0.shape or not x0_out.is_contiguous() or x0_out.device != x0.device:
-            raise ValueError(f"stitch_step: x0_out must be a contiguous float32 tensor of x0's shape {tuple(x0.shape)} on {x0.device}")
-        a.x0_out = x0_out.data_ptr()
+            raise ValueError(f"{who}: x0_out must be a contiguous float32 tensor of x0's shape {tuple(x0.shape)} on {x0.device}")
+        if dpm is not None:
+            a.x0_out = x0_out.data_ptr()
     rows = [ffi.f32c(r) for r in (ddim[:4] if ddim is not None else dpm)]
     if any(r.numel() != B for r in rows):
-        raise ValueError(f"stitch_step: the rows hold one value per sample ({B})")
+        raise ValueError(f"{who}: the rows hold one value per sample ({B})")
     if ddim is not None:
         rr = ffi.DdimRows(*[r.data_ptr() for r in rows], None)
         a.ddim = C.pointer(rr)
@@ -832,5 +858,32 @@ def stitch_step(x0: torch.Tensor, x_t: torch.Tensor, stitch, *, x0_a: Optional[t
         a.dpm = C.pointer(rr)
     keep += rows + [rr]
     a.clip, a.B, a.L, a.D = int(bool(clip)), B, L, D
-    ffi.check(lib.afm_stitch_step(C.byref(a), ffi.stream_of(x0)), "afm_stitch_step")
+    if grad is not None:
+        ffi.check(lib.afm_stitch_guide_step(C.byref(a), extra["grad"], extra["gk"], ffi.ptr(x0_out), ffi.stream_of(x0)), "afm_stitch_guide_step")
+    else:
+        ffi.check(lib.afm_stitch_step(C.byref(a), ffi.stream_of(x0)), "afm_stitch_step")
     return out
+
+
+def long_guidance(guide: "ffi.LongGuide", x: torch.Tensor, t: Optional[torch.Tensor] = None, *, grad: bool = True, energy: bool = False):
+    """afm_long_guidance of a filled description (afm.guidance.LongGuidance builds it): -> (grad [G * S, L, D] or None, the contact term's
+    energy [G] or None, the targets' energy [G] or None) of the windows x [G * S, L, D]: the windows joined, the terms evaluated on the long
+    motion, the gradient handed back to the windows.  ``t`` [G * S] int64 or None (long motion g has t[g * S]).  No atomics; the workspace is
+    allocated per call."""
+    lib = ffi.load()
+    ffi.require_gpu(x, t)
+    x = ffi.f32c(x)
+    B, L, D = x.shape
+    G = B // max(int(guide.stitch.windows), 1)
+    terms = guide.terms.contents
+    tt = None if t is None else t.to(dtype=torch.int64).contiguous()
+    g = torch.empty_like(x) if grad else None
+    ec = torch.empty(G, dtype=torch.float32, device=x.device) if energy and terms.contact else None
+    et = torch.empty(G, dtype=torch.float32, device=x.device) if energy and terms.targets else None
+    nbytes = int(lib.afm_long_guidance_workspace_bytes(C.byref(guide), B, L, D))
+    if nbytes < 0:
+        ffi.check(nbytes, "afm_long_guidance_workspace_bytes")
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ffi.check(lib.afm_long_guidance(C.byref(guide), x.data_ptr(), ffi.ptr(tt), ffi.ptr(g), ffi.ptr(ec), ffi.ptr(et), B, L, D, ws.data_ptr(),
+                                    ws.numel(), ffi.stream_of(x)), "afm_long_guidance")
+    return g, ec, et

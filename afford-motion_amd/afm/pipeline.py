@@ -15,7 +15,7 @@ import torch
 
 from . import dist as adist
 from .cmdm import GuidedCMDM
-from .guidance import MotionGuidance, Stitch
+from .guidance import LongGuidance, MotionGuidance, Stitch
 
 
 def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: torch.Tensor, xyz: torch.Tensor, frames: int,
@@ -90,7 +90,7 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
 def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: torch.Tensor, xyz: torch.Tensor, frames: int, overlap: int,
                        sampler: str = "dpm++", guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None, sigma: float = 0.8,
                        contact_mean: float = 0.0, contact_std: float = 1.0, seed: int = 0,
-                       sample_index0: int = 0) -> Dict[str, torch.Tensor]:
+                       sample_index0: int = 0, contact_guidance=None, joint_targets=None) -> Dict[str, torch.Tensor]:
     """One scene, one thing after another: G long motions of ``frames`` frames, each S windows with a text of its own, sampled as
     ``G * S`` overlapping windows stitched inside the native loop (afm.diffusion.Stitch; "walk to the sofa, sit down, stand up again" is
     S = 3).  text_feat [G, S, text_dim], xyz [G, N, 3] ->
@@ -103,7 +103,10 @@ def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: t
     of a last window, if any, is masked.  ``sampler``: "dpm++" (dpm_solver_sample_loop) or "ddim" (ddim_sample_loop, eta = 0) on the spaced
     process of each diffusion - both deterministic, which is what keeps shared frames bit-identical in both windows.
     ``guidance_scale``: as `two_stage_sample`'s, a [G * S] tensor giving every window a scale of its own.  ``motion_impute``: an
-    afm.diffusion.Impute in the LONG form ([G, frames, D]); it is cut into windows consistently (`Stitch.impute`)."""
+    afm.diffusion.Impute in the LONG form ([G, frames, D]); it is cut into windows consistently (`Stitch.impute`).
+    ``contact_guidance`` (a `ContactGuidance`) / ``joint_targets`` (a `JointTargets` in the LONG form, target [G, frames, K, 3]): wrapped
+    into one afm.diffusion.LongGuidance on this call's Stitch and handed to stage 2 as its ``cond_fn`` - the terms are evaluated on the
+    joined long motion against the stage's own ``cond``, each window with its own contact map; their scales are floats or [G] tensors."""
     if sampler not in ("dpm++", "ddim"):
         raise ValueError(f"long_motion_sample: sampler must be 'dpm++' or 'ddim' (a deterministic update), not {sampler!r}")
     if text_feat.dim() != 3 or xyz.dim() != 3 or xyz.shape[0] != text_feat.shape[0] or xyz.shape[2] != 3:
@@ -114,9 +117,12 @@ def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: t
             raise ValueError(f"guidance_drop {sorted(dropped)} contradicts the conditions of the guidance_scale mapping {list(guidance_scale)}")
     G, S, N = text_feat.shape[0], text_feat.shape[1], xyz.shape[1]
     stitch = Stitch(S, overlap, frames)
+    guide = None if contact_guidance is None and joint_targets is None else LongGuidance(stitch, contact_guidance, joint_targets)
     L, B, dev = stitch.length, G * S, xyz.device
     if motion_impute is not None and tuple(motion_impute.shape[:2]) != (G, frames):          # (refused before the first stage runs)
         raise ValueError(f"long_motion_sample: motion_impute is the long form [{G}, {frames}, D], got {motion_impute.shape}")
+    if joint_targets is not None and tuple(joint_targets.target.shape[:2]) != (G, frames):          # (likewise)
+        raise ValueError(f"long_motion_sample: joint_targets is the long form, target [{G}, {frames}, K, 3], got {tuple(joint_targets.target.shape)}")
     x_mask = stitch.x_mask(G, dev, model=amdm)
     text = text_feat.reshape(B, text_feat.shape[2])
     cloud = xyz[:, None].expand(G, S, N, 3).reshape(B, N, 3)
@@ -133,6 +139,6 @@ def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: t
     imp = None if motion_impute is None else stitch.impute(motion_impute.known, motion_impute.mask)
     if guidance_scale is not None:
         amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
-    windows = loop(amdm_diffusion, amdm, (B, L, amdm.motion_dim), clip_denoised=False, denoised_fn=imp, model_kwargs=amdm_kw, seed=seed + 1,
-                   sample_index0=sample_index0, stitch=stitch)
+    windows = loop(amdm_diffusion, amdm, (B, L, amdm.motion_dim), clip_denoised=False, denoised_fn=imp, cond_fn=guide, model_kwargs=amdm_kw,
+                   seed=seed + 1, sample_index0=sample_index0, stitch=stitch)
     return {"contact": contact.reshape(G, S, N, -1), "cond": cond, "motion": stitch.join(windows), "windows": windows}

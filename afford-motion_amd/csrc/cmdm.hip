@@ -505,6 +505,7 @@ struct LoopCall {
     afm_motion_guide guide = {};      // guided loop: the terms' descriptions of the whole batch (neither term set: none)
     bool guided() const { return guide.contact || guide.targets; }
     afm_stitch stitch = {};           // stitched loop: the batch is windows of long motions (windows == 0: not stitched)
+    const afm_long_guide* lguide = nullptr;      // long-guided stitched loop: `guide` holds its terms, `stitch` its stitch
     bool stitched() const { return stitch.windows > 0; }
 };
 
@@ -549,7 +550,8 @@ struct SubBatch : SubRange {
 };
 
 // carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
-int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist, const afm_motion_guide* guide = nullptr) {
+int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist, const afm_motion_guide* guide = nullptr,
+                  const afm_long_guide* lguide = nullptr) {
     sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
     int64_t off = sb->ws.bytes;
     for (int i = 0; i < g.n; ++i) {
@@ -568,7 +570,8 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
         sb->ggrad = base ? (float*)(base + off) : nullptr;
         off += align256((int64_t)sb->count * L * w.motion_dim * 4);
         sb->gws = base ? base + off : nullptr;
-        sb->gws_bytes = afm_motion_guide_workspace_bytes(guide, sb->count, L, w.motion_dim);
+        sb->gws_bytes = lguide ? afm_long_guide_workspace_bytes(lguide, sb->count / lguide->stitch.windows, L, w.motion_dim)
+                               : afm_motion_guide_workspace_bytes(guide, sb->count, L, w.motion_dim);
         off += align256(sb->gws_bytes);
     }
     return off;
@@ -576,7 +579,7 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
 
 // the loop workspace of either public description of the guidance (neither: the unguided loop's); AFM_E_BADARG as the loop itself
 int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams,
-                             bool hist = false, const afm_motion_guide* guide = nullptr, int unit = 1) {
+                             bool hist = false, const afm_motion_guide* guide = nullptr, int unit = 1, const afm_long_guide* lguide = nullptr) {
     if (validate(w, B, L) != 0 || n_streams < 0 || unit < 1 || B % unit != 0) return AFM_E_BADARG;
     if (guide && !guide->contact && !guide->targets) return AFM_E_BADARG;
     if (guide && guide->contact && afm_contact_guidance_workspace_bytes(B, guide->contact->N, guide->contact->K) < 0) return AFM_E_BADARG;
@@ -588,7 +591,7 @@ int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one,
     for (int s = 0; s < n; ++s) {
         SubBatch sb = {};
         unit_sub_range(B, unit, n, s, &sb.start, &sb.count);
-        total += carve_sub(*w, g, L, nullptr, &sb, hist, guide);
+        total += carve_sub(*w, g, L, nullptr, &sb, hist, guide, lguide);
     }
     return total;
 }
@@ -616,13 +619,14 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     if (a.dpm && (!a.ddim || a.noise_term() || a.step_noise || a.first_step < 0)) return AFM_E_BADARG;
     if (c.guided()) {
-        AFM_TRY(afm_motion_guide_check(&c.guide, c.L, c.w->motion_dim));
+        AFM_TRY(c.lguide ? afm_long_guide_check(c.lguide, c.L, c.w->motion_dim) : afm_motion_guide_check(&c.guide, c.L, c.w->motion_dim));
         if (!c.guide.gk || (c.guide.contact && c.guide.contact->first_guided < 0) || (c.guide.targets && c.guide.targets->first_guided < 0)) return AFM_E_BADARG;
     }
     const int unit = c.stitched() ? c.stitch.windows : 1;
-    if (c.stitched()) {               // whole long motions, a frame in at most two windows, a deterministic update, no gradient term
+    if (c.lguide && !c.stitched()) return AFM_E_BADARG;
+    if (c.stitched()) {               // whole long motions, a frame in at most two windows, a deterministic update, no gradient term but a long one
         const afm_stitch& st = c.stitch;
-        if (st.overlap < 0 || 2 * (int64_t)st.overlap > c.L || a.B % st.windows != 0 || !a.ddim || a.noise_term() || a.step_noise || c.guided()) return AFM_E_BADARG;
+        if (st.overlap < 0 || 2 * (int64_t)st.overlap > c.L || a.B % st.windows != 0 || !a.ddim || a.noise_term() || a.step_noise || (c.guided() && !c.lguide)) return AFM_E_BADARG;
         if (st.windows > 1 && st.overlap > 0 && !st.weights) return AFM_E_BADARG;
     }
     p->nsub = 0;
@@ -634,7 +638,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         SubBatch& sb = p->sb[s];
         sb = {};
         unit_sub_range(a.B, unit, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guided() || c.stitched(), c.guided() ? &c.guide : nullptr);
+        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guided() || c.stitched(), c.guided() ? &c.guide : nullptr, c.lguide);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
         if (p->branch_streams) sb.branch = (hipStream_t)g.branch_streams[s];
     }
@@ -697,6 +701,11 @@ inline bool guided_step(const Loop& l, int j) { return contact_step(l, j) || tar
 // the gradient of (sub-batch, step j) at the x the step's evaluations read, on the sub-batch's stream: the launches of afm_motion_guidance
 // for the step's terms (contact: two, h3d four; targets: one, h3d three) into the sub-batch's gradient buffer
 int guide_launch(const Loop& l, const SubBatch& sb, int j) {
+    if (l.c.lguide) {                 // (sb.start and sb.count are whole long motions)
+        const int S = l.c.lguide->stitch.windows;
+        return afm_long_guidance_sub(l.c.lguide, contact_step(l, j), targets_step(l, j), sb.start / S, sub_x(l, sb), nullptr, sb.ggrad, nullptr, nullptr,
+                                     sb.count / S, l.c.L, l.p.w.motion_dim, sb.gws, sb.gws_bytes, sb.stream);
+    }
     // (the guidance's own mask: the denoiser's frame_mask is NULL for a model that does not mask its motion tokens)
     const uint8_t* fm = l.c.guide.frame_mask ? l.c.guide.frame_mask + (int64_t)sb.start * l.c.L : nullptr;
     return afm_motion_guidance_sub(&l.c.guide, contact_step(l, j), targets_step(l, j), sb.start, sub_x(l, sb), fm, nullptr, sb.ggrad, nullptr, nullptr,
@@ -853,7 +862,7 @@ int every_form_range(const afm_cmdm_weights* w, float* x, const float* cond_toke
                      const float* d_sigma, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
                      const afm_motion_guide* guide, const afm_stitch* stitch, int32_t n_steps, int32_t first_step, uint64_t seed,
                      int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
-                     void* const* side_streams, void* stream) {
+                     void* const* side_streams, void* stream, const afm_long_guide* lguide = nullptr) {
     if (first_step < 0 || (guide && !guide->contact && !guide->targets) || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
     afm_ddim_rows as_ddim = {};
     AFM_TRY(one_kind_of_rows(&rows, dpm, d_c1 || d_c2 || d_sigma, &as_ddim));
@@ -863,6 +872,7 @@ int every_form_range(const afm_cmdm_weights* w, float* x, const float* cond_toke
     c.a.dpm = dpm != nullptr;
     if (guide) c.guide = *guide;
     if (stitch) c.stitch = *stitch;
+    c.lguide = lguide;
     return sample_loop_impl(c);
 }
 
@@ -1035,4 +1045,26 @@ extern "C" int afm_cmdm_stitch_loop_range(const afm_cmdm_weights* w, float* x, c
     if (B < 0 || B % stitch->windows != 0 || stitch->overlap < 0 || 2 * (int64_t)stitch->overlap > L) return AFM_E_BADARG;
     return every_form_range(w, x, cond_tokens, frame_mask, nullptr, d_timestep_map, rows, dpm, nullptr, nullptr, nullptr, cfg, cfg2, known, mask, nullptr, stitch,
                             n_steps, first_step, 0, 0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream);
+}
+
+// The stitched loop guided on the joined long motions (afm_long_guide): the stitched loop above with the launches of afm_long_guidance in
+// front of a guided step's evaluations and grad / gk in its stitched update launch.
+extern "C" int64_t afm_cmdm_long_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                            const afm_cfg2_args* cfg2, const afm_long_guide* guide) {
+    if ((cfg && cfg2) || !guide || !w || afm_long_guide_check(guide, L, w->motion_dim) != 0) return AFM_E_BADARG;
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, guide->terms, guide->stitch.windows, guide);
+}
+
+extern "C" int afm_cmdm_long_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                              const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                              const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                              const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_long_guide* guide,
+                                              int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                              void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
+    (void)seed; (void)sample_index0;          // (no noise is drawn)
+    if (first_step < 0 || !guide || !guide->terms || guide->stitch.windows < 1 || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
+    if (d_c1 || d_c2 || d_sigma || step_noise || (rows && rows->sigma)) return AFM_E_BADARG;          // a deterministic update only
+    if (B < 0 || B % guide->stitch.windows != 0) return AFM_E_BADARG;
+    return every_form_range(w, x, cond_tokens, frame_mask, nullptr, d_timestep_map, rows, dpm, nullptr, nullptr, nullptr, cfg, cfg2, known, mask, guide->terms,
+                            &guide->stitch, n_steps, first_step, 0, 0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, guide);
 }

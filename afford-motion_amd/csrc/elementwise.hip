@@ -322,7 +322,7 @@ __attribute__((visibility("hidden"))) int afm_sampling_update(const afm_loop::Up
     if (p.xpad && (p.cols <= 0 || p.ldpad < p.cols)) return AFM_E_BADARG;
     if (p.st_S != 0 || p.st_ov != 0) {          // stitched windows: whole long motions, a frame in at most two windows, a deterministic update
         if (p.st_S < 1 || p.st_ov < 0 || p.st_L <= 0 || p.st_D <= 0 || (int64_t)p.st_L * p.st_D != p.per_sample || 2 * (int64_t)p.st_ov > p.st_L ||
-            B % p.st_S != 0 || !p.ddim || p.sg || p.grad || (p.stitched() && !p.st_w)) return AFM_E_BADARG;
+            B % p.st_S != 0 || !p.ddim || p.sg || (p.stitched() && !p.st_w)) return AFM_E_BADARG;
         if (p.x0_keep && (p.x0_keep == p.x0 || p.x0_keep == p.x0_u || p.x0_keep == p.x0_a)) return AFM_E_BADARG;
         if (p.xn == p.x0 || p.xn == p.x0_u || p.xn == p.x0_a) return AFM_E_BADARG;          // (the neighbour's x0 is read by another thread)
     }
@@ -629,7 +629,9 @@ extern "C" int afm_stitch_join(const float* windows, float* long_motion, int32_t
     return 0;
 }
 
-extern "C" int afm_stitch_step(const afm_stitch_step_args* a, void* stream) {
+namespace {
+// afm_stitch_step, with the gradient term of afm_stitch_guide_step when grad is given (x0_out: the shifted x0, DDIM rows too)
+int stitch_step(const afm_stitch_step_args* a, const float* grad, const float* gk, float* x0_out, void* stream) {
     if (!a || !a->x0_c || !a->stitch || !a->known != !a->mask) return AFM_E_BADARG;
     if ((a->ddim != nullptr) + (a->dpm != nullptr) != 1) return AFM_E_BADARG;          // one kind of rows, both deterministic
     if (a->ddim && a->ddim->sigma) return AFM_E_BADARG;          // (the step noise of shared frames would have to be shared)
@@ -643,6 +645,15 @@ extern "C" int afm_stitch_step(const afm_stitch_step_args* a, void* stream) {
     p.x0_a = a->x0_a; p.x0_u = a->x0_u; p.scale = a->scale; p.scale2 = a->scale2;
     p.known = a->known; p.mask = a->mask;
     if (a->x0_out && !a->dpm) return AFM_E_BADARG;
+    if (grad) { p.grad = grad; p.gk = gk; if (x0_out) p.x0_keep = x0_out; }
     p.st_S = a->stitch->windows; p.st_ov = a->stitch->overlap; p.st_L = a->L; p.st_D = a->D; p.st_w = a->stitch->weights;
     return afm_sampling_update(p, a->B, stream);
+}
+}  // namespace
+
+extern "C" int afm_stitch_step(const afm_stitch_step_args* a, void* stream) { return stitch_step(a, nullptr, nullptr, nullptr, stream); }
+
+extern "C" int afm_stitch_guide_step(const afm_stitch_step_args* a, const float* grad, const float* gk, float* x0_out, void* stream) {
+    if (!grad || !gk) return AFM_E_BADARG;
+    return stitch_step(a, grad, gk, x0_out, stream);
 }

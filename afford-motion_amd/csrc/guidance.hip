@@ -146,17 +146,25 @@ __global__ __launch_bounds__(256) void h3d_recover_kernel(const H3dDev h, const 
         }
 }
 
-// Pass 1 behind its staging, for sample blockIdx.y with the positions in sp[K][L][3] (the [L] validity flags go behind them here), one
+// Pass 1 behind its staging, for sample blockIdx.y with the positions in sp[K][L][3] and the [L] validity flags behind them (both staged by
+// the front: valid_of_mask, or a window's frame count), one
 // thread per (k, n) (e = k * N + n: a wave shares k but for one boundary): the minimum of d2 = (dx*dx + dy*dy) + dz*dz over the valid
 // frames and the FIRST frame that attains it (strict <), chat = exp(-d2 / two_s2) (no valid frame: f* = -1, chat = 0),
-// w = (chat - c) * chat; the block's sum of (chat - c)^2 in a fixed order into partial[b][block].  Both forms' pass 1 is this on their p.
-__device__ __forceinline__ void nearest_of_staged(const GuideDev& g, float* sp, const uint8_t* __restrict__ fmask, int* __restrict__ fstar,
-                                                  float* __restrict__ w, float* __restrict__ partial) {
+// w = (chat - c) * chat; the block's sum of (chat - c)^2 in a fixed order into partial[b][block].  Every form's pass 1 is this on its p.
+// `first`: the index of staged frame 0 in what fstar counts (a window of a long motion stores long frame indices).
+
+// the validity flags of sample blockIdx.y from its frame mask (NULL: every frame valid)
+__device__ __forceinline__ void valid_of_mask(const GuideDev& g, float* sp, const uint8_t* __restrict__ fmask) {
+    int* sval = reinterpret_cast<int*>(sp + (size_t)g.K * g.L * 3);
+    for (int f = threadIdx.x; f < g.L; f += 256) sval[f] = !(fmask && fmask[(int64_t)blockIdx.y * g.L + f]);
+}
+
+__device__ __forceinline__ void nearest_of_staged(const GuideDev& g, float* sp, int* __restrict__ fstar, float* __restrict__ w,
+                                                  float* __restrict__ partial, int first = 0) {
 #pragma clang fp contract(off)
     __shared__ float red[4];
     const int b = blockIdx.y, K = g.K, N = g.N, L = g.L;
-    int* sval = reinterpret_cast<int*>(sp + (size_t)K * L * 3);
-    for (int f = threadIdx.x; f < L; f += 256) sval[f] = !(fmask && fmask[(int64_t)b * L + f]);
+    const int* sval = reinterpret_cast<const int*>(sp + (size_t)K * L * 3);
     __syncthreads();
     const int e = blockIdx.x * 256 + threadIdx.x;
     float sq = 0.f;
@@ -177,7 +185,7 @@ __device__ __forceinline__ void nearest_of_staged(const GuideDev& g, float* sp, 
         const float chat = bf >= 0 ? expf(-best / g.two_s2) : 0.f;
         const float df = chat - g.c[((int64_t)b * N + n) * K + k];
         const int64_t o = ((int64_t)b * K + k) * N + n;
-        fstar[o] = bf;
+        fstar[o] = bf >= 0 ? first + bf : -1;
         w[o] = df * chat;
         sq = df * df;
     }
@@ -199,7 +207,8 @@ __global__ __launch_bounds__(256) void guide_nearest_kernel(const GuideDev g, co
 #pragma unroll
         for (int a = 0; a < 3; ++a) sp[i * 3 + a] = denorm(xrow, g.mean, g.std, scols[k] + a);
     }
-    nearest_of_staged(g, sp, fmask, fstar, w, partial);
+    valid_of_mask(g, sp, fmask);
+    nearest_of_staged(g, sp, fstar, w, partial);
 }
 
 // pass 1 of the h3d form: p = the recovery kernel's pos[b][K][L][3], the very order staged
@@ -209,7 +218,8 @@ __global__ __launch_bounds__(256) void guide_nearest_h3d_kernel(const GuideDev g
     const int n = g.K * g.L * 3;
     const float* pb = pos + (int64_t)blockIdx.y * n;
     for (int i = threadIdx.x; i < n; i += 256) sp[i] = pb[i];
-    nearest_of_staged(g, sp, fmask, fstar, w, partial);
+    valid_of_mask(g, sp, fmask);
+    nearest_of_staged(g, sp, fstar, w, partial);
 }
 
 // Pass 2's energy: block 0 of sample blockIdx.y adds the sample's partials in order, energy[b] = sum / (N K)
@@ -223,12 +233,12 @@ __device__ __forceinline__ void sample_energy(const GuideDev& g, const float* __
     }
 }
 
-// Pass 2's sums for (frame blockIdx.x, sample blockIdx.y, joint k) on one wave: S_a = sum over the points n with f*(b, n, k) == f of
+// Pass 2's sums for (frame f, sample b, joint k) on one wave: S_a = sum over the points n with f*(b, n, k) == f of
 // w * (p_a - q_a) - lane l adds n = l, l + 64, ... in that order, then the fixed butterfly of wave_sum.  Lane a < 3 gets S_a.
-__device__ __forceinline__ float frame_sum(const GuideDev& g, const int* __restrict__ fstar, const float* __restrict__ w, int k, float p0,
-                                           float p1, float p2) {
+__device__ __forceinline__ float frame_sum(const GuideDev& g, const int* __restrict__ fstar, const float* __restrict__ w, int b, int f, int k,
+                                           float p0, float p1, float p2) {
 #pragma clang fp contract(off)
-    const int b = blockIdx.y, f = blockIdx.x, N = g.N, lane = threadIdx.x & 63;
+    const int N = g.N, lane = threadIdx.x & 63;
     const int64_t o = ((int64_t)b * g.K + k) * N;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
     for (int n = lane; n < N; n += 64) {
@@ -269,7 +279,7 @@ __global__ __launch_bounds__(256) void guide_gather_kernel(const GuideDev g, con
     const float ks = g.scale[b] * g.coef;
     for (int k = threadIdx.x >> 6; k < K; k += 4) {
         const int col = scols[k];
-        const float s = frame_sum(g, fstar, w, k, denorm(xrow, g.mean, g.std, col), denorm(xrow, g.mean, g.std, col + 1),
+        const float s = frame_sum(g, fstar, w, b, f, k, denorm(xrow, g.mean, g.std, col), denorm(xrow, g.mean, g.std, col + 1),
                                   denorm(xrow, g.mean, g.std, col + 2));
         if (lane < 3) {
             const float kss = ks * g.std[col + lane];
@@ -289,9 +299,153 @@ __global__ __launch_bounds__(256) void guide_sums_h3d_kernel(const GuideDev g, c
     if (!S) return;
     for (int k = threadIdx.x >> 6; k < K; k += 4) {
         const float* pp = pos + (((int64_t)b * K + k) * g.L + f) * 3;
-        const float s = frame_sum(g, fstar, w, k, pp[0], pp[1], pp[2]);
+        const float s = frame_sum(g, fstar, w, b, f, k, pp[0], pp[1], pp[2]);
         if (lane < 3) S[(((int64_t)b * g.L + f) * K + k) * 3 + lane] = s;
     }
+}
+
+// ---- long motions (afm_long_guide): the batch is G * S windows of L frames, window b = g * S + w holding the long frames a_w = w * hop ..
+// a_w + L - 1 (hop = L - ov) clipped to < F; the positions come from the joined long motion [G][F][D], q / c / fstar / w stay per window.
+struct LongGeo { int S, ov, F; };
+
+// the frames window blockIdx.y holds, n_w = min(L, F - a_w), as the validity flags of pass 1; -> a_w
+__device__ __forceinline__ int valid_of_window(const GuideDev& g, const LongGeo& lg, float* sp) {
+    int* sval = reinterpret_cast<int*>(sp + (size_t)g.K * g.L * 3);
+    const int first = ((int)blockIdx.y % lg.S) * (g.L - lg.ov);
+    const int n = min(g.L, lg.F - first);
+    for (int f = threadIdx.x; f < g.L; f += 256) sval[f] = f < n;
+    return first;
+}
+
+// windowed pass 1 of the column form: p = the de-normalised columns of the window's rows of the long motion
+__global__ __launch_bounds__(256) void long_nearest_kernel(const GuideDev g, const LongGeo lg, const float* __restrict__ lng, int* __restrict__ fstar,
+                                                           float* __restrict__ w, float* __restrict__ partial) {
+    extern __shared__ float sp[];                   // [K][L][3] positions, then [L] validity
+    __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
+    const int L = g.L, gi = blockIdx.y / lg.S;
+    stage_index(g.cols, scols);
+    const int first = valid_of_window(g, lg, sp);
+    const int n = min(L, lg.F - first);
+    __syncthreads();
+    for (int i = threadIdx.x; i < g.K * L; i += 256) {
+        const int k = i / L, f = i - k * L;
+        if (f >= n) continue;
+        const float* xrow = lng + ((int64_t)gi * lg.F + first + f) * g.D;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) sp[i * 3 + a] = denorm(xrow, g.mean, g.std, scols[k] + a);
+    }
+    nearest_of_staged(g, sp, fstar, w, partial, first);
+}
+
+// windowed pass 1 of the h3d form: p = the recovery's pos[g][K][F][3] of the long motion, the window's frames of every joint
+__global__ __launch_bounds__(256) void long_nearest_h3d_kernel(const GuideDev g, const LongGeo lg, const float* __restrict__ pos, int* __restrict__ fstar,
+                                                               float* __restrict__ w, float* __restrict__ partial) {
+    extern __shared__ float sp[];                   // [K][L][3] positions, then [L] validity
+    const int L = g.L, gi = blockIdx.y / lg.S;
+    const int first = valid_of_window(g, lg, sp);
+    const int n3 = min(L, lg.F - first) * 3;
+    const float* pb = pos + (int64_t)gi * g.K * lg.F * 3 + (int64_t)first * 3;
+    for (int i = threadIdx.x; i < g.K * L * 3; i += 256) {
+        const int k = i / (L * 3), r = i - k * (L * 3);
+        if (r < n3) sp[i] = pb[(int64_t)k * lg.F * 3 + r];
+    }
+    nearest_of_staged(g, sp, fstar, w, partial, first);
+}
+
+// the one or two windows of a long motion that hold long frame f: *later = min(f / hop, S - 1); the window in front of it holds f too iff
+// there is one and f lies in the later window's first ov frames
+__device__ __forceinline__ bool windows_of_frame(const LongGeo& lg, int L, int f, int* later) {
+    const int hop = L - lg.ov;
+    const int w1 = min(f / hop, lg.S - 1);
+    *later = w1;
+    return w1 > 0 && f - w1 * hop < lg.ov;
+}
+
+// the joined sums of (long frame blockIdx.x, long motion blockIdx.y, joint k) on one wave: the frame's window's frame_sum, or - a shared
+// frame - S_earlier + S_later, one rounded addition
+__device__ __forceinline__ float long_frame_sum(const GuideDev& g, const LongGeo& lg, const int* __restrict__ fstar, const float* __restrict__ w,
+                                                int k, float p0, float p1, float p2) {
+#pragma clang fp contract(off)
+    const int f = blockIdx.x;
+    int w1;
+    const bool two = windows_of_frame(lg, g.L, f, &w1);
+    const int b = (int)blockIdx.y * lg.S + w1;
+    const float later = frame_sum(g, fstar, w, b, f, k, p0, p1, p2);
+    if (!two) return later;
+    const float earlier = frame_sum(g, fstar, w, b - 1, f, k, p0, p1, p2);
+    return earlier + later;
+}
+
+// the long motion's contact energy: the windows' energies (each its partials in order, / (N K)) added serially in window order
+__device__ __forceinline__ void long_energy(const GuideDev& g, const LongGeo& lg, const float* __restrict__ partial, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && energy && threadIdx.x == 0) {
+        float e = 0.f;
+        for (int wi = 0; wi < lg.S; ++wi) {
+            const int64_t b = (int64_t)blockIdx.y * lg.S + wi;
+            float s = 0.f;
+            for (int i = 0; i < g.nblk; ++i) s += partial[b * g.nblk + i];
+            const float eb = s / (float)((int64_t)g.N * g.K);
+            e = e + eb;
+        }
+        energy[blockIdx.y] = e;
+    }
+}
+
+// Long pass 2 of the column form, one block per (long frame blockIdx.x, long motion blockIdx.y), wave v the joints k = v, v + 4, ...:
+// grad_long[g, f, cols[k] + a] = ((scale[g] * coef) * std_a) * S with S the joined sum; every other column of the row, and the whole row of
+// a long motion with t[g] >= t_start, is written as zero.  g.q / fstar / w are the windows', g.scale and t the long motions'.
+__global__ __launch_bounds__(256) void long_gather_kernel(const GuideDev g, const LongGeo lg, const float* __restrict__ lng, const int64_t* __restrict__ t,
+                                                          const int* __restrict__ fstar, const float* __restrict__ w,
+                                                          const float* __restrict__ partial, float* __restrict__ grad, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
+    const int gi = blockIdx.y, f = blockIdx.x, K = g.K;
+    stage_index(g.cols, scols);
+    __syncthreads();
+    long_energy(g, lg, partial, energy);
+    if (!grad) return;
+    float* row = grad + ((int64_t)gi * lg.F + f) * g.D;
+    const bool guided = !(t && t[gi] >= g.t_start);
+    for (int d = threadIdx.x; d < g.D; d += 256) {
+        bool named = false;
+        for (int k = 0; k < K; ++k) named = named || (d >= scols[k] && d < scols[k] + 3);
+        if (!guided || !named) row[d] = 0.f;
+    }
+    if (!guided) return;
+    const float* xrow = lng + ((int64_t)gi * lg.F + f) * g.D;
+    const int lane = threadIdx.x & 63;
+    const float ks = g.scale[gi] * g.coef;
+    for (int k = threadIdx.x >> 6; k < K; k += 4) {
+        const int col = scols[k];
+        const float s = long_frame_sum(g, lg, fstar, w, k, denorm(xrow, g.mean, g.std, col), denorm(xrow, g.mean, g.std, col + 1),
+                                       denorm(xrow, g.mean, g.std, col + 2));
+        if (lane < 3) {
+            const float kss = ks * g.std[col + lane];
+            row[col + lane] = kss * s;
+        }
+    }
+}
+
+// Long pass 2 of the h3d form: the same blocks, waves and joined sums on the recovery's pos[g][K][F][3]; the bare sums go to S[g][f][k][3] for
+// the adjoint over the F frames.  S == NULL: the energy alone, one block per long motion.
+__global__ __launch_bounds__(256) void long_sums_h3d_kernel(const GuideDev g, const LongGeo lg, const float* __restrict__ pos, const int* __restrict__ fstar,
+                                                            const float* __restrict__ w, const float* __restrict__ partial, float* __restrict__ S,
+                                                            float* __restrict__ energy) {
+    const int gi = blockIdx.y, f = blockIdx.x, K = g.K, lane = threadIdx.x & 63;
+    long_energy(g, lg, partial, energy);
+    if (!S) return;
+    for (int k = threadIdx.x >> 6; k < K; k += 4) {
+        const float* pp = pos + (((int64_t)gi * K + k) * lg.F + f) * 3;
+        const float s = long_frame_sum(g, lg, fstar, w, k, pp[0], pp[1], pp[2]);
+        if (lane < 3) S[(((int64_t)gi * lg.F + f) * K + k) * 3 + lane] = s;
+    }
+}
+
+// t of long motion g is its first window's: tl[g] = t[g * S]
+__global__ __launch_bounds__(256) void long_t_kernel(const int64_t* __restrict__ t, int64_t* __restrict__ tl, int S, int G) {
+    const int gi = blockIdx.x * 256 + threadIdx.x;
+    if (gi < G) tl[gi] = t[(int64_t)gi * S];
 }
 
 // The adjoint of the recovery for sample blockIdx.x: S[b][f][k][3] -> the sample's complete rows in `rows` [B][L][D], the zeros included.
@@ -766,4 +920,152 @@ extern "C" int afm_h3d_joints(const float* x, const float* mean, const float* st
                        (float*)nullptr);
     AFM_CHECK_LAUNCH();
     return 0;
+}
+
+// ---- the guidance of stitched long motions (afm_long_guide): the windows joined, the terms evaluated on the long motion, one gradient per
+// long frame handed back to the windows
+namespace {
+
+bool long_geometry_ok(const afm_long_guide* g, int32_t L) {
+    const int64_t S = g->stitch.windows, ov = g->stitch.overlap, F = g->frames;
+    if (S < 1 || ov < 0 || L <= 0 || 2 * ov > L) return false;
+    return F > (S - 1) * (L - ov) + (S > 1 ? ov : 0) && F <= S * L - (S - 1) * ov;
+}
+
+// the buffers of `count` long motions in front of the terms' own: the joined motion and its gradient [count][F][D], t per long motion
+struct LongPlan {
+    float *lng, *glong;
+    int64_t* tl;
+    char *cws, *tws;                // the contact term's buffers (its windows', then the h3d form's of the long motion), the targets'
+    int64_t cbytes, bytes;
+};
+
+LongPlan long_plan(const afm_long_guide* g, int64_t count, int32_t L, int32_t D, char* wp) {
+    const afm_motion_guide* m = g->terms;
+    const int64_t F = g->frames, S = g->stitch.windows;
+    LongPlan p = {};
+    char* base = wp;
+    const int64_t fd = afm_loop::align256(count * F * D * 4);
+    p.lng = (float*)wp; wp += fd;
+    p.glong = (float*)wp; wp += fd;
+    p.tl = (int64_t*)wp; wp += afm_loop::align256(count * 8);
+    p.cws = wp;
+    if (m->contact) {
+        p.cbytes = afm_loop::align256(afm_contact_guidance_workspace_bytes((int32_t)(count * S), m->contact->N, m->contact->K));
+        if (m->contact->h3d) p.cbytes += h3d_extra_bytes(count, F, m->contact->K);
+    }
+    wp += p.cbytes;
+    p.tws = wp;
+    if (m->targets) wp += targets_workspace_bytes(m->targets, m->contact != nullptr, count, F, D);
+    p.bytes = wp - base;
+    return p;
+}
+
+}  // namespace
+
+// what a long description must satisfy before anything is enqueued (L, D: the windows')
+__attribute__((visibility("hidden"))) int afm_long_guide_check(const afm_long_guide* g, int32_t L, int32_t D) {
+    if (!g || !g->terms || !long_geometry_ok(g, L)) return AFM_E_BADARG;
+    const int rc = afm_motion_guide_check(g->terms, L, D);
+    if (rc != 0) return rc;
+    const afm_motion_guide* m = g->terms;
+    if (g->frames > 65535) return AFM_E_UNSUPPORTED;
+    if (((m->contact && m->contact->h3d) || (m->targets && m->targets->h3d)) && (size_t)H3D_SCAN_ROWS * g->frames * 4 > (size_t)GUIDE_LDS_BYTES)
+        return AFM_E_UNSUPPORTED;           // the recovery and the adjoint hold 7 * F floats in LDS
+    return m->targets ? targets_check(m->targets, g->frames, D) : 0;
+}
+
+// the workspace of `count` long motions of a checked description
+__attribute__((visibility("hidden"))) int64_t afm_long_guide_workspace_bytes(const afm_long_guide* g, int32_t count, int32_t L, int32_t D) {
+    return long_plan(g, count, L, D, nullptr).bytes;
+}
+
+// the long motions [start, start + count) of the description's batch; x, t and grad already point at window start * S, the energies at
+// long motion `start`.  run_contact / run_targets: the terms this call computes
+__attribute__((visibility("hidden"))) int afm_long_guidance_sub(const afm_long_guide* g, bool run_contact, bool run_targets, int32_t start, const float* x,
+                                                                const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
+                                                                int32_t count, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes,
+                                                                void* stream) {
+    const int rc = afm_long_guide_check(g, L, D);
+    if (rc != 0) return rc;
+    const afm_motion_guide* m = g->terms;
+    run_contact = run_contact && m->contact;
+    run_targets = run_targets && m->targets;
+    if (!x || (!grad && !energy_contact && !energy_targets) || start < 0 || count < 0 || (energy_contact && !run_contact) ||
+        (energy_targets && !run_targets) || (!run_contact && !run_targets)) return AFM_E_BADARG;
+    const int S = g->stitch.windows, ov = g->stitch.overlap, F = g->frames;
+    if ((int64_t)count * S > 65535) return AFM_E_UNSUPPORTED;
+    if (count == 0) return 0;
+    const LongPlan p = long_plan(g, count, L, D, (char*)workspace);
+    if (!workspace || workspace_bytes < p.bytes) return AFM_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int rcj = afm_stitch_join(x, p.lng, count, S, ov, L, D, F, stream);
+    if (rcj != 0) return rcj;
+    const int64_t* tl = nullptr;
+    if (t && grad) {
+        hipLaunchKernelGGL(long_t_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, t, p.tl, S, count);
+        AFM_CHECK_LAUNCH();
+        tl = p.tl;
+    }
+    const bool contact = run_contact && (grad || energy_contact);
+    if (contact) {
+        const afm_contact_guide* a = m->contact;
+        const int wins = count * S;
+        GuideDev d = {};
+        d.q = a->q + (int64_t)start * S * a->N * 3; d.c = a->c + (int64_t)start * S * a->N * a->K; d.mean = a->mean; d.std = a->std; d.scale = a->scale + start;
+        for (int k = 0; k < a->K; ++k) d.cols[k] = a->cols[k];
+        d.K = a->K; d.N = a->N; d.L = L; d.D = D; d.nblk = (int)guide_nblk(a->N, a->K);
+        d.two_s2 = (float)(2.0 * a->sigma * a->sigma);
+        d.coef = (float)(2.0 / ((double)a->N * a->K * a->sigma * a->sigma));
+        d.t_start = a->t_start;
+        const LongGeo lg = {S, ov, F};
+        char* wp = p.cws;
+        const int64_t nk = (int64_t)wins * a->N * a->K;
+        int* fstar = (int*)wp; wp += afm_loop::align256(nk * 4);
+        float* w = (float*)wp; wp += afm_loop::align256(nk * 4);
+        float* partial = (float*)wp;
+        const size_t lds = ((size_t)a->K * L * 3 + L) * 4;
+        const dim3 g1((unsigned)d.nblk, (unsigned)wins), g2(grad ? (unsigned)F : 1u, (unsigned)count);
+        if (a->h3d) {
+            wp = p.cws + afm_loop::align256(afm_contact_guidance_workspace_bytes(wins, a->N, a->K));
+            const H3dPlan h = h3d_plan(a->mean, a->std, d.scale, *a->h3d, a->K, F, D, start, count, true, d.coef, a->t_start, wp);
+            hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), h.scan_lds, s, h.rec, p.lng, (const uint8_t*)nullptr, h.pos,
+                               grad ? h.cs : nullptr);
+            AFM_CHECK_LAUNCH();
+            hipLaunchKernelGGL(long_nearest_h3d_kernel, g1, dim3(256), lds, s, d, lg, h.pos, fstar, w, partial);
+            AFM_CHECK_LAUNCH();
+            hipLaunchKernelGGL(long_sums_h3d_kernel, g2, dim3(256), 0, s, d, lg, h.pos, fstar, w, partial, grad ? h.S : nullptr, energy_contact);
+            AFM_CHECK_LAUNCH();
+            if (grad) {
+                hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), h.scan_lds, s, h.adj, p.lng, (const uint8_t*)nullptr, tl, h.cs, h.S,
+                                   p.glong);
+                AFM_CHECK_LAUNCH();
+            }
+        } else {
+            hipLaunchKernelGGL(long_nearest_kernel, g1, dim3(256), lds, s, d, lg, p.lng, fstar, w, partial);
+            AFM_CHECK_LAUNCH();
+            hipLaunchKernelGGL(long_gather_kernel, g2, dim3(256), 0, s, d, lg, p.lng, tl, fstar, w, partial, grad ? p.glong : nullptr, energy_contact);
+            AFM_CHECK_LAUNCH();
+        }
+    }
+    if (run_targets && (grad || energy_targets)) {
+        const int rct = targets_sub(m->targets, contact && grad, start, p.lng, nullptr, tl, grad ? p.glong : nullptr, energy_targets, count, F, D, p.tws, s);
+        if (rct != 0) return rct;
+    }
+    if (!grad) return 0;
+    return afm_stitch_windows(p.glong, grad, count, S, ov, L, D, F, stream);
+}
+
+extern "C" int64_t afm_long_guidance_workspace_bytes(const afm_long_guide* g, int32_t B, int32_t L, int32_t D) {
+    if (B < 0 || afm_long_guide_check(g, L, D) != 0 || B % g->stitch.windows != 0) return AFM_E_BADARG;
+    return afm_long_guide_workspace_bytes(g, B / g->stitch.windows, L, D) + 256;
+}
+
+extern "C" int afm_long_guidance(const afm_long_guide* g, const float* x_windows, const int64_t* t, float* grad_windows, float* energy_contact,
+                                 float* energy_targets, int32_t B, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes, void* stream) {
+    const int rc = afm_long_guide_check(g, L, D);
+    if (rc != 0) return rc;
+    if (B < 0 || B % g->stitch.windows != 0) return AFM_E_BADARG;
+    return afm_long_guidance_sub(g, true, true, 0, x_windows, t, grad_windows, energy_contact, energy_targets, B / g->stitch.windows, L, D, workspace,
+                                 workspace_bytes, stream);
 }

@@ -36,6 +36,15 @@ __attribute__((visibility("hidden"))) int afm_motion_guidance_sub(const afm_moti
                                                                   float* energy_targets, int32_t count, int32_t L, int32_t D, void* workspace,
                                                                   int64_t workspace_bytes, void* stream);
 
+// guidance.hip: the guidance of stitched long motions (afm_long_guide) - its checks, the workspace of `count` long motions of a checked
+// description, and afm_long_guidance on the long motions [start, start + count) (x, t, grad point at window start * S)
+__attribute__((visibility("hidden"))) int afm_long_guide_check(const afm_long_guide* g, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int64_t afm_long_guide_workspace_bytes(const afm_long_guide* g, int32_t count, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int afm_long_guidance_sub(const afm_long_guide* g, bool run_contact, bool run_targets, int32_t start, const float* x,
+                                                                const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
+                                                                int32_t count, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes,
+                                                                void* stream);
+
 namespace afm_loop {
 
 // ---- the sampling update x_t -> x_next of one launch, [B][per_sample] floats: every DDPM, DDIM and guided update outside the fused GEMM /
@@ -70,7 +79,7 @@ struct Update {
     // +- st_ov * st_D and combined with the NEIGHBOUR's scales.  Only the x0 buffers are read across samples and only the
     // element's own x_next / xpad / x0_keep are written, so the in-place update stays race-free (x0_keep must not alias an x0 buffer).
     // st_w: the weight row [2][st_ov], wl then wr.  st_S <= 1 or st_ov == 0: no blend (the unstitched kernel).  DDIM without a noise
-    // term or 2M only, no grad.
+    // term or 2M only; with grad the shift follows the clamp as in the unstitched kernel.
     int st_S, st_ov, st_L, st_D;
     const float* st_w;
     bool stitched() const { return st_S > 1 && st_ov > 0; }

@@ -1068,6 +1068,67 @@ int afm_cmdm_stitch_loop_range(const afm_cmdm_weights* w, float* x, const float*
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Guidance of stitched long motions (v7-additive): the contact and joint-target terms evaluated on the JOINED motion, so a target or a
+ * root path may lie beyond the first window and an h3d root is integrated from long frame 0.
+ *
+ * stitch: S windows, overlap ov, `frames` = F long frames; hop = L - ov.  Window w of long motion g is batch row b = g * S + w and holds the
+ * long frames a_w = w * hop .. a_w + L - 1, clipped to < F.  In a stitched chain the shared frames are bit-identical in both windows at
+ * every step, so the windows join into one long x_t.  With x [G * S][L][D]:
+ *   1. long = afm_stitch_join(x) [G][F][D] (a shared frame is read from the later window).
+ *   2. P[g,f,k,:] = the positions of `long` exactly as the kernels above compute them: the de-normalised columns, or the h3d recovery over
+ *      all F frames.  float32, every operation in its present order.
+ *   3. Targets term: the afm_motion_guidance targets launches on (long, B = G, L = F); target / weight are long-form [G][F][K][3] /
+ *      [G][F][K].  Its value is by definition targets(long).
+ *   4. Contact term, per window b (q [G * S][N][3] and c [G * S][N][K]: each window keeps its own map):
+ *      d2[b,n,k] = min over the window's long frames f of |P[g,f,k] - q[b,n]|^2, summed (dx*dx + dy*dy) + dz*dz; f* the first such frame,
+ *      stored as a long frame index; chat and w as above; E_b = sum (chat - c)^2 / (N K) with the partial and serial sums above;
+ *      S_b[f,k,:] = sum over {n: f*(b,n,k) = f} of w * (p - q) in the frame_sum order above.
+ *   5. Per long frame the windows' sums are joined: a frame in one window takes that window's sum as is, a frame in two windows takes
+ *      S_earlier + S_later - one rounded addition, earlier window first.  With w1 = min(f / hop, S - 1) the earlier window w1 - 1 also
+ *      holds f iff w1 > 0 and f - w1 * hop < ov.
+ *   6. Column form: grad_long[g,f,col+a] = ((scale[g] * coef) * std_a) * S.  h3d form: the joined S goes through the adjoint kernel on
+ *      (B = G, L = F) with scale[g].
+ *   7. The targets' launch adds its complete result to what the contact term wrote, as afm_motion_guidance does.
+ *   8. grad = afm_stitch_windows(grad_long): the padded tail is exact zeros, both copies of a shared frame hold the same bits.
+ * The terms' `scale` rows are [G]; to_scene is [3][4] or [G][3][4]; no frame mask is read - validity is the geometry (long frames
+ * 0 .. F-1 are valid, the padded tail of a last window does not exist in the long form).  t [G * S] or NULL: long motion g has t[g * S].
+ * energy_contact[g] = the serial sum of its windows' E_b in window order; energy_targets[g] = the targets' energy of the long motion.
+ * No atomics: a long motion's result depends neither on G nor on its place in the batch.  Launches with a gradient: join, the contact
+ * term's 2 (h3d: 4), the targets' 1 (h3d: 3), windows (+1 copying t when t is given).
+ * AFM_E_BADARG: the checks of afm_motion_guidance (on L for the contact staging, on F for the targets), a geometry F outside
+ * (S-1) hop + ov < F <= S L - (S-1) ov, B % S != 0.  AFM_E_UNSUPPORTED: 7 * F floats beyond the LDS with h3d, F > 65535.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const afm_motion_guide* terms;         /* scale rows [G]; targets long-form; q / c [G * S]; gk (loops) [T][G * S]; frame_mask unread */
+    afm_stitch stitch;
+    int32_t frames;                        /* F */
+} afm_long_guide;
+int64_t afm_long_guidance_workspace_bytes(const afm_long_guide* g, int32_t B, int32_t L, int32_t D);
+int afm_long_guidance(const afm_long_guide* g, const float* x_windows, const int64_t* t, float* grad_windows, float* energy_contact,
+                      float* energy_targets, int32_t B, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* afm_stitch_step with a cond_fn gradient term, one launch: combine -> blend -> select -> clamp -> x0 += gk * grad -> update (the
+ * afm_guide_step shift: m = gk[b] * grad rounded, then the addition rounded).  grad [B][L][D] and gk [B] are both required; x0_out
+ * (optional, DDIM rows too; overrides args->x0_out) receives the shifted x0.  afm_stitch_step_args is unchanged. */
+int afm_stitch_guide_step(const afm_stitch_step_args* args, const float* grad, const float* gk, float* x0_out, void* stream);
+
+/* The stitched native loop guided by an afm_long_guide: afm_cmdm_guide_loop_range's signature with the long description in the guidance's
+ * slot; the stitch is the description's own.  rows with eta = 0 (sigma NULL) or dpm only; cfg / cfg2 / known + mask as in the stitched
+ * loop; sub-batches are cut over whole long motions.  Per sub-batch and executed step first_step + j that has reached a term's
+ * first_guided, the launches of afm_long_guidance for the reached terms (t NULL) run on the sub-batch's stream in front of the
+ * evaluations, and the stitched update takes grad and gk row n_steps - 1 - j (terms->gk [T][G * S]).  Earlier steps launch exactly what
+ * afm_cmdm_stitch_loop_range launches.  Chained range calls on one workspace are bit-identical to one call. */
+int64_t afm_cmdm_long_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                 const afm_cfg2_args* cfg2, const afm_long_guide* guide);
+int afm_cmdm_long_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                   const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                   const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                   const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_long_guide* guide,
+                                   int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                   void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
  * CrossAttentionLayer, SelfAttentionBlock, MLP, Residual; pad mask / rotary / kv-cache never used).

@@ -13,8 +13,17 @@ process:
 reported as ms per long motion and ms per step (median of --reps windows, with the spread), and their ratio.  A timed window holds as many
 loop calls as fill 0.1 s.  With --parent-lib (a libafm_hip.so built from the parent commit) `bench.py --gpus 1 --steps K --warmup 20` runs
 on this build and on the parent's, alternated, each in a fresh child process while this one idles: bench.py's loops are untouched, so its
-figure should lie inside the parent's own call-to-call spread.  One JSON line at the end; --md also writes the table as markdown."""
+figure should lie inside the parent's own call-to-call spread.  One JSON line at the end; --md also writes the table as markdown.
+
+    python tools/bench_stitch.py --guided [contact|targets|both] --repr [pos|h3d] [--parent-lib PATH] [--md profiles/long_guidance_bench.md]
+
+What guiding a stitched chain costs (afm.diffusion.LongGuidance, afm_cmdm_long_guide_loop_range): the same cells, the arms "guided"
+(stitch= and the LongGuidance as cond_fn; every step guided) and "stitched" (the same chain without it) alternated in one call, as ms per
+long motion, with the guided step's gradient-launch count taken from torch.profiler (device kernels of a guided chain minus those of the
+unguided one, per step and sub-batch, counted at G = 1).  With --parent-lib the unguided stitched chain of every cell is also run on the parent's library in a fresh child
+process and compared bit for bit (sha256 of the result)."""
 import argparse
+import hashlib
 import json
 import math
 import os
@@ -34,6 +43,10 @@ GROUPS = (1, 8)
 SAMPLERS = {"dpm2m_logsnr20": ("logsnr20", "dpm"), "ddim50": ("ddim50", "ddim")}
 NEW = ("afm_stitch_blend", "afm_stitch_windows", "afm_stitch_join", "afm_stitch_step", "afm_cmdm_stitch_loop_workspace_bytes",
        "afm_cmdm_stitch_loop_range")
+LONG_NEW = ("afm_long_guidance_workspace_bytes", "afm_long_guidance", "afm_stitch_guide_step", "afm_cmdm_long_guide_loop_workspace_bytes",
+            "afm_cmdm_long_guide_loop_range")
+JOINTS = [0, 10, 11, 12, 20, 21]          # the six contact joints of the h3d skeleton
+COLS = [4, 259, 100, 7, 193, 64]          # --repr pos: six column triples of the 263-column vector read as absolute positions
 MIN_WINDOW_S = 0.1
 
 
@@ -56,7 +69,7 @@ def bench_child(lib):
     """Child process: bench.py on another build's library (the entry points it lacks are not bound)."""
     from afm import ffi
     ffi._LIB_PATH = os.path.abspath(lib)
-    for name in NEW:
+    for name in NEW + LONG_NEW:
         ffi.EXPORTS.pop(name, None)
     import runpy
     runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")
@@ -71,6 +84,143 @@ def _bench_once(lib, steps):
     return json.loads(line)["value"]
 
 
+def _setup():
+    """(the CMDM on synthetic weights, its config factory, the device)"""
+    from afm import synth
+    from afm.base import create_model
+    from afm.config import load_config
+    dev = torch.device("cuda:0")
+    cfg = lambda resp: load_config("text_to_motion_contact_motion_gen", "cmdm", ["model.data_repr=h3d", "model.input_feats=263",
+                                                                                "model.text_model.max_length=20", "diffusion.steps=1000",
+                                                                                f"diffusion.timestep_respacing='{resp}'"])
+    model = create_model(cfg("ddim50"), device=dev)
+    synth.fill_module_(model)
+    return model.to(dev).eval(), cfg, dev
+
+
+def _cells(model, cfg, dev):
+    """every (sampler, G) cell: (key, diffusion, loop, G, B, model_kwargs, x_T, stitch)"""
+    from afm import synth
+    from afm.base import create_gaussian_diffusion
+    from afm.diffusion import Stitch
+    st = Stitch(S, OV, length=L)
+    for name, (resp, kind) in SAMPLERS.items():
+        d = create_gaussian_diffusion(cfg(resp))
+        loop = d.ddim_sample_loop if kind == "ddim" else d.dpm_solver_sample_loop
+        for G in GROUPS:
+            B = G * S
+            kw = dict(c_text_feat=synth.text_feature(B).to(dev), c_pc_xyz=synth.scene_cloud(B, N).to(dev),
+                      c_pc_contact=synth.contact_map(B, N).to(dev), x_mask=torch.zeros(B, L, dtype=torch.bool, device=dev))
+            yield f"{name}/G{G}", d, loop, G, B, kw, st.x_T(B, L, D, dev, 1), st
+
+
+def _sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def hash_child(lib):
+    """Child process: the unguided stitched chain of every cell on another build's library; one JSON line of sha256 digests."""
+    from afm import ffi
+    ffi._LIB_PATH = os.path.abspath(lib)
+    for name in LONG_NEW:
+        ffi.EXPORTS.pop(name, None)
+    model, cfg, dev = _setup()
+    out = {}
+    for key, d, loop, G, B, kw, x_T, st in _cells(model, cfg, dev):
+        out[key] = _sha(loop(model, (B, L, D), noise=x_T, clip_denoised=False, model_kwargs=kw, stitch=st))
+    print(json.dumps(out))
+
+
+def _long_guide(st, G, terms, form, dev):
+    """the LongGuidance of the guided arm: six contact joints against each window's own map, the root's path as targets at every
+    tenth long frame, one scale per long motion"""
+    from afm import synth
+    from afm.diffusion import ContactGuidance, JointTargets, LongGuidance
+    F = st.full(L)
+    mean, std = 0.3 * synth.gaussian("bench_long_mean", (D,)), 0.5 + synth.gaussian("bench_long_std", (D,)).abs()
+    std[0], std[1:3] = 0.05, 0.1
+    target = synth.gaussian("bench_long_target", (G, F, 1, 3))
+    weight = torch.zeros(G, F, 1)
+    weight[:, ::10] = 1.0
+    scale = torch.full((G,), 2.0)
+    ct = tg = None
+    if terms in ("contact", "both"):
+        ct = ContactGuidance.h3d(JOINTS, mean, std, scale=scale) if form == "h3d" else ContactGuidance(COLS, mean, std, scale=scale)
+    if terms in ("targets", "both"):
+        kw = dict(target=target, weight=weight, scale=0.1 * scale)
+        tg = JointTargets.h3d(JOINTS[:1], mean, std, **kw) if form == "h3d" else JointTargets(COLS[:1], mean, std, **kw)
+    return LongGuidance(st, ct, tg)
+
+
+def _kernel_count(fn):
+    """device kernels of one call of fn, ATen's movers left out (torch.profiler)"""
+    import re
+    from torch.profiler import ProfilerActivity, profile
+    movers = re.compile(r"(FillFunctor|fill_kernel|copy|Copy|memcpy|Memcpy|memset|Memset)")
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return sum(1 for ev in prof.events() if str(getattr(ev, "device_type", "")).endswith("CUDA") and not movers.search(ev.name))
+
+
+def guided_main(args):
+    model, cfg, dev = _setup()
+    out = {"guided": args.guided, "repr": args.repr, "shape": {"S": S, "L": L, "overlap": OV, "N": N, "D": D},
+           "device": torch.cuda.get_device_name(0), "cells": {}}
+    hashes, launches = {}, {}
+    for key, d, loop, G, B, kw, x_T, st in _cells(model, cfg, dev):
+        out["shape"]["frames"] = st.full(L)
+        steps = d.num_timesteps
+        guide = _long_guide(st, G, args.guided, args.repr, dev)
+        arms = {"guided": lambda: loop(model, (B, L, D), noise=x_T, clip_denoised=False, cond_fn=guide, model_kwargs=kw, stitch=st),
+                "stitched": lambda: loop(model, (B, L, D), noise=x_T, clip_denoised=False, model_kwargs=kw, stitch=st)}
+        calls = {}
+        for arm, fn in arms.items():
+            fn()
+            fn()
+            calls[arm] = max(1, math.ceil(MIN_WINDOW_S / _timed(fn)))
+        hashes[key] = _sha(arms["stitched"]())
+        ts = {arm: [] for arm in arms}
+        for _ in range(args.reps):
+            for arm, fn in arms.items():
+                ts[arm].append(_timed(fn, calls[arm]))
+        cell = {arm: _stats(ts[arm], steps, G) for arm in arms}
+        cell["steps"], cell["rows"] = steps, B
+        cell["guided_over_stitched"] = round(statistics.median(ts["guided"]) / statistics.median(ts["stitched"]), 4)
+        # the launch count, per sub-batch: taken where the chain is one sub-batch (G = 1; the profiler drops events of the long G = 8 chains)
+        if G == GROUPS[0]:
+            launches[key.split("/")[0]] = (_kernel_count(arms["guided"]) - _kernel_count(arms["stitched"])) / steps
+        cell["gradient_launches_per_guided_step"] = launches[key.split("/")[0]]
+        out["cells"][key] = cell
+        print(f"[long guidance bench] {key}: {cell}", flush=True)
+    if args.parent_lib:
+        del model
+        torch.cuda.empty_cache()
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--hash-child", args.parent_lib], capture_output=True, text=True, cwd=ROOT, timeout=900)
+        if r.returncode != 0:
+            raise RuntimeError(f"the parent's chain failed ({r.returncode}): {r.stderr[-800:]}")
+        parent = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        out["unguided_chain_equals_parent"] = {k: parent.get(k) == v for k, v in hashes.items()}
+        print(f"[long guidance bench] unguided stitched chain, this build == parent's library: {out['unguided_chain_equals_parent']}", flush=True)
+    if args.md:
+        lines = [f"# Guided stitched long motions ({args.guided}, {args.repr}): S = {S}, L = {L}, ov = {OV} ({out['shape']['frames']} frames), "
+                 f"N = {N}, {out['device']}", "",
+                 "Every step guided; both arms alternated in one call, median of the timed windows.", "",
+                 "| sampler | G | rows | steps | guided ms / long motion | unguided stitched ms / long motion | guided / unguided | gradient launches / guided step and sub-batch (counted at G = 1) | spread % (guided, unguided) |",
+                 "|---|---|---|---|---|---|---|---|---|"]
+        for key, c in out["cells"].items():
+            s_, g = key.split("/G")
+            lines.append(f"| {s_} | {g} | {c['rows']} | {c['steps']} | {c['guided']['ms_per_long_motion']} | {c['stitched']['ms_per_long_motion']} | "
+                         f"{c['guided_over_stitched']} | {c['gradient_launches_per_guided_step']:g} | {c['guided']['spread_pct']}, {c['stitched']['spread_pct']} |")
+        if "unguided_chain_equals_parent" in out:
+            same = out["unguided_chain_equals_parent"]
+            lines += ["", "The unguided stitched chain of every cell, this build against the parent commit's library in a fresh process (sha256 of "
+                      f"the result): {'bit-identical in every cell' if all(same.values()) else 'DIFFERS: ' + str(same)}."]
+        with open(args.md, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -79,10 +229,17 @@ def main():
     ap.add_argument("--bench-rounds", type=int, default=3)
     ap.add_argument("--md", default=None)
     ap.add_argument("--bench-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--hash-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--guided", choices=("contact", "targets", "both"), default=None)
+    ap.add_argument("--repr", choices=("pos", "h3d"), default="h3d")
     args, rest = ap.parse_known_args()
     if args.bench_child:
         sys.argv = [os.path.join(ROOT, "bench.py")] + rest
         return bench_child(args.bench_child)
+    if args.hash_child:
+        return hash_child(args.hash_child)
+    if args.guided:
+        return guided_main(args)
 
     from afm import synth
     from afm.base import create_gaussian_diffusion, create_model
