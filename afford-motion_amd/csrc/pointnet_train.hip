@@ -33,7 +33,29 @@ __global__ __launch_bounds__(1024) void reduce_cols2_kernel(const float* __restr
     }
 }
 
-// Per-column pair sums over a chunk of rows.  MODE 0: (x, x^2).  MODE 1: (g, g * xhat) with g = dy * (y > 0 when y given),
+// K[c] = mean of the first S rows of x [rows, C] (S = min(rows, 64)): the pivot of the shifted sums below.  Block = 64 columns x 16 row lanes, the
+// rows of a lane ascending, the lanes in a fixed order: a function of x alone.  The pivot need not be accurate, only near the column mean: the sums
+// about it cancel like ((mean - K) / sigma)^2 2^-23, and about the tensor's FIRST row, as they were taken before, one outlying or zero-padded
+// first row K' sigma from the mean cost K'^2 ulps (measured: DESIGN.md 4.7, profiles/point_train_edges_parity.json).
+constexpr int PIVOT_ROWS = 64;
+__global__ __launch_bounds__(1024) void colpivot_kernel(const float* __restrict__ x, int C, int S, float* __restrict__ K) {
+    __shared__ float red[16][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + tx;
+    float a0 = 0.f;
+    if (c < C)
+        for (int s = ty; s < S; s += 16) a0 += x[(int64_t)s * C + c];
+    red[ty][tx] = a0;
+    __syncthreads();
+    if (ty == 0 && c < C) {
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v += red[i][tx];
+        K[c] = v / (float)S;
+    }
+}
+
+// Per-column pair sums over a chunk of rows.  MODE 0: (x - K, (x - K)^2) about the pivot K handed in as `mean`.  MODE 1: (g, g * xhat) with g = dy * (y > 0 when y given),
 // xhat = (x - mean) * rstd.  Block = CW column lanes x (256 / CW) row lanes; thread keeps NC = ceil(C / CW) column pairs.
 template <int MODE, int NC>
 __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__ a, const float* __restrict__ x, const float* __restrict__ y,
@@ -47,8 +69,8 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
     for (int j = 0; j < NC; ++j) {
         s0[j] = 0.f; s1[j] = 0.f;
         const int c = tx + j * CW;
-        // MODE 0: sums are taken about the tensor's first row (shifted-data variance: no E[x^2] - m^2 cancellation)
-        mu[j] = c < C ? (MODE == 1 ? mean[c] : a[c]) : 0.f;
+        // MODE 0: sums are taken about the pivot (shifted-data variance: no E[x^2] - m^2 cancellation)
+        mu[j] = c < C ? mean[c] : 0.f;
         rs[j] = (MODE == 1 && c < C) ? rstd[c] : 0.f;
     }
     for (int64_t r = r0 + ty; r < r1; r += RL) {
@@ -94,8 +116,8 @@ __global__ __launch_bounds__(256) void colstats4_kernel(const float* __restrict_
     const int QW = C >> 2, tx = threadIdx.x % QW, ty = threadIdx.x / QW, RL = 256 / QW;
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    // MODE 0: sums are taken about the tensor's first row (shifted-data variance: no E[x^2] - m^2 cancellation)
-    const float4 mu = *reinterpret_cast<const float4*>((MODE == 1 ? mean : a) + tx * 4);
+    // MODE 0: sums are taken about the pivot (shifted-data variance: no E[x^2] - m^2 cancellation)
+    const float4 mu = *reinterpret_cast<const float4*>(mean + tx * 4);
     const float4 rs = MODE == 1 ? *reinterpret_cast<const float4*>(rstd + tx * 4) : s0;
     auto add = [&](const float4& av, const float4& xv, const float4& yv) {
         if (MODE == 0) {
@@ -186,7 +208,7 @@ int launch_colstats(const float* a, const float* x, const float* y, const float*
     return 0;
 }
 
-// stats [world][3C] per rank: sum(x - K), sum((x - K)^2), K (= that rank's first row); equal row counts per rank.
+// stats [world][3C] per rank: sum(x - K), sum((x - K)^2), K (= that rank's pivot, colpivot_kernel); equal row counts per rank.
 // Per-rank mean / M2 are combined with the parallel-variance formula (as torch's batch_norm_gather_stats_with_counts).
 __global__ void bn_finalize_kernel(const float* __restrict__ stats, int world, float rows, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
@@ -214,11 +236,6 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, int world, f
         const float unbiased = count > 1.0f ? m2 / (count - 1.0f) : var;
         running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
     }
-}
-
-__global__ void copy_row_kernel(const float* __restrict__ src, float* __restrict__ dst, int C) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) dst[c] = src[c];
 }
 
 // y = relu?(x * scale[c] + shift[c] + residual)
@@ -610,11 +627,11 @@ extern "C" int64_t afm_colstats_workspace_bytes(int64_t rows, int32_t C) {
 
 extern "C" int afm_colstats(const float* x, int64_t rows, int32_t C, float* stats, void* ws, int64_t ws_bytes, void* stream) {
     if (!stats || rows <= 0 || !x) return AFM_E_BADARG;
-    const int rc = launch_colstats<0>(x, nullptr, nullptr, nullptr, nullptr, rows, C, stats, ws, ws_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(copy_row_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, x, stats + 2 * C, C);
+    if (C <= 0 || C > 512) return C > 512 ? AFM_E_UNSUPPORTED : AFM_E_BADARG;
+    float* pivot = stats + 2 * C;
+    hipLaunchKernelGGL(colpivot_kernel, dim3((C + 63) / 64), dim3(1024), 0, (hipStream_t)stream, x, C, (int)(rows < PIVOT_ROWS ? rows : PIVOT_ROWS), pivot);
     AFM_CHECK_LAUNCH();
-    return 0;
+    return launch_colstats<0>(x, nullptr, nullptr, pivot, nullptr, rows, C, stats, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int afm_bn_finalize(const float* stats, int32_t world, int64_t rows_per_rank, const float* gamma, const float* beta, float eps,

@@ -369,8 +369,9 @@ int afm_rowop(const float* x, const float* rowtab, int32_t period, const float* 
  * 102-123 under model.train()).  Batch statistics force a full pass between every BatchNorm and its consumer, so the
  * training graph is composed from bandwidth-bound passes over materialised [n, k, c] tensors. */
 
-/* Column statistics of a row-major [rows, C] matrix (C <= 512, rows >= 1), fixed summation order, taken about the
- * matrix's first row K (shifted-data variance: no E[x^2] - mean^2 cancellation):
+/* Column statistics of a row-major [rows, C] matrix (C <= 512, rows >= 1), fixed summation order, taken about a pivot K
+ * = the mean of the matrix's first min(rows, 64) rows (shifted-data variance: no E[x^2] - mean^2 cancellation; near the
+ * column mean whatever a single row holds):
  *   stats[0..C) = sum_r (x[r,c] - K[c]),  stats[C..2C) = sum_r (x[r,c] - K[c])^2,  stats[2C..3C) = K. */
 int64_t afm_colstats_workspace_bytes(int64_t rows, int32_t C);
 int afm_colstats(const float* x, int64_t rows, int32_t C, float* stats, void* ws, int64_t ws_bytes, void* stream);
@@ -399,7 +400,8 @@ int afm_group_points(const float* xyz, const float* new_xyz, const float* feat, 
 /* dst[idx[r], c] += src[r*ld + col_offset + c], c < C  (backward of a row gather; f32 atomics like the CUDA original) */
 int afm_scatter_add_rows(const float* src, int64_t ld, int32_t col_offset, const int32_t* idx, float* dst, int64_t rows,
                          int32_t C, void* stream);
-/* Deterministic form (ABI v7).  afm_scatter_plan: the inverse of an index list idx [entries] with values in [0, n_dst) - plan = int32 words
+/* Deterministic form (ABI v7).  afm_scatter_plan: the inverse of an index list idx [entries] with values in [0, n_dst) - entries outside
+ * that range are SKIPPED by the plan (and so by every segmented sum through it; off[n_dst] counts the valid ones) - plan = int32 words
  * [n_dst + 1 segment offsets | entries: the entries of every destination, ASCENDING | scratch], afm_scatter_plan_words(entries, n_dst) words in
  * all; integer atomics only, the result does not depend on any arrival order.  afm_segment_sum_rows: dst[d, c] = sum over the entries e of
  * destination d, in ascending order, of weight(e) * src[(e / row_div) * ld + col_offset + c]  (every destination row is WRITTEN: no zero-fill;
