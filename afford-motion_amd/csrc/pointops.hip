@@ -15,35 +15,51 @@
 //   * kNN: one lane per query, candidates streamed through an LDS tile (broadcast reads), the k best
 //     kept as a sorted register array with a branch-free insertion.
 #include "common.h"
+#include "fps_plan.h"
 #include "profile.h"
 #pragma clang fp contract(off)
-
-#ifdef AFM_PROBE
-int afm_probe_fps_threads = 0;
-int afm_probe_fps_prune = -1;                           // 0: plain fps_kernel even where the pruned one applies; 256 / 512 / 1024: its threads
-__device__ unsigned long long afm_probe_fps_cyc[8];     // summed phase cycles of wave 0 of workgroup 0 (tools/points_probe.hip)
-__device__ int afm_probe_fps_rounds[4];                 // [rounds of workgroup 0, picks taken as 1st / 2nd+ ...] (tools/fps_ks_probe.hip)
-#endif
-#ifdef AFM_PROBE_TIMELINE      // with -DAFM_PROBE: per-phase cycle stamps inside the FPS round (they lengthen the round by ~15 %)
-#define AFM_FPS_STAMP(k) do { if (probe_) { const unsigned long long t_ = __builtin_readcyclecounter(); cyc_[k] += t_ - last_; last_ = t_; } } while (0)
-#else
-#define AFM_FPS_STAMP(k) do { } while (0)
-#endif
-
-#ifndef AFM_FPS_KS
-#define AFM_FPS_KS 1             // samples per round of fps_pruned_kernel: 1 in the library.  KS = 2 / 4 / 8 (tools/fps_ks_probe.hip builds) are exact - same indices,
-                                 // 2047 -> 1082 / 663 / 571 rounds at n = 8192, m = 2048 - and NOT faster: 1.48 -> 1.54 / 1.53 / 1.63 ms (profiles/r06_fps_speculation.md)
-#endif
-
-#ifndef AFM_FPS_CELLS
-#define AFM_FPS_CELLS 1          // cells per thread of the pruned FPS: 1 = fps_pruned_kernel on 1024 threads (the library); 2 / 4 = fps_cells_kernel on 512 / 256 threads
-                                 // (probe builds): identical indices, 1.48 -> 1.72 / 2.30 ms at n = 8192, m = 2048 (profiles/r06_fps_speculation.md)
-#endif
 
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// ---------------------------------------------------------------- the arg-max of a round, shared by the two FPS kernels
+// Wave level of the arg-max: this lane's best (distance bits `bd`, point index `bi`; `valid` = the lane holds a point) -> the wave's key,
+// distance << 32 | ~lowest index, which orders by (distance bits, lowest point index); 0 when no lane is valid.  A 32-bit maximum of the
+// distances (DPP), then the lowest index among the lanes that hold it - one ballot and one v_readlane when a single lane does (the usual
+// case), a second 32-bit reduction only on a tie.  (A 64-bit key carried through the DPP steps costs a v_cmp_u64 + two selects per step: 250
+// cycles of the ~2200-cycle round, profiles/r02_points_probe.txt.)
+__device__ __forceinline__ unsigned long long fps_wave_key(bool valid, unsigned bd, unsigned bi) {
+    const unsigned wmax = wave_max_u32(valid ? bd : 0u);
+    const unsigned long long holders = __builtin_amdgcn_ballot_w64(valid && bd == wmax);
+    unsigned long long best = 0ull;
+    if (holders) {                                    // wave-uniform
+        unsigned wbi;
+        if ((holders & (holders - 1)) == 0) wbi = (unsigned)__builtin_amdgcn_readlane((int)bi, __builtin_ctzll(holders));
+        else wbi = wave_min_u32((valid && bd == wmax) ? bi : 0xFFFFFFFFu);
+        best = ((unsigned long long)wmax << 32) | (unsigned long long)(0xFFFFFFFFu - wbi);
+    }
+    return best;
+}
+
+// Workgroup level of round j: publish the wave's key (the key buffers alternate: ONE barrier per round), then the same scheme on the <= 16
+// wave keys (lane l of every row reads key l; one LDS round trip) -> the index of the round's sample, in an SGPR.
+__device__ __forceinline__ int fps_workgroup_pick(unsigned long long (*keys)[16], int j, unsigned long long best, int lane, int wave, int nw) {
+    if (lane == 0) keys[j & 1][wave] = best;
+    __syncthreads();
+    const bool has = (lane & 15) < nw;
+    const unsigned long long kw = keys[j & 1][has ? (lane & 15) : 0];
+    const unsigned khi = has ? (unsigned)(kw >> 32) : 0u, klo = has ? (unsigned)kw : 0u;       // lo = ~index: larger is the lower index
+    unsigned gm = khi;
+    gm = max(gm, dpp_u32<0xB1>(gm)); gm = max(gm, dpp_u32<0x4E>(gm)); gm = max(gm, dpp_u32<0x141>(gm)); gm = max(gm, dpp_u32<0x140>(gm));
+    const unsigned long long hold2 = __builtin_amdgcn_ballot_w64(has && lane < 16 && khi == gm);       // row 0 is enough: the rows are copies
+    unsigned wlo;
+    if ((hold2 & (hold2 - 1)) == 0) wlo = (unsigned)__builtin_amdgcn_readlane((int)klo, __builtin_ctzll(hold2 | (1ull << 63)));
+    else wlo = wave_max_u32((has && khi == gm) ? klo : 0u);
+    return __builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu - wlo));
+}
+
+// ---------------------------------------------------------------- FPS, every point scanned every round
 // Per-point work is kept minimal (the round's VALU time is 16 waves x PPT points on ONE CU): coordinates of two slots are
 // processed as packed f32 pairs (v_pk_add / v_pk_mul: same IEEE results, half the instructions), the per-thread arg-max is a
 // 32-bit (distance bits, slot) select - slots are visited in increasing point index, so a strict '>' keeps the lowest index on
@@ -70,6 +86,7 @@ __global__ __launch_bounds__(MAXT) void fps_kernel(const float* __restrict__ xyz
         tmpb[s] = ok ? __float_as_uint(1e10f) : 0u;
     }
     if (IN_LDS) {
+        // (written out here and in fps_pruned_kernel: as a shared inline function the same loop compiles to a different block layout)
         for (int i0 = tid; i0 < 3 * n; i0 += 8 * T) {                // eight loads in flight per thread (not a load -> store chain per element)
             float v[8];
 #pragma unroll
@@ -81,18 +98,12 @@ __global__ __launch_bounds__(MAXT) void fps_kernel(const float* __restrict__ xyz
     }
     int cur = 0;
     if (tid == 0 && m > 0) idx_out[(int64_t)b * m] = b * n;
-#ifdef AFM_PROBE_TIMELINE
-    const bool probe_ = blockIdx.x == 0 && wave == 0;
-    unsigned long long cyc_[6] = {0, 0, 0, 0, 0, 0}, last_ = __builtin_readcyclecounter();
-#endif
     for (int j = 1; j < m; ++j) {
-        AFM_FPS_STAMP(5);
         // the winner's coordinates head the round's dependent chain: an explicit LDS read (ds_read), not a generic-pointer load
         // (a run-time `in_lds ? pts : P` compiles to flat_load, which waits on both memory counters and takes the slow aperture path)
         float cx, cy, cz;
         if (IN_LDS) { cx = pts[cur * 3 + 0]; cy = pts[cur * 3 + 1]; cz = pts[cur * 3 + 2]; }
         else { cx = P[cur * 3 + 0]; cy = P[cur * 3 + 1]; cz = P[cur * 3 + 2]; }
-        AFM_FPS_STAMP(0);                             // winner's coordinates arrived
         const f32x2 cx2 = {cx, cx}, cy2 = {cy, cy}, cz2 = {cz, cz};
         unsigned bd = 0u, bs = 0u;                    // best distance bits (distances are >= 0: bits order like values), its slot
 #pragma unroll
@@ -111,43 +122,11 @@ __global__ __launch_bounds__(MAXT) void fps_kernel(const float* __restrict__ xyz
                 }
             }
         }
-        // slot 0 wins an all-zero tie, which is also the lowest index of this thread; invalid threads carry key 0.
-        // The key orders by (distance bits, lowest point index).  Wave level: a 32-bit maximum of the distances (DPP), then the lowest
-        // index among the lanes that hold it - one ballot and one v_readlane when a single lane does (the usual case), a second 32-bit
-        // reduction only on a tie.  (A 64-bit key carried through the DPP steps costs a v_cmp_u64 + two selects per step: 250 cycles
-        // of the ~2200-cycle round, profiles/r02_points_probe.txt.)
+        // slot 0 wins an all-zero tie, which is also the lowest index of this thread; invalid threads carry key 0
         const unsigned bi = bs * (unsigned)T + (unsigned)tid;
-        AFM_FPS_STAMP(1);                             // per-thread scan
-        const unsigned wmax = wave_max_u32(ok0 ? bd : 0u);
-        const unsigned long long holders = __builtin_amdgcn_ballot_w64(ok0 && bd == wmax);
-        unsigned long long best = 0ull;
-        if (holders) {                                // wave-uniform
-            unsigned wbi;
-            if ((holders & (holders - 1)) == 0) wbi = (unsigned)__builtin_amdgcn_readlane((int)bi, __builtin_ctzll(holders));
-            else wbi = wave_min_u32((ok0 && bd == wmax) ? bi : 0xFFFFFFFFu);
-            best = ((unsigned long long)wmax << 32) | (unsigned long long)(0xFFFFFFFFu - wbi);
-        }
-        AFM_FPS_STAMP(2);                             // wave arg-max
-        if (lane == 0) keys[j & 1][wave] = best;
-        __syncthreads();
-        AFM_FPS_STAMP(3);                             // LDS hop + barrier
-        // workgroup level, same scheme on the <= 16 wave keys (lane l of every row reads key l; one LDS round trip)
-        const bool has = (lane & 15) < nw;
-        const unsigned long long kw = keys[j & 1][has ? (lane & 15) : 0];
-        const unsigned khi = has ? (unsigned)(kw >> 32) : 0u, klo = has ? (unsigned)kw : 0u;       // lo = ~index: larger is the lower index
-        unsigned gm = khi;
-        gm = max(gm, dpp_u32<0xB1>(gm)); gm = max(gm, dpp_u32<0x4E>(gm)); gm = max(gm, dpp_u32<0x141>(gm)); gm = max(gm, dpp_u32<0x140>(gm));
-        const unsigned long long hold2 = __builtin_amdgcn_ballot_w64(has && lane < 16 && khi == gm);       // row 0 is enough: the rows are copies
-        unsigned wlo;
-        if ((hold2 & (hold2 - 1)) == 0) wlo = (unsigned)__builtin_amdgcn_readlane((int)klo, __builtin_ctzll(hold2 | (1ull << 63)));
-        else wlo = wave_max_u32((has && khi == gm) ? klo : 0u);
-        cur = __builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu - wlo));
-        AFM_FPS_STAMP(4);                             // cross-wave arg-max
+        cur = fps_workgroup_pick(keys, j, fps_wave_key(ok0, bd, bi), lane, wave, nw);
         if (tid == 0) idx_out[(int64_t)b * m + j] = b * n + cur;
     }
-#ifdef AFM_PROBE_TIMELINE
-    if (probe_ && lane == 0) for (int k = 0; k < 6; ++k) afm_probe_fps_cyc[k] = cyc_[k];
-#endif
 }
 
 // ---------------------------------------------------------------- FPS with an exact pruning of the per-round scan
@@ -165,20 +144,7 @@ __device__ __forceinline__ unsigned morton_part10(unsigned x) {
     return x;
 }
 
-// KS > 1 (round 6): up to KS samples PER ROUND.  A round's cost is its dependent chain (winner's coordinates -> box test -> scan -> wave arg-max ->
-// LDS hop -> barrier -> cross-wave arg-max: ~1500 cycles), and the chain of m - 1 rounds is the kernel.  But the point with the SECOND largest
-// running minimum is almost always far from the one with the largest: if its distance to the new sample is not below its own running minimum, that
-// minimum does not change, every other minimum can only shrink, and it IS the next sample - provably, not heuristically (keys are (distance
-// bits, lowest index), all unique).  So a round takes the best point, then the next best while that one is unaffected by every point taken before it
-// in the round (checked with the same float expression the scan uses), and the next round scans with all of them as centres.  What a wave
-// publishes is its best key and the distance bits of its SECOND best point: a candidate from another wave is only taken while its distance is
-// strictly above the second-best distance of every wave whose best was already taken (whose other points are not published).  Measured on
-// the synthetic scenes (profiles/r06_fps_speculation.md): 2047 rounds -> 1082 / 663 / 571 with KS = 2 / 4 / 8 (n = 8192, m = 2048), the sampled
-// indices identical by construction and by test (tests/test_gpu_points.py ran green on a KS = 4 build) - and the kernel NO faster: a round grows
-// from 0.72 to 1.42 / 2.31 / 2.85 us.  The 16 waves of a sample share ONE compute unit, whose four SIMDs issue every wave's per-round
-// instructions: the uniform selection logic of an extra sample (~50 instructions, executed by all 16 waves, plus a box test per centre and
-// wave) costs the CU as many issue slots as the whole one-sample round.  Kept as a measured form (AFM_FPS_KS), not compiled into the library.
-template <int PPT, int T, int KS = 1>
+template <int PPT, int T>
 __global__ __launch_bounds__(T) void fps_pruned_kernel(const float* __restrict__ xyz, int n, int m, int* __restrict__ idx_out) {
     constexpr int CAP = T * PPT, NP = PPT / 2;
     static_assert(PPT % 2 == 0 && PPT <= 32 && T % 64 == 0 && T <= 1024, "cell sizes");
@@ -248,7 +214,7 @@ __global__ __launch_bounds__(T) void fps_pruned_kernel(const float* __restrict__
         if (ok) { clo[0] = fminf(clo[0], x); chi[0] = fmaxf(chi[0], x); clo[1] = fminf(clo[1], y); chi[1] = fmaxf(chi[1], y); clo[2] = fminf(clo[2], z); chi[2] = fmaxf(chi[2], z); }
     }
     __syncthreads();                                  // the sort arrays are dead: the same LDS becomes the copy of the sample
-    for (int i0 = tid; i0 < 3 * n; i0 += 8 * T) {
+    for (int i0 = tid; i0 < 3 * n; i0 += 8 * T) {    // eight loads in flight per thread, as in fps_kernel
         float v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = i0 + u * T < 3 * n ? P[i0 + u * T] : 0.f;
@@ -271,121 +237,6 @@ __global__ __launch_bounds__(T) void fps_pruned_kernel(const float* __restrict__
             boi = min(boi, min(tmpb[s2] == bd ? oi[s2] : 0xFFFFFFFFu, tmpb[s2 + 1] == bd ? oi[s2 + 1] : 0xFFFFFFFFu));
     };
     cell_argmax();
-    if constexpr (KS > 1) {
-        __shared__ uint4 rec[2][16];                  // per wave: (best distance bits, ~lowest index, second-best distance bits of the wave, -)
-        unsigned long long bestk = 0ull;              // this wave's best key and second-best distance, kept across the rounds in which the wave skips
-        unsigned sec = 0u;
-        int ncen = 1;
-        int cen[KS];
-        float ccx[KS], ccy[KS], ccz[KS];
-#pragma unroll
-        for (int c = 0; c < KS; ++c) { cen[c] = 0; ccx[c] = pts[0]; ccy[c] = pts[1]; ccz[c] = pts[2]; }
-        if (tid == 0 && m > 0) idx_out[(int64_t)b * m] = b * n;
-        int j = 1, round = 0;
-        while (j < m) {
-            bool scanned = false;
-#pragma unroll
-            for (int c = 0; c < KS; ++c) {
-                if (c < ncen) {                                       // wave-uniform
-                    const float cx = ccx[c], cy = ccy[c], cz = ccz[c];
-                    // lower bound of every computed distance of the cell (same operations, same association as the scan); `bd` may be stale
-                    // (too large) after an earlier centre of this round: the test is then only more often true
-                    const float ex = fmaxf(fmaxf(clo[0] - cx, cx - chi[0]), 0.f), ey = fmaxf(fmaxf(clo[1] - cy, cy - chi[1]), 0.f), ez = fmaxf(fmaxf(clo[2] - cz, cz - chi[2]), 0.f);
-                    const float lb = (ex * ex + ey * ey) + ez * ez;
-                    const bool need = cell_ok && __float_as_uint(lb) < bd;
-                    if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
-                        const f32x2 cx2 = {cx, cx}, cy2 = {cy, cy}, cz2 = {cz, cz};
-#pragma unroll
-                        for (int p2 = 0; p2 < NP; ++p2) {
-                            const f32x2 dx = px[p2] - cx2, dy = py[p2] - cy2, dz = pz[p2] - cz2;
-                            const f32x2 d = (dx * dx + dy * dy) + dz * dz;
-                            tmpb[2 * p2] = min(tmpb[2 * p2], __float_as_uint(d[0]));
-                            tmpb[2 * p2 + 1] = min(tmpb[2 * p2 + 1], __float_as_uint(d[1]));
-                        }
-                        scanned = true;
-                    }
-                }
-            }
-            if (scanned) cell_argmax();
-            if (scanned || round == 0) {
-                const unsigned wmax = wave_max_u32(cell_ok ? bd : 0u);
-                const unsigned long long holders = __builtin_amdgcn_ballot_w64(cell_ok && bd == wmax);
-                bestk = 0ull; sec = 0u;
-                if (holders) {
-                    unsigned wbi;
-                    if ((holders & (holders - 1)) == 0) wbi = (unsigned)__builtin_amdgcn_readlane((int)boi, __builtin_ctzll(holders));
-                    else wbi = wave_min_u32((cell_ok && bd == wmax) ? boi : 0xFFFFFFFFu);
-                    bestk = ((unsigned long long)wmax << 32) | (unsigned long long)(0xFFFFFFFFu - wbi);
-                    // second-best DISTANCE of the wave: every point but the best one (wmax, wbi); a second point at the same distance counts
-                    unsigned v2 = cell_ok ? bd : 0u;
-                    if (cell_ok && bd == wmax && boi == wbi) {
-                        v2 = 0u;
-#pragma unroll
-                        for (int s2 = 0; s2 < PPT; ++s2) v2 = max(v2, oi[s2] == wbi ? 0u : tmpb[s2]);
-                    }
-                    sec = wave_max_u32(v2);
-                }
-            }
-            if (lane == 0) rec[round & 1][wave] = make_uint4((unsigned)(bestk >> 32), (unsigned)bestk, sec, 0u);
-            __syncthreads();
-            // ---- cross-wave: up to KS picks in key order (every wave computes them redundantly from the published records: no second barrier)
-            const bool has = (lane & 15) < nw;
-            const uint4 rw = rec[round & 1][has ? (lane & 15) : 0];
-            unsigned khi = has ? rw.x : 0u, klo = has ? rw.y : 0u;
-            const unsigned ksec = has ? rw.z : 0u;
-            unsigned thr = 0u;                            // largest second-best distance among the waves whose best was taken this round
-            int nacc = 0;
-            const int room = m - j < KS ? m - j : KS;
-#pragma unroll
-            for (int i = 0; i < KS; ++i) {
-                if (i < room && (i == 0 || nacc == i)) {              // wave-uniform: still extending the prefix
-                    unsigned gm = khi;
-                    gm = max(gm, dpp_u32<0xB1>(gm)); gm = max(gm, dpp_u32<0x4E>(gm)); gm = max(gm, dpp_u32<0x141>(gm)); gm = max(gm, dpp_u32<0x140>(gm));
-                    unsigned long long hold = __builtin_amdgcn_ballot_w64(has && lane < 16 && khi == gm);
-                    if (hold & (hold - 1)) {                          // several waves at this distance: the lowest index (largest ~index)
-                        const unsigned wlo = wave_max_u32((has && lane < 16 && khi == gm) ? klo : 0u);
-                        hold = __builtin_amdgcn_ballot_w64(has && lane < 16 && khi == gm && klo == wlo);
-                    }
-                    const int wl = __builtin_ctzll(hold | (1ull << 63)) & 15;
-                    const unsigned hi_i = (unsigned)__builtin_amdgcn_readlane((int)khi, wl), lo_i = (unsigned)__builtin_amdgcn_readlane((int)klo, wl);
-                    const unsigned sec_i = (unsigned)__builtin_amdgcn_readlane((int)ksec, wl);
-                    const int ci = (int)(0xFFFFFFFFu - lo_i);
-                    bool ok = true;
-                    float qx = 0.f, qy = 0.f, qz = 0.f;
-                    if (i > 0) ok = hi_i > thr;                       // (strictly above: a point at the same distance in a taken wave could come first; also excludes distance 0)
-                    if (ok) {
-                        qx = pts[ci * 3 + 0]; qy = pts[ci * 3 + 1]; qz = pts[ci * 3 + 2];
-#pragma unroll
-                        for (int a = 0; a < KS; ++a) {
-                            if (a < i && ok) {                        // unaffected by every point taken before it: the scan's own expression, point minus centre
-                                const float dx = qx - ccx[a], dy = qy - ccy[a], dz = qz - ccz[a];
-                                const float d = (dx * dx + dy * dy) + dz * dz;
-                                ok = __float_as_uint(d) >= hi_i;
-                            }
-                        }
-                    }
-                    if (ok) {
-                        cen[i] = ci; ccx[i] = qx; ccy[i] = qy; ccz[i] = qz;
-                        nacc = i + 1;
-                        thr = max(thr, sec_i);
-                        if ((lane & 15) == wl) { khi = 0u; klo = 0u; }         // taken (all four row copies)
-                    }
-                }
-            }
-            if (tid == 0) {
-#pragma unroll
-                for (int i = 0; i < KS; ++i)
-                    if (i < nacc) idx_out[(int64_t)b * m + j + i] = b * n + cen[i];
-            }
-            ncen = nacc;
-            j += nacc;
-            ++round;
-        }
-#ifdef AFM_PROBE
-        if (blockIdx.x == 0 && tid == 0) afm_probe_fps_rounds[0] = round;
-#endif
-        return;
-    }
     int cur = 0;
     unsigned long long best = 0ull;                   // this wave's key, kept across the rounds in which the wave skips
     if (tid == 0 && m > 0) idx_out[(int64_t)b * m] = b * n;
@@ -407,200 +258,10 @@ __global__ __launch_bounds__(T) void fps_pruned_kernel(const float* __restrict__
             }
             cell_argmax();
         }
-        // (distance bits, lowest original index): wave level, then the 16 wave keys - as in fps_kernel.  A wave that skipped the update holds
-        // the cells it held the round before: its key is unchanged and only re-published (the key buffers alternate)
-        if (scan || j == 1) {
-            const unsigned wmax = wave_max_u32(cell_ok ? bd : 0u);
-            const unsigned long long holders = __builtin_amdgcn_ballot_w64(cell_ok && bd == wmax);
-            best = 0ull;
-            if (holders) {
-                unsigned wbi;
-                if ((holders & (holders - 1)) == 0) wbi = (unsigned)__builtin_amdgcn_readlane((int)boi, __builtin_ctzll(holders));
-                else wbi = wave_min_u32((cell_ok && bd == wmax) ? boi : 0xFFFFFFFFu);
-                best = ((unsigned long long)wmax << 32) | (unsigned long long)(0xFFFFFFFFu - wbi);
-            }
-        }
-        if (lane == 0) keys[j & 1][wave] = best;
-        __syncthreads();
-        const bool has = (lane & 15) < nw;
-        const unsigned long long kw = keys[j & 1][has ? (lane & 15) : 0];
-        const unsigned khi = has ? (unsigned)(kw >> 32) : 0u, klo = has ? (unsigned)kw : 0u;
-        unsigned gm = khi;
-        gm = max(gm, dpp_u32<0xB1>(gm)); gm = max(gm, dpp_u32<0x4E>(gm)); gm = max(gm, dpp_u32<0x141>(gm)); gm = max(gm, dpp_u32<0x140>(gm));
-        const unsigned long long hold2 = __builtin_amdgcn_ballot_w64(has && lane < 16 && khi == gm);
-        unsigned wlo;
-        if ((hold2 & (hold2 - 1)) == 0) wlo = (unsigned)__builtin_amdgcn_readlane((int)klo, __builtin_ctzll(hold2 | (1ull << 63)));
-        else wlo = wave_max_u32((has && khi == gm) ? klo : 0u);
-        cur = __builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu - wlo));
-        if (tid == 0) idx_out[(int64_t)b * m + j] = b * n + cur;
-    }
-}
-
-// ---------------------------------------------------------------- FPS, several cells per thread (round 6)
-// A TEST of the hypothesis that fps_pruned_kernel's round is bound by the instruction slots of the one compute unit a sample occupies (of ~1300 slots per round,
-// ~720 are work every wave repeats whatever it owns: the cross-wave arg-max, publish + barrier, the box test) - REFUTED by this kernel: with the same cells on
-// half / a quarter of the waves the kernel is 16 % / 55 % SLOWER (1.48 -> 1.72 / 2.30 ms).  The round is a dependent latency chain per wave (winner's coordinates ->
-// box test -> scan -> arg-max -> LDS -> barrier -> cross-wave arg-max), and sixteen waves walk their cells in parallel where eight or four walk them in turn.
-// MEASUREMENT form (AFM_FPS_CELLS, probe builds only).  A thread owns CELLS cells of PPT sorted points each (cell c of thread t = sorted points [(c T + t) PPT, + PPT): slot c of a wave's 64 lanes is what one
-// wave of the T x CELLS-thread layout owns), so the pruning granularity and the wave-level skip are unchanged while the per-wave overheads are paid by T / 64
-// waves instead of CELLS T / 64.  Same state, same arithmetic, same (distance bits, lowest original index) order: identical indices.
-template <int PPT, int T, int CELLS>
-__global__ __launch_bounds__(T) void fps_cells_kernel(const float* __restrict__ xyz, int n, int m, int* __restrict__ idx_out) {
-    constexpr int CAP = T * PPT * CELLS, NP = PPT / 2;
-    static_assert(PPT % 2 == 0 && PPT <= 16 && T % 64 == 0 && T <= 1024 && CELLS >= 1 && CELLS <= 8, "cell sizes");
-    __shared__ unsigned long long keys[2][16];
-    __shared__ float bb[6][16];
-    extern __shared__ float pts[];                    // first the sort arrays (2 x CAP words), then the [3n] copy of the sample
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int nw = T / 64;
-    const float* P = xyz + (int64_t)b * n * 3;
-    float lo3[3] = {INFINITY, INFINITY, INFINITY}, hi3[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = tid; i < n; i += T) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { const float v = P[i * 3 + a]; lo3[a] = fminf(lo3[a], v); hi3[a] = fmaxf(hi3[a], v); }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { lo3[a] = fminf(lo3[a], __shfl_xor(lo3[a], o)); hi3[a] = fmaxf(hi3[a], __shfl_xor(hi3[a], o)); }
-        if (lane == 0) { bb[a][wave] = lo3[a]; bb[3 + a][wave] = hi3[a]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float l = bb[a][0], h = bb[3 + a][0];
-        for (int w2 = 1; w2 < nw; ++w2) { l = fminf(l, bb[a][w2]); h = fmaxf(h, bb[3 + a][w2]); }
-        lo3[a] = l; hi3[a] = 1023.0f / fmaxf(h - l, 1e-12f);
-    }
-    unsigned* kk = reinterpret_cast<unsigned*>(pts);
-    unsigned* vv = kk + CAP;
-    for (int i = tid; i < CAP; i += T) {
-        unsigned key = 0xFFFFFFFFu;
-        if (i < n) {
-            unsigned q[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { const float f = (P[i * 3 + a] - lo3[a]) * hi3[a]; q[a] = (unsigned)min(1023, max(0, (int)f)); }
-            key = morton_part10(q[0]) | (morton_part10(q[1]) << 1) | (morton_part10(q[2]) << 2);
-        }
-        kk[i] = key; vv[i] = i < n ? (unsigned)i : 0xFFFFFFFFu;
-    }
-    __syncthreads();
-    for (int k = 2; k <= CAP; k <<= 1) {
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int i = tid; i < CAP; i += T) {
-                const int x = i ^ jj;
-                if (x > i) {
-                    const unsigned ka = kk[i], kb = kk[x];
-                    if ((ka > kb) == ((i & k) == 0)) { kk[i] = kb; kk[x] = ka; const unsigned va = vv[i]; vv[i] = vv[x]; vv[x] = va; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // ---- this thread's cells
-    unsigned oi[CELLS][PPT];
-    f32x2 px[CELLS][NP], py[CELLS][NP], pz[CELLS][NP];
-    float clo[CELLS][3], chi[CELLS][3];
-    bool cell_ok[CELLS];
-#pragma unroll
-    for (int c = 0; c < CELLS; ++c) {
-        cell_ok[c] = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { clo[c][a] = INFINITY; chi[c][a] = -INFINITY; }
-#pragma unroll
-        for (int s2 = 0; s2 < PPT; ++s2) {
-            oi[c][s2] = vv[(c * T + tid) * PPT + s2];
-            const bool ok = oi[c][s2] != 0xFFFFFFFFu;
-            cell_ok[c] = cell_ok[c] || ok;
-            const float x = ok ? P[oi[c][s2] * 3 + 0] : 0.f, y = ok ? P[oi[c][s2] * 3 + 1] : 0.f, z = ok ? P[oi[c][s2] * 3 + 2] : 0.f;
-            px[c][s2 >> 1][s2 & 1] = x; py[c][s2 >> 1][s2 & 1] = y; pz[c][s2 >> 1][s2 & 1] = z;
-            if (ok) { clo[c][0] = fminf(clo[c][0], x); chi[c][0] = fmaxf(chi[c][0], x); clo[c][1] = fminf(clo[c][1], y); chi[c][1] = fmaxf(chi[c][1], y);
-                      clo[c][2] = fminf(clo[c][2], z); chi[c][2] = fmaxf(chi[c][2], z); }
-        }
-    }
-    __syncthreads();                                  // the sort arrays are dead: the same LDS becomes the copy of the sample
-    for (int i0 = tid; i0 < 3 * n; i0 += 8 * T) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = i0 + u * T < 3 * n ? P[i0 + u * T] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) if (i0 + u * T < 3 * n) pts[i0 + u * T] = v[u];
-    }
-    __syncthreads();
-    unsigned tmpb[CELLS][PPT], bd[CELLS], boi[CELLS];
-    auto cell_argmax = [&](int c) {
-        unsigned d = 0u;
-#pragma unroll
-        for (int s2 = 0; s2 < PPT; s2 += 2) d = max(d, max(tmpb[c][s2], tmpb[c][s2 + 1]));
-        unsigned o = 0xFFFFFFFFu;
-#pragma unroll
-        for (int s2 = 0; s2 < PPT; s2 += 2)
-            o = min(o, min(tmpb[c][s2] == d ? oi[c][s2] : 0xFFFFFFFFu, tmpb[c][s2 + 1] == d ? oi[c][s2 + 1] : 0xFFFFFFFFu));
-        bd[c] = d; boi[c] = o;
-    };
-    bool any_ok = false;
-#pragma unroll
-    for (int c = 0; c < CELLS; ++c) {
-#pragma unroll
-        for (int s2 = 0; s2 < PPT; ++s2) tmpb[c][s2] = oi[c][s2] != 0xFFFFFFFFu ? __float_as_uint(1e10f) : 0u;
-        cell_argmax(c);
-        any_ok = any_ok || cell_ok[c];
-    }
-    int cur = 0;
-    unsigned long long best = 0ull;                   // this wave's key, kept across the rounds in which the wave skips
-    if (tid == 0 && m > 0) idx_out[(int64_t)b * m] = b * n;
-    for (int j = 1; j < m; ++j) {
-        const float cx = pts[cur * 3 + 0], cy = pts[cur * 3 + 1], cz = pts[cur * 3 + 2];
-        bool scanned = false;
-#pragma unroll
-        for (int c = 0; c < CELLS; ++c) {
-            const float ex = fmaxf(fmaxf(clo[c][0] - cx, cx - chi[c][0]), 0.f), ey = fmaxf(fmaxf(clo[c][1] - cy, cy - chi[c][1]), 0.f),
-                        ez = fmaxf(fmaxf(clo[c][2] - cz, cz - chi[c][2]), 0.f);
-            const float lb = (ex * ex + ey * ey) + ez * ez;
-            const bool need = cell_ok[c] && __float_as_uint(lb) < bd[c];
-            if (__builtin_amdgcn_ballot_w64(need) != 0ull) {          // wave-uniform: some cell of slot c can change
-                const f32x2 cx2 = {cx, cx}, cy2 = {cy, cy}, cz2 = {cz, cz};
-#pragma unroll
-                for (int p2 = 0; p2 < NP; ++p2) {
-                    const f32x2 dx = px[c][p2] - cx2, dy = py[c][p2] - cy2, dz = pz[c][p2] - cz2;
-                    const f32x2 d = (dx * dx + dy * dy) + dz * dz;
-                    tmpb[c][2 * p2] = min(tmpb[c][2 * p2], __float_as_uint(d[0]));
-                    tmpb[c][2 * p2 + 1] = min(tmpb[c][2 * p2 + 1], __float_as_uint(d[1]));
-                }
-                cell_argmax(c);
-                scanned = true;
-            }
-        }
-        if (scanned || j == 1) {
-            // this thread's best over its cells: (distance bits, lowest original index)
-            unsigned tb = bd[0], to = boi[0];
-#pragma unroll
-            for (int c = 1; c < CELLS; ++c) {
-                const bool better = bd[c] > tb || (bd[c] == tb && boi[c] < to);
-                tb = better ? bd[c] : tb; to = better ? boi[c] : to;
-            }
-            const unsigned wmax = wave_max_u32(any_ok ? tb : 0u);
-            const unsigned long long holders = __builtin_amdgcn_ballot_w64(any_ok && tb == wmax);
-            best = 0ull;
-            if (holders) {
-                unsigned wbi;
-                if ((holders & (holders - 1)) == 0) wbi = (unsigned)__builtin_amdgcn_readlane((int)to, __builtin_ctzll(holders));
-                else wbi = wave_min_u32((any_ok && tb == wmax) ? to : 0xFFFFFFFFu);
-                best = ((unsigned long long)wmax << 32) | (unsigned long long)(0xFFFFFFFFu - wbi);
-            }
-        }
-        if (lane == 0) keys[j & 1][wave] = best;
-        __syncthreads();
-        const bool has = (lane & 15) < nw;
-        const unsigned long long kw = keys[j & 1][has ? (lane & 15) : 0];
-        const unsigned khi = has ? (unsigned)(kw >> 32) : 0u, klo = has ? (unsigned)kw : 0u;
-        unsigned gm = khi;
-        gm = max(gm, dpp_u32<0xB1>(gm)); gm = max(gm, dpp_u32<0x4E>(gm)); gm = max(gm, dpp_u32<0x141>(gm)); gm = max(gm, dpp_u32<0x140>(gm));
-        const unsigned long long hold2 = __builtin_amdgcn_ballot_w64(has && lane < 16 && khi == gm);
-        unsigned wlo;
-        if ((hold2 & (hold2 - 1)) == 0) wlo = (unsigned)__builtin_amdgcn_readlane((int)klo, __builtin_ctzll(hold2 | (1ull << 63)));
-        else wlo = wave_max_u32((has && khi == gm) ? klo : 0u);
-        cur = __builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu - wlo));
+        // (distance bits, lowest ORIGINAL index).  A wave that skipped the update holds the cells it held the round before: its key is
+        // unchanged and only re-published
+        if (scan || j == 1) best = fps_wave_key(cell_ok, bd, boi);
+        cur = fps_workgroup_pick(keys, j, best, lane, wave, nw);
         if (tid == 0) idx_out[(int64_t)b * m + j] = b * n + cur;
     }
 }
@@ -1036,100 +697,40 @@ extern "C" int afm_segment_mean(const float* x, float* out, int32_t B, int32_t n
     return 0;
 }
 
+// The kernel a plan names (nullptr: unsupported).  These ten are every (form, ppt) fps_plan can return, and the only FPS kernels compiled.
+// The second template argument of fps_kernel is its __launch_bounds__, i.e. its register budget, not the launch's thread count.
+typedef void (*fps_kernel_fn)(const float*, int, int, int*);
+static fps_kernel_fn fps_kernel_of(const FpsPlan& pl) {
+    switch (pl.form) {
+        case FPS_PRUNED:
+            return pl.ppt == 2 ? fps_pruned_kernel<2, 1024> : pl.ppt == 4 ? fps_pruned_kernel<4, 1024> : fps_pruned_kernel<8, 1024>;
+        case FPS_PLAIN_LDS:
+            switch (pl.ppt) {
+                case 1: return fps_kernel<1, 1024, true>;
+                case 2: return fps_kernel<2, 1024, true>;
+                case 4: return fps_kernel<4, 1024, true>;
+                case 8: return fps_kernel<8, 1024, true>;
+                case 16: return fps_kernel<16, 1024, true>;
+                default: return fps_kernel<32, 512, true>;
+            }
+        case FPS_PLAIN_GLOBAL: return fps_kernel<32, 512, false>;
+        default: return nullptr;
+    }
+}
+
 extern "C" int afm_fps(const float* xyz, int32_t B, int32_t n, int32_t m, int32_t* idx_out, void* stream) {
     if (!xyz || !idx_out || B < 0 || n <= 0 || m < 0 || m > n) return AFM_E_BADARG;
     if (B == 0 || m == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    {   // exact pruning of the scan (fps_pruned_kernel): PT threads, np2 / PT Morton-consecutive points per thread
-        int np2 = 2048;
-        while (np2 < n) np2 <<= 1;
-        bool prune = n >= 1536 && np2 <= 8192 && m >= 32;
-        int PT = 1024;
-#ifdef AFM_PROBE
-        if (afm_probe_fps_prune == 0) prune = false;
-        if (afm_probe_fps_prune > 0) PT = afm_probe_fps_prune;
-#endif
-        if (prune && AFM_FPS_KS == 1 && AFM_FPS_CELLS > 1 && PT == 1024) {
-            // round 6: CELLS cells of 8 sorted points per thread on 1024 / CELLS threads (same cells, same pruning, fewer waves to pay the per-wave overheads)
-            AfmProf prof(AFM_PROF_FPS, (double)B * (m - 1) * n, s);
-            const size_t lds = (size_t)max(3 * n, 2 * np2) * sizeof(float);
-            constexpr int TC = 1024 / AFM_FPS_CELLS;
-#define AFM_FPS_CELLS_GO(P)                                                                                                                 \
-    do {                                                                                                                            \
-        if (lds > 48 * 1024) {                                                                                                      \
-            hipError_t e__ = hipFuncSetAttribute((const void*)fps_cells_kernel<P, TC, AFM_FPS_CELLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-            if (e__ != hipSuccess) return (int)e__;                                                                                 \
-        }                                                                                                                           \
-        hipLaunchKernelGGL((fps_cells_kernel<P, TC, AFM_FPS_CELLS>), dim3(B), dim3(TC), lds, s, xyz, n, m, idx_out);                \
-    } while (0)
-            if (np2 == 2048) AFM_FPS_CELLS_GO(2);
-            else if (np2 == 4096) AFM_FPS_CELLS_GO(4);
-            else AFM_FPS_CELLS_GO(8);
-#undef AFM_FPS_CELLS_GO
-            AFM_CHECK_LAUNCH();
-            return 0;
-        }
-        if (prune) {
-            AfmProf prof(AFM_PROF_FPS, (double)B * (m - 1) * n, s);
-            const size_t lds = (size_t)max(3 * n, 2 * np2) * sizeof(float);
-#define AFM_FPS_PRUNED(P, PT_)                                                                                                          \
-    do {                                                                                                                            \
-        if (lds > 48 * 1024) {                                                                                                      \
-            hipError_t e__ = hipFuncSetAttribute((const void*)fps_pruned_kernel<P, PT_, AFM_FPS_KS>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-            if (e__ != hipSuccess) return (int)e__;                                                                                 \
-        }                                                                                                                           \
-        hipLaunchKernelGGL((fps_pruned_kernel<P, PT_, AFM_FPS_KS>), dim3(B), dim3(PT_), lds, s, xyz, n, m, idx_out);                \
-    } while (0)
-#define AFM_FPS_PRUNED_T(PT_)                                                                                                           \
-    do {                                                                                                                            \
-        if (np2 == 2048) AFM_FPS_PRUNED(2048 / PT_, PT_);                                                                           \
-        else if (np2 == 4096) AFM_FPS_PRUNED(4096 / PT_, PT_);                                                                      \
-        else AFM_FPS_PRUNED(8192 / PT_, PT_);                                                                                       \
-    } while (0)
-            if (PT == 256) AFM_FPS_PRUNED_T(256);
-            else if (PT == 512) AFM_FPS_PRUNED_T(512);
-            else AFM_FPS_PRUNED_T(1024);
-#undef AFM_FPS_PRUNED_T
-#undef AFM_FPS_PRUNED
-            AFM_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    // Threads per workgroup: a round is a dependent chain (per-thread scan -> wave arg-max -> LDS hop -> barrier -> broadcast) on ONE
-    // compute unit per sample.  Its VALU work (n points x 8 instructions: ~1100 issue cycles of the ~2100-cycle round at n = 8192) is
-    // the same for every split, the reductions are not: 0.94 / 0.96 / 0.91 us per round with 1024 / 512 / 256 threads
-    // (profiles/r02_points_probe.txt).  Results do not depend on the split.
-    int T = (((n + 31) / 32 + 63) / 64) * 64;
-    if (T < 64) T = 64;
-    if (T > 512) T = 512;
-    if ((n + T - 1) / T > 32) T = 1024;              // n > 16384: the round-1 shape (up to 16 points per thread)
-#ifdef AFM_PROBE               // tools/points_probe.hip only: threads per workgroup override for experiments
-    if (afm_probe_fps_threads > 0) T = afm_probe_fps_threads;
-#endif
-    const int ppt = (n + T - 1) / T;
+    const FpsPlan pl = fps_plan(n, m);
+    const fps_kernel_fn kernel = fps_kernel_of(pl);
+    if (!kernel) return AFM_E_UNSUPPORTED;
     AfmProf prof(AFM_PROF_FPS, (double)B * (m - 1) * n, s);
-    const size_t lds = (size_t)3 * n * sizeof(float);
-    const int in_lds = lds <= 150 * 1024 ? 1 : 0;
-#define AFM_FPS(P, MT)                                                                                                              \
-    do {                                                                                                                            \
-        if (in_lds) {                                                                                                               \
-            if (lds > 48 * 1024) {                                                                                                  \
-                hipError_t e__ = hipFuncSetAttribute((const void*)fps_kernel<P, MT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-                if (e__ != hipSuccess) return (int)e__;                                                                             \
-            }                                                                                                                       \
-            hipLaunchKernelGGL((fps_kernel<P, MT, true>), dim3(B), dim3(T), lds, s, xyz, n, m, idx_out);                            \
-        } else {                                                                                                                    \
-            hipLaunchKernelGGL((fps_kernel<P, MT, false>), dim3(B), dim3(T), 0, s, xyz, n, m, idx_out);                             \
-        }                                                                                                                           \
-    } while (0)
-    if (T <= 512 && ppt > 16 && ppt <= 32) AFM_FPS(32, 512);
-    else if (ppt <= 1) AFM_FPS(1, 1024);
-    else if (ppt <= 2) AFM_FPS(2, 1024);
-    else if (ppt <= 4) AFM_FPS(4, 1024);
-    else if (ppt <= 8) AFM_FPS(8, 1024);
-    else if (ppt <= 16) AFM_FPS(16, 1024);
-    else return AFM_E_UNSUPPORTED;
-#undef AFM_FPS
+    if (pl.lds_bytes > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FPS_LDS_LIMIT);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(pl.threads), pl.lds_bytes, s, xyz, n, m, idx_out);
     AFM_CHECK_LAUNCH();
     return 0;
 }

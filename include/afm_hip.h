@@ -460,6 +460,7 @@ int afm_adamw_multi(const afm_adamw_tensor* d_table, int32_t n_tensors, int64_t 
  * afm_fps replaces pointops_cuda.furthestsampling_cuda (pointops.py:10-27; called from
  * TransitionDown.forward, pointtransformer.py:61): start at the sample's first point, running
  * min squared distance initialised to 1e10, arg-max each round (ties -> lowest index).
+ * n <= 16384 points per sample; beyond that afm_fps returns AFM_E_UNSUPPORTED (before any launch).
  * afm_knn replaces pointops_cuda.knnquery_cuda (pointops.py:30-45): brute force, neighbours in
  * ascending (dist2, index) order; dist2 is the SQUARED distance (the wrapper's sqrt is the caller's).
  * Both evaluate d2 = (dx*dx + dy*dy) + dz*dz in float32 without fma contraction (bit-exact indices

@@ -25,6 +25,31 @@ def test_fps_bit_exact(B, n, m):
     assert torch.equal(got, want), f"{(got != want).sum().item()} of {got.numel()} indices differ"
 
 
+_FPS_EDGES = [64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 1535, 1536, 2048, 2049, 4096, 4097, 8192, 8193, 12800, 12801, 16384]
+
+
+@pytest.mark.parametrize("n,m", [(n, min(n, 40)) for n in _FPS_EDGES] + [(1536, 31), (16384, 2)])
+def test_fps_on_both_sides_of_every_dispatch_boundary(n, m):
+    """csrc/fps_plan.h changes kernel between n and n + 1 at each of these sizes (tests/test_fps_plan_host.py pins the rule itself); at
+    n = 1536 also between m = 31 (plain kernel) and m = 32 (pruned).  12800 < n <= 16384 is the only range of the kernel that reads the winner's
+    coordinates from global memory (12 n bytes exceed the LDS budget): 12801, 16384, and (16384, 2) as its shortest run.
+    Two samples, so the second one's row offset is exercised.  Bit-exact against the oracle."""
+    from oracle import pointops_ref as po
+    B = 2
+    p = synth.scene_cloud(B, n, seed=29).reshape(B * n, 3)
+    want = po.furthest_sampling(p, torch.tensor([n, 2 * n], dtype=torch.int32), torch.tensor([m, 2 * m], dtype=torch.int32))
+    got = pointops.furthest_point_sampling(p.to(dev()), B, n, m).cpu()
+    assert torch.equal(got, want), f"{(got != want).sum().item()} of {got.numel()} indices differ"
+
+
+def test_fps_refuses_more_than_16384_points():
+    """include/afm_hip.h: n <= 16384.  The refusal (AFM_E_UNSUPPORTED) is returned before any launch."""
+    from afm import ffi
+    p = torch.zeros(16385, 3, device=dev())
+    with pytest.raises(ffi.AfmError, match="afm_fps failed: unsupported shape"):
+        pointops.furthest_point_sampling(p, 1, 16385, 2)
+
+
 def test_fps_ties_pick_lowest_index():
     # duplicated points (real chunks contain them, prepare/generate_contact_data.py:418-423): ties -> lowest index
     from oracle import pointops_ref as po
@@ -41,9 +66,8 @@ def test_fps_ties_across_lanes_and_waves(n, shift, m):
     """Every point twice, the copies `shift` rows apart: the two holders of every maximum sit in different lanes and (n = 8192: 4 waves,
     n = 2048: 1 wave of 32-point threads) different waves, so each round exercises the tie paths of the wave-level and of the workgroup-level
     arg-max (ballot with more than one holder -> lowest index).  m above the number of DISTINCT points (round 6: 3000 of 2048, 8192 of 4096) runs
-    the rounds in which every remaining minimum is zero - where the several-samples-per-round form of fps_pruned_kernel must stop extending a
-    round (a candidate is only taken while its distance is strictly above the second-best distance of the waves already taken from, which
-    excludes distance 0).  Bit-exact against the oracle."""
+    the rounds in which every remaining minimum is zero: all wave keys tie at distance 0, no box test of fps_pruned_kernel asks for a scan
+    (no lower bound is below a maximum of 0), and the pick is the lowest index of the sample, round after round.  Bit-exact against the oracle."""
     from oracle import pointops_ref as po
     base = synth.scene_cloud(1, n // 2, seed=27).reshape(n // 2, 3)
     p = torch.cat([base, base.roll(shift, 0)], 0).contiguous()
