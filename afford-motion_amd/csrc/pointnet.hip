@@ -18,6 +18,7 @@
 namespace {
 
 constexpr int BK = 32, LDK = 36, TD_K = 16;
+constexpr size_t PT_LDS_LIMIT = 160 * 1024;          // LDS of one gfx950 workgroup
 
 __global__ __launch_bounds__(256, 2) void transition_down_kernel(const float* __restrict__ p, const float* __restrict__ x, int c,
                                                                  const float* __restrict__ n_p, const int* __restrict__ knn,
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(256) void pt_attention_kernel(const PtAttnArgs a) {
         {   // ---- phase B ((neighbour, weight-channel)-parallel): Linear(C -> C/s) + BN + ReLU
             float accu[NE];
 #pragma unroll
-            for (int e = 0; e < NE; ++e) accu[e] = b2;
+            for (int e = 0; e < NE; ++e) accu[e] = 0.f;              // the bias joins the finished sum (see phase C)
             for (int ch = 0; ch < C; ++ch) {
                 const float wv = a.w2_lds ? W2T[ch * CS + tt] : a.w2_w[(int64_t)tt * C + ch];
 #pragma unroll
@@ -228,14 +229,17 @@ __global__ __launch_bounds__(256) void pt_attention_kernel(const PtAttnArgs a) {
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 const int j = jb + e * jstep;
-                if (j < KN) u[j * CS + tt] = fmaxf(accu[e] * s3 + t3, 0.f);
+                if (j < KN) u[j * CS + tt] = fmaxf((accu[e] + b2) * s3 + t3, 0.f);
             }
         }
         __syncthreads();
         {   // ---- phase C: Linear(C/s -> C/s)
             float z[NE];
 #pragma unroll
-            for (int e = 0; e < NE; ++e) z[e] = b5;
+            // the sum starts at 0 and the bias is added to it once: started AT the bias, every one of the CS partial sums is rounded at
+            // the bias's size - with b5 + 1e4 (softmax is shift-invariant) that order, emulated on the host, is 2.4 (CS = 8) and 3.4 (CS = 32)
+            // times less exact than torch's
+            for (int e = 0; e < NE; ++e) z[e] = 0.f;
             for (int t2 = 0; t2 < CS; ++t2) {
                 const float wv = W5T[t2 * CS + tt];
 #pragma unroll
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(256) void pt_attention_kernel(const PtAttnArgs a) {
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 const int j = jb + e * jstep;
-                if (j < KN) att[j * CS + tt] = z[e];
+                if (j < KN) att[j * CS + tt] = z[e] + b5;
             }
         }
         __syncthreads();
@@ -314,24 +318,28 @@ extern "C" int afm_pt_attention(const afm_pt_attention_args* g, void* stream) {
     a.w2_lds = C <= 256 ? 1 : 0;
     const int nwv = C <= 256 ? 4 : 1;                // the 512-channel level has N/256 points per sample: one wave per block
     const size_t lds = (size_t)((a.w2_lds ? C * CS : 0) + CS * CS + nwv * (KN * (C + 1) + 2 * KN * CS)) * sizeof(float);
+    if (KN == 8 ? (ne > 4 || cpl > 4 || !a.w2_lds) : (ne > 16 || cpl > 8)) return AFM_E_UNSUPPORTED;       // no instantiation (KN = 8 is not built for C > 256)
+    // a workgroup of gfx950 addresses at most 160 KB of LDS: a shape beyond it (e.g. C = 256, share_planes = 4, nsample = 16: 180 480 bytes)
+    // is refused here, before anything is launched
+    if (lds > PT_LDS_LIMIT) return AFM_E_UNSUPPORTED;
     int quads = (g->n + nwv - 1) / nwv;
     const dim3 grid(quads < 2048 ? quads : 2048), block(64 * nwv);
     hipStream_t s = (hipStream_t)stream;
     AfmProf prof(AFM_PROF_PTATTN, 2.0 * g->n * KN * ((double)C * CS + CS * CS + 5.0 * C), s);
 #define AFM_PT(CPL_, KN_, NE_)                                                                                             \
     do {                                                                                                                   \
-        if (lds > 64 * 1024)                                                                                               \
-            (void)hipFuncSetAttribute((const void*)pt_attention_kernel<CPL_, KN_, NE_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                                 \
+        if (lds > 64 * 1024) {                                                                                             \
+            const hipError_t e_ = hipFuncSetAttribute((const void*)pt_attention_kernel<CPL_, KN_, NE_>,                       \
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
+            if (e_ != hipSuccess) return (int)e_;                                                                          \
+        }                                                                                                                  \
         hipLaunchKernelGGL((pt_attention_kernel<CPL_, KN_, NE_>), grid, block, lds, s, a);                                 \
     } while (0)
     if (KN == 8) {
-        if (ne > 4 || cpl > 4 || !a.w2_lds) return AFM_E_UNSUPPORTED;
         if (cpl == 1 && ne <= 1) AFM_PT(1, 8, 1);
         else if (cpl <= 2 && ne <= 2) AFM_PT(2, 8, 2);
         else AFM_PT(4, 8, 4);
     } else {
-        if (ne > 16 || cpl > 8) return AFM_E_UNSUPPORTED;
         if (cpl == 1 && ne <= 2) AFM_PT(1, 16, 2);
         else if (cpl <= 2 && ne <= 4) AFM_PT(2, 16, 4);
         else if (cpl <= 4 && ne <= 8) AFM_PT(4, 16, 8);

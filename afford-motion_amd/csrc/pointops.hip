@@ -5,6 +5,10 @@
 //   d2 = (dx*dx + dy*dy) + dz*dz in float32 with fma contraction OFF;
 //   FPS: start at the first point of the sample, tmp initialised to 1e10, ties -> lowest index;
 //   kNN: neighbours ascending in (d2, index) lexicographic order.
+// Non-finite coordinates (include/afm_hip.h, "the kNN / FPS contract"): a candidate whose d2 is NaN or +inf is not a neighbour; with
+// j < k neighbours the entries j .. k-1 repeat entry j-1, with none every entry is (b*n, +inf).  Every output entry is written and every
+// index lies in its sample: no address and no trip count below depends on a coordinate's VALUE (the Morton keys are clamped before they
+// are converted and only order a permutation; boxes are built with fminf / fmaxf, which drop a NaN).
 // Every sample has the same point count, so batch offsets are implicit (sample b owns rows
 // [b*n, (b+1)*n)); returned indices are GLOBAL row numbers like the reference's.
 //
@@ -72,7 +76,8 @@ __global__ __launch_bounds__(MAXT) void fps_kernel(const float* __restrict__ xyz
     const int b = blockIdx.x, T = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
     const float* P = xyz + (int64_t)b * n * 3;
     f32x2 px[NP], py[NP], pz[NP];
-    // running minimum distance of every slot, kept as BITS: distances are sums of squares (>= +0, never NaN), so unsigned order is
+    // running minimum distance of every slot, kept as BITS: distances are sums of squares (>= +0; NaN or +inf only from coordinates that
+    // are not finite, and those bits lie above 1e10's, so the minimum never stores them), so unsigned order is
     // float order and v_min_u32 replaces fminf (no canonicalisation of the operands, the bits feed the arg-max directly).  A slot
     // without a point starts at 0 and stays there: it can never beat the strict '>' below (what the per-slot validity select did).
     unsigned tmpb[2 * NP];
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(T) void fps_pruned_kernel(const float* __restrict__
         if (i < n) {
             unsigned q[3];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) { const float f = (P[i * 3 + a] - lo3[a]) * hi3[a]; q[a] = (unsigned)min(1023, max(0, (int)f)); }
+            for (int a = 0; a < 3; ++a) { const float f = (P[i * 3 + a] - lo3[a]) * hi3[a]; q[a] = (unsigned)(int)fminf(fmaxf(f, 0.f), 1023.f); }      // (clamped as a float: a NaN becomes 0, no conversion is out of range)
             key = morton_part10(q[0]) | (morton_part10(q[1]) << 1) | (morton_part10(q[2]) << 2);
         }
         kk[i] = key; vv[i] = i < n ? (unsigned)i : 0xFFFFFFFFu;
@@ -361,7 +366,9 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ xyz,
     if (valid) {
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            if (j > 0 && bi[j] < 0) { bi[j] = bi[j - 1]; bd[j] = bd[j - 1]; }     // fewer than K points: repeat the last
+            // fewer than K candidates at a finite distance (`d < bd[K - 1]` never takes a NaN or +inf): repeat the last one; none at
+            // all: the sample's first row at +inf (bd[0] still holds it).  No entry leaves the sample, whatever the coordinates are.
+            if (bi[j] < 0) { bi[j] = j > 0 ? bi[j - 1] : 0; bd[j] = j > 0 ? bd[j - 1] : INFINITY; }
             idx_out[((int64_t)b * m + q) * K + j] = b * n + bi[j];
             d2_out[((int64_t)b * m + q) * K + j] = bd[j];
         }
@@ -418,7 +425,7 @@ __global__ __launch_bounds__(1024) void knn_sort_kernel(const float* __restrict_
         if (i < cnt) {
             unsigned q[3];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) { const float f = (P[i * 3 + a] - lo3[a]) * hi3[a]; q[a] = (unsigned)min(1023, max(0, (int)f)); }
+            for (int a = 0; a < 3; ++a) { const float f = (P[i * 3 + a] - lo3[a]) * hi3[a]; q[a] = (unsigned)(int)fminf(fmaxf(f, 0.f), 1023.f); }      // (clamped as a float: a NaN becomes 0, no conversion is out of range)
             key = morton_part10(q[0]) | (morton_part10(q[1]) << 1) | (morton_part10(q[2]) << 2);
         }
         kk[i] = key; vv[i] = i < cnt ? (unsigned)i : 0xFFFFFFFFu;
@@ -471,7 +478,9 @@ template <int K>
 __global__ __launch_bounds__(256) void knn_pruned_kernel(const float4* __restrict__ cs4, const float* __restrict__ tbox, const float4* __restrict__ qs4, int n, int m,
                                                          int nt, int* __restrict__ idx_out, float* __restrict__ d2_out) {
     constexpr int BUF = 8;
-    constexpr unsigned long long EMPTY = ((unsigned long long)0x7F800000u << 32) | 0xFFFFFFFFull;      // (+inf, no index): nothing real is above it
+    // (+inf, index 0): the smallest key of a distance that is not finite (NaN bits of either sign lie above +inf's as unsigned numbers), so
+    // `key < bk[K - 1]` never takes such a candidate - nor the (inf, inf, inf) padding of a ragged tile - and a slot is empty iff it is >= EMPTY
+    constexpr unsigned long long EMPTY = (unsigned long long)0x7F800000u << 32;
     __shared__ float4 tile[4][KNN_TS];
     __shared__ unsigned long long buf[4][BUF + 1][64];                  // [wave][entry][lane], row BUF = dump row
     __shared__ unsigned long long mk[4][K][64];                         // the sorted lists at the end: [wave][position][lane]
@@ -574,13 +583,17 @@ __global__ __launch_bounds__(256) void knn_pruned_kernel(const float4* __restric
             kd = bound();
         }
     }
-    // ---- merge the four lists of every query by rank
+    // ---- merge the four lists of every query by rank: real keys go to their rank in the query's merged list (the drained append buffer
+    // of this wave, [rank][query]); the list's length is the number of finite-distance candidates found, at most K
 #pragma unroll
     for (int j = 0; j < K; ++j) mk[wave][j][lane] = bk[j];
     __builtin_amdgcn_wave_barrier();
     int rank[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) rank[j] = j;
+    int found = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) found += bk[j] < EMPTY ? 1 : 0;
 #pragma unroll
     for (int o = 1; o < 4; ++o) {
         const int other = qi + 16 * ((sub + o) & 3);
@@ -588,17 +601,26 @@ __global__ __launch_bounds__(256) void knn_pruned_kernel(const float4* __restric
 #pragma unroll
         for (int i = 0; i < K; ++i) ok[i] = mk[wave][i][other];
 #pragma unroll
+        for (int i = 0; i < K; ++i) found += ok[i] < EMPTY ? 1 : 0;
+#pragma unroll
         for (int j = 0; j < K; ++j)
 #pragma unroll
             for (int i = 0; i < K; ++i) rank[j] += ok[i] < bk[j] ? 1 : 0;
     }
-    if (valid) {
+    found = min(found, K);
+    unsigned long long* merged = &buf[wave][0][0];                      // K x 16 of its (BUF + 1) x 64 entries
 #pragma unroll
-        for (int j = 0; j < K; ++j)
-            if (rank[j] < K && (unsigned)bk[j] != 0xFFFFFFFFu) {         // (n >= 1024 > K: the K best of the union are real points)
-                idx_out[((int64_t)b * m + qorig) * K + rank[j]] = b * n + (int)(unsigned)bk[j];
-                d2_out[((int64_t)b * m + qorig) * K + rank[j]] = __uint_as_float((unsigned)(bk[j] >> 32));
-            }
+    for (int j = 0; j < K; ++j)
+        if (rank[j] < K && bk[j] < EMPTY) merged[rank[j] * 16 + qi] = bk[j];
+    __builtin_amdgcn_wave_barrier();
+    // every entry is written, by the sub-slot its position falls to: the found neighbours, then the last of them again (fewer than K
+    // candidates at a finite distance), or the sample's first row at +inf when there is none
+    if (valid) {
+        for (int r = sub; r < K; r += 4) {
+            const unsigned long long key = found > 0 ? merged[min(r, found - 1) * 16 + qi] : EMPTY;
+            idx_out[((int64_t)b * m + qorig) * K + r] = b * n + (int)(unsigned)key;
+            d2_out[((int64_t)b * m + qorig) * K + r] = __uint_as_float((unsigned)(key >> 32));
+        }
     }
 }
 
@@ -646,14 +668,39 @@ __global__ __launch_bounds__(256) void interpolate_bwd_kernel(const float* __res
     }
 }
 
-// out[b,:] = mean over the n rows of sample b  (grid B, block 256; c <= 4096)
+// out[b,:] = mean over the n rows of sample b, as a FIXED-ORDER blocked sum: row i of the sample goes to partial chain i % 64, a chain adds
+// its rows in ascending order from 0, the 64 chains are combined by the tree s[p] += s[p + h], h = 32, 16, ..., 1, and the total is divided
+// by n.  (One ascending chain over all n rows, the earlier form, leaves the float32 class at n >= 2048: 9.0e-7 on post-ReLU features at
+// n = 8192, where this order gives 3.3e-8 - DESIGN.md 4.6.)  The order is a function of the sample's rows alone: the same bits from run to
+// run, for every B and every position of the sample in the batch.  grid B x ceil(c / 32), block 256 = 8 row lanes x 32 channels; a thread
+// owns the chains rl, rl + 8, ..., rl + 56 of its channel: eight independent loads and adds per trip.
+constexpr int SM_CHAINS = 64, SM_CW = 32, SM_RL = 8;
 __global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restrict__ x, float* __restrict__ out, int n, int c) {
-    const int b = blockIdx.x;
-    for (int ch = threadIdx.x; ch < c; ch += blockDim.x) {
-        float s = 0.f;
-        for (int i = 0; i < n; ++i) s += x[((int64_t)b * n + i) * c + ch];
-        out[(int64_t)b * c + ch] = s / (float)n;
+    constexpr int PER = SM_CHAINS / SM_RL;
+    __shared__ float part[SM_CHAINS][SM_CW + 1];
+    const int tiles = (c + SM_CW - 1) / SM_CW, b = blockIdx.x / tiles;
+    const int cl = threadIdx.x & (SM_CW - 1), rl = threadIdx.x / SM_CW, ch = (blockIdx.x % tiles) * SM_CW + cl;
+    const bool ok = ch < c;
+    const float* X = x + (int64_t)b * n * c + (ok ? ch : 0);
+    float acc[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) acc[u] = 0.f;
+    for (int i0 = 0; i0 < n; i0 += SM_CHAINS) {
+        float v[PER];
+#pragma unroll
+        for (int u = 0; u < PER; ++u) { const int i = i0 + rl + SM_RL * u; v[u] = (ok && i < n) ? X[(int64_t)i * c] : 0.f; }
+#pragma unroll
+        for (int u = 0; u < PER; ++u) acc[u] += v[u];                  // (a chain's missing last row adds +0: the sum is unchanged)
     }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) part[rl + SM_RL * u][cl] = acc[u];
+    __syncthreads();
+#pragma unroll
+    for (int h = SM_CHAINS / 2; h > 0; h >>= 1) {
+        for (int e = threadIdx.x; e < h * SM_CW; e += 256) { const int p = e / SM_CW, q = e % SM_CW; part[p][q] += part[p + h][q]; }
+        __syncthreads();
+    }
+    if (rl == 0 && ok) out[(int64_t)b * c + ch] = part[0][cl] / (float)n;
 }
 
 }  // namespace
@@ -692,7 +739,9 @@ extern "C" int afm_segment_mean(const float* x, float* out, int32_t B, int32_t n
     if (B < 0 || n <= 0 || c <= 0) return AFM_E_BADARG;
     if (B == 0) return 0;
     if (!x || !out) return AFM_E_BADARG;
-    hipLaunchKernelGGL(segment_mean_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, out, n, c);
+    const int64_t blocks = (int64_t)B * ((c + SM_CW - 1) / SM_CW);
+    if (blocks > 0x7FFFFFFF) return AFM_E_UNSUPPORTED;
+    hipLaunchKernelGGL(segment_mean_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, out, n, c);
     AFM_CHECK_LAUNCH();
     return 0;
 }

@@ -465,6 +465,15 @@ int afm_adamw_multi(const afm_adamw_tensor* d_table, int32_t n_tensors, int64_t 
  * ascending (dist2, index) order; dist2 is the SQUARED distance (the wrapper's sqrt is the caller's).
  * Both evaluate d2 = (dx*dx + dy*dy) + dz*dz in float32 without fma contraction (bit-exact indices
  * against oracle/pointops_ref.py).  k in {3, 8, 16}.
+ *
+ * The kNN / FPS contract on coordinates that are not finite (afm_knn and afm_knn_ws alike, bit for bit against the oracle):
+ *  1. Every entry of idx_out and dist2_out is written, and every index lies in its own sample [b*n, (b+1)*n), whatever the
+ *     coordinates are - NaN, +-inf, or finite values whose squared difference overflows.  afm_fps likewise writes every index
+ *     in range (which points it samples from such a cloud is not specified further).
+ *  2. A candidate whose d2 to the query is not finite (NaN or +inf) is not a neighbour.
+ *  3. With j < k candidates at a finite distance (fewer than k points in the sample among them), entries j .. k-1 repeat entry j-1.
+ *  4. With j = 0 every entry is b*n with dist2 = +inf.
+ * The consumers (afm_transition_down, afm_pt_attention, afm_interpolate, afm_gather_rows) do not check the indices they are given.
  */
 int afm_fps(const float* xyz, int32_t B, int32_t n, int32_t m, int32_t* idx_out, void* stream);
 int afm_knn(int32_t k, const float* xyz, const float* new_xyz, int32_t B, int32_t n, int32_t m,
@@ -484,7 +493,10 @@ int afm_gather_rows(const float* src, const int32_t* idx, float* out, int64_t ro
 /* afm_interpolate: inverse-distance-weighted feature upsampling of pointops.interpolation (pointops.py:164-178):
  *   out[i,:] = base[i,:] + sum_j w_ij feat[idx[i,j],:],  w_ij = r_ij / sum_j r_ij,  r_ij = 1 / (sqrt(dist2[i,j]) + 1e-8)
  * idx / dist2 [n,k] come from afm_knn (k = 3); base may be NULL.  Fuses the `linear1(x1) +` of TransitionUp
- * (pointtransformer.py:98).  afm_segment_mean: per-sample mean over n rows (TransitionUp head mode, :90). */
+ * (pointtransformer.py:98).  afm_segment_mean: per-sample mean over n rows (TransitionUp head mode, :90), summed in float32 in a FIXED
+ * order - row i of a sample joins partial chain i mod 64, a chain adds its rows in ascending order, the chains are combined by the tree
+ * s[p] += s[p + h], h = 32 ... 1, the total is divided by n - which depends on the sample's rows alone: the same bits from run to run, for
+ * every B and every place of the sample in the batch. */
 int afm_interpolate(const float* feat, const int32_t* idx, const float* dist2, const float* base, float* out,
                     int64_t n, int32_t c, int32_t k, void* stream);
 int afm_segment_mean(const float* x, float* out, int32_t B, int32_t n, int32_t c, void* stream);
@@ -507,7 +519,12 @@ int afm_transition_down(const float* p, const float* x, int32_t c, const float* 
  *   p_r = lp3(ReLU(BN(lp0(p_j - p_i)))),  w = softmax_j(w5(ReLU(BN(w2(ReLU(BN(k_j - q_i + p_r))))))),
  *   out[i, c] = sum_j (v_j + p_r)[c] * w[j, c mod (C/share_planes)],  then optional out*out_scale+out_shift, ReLU.
  * qkv [n, 3C] = [linear_q(x) | linear_k(x) | linear_v(x)], knn_idx [n, nsample] (self-kNN, nsample 8 or 16).
- * BatchNorms are passed folded (scale, shift). */
+ * BatchNorms are passed folded (scale, shift).
+ * Shapes served: channels <= 512, channels % share_planes == 0 (else AFM_E_BADARG), C/share_planes a divisor of 64, nsample 8 (channels
+ * <= 256 only) or 16.  channels <= 256 runs four points per workgroup with w2 held in LDS, above that one point per workgroup with w2
+ * read from global memory.  A shape whose workgroup would need more than the 160 KB of LDS a gfx950 workgroup has - channels = 256,
+ * share_planes = 4, nsample = 16 asks for 180 480 bytes - is refused with AFM_E_UNSUPPORTED like every other unserved shape, before
+ * anything is launched and with `out` untouched. */
 typedef struct {
     const float* p; const float* qkv; const int32_t* knn_idx; float* out;
     int32_t n, channels, nsample, share_planes;

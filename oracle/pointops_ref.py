@@ -17,6 +17,16 @@ Rules we add (and the HIP kernels implement bit-exactly):
   d2 = (dx*dx + dy*dy) + dz*dz evaluated in float32 WITHOUT fma contraction;
   FPS ties -> lowest index; kNN order -> lexicographic (d2, index).
 
+The kNN / FPS contract on non-finite coordinates (include/afm_hip.h states the same; upstream has no rule):
+  1. every entry of idx and dist2 is written and every index lies in its own sample [b*n, (b+1)*n), whatever the
+     coordinates are; FPS likewise writes every index in range (and nothing more is promised of it);
+  2. a candidate whose d2 to the query is not finite (NaN or +inf: a NaN or infinite coordinate on either side, or
+     a difference whose square overflows) is not a neighbour;
+  3. with j < k candidates at a finite distance, entries j .. k-1 repeat entry j-1 (the n < k rule);
+  4. with j = 0 every entry is the sample's first row b*n with dist2 = +inf.
+`knn_query` masks by torch.isfinite BEFORE it builds its integer keys: the bits of a NaN with the sign set would
+otherwise sort first.  On finite input nothing changes.
+
 Why the tie rule cannot change a result.  Upstream's FPS kernel is the usual PointNet++ one: every thread scans a
 strided subset of the points and a shared-memory tree keeps `v2 > v1 ? i2 : i1`, so among EXACTLY equal running
 distances it prefers the lowest THREAD (point 1024, owned by thread 0, would beat point 1, owned by thread 1, once
@@ -83,17 +93,23 @@ def knn_query(nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor, offset: to
         n = p.shape[0]
         k = min(nsample, n)
         ar = torch.arange(n, dtype=torch.int64)[None, :]
+        never = torch.iinfo(torch.int64).max                           # above every real key
+        slot = torch.arange(nsample, dtype=torch.int64)[None, :]
         for c0 in range(s_m, e_m, chunk):
             c1 = min(c0 + chunk, e_m)
             d = _d2(new_xyz[c0:c1, None, :], p[None, :, :])            # [c, n]
-            key = (d.view(torch.int32).to(torch.int64) << 32) | ar      # d >= 0 so bits are monotone
+            fin = torch.isfinite(d)                                    # rule 2
+            key = (d.view(torch.int32).to(torch.int64) << 32) | ar      # finite d >= 0 so bits are monotone
+            key = torch.where(fin, key, torch.full_like(key, never))
             kk = torch.topk(key, k, dim=1, largest=False, sorted=True).values
             ii = (kk & 0xFFFFFFFF).to(torch.int64)
-            idx[c0:c1, :k] = (ii + s_n).to(torch.int32)
-            dist2[c0:c1, :k] = torch.gather(d, 1, ii)
-            if k < nsample:                                            # fewer points than k: repeat the last
-                idx[c0:c1, k:] = idx[c0:c1, k - 1:k]
-                dist2[c0:c1, k:] = dist2[c0:c1, k - 1:k]
+            found = fin.sum(1, keepdim=True).clamp(max=k)              # neighbours a query has: rule 3 repeats the last, rule 4 has none
+            take = torch.minimum(slot, (found - 1).clamp(min=0)).expand(c1 - c0, nsample)
+            ii = torch.gather(ii, 1, take.clamp(max=k - 1)).clamp(max=n - 1)   # (the clamp acts on a query without neighbours only)
+            dd = torch.gather(d, 1, ii)
+            none = (found == 0).expand(c1 - c0, nsample)
+            idx[c0:c1] = (torch.where(none, torch.zeros_like(ii), ii) + s_n).to(torch.int32)
+            dist2[c0:c1] = torch.where(none, torch.full_like(dd, float("inf")), dd)
         s_n, s_m = e_n, e_m
     return idx, dist2
 
