@@ -26,7 +26,7 @@ from . import autograd as AG
 from . import ffi, fold, ops
 from ._cache import HeldKey
 from .base import Model
-from .guidance import ContactGuidance, JointTargets, LongGuidance, MotionGuidance, scale_row, scale_value
+from .guidance import ContactGuidance, JointTargets, LongGuidance, MotionGuidance, SceneClearance, scale_row, scale_value
 from .scene import SceneMapEncoder, SceneMapEncoderDecoder
 from .text import TextEncoderMixin, lang_feat_dim_type
 
@@ -146,7 +146,8 @@ class LoopExtras(NamedTuple):
     """The ``_guidance`` of `CMDM.afm_native_loop`: what only this denoiser's native loop takes (a plain tuple in this order serves too).
     ``cfg`` / ``branch_streams``: GuidedCMDM's afm_cfg_args or afm_cfg2_args and its branch-stream switch.  ``guide``: an
     afm.diffusion.ContactGuidance (afm_cmdm_guide_loop_range), JointTargets or MotionGuidance (afm_cmdm_motion_guide_loop_range: the step's
-    gradient the sum of the terms that have started) - the gradient at every guided step's x_t is computed on the sub-batch's stream and
+    gradient the sum of the terms that have started), a SceneClearance or a MotionGuidance that carries one
+    (afm_cmdm_scene_guide_loop_range) - the gradient at every guided step's x_t is computed on the sub-batch's stream and
     enters the update launch; the loop runs in the separate-update form like an imputing one, and steps before the guidance starts launch
     what an imputing loop launches.  ``stitch``: an afm.diffusion.Stitch - the batch rows are overlapping windows of long motions and
     every step's update launch gives the frames two windows share one pred_xstart (afm_cmdm_stitch_loop_range, every deterministic
@@ -170,7 +171,8 @@ class LoopPlan(NamedTuple):
 
 def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, term: str = "none", stitch: bool = False) -> LoopPlan:
     """The entry a chain reaches: ``update`` "ddpm" / "ddim" / "dpm", ``guidance`` "none" / "cfg" (one scale) / "cfg2" (two), with or without
-    ``impute``, ``term`` "none" / "contact" (a bare ContactGuidance) / "motion" (anything that carries targets) / "long" (a LongGuidance:
+    ``impute``, ``term`` "none" / "contact" (a bare ContactGuidance) / "motion" (anything that carries targets) / "scene" (anything that carries a
+    SceneClearance) / "long" (a LongGuidance:
     only stitched, only with a deterministic update; the long description takes the guidance's slot and carries the stitch), stitched or not.  By
     priority: a term's entry, the stitched one, the 2M one (each runs every form it is asked for on a workspace of its own size: a history
     buffer, gradient buffers, sub-batches over long motions), then the entries of both updates (cfg2, impute), then one per update."""
@@ -184,7 +186,7 @@ def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, te
     ddim = "ddim_rows" if update == "ddim" else None
     ddpm = ("c1", "c2", "sigma") if update == "ddpm" else (None, None, None)
     tail = ("n_steps", "first_step", "seed", "sample_index0")
-    own = {"contact": "guide", "motion": "motion_guide", "long": "long_guide"}.get(term, "stitch" if stitch else None)
+    own = {"contact": "guide", "motion": "motion_guide", "scene": "scene_guide", "long": "long_guide"}.get(term, "stitch" if stitch else None)
     if own is not None:                 # both kinds of rows and the 2M rows, one of the three set
         last = ("stitch" if own == "stitch" else "term",)
         return LoopPlan(f"afm_cmdm_{own}_loop_range", f"afm_cmdm_{own}_loop_workspace_bytes", cfgs + last, (own, base),
@@ -638,7 +640,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             term, term_keep, kind, kind_key = None, None, "none", None
             gk_of = None                    # the description whose gk rows a range call sets
             if ex.guide is not None:
-                both = MotionGuidance(targets=ex.guide) if isinstance(ex.guide, JointTargets) else ex.guide
+                both = MotionGuidance(targets=ex.guide) if isinstance(ex.guide, JointTargets) else \
+                    MotionGuidance(clearance=ex.guide) if isinstance(ex.guide, SceneClearance) else ex.guide
                 term, term_fm, term_keep = both.describe(x, model_kwargs, diffusion)
                 gk_of = term
                 if isinstance(both, ContactGuidance):      # a bare contact term keeps its own entry
@@ -646,7 +649,10 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 else:                                                # anything that carries targets: the sum's entry (a LongGuidance: its own)
                     ct, tg = both.contact, both.targets
                     kind, kind_key = "motion", (None if ct is None else (ct.K, model_kwargs["c_pc_xyz"].shape[1]), None if tg is None else tg.K,
-                                                (ct or tg).joints is not None)
+                                                (ct or tg or getattr(both, "clearance", None)).joints is not None)
+                    sc = getattr(both, "clearance", None)
+                    if sc is not None:                               # anything that carries a clearance: the scene entry
+                        kind, kind_key = "scene", kind_key + (sc.K, model_kwargs["c_pc_xyz"].shape[1])
                 if isinstance(both, LongGuidance):         # no frame mask: validity is the geometry; gk rows per window, on its terms
                     kind, gk_of, long_key = "long", term.terms.contents, kind_key + (term.frames,)
                 else:

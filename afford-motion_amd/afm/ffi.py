@@ -231,6 +231,26 @@ class MotionGuide(C.Structure):
     _fields_ = [("contact", C.POINTER(ContactGuide)), ("targets", C.POINTER(JointTargets)), ("gk", c_f32p), ("frame_mask", C.c_void_p)]
 
 
+CLEAR_WAVES = 8                   # waves per block of the clearance kernel: the spans of its summation order
+CLEAR_TILE = 1024                 # points per LDS tile of the clearance kernel
+
+
+class SceneClearance(C.Structure):
+    """afm_scene_clearance (v7-additive): the scene-clearance description - scene points, point weights (or NULL), the contact map of
+    the exemption (or NULL) with its column count and threshold, de-normalisation, scale, the columns (or ``h3d``), a radius per joint,
+    the up axis and the floor height with its flag, and for the loops the term's own first guided step."""
+    _fields_ = [("q", c_f32p), ("weight", c_f32p), ("c", c_f32p), ("mean", c_f32p), ("std", c_f32p), ("scale", c_f32p),
+                ("cols", i32 * GUIDE_MAX_JOINTS), ("K", i32), ("N", i32), ("Kc", i32), ("exempt", i32), ("c_min", C.c_double),
+                ("radius", C.c_double * GUIDE_MAX_JOINTS), ("up", i32), ("has_min_height", i32), ("min_height", C.c_double),
+                ("first_guided", i32), ("t_start", i64), ("h3d", C.POINTER(H3dLayout))]
+
+
+class SceneGuide(C.Structure):
+    """afm_scene_guide (v7-additive): the sum of an afm_motion_guide (or NULL) and the scene clearance (or NULL) and, for the loops, the gk
+    rows [T][B] and the guidance's frame mask."""
+    _fields_ = [("terms", C.POINTER(MotionGuide)), ("clearance", C.POINTER(SceneClearance)), ("gk", c_f32p), ("frame_mask", C.c_void_p)]
+
+
 class Stitch(C.Structure):
     """afm_stitch (v7-additive): a batch of G * S overlapping windows of G long motions - windows per motion, shared frames of two
     neighbours, the device weight row [2][overlap] (wl then wr)."""
@@ -326,6 +346,15 @@ EXPORTS = {
                                                    C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p,
                                                    C.c_void_p, C.POINTER(MotionGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                                    C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_scene_guidance_workspace_bytes": (i64, [C.POINTER(SceneGuide), i32, i32, i32]),
+    "afm_scene_guidance": (C.c_int, [C.POINTER(SceneGuide), c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, C.c_void_p,
+                                     i64, C.c_void_p]),
+    "afm_cmdm_scene_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
+                                                        C.POINTER(SceneGuide)]),
+    "afm_cmdm_scene_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                                  C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p,
+                                                  C.c_void_p, C.POINTER(SceneGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                                  C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_cmdm_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
                                                   C.POINTER(ContactGuide)]),
     "afm_cmdm_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),

@@ -1,5 +1,5 @@
 """What a sampling chain is conditioned on besides the denoiser's own inputs: known values (`Impute`), overlapping windows of a long
-motion (`Stitch`), and the analytic ``cond_fn`` guidance terms (`ContactGuidance`, `JointTargets`, their sum `MotionGuidance`, and
+motion (`Stitch`), and the analytic ``cond_fn`` guidance terms (`ContactGuidance`, `JointTargets`, `SceneClearance`, their sum `MotionGuidance`, and
 `LongGuidance`, the terms on the joined long motion of a stitched chain).  The
 samplers of afm.diffusion take them, the native loops of afm.cmdm / afm.cdm read their descriptions; afm.diffusion re-exports every name
 (``afm.diffusion.Stitch is afm.guidance.Stitch``).  This module imports `ffi` and `ops` only: of a diffusion object it reads
@@ -274,7 +274,7 @@ def _guide_mask(x: torch.Tensor, model_kwargs, who: str):
 
 
 class _JointTerm:
-    """What `ContactGuidance` and `JointTargets` share: K joints named as column triples of absolute positions or (``.h3d``) as joints of
+    """What `ContactGuidance`, `JointTargets` and `SceneClearance` share: K joints named as column triples of absolute positions or (``.h3d``) as joints of
     HumanML3D features placed by ``to_scene``, the mean / std that de-normalise the motion, a scale per sample, ``t_start`` - and, per
     call, the pieces of the C description both fill the same way."""
     _NOUN = "guided"            # "1 to 16 <noun> joints" (_NAME: the class's name in its messages)
@@ -528,41 +528,166 @@ class JointTargets(_JointTerm):
         return MotionGuidance(targets=self).energies(x, **model_kwargs)[1]
 
 
-class MotionGuidance:
-    """The sum of a `ContactGuidance` and a `JointTargets` as one ``cond_fn`` (either may be None, not both):
-    grad = grad_contact + grad_targets, each term the float32 result of that guidance alone, joined by one rounded addition per element -
-    ``MotionGuidance(contact, targets)(x, t, **kw)`` equals ``contact(x, t, **kw) + targets(x, t, **kw)`` bit for bit.  Each term keeps its
-    own ``scale`` and ``t_start``: a sample (step by step) or a step (native loops) a term does not guide gets exactly zero from it.  The two
-    terms describe one motion: the same ``mean`` / ``std``, both on columns or both on HumanML3D features, the same ``to_scene`` -
-    ValueError otherwise.  The joint lists may differ; an h3d motion is recovered once per term.  Launches per guided step: the contact
-    term's 2 (h3d: 4) plus the targets' 1 (h3d: 3).  ``energies(x, **kw)`` returns (E_contact or None, E_targets or None)."""
+class SceneClearance(_JointTerm):
+    """A ``cond_fn`` that pushes joints off the obstacle points of the scene cloud - the one term that pushes: `ContactGuidance` and
+    `JointTargets` pull, this one keeps the skeleton out of the furniture (afm_scene_guidance, HIP; no network, no autograd).
 
-    def __init__(self, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None):
-        if contact is None and targets is None:
-            raise ValueError("MotionGuidance: at least one of contact / targets")
+    ``cols``: K ints (K <= 16) as for `ContactGuidance`; ``SceneClearance.h3d(joints, mean, std, to_scene=None, ...)`` names joints 0..21
+    of a HumanML3D-feature motion instead.  ``radius``: a positive float or K of them - a joint is pushed by the points closer than its
+    radius.  ``weight`` [B, N] float (None: every point weighs 1).  ``up`` (0..2) and ``min_height``: points with ``q[up] < min_height``
+    weigh 0 - that takes the floor out.  ``exempt_contact``: points whose largest ``c_pc_contact`` value over the map's joints is >= it
+    weigh 0 - what the contact map marks stays reachable.  ``scale``: a float or a [B] tensor.  ``t_start`` as for the other terms.
+    Read from ``model_kwargs``: ``c_pc_xyz`` [B, N, 3], ``x_mask``, and ``c_pc_contact`` [B, N, J] only with ``exempt_contact``.
+
+    With p[b,f,k,:] the positions the other terms compute, q the scene points and w[b,n] the obstacle weight, float32, each operation
+    rounded on its own, ir2[k] = float32(1 / r_k^2) and coef_k = float32(4 / r_k^2) formed in float64 and rounded once:
+
+        d = p - q_n;  d2 = (dx*dx + dy*dy) + dz*dz;  u = max(0, 1 - d2 * ir2[k]);  wu = w * u
+        E[b]       = sum over valid frames f, joints k, points n of  wu * u          (not normalised)
+        S[b,f,k,:] = sum_n wu * d
+        columns:  grad[b,f,cols[k]+a] = ((scale[b] * coef_k) * std_a) * S_a                                             (one launch)
+        h3d:      coef_k * S, rounded, carried through the adjoint of the recovery with scale[b] (three launches: recovery, clearance, adjoint)
+
+    ``guide(x, t, **model_kwargs)`` returns -scale[b] * dE/dx - u * u and its derivative both vanish at d = r, so the gradient is
+    continuous - exactly zero in every other column, in padded frames, in a sample with t >= t_start and in a joint-frame with no obstacle
+    point inside its radius.  ``guide.energy(x, **model_kwargs)`` returns E [B]; a sample whose frames are all padded has E = 0.
+
+    Order of the sums (no atomics; a function of the sample alone): the kernel runs 8 waves on tiles of 1024 points; for one joint-frame
+    wave v adds, from 0 and in ascending n, the points with (n mod 1024) // 128 == v, then S = ((((((s_0 + s_1) + s_2) + s_3) + s_4) + s_5)
+    + s_6) + s_7.  E[b]: blocks of 64 // K whole frames, lane i = (f - f0) * K + k adds its joint-frame's e over the blocks in order, then
+    a fixed wave butterfly.  Handed as ``cond_fn`` it stays in the native loops wherever the other terms do
+    (afm_cmdm_scene_guide_loop_range); `MotionGuidance` sums it with them."""
+    _NAME = "SceneClearance"
+
+    def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, radius, scale=1.0, t_start: Optional[int] = None, weight=None,
+                 up: int = 2, min_height: Optional[float] = None, exempt_contact: Optional[float] = None):
+        self._init(cols, None, None, mean, std, scale, t_start, radius=radius, weight=weight, up=up, min_height=min_height,
+                   exempt_contact=exempt_contact)
+
+    @classmethod
+    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, radius, to_scene: Optional[torch.Tensor] = None, scale=1.0,
+            t_start: Optional[int] = None, weight=None, up: int = 2, min_height: Optional[float] = None,
+            exempt_contact: Optional[float] = None) -> "SceneClearance":
+        """The clearance of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67): ``joints`` are joint indices 0..21, ``to_scene`` a
+        float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity).  See the class docstring."""
+        self = cls.__new__(cls)
+        self._init(None, joints, to_scene, mean, std, scale, t_start, radius=radius, weight=weight, up=up, min_height=min_height,
+                   exempt_contact=exempt_contact)
+        return self
+
+    def _own(self, radius, weight, up, min_height, exempt_contact) -> tuple:
+        who, K = self._who, self.K
+        try:
+            r = [float(radius)] * K if not hasattr(radius, "__len__") else [float(v) for v in radius]
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: radius must be a positive float or {K} of them, got {radius!r}") from None
+        if len(r) != K:
+            raise ValueError(f"{who}: radius must be a positive float or {K} of them, got {len(r)}")
+        if not all(v > 0.0 and v < float("inf") for v in r):
+            raise ValueError(f"{who}: every radius must be positive, got {r}")
+        if int(up) not in (0, 1, 2):
+            raise ValueError(f"{who}: up names a coordinate 0..2, got {up!r}")
+        if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dim() != 2 or not weight.is_floating_point()):
+            raise ValueError(f"{who}: weight must be a floating [B, N] tensor, got {tuple(getattr(weight, 'shape', ()))}")
+        self.radius, self.up = r, int(up)
+        self.min_height = None if min_height is None else float(min_height)
+        self.exempt_contact = None if exempt_contact is None else float(exempt_contact)
+        self.weight = None if weight is None else ffi.f32c(weight.detach())
+        return () if self.weight is None else (self.weight,)
+
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, shared=None) -> tuple:
+        """(afm_scene_clearance of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).
+        ``shared``: the (mean, std, to_scene, stride) device tensors of the term in front of it in a sum - a sum names one set of them."""
+        who = self._who
+        self._check_sample(x)
+        if "c_pc_xyz" not in model_kwargs:
+            raise ValueError("SceneClearance reads c_pc_xyz from model_kwargs")
+        B, q, c = x.shape[0], model_kwargs["c_pc_xyz"], None
+        if q.dim() != 3 or q.shape[0] != B or q.shape[2] != 3:
+            raise ValueError(f"SceneClearance: c_pc_xyz must be [{B}, N, 3], got {tuple(q.shape)}")
+        N = q.shape[1]
+        if self.exempt_contact is not None:
+            if model_kwargs.get("c_pc_contact") is None:
+                raise ValueError("SceneClearance: exempt_contact reads c_pc_contact from model_kwargs")
+            c = model_kwargs["c_pc_contact"]
+            if c.dim() != 3 or tuple(c.shape[:2]) != (B, N) or c.shape[2] < 1:
+                raise ValueError(f"SceneClearance: c_pc_contact must be [{B}, {N}, J], got {tuple(c.shape)}")
+        if self.weight is not None and tuple(self.weight.shape) != (B, N):
+            raise ValueError(f"{who}: weight is {tuple(self.weight.shape)}, the scene needs [{B}, {N}]")
+        scale_fits(self.scale, B, who)
+        fm = _guide_mask(x, model_kwargs, who)
+        ts, stride = self._to_scene_on(B, x.device)
+        ffi.require_gpu(x, q, c)
+        own = self._on(x.device)
+        mean, std, weight = own[0], own[1], own[2] if len(own) > 2 else None
+        scale = scale_row(self.scale, B, x.device, who)
+        q, c = ffi.f32c(q), None if c is None else ffi.f32c(c)
+        if shared is not None:
+            mean, std = shared[0], shared[1]
+            if self.joints is not None:
+                ts, stride = shared[2], shared[3]
+        g = ffi.SceneClearance()
+        lay = self._fill(g, mean, std, scale, ts, stride, diffusion)
+        g.q, g.weight, g.N, g.up = q.data_ptr(), ffi.ptr(weight), N, self.up
+        g.radius[:self.K] = self.radius
+        if c is not None:
+            g.c, g.Kc, g.exempt, g.c_min = c.data_ptr(), c.shape[2], 1, self.exempt_contact
+        if self.min_height is not None:
+            g.has_min_height, g.min_height = 1, self.min_height
+        return g, fm, (q, c, weight, mean, std, scale, fm, lay, ts)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        return MotionGuidance(clearance=self)(x, t, **model_kwargs)
+
+    def energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        g, fm, keep = MotionGuidance(clearance=self).describe(x, model_kwargs)
+        return ops.scene_guidance(g, x, fm, grad=False, energy=True)[3]
+
+
+class MotionGuidance:
+    """The sum of a `ContactGuidance`, a `JointTargets` and a `SceneClearance` as one ``cond_fn`` (each may be None, not all):
+    grad = grad_contact + grad_targets + grad_clearance in that order, each term the float32 result of that guidance alone, joined by one
+    rounded addition per element - ``MotionGuidance(contact, targets)(x, t, **kw)`` equals ``contact(x, t, **kw) + targets(x, t, **kw)`` bit
+    for bit, and with a clearance ``... + clearance(x, t, **kw)``.  Each term keeps its
+    own ``scale`` and ``t_start``: a sample (step by step) or a step (native loops) a term does not guide gets exactly zero from it.  The
+    terms describe one motion: the same ``mean`` / ``std``, all on columns or all on HumanML3D features, the same ``to_scene`` -
+    ValueError otherwise.  The joint lists may differ; an h3d motion is recovered once per term.  Launches per guided step: the contact
+    term's 2 (h3d: 4) plus the targets' 1 (h3d: 3) plus the clearance's 1 (h3d: 3).  ``energies(x, **kw)`` returns (E_contact or None,
+    E_targets or None); the clearance's value is ``guide.clearance.energy(x, **kw)``."""
+
+    def __init__(self, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None,
+                 clearance: Optional[SceneClearance] = None):
+        if contact is None and targets is None and clearance is None:
+            raise ValueError("MotionGuidance: at least one of contact / targets / clearance")
         if contact is not None and not isinstance(contact, ContactGuidance):
             raise TypeError(f"MotionGuidance: contact must be a ContactGuidance, not {type(contact).__name__}")
         if targets is not None and not isinstance(targets, JointTargets):
             raise TypeError(f"MotionGuidance: targets must be a JointTargets, not {type(targets).__name__}")
-        if contact is not None and targets is not None:
-            if contact.D != targets.D or not torch.equal(contact.mean.cpu(), targets.mean.cpu()) or not torch.equal(contact.std.cpu(), targets.std.cpu()):
+        if clearance is not None and not isinstance(clearance, SceneClearance):
+            raise TypeError(f"MotionGuidance: clearance must be a SceneClearance, not {type(clearance).__name__}")
+        terms = [g for g in (contact, targets, clearance) if g is not None]
+        for first, other in zip(terms, terms[1:]):
+            if first.D != other.D or not torch.equal(first.mean.cpu(), other.mean.cpu()) or not torch.equal(first.std.cpu(), other.std.cpu()):
                 raise ValueError("MotionGuidance: the two terms de-normalise the motion with different mean / std")
-            if (contact.joints is None) != (targets.joints is None):
+            if (first.joints is None) != (other.joints is None):
                 raise ValueError("MotionGuidance: one term names columns of absolute positions, the other joints of HumanML3D features")
-            a, b = contact.to_scene, targets.to_scene
+            a, b = first.to_scene, other.to_scene
             if (a is None) != (b is None) or (a is not None and a is not b and (a.shape != b.shape or a.device != b.device or not torch.equal(a.cpu(), b.cpu()))):          # (compared on the host: no device arithmetic)
                 raise ValueError("MotionGuidance: the two terms place the motion in the scene with different to_scene transforms")
-        self.contact, self.targets = contact, targets
+        self.contact, self.targets, self.clearance = contact, targets, clearance
+
+    def _terms(self) -> list:
+        return [g for g in (self.contact, self.targets, self.clearance) if g is not None]
 
     @property
     def t_start(self):
         """None if any term guides every step, else the latest start"""
-        ts = [g.t_start for g in (self.contact, self.targets) if g is not None]
+        ts = [g.t_start for g in self._terms()]
         return None if any(t is None for t in ts) else max(ts)
 
     def describe(self, x: torch.Tensor, model_kwargs, diffusion: Optional["GaussianDiffusion"] = None) -> tuple:
-        """(afm_motion_guide of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).  With
-        ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
+        """(afm_motion_guide - with a clearance: afm_scene_guide - of this sample tensor and these conditions, x_mask as uint8 or None,
+        what must stay alive with it).  With ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
         cg = tg = fm = shared = None
         keep = []
         if self.contact is not None:
@@ -572,24 +697,36 @@ class MotionGuidance:
         if self.targets is not None:
             tg, fm, tk = self.targets.describe(x, model_kwargs, diffusion, shared=shared)
             keep.append((tg, tk))
+            shared = (tk[2], tk[3], tk[7], tg.h3d.contents.to_scene_stride if tg.h3d else 0)
         g = ffi.MotionGuide()
         if cg is not None:
             g.contact = C.pointer(cg)
         if tg is not None:
             g.targets = C.pointer(tg)
-        return g, fm, keep
+        if self.clearance is None:
+            return g, fm, keep
+        sg, fm, sk = self.clearance.describe(x, model_kwargs, diffusion, shared=shared)
+        keep.append((sg, sk, g))
+        s = ffi.SceneGuide()
+        s.clearance = C.pointer(sg)
+        if cg is not None or tg is not None:
+            s.terms = C.pointer(g)
+        return s, fm, keep
 
     def first_guided(self, diffusion: "GaussianDiffusion") -> int:
         """the first executed step of a chain on ``diffusion`` that carries any term"""
-        return min(g.first_guided(diffusion) for g in (self.contact, self.targets) if g is not None)
+        return min(g.first_guided(diffusion) for g in self._terms())
 
     def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
         g, fm, keep = self.describe(x, model_kwargs)
-        timed = any(q is not None and q.t_start is not None for q in (self.contact, self.targets))
-        return ops.motion_guidance(g, x, fm, t.to(x.device) if timed else None)[0]
+        timed = any(q.t_start is not None for q in self._terms())
+        run = ops.motion_guidance if self.clearance is None else ops.scene_guidance
+        return run(g, x, fm, t.to(x.device) if timed else None)[0]
 
     def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
-        g, fm, keep = self.describe(x, model_kwargs)
+        if self.contact is None and self.targets is None:
+            return None, None
+        g, fm, keep = MotionGuidance(self.contact, self.targets).describe(x, model_kwargs)
         return ops.motion_guidance(g, x, fm, grad=False, energy=True)[1:]
 
 

@@ -922,6 +922,325 @@ extern "C" int afm_h3d_joints(const float* x, const float* mean, const float* st
     return 0;
 }
 
+// ---- scene clearance (afm_scene_clearance): every joint-frame against every obstacle point of its sample, n-body style.  A block owns
+// whole frames - at most 64 joint-frames, one per lane - and all of its CLEAR_WAVES waves hold the same joint-frames in registers; the
+// sample's points pass through LDS in tiles of {x, y, z, w} (w decided once by the staging threads), each wave takes its own fixed span
+// of every tile - all lanes read the same entry, an LDS broadcast - and the waves' partial sums are joined through LDS in wave order.
+namespace {
+
+constexpr int CLEAR_WAVES = AFM_CLEAR_WAVES, CLEAR_THREADS = 64 * CLEAR_WAVES, CLEAR_TILE = AFM_CLEAR_TILE, CLEAR_SPAN = CLEAR_TILE / CLEAR_WAVES;
+
+struct ClearDev {
+    const float *q, *weight, *c, *mean, *std, *scale;          // c: NULL without the exemption
+    int cols[AFM_GUIDE_MAX_JOINTS];
+    float ir2[AFM_GUIDE_MAX_JOINTS], coef[AFM_GUIDE_MAX_JOINTS];          // 1 / r^2 and 4 / r^2, rounded once from float64
+    int K, N, Kc, L, D, up, fpb;                                // fpb: frames per block, 64 / K
+    float min_height, c_min;                                    // the smallest float32 >= the threshold (-inf / +inf: not set)
+    int64_t t_start;
+};
+
+// the per-joint rows of a by-value kernel argument into LDS with static indices (a dynamic index would put the arrays in scratch)
+__device__ __forceinline__ void stage_clear_rows(const ClearDev& g, int* scols, float* sir2, float* scoef) {
+#pragma unroll
+    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
+        if (threadIdx.x == k) { scols[k] = g.cols[k]; sir2[k] = g.ir2[k]; scoef[k] = g.coef[k]; }
+}
+
+struct ClearShared {
+    float4 pt[CLEAR_TILE];                  // the tile: x, y, z, w
+    float join[CLEAR_WAVES][4][64];         // a wave's partial S_x, S_y, S_z, e of lane i
+    float term[64][3];                      // the column form's finished terms of joint-frame i
+    int cols[AFM_GUIDE_MAX_JOINTS];
+    float ir2[AFM_GUIDE_MAX_JOINTS], coef[AFM_GUIDE_MAX_JOINTS];
+};
+
+// The sums of block `blk` of sample blockIdx.y, on every wave alike: lane i holds joint-frame (f, k) = (blk * fpb + i / K, i % K);
+// *live: the lane has one; *valid: and its frame is not padded.  -> S (s[0..2]) and e (s[3]), zero where not valid.  Wave v adds, from 0
+// and in ascending n, the points with (n mod CLEAR_TILE) / CLEAR_SPAN == v; the join is the serial sum over v = 0 .. CLEAR_WAVES - 1.
+// `pos`: the recovery's positions [b][f][k][3] (h3d), else the de-normalised columns of x.  The first barrier of the tile loop also
+// separates this call's writes to sh.join from the previous call's reads (N > 0: the loop runs).
+__device__ __forceinline__ void clear_block_sums(const ClearDev& g, ClearShared& sh, const float* __restrict__ x, const float* __restrict__ pos,
+                                                 const uint8_t* __restrict__ fmask, int blk, float s[4], int* fo, int* ko, bool* live, bool* valid) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y, K = g.K, L = g.L, N = g.N;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int fr = lane / K, k = lane - fr * K, f = blk * g.fpb + fr;
+    *fo = f; *ko = k;
+    *live = fr < g.fpb && f < L;
+    *valid = *live && !(fmask && fmask[(int64_t)b * L + f]);
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f, ir2 = 0.f;
+    if (*valid) {
+        if (pos) {
+            const float* pp = pos + (((int64_t)b * L + f) * K + k) * 3;
+            p0 = pp[0]; p1 = pp[1]; p2 = pp[2];
+        } else {
+            const float* xrow = x + ((int64_t)b * L + f) * g.D;
+            const int col = sh.cols[k];
+            p0 = denorm(xrow, g.mean, g.std, col); p1 = denorm(xrow, g.mean, g.std, col + 1); p2 = denorm(xrow, g.mean, g.std, col + 2);
+        }
+        ir2 = sh.ir2[k];
+    }
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, e = 0.f;
+    for (int t0 = 0; t0 < N; t0 += CLEAR_TILE) {
+        __syncthreads();
+        for (int j = threadIdx.x; j < CLEAR_TILE; j += CLEAR_THREADS) {
+            const int n = t0 + j;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (n < N) {
+                const int64_t o = (int64_t)b * N + n;
+                const float* qp = g.q + o * 3;
+                v.x = qp[0]; v.y = qp[1]; v.z = qp[2];
+                float w = g.weight ? g.weight[o] : 1.f;
+                const float h = g.up == 0 ? v.x : (g.up == 1 ? v.y : v.z);
+                if (h < g.min_height) w = 0.f;
+                if (g.c) {
+                    const float* cp = g.c + o * g.Kc;
+                    float mx = cp[0];
+                    for (int j2 = 1; j2 < g.Kc; ++j2) mx = fmaxf(mx, cp[j2]);
+                    if (mx >= g.c_min) w = 0.f;
+                }
+                v.w = w;
+            }
+            sh.pt[j] = v;
+        }
+        __syncthreads();
+        const int cnt = min(CLEAR_SPAN, N - t0 - wave * CLEAR_SPAN);
+        const float4* my = sh.pt + wave * CLEAR_SPAN;
+        float4 next = my[0];
+        for (int j = 0; j < cnt; ++j) {
+            const float4 v = next;
+            next = my[min(j + 1, CLEAR_SPAN - 1)];              // (the entry behind this one is on its way while this one is used)
+            const float dx = p0 - v.x, dy = p1 - v.y, dz = p2 - v.z;
+            const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+            const float d2 = (xx + yy) + zz;
+            const float m = d2 * ir2;
+            const float u = fmaxf(0.f, 1.f - m);
+            const float wu = v.w * u;
+            if (wu != 0.f) {
+                const float m0 = wu * dx, m1 = wu * dy, m2 = wu * dz, me = wu * u;
+                s0 = s0 + m0; s1 = s1 + m1; s2 = s2 + m2; e = e + me;
+            }
+        }
+    }
+    sh.join[wave][0][lane] = s0; sh.join[wave][1][lane] = s1; sh.join[wave][2][lane] = s2; sh.join[wave][3][lane] = e;
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        float acc = sh.join[0][a][lane];
+#pragma unroll
+        for (int v = 1; v < CLEAR_WAVES; ++v) acc = acc + sh.join[v][a][lane];
+        s[a] = *valid ? acc : 0.f;
+    }
+}
+
+// One launch, blocks (frame block blockIdx.x, sample blockIdx.y).  out != NULL, column form (pos == NULL): the block's complete grad rows -
+// grad[b,f,cols[k]+a] = ((scale[b] * coef_k) * std_a) * S_a, zero in every other column, in a padded frame and in a sample with
+// t[b] >= t_start; acc: row[d] = row[d] + term for EVERY column (one rounded addition per element on what the terms in front wrote).
+// h3d form (pos set): coef_k * S_a (zero in a padded frame) to out = S[b][f][k][3] for the adjoint, whose business scale, t_start and
+// the rows are.  energy != NULL: the sample's block 0 walks every frame block in order, lane i adding its e, then one wave's butterfly.
+__global__ __launch_bounds__(CLEAR_THREADS) void clear_kernel(const ClearDev g, const float* __restrict__ x, const float* __restrict__ pos,
+                                                              const uint8_t* __restrict__ fmask, const int64_t* __restrict__ t, int acc,
+                                                              float* __restrict__ out, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    __shared__ ClearShared sh;
+    const int b = blockIdx.y, K = g.K, L = g.L, D = g.D, lane = threadIdx.x & 63;
+    stage_clear_rows(g, sh.cols, sh.ir2, sh.coef);
+    __syncthreads();
+    float s[4];
+    int f, k;
+    bool live, valid;
+    if (out) {
+        const bool late = t && t[b] >= g.t_start;               // (uniform over the block)
+        if (late) {
+            const int fr = lane / K;
+            k = lane - fr * K; f = blockIdx.x * g.fpb + fr;
+            live = fr < g.fpb && f < L; valid = false;
+            s[0] = s[1] = s[2] = 0.f;
+        } else {
+            clear_block_sums(g, sh, x, pos, fmask, blockIdx.x, s, &f, &k, &live, &valid);
+        }
+        if (pos) {
+            if (threadIdx.x < 64 && live) {
+                float* o = out + (((int64_t)b * L + f) * K + k) * 3;
+                const float ck = sh.coef[k];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) o[a] = valid ? ck * s[a] : 0.f;
+            }
+        } else {
+            if (threadIdx.x < 64 && live) {
+                const float ks = g.scale[b] * sh.coef[k];
+                const int col = sh.cols[k];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const float kss = ks * g.std[col + a];
+                    sh.term[lane][a] = valid ? kss * s[a] : 0.f;
+                }
+            }
+            __syncthreads();
+            const int f0 = blockIdx.x * g.fpb, nf = min(g.fpb, L - f0);
+            float* rows = out + ((int64_t)b * L + f0) * D;
+            for (int i = threadIdx.x; i < nf * D; i += CLEAR_THREADS) {
+                const int fr = i / D, d = i - fr * D;
+                float term = 0.f;
+                for (int kk = 0; kk < K; ++kk) {
+                    const int a = d - sh.cols[kk];
+                    if (a >= 0 && a < 3) { term = sh.term[fr * K + kk][a]; break; }
+                }
+                rows[i] = acc ? rows[i] + term : term;
+            }
+        }
+    }
+    if (energy && blockIdx.x == 0) {
+        float e = 0.f;
+        const int nblk = (L + g.fpb - 1) / g.fpb;
+        for (int c = 0; c < nblk; ++c) {
+            clear_block_sums(g, sh, x, pos, fmask, c, s, &f, &k, &live, &valid);
+            e = e + s[3];
+        }
+        if (threadIdx.x < 64) {
+            e = wave_sum(e);
+            if (threadIdx.x == 0) energy[b] = e;
+        }
+    }
+}
+
+// the smallest float32 >= v: a float32 value compares with it as with v itself
+float ceil_f32(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+int clear_check(const afm_scene_clearance* a, int32_t L, int32_t D) {
+    if (!a->q || !a->mean || !a->std || !a->scale || L <= 0 || D <= 0) return AFM_E_BADARG;
+    if (a->K <= 0 || a->K > AFM_GUIDE_MAX_JOINTS || a->N <= 0 || a->up < 0 || a->up > 2) return AFM_E_BADARG;
+    for (int k = 0; k < a->K; ++k)
+        if (!(a->radius[k] > 0.0) || !(1.0 / (a->radius[k] * a->radius[k]) <= 3.0e38)) return AFM_E_BADARG;
+    if (a->exempt && (!a->c || a->Kc <= 0)) return AFM_E_BADARG;
+    if (a->has_min_height && a->min_height != a->min_height) return AFM_E_BADARG;
+    if (joints_check(a->cols, a->h3d, a->K, D) != 0) return AFM_E_BADARG;
+    if (L > 65535) return AFM_E_UNSUPPORTED;
+    if (a->h3d && (size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
+    return 0;
+}
+
+// h3d: positions and S [count][L][K][3], c / s [count][L][2]; added to the terms in front: the adjoint's own rows [count][L][D]
+int64_t clear_workspace_bytes(const afm_scene_clearance* a, bool add, int64_t count, int64_t L, int64_t D) {
+    if (!a->h3d) return 0;
+    return h3d_extra_bytes(count, L, a->K) + (add ? afm_loop::align256(count * L * D * 4) : 0);
+}
+
+// the clearance's launches on the samples [start, start + count); add: grad holds the result of the terms in front, the sum goes there
+int clear_sub(const afm_scene_clearance* a, bool add, int32_t start, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+              float* energy, int32_t count, int32_t L, int32_t D, char* wp, hipStream_t s) {
+    ClearDev g = {};
+    g.q = a->q + (int64_t)start * a->N * 3;
+    g.weight = a->weight ? a->weight + (int64_t)start * a->N : nullptr;
+    g.c = a->exempt ? a->c + (int64_t)start * a->N * a->Kc : nullptr;
+    g.mean = a->mean; g.std = a->std; g.scale = a->scale + start;
+    for (int k = 0; k < a->K; ++k) {
+        g.cols[k] = a->h3d ? 0 : a->cols[k];
+        const double r2 = a->radius[k] * a->radius[k];
+        g.ir2[k] = (float)(1.0 / r2);
+        g.coef[k] = (float)(4.0 / r2);
+    }
+    g.K = a->K; g.N = a->N; g.Kc = a->Kc; g.L = L; g.D = D; g.up = a->up; g.fpb = 64 / a->K;
+    g.min_height = a->has_min_height ? ceil_f32(a->min_height) : -INFINITY;
+    g.c_min = a->exempt ? ceil_f32(a->c_min) : INFINITY;
+    g.t_start = a->t_start;
+    const unsigned nblk = (unsigned)((L + g.fpb - 1) / g.fpb);
+    const dim3 grid(grad ? nblk : 1u, (unsigned)count);
+    if (!a->h3d) {
+        hipLaunchKernelGGL(clear_kernel, grid, dim3(CLEAR_THREADS), 0, s, g, x, (const float*)nullptr, frame_mask, t, add ? 1 : 0, grad, energy);
+        AFM_CHECK_LAUNCH();
+        return 0;
+    }
+    const H3dPlan p = h3d_plan(a->mean, a->std, g.scale, *a->h3d, a->K, L, D, start, count, false, 1.f, a->t_start, wp);
+    float* tmp = (float*)p.end;                     // (add: the adjoint's own rows [count][L][D])
+    hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.rec, x, frame_mask, p.pos, grad ? p.cs : nullptr);
+    AFM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(clear_kernel, grid, dim3(CLEAR_THREADS), 0, s, g, x, (const float*)p.pos, frame_mask, (const int64_t*)nullptr, 0,
+                       grad ? p.S : nullptr, energy);
+    AFM_CHECK_LAUNCH();
+    if (!grad) return 0;
+    if (add) hipLaunchKernelGGL(h3d_adjoint_add_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, x, frame_mask, t, p.cs, p.S, tmp, grad);
+    else hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, x, frame_mask, t, p.cs, p.S, grad);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+inline const afm_motion_guide* set_terms(const afm_motion_guide* terms) { return terms && (terms->contact || terms->targets) ? terms : nullptr; }
+
+}  // namespace
+
+__attribute__((visibility("hidden"))) int afm_scene_guide_check(const afm_motion_guide* terms, const afm_scene_clearance* clear, int32_t L, int32_t D) {
+    terms = set_terms(terms);
+    if (!terms && !clear) return AFM_E_BADARG;
+    if (terms) {
+        const int rc = afm_motion_guide_check(terms, L, D);
+        if (rc != 0) return rc;
+    }
+    if (!clear) return 0;
+    const int rc = clear_check(clear, L, D);
+    if (rc != 0) return rc;
+    if (terms) {
+        const float *mean = terms->contact ? terms->contact->mean : terms->targets->mean, *std = terms->contact ? terms->contact->std : terms->targets->std;
+        const afm_h3d_layout* h = terms->contact ? terms->contact->h3d : terms->targets->h3d;
+        if (mean != clear->mean || std != clear->std || !h != !clear->h3d) return AFM_E_BADARG;
+        if (h && (h->to_scene != clear->h3d->to_scene || h->to_scene_stride != clear->h3d->to_scene_stride)) return AFM_E_BADARG;
+    }
+    return 0;
+}
+
+// the workspace of `count` samples of a checked sum: the terms', then the clearance's
+__attribute__((visibility("hidden"))) int64_t afm_scene_guide_workspace_bytes(const afm_motion_guide* terms, const afm_scene_clearance* clear, int32_t count,
+                                                                              int32_t L, int32_t D) {
+    terms = set_terms(terms);
+    const int64_t n = terms ? afm_motion_guide_workspace_bytes(terms, count, L, D) : 0;
+    return clear ? afm_loop::align256(n) + clear_workspace_bytes(clear, terms != nullptr, count, L, D) : n;
+}
+
+__attribute__((visibility("hidden"))) int afm_scene_guidance_sub(const afm_motion_guide* terms, const afm_scene_clearance* clear, bool run_contact,
+                                                                 bool run_targets, bool run_clear, int32_t start, const float* x, const uint8_t* frame_mask,
+                                                                 const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
+                                                                 float* energy_clear, int32_t count, int32_t L, int32_t D, void* workspace,
+                                                                 int64_t workspace_bytes, void* stream) {
+    terms = set_terms(terms);
+    const int rc = afm_scene_guide_check(terms, clear, L, D);
+    if (rc != 0) return rc;
+    run_contact = run_contact && terms && terms->contact;
+    run_targets = run_targets && terms && terms->targets;
+    run_clear = run_clear && clear;
+    if (!x || (!grad && !energy_contact && !energy_targets && !energy_clear) || start < 0 || count < 0 || (energy_contact && !run_contact) ||
+        (energy_targets && !run_targets) || (energy_clear && !run_clear) || (!run_contact && !run_targets && !run_clear)) return AFM_E_BADARG;
+    if (count > 65535) return AFM_E_UNSUPPORTED;
+    if (count == 0) return 0;
+    if (!workspace || workspace_bytes < afm_scene_guide_workspace_bytes(terms, clear, count, L, D)) return AFM_E_WORKSPACE;
+    const int64_t tbytes = terms ? afm_loop::align256(afm_motion_guide_workspace_bytes(terms, count, L, D)) : 0;
+    const bool front = (run_contact || run_targets) && (grad || energy_contact || energy_targets);
+    if (front) {
+        const int rcm = afm_motion_guidance_sub(terms, run_contact, run_targets, start, x, frame_mask, t, grad, energy_contact, energy_targets, count, L, D,
+                                                workspace, tbytes, stream);
+        if (rcm != 0) return rcm;
+    }
+    if (run_clear && (grad || energy_clear))
+        return clear_sub(clear, front && grad, start, x, frame_mask, t, grad, energy_clear, count, L, D, (char*)workspace + tbytes, (hipStream_t)stream);
+    return 0;
+}
+
+extern "C" int64_t afm_scene_guidance_workspace_bytes(const afm_scene_guide* g, int32_t B, int32_t L, int32_t D) {
+    if (!g || B < 0 || afm_scene_guide_check(g->terms, g->clearance, L, D) != 0) return AFM_E_BADARG;
+    return afm_scene_guide_workspace_bytes(g->terms, g->clearance, B, L, D) + 256;          // (never zero: the column forms need none)
+}
+
+extern "C" int afm_scene_guidance(const afm_scene_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                                  float* energy_contact, float* energy_targets, float* energy_clearance, int32_t B, int32_t L, int32_t D,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!g) return AFM_E_BADARG;
+    return afm_scene_guidance_sub(g->terms, g->clearance, true, true, true, 0, x, frame_mask, t, grad, energy_contact, energy_targets, energy_clearance, B, L,
+                                  D, workspace, workspace_bytes, stream);
+}
+
 // ---- the guidance of stitched long motions (afm_long_guide): the windows joined, the terms evaluated on the long motion, one gradient per
 // long frame handed back to the windows
 namespace {

@@ -36,6 +36,18 @@ __attribute__((visibility("hidden"))) int afm_motion_guidance_sub(const afm_moti
                                                                   float* energy_targets, int32_t count, int32_t L, int32_t D, void* workspace,
                                                                   int64_t workspace_bytes, void* stream);
 
+// guidance.hip: the sum with the scene clearance (afm_scene_guide, taken apart: `terms` NULL or a sum with a term set, `clear` NULL or the
+// clearance; at least one) - its checks, the workspace of `count` samples of a checked sum (clear == NULL: afm_motion_guide_workspace_bytes
+// exactly), and afm_scene_guidance on the samples [start, start + count), computing the terms named (clear == NULL: afm_motion_guidance_sub)
+__attribute__((visibility("hidden"))) int afm_scene_guide_check(const afm_motion_guide* terms, const afm_scene_clearance* clear, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int64_t afm_scene_guide_workspace_bytes(const afm_motion_guide* terms, const afm_scene_clearance* clear, int32_t count,
+                                                                              int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int afm_scene_guidance_sub(const afm_motion_guide* terms, const afm_scene_clearance* clear, bool run_contact,
+                                                                 bool run_targets, bool run_clear, int32_t start, const float* x, const uint8_t* frame_mask,
+                                                                 const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
+                                                                 float* energy_clear, int32_t count, int32_t L, int32_t D, void* workspace,
+                                                                 int64_t workspace_bytes, void* stream);
+
 // guidance.hip: the guidance of stitched long motions (afm_long_guide) - its checks, the workspace of `count` long motions of a checked
 // description, and afm_long_guidance on the long motions [start, start + count) (x, t, grad point at window start * S)
 __attribute__((visibility("hidden"))) int afm_long_guide_check(const afm_long_guide* g, int32_t L, int32_t D);

@@ -1020,6 +1020,84 @@ int afm_cmdm_motion_guide_loop_range(const afm_cmdm_weights* w, float* x, const 
                                      void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
                                      void* stream);
 
+/* Scene clearance (v7-additive): the one term that pushes - every joint-frame is pushed off the obstacle points of the scene cloud that lie
+ * inside the joint's radius.  p[b,f,k,:] are the positions the other terms use (the de-normalised columns, or with `h3d` the recovery
+ * kernel's output); q = the scene points [B][N][3].  The obstacle weight of a point, decided once per point:
+ *   w[b,n] = weight[b,n] (1 where weight == NULL), but 0 if  (has_min_height and q[b,n,up] < min_height)  - the floor -
+ *            or  (exempt and max_j c[b,n,j] >= c_min, j < Kc)  - points the contact map marks stay reachable
+ * (both comparisons are exact: the float32 value against the double threshold).  float32, every operation rounded on its own, with
+ * ir2[k] = (float)(1 / r_k^2) and coef[k] = (float)(4 / r_k^2), each formed in float64 and rounded once:
+ *   d  = p[b,f,k,:] - q[b,n,:];   d2 = (dx*dx + dy*dy) + dz*dz;   u = max(0, 1 - d2 * ir2[k]);   wu = w * u
+ *   E[b]       = sum over valid frames f, joints k, points n of  wu * u                      (not normalised)
+ *   S[b,f,k,a] = sum_n wu * d_a
+ *   column form:  grad[b,f,cols[k]+a] = ((scale[b] * coef[k]) * std_a) * S_a                  (one launch)
+ *   h3d form:     (coef[k] * S_a), rounded, goes to S[b][f][k][3] and through the recovery's adjoint with coef = 1, i.e. with scale[b]
+ *                 alone (three launches: recovery, clearance, adjoint)
+ * which is -scale[b] * dE/dx: u * u and its derivative both vanish at d = r.  grad is exactly zero in every other column, in padded
+ * frames, in a sample with t[b] >= t_start and in a joint-frame with no obstacle point inside its radius; a sample whose frames are all
+ * padded has E = 0.  A point with wu == 0 adds nothing and is skipped.
+ * The order of the sums (no atomics; a function of the sample alone - not of B, of the sample's place or of the run): the kernel runs
+ * AFM_CLEAR_WAVES = 8 waves per block on tiles of AFM_CLEAR_TILE = 1024 points.  For one joint-frame, wave v adds, from 0 and in ascending
+ * n, the points with (n mod 1024) / 128 == v; then S = ((((((s_0 + s_1) + s_2) + s_3) + s_4) + s_5) + s_6) + s_7, and the joint-frame's
+ * energy e likewise.  E[b]: a block of whole frames holds at most 64 joint-frames i = (f - f0) * K + k, f0 = block * (64 / K); lane i adds
+ * its e over the blocks in ascending block order (a padded frame's e counts as 0), then the fixed butterfly of one wave.  The energy is
+ * computed by the sample's first block alone (a score, not part of a sampling step).
+ * Any N fits (the points are tiled through 16 KiB of LDS); AFM_E_UNSUPPORTED: L or B beyond 65535, 7 * L floats beyond the LDS with h3d. */
+#define AFM_CLEAR_WAVES 8
+#define AFM_CLEAR_TILE 1024
+typedef struct {
+    const float* q;                        /* device [B][N][3]: the scene points                                          */
+    const float* weight;                   /* device [B][N] or NULL (every point weighs 1)                                */
+    const float* c;                        /* device [B][N][Kc]: the contact map of the exemption, or NULL                */
+    const float* mean; const float* std;   /* device [D]: de-normalisation of the motion                                  */
+    const float* scale;                    /* device [B]                                                                  */
+    int32_t cols[AFM_GUIDE_MAX_JOINTS];    /* column of x of joint k (y, z: the next two); ignored with `h3d`             */
+    int32_t K; int32_t N;
+    int32_t Kc;                            /* columns of c                                                                */
+    int32_t exempt;                        /* nonzero: points with max_j c >= c_min weigh 0 (needs c)                     */
+    double c_min;
+    double radius[AFM_GUIDE_MAX_JOINTS];   /* r_k > 0                                                                     */
+    int32_t up;                            /* 0..2: the coordinate min_height is compared with                            */
+    int32_t has_min_height;                /* nonzero: points with q[up] < min_height weigh 0                             */
+    double min_height;
+    int32_t first_guided;                  /* loops only: executed steps (first_step + j) below it do not carry this term */
+    int64_t t_start;                       /* with t: samples with t[b] >= t_start get a zero gradient                    */
+    const afm_h3d_layout* h3d;             /* NULL: `cols` name absolute positions; set: x holds HumanML3D features       */
+} afm_scene_clearance;
+
+/* The sum of the three terms: grad = (grad_contact + grad_targets) + grad_clearance, each term the float32 result of that term alone,
+ * joined by one rounded addition per element in that order (the clearance launch - the column kernel, or the adjoint - adds its complete
+ * result to what the terms in front of it wrote); a term that is not set contributes nothing.  At least one term is set; the clearance
+ * and `terms` agree exactly as the two terms of afm_motion_guide must: the same mean / std, the same form, the same to_scene (pointer
+ * and stride).  The gk and frame_mask of `terms` are not read through this struct. */
+typedef struct {
+    const afm_motion_guide* terms;         /* or NULL                                                                     */
+    const afm_scene_clearance* clearance;  /* or NULL                                                                     */
+    const float* gk;                       /* loops only: device [T][B], row i = the coefficient of spaced timestep i     */
+    const uint8_t* frame_mask;             /* loops only: device [B][L], nonzero = padded frame, or NULL                  */
+} afm_scene_guide;
+
+/* grad [B][L][D] and / or the three energies [B] (each may be NULL; an energy of a term that is not set must be NULL) of x [B][L][D];
+ * frame_mask [B][L] or NULL; t [B] or NULL.  AFM_E_BADARG before anything is enqueued: no term set, what afm_motion_guidance refuses, a
+ * radius that is not positive, `up` outside 0..2, an exemption without c (or with Kc <= 0), terms that disagree (above). */
+int64_t afm_scene_guidance_workspace_bytes(const afm_scene_guide* g, int32_t B, int32_t L, int32_t D);
+int afm_scene_guidance(const afm_scene_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                       float* energy_contact, float* energy_targets, float* energy_clearance, int32_t B, int32_t L, int32_t D,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* afm_cmdm_motion_guide_loop_range with the description swapped: the same loop body, the step's gradient the sum above over the terms
+ * whose own first_guided the executed step has reached (a term not yet reached launches nothing and contributes exactly zero).  The
+ * clearance adds one launch per guided step and sub-batch (h3d: three).  Also AFM_E_BADARG: g->gk missing, a negative first_guided. */
+int64_t afm_cmdm_scene_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                  const afm_cfg2_args* cfg2, const afm_scene_guide* guide);
+int afm_cmdm_scene_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                    const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                    const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                    const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_scene_guide* guide,
+                                    int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                    void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                    void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Long motions as overlapping windows (v7-additive).  G long motions are B = G * S samples [B][L][D]: sample g * S + w is window w of
  * motion g and holds the long frames w * (L - overlap) .. w * (L - overlap) + L - 1, so neighbouring windows share `overlap` frames and,
