@@ -152,7 +152,8 @@ class LoopExtras(NamedTuple):
     what an imputing loop launches.  ``stitch``: an afm.diffusion.Stitch - the batch rows are overlapping windows of long motions and
     every step's update launch gives the frames two windows share one pred_xstart (afm_cmdm_stitch_loop_range, every deterministic
     form; the separate-update form; sub-batches are cut over long motions).  With ``stitch`` the one ``guide`` taken is an
-    afm.diffusion.LongGuidance on the same geometry (afm_cmdm_long_guide_loop_range: the terms on the joined long motions)."""
+    afm.diffusion.LongGuidance on the same geometry (afm_cmdm_long_guide_loop_range: the terms on the joined long motions; one that carries
+    a SceneClearance: afm_cmdm_long_scene_guide_loop_range)."""
     cfg: object = None
     branch_streams: bool = False
     guide: object = None
@@ -173,12 +174,13 @@ def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, te
     """The entry a chain reaches: ``update`` "ddpm" / "ddim" / "dpm", ``guidance`` "none" / "cfg" (one scale) / "cfg2" (two), with or without
     ``impute``, ``term`` "none" / "contact" (a bare ContactGuidance) / "motion" (anything that carries targets) / "scene" (anything that carries a
     SceneClearance) / "long" (a LongGuidance:
-    only stitched, only with a deterministic update; the long description takes the guidance's slot and carries the stitch), stitched or not.  By
+    only stitched, only with a deterministic update; the long description takes the guidance's slot and carries the stitch) / "long_scene" (a
+    LongGuidance that carries a SceneClearance: the same slots, afm_cmdm_long_scene_guide_loop_range), stitched or not.  By
     priority: a term's entry, the stitched one, the 2M one (each runs every form it is asked for on a workspace of its own size: a history
     buffer, gradient buffers, sub-batches over long motions), then the entries of both updates (cfg2, impute), then one per update."""
-    if term == "long" and not stitch:
-        raise ValueError("term 'long' guides stitched windows: no such loop with stitch=False")
-    if stitch and (update == "ddpm" or term not in ("none", "long")):
+    if term in ("long", "long_scene") and not stitch:
+        raise ValueError(f"term {term!r} guides stitched windows: no such loop with stitch=False")
+    if stitch and (update == "ddpm" or term not in ("none", "long", "long_scene")):
         raise ValueError(f"no stitched loop with update {update!r} and term {term!r}")
     base = {"none": "loop", "cfg": "cfg_loop", "cfg2": "cfg2_loop"}[guidance]
     cfgs = ("cfg" if guidance == "cfg" else None, "cfg2" if guidance == "cfg2" else None)
@@ -186,7 +188,8 @@ def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, te
     ddim = "ddim_rows" if update == "ddim" else None
     ddpm = ("c1", "c2", "sigma") if update == "ddpm" else (None, None, None)
     tail = ("n_steps", "first_step", "seed", "sample_index0")
-    own = {"contact": "guide", "motion": "motion_guide", "scene": "scene_guide", "long": "long_guide"}.get(term, "stitch" if stitch else None)
+    own = {"contact": "guide", "motion": "motion_guide", "scene": "scene_guide", "long": "long_guide",
+           "long_scene": "long_scene_guide"}.get(term, "stitch" if stitch else None)
     if own is not None:                 # both kinds of rows and the 2M rows, one of the three set
         last = ("stitch" if own == "stitch" else "term",)
         return LoopPlan(f"afm_cmdm_{own}_loop_range", f"afm_cmdm_{own}_loop_workspace_bytes", cfgs + last, (own, base),
@@ -654,7 +657,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                     if sc is not None:                               # anything that carries a clearance: the scene entry
                         kind, kind_key = "scene", kind_key + (sc.K, model_kwargs["c_pc_xyz"].shape[1])
                 if isinstance(both, LongGuidance):         # no frame mask: validity is the geometry; gk rows per window, on its terms
-                    kind, gk_of, long_key = "long", term.terms.contents, kind_key + (term.frames,)
+                    base = term if both.clearance is None else term.base.contents          # (a clearance: the long description is the base)
+                    kind, gk_of, long_key = "long" if both.clearance is None else "long_scene", base.terms.contents, kind_key + (base.frames,)
                 else:
                     term.frame_mask = ffi.ptr(term_fm)      # the guidance masks by x_mask also where the model does not (mask_motion=False)
                 gk_rows = diffusion.guidance_rows(x.device, "mean" if ddim_eta is None and dpm_order is None else "x0", B)
@@ -670,7 +674,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             if ex.stitch is not None:          # sub-batches are cut over long motions: a window and its neighbour share one
                 st, st_keep = ex.stitch.describe(x.device)
                 nsub = max(1, min(nsub, B // ex.stitch.windows))
-                kind_key = (st.windows, st.overlap) + (long_key if kind == "long" else ())
+                kind_key = (st.windows, st.overlap) + (long_key if kind in ("long", "long_scene") else ())
             self._side_streams = ffi.stream_pool(x.device, nsub)          # process-wide pool (hardware queues are few: ffi.stream_pool)
             handles = (C.c_void_p * nsub)(*[s.cuda_stream for s in self._side_streams[:nsub]])
             # ex.cfg (GuidedCMDM only): the afm_cfg_args of a guided loop (afm_cmdm_cfg_*_loop_range; scales already [B] on the device)

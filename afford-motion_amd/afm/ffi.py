@@ -271,6 +271,12 @@ class LongGuide(C.Structure):
     _fields_ = [("terms", C.POINTER(MotionGuide)), ("stitch", Stitch), ("frames", i32)]
 
 
+class LongSceneGuide(C.Structure):
+    """afm_long_scene_guide (v7-additive): the long guidance with the scene clearance as a third term - the long description (its terms
+    always set, possibly naming neither term) and the clearance (q / weight / c per window, scale [G]) or NULL."""
+    _fields_ = [("base", C.POINTER(LongGuide)), ("clearance", C.POINTER(SceneClearance))]
+
+
 CFG_FORCE_MASKED = 0x1
 
 EXPORTS = {
@@ -380,6 +386,15 @@ EXPORTS = {
                                                  C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p, C.c_void_p,
                                                  C.POINTER(LongGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                                  C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_long_scene_guidance_workspace_bytes": (i64, [C.POINTER(LongSceneGuide), i32, i32, i32]),
+    "afm_long_scene_guidance": (C.c_int, [C.POINTER(LongSceneGuide), c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, C.c_void_p, i64,
+                                          C.c_void_p]),
+    "afm_cmdm_long_scene_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
+                                                             C.POINTER(LongSceneGuide)]),
+    "afm_cmdm_long_scene_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                                       C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p,
+                                                       C.c_void_p, C.POINTER(LongSceneGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64,
+                                                       i32, C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_bn_fold": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, c_f32p, i32, C.c_void_p]),
     "afm_contact_glue": (C.c_int, [c_f32p, c_f32p, i64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "afm_masked_mse": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, i32, i32, i32, C.c_void_p]),

@@ -595,9 +595,11 @@ class SceneClearance(_JointTerm):
         self.weight = None if weight is None else ffi.f32c(weight.detach())
         return () if self.weight is None else (self.weight,)
 
-    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, shared=None) -> tuple:
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, shared=None, long=None) -> tuple:
         """(afm_scene_clearance of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).
-        ``shared``: the (mean, std, to_scene, stride) device tensors of the term in front of it in a sum - a sum names one set of them."""
+        ``shared``: the (mean, std, to_scene, stride) device tensors of the term in front of it in a sum - a sum names one set of them.
+        ``long`` = (G, F), `LongGuidance`'s: x holds the windows of G long motions - q / weight / c stay per window, scale and to_scene are
+        per long motion, x_mask is not read."""
         who = self._who
         self._check_sample(x)
         if "c_pc_xyz" not in model_kwargs:
@@ -614,13 +616,14 @@ class SceneClearance(_JointTerm):
                 raise ValueError(f"SceneClearance: c_pc_contact must be [{B}, {N}, J], got {tuple(c.shape)}")
         if self.weight is not None and tuple(self.weight.shape) != (B, N):
             raise ValueError(f"{who}: weight is {tuple(self.weight.shape)}, the scene needs [{B}, {N}]")
-        scale_fits(self.scale, B, who)
-        fm = _guide_mask(x, model_kwargs, who)
-        ts, stride = self._to_scene_on(B, x.device)
+        rows = B if long is None else long[0]
+        scale_fits(self.scale, rows, who)
+        fm = _guide_mask(x, model_kwargs, who) if long is None else None
+        ts, stride = self._to_scene_on(rows, x.device)
         ffi.require_gpu(x, q, c)
         own = self._on(x.device)
         mean, std, weight = own[0], own[1], own[2] if len(own) > 2 else None
-        scale = scale_row(self.scale, B, x.device, who)
+        scale = scale_row(self.scale, rows, x.device, who)
         q, c = ffi.f32c(q), None if c is None else ffi.f32c(c)
         if shared is not None:
             mean, std = shared[0], shared[1]
@@ -731,7 +734,7 @@ class MotionGuidance:
 
 
 class LongGuidance:
-    """A ``cond_fn`` for chains that run with ``stitch=``: a `ContactGuidance` and / or a `JointTargets` evaluated on the JOINED long motion
+    """A ``cond_fn`` for chains that run with ``stitch=``: a `ContactGuidance`, a `JointTargets` and / or a `SceneClearance` evaluated on the JOINED long motion
     (afm_long_guidance, HIP), so a long motion is pulled to its own contact maps, and a root path or a target may lie beyond the first
     window - on HumanML3D features the root is integrated from long frame 0, not from each window's own origin.  In a stitched chain the
     shared frames are bit-identical in both windows at every step, so the windows join into one long x_t; the gradient goes back to the
@@ -767,16 +770,44 @@ class LongGuidance:
     ValueError before anything runs: a batch or L that does not match ``stitch``, long-form shapes that do not match, F beyond what 7 * F
     floats of LDS allow for the h3d recovery, a term with a per-window scale.
 
-    Handed as ``cond_fn`` to ``ddim_sample_loop(..., stitch=)`` / ``dpm_solver_sample_loop(..., stitch=)`` with the same `Stitch` geometry; a
-    CMDM `trans_enc` or a GuidedCMDM runs the whole chain natively (afm_cmdm_long_guide_loop_range).  Launches per guided step: join + the
-    contact term's 2 (h3d: 4) + the targets' 1 (h3d: 3) + windows."""
+    ``clearance``: a `SceneClearance` (column form or ``.h3d``) as a third term (afm_long_scene_guidance, HIP).  Each window clears ITS OWN
+    frames of the joined motion against ITS OWN scene: ``c_pc_xyz`` [G * S, N, 3], the term's ``weight`` [G * S, N] (row g * S + w) and - with
+    ``exempt_contact`` - ``c_pc_contact`` [G * S, N, J] are per window, so the window "sit down" exempts the sofa its contact map marks and the
+    window "walk" does not; ``scale`` is a float or [G], ``to_scene`` [3, 4] or [G, 3, 4].  Per window b and each of its long frames f, with
+    p = P[g,f,k,:], d, d2, u and wu are formed exactly as `SceneClearance` forms them and
 
-    def __init__(self, stitch: Stitch, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None):
+        S_b[f,k,:] = sum_n wu * d,   e_b[f,k] = sum_n wu * u          (the clearance kernel's order: eight spans of 128 of every 1024 points)
+
+    Per long frame the windows' sums are crossfaded with the stitch's own weight row: with w1 = min(f // hop, S - 1), the earlier window
+    w1 - 1 also holds f iff w1 > 0 and i = f - w1 * hop < ov;
+
+        one window:   J[g,f,k,:] = S_b[f,k,:]                                  (the bits as they are)
+        two windows:  J[g,f,k,:] = (wl[i] * S_earlier) + (wr[i] * S_later)     float32, each product rounded, then the sum
+
+    (the contact term's plain sum would push twice as hard inside every overlap of one room; identical clouds in both windows give the
+    single-scene push up to rounding; an exemption fades out as the next action fades in).  Column form:
+    grad_long[g,f,cols[k]+a] = ((scale[g] * coef_k) * std_a) * J_a; h3d form: coef_k * J_a, rounded, goes through the adjoint kernel on
+    (B = G, L = F) with scale[g].  With S == 1, F == L and no mask this is `SceneClearance` on the one window, bit for bit.  The sum is
+    grad_long = (grad_contact + grad_targets) + grad_clearance - the clearance's last launch adds its complete result to what the terms in
+    front of it wrote, one rounded addition per element - then step 8.  Exact zeros: every unnamed column, the padded tail, a long motion
+    with t >= t_start, a joint-frame with no obstacle point inside its radius in any window that holds it.
+    ``clearance_energy(x, **kw)`` returns E_clearance [G] with grad = -scale * dE/dx: a joint-frame's e_b times its frame weight (1 outside
+    overlaps, wl[i] / wr[i] in the earlier / later window), summed per window as `SceneClearance` sums a sample (blocks of 64 // K whole
+    frames, a frame at or behind F counting 0), the windows' values added in window order.  ``energies`` keeps its 2-tuple.  Also a
+    ValueError before anything runs: a clearance ``weight`` whose rows are not the windows'.
+
+    Handed as ``cond_fn`` to ``ddim_sample_loop(..., stitch=)`` / ``dpm_solver_sample_loop(..., stitch=)`` with the same `Stitch` geometry; a
+    CMDM `trans_enc` or a GuidedCMDM runs the whole chain natively (afm_cmdm_long_guide_loop_range; with a clearance:
+    afm_cmdm_long_scene_guide_loop_range).  Launches per guided step: join + the contact term's 2 (h3d: 4) + the targets' 1 (h3d: 3) + the
+    clearance's 2 (h3d: 4) + windows."""
+
+    def __init__(self, stitch: Stitch, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None,
+                 clearance: Optional[SceneClearance] = None):
         if not isinstance(stitch, Stitch):
             raise TypeError(f"LongGuidance: stitch must be a Stitch, not {type(stitch).__name__}")
         self.stitch = stitch
-        self._sum = MotionGuidance(contact, targets)          # (the terms' types and their agreement, checked once)
-        self.contact, self.targets = contact, targets
+        self._sum = MotionGuidance(contact, targets, clearance)          # (the terms' types and their agreement, checked once)
+        self.contact, self.targets, self.clearance = contact, targets, clearance
 
     @property
     def t_start(self):
@@ -799,7 +830,7 @@ class LongGuidance:
         F = self.stitch.check(B, L)
         S = self.stitch.windows
         G = B // S
-        for term in (self.contact, self.targets):
+        for term in (self.contact, self.targets, self.clearance):
             if term is None:
                 continue
             term._check_sample(x)
@@ -816,11 +847,15 @@ class LongGuidance:
         if tg is not None and tuple(tg.target.shape) != (G, F, tg.K, 3):
             raise ValueError(f"{who}: the targets are long-form - target [{G}, {F}, {tg.K}, 3] and weight [{G}, {F}, {tg.K}], got "
                              f"{tuple(tg.target.shape)} and {tuple(tg.weight.shape)}")
+        sc = self.clearance
+        if sc is not None and sc.weight is not None and sc.weight.shape[0] != B:
+            raise ValueError(f"{who}: the SceneClearance's weight is per window, [{B}, N] - row g * {S} + w weighs window w's cloud -, got "
+                             f"{tuple(sc.weight.shape)}")
         return G, F
 
     def describe(self, x: torch.Tensor, model_kwargs, diffusion=None) -> tuple:
-        """(afm_long_guide of these windows and conditions, None - no frame mask is read -, what must stay alive with it).  With
-        ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
+        """(afm_long_guide - with a clearance: afm_long_scene_guide - of these windows and conditions, None - no frame mask is read -,
+        what must stay alive with it).  With ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
         long = self.check(x)
         cg = tg = shared = None
         keep = []
@@ -831,6 +866,7 @@ class LongGuidance:
         if self.targets is not None:
             tg, _, tk = self.targets.describe(x, model_kwargs, diffusion, shared=shared, long=long)
             keep.append((tg, tk))
+            shared = (tk[2], tk[3], tk[7], tg.h3d.contents.to_scene_stride if tg.h3d else 0)
         m = ffi.MotionGuide()
         if cg is not None:
             m.contact = C.pointer(cg)
@@ -839,15 +875,30 @@ class LongGuidance:
         st, st_keep = self.stitch.describe(x.device)
         g = ffi.LongGuide()
         g.terms, g.stitch, g.frames = C.pointer(m), st, long[1]
-        return g, None, (m, keep, st_keep)
+        if self.clearance is None:
+            return g, None, (m, keep, st_keep)
+        sg, _, sk = self.clearance.describe(x, model_kwargs, diffusion, shared=shared, long=long)
+        s = ffi.LongSceneGuide()
+        s.base, s.clearance = C.pointer(g), C.pointer(sg)
+        return s, None, (m, keep, st_keep, g, sg, sk)
 
     def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
         g, _, keep = self.describe(x, model_kwargs)
-        return ops.long_guidance(g, x, t.to(x.device) if self._timed() else None)[0]
+        run = ops.long_guidance if self.clearance is None else ops.long_scene_guidance
+        return run(g, x, t.to(x.device) if self._timed() else None)[0]
 
     def _timed(self) -> bool:
-        return any(q is not None and q.t_start is not None for q in (self.contact, self.targets))
+        return any(q is not None and q.t_start is not None for q in (self.contact, self.targets, self.clearance))
 
     def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
-        g, _, keep = self.describe(x, model_kwargs)
+        if self.contact is None and self.targets is None:
+            return None, None
+        g, _, keep = LongGuidance(self.stitch, self.contact, self.targets).describe(x, model_kwargs)
         return ops.long_guidance(g, x, grad=False, energy=True)[1:]
+
+    def clearance_energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        """E_clearance [G] of the windows x: the windows' omega-weighted energies added in window order (see the class docstring)"""
+        if self.clearance is None:
+            raise ValueError("LongGuidance: clearance_energy needs a clearance term")
+        g, _, keep = LongGuidance(self.stitch, clearance=self.clearance).describe(x, model_kwargs)
+        return ops.long_scene_guidance(g, x, grad=False, energy=True)[3]

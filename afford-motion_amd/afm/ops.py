@@ -912,3 +912,29 @@ def long_guidance(guide: "ffi.LongGuide", x: torch.Tensor, t: Optional[torch.Ten
     ffi.check(lib.afm_long_guidance(C.byref(guide), x.data_ptr(), ffi.ptr(tt), ffi.ptr(g), ffi.ptr(ec), ffi.ptr(et), B, L, D, ws.data_ptr(),
                                     ws.numel(), ffi.stream_of(x)), "afm_long_guidance")
     return g, ec, et
+
+
+def long_scene_guidance(guide: "ffi.LongSceneGuide", x: torch.Tensor, t: Optional[torch.Tensor] = None, *, grad: bool = True, energy: bool = False):
+    """afm_long_scene_guidance of a filled description (afm.guidance.LongGuidance with a clearance builds it): -> (grad [G * S, L, D] or None,
+    the contact term's energy [G] or None, the targets', the clearance's) of the windows x [G * S, L, D].  grad_long = (grad_contact +
+    grad_targets) + grad_clearance on the joined motion - the clearance per window against the window's own cloud, crossfaded per long frame
+    - handed back to the windows.  ``t`` [G * S] int64 or None (long motion g has t[g * S]).  The clearance adds 2 launches (h3d: 4); no
+    atomics; the workspace is allocated per call."""
+    lib = ffi.load()
+    ffi.require_gpu(x, t)
+    x = ffi.f32c(x)
+    B, L, D = x.shape
+    base = guide.base.contents
+    G = B // max(int(base.stitch.windows), 1)
+    terms = base.terms.contents
+    tt = None if t is None else t.to(dtype=torch.int64).contiguous()
+    g = torch.empty_like(x) if grad else None
+    new = lambda on: torch.empty(G, dtype=torch.float32, device=x.device) if energy and on else None
+    ec, et, el = new(bool(terms.contact)), new(bool(terms.targets)), new(bool(guide.clearance))
+    nbytes = int(lib.afm_long_scene_guidance_workspace_bytes(C.byref(guide), B, L, D))
+    if nbytes < 0:
+        ffi.check(nbytes, "afm_long_scene_guidance_workspace_bytes")
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ffi.check(lib.afm_long_scene_guidance(C.byref(guide), x.data_ptr(), ffi.ptr(tt), ffi.ptr(g), ffi.ptr(ec), ffi.ptr(et), ffi.ptr(el), B, L, D,
+                                          ws.data_ptr(), ws.numel(), ffi.stream_of(x)), "afm_long_scene_guidance")
+    return g, ec, et, el

@@ -94,7 +94,7 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
 def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: torch.Tensor, xyz: torch.Tensor, frames: int, overlap: int,
                        sampler: str = "dpm++", guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None, sigma: float = 0.8,
                        contact_mean: float = 0.0, contact_std: float = 1.0, seed: int = 0,
-                       sample_index0: int = 0, contact_guidance=None, joint_targets=None) -> Dict[str, torch.Tensor]:
+                       sample_index0: int = 0, contact_guidance=None, joint_targets=None, clearance=None) -> Dict[str, torch.Tensor]:
     """One scene, one thing after another: G long motions of ``frames`` frames, each S windows with a text of its own, sampled as
     ``G * S`` overlapping windows stitched inside the native loop (afm.diffusion.Stitch; "walk to the sofa, sit down, stand up again" is
     S = 3).  text_feat [G, S, text_dim], xyz [G, N, 3] ->
@@ -110,7 +110,11 @@ def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: t
     afm.diffusion.Impute in the LONG form ([G, frames, D]); it is cut into windows consistently (`Stitch.impute`).
     ``contact_guidance`` (a `ContactGuidance`) / ``joint_targets`` (a `JointTargets` in the LONG form, target [G, frames, K, 3]): wrapped
     into one afm.diffusion.LongGuidance on this call's Stitch and handed to stage 2 as its ``cond_fn`` - the terms are evaluated on the
-    joined long motion against the stage's own ``cond``, each window with its own contact map; their scales are floats or [G] tensors."""
+    joined long motion against the stage's own ``cond``, each window with its own contact map; their scales are floats or [G] tensors.
+    ``clearance``: an afm.diffusion.SceneClearance (or ``SceneClearance.h3d``) wrapped into the same `LongGuidance` as its third term - every
+    window's frames are pushed off the group's cloud, expanded per window as for the other conditions; ``exempt_contact`` reads the stage's
+    own ``cond`` per window (the window "sit down" exempts the sofa its contact map marks, the window "walk" does not); its ``weight`` is None
+    or [G * S, N], row g * S + w; its scale a float or a [G] tensor.  Shapes that do not fit are refused before stage 1 runs."""
     if sampler not in ("dpm++", "ddim"):
         raise ValueError(f"long_motion_sample: sampler must be 'dpm++' or 'ddim' (a deterministic update), not {sampler!r}")
     if text_feat.dim() != 3 or xyz.dim() != 3 or xyz.shape[0] != text_feat.shape[0] or xyz.shape[2] != 3:
@@ -121,12 +125,18 @@ def long_motion_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: t
             raise ValueError(f"guidance_drop {sorted(dropped)} contradicts the conditions of the guidance_scale mapping {list(guidance_scale)}")
     G, S, N = text_feat.shape[0], text_feat.shape[1], xyz.shape[1]
     stitch = Stitch(S, overlap, frames)
-    guide = None if contact_guidance is None and joint_targets is None else LongGuidance(stitch, contact_guidance, joint_targets)
+    guide = None if contact_guidance is None and joint_targets is None and clearance is None else \
+        LongGuidance(stitch, contact_guidance, joint_targets, clearance)
     L, B, dev = stitch.length, G * S, xyz.device
     if motion_impute is not None and tuple(motion_impute.shape[:2]) != (G, frames):          # (refused before the first stage runs)
         raise ValueError(f"long_motion_sample: motion_impute is the long form [{G}, {frames}, D], got {motion_impute.shape}")
     if joint_targets is not None and tuple(joint_targets.target.shape[:2]) != (G, frames):          # (likewise)
         raise ValueError(f"long_motion_sample: joint_targets is the long form, target [{G}, {frames}, K, 3], got {tuple(joint_targets.target.shape)}")
+    if clearance is not None:          # (likewise)
+        if clearance.weight is not None and tuple(clearance.weight.shape) != (B, N):
+            raise ValueError(f"long_motion_sample: the clearance's weight is per window, [{B}, {N}] (row g * {S} + w), got {tuple(clearance.weight.shape)}")
+        if isinstance(clearance.scale, torch.Tensor) and clearance.scale.numel() != G:
+            raise ValueError(f"long_motion_sample: the clearance's scale holds {clearance.scale.numel()} values for {G} long motions")
     x_mask = stitch.x_mask(G, dev, model=amdm)
     text = text_feat.reshape(B, text_feat.shape[2])
     cloud = xyz[:, None].expand(G, S, N, 3).reshape(B, N, 3)

@@ -571,7 +571,7 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
         sb->ggrad = base ? (float*)(base + off) : nullptr;
         off += align256((int64_t)sb->count * L * w.motion_dim * 4);
         sb->gws = base ? base + off : nullptr;
-        sb->gws_bytes = lguide ? afm_long_guide_workspace_bytes(lguide, sb->count / lguide->stitch.windows, L, w.motion_dim)
+        sb->gws_bytes = lguide ? afm_long_scene_guide_workspace_bytes(lguide, clear, sb->count / lguide->stitch.windows, L, w.motion_dim)
                                : afm_scene_guide_workspace_bytes(guide, clear, sb->count, L, w.motion_dim);
         off += align256(sb->gws_bytes);
     }
@@ -584,7 +584,8 @@ int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one,
                              const afm_scene_clearance* clear = nullptr) {
     if (validate(w, B, L) != 0 || n_streams < 0 || unit < 1 || B % unit != 0) return AFM_E_BADARG;
     if (guide && !guide->contact && !guide->targets && !clear) return AFM_E_BADARG;
-    if (clear && afm_scene_guide_check(guide, clear, L, w->motion_dim) != 0) return AFM_E_BADARG;
+    if (clear && (lguide ? afm_long_scene_guide_check(lguide, clear, L, w->motion_dim) : afm_scene_guide_check(guide, clear, L, w->motion_dim)) != 0)
+        return AFM_E_BADARG;
     if (guide && guide->contact && afm_contact_guidance_workspace_bytes(B, guide->contact->N, guide->contact->K) < 0) return AFM_E_BADARG;
     if (guide && guide->targets && (guide->targets->K <= 0 || guide->targets->K > AFM_GUIDE_MAX_JOINTS)) return AFM_E_BADARG;
     Guidance g = {};
@@ -622,7 +623,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     if (a.dpm && (!a.ddim || a.noise_term() || a.step_noise || a.first_step < 0)) return AFM_E_BADARG;
     if (c.guided()) {
-        AFM_TRY(c.lguide ? afm_long_guide_check(c.lguide, c.L, c.w->motion_dim) : afm_scene_guide_check(&c.guide, c.clear, c.L, c.w->motion_dim));
+        AFM_TRY(c.lguide ? afm_long_scene_guide_check(c.lguide, c.clear, c.L, c.w->motion_dim) : afm_scene_guide_check(&c.guide, c.clear, c.L, c.w->motion_dim));
         if (!c.guide.gk || (c.guide.contact && c.guide.contact->first_guided < 0) || (c.guide.targets && c.guide.targets->first_guided < 0) ||
             (c.clear && c.clear->first_guided < 0)) return AFM_E_BADARG;
     }
@@ -708,8 +709,9 @@ inline bool guided_step(const Loop& l, int j) { return contact_step(l, j) || tar
 int guide_launch(const Loop& l, const SubBatch& sb, int j) {
     if (l.c.lguide) {                 // (sb.start and sb.count are whole long motions)
         const int S = l.c.lguide->stitch.windows;
-        return afm_long_guidance_sub(l.c.lguide, contact_step(l, j), targets_step(l, j), sb.start / S, sub_x(l, sb), nullptr, sb.ggrad, nullptr, nullptr,
-                                     sb.count / S, l.c.L, l.p.w.motion_dim, sb.gws, sb.gws_bytes, sb.stream);
+        return afm_long_scene_guidance_sub(l.c.lguide, l.c.clear, contact_step(l, j), targets_step(l, j), clear_step(l, j), sb.start / S, sub_x(l, sb),
+                                           nullptr, sb.ggrad, nullptr, nullptr, nullptr, sb.count / S, l.c.L, l.p.w.motion_dim, sb.gws, sb.gws_bytes,
+                                           sb.stream);
     }
     // (the guidance's own mask: the denoiser's frame_mask is NULL for a model that does not mask its motion tokens)
     const uint8_t* fm = l.c.guide.frame_mask ? l.c.guide.frame_mask + (int64_t)sb.start * l.c.L : nullptr;
@@ -1096,4 +1098,30 @@ extern "C" int afm_cmdm_long_guide_loop_range(const afm_cmdm_weights* w, float* 
     if (B < 0 || B % guide->stitch.windows != 0) return AFM_E_BADARG;
     return every_form_range(w, x, cond_tokens, frame_mask, nullptr, d_timestep_map, rows, dpm, nullptr, nullptr, nullptr, cfg, cfg2, known, mask, guide->terms,
                             &guide->stitch, n_steps, first_step, 0, 0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, guide);
+}
+
+// The same stitched loop with the scene clearance next to (or without) the long description's terms (afm_long_scene_guide): per window its
+// own frames against its own cloud, crossfaded per long frame; its last launch adds to what the terms in front of it wrote.
+extern "C" int64_t afm_cmdm_long_scene_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams,
+                                                                  const afm_cfg_args* cfg, const afm_cfg2_args* cfg2,
+                                                                  const afm_long_scene_guide* guide) {
+    if ((cfg && cfg2) || !guide || !w || afm_long_scene_guide_check(guide->base, guide->clearance, L, w->motion_dim) != 0) return AFM_E_BADARG;
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, guide->base->terms, guide->base->stitch.windows, guide->base, guide->clearance);
+}
+
+extern "C" int afm_cmdm_long_scene_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                                    const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows,
+                                                    const afm_dpm_rows* dpm, const float* d_c1, const float* d_c2, const float* d_sigma,
+                                                    const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
+                                                    const afm_long_scene_guide* guide, int32_t n_steps, int32_t first_step, uint64_t seed,
+                                                    int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace,
+                                                    int64_t workspace_bytes, int32_t n_streams, void* const* side_streams, void* stream) {
+    (void)seed; (void)sample_index0;          // (no noise is drawn)
+    if (first_step < 0 || !guide || !guide->base || !guide->base->terms || guide->base->stitch.windows < 1 || (cfg && cfg2) || !known != !mask)
+        return AFM_E_BADARG;
+    if (d_c1 || d_c2 || d_sigma || step_noise || (rows && rows->sigma)) return AFM_E_BADARG;          // a deterministic update only
+    if (B < 0 || B % guide->base->stitch.windows != 0) return AFM_E_BADARG;
+    return every_form_range(w, x, cond_tokens, frame_mask, nullptr, d_timestep_map, rows, dpm, nullptr, nullptr, nullptr, cfg, cfg2, known, mask,
+                            guide->base->terms, &guide->base->stitch, n_steps, first_step, 0, 0, B, L, sched_scratch, workspace, workspace_bytes, n_streams,
+                            side_streams, stream, guide->base, guide->clearance);
 }

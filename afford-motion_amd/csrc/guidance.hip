@@ -958,23 +958,26 @@ struct ClearShared {
 // *live: the lane has one; *valid: and its frame is not padded.  -> S (s[0..2]) and e (s[3]), zero where not valid.  Wave v adds, from 0
 // and in ascending n, the points with (n mod CLEAR_TILE) / CLEAR_SPAN == v; the join is the serial sum over v = 0 .. CLEAR_WAVES - 1.
 // `pos`: the recovery's positions [b][f][k][3] (h3d), else the de-normalised columns of x.  The first barrier of the tile loop also
-// separates this call's writes to sh.join from the previous call's reads (N > 0: the loop runs).
+// separates this call's writes to sh.join from the previous call's reads (N > 0: the loop runs).  `row0`: the row of x / pos that holds the
+// sample's frame 0 (b * L; a window of a long motion: its first long frame's row of the joined motion), `nfr`: the frames that exist (L; a
+// window: those in front of the long motion's end).
 __device__ __forceinline__ void clear_block_sums(const ClearDev& g, ClearShared& sh, const float* __restrict__ x, const float* __restrict__ pos,
-                                                 const uint8_t* __restrict__ fmask, int blk, float s[4], int* fo, int* ko, bool* live, bool* valid) {
+                                                 const uint8_t* __restrict__ fmask, int blk, int64_t row0, int nfr, float s[4], int* fo, int* ko,
+                                                 bool* live, bool* valid) {
 #pragma clang fp contract(off)
     const int b = blockIdx.y, K = g.K, L = g.L, N = g.N;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int fr = lane / K, k = lane - fr * K, f = blk * g.fpb + fr;
     *fo = f; *ko = k;
     *live = fr < g.fpb && f < L;
-    *valid = *live && !(fmask && fmask[(int64_t)b * L + f]);
+    *valid = *live && f < nfr && !(fmask && fmask[(int64_t)b * L + f]);
     float p0 = 0.f, p1 = 0.f, p2 = 0.f, ir2 = 0.f;
     if (*valid) {
         if (pos) {
-            const float* pp = pos + (((int64_t)b * L + f) * K + k) * 3;
+            const float* pp = pos + ((row0 + f) * K + k) * 3;
             p0 = pp[0]; p1 = pp[1]; p2 = pp[2];
         } else {
-            const float* xrow = x + ((int64_t)b * L + f) * g.D;
+            const float* xrow = x + (row0 + f) * g.D;
             const int col = sh.cols[k];
             p0 = denorm(xrow, g.mean, g.std, col); p1 = denorm(xrow, g.mean, g.std, col + 1); p2 = denorm(xrow, g.mean, g.std, col + 2);
         }
@@ -1057,7 +1060,7 @@ __global__ __launch_bounds__(CLEAR_THREADS) void clear_kernel(const ClearDev g, 
             live = fr < g.fpb && f < L; valid = false;
             s[0] = s[1] = s[2] = 0.f;
         } else {
-            clear_block_sums(g, sh, x, pos, fmask, blockIdx.x, s, &f, &k, &live, &valid);
+            clear_block_sums(g, sh, x, pos, fmask, blockIdx.x, (int64_t)b * L, L, s, &f, &k, &live, &valid);
         }
         if (pos) {
             if (threadIdx.x < 64 && live) {
@@ -1094,13 +1097,137 @@ __global__ __launch_bounds__(CLEAR_THREADS) void clear_kernel(const ClearDev g, 
         float e = 0.f;
         const int nblk = (L + g.fpb - 1) / g.fpb;
         for (int c = 0; c < nblk; ++c) {
-            clear_block_sums(g, sh, x, pos, fmask, c, s, &f, &k, &live, &valid);
+            clear_block_sums(g, sh, x, pos, fmask, c, (int64_t)b * L, L, s, &f, &k, &live, &valid);
             e = e + s[3];
         }
         if (threadIdx.x < 64) {
             e = wave_sum(e);
             if (threadIdx.x == 0) energy[b] = e;
         }
+    }
+}
+
+// ---- the clearance of stitched long motions: every window clears its own frames of the joined motion against its own cloud, and per long
+// frame the windows' sums are crossfaded with the stitch's weight row.
+//
+// The long pass, blocks (frame block blockIdx.x of a window, window blockIdx.y = g * S + w): clear_block_sums on the window's frames -
+// positions from row g * F + a_w + f of the joined motion (`lng`, or the recovery's pos[g][F][K][3]), points from the window's cloud - and
+// the raw S_b (3) and e_b of every joint-frame to Sb[b][f][k][4]; a frame at or behind F gets zeros.  tl (the gradient alone is asked for):
+// a long motion with tl[g] >= t_start is skipped, the join writes its zeros without reading Sb.
+__global__ __launch_bounds__(CLEAR_THREADS) void long_clear_kernel(const ClearDev g, const LongGeo lg, const float* __restrict__ lng,
+                                                                   const float* __restrict__ pos, const int64_t* __restrict__ tl,
+                                                                   float* __restrict__ Sb) {
+    __shared__ ClearShared sh;
+    const int b = blockIdx.y, K = g.K, L = g.L;
+    const int gi = b / lg.S, first = (b % lg.S) * (L - lg.ov);
+    if (tl && tl[gi] >= g.t_start) return;                      // (uniform over the block)
+    stage_clear_rows(g, sh.cols, sh.ir2, sh.coef);
+    __syncthreads();
+    float s[4];
+    int f, k;
+    bool live, valid;
+    clear_block_sums(g, sh, lng, pos, nullptr, blockIdx.x, (int64_t)gi * lg.F + first, min(L, lg.F - first), s, &f, &k, &live, &valid);
+    if (threadIdx.x < 64 && live) {
+        float* o = Sb + (((int64_t)b * L + f) * K + k) * 4;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) o[a] = s[a];
+    }
+}
+
+// The join, blocks (long frame block blockIdx.x, long motion blockIdx.y) of 64 / K whole long frames, lane i < 64 the joint-frame
+// (f, k) = (blockIdx.x * fpb + i / K, i % K).  J = the frame's window's sum as it is, or - a shared frame, i = f - w1 * hop -
+// (wl[i] * S_earlier) + (wr[i] * S_later), each product rounded, then the sum.  out, column form: the block's complete rows of grad_long -
+// ((scale[g] * coef_k) * std_a) * J_a, zero in every other column and in a long motion with tl[g] >= t_start; acc: row[d] = row[d] + term
+// for EVERY column.  h3d: coef_k * J_a to out = S[g][f][k][3] for the adjoint.  energy: block 0's first wave - per window, lane i adds
+// omega * e_b of its joint-frame over the window's frame blocks in ascending order (omega = wl[i] / wr[i] of a shared frame in the earlier /
+// later window, a frame at or behind F counts 0), one butterfly; E[g] = the windows' values added serially from 0 in window order.
+__global__ __launch_bounds__(256) void long_clear_join_kernel(const ClearDev g, const LongGeo lg, const float* __restrict__ wgt,
+                                                              const float* __restrict__ Sb, const int64_t* __restrict__ tl, int h3d, int acc,
+                                                              float* __restrict__ out, float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    __shared__ int scols[AFM_GUIDE_MAX_JOINTS];
+    __shared__ float sir2[AFM_GUIDE_MAX_JOINTS], scoef[AFM_GUIDE_MAX_JOINTS];
+    __shared__ float term[64][3];
+    const int gi = blockIdx.y, K = g.K, L = g.L, D = g.D, F = lg.F, hop = L - lg.ov;
+    stage_clear_rows(g, scols, sir2, scoef);
+    __syncthreads();
+    if (out) {
+        const bool late = tl && tl[gi] >= g.t_start;            // (uniform over the block)
+        const int fr = (int)threadIdx.x / K, k = (int)threadIdx.x - fr * K, f = blockIdx.x * g.fpb + fr;
+        const bool live = threadIdx.x < 64 && fr < g.fpb && f < F;
+        float J[3] = {0.f, 0.f, 0.f};
+        if (live && !late) {
+            int w1;
+            const bool two = windows_of_frame(lg, L, f, &w1);
+            const int fl = f - w1 * hop;
+            const int64_t bl = (int64_t)gi * lg.S + w1;
+            const float* sl = Sb + ((bl * L + fl) * K + k) * 4;
+            if (two) {
+                const float* se = Sb + (((bl - 1) * L + fl + hop) * K + k) * 4;
+                const float wl = wgt[fl], wr = wgt[lg.ov + fl];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const float m0 = wl * se[a], m1 = wr * sl[a];
+                    J[a] = m0 + m1;
+                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) J[a] = sl[a];
+            }
+        }
+        if (h3d) {
+            if (live) {
+                float* o = out + (((int64_t)gi * F + f) * K + k) * 3;
+                const float ck = scoef[k];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) o[a] = late ? 0.f : ck * J[a];
+            }
+        } else {
+            if (live) {
+                const float ks = g.scale[gi] * scoef[k];
+                const int col = scols[k];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const float kss = ks * g.std[col + a];
+                    term[threadIdx.x][a] = late ? 0.f : kss * J[a];
+                }
+            }
+            __syncthreads();
+            const int f0 = blockIdx.x * g.fpb, nf = min(g.fpb, F - f0);
+            float* rows = out + ((int64_t)gi * F + f0) * D;
+            for (int i = threadIdx.x; i < nf * D; i += 256) {
+                const int fr2 = i / D, d = i - fr2 * D;
+                float v = 0.f;
+                for (int kk = 0; kk < K; ++kk) {
+                    const int a = d - scols[kk];
+                    if (a >= 0 && a < 3) { v = term[fr2 * K + kk][a]; break; }
+                }
+                rows[i] = acc ? rows[i] + v : v;
+            }
+        }
+    }
+    if (energy && blockIdx.x == 0 && threadIdx.x < 64) {
+        const int fr = (int)threadIdx.x / K, k = (int)threadIdx.x - fr * K;
+        const int nblk = (L + g.fpb - 1) / g.fpb;
+        float E = 0.f;
+        for (int w = 0; w < lg.S; ++w) {
+            const int64_t b = (int64_t)gi * lg.S + w;
+            const int first = w * hop;
+            float e = 0.f;
+            for (int c = 0; c < nblk; ++c) {
+                const int fl = c * g.fpb + fr;
+                float v = 0.f;
+                if (fr < g.fpb && fl < L && first + fl < F) {
+                    v = Sb[((b * L + fl) * K + k) * 4 + 3];
+                    if (w + 1 < lg.S && fl >= hop) v = wgt[fl - hop] * v;
+                    else if (w > 0 && fl < lg.ov) v = wgt[lg.ov + fl] * v;
+                }
+                e = e + v;
+            }
+            e = wave_sum(e);
+            E = E + e;
+        }
+        if (threadIdx.x == 0) energy[gi] = E;
     }
 }
 
@@ -1124,20 +1251,14 @@ int clear_check(const afm_scene_clearance* a, int32_t L, int32_t D) {
     return 0;
 }
 
-// h3d: positions and S [count][L][K][3], c / s [count][L][2]; added to the terms in front: the adjoint's own rows [count][L][D]
-int64_t clear_workspace_bytes(const afm_scene_clearance* a, bool add, int64_t count, int64_t L, int64_t D) {
-    if (!a->h3d) return 0;
-    return h3d_extra_bytes(count, L, a->K) + (add ? afm_loop::align256(count * L * D * 4) : 0);
-}
-
-// the clearance's launches on the samples [start, start + count); add: grad holds the result of the terms in front, the sum goes there
-int clear_sub(const afm_scene_clearance* a, bool add, int32_t start, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
-              float* energy, int32_t count, int32_t L, int32_t D, char* wp, hipStream_t s) {
+// what the clearance kernels take of a description: the clouds from sample (window) `cloud0` on, the scale rows from `scale0` on (a long
+// motion's windows have one), L frames per sample
+ClearDev clear_dev(const afm_scene_clearance* a, int64_t cloud0, int64_t scale0, int32_t L, int32_t D) {
     ClearDev g = {};
-    g.q = a->q + (int64_t)start * a->N * 3;
-    g.weight = a->weight ? a->weight + (int64_t)start * a->N : nullptr;
-    g.c = a->exempt ? a->c + (int64_t)start * a->N * a->Kc : nullptr;
-    g.mean = a->mean; g.std = a->std; g.scale = a->scale + start;
+    g.q = a->q + cloud0 * a->N * 3;
+    g.weight = a->weight ? a->weight + cloud0 * a->N : nullptr;
+    g.c = a->exempt ? a->c + cloud0 * a->N * a->Kc : nullptr;
+    g.mean = a->mean; g.std = a->std; g.scale = a->scale + scale0;
     for (int k = 0; k < a->K; ++k) {
         g.cols[k] = a->h3d ? 0 : a->cols[k];
         const double r2 = a->radius[k] * a->radius[k];
@@ -1148,6 +1269,19 @@ int clear_sub(const afm_scene_clearance* a, bool add, int32_t start, const float
     g.min_height = a->has_min_height ? ceil_f32(a->min_height) : -INFINITY;
     g.c_min = a->exempt ? ceil_f32(a->c_min) : INFINITY;
     g.t_start = a->t_start;
+    return g;
+}
+
+// h3d: positions and S [count][L][K][3], c / s [count][L][2]; added to the terms in front: the adjoint's own rows [count][L][D]
+int64_t clear_workspace_bytes(const afm_scene_clearance* a, bool add, int64_t count, int64_t L, int64_t D) {
+    if (!a->h3d) return 0;
+    return h3d_extra_bytes(count, L, a->K) + (add ? afm_loop::align256(count * L * D * 4) : 0);
+}
+
+// the clearance's launches on the samples [start, start + count); add: grad holds the result of the terms in front, the sum goes there
+int clear_sub(const afm_scene_clearance* a, bool add, int32_t start, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+              float* energy, int32_t count, int32_t L, int32_t D, char* wp, hipStream_t s) {
+    const ClearDev g = clear_dev(a, start, start, L, D);
     const unsigned nblk = (unsigned)((L + g.fpb - 1) / g.fpb);
     const dim3 grid(grad ? nblk : 1u, (unsigned)count);
     if (!a->h3d) {
@@ -1169,7 +1303,57 @@ int clear_sub(const afm_scene_clearance* a, bool add, int32_t start, const float
     return 0;
 }
 
+// the long clearance's buffers of `count` long motions: the windows' raw sums Sb [count * S][L][K][4], then - h3d - the recovery's and the
+// adjoint's of (count, F), with the adjoint's own rows when its result is added
+int64_t long_clear_workspace_bytes(const afm_scene_clearance* a, bool add, int64_t count, int64_t S, int64_t L, int64_t F, int64_t D) {
+    return afm_loop::align256(count * S * L * a->K * 16) + clear_workspace_bytes(a, add, count, F, D);
+}
+
+// the long clearance's launches on the long motions [start, start + count): lng / glong [count][F][D] the joined motion and its gradient,
+// tl [count] or NULL; add: glong holds the result of the terms in front, the sum goes there.  Column form: the long pass and the join;
+// h3d: recovery over F frames, long pass, join, adjoint.
+int long_clear_sub(const afm_scene_clearance* a, const afm_stitch& st, int32_t F, bool add, int32_t start, const float* lng, const int64_t* tl,
+                   float* glong, float* energy, int32_t count, int32_t L, int32_t D, char* wp, hipStream_t s) {
+    const int S = st.windows, wins = count * S;
+    const ClearDev g = clear_dev(a, (int64_t)start * S, start, L, D);
+    const LongGeo lg = {S, st.overlap, F};
+    float* Sb = (float*)wp; wp += afm_loop::align256((int64_t)wins * L * a->K * 16);
+    const dim3 g1((unsigned)((L + g.fpb - 1) / g.fpb), (unsigned)wins), g2(glong ? (unsigned)((F + g.fpb - 1) / g.fpb) : 1u, (unsigned)count);
+    const int64_t* skip = energy ? nullptr : tl;                // (the energy reads every long motion's sums)
+    if (!a->h3d) {
+        hipLaunchKernelGGL(long_clear_kernel, g1, dim3(CLEAR_THREADS), 0, s, g, lg, lng, (const float*)nullptr, skip, Sb);
+        AFM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(long_clear_join_kernel, g2, dim3(256), 0, s, g, lg, st.weights, (const float*)Sb, tl, 0, add ? 1 : 0, glong, energy);
+        AFM_CHECK_LAUNCH();
+        return 0;
+    }
+    const H3dPlan p = h3d_plan(a->mean, a->std, g.scale, *a->h3d, a->K, F, D, start, count, false, 1.f, a->t_start, wp);
+    float* tmp = (float*)p.end;                     // (add: the adjoint's own rows [count][F][D])
+    hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.rec, lng, (const uint8_t*)nullptr, p.pos,
+                       glong ? p.cs : nullptr);
+    AFM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(long_clear_kernel, g1, dim3(CLEAR_THREADS), 0, s, g, lg, lng, (const float*)p.pos, skip, Sb);
+    AFM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(long_clear_join_kernel, g2, dim3(256), 0, s, g, lg, st.weights, (const float*)Sb, tl, 1, 0, glong ? p.S : nullptr, energy);
+    AFM_CHECK_LAUNCH();
+    if (!glong) return 0;
+    if (add) hipLaunchKernelGGL(h3d_adjoint_add_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, lng, (const uint8_t*)nullptr, tl, p.cs,
+                                p.S, tmp, glong);
+    else hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, lng, (const uint8_t*)nullptr, tl, p.cs, p.S,
+                            glong);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
 inline const afm_motion_guide* set_terms(const afm_motion_guide* terms) { return terms && (terms->contact || terms->targets) ? terms : nullptr; }
+
+// a sum's terms and the clearance next to them describe one motion: the same mean / std, the same form, the same to_scene
+bool terms_agree(const afm_motion_guide* terms, const afm_scene_clearance* clear) {
+    const float *mean = terms->contact ? terms->contact->mean : terms->targets->mean, *std = terms->contact ? terms->contact->std : terms->targets->std;
+    const afm_h3d_layout* h = terms->contact ? terms->contact->h3d : terms->targets->h3d;
+    if (mean != clear->mean || std != clear->std || !h != !clear->h3d) return false;
+    return !h || (h->to_scene == clear->h3d->to_scene && h->to_scene_stride == clear->h3d->to_scene_stride);
+}
 
 }  // namespace
 
@@ -1183,12 +1367,7 @@ __attribute__((visibility("hidden"))) int afm_scene_guide_check(const afm_motion
     if (!clear) return 0;
     const int rc = clear_check(clear, L, D);
     if (rc != 0) return rc;
-    if (terms) {
-        const float *mean = terms->contact ? terms->contact->mean : terms->targets->mean, *std = terms->contact ? terms->contact->std : terms->targets->std;
-        const afm_h3d_layout* h = terms->contact ? terms->contact->h3d : terms->targets->h3d;
-        if (mean != clear->mean || std != clear->std || !h != !clear->h3d) return AFM_E_BADARG;
-        if (h && (h->to_scene != clear->h3d->to_scene || h->to_scene_stride != clear->h3d->to_scene_stride)) return AFM_E_BADARG;
-    }
+    if (terms && !terms_agree(terms, clear)) return AFM_E_BADARG;
     return 0;
 }
 
@@ -1255,11 +1434,11 @@ bool long_geometry_ok(const afm_long_guide* g, int32_t L) {
 struct LongPlan {
     float *lng, *glong;
     int64_t* tl;
-    char *cws, *tws;                // the contact term's buffers (its windows', then the h3d form's of the long motion), the targets'
+    char *cws, *tws, *lws;          // the contact term's buffers (its windows', then the h3d form's of the long motion), the targets', the clearance's
     int64_t cbytes, bytes;
 };
 
-LongPlan long_plan(const afm_long_guide* g, int64_t count, int32_t L, int32_t D, char* wp) {
+LongPlan long_plan(const afm_long_guide* g, int64_t count, int32_t L, int32_t D, char* wp, const afm_scene_clearance* clear = nullptr) {
     const afm_motion_guide* m = g->terms;
     const int64_t F = g->frames, S = g->stitch.windows;
     LongPlan p = {};
@@ -1276,6 +1455,8 @@ LongPlan long_plan(const afm_long_guide* g, int64_t count, int32_t L, int32_t D,
     wp += p.cbytes;
     p.tws = wp;
     if (m->targets) wp += targets_workspace_bytes(m->targets, m->contact != nullptr, count, F, D);
+    p.lws = wp;
+    if (clear) wp += long_clear_workspace_bytes(clear, m->contact || m->targets, count, S, L, F, D);
     p.bytes = wp - base;
     return p;
 }
@@ -1299,23 +1480,50 @@ __attribute__((visibility("hidden"))) int64_t afm_long_guide_workspace_bytes(con
     return long_plan(g, count, L, D, nullptr).bytes;
 }
 
+// what a long description with a clearance next to its terms (either may be missing, not both) must satisfy before anything is enqueued
+__attribute__((visibility("hidden"))) int afm_long_scene_guide_check(const afm_long_guide* g, const afm_scene_clearance* clear, int32_t L, int32_t D) {
+    if (!g || !g->terms || !long_geometry_ok(g, L)) return AFM_E_BADARG;
+    const afm_motion_guide* terms = set_terms(g->terms);
+    if (!terms && !clear) return AFM_E_BADARG;
+    if (terms) {
+        const int rc = afm_long_guide_check(g, L, D);
+        if (rc != 0) return rc;
+    }
+    if (!clear) return 0;
+    const int rc = clear_check(clear, L, D);
+    if (rc != 0) return rc;
+    if (g->stitch.windows > 1 && g->stitch.overlap > 0 && !g->stitch.weights) return AFM_E_BADARG;          // the crossfade reads the row
+    if (terms && !terms_agree(terms, clear)) return AFM_E_BADARG;
+    if (g->frames > 65535) return AFM_E_UNSUPPORTED;
+    if (clear->h3d && (size_t)H3D_SCAN_ROWS * g->frames * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
+    return 0;
+}
+
+// the workspace of `count` long motions of a checked description (clear == NULL: afm_long_guide_workspace_bytes exactly)
+__attribute__((visibility("hidden"))) int64_t afm_long_scene_guide_workspace_bytes(const afm_long_guide* g, const afm_scene_clearance* clear, int32_t count,
+                                                                                   int32_t L, int32_t D) {
+    return long_plan(g, count, L, D, nullptr, clear).bytes;
+}
+
 // the long motions [start, start + count) of the description's batch; x, t and grad already point at window start * S, the energies at
-// long motion `start`.  run_contact / run_targets: the terms this call computes
-__attribute__((visibility("hidden"))) int afm_long_guidance_sub(const afm_long_guide* g, bool run_contact, bool run_targets, int32_t start, const float* x,
-                                                                const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
-                                                                int32_t count, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes,
-                                                                void* stream) {
-    const int rc = afm_long_guide_check(g, L, D);
+// long motion `start`.  run_contact / run_targets / run_clear: the terms this call computes (clear == NULL: afm_long_guidance's launches)
+__attribute__((visibility("hidden"))) int afm_long_scene_guidance_sub(const afm_long_guide* g, const afm_scene_clearance* clear, bool run_contact,
+                                                                      bool run_targets, bool run_clear, int32_t start, const float* x, const int64_t* t,
+                                                                      float* grad, float* energy_contact, float* energy_targets, float* energy_clear,
+                                                                      int32_t count, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes,
+                                                                      void* stream) {
+    const int rc = afm_long_scene_guide_check(g, clear, L, D);
     if (rc != 0) return rc;
     const afm_motion_guide* m = g->terms;
     run_contact = run_contact && m->contact;
     run_targets = run_targets && m->targets;
-    if (!x || (!grad && !energy_contact && !energy_targets) || start < 0 || count < 0 || (energy_contact && !run_contact) ||
-        (energy_targets && !run_targets) || (!run_contact && !run_targets)) return AFM_E_BADARG;
+    run_clear = run_clear && clear;
+    if (!x || (!grad && !energy_contact && !energy_targets && !energy_clear) || start < 0 || count < 0 || (energy_contact && !run_contact) ||
+        (energy_targets && !run_targets) || (energy_clear && !run_clear) || (!run_contact && !run_targets && !run_clear)) return AFM_E_BADARG;
     const int S = g->stitch.windows, ov = g->stitch.overlap, F = g->frames;
     if ((int64_t)count * S > 65535) return AFM_E_UNSUPPORTED;
     if (count == 0) return 0;
-    const LongPlan p = long_plan(g, count, L, D, (char*)workspace);
+    const LongPlan p = long_plan(g, count, L, D, (char*)workspace, clear);
     if (!workspace || workspace_bytes < p.bytes) return AFM_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int rcj = afm_stitch_join(x, p.lng, count, S, ov, L, D, F, stream);
@@ -1367,12 +1575,28 @@ __attribute__((visibility("hidden"))) int afm_long_guidance_sub(const afm_long_g
             AFM_CHECK_LAUNCH();
         }
     }
-    if (run_targets && (grad || energy_targets)) {
+    const bool targets = run_targets && (grad || energy_targets);
+    if (targets) {
         const int rct = targets_sub(m->targets, contact && grad, start, p.lng, nullptr, tl, grad ? p.glong : nullptr, energy_targets, count, F, D, p.tws, s);
         if (rct != 0) return rct;
     }
+    if (run_clear && (grad || energy_clear)) {
+        const int rcl = long_clear_sub(clear, g->stitch, F, (contact || targets) && grad, start, p.lng, tl, grad ? p.glong : nullptr, energy_clear, count, L,
+                                       D, p.lws, s);
+        if (rcl != 0) return rcl;
+    }
     if (!grad) return 0;
     return afm_stitch_windows(p.glong, grad, count, S, ov, L, D, F, stream);
+}
+
+__attribute__((visibility("hidden"))) int afm_long_guidance_sub(const afm_long_guide* g, bool run_contact, bool run_targets, int32_t start, const float* x,
+                                                                const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
+                                                                int32_t count, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes,
+                                                                void* stream) {
+    const int rc = afm_long_guide_check(g, L, D);
+    if (rc != 0) return rc;
+    return afm_long_scene_guidance_sub(g, nullptr, run_contact, run_targets, false, start, x, t, grad, energy_contact, energy_targets, nullptr, count, L, D,
+                                       workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t afm_long_guidance_workspace_bytes(const afm_long_guide* g, int32_t B, int32_t L, int32_t D) {
@@ -1387,4 +1611,20 @@ extern "C" int afm_long_guidance(const afm_long_guide* g, const float* x_windows
     if (B < 0 || B % g->stitch.windows != 0) return AFM_E_BADARG;
     return afm_long_guidance_sub(g, true, true, 0, x_windows, t, grad_windows, energy_contact, energy_targets, B / g->stitch.windows, L, D, workspace,
                                  workspace_bytes, stream);
+}
+
+extern "C" int64_t afm_long_scene_guidance_workspace_bytes(const afm_long_scene_guide* g, int32_t B, int32_t L, int32_t D) {
+    if (!g || B < 0 || afm_long_scene_guide_check(g->base, g->clearance, L, D) != 0 || B % g->base->stitch.windows != 0) return AFM_E_BADARG;
+    return afm_long_scene_guide_workspace_bytes(g->base, g->clearance, B / g->base->stitch.windows, L, D) + 256;
+}
+
+extern "C" int afm_long_scene_guidance(const afm_long_scene_guide* g, const float* x_windows, const int64_t* t, float* grad_windows,
+                                       float* energy_contact, float* energy_targets, float* energy_clearance, int32_t B, int32_t L, int32_t D,
+                                       void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!g) return AFM_E_BADARG;
+    const int rc = afm_long_scene_guide_check(g->base, g->clearance, L, D);
+    if (rc != 0) return rc;
+    if (B < 0 || B % g->base->stitch.windows != 0) return AFM_E_BADARG;
+    return afm_long_scene_guidance_sub(g->base, g->clearance, true, true, true, 0, x_windows, t, grad_windows, energy_contact, energy_targets,
+                                       energy_clearance, B / g->base->stitch.windows, L, D, workspace, workspace_bytes, stream);
 }

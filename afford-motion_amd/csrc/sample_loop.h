@@ -57,6 +57,18 @@ __attribute__((visibility("hidden"))) int afm_long_guidance_sub(const afm_long_g
                                                                 int32_t count, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes,
                                                                 void* stream);
 
+// guidance.hip: the long guidance with the scene clearance next to (or without) its terms (afm_long_scene_guide, taken apart: `clear` NULL
+// or the clearance; g->terms may name neither term when it is set) - its checks, the workspace of `count` long motions of a checked
+// description (clear == NULL: afm_long_guide_workspace_bytes exactly), and afm_long_scene_guidance on the long motions [start, start + count)
+__attribute__((visibility("hidden"))) int afm_long_scene_guide_check(const afm_long_guide* g, const afm_scene_clearance* clear, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int64_t afm_long_scene_guide_workspace_bytes(const afm_long_guide* g, const afm_scene_clearance* clear, int32_t count,
+                                                                                   int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int afm_long_scene_guidance_sub(const afm_long_guide* g, const afm_scene_clearance* clear, bool run_contact,
+                                                                      bool run_targets, bool run_clear, int32_t start, const float* x, const int64_t* t,
+                                                                      float* grad, float* energy_contact, float* energy_targets, float* energy_clear,
+                                                                      int32_t count, int32_t L, int32_t D, void* workspace, int64_t workspace_bytes,
+                                                                      void* stream);
+
 namespace afm_loop {
 
 // ---- the sampling update x_t -> x_next of one launch, [B][per_sample] floats: every DDPM, DDIM and guided update outside the fused GEMM /

@@ -1227,6 +1227,65 @@ int afm_cmdm_long_guide_loop_range(const afm_cmdm_weights* w, float* x, const fl
                                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scene clearance of stitched long motions (v7-additive): afm_scene_clearance as a third term of the long guidance.  Each window clears
+ * ITS OWN frames of the joined motion against ITS OWN scene: q [G * S][N][3], weight [G * S][N] or NULL and - with `exempt` - c
+ * [G * S][N][Kc] are per window (the window "sit down" exempts the sofa its contact map marks, the window "walk" does not); scale is [G],
+ * to_scene [3][4] or [G][3][4], t of long motion g is t[g * S], no frame mask is read.  With P[g,f,k,:] the positions of the joined motion
+ * (afm_long_guide, steps 1 and 2), per window b = g * S + w and each of its long frames f = a_w .. min(a_w + L, F) - 1:
+ *   d, d2, u, wu of p = P[g,f,k,:] against the points of window b exactly as afm_scene_clearance forms them (ir2, coef rounded once from
+ *   float64, the w rules of min_height and exempt unchanged);  S_b[f,k,:] = sum_n wu * d,  e_b[f,k] = sum_n wu * u  in the order of the
+ *   clearance kernel: wave v adds, from 0 and in ascending n, the points with (n mod 1024) / 128 == v, then the eight partial sums are
+ *   joined serially, v = 0 .. 7.
+ * Per long frame the windows' sums are crossfaded with the stitch's own weight row (wl, wr = afm_stitch.weights, [2][ov]): with
+ * w1 = min(f / hop, S - 1), the earlier window w1 - 1 also holds f iff w1 > 0 and i = f - w1 * hop < ov;
+ *   one window:   J[g,f,k,:] = S_b[f,k,:]                               (the bits as they are)
+ *   two windows:  J[g,f,k,:] = (wl[i] * S_earlier) + (wr[i] * S_later)  float32, each product rounded, then the sum, no contraction
+ * (a plain sum would push twice as hard inside every overlap of one room; identical clouds in both windows give the single-scene push up
+ * to rounding; an exemption fades out as the next action fades in).
+ *   column form:  grad_long[g,f,cols[k]+a] = ((scale[g] * coef[k]) * std_a) * J_a
+ *   h3d form:     coef[k] * J_a, rounded, goes to S[g][f][k][3] and through the recovery's adjoint on (B = G, L = F) with scale[g]
+ * With S == 1, F == L and no mask this is bit-identical to afm_scene_guidance's clearance on the one window.
+ * The sum: grad_long = (grad_contact + grad_targets) + grad_clearance - the clearance's last launch (the join, or the adjoint) adds its
+ * complete result to what the terms in front of it wrote, one rounded addition per element; then afm_stitch_windows.  Exact zeros: every
+ * unnamed column, the padded tail, a long motion with t >= t_start, a joint-frame with no obstacle point inside its radius in any window
+ * that holds it.
+ * energy_clearance[g]: a joint-frame's e_b times its frame weight omega, rounded (omega = 1 outside overlaps - the value as it is -,
+ * wl[i] / wr[i] in the earlier / later window of a shared frame); E_b = the clearance kernel's energy reduction over the window's L
+ * frames - blocks of 64 / K whole frames, lane i adds its joint-frame's value over the blocks in ascending order, a frame at or behind F
+ * counting 0, then one wave's butterfly; E[g] = the serial sum of its windows' E_b from 0 in window order.  The gradient is
+ * -scale * dE/dx.  No atomics: a long motion's result depends neither on G nor on its place in the batch.
+ * Launches of the clearance with a gradient: the long pass (blocks over (frame block of a window, window)) and the join (blocks over
+ * (frame block of the long motion, long motion)) - 2; h3d: recovery over F frames, long pass, join, adjoint - 4.  afm_long_guidance's join
+ * and windows launches are shared with the terms in front.
+ *
+ * base->terms is always set (it carries gk [T][G * S] for the loops) and may name neither term; then the clearance must be set.
+ * AFM_E_BADARG before anything is enqueued: everything afm_long_guidance and afm_scene_guidance refuse (a radius that is not positive,
+ * `up` outside 0..2, an exemption without c), terms and clearance that disagree on mean / std, form or to_scene, no term at all, weights
+ * missing where two windows share frames.  AFM_E_UNSUPPORTED: F > 65535, more than 65535 windows, 7 * F floats beyond the LDS with h3d.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const afm_long_guide* base;            /* stitch, frames, terms; base->terms is always set and may name neither term */
+    const afm_scene_clearance* clearance;  /* q / weight / c per window [G * S]; scale [G]; first_guided / t_start as everywhere; or NULL */
+} afm_long_scene_guide;
+int64_t afm_long_scene_guidance_workspace_bytes(const afm_long_scene_guide* g, int32_t B, int32_t L, int32_t D);
+int afm_long_scene_guidance(const afm_long_scene_guide* g, const float* x_windows, const int64_t* t, float* grad_windows,
+                            float* energy_contact, float* energy_targets, float* energy_clearance, int32_t B, int32_t L, int32_t D,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/* afm_cmdm_long_guide_loop_range with the description swapped: the same loop body, the step's gradient the sum above over the terms whose
+ * own first_guided the executed step has reached (a term not yet reached launches nothing and contributes exactly zero; steps before any
+ * term starts launch exactly what afm_cmdm_stitch_loop_range launches).  gk: base->terms->gk [T][G * S]. */
+int64_t afm_cmdm_long_scene_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                       const afm_cfg2_args* cfg2, const afm_long_scene_guide* guide);
+int afm_cmdm_long_scene_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                         const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                         const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                         const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_long_scene_guide* guide,
+                                         int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                         void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CDM (`Perceiver`) denoiser forward.  Replaces CDM.forward + ContactPerceiver.forward
  * (models/cdm.py:474-513,155-188) and the Perceiver-IO blocks it uses (models/modules.py:234-661:
  * CrossAttentionLayer, SelfAttentionBlock, MLP, Residual; pad mask / rotary / kv-cache never used).

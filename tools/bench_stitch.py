@@ -21,7 +21,19 @@ What guiding a stitched chain costs (afm.diffusion.LongGuidance, afm_cmdm_long_g
 (stitch= and the LongGuidance as cond_fn; every step guided) and "stitched" (the same chain without it) alternated in one call, as ms per
 long motion, with the guided step's gradient-launch count taken from torch.profiler (device kernels of a guided chain minus those of the
 unguided one, per step and sub-batch, counted at G = 1).  With --parent-lib the unguided stitched chain of every cell is also run on the parent's library in a fresh child
-process and compared bit for bit (sha256 of the result)."""
+process and compared bit for bit (sha256 of the result).
+
+    python tools/bench_stitch.py --clearance [--guided contact|targets|both] --repr [pos|h3d] [--parent-lib PATH] [--md profiles/long_clearance_bench.md]
+
+What a SceneClearance costs on a stitched chain (LongGuidance(stitch, contact, targets, clearance), afm_cmdm_long_scene_guide_loop_range):
+K = 16 joints, radius 0.5, every window against its own cloud of N points.  Arms, alternated inside every repetition: "clearance" (the
+guided arm with the term added - or, without --guided, the term alone), "guided" (only with --guided: the same LongGuidance without it) and
+"stitched" (unguided).  With --parent-lib the "guided" and "stitched" arms also run on the parent commit's library, one timed window each
+in a fresh child process in front of every repetition: their code path is the parent's.  --md appends a section to the file.
+
+    python tools/bench_stitch.py --clearance --kernel --repr [pos|h3d] --groups G [--calls 20]
+
+only gradient evaluations of the term on G long motions, for a kernel trace (rocprofv3 --kernel-trace --stats)."""
 import argparse
 import hashlib
 import json
@@ -45,6 +57,9 @@ NEW = ("afm_stitch_blend", "afm_stitch_windows", "afm_stitch_join", "afm_stitch_
        "afm_cmdm_stitch_loop_range")
 LONG_NEW = ("afm_long_guidance_workspace_bytes", "afm_long_guidance", "afm_stitch_guide_step", "afm_cmdm_long_guide_loop_workspace_bytes",
             "afm_cmdm_long_guide_loop_range")
+LONG_SCENE_NEW = ("afm_long_scene_guidance_workspace_bytes", "afm_long_scene_guidance", "afm_cmdm_long_scene_guide_loop_workspace_bytes",
+                  "afm_cmdm_long_scene_guide_loop_range")
+CLEAR_K, CLEAR_RADIUS, CLEAR_SCALE = 16, 0.5, 1e-3          # tools/bench_clearance.py's term: a small scale keeps the synthetic model's samples finite
 JOINTS = [0, 10, 11, 12, 20, 21]          # the six contact joints of the h3d skeleton
 COLS = [4, 259, 100, 7, 193, 64]          # --repr pos: six column triples of the 263-column vector read as absolute positions
 MIN_WINDOW_S = 0.1
@@ -69,7 +84,7 @@ def bench_child(lib):
     """Child process: bench.py on another build's library (the entry points it lacks are not bound)."""
     from afm import ffi
     ffi._LIB_PATH = os.path.abspath(lib)
-    for name in NEW + LONG_NEW:
+    for name in NEW + LONG_NEW + LONG_SCENE_NEW:
         ffi.EXPORTS.pop(name, None)
     import runpy
     runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")
@@ -122,7 +137,7 @@ def hash_child(lib):
     """Child process: the unguided stitched chain of every cell on another build's library; one JSON line of sha256 digests."""
     from afm import ffi
     ffi._LIB_PATH = os.path.abspath(lib)
-    for name in LONG_NEW:
+    for name in LONG_NEW + LONG_SCENE_NEW:
         ffi.EXPORTS.pop(name, None)
     model, cfg, dev = _setup()
     out = {}
@@ -131,11 +146,11 @@ def hash_child(lib):
     print(json.dumps(out))
 
 
-def _long_guide(st, G, terms, form, dev):
+def _long_guide(st, G, terms, form, dev, clearance=False):
     """the LongGuidance of the guided arm: six contact joints against each window's own map, the root's path as targets at every
-    tenth long frame, one scale per long motion"""
+    tenth long frame, one scale per long motion; ``clearance``: with a SceneClearance on 16 joints as the third term (terms None: alone)"""
     from afm import synth
-    from afm.diffusion import ContactGuidance, JointTargets, LongGuidance
+    from afm.diffusion import ContactGuidance, JointTargets, LongGuidance, SceneClearance
     F = st.full(L)
     mean, std = 0.3 * synth.gaussian("bench_long_mean", (D,)), 0.5 + synth.gaussian("bench_long_std", (D,)).abs()
     std[0], std[1:3] = 0.05, 0.1
@@ -149,7 +164,11 @@ def _long_guide(st, G, terms, form, dev):
     if terms in ("targets", "both"):
         kw = dict(target=target, weight=weight, scale=0.1 * scale)
         tg = JointTargets.h3d(JOINTS[:1], mean, std, **kw) if form == "h3d" else JointTargets(COLS[:1], mean, std, **kw)
-    return LongGuidance(st, ct, tg)
+    clr = None
+    if clearance:
+        kw = dict(radius=CLEAR_RADIUS, scale=CLEAR_SCALE)
+        clr = SceneClearance.h3d(list(range(CLEAR_K)), mean, std, **kw) if form == "h3d" else SceneClearance([3 * j for j in range(CLEAR_K)], mean, std, **kw)
+    return LongGuidance(st, ct, tg, clr)
 
 
 def _kernel_count(fn):
@@ -161,6 +180,123 @@ def _kernel_count(fn):
         fn()
         torch.cuda.synchronize()
     return sum(1 for ev in prof.events() if str(getattr(ev, "device_type", "")).endswith("CUDA") and not movers.search(ev.name))
+
+
+def _clear_arms(args, model, loop, B, kw, x_T, st, G, dev):
+    """the arms of one --clearance cell"""
+    run = lambda guide: (lambda: loop(model, (B, L, D), noise=x_T, clip_denoised=False, cond_fn=guide, model_kwargs=kw, stitch=st))
+    arms = {"clearance": run(_long_guide(st, G, args.guided, args.repr, dev, clearance=True))}
+    if args.guided:
+        arms["guided"] = run(_long_guide(st, G, args.guided, args.repr, dev))
+    arms["stitched"] = run(None)
+    return arms
+
+
+def time_child(args):
+    """Child process: one timed window of the "guided" and "stitched" arms of every --clearance cell on another build's library"""
+    from afm import ffi
+    ffi._LIB_PATH = os.path.abspath(args.time_child)
+    for name in LONG_SCENE_NEW:
+        ffi.EXPORTS.pop(name, None)
+    model, cfg, dev = _setup()
+    out = {}
+    for key, d, loop, G, B, kw, x_T, st in _cells(model, cfg, dev):
+        arms = _clear_arms(args, model, loop, B, kw, x_T, st, G, dev)
+        for arm in ("guided", "stitched"):
+            if arm in arms:
+                fn = arms[arm]
+                fn()
+                fn()
+                out[f"{key}/{arm}"] = _timed(fn, max(1, math.ceil(MIN_WINDOW_S / _timed(fn))))
+    print("CHILD " + json.dumps(out), flush=True)
+
+
+def clearance_kernel(args):
+    """only gradient evaluations of the term on --groups long motions (a kernel trace reads the kernels' own times)"""
+    from afm import synth
+    from afm.diffusion import Stitch
+    dev = torch.device("cuda:0")
+    st, G = Stitch(S, OV, length=L), args.groups
+    guide = _long_guide(st, G, None, args.repr, dev, clearance=True)
+    x = st.windows_of(synth.gaussian(f"bench_long_clear_x_{G}", (G, st.full(L), D)).to(dev), L)
+    kw = dict(c_pc_xyz=synth.scene_cloud(G * S, N).to(dev))
+    t = torch.zeros(G * S, dtype=torch.int64, device=dev)
+    for _ in range(args.calls):
+        g = guide(x, t, **kw)
+    torch.cuda.synchronize()
+    print(json.dumps({"tool": "bench_stitch --clearance --kernel", "repr": args.repr, "G": G, "S": S, "L": L, "F": st.full(L), "K": CLEAR_K, "N": N,
+                      "calls": args.calls, "pairs_per_call": G * S * L * CLEAR_K * N, "finite": bool(torch.isfinite(g).all()), "nonzero": bool(g.any())}))
+
+
+def clearance_main(args):
+    model, cfg, dev = _setup()
+    what = f"{args.guided} + clearance" if args.guided else "clearance alone"
+    out = {"clearance": what, "repr": args.repr, "shape": {"S": S, "L": L, "overlap": OV, "N": N, "D": D, "K": CLEAR_K, "radius": CLEAR_RADIUS},
+           "device": torch.cuda.get_device_name(0), "reps": args.reps, "cells": {}}
+    cells = list(_cells(model, cfg, dev))
+    arms, calls, ts, finite, launches, parent = {}, {}, {}, {}, {}, {}
+    for key, d, loop, G, B, kw, x_T, st in cells:
+        out["shape"]["frames"] = st.full(L)
+        arms[key] = _clear_arms(args, model, loop, B, kw, x_T, st, G, dev)
+        for arm, fn in arms[key].items():
+            fn()
+            last = fn()
+            calls[key, arm], ts[key, arm] = max(1, math.ceil(MIN_WINDOW_S / _timed(fn))), []
+            if arm == "clearance":
+                finite[key] = bool(torch.isfinite(last).all())
+        if G == GROUPS[0]:          # the launch count, per sub-batch: taken where the chain is one sub-batch
+            launches[key.split("/")[0]] = (_kernel_count(arms[key]["clearance"]) - _kernel_count(arms[key]["guided" if args.guided else "stitched"])) / d.num_timesteps
+    for _ in range(args.reps):
+        if args.parent_lib:          # a fresh process (this one has the GPU open; it idles meanwhile)
+            torch.cuda.synchronize()
+            cmd = [sys.executable, os.path.abspath(__file__), "--time-child", args.parent_lib, "--clearance", "--repr", args.repr]
+            r = subprocess.run(cmd + (["--guided", args.guided] if args.guided else []), capture_output=True, text=True, cwd=ROOT, timeout=600)
+            line = [l for l in r.stdout.splitlines() if l.startswith("CHILD ")]
+            if r.returncode != 0 or not line:
+                raise RuntimeError(f"the parent library's child failed ({r.returncode}): {r.stderr[-800:]}")
+            for k, v in json.loads(line[0][6:]).items():
+                parent.setdefault(k, []).append(v)
+        for key, *_ in cells:          # alternated: a drift of the chip's clocks lands on every arm
+            for arm, fn in arms[key].items():
+                ts[key, arm].append(_timed(fn, calls[key, arm]))
+    for key, d, loop, G, B, kw, x_T, st in cells:
+        steps = d.num_timesteps
+        cell = {arm: _stats(ts[key, arm], steps, G) for arm in arms[key]}
+        for arm in ("guided", "stitched"):
+            if f"{key}/{arm}" in parent:
+                cell[f"parent_{arm}"] = _stats(parent[f"{key}/{arm}"], steps, G)
+                cell[f"{arm}_over_parent"] = round(statistics.median(ts[key, arm]) / statistics.median(parent[f"{key}/{arm}"]), 4)
+        base = "guided" if args.guided else "stitched"
+        cell["steps"], cell["rows"], cell["finite"] = steps, B, finite[key]
+        cell["clearance_over_" + base] = round(statistics.median(ts[key, "clearance"]) / statistics.median(ts[key, base]), 4)
+        cell["added_ms_per_step"] = round((statistics.median(ts[key, "clearance"]) - statistics.median(ts[key, base])) * 1e3 / steps, 4)
+        cell["added_launches_per_guided_step"] = launches[key.split("/")[0]]
+        out["cells"][key] = cell
+        print(f"[long clearance bench] {key}: {cell}", flush=True)
+    if args.md:
+        f = out["shape"]["frames"]
+        lines = [f"## {what}, `{args.repr}`: S = {S}, L = {L}, ov = {OV} ({f} frames), N = {N}, K = {CLEAR_K}, radius {CLEAR_RADIUS}, {out['device']}", "",
+                 f"`tools/bench_stitch.py --clearance{' --guided ' + args.guided if args.guided else ''} --repr {args.repr}`, {args.reps} repetitions, the arms "
+                 "alternated inside every repetition, a timed window = the loop calls that fill 100 ms; ms per long motion (median; spread = (max - min) / median, %).  "
+                 f"Every step guided.  Final samples of the clearance arm finite: {all(finite.values())}.", "",
+                 "| sampler | G | rows | steps | arm | ms / long motion | ms / step | spread % |", "|---|---|---|---|---|---|---|---|"]
+        for key, c in out["cells"].items():
+            s_, g = key.split("/G")
+            for arm in ("stitched", "parent_stitched", "guided", "parent_guided", "clearance"):
+                if arm in c:
+                    lines.append(f"| {s_} | {g} | {c['rows']} | {c['steps']} | {arm} | {c[arm]['ms_per_long_motion']} | {c[arm]['ms_per_step']} | {c[arm]['spread_pct']} |")
+        base = "guided" if args.guided else "stitched"
+        lines += ["", f"| sampler | G | clearance / {base} | added ms / step | added launches / guided step and sub-batch (counted at G = 1) | stitched / parent's | guided / parent's |",
+                  "|---|---|---|---|---|---|---|"]
+        for key, c in out["cells"].items():
+            s_, g = key.split("/G")
+            lines.append(f"| {s_} | {g} | {c['clearance_over_' + base]} | {c['added_ms_per_step']} | {c['added_launches_per_guided_step']:g} | "
+                         f"{c.get('stitched_over_parent', 'n/a')} | {c.get('guided_over_parent', 'n/a')} |")
+        os.makedirs(os.path.dirname(os.path.abspath(args.md)), exist_ok=True)
+        with open(args.md, "a") as fh:
+            fh.write("\n".join(lines) + "\n\n")
+    print(json.dumps(out))
+    return 0 if all(finite.values()) else 1
 
 
 def guided_main(args):
@@ -232,12 +368,21 @@ def main():
     ap.add_argument("--hash-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--guided", choices=("contact", "targets", "both"), default=None)
     ap.add_argument("--repr", choices=("pos", "h3d"), default="h3d")
+    ap.add_argument("--clearance", action="store_true")
+    ap.add_argument("--kernel", action="store_true", help="with --clearance: only gradient evaluations of the term, for a kernel trace")
+    ap.add_argument("--groups", type=int, default=8)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--time-child", default=None, help=argparse.SUPPRESS)
     args, rest = ap.parse_known_args()
     if args.bench_child:
         sys.argv = [os.path.join(ROOT, "bench.py")] + rest
         return bench_child(args.bench_child)
     if args.hash_child:
         return hash_child(args.hash_child)
+    if args.time_child:
+        return time_child(args)
+    if args.clearance:
+        return clearance_kernel(args) if args.kernel else clearance_main(args)
     if args.guided:
         return guided_main(args)
 
