@@ -26,7 +26,7 @@ from . import autograd as AG
 from . import ffi, fold, ops
 from ._cache import HeldKey
 from .base import Model
-from .guidance import ContactGuidance, JointTargets, LongGuidance, MotionGuidance, SceneClearance, scale_row, scale_value
+from .guidance import ContactGuidance, FootGrounding, JointTargets, LongGuidance, MotionGuidance, SceneClearance, scale_row, scale_value
 from .scene import SceneMapEncoder, SceneMapEncoderDecoder
 from .text import TextEncoderMixin, lang_feat_dim_type
 
@@ -147,7 +147,8 @@ class LoopExtras(NamedTuple):
     ``cfg`` / ``branch_streams``: GuidedCMDM's afm_cfg_args or afm_cfg2_args and its branch-stream switch.  ``guide``: an
     afm.diffusion.ContactGuidance (afm_cmdm_guide_loop_range), JointTargets or MotionGuidance (afm_cmdm_motion_guide_loop_range: the step's
     gradient the sum of the terms that have started), a SceneClearance or a MotionGuidance that carries one
-    (afm_cmdm_scene_guide_loop_range) - the gradient at every guided step's x_t is computed on the sub-batch's stream and
+    (afm_cmdm_scene_guide_loop_range), a FootGrounding or a MotionGuidance that carries one (afm_cmdm_ground_guide_loop_range; no stitched
+    chain takes a grounding) - the gradient at every guided step's x_t is computed on the sub-batch's stream and
     enters the update launch; the loop runs in the separate-update form like an imputing one, and steps before the guidance starts launch
     what an imputing loop launches.  ``stitch``: an afm.diffusion.Stitch - the batch rows are overlapping windows of long motions and
     every step's update launch gives the frames two windows share one pred_xstart (afm_cmdm_stitch_loop_range, every deterministic
@@ -173,7 +174,7 @@ class LoopPlan(NamedTuple):
 def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, term: str = "none", stitch: bool = False) -> LoopPlan:
     """The entry a chain reaches: ``update`` "ddpm" / "ddim" / "dpm", ``guidance`` "none" / "cfg" (one scale) / "cfg2" (two), with or without
     ``impute``, ``term`` "none" / "contact" (a bare ContactGuidance) / "motion" (anything that carries targets) / "scene" (anything that carries a
-    SceneClearance) / "long" (a LongGuidance:
+    SceneClearance) / "ground" (anything that carries a FootGrounding) / "long" (a LongGuidance:
     only stitched, only with a deterministic update; the long description takes the guidance's slot and carries the stitch) / "long_scene" (a
     LongGuidance that carries a SceneClearance: the same slots, afm_cmdm_long_scene_guide_loop_range), stitched or not.  By
     priority: a term's entry, the stitched one, the 2M one (each runs every form it is asked for on a workspace of its own size: a history
@@ -188,7 +189,7 @@ def plan_loop_call(update: str, guidance: str = "none", impute: bool = False, te
     ddim = "ddim_rows" if update == "ddim" else None
     ddpm = ("c1", "c2", "sigma") if update == "ddpm" else (None, None, None)
     tail = ("n_steps", "first_step", "seed", "sample_index0")
-    own = {"contact": "guide", "motion": "motion_guide", "scene": "scene_guide", "long": "long_guide",
+    own = {"contact": "guide", "motion": "motion_guide", "scene": "scene_guide", "ground": "ground_guide", "long": "long_guide",
            "long_scene": "long_scene_guide"}.get(term, "stitch" if stitch else None)
     if own is not None:                 # both kinds of rows and the 2M rows, one of the three set
         last = ("stitch" if own == "stitch" else "term",)
@@ -644,7 +645,8 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
             gk_of = None                    # the description whose gk rows a range call sets
             if ex.guide is not None:
                 both = MotionGuidance(targets=ex.guide) if isinstance(ex.guide, JointTargets) else \
-                    MotionGuidance(clearance=ex.guide) if isinstance(ex.guide, SceneClearance) else ex.guide
+                    MotionGuidance(clearance=ex.guide) if isinstance(ex.guide, SceneClearance) else \
+                    MotionGuidance(feet=ex.guide) if isinstance(ex.guide, FootGrounding) else ex.guide
                 term, term_fm, term_keep = both.describe(x, model_kwargs, diffusion)
                 gk_of = term
                 if isinstance(both, ContactGuidance):      # a bare contact term keeps its own entry
@@ -652,10 +654,13 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
                 else:                                                # anything that carries targets: the sum's entry (a LongGuidance: its own)
                     ct, tg = both.contact, both.targets
                     kind, kind_key = "motion", (None if ct is None else (ct.K, model_kwargs["c_pc_xyz"].shape[1]), None if tg is None else tg.K,
-                                                (ct or tg or getattr(both, "clearance", None)).joints is not None)
+                                                (ct or tg or getattr(both, "clearance", None) or getattr(both, "feet", None)).joints is not None)
                     sc = getattr(both, "clearance", None)
                     if sc is not None:                               # anything that carries a clearance: the scene entry
                         kind, kind_key = "scene", kind_key + (sc.K, model_kwargs["c_pc_xyz"].shape[1])
+                    ft = getattr(both, "feet", None)
+                    if ft is not None:                               # anything that carries a grounding: the ground entry, a kind of its own
+                        kind, kind_key = "ground", kind_key + (None if sc is None else "scene", ft.K)
                 if isinstance(both, LongGuidance):         # no frame mask: validity is the geometry; gk rows per window, on its terms
                     base = term if both.clearance is None else term.base.contents          # (a clearance: the long description is the base)
                     kind, gk_of, long_key = "long" if both.clearance is None else "long_scene", base.terms.contents, kind_key + (base.frames,)

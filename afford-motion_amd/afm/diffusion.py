@@ -28,7 +28,7 @@ import torch
 
 from . import ffi, ops
 from .cmdm import COND_SWITCHES, LoopExtras
-from .guidance import CondFnError, ContactGuidance, Impute, JointTargets, LongGuidance, MotionGuidance, SceneClearance, Stitch, _guide_mask          # noqa: F401 (kept in this namespace)
+from .guidance import CondFnError, ContactGuidance, FootGrounding, Impute, JointTargets, LongGuidance, MotionGuidance, SceneClearance, Stitch, _guide_mask          # noqa: F401 (kept in this namespace)
 
 
 def betas_for_alpha_bar(num_diffusion_timesteps: int, alpha_bar: Callable[[float], float], max_beta: float = 0.999):
@@ -529,13 +529,13 @@ class GaussianDiffusion:
         """The keywords of ``native(...)`` for this chain, or None: sample step by step.  Native: the denoiser has an ``afm_native_loop``
         and nothing needs the host between steps - no rescaled timesteps, no condition switch in ``model_kwargs``, no generic
         ``denoised_fn`` / ``cond_fn``.  A ``denoised_fn`` that is an `Impute` stays native where the loop names ``impute``, DPM-Solver++
-        where it names ``dpm_order``; a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets`, a `SceneClearance`, a `MotionGuidance` or (stitched) a `LongGuidance`, and a `Stitch`,
+        where it names ``dpm_order``; a ``cond_fn`` that is a `ContactGuidance`, a `JointTargets`, a `SceneClearance`, a `FootGrounding`, a `MotionGuidance` or (stitched) a `LongGuidance`, and a `Stitch`,
         where it names ``contact_guide`` / ``stitch`` (GuidedCMDM) or - the plain CMDM, whose public keywords stay the CDM's - takes a
         private ``_guidance`` bundle (afm.cmdm.LoopExtras)."""
         if native is None or self.rescale_timesteps or any(k in (model_kwargs or {}) for k in COND_SWITCHES):
             return None
         impute = denoised_fn if isinstance(denoised_fn, Impute) else None
-        guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance, SceneClearance, LongGuidance)) else None
+        guide = cond_fn if isinstance(cond_fn, (ContactGuidance, JointTargets, MotionGuidance, SceneClearance, FootGrounding, LongGuidance)) else None
         if (denoised_fn is not None and impute is None) or (cond_fn is not None and guide is None):
             return None
         kw, private = {}, {}

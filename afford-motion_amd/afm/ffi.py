@@ -251,6 +251,24 @@ class SceneGuide(C.Structure):
     _fields_ = [("terms", C.POINTER(MotionGuide)), ("clearance", C.POINTER(SceneClearance)), ("gk", c_f32p), ("frame_mask", C.c_void_p)]
 
 
+GROUND_LABEL_COL = 259            # HumanML3D's foot-contact columns 259..262
+GROUND_LABEL_SLOT = {7: 0, 10: 1, 8: 2, 11: 3}          # left foot (joints 7, 10) before the right one (8, 11)
+
+
+class FootGrounding(C.Structure):
+    """afm_foot_grounding (v7-additive): the foot-grounding description - de-normalisation, scale, the columns (or ``h3d``), the up axis,
+    the labels switch, for the loops the term's own first guided step, the floor, a height per joint and the two weights."""
+    _fields_ = [("mean", c_f32p), ("std", c_f32p), ("scale", c_f32p), ("cols", i32 * GUIDE_MAX_JOINTS), ("K", i32), ("up", i32),
+                ("labels", i32), ("first_guided", i32), ("floor", C.c_double), ("height", C.c_double * GUIDE_MAX_JOINTS),
+                ("floor_weight", C.c_double), ("skate_weight", C.c_double), ("t_start", i64), ("h3d", C.POINTER(H3dLayout))]
+
+
+class GroundGuide(C.Structure):
+    """afm_ground_guide (v7-additive): the sum of an afm_scene_guide (or NULL) and the foot grounding (or NULL) and, for the loops, the gk
+    rows [T][B] and the guidance's frame mask."""
+    _fields_ = [("terms", C.POINTER(SceneGuide)), ("feet", C.POINTER(FootGrounding)), ("gk", c_f32p), ("frame_mask", C.c_void_p)]
+
+
 class Stitch(C.Structure):
     """afm_stitch (v7-additive): a batch of G * S overlapping windows of G long motions - windows per motion, shared frames of two
     neighbours, the device weight row [2][overlap] (wl then wr)."""
@@ -351,6 +369,15 @@ EXPORTS = {
     "afm_cmdm_motion_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
                                                    C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p,
                                                    C.c_void_p, C.POINTER(MotionGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
+                                                   C.POINTER(C.c_void_p), C.c_void_p]),
+    "afm_ground_guidance_workspace_bytes": (i64, [C.POINTER(GroundGuide), i32, i32, i32]),
+    "afm_ground_guidance": (C.c_int, [C.POINTER(GroundGuide), c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32,
+                                      C.c_void_p, i64, C.c_void_p]),
+    "afm_cmdm_ground_guide_loop_workspace_bytes": (i64, [C.POINTER(CmdmWeights), i32, i32, i32, C.POINTER(CfgArgs), C.POINTER(Cfg2Args),
+                                                         C.POINTER(GroundGuide)]),
+    "afm_cmdm_ground_guide_loop_range": (C.c_int, [C.POINTER(CmdmWeights), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.POINTER(DdimRows),
+                                                   C.POINTER(DpmRows), c_f32p, c_f32p, c_f32p, C.POINTER(CfgArgs), C.POINTER(Cfg2Args), c_f32p,
+                                                   C.c_void_p, C.POINTER(GroundGuide), i32, i32, u64, i64, i32, i32, C.c_void_p, C.c_void_p, i64, i32,
                                                    C.POINTER(C.c_void_p), C.c_void_p]),
     "afm_scene_guidance_workspace_bytes": (i64, [C.POINTER(SceneGuide), i32, i32, i32]),
     "afm_scene_guidance": (C.c_int, [C.POINTER(SceneGuide), c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, C.c_void_p,

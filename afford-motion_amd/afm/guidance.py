@@ -1,5 +1,5 @@
 """What a sampling chain is conditioned on besides the denoiser's own inputs: known values (`Impute`), overlapping windows of a long
-motion (`Stitch`), and the analytic ``cond_fn`` guidance terms (`ContactGuidance`, `JointTargets`, `SceneClearance`, their sum `MotionGuidance`, and
+motion (`Stitch`), and the analytic ``cond_fn`` guidance terms (`ContactGuidance`, `JointTargets`, `SceneClearance`, `FootGrounding`, their sum `MotionGuidance`, and
 `LongGuidance`, the terms on the joined long motion of a stitched chain).  The
 samplers of afm.diffusion take them, the native loops of afm.cmdm / afm.cdm read their descriptions; afm.diffusion re-exports every name
 (``afm.diffusion.Stitch is afm.guidance.Stitch``).  This module imports `ffi` and `ops` only: of a diffusion object it reads
@@ -274,7 +274,7 @@ def _guide_mask(x: torch.Tensor, model_kwargs, who: str):
 
 
 class _JointTerm:
-    """What `ContactGuidance`, `JointTargets` and `SceneClearance` share: K joints named as column triples of absolute positions or (``.h3d``) as joints of
+    """What `ContactGuidance`, `JointTargets`, `SceneClearance` and `FootGrounding` share: K joints named as column triples of absolute positions or (``.h3d``) as joints of
     HumanML3D features placed by ``to_scene``, the mean / std that de-normalise the motion, a scale per sample, ``t_start`` - and, per
     call, the pieces of the C description both fill the same way."""
     _NOUN = "guided"            # "1 to 16 <noun> joints" (_NAME: the class's name in its messages)
@@ -647,28 +647,158 @@ class SceneClearance(_JointTerm):
         return ops.scene_guidance(g, x, fm, grad=False, energy=True)[3]
 
 
+class FootGrounding(_JointTerm):
+    """A ``cond_fn`` that keeps the feet honest: no joint below the floor, no planted foot sliding over it - the one term that couples
+    frame f with frame f + 1 (afm_ground_guidance, HIP; no network, no autograd).  The harder the other terms pull or push, the more a
+    planted foot skates; this term holds it.
+
+    ``cols``: K ints (K <= 16) as for `ContactGuidance`; ``FootGrounding.h3d(joints, mean, std, to_scene=None, ...)`` names joints 0..21
+    of a HumanML3D-feature motion instead (the feet are 7, 10 - left ankle, left toes - and 8, 11).  ``floor``: the floor's height along
+    ``up`` (0..2).  ``height``: a positive float or K of them - a joint counts as planted at the floor and as free at ``floor + height``.
+    ``floor_weight`` / ``skate_weight``: both >= 0, not both 0.  ``contact``: "height" (the pair weights come from the joints' heights) or
+    "labels" (``.h3d`` only: they are the motion's own foot-contact columns).  ``scale``: a float or a [B] tensor.  ``t_start`` as for the
+    other terms.  Read from ``model_kwargs``: ``x_mask``.
+
+    With p[b,f,k,:] the positions the other terms compute, float32, each operation rounded on its own, ih[k] = float32(1 / height_k),
+    fw / sw = float32 of the weights, cf = float32(2 * floor_weight) and cs = float32(2 * skate_weight) formed in float64 and rounded once,
+    a < b the two axes that are not ``up``:
+
+        h      = p[b,f,k,up] - float32(floor);   pen = max(0, -h);   g = min(1, max(0, 1 - h * ih[k]))
+        s[f,k] = g[f,k] * g[f+1,k]  if the frames f and f + 1 are both valid, else 0                           (contact="height")
+        s[f,k] = min(1, max(0, x[b,f,259+slot(k)] * std + mean))  under the same validity rule                 (contact="labels")
+        dl_a   = p[b,f+1,k,a] - p[b,f,k,a]
+        E[b]   = sum over valid f, k of  fw * (pen * pen) + sw * (s[f,k] * (dl_a * dl_a + dl_b * dl_b))
+        m[f,k,up] = cf * pen;   m[f,k,a] = cs * (s[f,k] * dl_a[f] - s[f-1,k] * dl_a[f-1])    (a missing or invalid pair contributes 0)
+        columns:  grad[b,f,cols[k]+a] = (scale[b] * std_a) * m_a                                                (one launch)
+        h3d:      m, carried through the adjoint of the recovery with scale[b] (three launches: recovery, grounding, adjoint)
+
+    ``guide(x, t, **model_kwargs)`` returns -scale[b] * dE/dx WITH THE PAIR WEIGHTS s HELD CONSTANT.  That is on purpose: differentiating
+    s would lift a sliding foot out of contact to escape the penalty; with s held the foot is slowed down where it is.  The floor part is
+    the exact gradient.  The result is exactly zero in every other column, in padded frames, in a sample with t >= t_start, in a sample
+    without a valid frame and in a joint-frame that neither penetrates the floor nor belongs to a pair with s > 0.
+    ``guide.energy(x, **model_kwargs)`` returns E [B]; a sample whose frames are all padded has E = 0.
+
+    ``contact="labels"``: HumanML3D's feature layout puts the left foot (joints 7 and 10) before the right one (8 and 11) in its
+    foot-contact columns 259..262, so slot = {7: 0, 10: 1, 8: 2, 11: 3}; the label of frame f describes the step f -> f + 1, which is why
+    it weights that pair.  The convention is HumanML3D's own and is NOT pinned by the reference project, which holds no code that reads
+    these columns.  It needs the ``.h3d`` form, D >= 263 and joints out of {7, 10, 8, 11}.
+
+    Every element of the gradient is one expression of the sample's own values (no sum across threads).  Order of the energy's sum (no
+    atomics; bit-identical run to run; a function of the sample alone): one block of 256 threads per sample, thread i adds from 0 the
+    items e = f * K + k = i, i + 256, ... in that order (a padded frame's item is skipped), then the fixed butterfly of each wave and
+    ((r0 + r1) + r2) + r3 over the four waves.  Handed as ``cond_fn`` it stays in the native loops wherever
+    the other terms do (afm_cmdm_ground_guide_loop_range); `MotionGuidance` sums it with them.  Stitched chains (`LongGuidance`) do not
+    take it yet."""
+    _NAME = "FootGrounding"
+
+    def __init__(self, cols, mean: torch.Tensor, std: torch.Tensor, *, floor: float = 0.0, height=0.05, up: int = 2, floor_weight: float = 1.0,
+                 skate_weight: float = 1.0, contact: str = "height", scale=1.0, t_start: Optional[int] = None):
+        self._init(cols, None, None, mean, std, scale, t_start, floor=floor, height=height, up=up, floor_weight=floor_weight,
+                   skate_weight=skate_weight, contact=contact)
+
+    @classmethod
+    def h3d(cls, joints, mean: torch.Tensor, std: torch.Tensor, *, to_scene: Optional[torch.Tensor] = None, floor: float = 0.0, height=0.05,
+            up: int = 2, floor_weight: float = 1.0, skate_weight: float = 1.0, contact: str = "height", scale=1.0,
+            t_start: Optional[int] = None) -> "FootGrounding":
+        """The grounding of a HumanML3D-feature motion (``data_repr`` "h3d", D >= 67; ``contact="labels"``: D >= 263): ``joints`` are joint
+        indices 0..21, ``to_scene`` a float32 [3, 4] or [B, 3, 4] tensor [A|t] on the samples' device (None: identity; ``up`` names an axis
+        of the scene).  See the class docstring."""
+        self = cls.__new__(cls)
+        self._init(None, joints, to_scene, mean, std, scale, t_start, floor=floor, height=height, up=up, floor_weight=floor_weight,
+                   skate_weight=skate_weight, contact=contact)
+        return self
+
+    def _own(self, floor, height, up, floor_weight, skate_weight, contact) -> tuple:
+        who, K = self._who, self.K
+        try:
+            h = [float(height)] * K if not hasattr(height, "__len__") else [float(v) for v in height]
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: height must be a positive float or {K} of them, got {height!r}") from None
+        if len(h) != K:
+            raise ValueError(f"{who}: height must be a positive float or {K} of them, got {len(h)}")
+        if not all(v > 0.0 and v < float("inf") for v in h):
+            raise ValueError(f"{who}: every height must be positive, got {h}")
+        if int(up) not in (0, 1, 2):
+            raise ValueError(f"{who}: up names a coordinate 0..2, got {up!r}")
+        fw, sw, fl = float(floor_weight), float(skate_weight), float(floor)
+        if not (0.0 <= fw < float("inf") and 0.0 <= sw < float("inf")):
+            raise ValueError(f"{who}: floor_weight and skate_weight must be >= 0, got {floor_weight!r} and {skate_weight!r}")
+        if fw == 0.0 and sw == 0.0:
+            raise ValueError(f"{who}: floor_weight and skate_weight are both 0 - the term would do nothing")
+        if fl != fl or abs(fl) == float("inf"):
+            raise ValueError(f"{who}: floor must be a finite height, got {floor!r}")
+        if contact not in ("height", "labels"):
+            raise ValueError(f"{who}: contact must be 'height' or 'labels', got {contact!r}")
+        if contact == "labels":
+            if self.joints is None:
+                raise ValueError(f"{who}: contact='labels' reads HumanML3D's foot-contact columns - it needs FootGrounding.h3d")
+            if self.D < ffi.GROUND_LABEL_COL + 4:
+                raise ValueError(f"{who}: contact='labels' reads columns {ffi.GROUND_LABEL_COL}..{ffi.GROUND_LABEL_COL + 3}, the motion vector "
+                                 f"has {self.D}")
+            bad = [j for j in self.joints if j not in ffi.GROUND_LABEL_SLOT]
+            if bad:
+                raise ValueError(f"{who}: contact='labels' has labels for the joints 7, 10, 8 and 11 only, got {bad}")
+        self.floor, self.height, self.up, self.floor_weight, self.skate_weight, self.contact = fl, h, int(up), fw, sw, contact
+        return ()
+
+    def describe(self, x: torch.Tensor, model_kwargs, diffusion=None, *, shared=None) -> tuple:
+        """(afm_foot_grounding of this sample tensor and these conditions, x_mask as uint8 or None, what must stay alive with it).
+        ``shared``: the (mean, std, to_scene, stride) device tensors of the term in front of it in a sum - a sum names one set of them."""
+        who = self._who
+        self._check_sample(x)
+        B, L = x.shape[0], x.shape[1]
+        if ((3 * self.K + 1) * L) * 4 > ffi.GUIDE_LDS_BYTES:
+            raise ValueError(f"{who}: the kernel keeps (3 K + 1) * L floats in LDS - {L} frames of {self.K} joints are beyond "
+                             f"{ffi.GUIDE_LDS_BYTES} bytes")
+        scale_fits(self.scale, B, who)
+        fm = _guide_mask(x, model_kwargs, who)
+        ts, stride = self._to_scene_on(B, x.device)
+        ffi.require_gpu(x)
+        mean, std = self._on(x.device)
+        scale = scale_row(self.scale, B, x.device, who)
+        if shared is not None:
+            mean, std = shared[0], shared[1]
+            if self.joints is not None:
+                ts, stride = shared[2], shared[3]
+        g = ffi.FootGrounding()
+        lay = self._fill(g, mean, std, scale, ts, stride, diffusion)
+        g.up, g.labels, g.floor, g.floor_weight, g.skate_weight = self.up, int(self.contact == "labels"), self.floor, self.floor_weight, self.skate_weight
+        g.height[:self.K] = self.height
+        return g, fm, (None, None, mean, std, scale, fm, lay, ts)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        return MotionGuidance(feet=self)(x, t, **model_kwargs)
+
+    def energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        return MotionGuidance(feet=self).feet_energy(x, **model_kwargs)
+
+
 class MotionGuidance:
-    """The sum of a `ContactGuidance`, a `JointTargets` and a `SceneClearance` as one ``cond_fn`` (each may be None, not all):
-    grad = grad_contact + grad_targets + grad_clearance in that order, each term the float32 result of that guidance alone, joined by one
-    rounded addition per element - ``MotionGuidance(contact, targets)(x, t, **kw)`` equals ``contact(x, t, **kw) + targets(x, t, **kw)`` bit
-    for bit, and with a clearance ``... + clearance(x, t, **kw)``.  Each term keeps its
+    """The sum of a `ContactGuidance`, a `JointTargets`, a `SceneClearance` and a `FootGrounding` as one ``cond_fn`` (each may be None, not all):
+    grad = ((grad_contact + grad_targets) + grad_clearance) + grad_feet in that order, each term the float32 result of that guidance alone,
+    joined by one rounded addition per element - ``MotionGuidance(contact, targets)(x, t, **kw)`` equals ``contact(x, t, **kw) +
+    targets(x, t, **kw)`` bit for bit, with a clearance ``... + clearance(x, t, **kw)`` and with a grounding ``... + feet(x, t, **kw)``.
+    Each term keeps its
     own ``scale`` and ``t_start``: a sample (step by step) or a step (native loops) a term does not guide gets exactly zero from it.  The
     terms describe one motion: the same ``mean`` / ``std``, all on columns or all on HumanML3D features, the same ``to_scene`` -
     ValueError otherwise.  The joint lists may differ; an h3d motion is recovered once per term.  Launches per guided step: the contact
-    term's 2 (h3d: 4) plus the targets' 1 (h3d: 3) plus the clearance's 1 (h3d: 3).  ``energies(x, **kw)`` returns (E_contact or None,
-    E_targets or None); the clearance's value is ``guide.clearance.energy(x, **kw)``."""
+    term's 2 (h3d: 4) plus the targets' 1 (h3d: 3) plus the clearance's 1 (h3d: 3) plus the grounding's 1 (h3d: 3).  ``energies(x, **kw)``
+    returns (E_contact or None, E_targets or None); the clearance's value is ``guide.clearance.energy(x, **kw)``, the grounding's
+    ``guide.feet_energy(x, **kw)``.  A sum without a grounding reaches the entry it reached before there was one."""
 
     def __init__(self, contact: Optional[ContactGuidance] = None, targets: Optional[JointTargets] = None,
-                 clearance: Optional[SceneClearance] = None):
-        if contact is None and targets is None and clearance is None:
-            raise ValueError("MotionGuidance: at least one of contact / targets / clearance")
+                 clearance: Optional[SceneClearance] = None, feet: Optional["FootGrounding"] = None):
+        if contact is None and targets is None and clearance is None and feet is None:
+            raise ValueError("MotionGuidance: at least one of contact / targets / clearance / feet")
+        if feet is not None and not isinstance(feet, FootGrounding):
+            raise TypeError(f"MotionGuidance: feet must be a FootGrounding, not {type(feet).__name__}")
         if contact is not None and not isinstance(contact, ContactGuidance):
             raise TypeError(f"MotionGuidance: contact must be a ContactGuidance, not {type(contact).__name__}")
         if targets is not None and not isinstance(targets, JointTargets):
             raise TypeError(f"MotionGuidance: targets must be a JointTargets, not {type(targets).__name__}")
         if clearance is not None and not isinstance(clearance, SceneClearance):
             raise TypeError(f"MotionGuidance: clearance must be a SceneClearance, not {type(clearance).__name__}")
-        terms = [g for g in (contact, targets, clearance) if g is not None]
+        terms = [g for g in (contact, targets, clearance, feet) if g is not None]
         for first, other in zip(terms, terms[1:]):
             if first.D != other.D or not torch.equal(first.mean.cpu(), other.mean.cpu()) or not torch.equal(first.std.cpu(), other.std.cpu()):
                 raise ValueError("MotionGuidance: the two terms de-normalise the motion with different mean / std")
@@ -677,10 +807,10 @@ class MotionGuidance:
             a, b = first.to_scene, other.to_scene
             if (a is None) != (b is None) or (a is not None and a is not b and (a.shape != b.shape or a.device != b.device or not torch.equal(a.cpu(), b.cpu()))):          # (compared on the host: no device arithmetic)
                 raise ValueError("MotionGuidance: the two terms place the motion in the scene with different to_scene transforms")
-        self.contact, self.targets, self.clearance = contact, targets, clearance
+        self.contact, self.targets, self.clearance, self.feet = contact, targets, clearance, feet
 
     def _terms(self) -> list:
-        return [g for g in (self.contact, self.targets, self.clearance) if g is not None]
+        return [g for g in (self.contact, self.targets, self.clearance, self.feet) if g is not None]
 
     @property
     def t_start(self):
@@ -689,8 +819,8 @@ class MotionGuidance:
         return None if any(t is None for t in ts) else max(ts)
 
     def describe(self, x: torch.Tensor, model_kwargs, diffusion: Optional["GaussianDiffusion"] = None) -> tuple:
-        """(afm_motion_guide - with a clearance: afm_scene_guide - of this sample tensor and these conditions, x_mask as uint8 or None,
-        what must stay alive with it).  With ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
+        """(afm_motion_guide - with a clearance: afm_scene_guide, with a grounding: afm_ground_guide - of this sample tensor and these
+        conditions, x_mask as uint8 or None, what must stay alive with it).  With ``diffusion``: each term's first_guided set for a chain on it (the loops)."""
         cg = tg = fm = shared = None
         keep = []
         if self.contact is not None:
@@ -706,15 +836,29 @@ class MotionGuidance:
             g.contact = C.pointer(cg)
         if tg is not None:
             g.targets = C.pointer(tg)
-        if self.clearance is None:
+        if self.clearance is None and self.feet is None:
             return g, fm, keep
-        sg, fm, sk = self.clearance.describe(x, model_kwargs, diffusion, shared=shared)
-        keep.append((sg, sk, g))
-        s = ffi.SceneGuide()
-        s.clearance = C.pointer(sg)
-        if cg is not None or tg is not None:
+        s = None
+        if self.clearance is not None:
+            sg, fm, sk = self.clearance.describe(x, model_kwargs, diffusion, shared=shared)
+            keep.append((sg, sk, g))
+            shared = (sk[3], sk[4], sk[8], sg.h3d.contents.to_scene_stride if sg.h3d else 0)
+            s = ffi.SceneGuide()
+            s.clearance = C.pointer(sg)
+            if cg is not None or tg is not None:
+                s.terms = C.pointer(g)
+        elif cg is not None or tg is not None:
+            s = ffi.SceneGuide()
             s.terms = C.pointer(g)
-        return s, fm, keep
+        if self.feet is None:
+            return s, fm, keep
+        fg, fm, fk = self.feet.describe(x, model_kwargs, diffusion, shared=shared)
+        keep.append((fg, fk, g, s))
+        r = ffi.GroundGuide()
+        r.feet = C.pointer(fg)
+        if s is not None:
+            r.terms = C.pointer(s)
+        return r, fm, keep
 
     def first_guided(self, diffusion: "GaussianDiffusion") -> int:
         """the first executed step of a chain on ``diffusion`` that carries any term"""
@@ -723,7 +867,7 @@ class MotionGuidance:
     def __call__(self, x: torch.Tensor, t: torch.Tensor, **model_kwargs) -> torch.Tensor:
         g, fm, keep = self.describe(x, model_kwargs)
         timed = any(q.t_start is not None for q in self._terms())
-        run = ops.motion_guidance if self.clearance is None else ops.scene_guidance
+        run = ops.ground_guidance if self.feet is not None else ops.motion_guidance if self.clearance is None else ops.scene_guidance
         return run(g, x, fm, t.to(x.device) if timed else None)[0]
 
     def energies(self, x: torch.Tensor, **model_kwargs) -> tuple:
@@ -731,6 +875,13 @@ class MotionGuidance:
             return None, None
         g, fm, keep = MotionGuidance(self.contact, self.targets).describe(x, model_kwargs)
         return ops.motion_guidance(g, x, fm, grad=False, energy=True)[1:]
+
+    def feet_energy(self, x: torch.Tensor, **model_kwargs) -> torch.Tensor:
+        """E_feet [B] of the grounding term (see `FootGrounding`)"""
+        if self.feet is None:
+            raise ValueError("MotionGuidance: feet_energy needs a grounding term")
+        g, fm, keep = MotionGuidance(feet=self.feet).describe(x, model_kwargs)
+        return ops.ground_guidance(g, x, fm, grad=False, energy=True)[4]
 
 
 class LongGuidance:
@@ -805,6 +956,10 @@ class LongGuidance:
                  clearance: Optional[SceneClearance] = None):
         if not isinstance(stitch, Stitch):
             raise TypeError(f"LongGuidance: stitch must be a Stitch, not {type(stitch).__name__}")
+        for term in (contact, targets, clearance):
+            if isinstance(term, FootGrounding):
+                raise ValueError("LongGuidance: a FootGrounding is not evaluated on the joined long motion yet - stitched chains take contact, "
+                                 "targets and clearance only")
         self.stitch = stitch
         self._sum = MotionGuidance(contact, targets, clearance)          # (the terms' types and their agreement, checked once)
         self.contact, self.targets, self.clearance = contact, targets, clearance

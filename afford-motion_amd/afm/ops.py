@@ -606,6 +606,34 @@ def scene_guidance(guide: "ffi.SceneGuide", x: torch.Tensor, frame_mask: Optiona
     return g, ec, et, el
 
 
+def ground_guidance(guide: "ffi.GroundGuide", x: torch.Tensor, frame_mask: Optional[torch.Tensor], t: Optional[torch.Tensor] = None, *,
+                    grad: bool = True, energy: bool = False):
+    """afm_ground_guidance of a filled sum (afm.diffusion.FootGrounding / MotionGuidance build it): -> (grad [B, L, D] or None, the contact
+    term's energy [B] or None, the targets', the clearance's, the grounding's) of x [B, L, D].  grad = ((grad_contact + grad_targets) +
+    grad_clearance) + grad_feet, each term the float32 result of that term alone, one rounded addition per element; a term that is not set
+    contributes nothing and has no energy.  Launches: the terms' of afm_scene_guidance plus the grounding's 1 (h3d: 3); no atomics; the
+    workspace is allocated per call."""
+    lib = ffi.load()
+    ffi.require_gpu(x, frame_mask, t)
+    x = ffi.f32c(x)
+    B, L, D = x.shape
+    fm = None if frame_mask is None else _mask_u8(frame_mask.reshape(B, L))
+    tt = None if t is None else t.to(dtype=torch.int64).contiguous()
+    g = torch.empty_like(x) if grad else None
+    scene = guide.terms.contents if guide.terms else None
+    terms = scene.terms.contents if scene is not None and scene.terms else None
+    new = lambda on: torch.empty(B, dtype=torch.float32, device=x.device) if energy and on else None
+    ec, et = new(terms is not None and bool(terms.contact)), new(terms is not None and bool(terms.targets))
+    el, ef = new(scene is not None and bool(scene.clearance)), new(bool(guide.feet))
+    nbytes = int(lib.afm_ground_guidance_workspace_bytes(C.byref(guide), B, L, D))
+    if nbytes < 0:
+        ffi.check(nbytes, "afm_ground_guidance_workspace_bytes")
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ffi.check(lib.afm_ground_guidance(C.byref(guide), x.data_ptr(), ffi.ptr(fm), ffi.ptr(tt), ffi.ptr(g), ffi.ptr(ec), ffi.ptr(et), ffi.ptr(el), ffi.ptr(ef),
+                                      B, L, D, ws.data_ptr(), ws.numel(), ffi.stream_of(x)), "afm_ground_guidance")
+    return g, ec, et, el, ef
+
+
 def h3d_joint_list(joints, limit: int, who: str):
     """the joint list of a HumanML3D-feature motion as ints (None: all 22), checked: 1..limit joints, each 0..21, none twice"""
     joints = list(range(ffi.H3D_JOINTS)) if joints is None else [int(j) for j in joints]

@@ -24,7 +24,7 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
                      adm_noise: Optional[Dict[str, torch.Tensor]] = None,
                      amdm_noise: Optional[Dict[str, torch.Tensor]] = None, sampler: str = "ddpm",
                      eta: float = 0.0, guidance_scale=None, guidance_drop=("text", "pc"), motion_impute=None,
-                     contact_impute=None, contact_guidance=None, joint_targets=None, clearance=None) -> Dict[str, torch.Tensor]:
+                     contact_impute=None, contact_guidance=None, joint_targets=None, clearance=None, grounding=None) -> Dict[str, torch.Tensor]:
     """text_feat [B, text_dim], xyz [B, N, 3] (B = scenes x k_sample, already flattened) ->
     {"contact": [B, N, J] ADM sample, "cond": [B, N, J] AMDM condition, "motion": [B, frames, D]}.
 
@@ -49,7 +49,8 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
     the motion stage's ``cond_fn``; with ``contact_guidance`` too the stage is guided by their sum (afm.diffusion.MotionGuidance), still in
     its native loop.  ``clearance``: an afm.diffusion.SceneClearance (or ``SceneClearance.h3d``) - joints pushed off the obstacle points of
     ``xyz`` - summed with ``contact_guidance`` / ``joint_targets`` when given; the ``c_pc_contact`` its ``exempt_contact`` reads is the
-    stage's own ``cond``."""
+    stage's own ``cond``.  ``grounding``: an afm.diffusion.FootGrounding (or ``FootGrounding.h3d``) - no joint below the floor, no planted
+    foot sliding - summed with the other three terms when they are given."""
     if sampler not in ("ddpm", "ddim", "dpm++"):
         raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpm++', not {sampler!r}")
     if sampler == "dpm++" and float(eta) != 0.0:
@@ -84,6 +85,8 @@ def two_stage_sample(adm, adm_diffusion, amdm, amdm_diffusion, *, text_feat: tor
         cond_fn = joint_targets if contact_guidance is None else MotionGuidance(contact_guidance, joint_targets)
     if clearance is not None:
         cond_fn = clearance if cond_fn is None else MotionGuidance(contact_guidance, joint_targets, clearance)
+    if grounding is not None:
+        cond_fn = grounding if cond_fn is None else MotionGuidance(contact_guidance, joint_targets, clearance, grounding)
     if guidance_scale is not None:
         amdm = GuidedCMDM(amdm, guidance_scale, guidance_drop)
     motion = loop(amdm_diffusion, amdm, (B, frames, amdm.motion_dim), noise=mn.get("x_T"), clip_denoised=False,

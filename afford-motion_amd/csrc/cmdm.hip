@@ -489,7 +489,7 @@ namespace {
 constexpr int MAX_SUB = 16;           // sub-batches (streams) of one loop call
 constexpr int NEV = 2 * AFM_MAX_LAYERS;      // events of the paired schedule: two cross-stream edges per layer
 
-// the arguments of the loop entry points (afm_cmdm_sample_loop and the twelve *_loop_range entries): the model's tensors, the guidance as
+// the arguments of the loop entry points (afm_cmdm_sample_loop and the thirteen *_loop_range entries): the model's tensors, the guidance as
 // the caller describes it (at most one of cfg / cfg2; neither: unguided), what every loop takes, the imputation
 struct LoopCall {
     const afm_cmdm_weights* w;
@@ -504,7 +504,8 @@ struct LoopCall {
     const afm_cfg2_args* cfg2 = nullptr;
     afm_motion_guide guide = {};      // guided loop: the terms' descriptions of the whole batch (neither term set: none)
     const afm_scene_clearance* clear = nullptr;      // scene-guided loop: the clearance next to (or without) the terms of `guide`
-    bool guided() const { return guide.contact || guide.targets || clear; }
+    const afm_foot_grounding* feet = nullptr;        // ground-guided loop: the foot grounding behind (or without) the other terms
+    bool guided() const { return guide.contact || guide.targets || clear || feet; }
     afm_stitch stitch = {};           // stitched loop: the batch is windows of long motions (windows == 0: not stitched)
     const afm_long_guide* lguide = nullptr;      // long-guided stitched loop: `guide` holds its terms, `stitch` its stitch
     bool stitched() const { return stitch.windows > 0; }
@@ -552,7 +553,7 @@ struct SubBatch : SubRange {
 
 // carves the workspaces of a sub-batch whose range is set at `base` (NULL: sizes only); -> their bytes
 int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* base, SubBatch* sb, bool hist, const afm_motion_guide* guide = nullptr,
-                  const afm_long_guide* lguide = nullptr, const afm_scene_clearance* clear = nullptr) {
+                  const afm_long_guide* lguide = nullptr, const afm_scene_clearance* clear = nullptr, const afm_foot_grounding* feet = nullptr) {
     sb->ws = carve(w, sb->count, L, base, NOISE_STEPS);
     int64_t off = sb->ws.bytes;
     for (int i = 0; i < g.n; ++i) {
@@ -572,7 +573,7 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
         off += align256((int64_t)sb->count * L * w.motion_dim * 4);
         sb->gws = base ? base + off : nullptr;
         sb->gws_bytes = lguide ? afm_long_scene_guide_workspace_bytes(lguide, clear, sb->count / lguide->stitch.windows, L, w.motion_dim)
-                               : afm_scene_guide_workspace_bytes(guide, clear, sb->count, L, w.motion_dim);
+                               : afm_ground_guide_workspace_bytes(guide, clear, feet, sb->count, L, w.motion_dim);
         off += align256(sb->gws_bytes);
     }
     return off;
@@ -581,10 +582,12 @@ int64_t carve_sub(const afm_cmdm_weights& w, const Guidance& g, int L, char* bas
 // the loop workspace of either public description of the guidance (neither: the unguided loop's); AFM_E_BADARG as the loop itself
 int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one, const afm_cfg2_args* two, int B, int L, int n_streams,
                              bool hist = false, const afm_motion_guide* guide = nullptr, int unit = 1, const afm_long_guide* lguide = nullptr,
-                             const afm_scene_clearance* clear = nullptr) {
+                             const afm_scene_clearance* clear = nullptr, const afm_foot_grounding* feet = nullptr) {
     if (validate(w, B, L) != 0 || n_streams < 0 || unit < 1 || B % unit != 0) return AFM_E_BADARG;
-    if (guide && !guide->contact && !guide->targets && !clear) return AFM_E_BADARG;
-    if (clear && (lguide ? afm_long_scene_guide_check(lguide, clear, L, w->motion_dim) : afm_scene_guide_check(guide, clear, L, w->motion_dim)) != 0)
+    if (guide && !guide->contact && !guide->targets && !clear && !feet) return AFM_E_BADARG;
+    if (feet && lguide) return AFM_E_BADARG;
+    if ((clear || feet) &&
+        (lguide ? afm_long_scene_guide_check(lguide, clear, L, w->motion_dim) : afm_ground_guide_check(guide, clear, feet, L, w->motion_dim)) != 0)
         return AFM_E_BADARG;
     if (guide && guide->contact && afm_contact_guidance_workspace_bytes(B, guide->contact->N, guide->contact->K) < 0) return AFM_E_BADARG;
     if (guide && guide->targets && (guide->targets->K <= 0 || guide->targets->K > AFM_GUIDE_MAX_JOINTS)) return AFM_E_BADARG;
@@ -595,7 +598,7 @@ int64_t loop_workspace_bytes(const afm_cmdm_weights* w, const afm_cfg_args* one,
     for (int s = 0; s < n; ++s) {
         SubBatch sb = {};
         unit_sub_range(B, unit, n, s, &sb.start, &sb.count);
-        total += carve_sub(*w, g, L, nullptr, &sb, hist, guide, lguide, clear);
+        total += carve_sub(*w, g, L, nullptr, &sb, hist, guide, lguide, clear, feet);
     }
     return total;
 }
@@ -623,9 +626,11 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
     if (!c.x || (c.w->n_cond > 0 && !c.cond_tokens) || !a.ok() || !c.known != !c.mask) return AFM_E_BADARG;
     if (a.dpm && (!a.ddim || a.noise_term() || a.step_noise || a.first_step < 0)) return AFM_E_BADARG;
     if (c.guided()) {
-        AFM_TRY(c.lguide ? afm_long_scene_guide_check(c.lguide, c.clear, c.L, c.w->motion_dim) : afm_scene_guide_check(&c.guide, c.clear, c.L, c.w->motion_dim));
+        if (c.lguide && c.feet) return AFM_E_BADARG;          // (a long or stitched description takes no grounding)
+        AFM_TRY(c.lguide ? afm_long_scene_guide_check(c.lguide, c.clear, c.L, c.w->motion_dim)
+                         : afm_ground_guide_check(&c.guide, c.clear, c.feet, c.L, c.w->motion_dim));
         if (!c.guide.gk || (c.guide.contact && c.guide.contact->first_guided < 0) || (c.guide.targets && c.guide.targets->first_guided < 0) ||
-            (c.clear && c.clear->first_guided < 0)) return AFM_E_BADARG;
+            (c.clear && c.clear->first_guided < 0) || (c.feet && c.feet->first_guided < 0)) return AFM_E_BADARG;
     }
     const int unit = c.stitched() ? c.stitch.windows : 1;
     if (c.lguide && !c.stitched()) return AFM_E_BADARG;
@@ -643,7 +648,7 @@ int plan_loop(const LoopCall& c, LoopPlan* p) {
         SubBatch& sb = p->sb[s];
         sb = {};
         unit_sub_range(a.B, unit, p->nsub, s, &sb.start, &sb.count);
-        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guided() || c.stitched(), c.guided() ? &c.guide : nullptr, c.lguide, c.clear);
+        off += carve_sub(*c.w, g, c.L, (char*)a.workspace + off, &sb, a.dpm || c.guided() || c.stitched(), c.guided() ? &c.guide : nullptr, c.lguide, c.clear, c.feet);
         sb.stream = p->nsub > 1 ? (hipStream_t)a.streams[s] : (hipStream_t)a.stream;
         if (p->branch_streams) sb.branch = (hipStream_t)g.branch_streams[s];
     }
@@ -702,10 +707,11 @@ int cond_forward(const Loop& l, const SubBatch& sb, int j, StepRows* rows, afm_d
 inline bool contact_step(const Loop& l, int j) { return l.c.guide.contact && l.c.a.first_step + j >= l.c.guide.contact->first_guided; }
 inline bool targets_step(const Loop& l, int j) { return l.c.guide.targets && l.c.a.first_step + j >= l.c.guide.targets->first_guided; }
 inline bool clear_step(const Loop& l, int j) { return l.c.clear && l.c.a.first_step + j >= l.c.clear->first_guided; }
-inline bool guided_step(const Loop& l, int j) { return contact_step(l, j) || targets_step(l, j) || clear_step(l, j); }
+inline bool feet_step(const Loop& l, int j) { return l.c.feet && l.c.a.first_step + j >= l.c.feet->first_guided; }
+inline bool guided_step(const Loop& l, int j) { return contact_step(l, j) || targets_step(l, j) || clear_step(l, j) || feet_step(l, j); }
 
 // the gradient of (sub-batch, step j) at the x the step's evaluations read, on the sub-batch's stream: the launches of afm_motion_guidance
-// for the step's terms (contact: two, h3d four; targets: one, h3d three; clearance: one, h3d three) into the sub-batch's gradient buffer
+// for the step's terms (contact: two, h3d four; targets: one, h3d three; clearance: one, h3d three; grounding: one, h3d three) into the sub-batch's gradient buffer
 int guide_launch(const Loop& l, const SubBatch& sb, int j) {
     if (l.c.lguide) {                 // (sb.start and sb.count are whole long motions)
         const int S = l.c.lguide->stitch.windows;
@@ -715,8 +721,9 @@ int guide_launch(const Loop& l, const SubBatch& sb, int j) {
     }
     // (the guidance's own mask: the denoiser's frame_mask is NULL for a model that does not mask its motion tokens)
     const uint8_t* fm = l.c.guide.frame_mask ? l.c.guide.frame_mask + (int64_t)sb.start * l.c.L : nullptr;
-    return afm_scene_guidance_sub(&l.c.guide, l.c.clear, contact_step(l, j), targets_step(l, j), clear_step(l, j), sb.start, sub_x(l, sb), fm, nullptr,
-                                  sb.ggrad, nullptr, nullptr, nullptr, sb.count, l.c.L, l.p.w.motion_dim, sb.gws, sb.gws_bytes, sb.stream);
+    return afm_ground_guidance_sub(&l.c.guide, l.c.clear, l.c.feet, contact_step(l, j), targets_step(l, j), clear_step(l, j), feet_step(l, j), sb.start,
+                                   sub_x(l, sb), fm, nullptr, sb.ggrad, nullptr, nullptr, nullptr, nullptr, sb.count, l.c.L, l.p.w.motion_dim, sb.gws,
+                                   sb.gws_bytes, sb.stream);
 }
 
 // the update of a sub-batch from its stored pred_xstart (ws.x0; guided: and each branch's, wsb[i].x0 - the list's last branch is the
@@ -869,8 +876,9 @@ int every_form_range(const afm_cmdm_weights* w, float* x, const float* cond_toke
                      const float* d_sigma, const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
                      const afm_motion_guide* guide, const afm_stitch* stitch, int32_t n_steps, int32_t first_step, uint64_t seed,
                      int64_t sample_index0, int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
-                     void* const* side_streams, void* stream, const afm_long_guide* lguide = nullptr, const afm_scene_clearance* clear = nullptr) {
-    if (first_step < 0 || (guide && !guide->contact && !guide->targets && !clear) || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
+                     void* const* side_streams, void* stream, const afm_long_guide* lguide = nullptr, const afm_scene_clearance* clear = nullptr,
+                     const afm_foot_grounding* feet = nullptr) {
+    if (first_step < 0 || (guide && !guide->contact && !guide->targets && !clear && !feet) || (cfg && cfg2) || !known != !mask) return AFM_E_BADARG;
     afm_ddim_rows as_ddim = {};
     AFM_TRY(one_kind_of_rows(&rows, dpm, d_c1 || d_c2 || d_sigma, &as_ddim));
     if ((dpm && step_noise) || (cfg2 && (!frame_mask || !cfg2_ok(cfg2)))) return AFM_E_BADARG;
@@ -881,6 +889,7 @@ int every_form_range(const afm_cmdm_weights* w, float* x, const float* cond_toke
     if (stitch) c.stitch = *stitch;
     c.lguide = lguide;
     c.clear = clear;
+    c.feet = feet;
     return sample_loop_impl(c);
 }
 
@@ -1051,6 +1060,36 @@ extern "C" int afm_cmdm_scene_guide_loop_range(const afm_cmdm_weights* w, float*
     return every_form_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask, &sum, nullptr,
                             n_steps, first_step, seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, nullptr,
                             guide->clearance);
+}
+
+// The same loop with the foot grounding behind (or without) the three terms (afm_ground_guide): the grounding's launch adds to what the
+// terms in front of it wrote.  The loop reads the description's own gk and frame_mask.
+namespace {
+afm_motion_guide ground_sum(const afm_ground_guide* guide) {
+    const afm_motion_guide* m = guide->terms ? guide->terms->terms : nullptr;
+    return {m ? m->contact : nullptr, m ? m->targets : nullptr, guide->gk, guide->frame_mask};
+}
+}  // namespace
+
+extern "C" int64_t afm_cmdm_ground_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                              const afm_cfg2_args* cfg2, const afm_ground_guide* guide) {
+    if ((cfg && cfg2) || !guide || (!guide->terms && !guide->feet)) return AFM_E_BADARG;
+    const afm_motion_guide sum = ground_sum(guide);
+    return loop_workspace_bytes(w, cfg, cfg2, B, L, n_streams, true, &sum, 1, nullptr, guide->terms ? guide->terms->clearance : nullptr, guide->feet);
+}
+
+extern "C" int afm_cmdm_ground_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                                const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows,
+                                                const afm_dpm_rows* dpm, const float* d_c1, const float* d_c2, const float* d_sigma,
+                                                const afm_cfg_args* cfg, const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask,
+                                                const afm_ground_guide* guide, int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0,
+                                                int32_t B, int32_t L, void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams,
+                                                void* const* side_streams, void* stream) {
+    if (!guide || (!guide->terms && !guide->feet)) return AFM_E_BADARG;
+    const afm_motion_guide sum = ground_sum(guide);
+    return every_form_range(w, x, cond_tokens, frame_mask, step_noise, d_timestep_map, rows, dpm, d_c1, d_c2, d_sigma, cfg, cfg2, known, mask, &sum, nullptr,
+                            n_steps, first_step, seed, sample_index0, B, L, sched_scratch, workspace, workspace_bytes, n_streams, side_streams, stream, nullptr,
+                            guide->terms ? guide->terms->clearance : nullptr, guide->feet);
 }
 
 // The stitched loop (afm_stitch: the batch is G * S windows of G long motions), every form behind one entry: the separate-update loop of

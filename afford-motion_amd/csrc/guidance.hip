@@ -1420,6 +1420,333 @@ extern "C" int afm_scene_guidance(const afm_scene_guide* g, const float* x, cons
                                   D, workspace, workspace_bytes, stream);
 }
 
+// ---- foot grounding (afm_foot_grounding): the one term that couples frame f with frame f + 1.  A block owns GROUND_FPB frames of one
+// sample and keeps their K x 3 positions and validity flags, and those of one neighbouring frame on either side, in LDS, so every item
+// (f, k) reads its joint's neighbouring frames from there; the contact weights of a pair are recomputed by both of its frames from the
+// same staged values, hence with the same bits.  The energy, a score, is summed by the sample's block 0 alone, which then stages the whole
+// sample (the contact term's fit: (3 K + 1) L floats).
+namespace {
+
+struct GroundDev {
+    const float *mean, *std, *scale;
+    int cols[AFM_GUIDE_MAX_JOINTS];
+    int lab[AFM_GUIDE_MAX_JOINTS];          // the label column of joint k (contact = labels), else -1
+    float ih[AFM_GUIDE_MAX_JOINTS];         // 1 / height_k, rounded once from float64
+    int K, L, D, up, ax0, ax1;              // ax0 < ax1: the two axes that are not `up`
+    float floor, fw, sw, cf, cs;            // floor_weight, skate_weight, 2 * floor_weight, 2 * skate_weight, each rounded once
+    int64_t t_start;
+};
+
+struct GroundRows {
+    int cols[AFM_GUIDE_MAX_JOINTS], lab[AFM_GUIDE_MAX_JOINTS];
+    float ih[AFM_GUIDE_MAX_JOINTS];
+};
+
+constexpr int GROUND_FPB = 8;               // frames per block: a block stages its frames and one neighbour on either side
+
+// the frames [fs0, fs1) of the sample staged in LDS: positions [fs1 - fs0][K][3] and the validity flags
+struct GroundView {
+    const float* sp;
+    const int* sval;
+    int fs0;
+};
+
+__device__ __forceinline__ float ground_p(const GroundDev& g, const GroundView& v, int f, int k, int a) { return v.sp[((f - v.fs0) * g.K + k) * 3 + a]; }
+
+// g = min(1, max(0, 1 - h * ih)) of the staged joint-frame (f, k)
+__device__ __forceinline__ float ground_gate(const GroundDev& g, const GroundView& v, int f, int k, float ih) {
+#pragma clang fp contract(off)
+    const float h = ground_p(g, v, f, k, g.up) - g.floor;
+    const float m = h * ih;
+    return fminf(1.f, fmaxf(0.f, 1.f - m));
+}
+
+// s[f,k]: the weight of the pair (f, f + 1) of joint k - 0 unless both frames exist and are valid
+__device__ __forceinline__ float ground_pair(const GroundDev& g, const GroundRows& r, const GroundView& v, const float* __restrict__ xb, int f, int k) {
+#pragma clang fp contract(off)
+    if (f < 0 || f + 1 >= g.L || !v.sval[f - v.fs0] || !v.sval[f + 1 - v.fs0]) return 0.f;
+    if (r.lab[k] >= 0) return fminf(1.f, fmaxf(0.f, denorm(xb + (int64_t)f * g.D, g.mean, g.std, r.lab[k])));
+    const float g0 = ground_gate(g, v, f, k, r.ih[k]), g1 = ground_gate(g, v, f + 1, k, r.ih[k]);
+    return g0 * g1;
+}
+
+// s * (p[f+1,k,a] - p[f,k,a]) of a pair with weight s (0: nothing is read)
+__device__ __forceinline__ float ground_slide(const GroundDev& g, const GroundView& v, float s, int f, int k, int a) {
+#pragma clang fp contract(off)
+    if (s == 0.f) return 0.f;
+    const float dl = ground_p(g, v, f + 1, k, a) - ground_p(g, v, f, k, a);
+    return s * dl;
+}
+
+// m[f,k,:] of a valid frame's item: m_up = cf * pen, m_a = cs * (s[f] * dl_a[f] - s[f-1] * dl_a[f-1])
+__device__ __forceinline__ void ground_item(const GroundDev& g, const GroundRows& r, const GroundView& v, const float* __restrict__ xb, int f, int k,
+                                            float m[3]) {
+#pragma clang fp contract(off)
+    const float h = ground_p(g, v, f, k, g.up) - g.floor;
+    const float pen = fmaxf(0.f, -h);
+    const float s1 = ground_pair(g, r, v, xb, f, k), s0 = ground_pair(g, r, v, xb, f - 1, k);
+    const float mu = g.cf * pen;
+    const float u0 = ground_slide(g, v, s1, f, k, g.ax0), v0 = ground_slide(g, v, s0, f - 1, k, g.ax0);
+    const float u1 = ground_slide(g, v, s1, f, k, g.ax1), v1 = ground_slide(g, v, s0, f - 1, k, g.ax1);
+    const float m0 = g.cs * (u0 - v0), m1 = g.cs * (u1 - v1);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) m[a] = a == g.up ? mu : (a == g.ax0 ? m0 : m1);          // (static indices: the array stays in registers)
+}
+
+// One launch, blocks (frame block blockIdx.x, sample blockIdx.y); a block owns the frames [f0, f1), f0 = blockIdx.x * GROUND_FPB, and stages
+// them with one neighbour on either side.  pos == NULL, the column form: p = the de-normalised columns; out = the block's complete grad
+// rows - grad[b,f,cols[k]+a] = (scale[b] * std_a) * m_a, zero in every other column, in a padded frame and in a sample with
+// t[b] >= t_start; ACC: row[d] = row[d] + term for EVERY column (one rounded addition per element on what the terms in front wrote).
+// pos set, the h3d form: p = the recovery's positions [b][f][k][3]; out = S[b][f][k][3] = m (zero in a padded frame) for the adjoint, whose
+// business scale, t_start and the rows are.  energy: the sample's block 0 stages every frame and thread i adds the items
+// e = f * K + k = i, i + 256, ... in that order (a padded frame's item counts as 0 and is skipped),
+// item = fw * (pen * pen) + sw * (s * (dl_a0 * dl_a0 + dl_a1 * dl_a1)), then block_sum (a score, not part of a sampling step).
+template <bool ACC>
+__global__ __launch_bounds__(256) void ground_kernel(const GroundDev g, const float* __restrict__ x, const float* __restrict__ pos,
+                                                     const uint8_t* __restrict__ fmask, const int64_t* __restrict__ t, float* __restrict__ out,
+                                                     float* __restrict__ energy) {
+#pragma clang fp contract(off)
+    extern __shared__ float gsh[];                  // positions [frames staged][K][3], then their validity flags
+    __shared__ GroundRows r;
+    __shared__ float red[4];
+    const int b = blockIdx.y, K = g.K, L = g.L, D = g.D;
+    const bool whole = energy && blockIdx.x == 0;               // (uniform over the block)
+    const int f0 = blockIdx.x * GROUND_FPB, f1 = min(L, f0 + GROUND_FPB);
+    const int fs0 = whole ? 0 : max(0, f0 - 1), fs1 = whole ? L : min(L, f1 + 1), nfs = fs1 - fs0;
+    float* sp = gsh;
+    int* sval = reinterpret_cast<int*>(gsh + (size_t)nfs * K * 3);
+#pragma unroll
+    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k)
+        if (threadIdx.x == k) { r.cols[k] = g.cols[k]; r.lab[k] = g.lab[k]; r.ih[k] = g.ih[k]; }
+    __syncthreads();
+    const float* xb = x + (int64_t)b * L * D;
+    const bool late = !pos && t && t[b] >= g.t_start;           // (uniform over the block)
+    for (int i = threadIdx.x; i < nfs; i += 256) sval[i] = !(fmask && fmask[(int64_t)b * L + fs0 + i]);
+    for (int e = threadIdx.x; e < nfs * K; e += 256) {
+        const int fr = e / K, k = e - fr * K, f = fs0 + fr;
+        float p0 = 0.f, p1 = 0.f, p2 = 0.f;
+        if (!(fmask && fmask[(int64_t)b * L + f])) {
+            if (pos) {
+                const float* pp = pos + (((int64_t)b * L + f) * K + k) * 3;
+                p0 = pp[0]; p1 = pp[1]; p2 = pp[2];
+            } else {
+                const float* xrow = xb + (int64_t)f * D;
+                const int col = r.cols[k];
+                p0 = denorm(xrow, g.mean, g.std, col); p1 = denorm(xrow, g.mean, g.std, col + 1); p2 = denorm(xrow, g.mean, g.std, col + 2);
+            }
+        }
+        sp[e * 3] = p0; sp[e * 3 + 1] = p1; sp[e * 3 + 2] = p2;
+    }
+    __syncthreads();
+    const GroundView v = {sp, sval, fs0};
+    if (whole) {
+        float acc = 0.f;
+        for (int e = threadIdx.x; e < L * K; e += 256) {
+            const int f = e / K, k = e - f * K;
+            if (!sval[f]) continue;
+            const float h = ground_p(g, v, f, k, g.up) - g.floor;
+            const float pen = fmaxf(0.f, -h);
+            const float ef = g.fw * (pen * pen);
+            const float s = ground_pair(g, r, v, xb, f, k);
+            float es = 0.f;
+            if (s != 0.f) {
+                const float d0 = ground_p(g, v, f + 1, k, g.ax0) - ground_p(g, v, f, k, g.ax0);
+                const float d1 = ground_p(g, v, f + 1, k, g.ax1) - ground_p(g, v, f, k, g.ax1);
+                const float q0 = d0 * d0, q1 = d1 * d1;
+                es = g.sw * (s * (q0 + q1));
+            }
+            acc = acc + (ef + es);
+        }
+        acc = block_sum(acc, red);
+        if (threadIdx.x == 0) energy[b] = acc;
+    }
+    if (!out || f0 >= L) return;
+    const int nf = f1 - f0;
+    if (pos) {
+        for (int e = threadIdx.x; e < nf * K; e += 256) {
+            const int fr = e / K, k = e - fr * K, f = f0 + fr;
+            float m[3] = {0.f, 0.f, 0.f};
+            if (sval[f - fs0]) ground_item(g, r, v, xb, f, k, m);
+            float* o = out + (((int64_t)b * L + f) * K + k) * 3;
+            o[0] = m[0]; o[1] = m[1]; o[2] = m[2];
+        }
+        return;
+    }
+    float* rows = out + ((int64_t)b * L + f0) * D;
+    const float sc = g.scale[b];
+    for (int i = threadIdx.x; i < nf * D; i += 256) {
+        const int fr = i / D, d = i - fr * D, f = f0 + fr;
+        float term = 0.f;
+        if (!late && sval[f - fs0])
+            for (int k = 0; k < K; ++k) {
+                const int a = d - r.cols[k];
+                if (a < 0 || a >= 3) continue;
+                float m[3];
+                ground_item(g, r, v, xb, f, k, m);
+                const float ma = a == 0 ? m[0] : (a == 1 ? m[1] : m[2]);
+                term = (sc * g.std[d]) * ma;
+                break;
+            }
+        rows[i] = ACC ? rows[i] + term : term;
+    }
+}
+
+constexpr int GROUND_LABEL_COL = 259;       // HumanML3D's foot-contact columns 259..262: left foot (joints 7, 10), then right (8, 11)
+
+int ground_label_slot(int joint) { return joint == 7 ? 0 : joint == 10 ? 1 : joint == 8 ? 2 : joint == 11 ? 3 : -1; }
+
+int ground_check(const afm_foot_grounding* a, int32_t L, int32_t D) {
+    if (!a->mean || !a->std || !a->scale || L <= 0 || D <= 0) return AFM_E_BADARG;
+    if (a->K <= 0 || a->K > AFM_GUIDE_MAX_JOINTS || a->up < 0 || a->up > 2) return AFM_E_BADARG;
+    for (int k = 0; k < a->K; ++k)
+        if (!(a->height[k] > 0.0) || !(1.0 / a->height[k] <= 3.0e38)) return AFM_E_BADARG;
+    if (!(a->floor_weight >= 0.0) || !(a->skate_weight >= 0.0) || !(a->floor_weight + a->skate_weight > 0.0) ||
+        !(a->floor_weight <= 1.0e38) || !(a->skate_weight <= 1.0e38) || !(a->floor == a->floor)) return AFM_E_BADARG;
+    if (joints_check(a->cols, a->h3d, a->K, D) != 0) return AFM_E_BADARG;
+    if (a->labels) {
+        if (!a->h3d || D < GROUND_LABEL_COL + 4) return AFM_E_BADARG;
+        for (int k = 0; k < a->K; ++k)
+            if (ground_label_slot(a->h3d->joints[k]) < 0) return AFM_E_BADARG;
+    }
+    if (((size_t)a->K * L * 3 + L) * 4 > (size_t)GUIDE_LDS_BYTES || L > 65535) return AFM_E_UNSUPPORTED;
+    if (a->h3d && (size_t)H3D_SCAN_ROWS * L * 4 > (size_t)GUIDE_LDS_BYTES) return AFM_E_UNSUPPORTED;
+    return 0;
+}
+
+// h3d: positions and S [count][L][K][3], c / s [count][L][2]; added to the terms in front: the adjoint's own rows [count][L][D]
+int64_t ground_workspace_bytes(const afm_foot_grounding* a, bool add, int64_t count, int64_t L, int64_t D) {
+    if (!a->h3d) return 0;
+    return h3d_extra_bytes(count, L, a->K) + (add ? afm_loop::align256(count * L * D * 4) : 0);
+}
+
+// the grounding's launches on the samples [start, start + count); add: grad holds the result of the terms in front, the sum goes there
+int ground_sub(const afm_foot_grounding* a, bool add, int32_t start, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+               float* energy, int32_t count, int32_t L, int32_t D, char* wp, hipStream_t s) {
+    GroundDev g = {};
+    g.mean = a->mean; g.std = a->std; g.scale = a->scale + start;
+    for (int k = 0; k < AFM_GUIDE_MAX_JOINTS; ++k) { g.cols[k] = 0; g.lab[k] = -1; g.ih[k] = 0.f; }
+    for (int k = 0; k < a->K; ++k) {
+        g.cols[k] = a->h3d ? 0 : a->cols[k];
+        g.lab[k] = a->labels ? GROUND_LABEL_COL + ground_label_slot(a->h3d->joints[k]) : -1;
+        g.ih[k] = (float)(1.0 / a->height[k]);
+    }
+    g.K = a->K; g.L = L; g.D = D; g.up = a->up;
+    g.ax0 = a->up == 0 ? 1 : 0; g.ax1 = a->up == 2 ? 1 : 2;
+    g.floor = (float)a->floor;
+    g.fw = (float)a->floor_weight; g.sw = (float)a->skate_weight;
+    g.cf = (float)(2.0 * a->floor_weight); g.cs = (float)(2.0 * a->skate_weight);
+    g.t_start = a->t_start;
+    // (the energy's block stages the whole sample; a launch without it GROUND_FPB frames and the two around them)
+    const size_t lds = ((size_t)a->K * 3 + 1) * (energy || L < GROUND_FPB + 2 ? L : GROUND_FPB + 2) * 4;
+    const dim3 grid(grad ? (unsigned)((L + GROUND_FPB - 1) / GROUND_FPB) : 1u, (unsigned)count);
+    if (!a->h3d) {
+        if (add) hipLaunchKernelGGL(ground_kernel<true>, grid, dim3(256), lds, s, g, x, (const float*)nullptr, frame_mask, t, grad, energy);
+        else hipLaunchKernelGGL(ground_kernel<false>, grid, dim3(256), lds, s, g, x, (const float*)nullptr, frame_mask, t, grad, energy);
+        AFM_CHECK_LAUNCH();
+        return 0;
+    }
+    const H3dPlan p = h3d_plan(a->mean, a->std, g.scale, *a->h3d, a->K, L, D, start, count, false, 1.f, a->t_start, wp);
+    float* tmp = (float*)p.end;                     // (add: the adjoint's own rows [count][L][D])
+    hipLaunchKernelGGL(h3d_recover_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.rec, x, frame_mask, p.pos, grad ? p.cs : nullptr);
+    AFM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ground_kernel<false>, grid, dim3(256), lds, s, g, x, (const float*)p.pos, frame_mask, (const int64_t*)nullptr,
+                       grad ? p.S : nullptr, energy);
+    AFM_CHECK_LAUNCH();
+    if (!grad) return 0;
+    if (add) hipLaunchKernelGGL(h3d_adjoint_add_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, x, frame_mask, t, p.cs, p.S, tmp, grad);
+    else hipLaunchKernelGGL(h3d_adjoint_kernel, dim3((unsigned)count), dim3(256), p.scan_lds, s, p.adj, x, frame_mask, t, p.cs, p.S, grad);
+    AFM_CHECK_LAUNCH();
+    return 0;
+}
+
+// the grounding and the terms in front of it describe one motion: the same mean / std, the same form, the same to_scene
+bool feet_agree(const afm_motion_guide* terms, const afm_scene_clearance* clear, const afm_foot_grounding* feet) {
+    const float *mean, *std;
+    const afm_h3d_layout* h;
+    if (clear) { mean = clear->mean; std = clear->std; h = clear->h3d; }
+    else if (terms->contact) { mean = terms->contact->mean; std = terms->contact->std; h = terms->contact->h3d; }
+    else { mean = terms->targets->mean; std = terms->targets->std; h = terms->targets->h3d; }
+    if (mean != feet->mean || std != feet->std || !h != !feet->h3d) return false;
+    return !h || (h->to_scene == feet->h3d->to_scene && h->to_scene_stride == feet->h3d->to_scene_stride);
+}
+
+}  // namespace
+
+// the sum with the foot grounding; feet == NULL: afm_scene_guide_check / _workspace_bytes / afm_scene_guidance_sub exactly
+__attribute__((visibility("hidden"))) int afm_ground_guide_check(const afm_motion_guide* terms, const afm_scene_clearance* clear,
+                                                                 const afm_foot_grounding* feet, int32_t L, int32_t D) {
+    terms = set_terms(terms);
+    if (!feet) return afm_scene_guide_check(terms, clear, L, D);
+    if (terms || clear) {
+        const int rc = afm_scene_guide_check(terms, clear, L, D);
+        if (rc != 0) return rc;
+    }
+    const int rc = ground_check(feet, L, D);
+    if (rc != 0) return rc;
+    if ((terms || clear) && !feet_agree(terms, clear, feet)) return AFM_E_BADARG;
+    return 0;
+}
+
+__attribute__((visibility("hidden"))) int64_t afm_ground_guide_workspace_bytes(const afm_motion_guide* terms, const afm_scene_clearance* clear,
+                                                                               const afm_foot_grounding* feet, int32_t count, int32_t L, int32_t D) {
+    terms = set_terms(terms);
+    const int64_t n = terms || clear ? afm_scene_guide_workspace_bytes(terms, clear, count, L, D) : 0;
+    return feet ? afm_loop::align256(n) + ground_workspace_bytes(feet, terms || clear, count, L, D) : n;
+}
+
+__attribute__((visibility("hidden"))) int afm_ground_guidance_sub(const afm_motion_guide* terms, const afm_scene_clearance* clear,
+                                                                  const afm_foot_grounding* feet, bool run_contact, bool run_targets, bool run_clear,
+                                                                  bool run_feet, int32_t start, const float* x, const uint8_t* frame_mask,
+                                                                  const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
+                                                                  float* energy_clear, float* energy_feet, int32_t count, int32_t L, int32_t D,
+                                                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    terms = set_terms(terms);
+    if (!feet) {
+        if (energy_feet) return AFM_E_BADARG;
+        return afm_scene_guidance_sub(terms, clear, run_contact, run_targets, run_clear, start, x, frame_mask, t, grad, energy_contact, energy_targets,
+                                      energy_clear, count, L, D, workspace, workspace_bytes, stream);
+    }
+    const int rc = afm_ground_guide_check(terms, clear, feet, L, D);
+    if (rc != 0) return rc;
+    run_contact = run_contact && terms && terms->contact;
+    run_targets = run_targets && terms && terms->targets;
+    run_clear = run_clear && clear;
+    if (!x || (!grad && !energy_contact && !energy_targets && !energy_clear && !energy_feet) || start < 0 || count < 0 ||
+        (energy_contact && !run_contact) || (energy_targets && !run_targets) || (energy_clear && !run_clear) || (energy_feet && !run_feet) ||
+        (!run_contact && !run_targets && !run_clear && !run_feet)) return AFM_E_BADARG;
+    if (count > 65535) return AFM_E_UNSUPPORTED;
+    if (count == 0) return 0;
+    if (!workspace || workspace_bytes < afm_ground_guide_workspace_bytes(terms, clear, feet, count, L, D)) return AFM_E_WORKSPACE;
+    const int64_t fbytes = terms || clear ? afm_loop::align256(afm_scene_guide_workspace_bytes(terms, clear, count, L, D)) : 0;
+    const bool front = (run_contact || run_targets || run_clear) && (grad || energy_contact || energy_targets || energy_clear);
+    if (front) {
+        const int rcs = afm_scene_guidance_sub(terms, clear, run_contact, run_targets, run_clear, start, x, frame_mask, t, grad, energy_contact,
+                                               energy_targets, energy_clear, count, L, D, workspace, fbytes, stream);
+        if (rcs != 0) return rcs;
+    }
+    if (run_feet && (grad || energy_feet))
+        return ground_sub(feet, front && grad, start, x, frame_mask, t, grad, energy_feet, count, L, D, (char*)workspace + fbytes, (hipStream_t)stream);
+    return 0;
+}
+
+namespace {
+inline const afm_motion_guide* ground_motion(const afm_ground_guide* g) { return g->terms ? g->terms->terms : nullptr; }
+inline const afm_scene_clearance* ground_clear(const afm_ground_guide* g) { return g->terms ? g->terms->clearance : nullptr; }
+}  // namespace
+
+extern "C" int64_t afm_ground_guidance_workspace_bytes(const afm_ground_guide* g, int32_t B, int32_t L, int32_t D) {
+    if (!g || B < 0 || afm_ground_guide_check(ground_motion(g), ground_clear(g), g->feet, L, D) != 0) return AFM_E_BADARG;
+    return afm_ground_guide_workspace_bytes(ground_motion(g), ground_clear(g), g->feet, B, L, D) + 256;          // (never zero)
+}
+
+extern "C" int afm_ground_guidance(const afm_ground_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                                   float* energy_contact, float* energy_targets, float* energy_clearance, float* energy_feet, int32_t B, int32_t L,
+                                   int32_t D, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!g) return AFM_E_BADARG;
+    return afm_ground_guidance_sub(ground_motion(g), ground_clear(g), g->feet, true, true, true, true, 0, x, frame_mask, t, grad, energy_contact,
+                                   energy_targets, energy_clearance, energy_feet, B, L, D, workspace, workspace_bytes, stream);
+}
+
 // ---- the guidance of stitched long motions (afm_long_guide): the windows joined, the terms evaluated on the long motion, one gradient per
 // long frame handed back to the windows
 namespace {

@@ -48,6 +48,20 @@ __attribute__((visibility("hidden"))) int afm_scene_guidance_sub(const afm_motio
                                                                  float* energy_clear, int32_t count, int32_t L, int32_t D, void* workspace,
                                                                  int64_t workspace_bytes, void* stream);
 
+// guidance.hip: the sum with the foot grounding (afm_ground_guide, taken apart: `terms` and `clear` as above, `feet` NULL or the grounding;
+// at least one of the three) - its checks, the workspace of `count` samples of a checked sum and afm_ground_guidance on the samples
+// [start, start + count), computing the terms named.  feet == NULL: the three functions above, exactly.
+__attribute__((visibility("hidden"))) int afm_ground_guide_check(const afm_motion_guide* terms, const afm_scene_clearance* clear,
+                                                                 const afm_foot_grounding* feet, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int64_t afm_ground_guide_workspace_bytes(const afm_motion_guide* terms, const afm_scene_clearance* clear,
+                                                                               const afm_foot_grounding* feet, int32_t count, int32_t L, int32_t D);
+__attribute__((visibility("hidden"))) int afm_ground_guidance_sub(const afm_motion_guide* terms, const afm_scene_clearance* clear,
+                                                                  const afm_foot_grounding* feet, bool run_contact, bool run_targets, bool run_clear,
+                                                                  bool run_feet, int32_t start, const float* x, const uint8_t* frame_mask,
+                                                                  const int64_t* t, float* grad, float* energy_contact, float* energy_targets,
+                                                                  float* energy_clear, float* energy_feet, int32_t count, int32_t L, int32_t D,
+                                                                  void* workspace, int64_t workspace_bytes, void* stream);
+
 // guidance.hip: the guidance of stitched long motions (afm_long_guide) - its checks, the workspace of `count` long motions of a checked
 // description, and afm_long_guidance on the long motions [start, start + count) (x, t, grad point at window start * S)
 __attribute__((visibility("hidden"))) int afm_long_guide_check(const afm_long_guide* g, int32_t L, int32_t D);

@@ -1098,6 +1098,88 @@ int afm_cmdm_scene_guide_loop_range(const afm_cmdm_weights* w, float* x, const f
                                     void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
                                     void* stream);
 
+/* Foot grounding (v7-additive): no floor penetration, no foot skating - the one term that couples frame f with frame f + 1.  p[b,f,k,:]
+ * are the positions the other terms use (the de-normalised columns, or with `h3d` the recovery kernel's output).  float32, every operation
+ * rounded on its own, with ih[k] = (float)(1 / height[k]), fw = (float)floor_weight, sw = (float)skate_weight,
+ * cf = (float)(2 * floor_weight) and cs = (float)(2 * skate_weight), each formed in float64 and rounded once; a, b = the two axes that are
+ * not `up`, a < b:
+ *   h      = p[b,f,k,up] - (float)floor
+ *   pen    = max(0, -h)                                          depth below the floor
+ *   g      = min(1, max(0, 1 - h * ih[k]))                       1 at / below the floor, 0 at / above height[k]
+ *   s[f,k] = g[f,k] * g[f+1,k]  if the frames f and f + 1 both exist and are valid, else 0                       (labels == 0)
+ *   s[f,k] = min(1, max(0, x[b,f,259+slot(k)] * std + mean))  under the same validity rule                       (labels != 0, h3d only)
+ *   dl_a   = p[b,f+1,k,a] - p[b,f,k,a]
+ *   E[b]   = sum over valid f, k of  fw * (pen * pen) + sw * (s[f,k] * (dl_a * dl_a + dl_b * dl_b))
+ *   m[f,k,up] = cf * pen;   m[f,k,a] = cs * (s[f,k] * dl_a[f] - s[f-1,k] * dl_a[f-1])     (a missing or invalid pair contributes 0)
+ *   column form:  grad[b,f,cols[k]+a] = (scale[b] * std_a) * m_a                                                  (one launch)
+ *   h3d form:     S[b][f][k][3] = m goes through the recovery's adjoint with coef = 1, i.e. with scale[b] alone    (three launches:
+ *                 recovery, grounding, adjoint)
+ * grad is -scale[b] * dE/dx WITH THE PAIR WEIGHTS s HELD CONSTANT - on purpose: a sliding foot is slowed down, it is not lifted out of
+ * contact to escape the penalty.  The floor part is the exact gradient.  grad is exactly zero in every other column, in padded frames, in
+ * a sample with t[b] >= t_start, in a sample without a valid frame (E = 0) and in a joint-frame that neither penetrates the floor nor
+ * belongs to a pair with s > 0.
+ * labels: HumanML3D's own foot-contact columns 259..262 weight the pairs; its feature layout puts the left foot (joints 7, 10) before the
+ * right one (8, 11): slot = {7: 0, 10: 1, 8: 2, 11: 3}; the label of frame f describes the step f -> f + 1.  (The convention is
+ * HumanML3D's; the project this library follows holds no code that reads these columns.)  Needs `h3d`, D >= 263 and joints out of
+ * {7, 10, 8, 11}: AFM_E_BADARG otherwise.
+ * One launch: a block of 256 threads owns 8 frames of one sample and holds their K x 3 positions, and those of one neighbouring frame on
+ * either side, in LDS; the weight of a pair is recomputed by both of its frames from the same staged values.  Every element of grad is
+ * the result of one expression: there is no sum across threads in it.
+ * The order of the energy's sum (no atomics; a function of the sample alone - not of B, of the sample's place or of the run): the sample's
+ * first block stages the sample's L x K x 3 positions; thread i adds, from 0, the items e = f * K + k = i, i + 256, ... in that order (an
+ * item of a padded frame is skipped), item = fw * (pen * pen) + sw * (s * (dl_a * dl_a + dl_b * dl_b)) with the second addend 0 where
+ * s == 0; then the fixed butterfly of each wave and ((r0 + r1) + r2) + r3 over the four waves.  (A score, not part of a sampling step.)
+ * AFM_E_UNSUPPORTED: (3 K + 1) L floats beyond 60 KiB of LDS, L or B beyond 65535, 7 * L floats beyond the LDS with h3d. */
+typedef struct {
+    const float* mean; const float* std;   /* device [D]: de-normalisation of the motion                                  */
+    const float* scale;                    /* device [B]                                                                  */
+    int32_t cols[AFM_GUIDE_MAX_JOINTS];    /* column of x of joint k (y, z: the next two); ignored with `h3d`             */
+    int32_t K;
+    int32_t up;                            /* 0..2: the coordinate that is the height                                     */
+    int32_t labels;                        /* nonzero: the pair weights are the motion's own foot-contact columns         */
+    int32_t first_guided;                  /* loops only: executed steps (first_step + j) below it do not carry this term */
+    double floor;                          /* the floor's height along `up`                                               */
+    double height[AFM_GUIDE_MAX_JOINTS];   /* > 0: joint k counts as planted at the floor, as free at floor + height[k]   */
+    double floor_weight; double skate_weight;  /* both >= 0, not both 0                                                   */
+    int64_t t_start;                       /* with t: samples with t[b] >= t_start get a zero gradient                    */
+    const afm_h3d_layout* h3d;             /* NULL: `cols` name absolute positions; set: x holds HumanML3D features       */
+} afm_foot_grounding;
+
+/* The sum of the four terms: grad = ((grad_contact + grad_targets) + grad_clearance) + grad_feet, each term the float32 result of that
+ * term alone, joined by one rounded addition per element in that order (the grounding's launch - the column kernel, or the adjoint - adds
+ * its complete result to what the terms in front of it wrote); a term that is not set contributes nothing.  At least one term is set; the
+ * grounding and the terms in front agree as the terms of afm_scene_guide must: the same mean / std, the same form, the same to_scene.
+ * The gk and frame_mask of `terms` are not read through this struct. */
+typedef struct {
+    const afm_scene_guide* terms;          /* or NULL                                                                     */
+    const afm_foot_grounding* feet;        /* or NULL                                                                     */
+    const float* gk;                       /* loops only: device [T][B], row i = the coefficient of spaced timestep i     */
+    const uint8_t* frame_mask;             /* loops only: device [B][L], nonzero = padded frame, or NULL                  */
+} afm_ground_guide;
+
+/* grad [B][L][D] and / or the four energies [B] (each may be NULL; an energy of a term that is not set must be NULL) of x [B][L][D];
+ * frame_mask [B][L] or NULL; t [B] or NULL.  AFM_E_BADARG before anything is enqueued: no term set, what afm_scene_guidance refuses, a
+ * height that is not positive, `up` outside 0..2, a negative weight or both 0, labels without h3d / with D < 263 / with another joint,
+ * terms that disagree (above).  AFM_E_WORKSPACE: a workspace below afm_ground_guidance_workspace_bytes. */
+int64_t afm_ground_guidance_workspace_bytes(const afm_ground_guide* g, int32_t B, int32_t L, int32_t D);
+int afm_ground_guidance(const afm_ground_guide* g, const float* x, const uint8_t* frame_mask, const int64_t* t, float* grad,
+                        float* energy_contact, float* energy_targets, float* energy_clearance, float* energy_feet, int32_t B, int32_t L,
+                        int32_t D, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* afm_cmdm_scene_guide_loop_range with the description swapped: the same loop body, the step's gradient the sum above over the terms
+ * whose own first_guided the executed step has reached (a term not yet reached launches nothing and contributes exactly zero).  The
+ * grounding adds one launch per guided step and sub-batch (h3d: three).  Also AFM_E_BADARG: g->gk missing, a negative first_guided.
+ * Stitched and long descriptions take no grounding. */
+int64_t afm_cmdm_ground_guide_loop_workspace_bytes(const afm_cmdm_weights* w, int32_t B, int32_t L, int32_t n_streams, const afm_cfg_args* cfg,
+                                                   const afm_cfg2_args* cfg2, const afm_ground_guide* guide);
+int afm_cmdm_ground_guide_loop_range(const afm_cmdm_weights* w, float* x, const float* cond_tokens, const uint8_t* frame_mask,
+                                     const float* step_noise, const int64_t* d_timestep_map, const afm_ddim_rows* rows, const afm_dpm_rows* dpm,
+                                     const float* d_c1, const float* d_c2, const float* d_sigma, const afm_cfg_args* cfg,
+                                     const afm_cfg2_args* cfg2, const float* known, const uint8_t* mask, const afm_ground_guide* guide,
+                                     int32_t n_steps, int32_t first_step, uint64_t seed, int64_t sample_index0, int32_t B, int32_t L,
+                                     void* sched_scratch, void* workspace, int64_t workspace_bytes, int32_t n_streams, void* const* side_streams,
+                                     void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Long motions as overlapping windows (v7-additive).  G long motions are B = G * S samples [B][L][D]: sample g * S + w is window w of
  * motion g and holds the long frames w * (L - overlap) .. w * (L - overlap) + L - 1, so neighbouring windows share `overlap` frames and,
