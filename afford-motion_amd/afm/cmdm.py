@@ -142,6 +142,13 @@ def _dist_rank() -> int:
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
+def drop_seed(initial_seed: int, drop_calls: int, rank: int = 0) -> int:
+    """The 64-bit seed of one training forward's dropout masks: torch's initial seed, advanced per forward pass with dropout (every pass
+    draws fresh masks) and per rank (every rank draws its own), modulo 2^64.  Pure: the masks of a pass are a function of this seed, the
+    mask id and the element (csrc/common.h DropKey)."""
+    return (initial_seed + 0x9E3779B97F4A7C15 * drop_calls + 0xD1B54A32D192ED03 * rank) & (2**64 - 1)
+
+
 class LoopExtras(NamedTuple):
     """The ``_guidance`` of `CMDM.afm_native_loop`: what only this denoiser's native loop takes (a plain tuple in this order serves too).
     ``cfg`` / ``branch_streams``: GuidedCMDM's afm_cfg_args or afm_cfg2_args and its branch-stream switch.  ``guide``: an
@@ -522,7 +529,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         p_drop = self.dropout_p if self.training else 0.0
         p_pe = float(self.positional_encoder.dropout.p) if self.training else 0.0
         self._drop_calls += 1
-        seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._drop_calls + 0xD1B54A32D192ED03 * _dist_rank()) & (2**64 - 1)
+        seed = drop_seed(torch.initial_seed(), self._drop_calls, _dist_rank())
         # memories: [x4, x3, x2, x1] -> kv_mappling (the K | V projections live inside the decoder layer operator)
         feats = self.contact_encoder(kwargs["c_pc_xyz"], kwargs["c_pc_contact"])
         mems = []
@@ -574,7 +581,7 @@ class CMDM(_FlatParamsMixin, TextEncoderMixin, nn.Module):
         p_drop = self.dropout_p if self.training else 0.0
         p_pe = float(self.positional_encoder.dropout.p) if self.training else 0.0
         self._drop_calls += 1
-        seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._drop_calls + 0xD1B54A32D192ED03 * _dist_rank()) & (2**64 - 1)   # per call, per rank
+        seed = drop_seed(torch.initial_seed(), self._drop_calls, _dist_rank())
 
         # time token: pe[t] -> Linear -> SiLU -> Linear (modules.py:48-53)
         time_emb = self.timestep_embedder.run(timesteps.to(device=dev, dtype=torch.int64)).view(B, 1, d)

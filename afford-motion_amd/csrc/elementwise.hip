@@ -263,8 +263,8 @@ extern "C" int afm_contact_glue(const float* sample, float* out, int64_t n, floa
 
 extern "C" int afm_masked_mse(const float* target, const float* pred, const uint8_t* frame_mask, float* out, int32_t B,
                               int32_t L, int32_t D, void* stream) {
+    if (B == 0) return 0;                                     // empty batch (pointers may be null), as afm_masked_mse_bwd
     if (!target || !pred || !out || B < 0 || L <= 0 || D <= 0) return AFM_E_BADARG;
-    if (B == 0) return 0;
     hipLaunchKernelGGL(masked_mse_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, target, pred, frame_mask, out, L, D);
     AFM_CHECK_LAUNCH();
     return 0;

@@ -289,7 +289,9 @@ int afm_bn_fold(const float* w, const float* b, const float* running_mean, const
 int afm_contact_glue(const float* sample, float* out, int64_t n, float sigma_sq, float mean, float std, void* stream);
 
 /* afm_masked_mse: out[b] = sum((target - pred)^2 * keep) / (sum(keep) * D) over [L, D], keep = !frame_mask.
- * Replaces the loss reduction of training_losses (gaussian_diffusion.py:815-818, sum_flat nn.py:93-97). */
+ * Replaces the loss reduction of training_losses (gaussian_diffusion.py:815-818, sum_flat nn.py:93-97).  B == 0 is an empty batch: this
+ * entry point and afm_masked_mse_bwd return 0 and touch nothing, whatever the pointers.  A sample without a kept frame gives NaN (0 / 0,
+ * as the torch expression) and an all-zero dpred. */
 int afm_masked_mse(const float* target, const float* pred, const uint8_t* frame_mask, float* out,
                    int32_t B, int32_t L, int32_t D, void* stream);
 

@@ -14,9 +14,47 @@ from typing import Dict, Optional
 import torch
 import torch.nn.functional as F
 
-from . import scene_ref
+from . import rng_ref, scene_ref
 
 SD = Dict[str, torch.Tensor]
+
+
+# ------------------------------------------------------------------ train-mode dropout, by the library's counter-hash masks
+def keep_scale(p: float, seed: int, mask_id: int, shape, dtype=torch.float32) -> torch.Tensor:
+    """The factor dropout mask (seed, mask_id) multiplies a tensor of ``shape`` by: rng_ref.keep_mask over rows = prod(shape[:-1]),
+    cols = shape[-1] (row-major: an attention mask [B, H, Tq, Tk] has row (b H + h) Tq + query and column key), inv_keep (the float32
+    value, exact in ``dtype``) where the element is kept and 0 where it is dropped."""
+    rows = 1
+    for n in shape[:-1]:
+        rows *= int(n)
+    keep, inv_keep = rng_ref.keep_mask(p, seed, mask_id, rows, int(shape[-1]))
+    return (torch.from_numpy(keep).to(dtype) * float(inv_keep)).view(*shape)
+
+
+def encoder_layer_masks(p, seed, id0, B, T, d, ff, nhead, dtype=torch.float32):
+    """The four masks of one encoder layer as afm/autograd.py numbers them: id0 the attention probabilities, id0 + 1 out_proj(...)
+    before the residual, id0 + 2 gelu(z), id0 + 3 linear2(...) before the residual."""
+    return {"attn": keep_scale(p, seed, id0, (B, nhead, T, T), dtype), "drop1": keep_scale(p, seed, id0 + 1, (B, T, d), dtype),
+            "ffn": keep_scale(p, seed, id0 + 2, (B, T, ff), dtype), "drop2": keep_scale(p, seed, id0 + 3, (B, T, d), dtype)}
+
+
+def decoder_layer_masks(p, seed, id0, B, T, n, d, ff, nhead, dtype=torch.float32):
+    """The six masks of one decoder layer: id0 the self-attention probabilities, + 1 dropout1, + 2 the cross-attention probabilities
+    [B, H, T, n], + 3 dropout2, + 4 gelu(z), + 5 dropout3."""
+    return {"attn": keep_scale(p, seed, id0, (B, nhead, T, T), dtype), "drop1": keep_scale(p, seed, id0 + 1, (B, T, d), dtype),
+            "cross": keep_scale(p, seed, id0 + 2, (B, nhead, T, n), dtype), "drop2": keep_scale(p, seed, id0 + 3, (B, T, d), dtype),
+            "ffn": keep_scale(p, seed, id0 + 4, (B, T, ff), dtype), "drop3": keep_scale(p, seed, id0 + 5, (B, T, d), dtype)}
+
+
+def cmdm_masks(p, p_pos, seed, B, T, d, ff, nhead, num_layers, dtype=torch.float32):
+    """The masks of one CMDM (`trans_enc`) training forward: id 1 with the positional encoder's p on [B T, d], ids 16 + 4 i .. + 3 for
+    encoder layer i."""
+    return {"pos": keep_scale(p_pos, seed, 1, (B, T, d), dtype),
+            "layers": [encoder_layer_masks(p, seed, 16 + 4 * i, B, T, d, ff, nhead, dtype) for i in range(num_layers)]}
+
+
+def _drop(x, masks, key):
+    return x if masks is None or masks.get(key) is None else x * masks[key]
 
 
 def sinusoid_table(max_len: int, d: int) -> torch.Tensor:
@@ -46,9 +84,11 @@ def timestep_embed(sd: SD, pre: str, t: torch.Tensor, te_dim: int, max_len: int 
     return _lin(sd, pre + "time_embed.2", F.silu(_lin(sd, pre + "time_embed.0", e)))
 
 
-def encoder_layer(sd: SD, pre: str, x: torch.Tensor, key_padding_mask: Optional[torch.Tensor], nhead: int):
+def encoder_layer(sd: SD, pre: str, x: torch.Tensor, key_padding_mask: Optional[torch.Tensor], nhead: int, masks: Optional[dict] = None):
     """nn.TransformerEncoderLayer(batch_first, post-LN, exact-erf GELU, eps 1e-5) as the
-    reference builds it (cmdm.py:66-77); masked keys get -inf before the softmax."""
+    reference builds it (cmdm.py:66-77); masked keys get -inf before the softmax.  ``masks`` (encoder_layer_masks; None: eval mode)
+    multiplies the train-mode dropouts in where afm/autograd.py applies them; its key "attn_out" [B, H, T, dh] is NOT the layer: it
+    drops the attention output after P V, the deliberately wrong variant tests/test_trunk_train_edges_host.py tells from the right one."""
     B, T, D = x.shape
     dh = D // nhead
     qkv = F.linear(x, sd[pre + ".self_attn.in_proj_weight"], sd[pre + ".self_attn.in_proj_bias"])
@@ -56,18 +96,20 @@ def encoder_layer(sd: SD, pre: str, x: torch.Tensor, key_padding_mask: Optional[
     s = (q * (dh ** -0.5)) @ k.transpose(-1, -2)                        # [B, h, T, T]
     if key_padding_mask is not None:
         s = s.masked_fill(key_padding_mask[:, None, None, :], float("-inf"))
-    a = torch.softmax(s, dim=-1) @ v
+    a = _drop(_drop(torch.softmax(s, dim=-1), masks, "attn") @ v, masks, "attn_out")
     a = a.transpose(1, 2).reshape(B, T, D)
-    x = _ln(sd, pre + ".norm1", x + _lin(sd, pre + ".self_attn.out_proj", a))
-    ff = _lin(sd, pre + ".linear2", F.gelu(_lin(sd, pre + ".linear1", x)))
+    x = _ln(sd, pre + ".norm1", x + _drop(_lin(sd, pre + ".self_attn.out_proj", a), masks, "drop1"))
+    ff = _drop(_lin(sd, pre + ".linear2", _drop(F.gelu(_lin(sd, pre + ".linear1", x)), masks, "ffn")), masks, "drop2")
     return _ln(sd, pre + ".norm2", x + ff)
 
 
 def cmdm_forward(sd: SD, x, t, text_feat, c_pc_xyz=None, c_pc_contact=None, x_mask=None, *,
                  time_emb_dim: int = 512, nhead: int = 8, num_layers: int = 5,
                  blocks=(2, 2, 2, 2), mask_motion: bool = True, cont_emb: Optional[torch.Tensor] = None,
-                 return_tokens: bool = False, c_text_mask=None, c_text_erase=None, c_pc_mask=None, c_pc_erase=None):
-    """CMDM.forward, `trans_enc` branch (cmdm.py:118-170,195).
+                 return_tokens: bool = False, c_text_mask=None, c_text_erase=None, c_pc_mask=None, c_pc_erase=None,
+                 masks: Optional[dict] = None):
+    """CMDM.forward, `trans_enc` branch (cmdm.py:118-170,195).  ``masks`` (cmdm_masks; None: eval mode): the train-mode dropouts, "pos"
+    after the positional-encoding add and one encoder_layer_masks per layer.
 
     ``cont_emb`` (the SceneMapEncoder output, [B, G, planes[-1]]) may be passed in to
     skip the step-invariant point-cloud encoder; otherwise it is computed from
@@ -88,7 +130,7 @@ def cmdm_forward(sd: SD, x, t, text_feat, c_pc_xyz=None, c_pc_contact=None, x_ma
     G = cont.shape[1]
     seq = torch.cat([time_emb, text_emb, cont, _lin(sd, "motion_adapter", x)], dim=1)
     T = seq.shape[1]
-    seq = seq + sinusoid_table(5000, d)[:T].unsqueeze(0)                           # PositionalEncoding, dropout off
+    seq = _drop(seq + sinusoid_table(5000, d)[:T].unsqueeze(0), masks, "pos")        # PositionalEncoding (+ its dropout)
     mask = None
     if mask_motion:
         if x_mask is None:
@@ -97,7 +139,7 @@ def cmdm_forward(sd: SD, x, t, text_feat, c_pc_xyz=None, c_pc_contact=None, x_ma
         cm = torch.zeros(B, G, dtype=torch.bool) if c_pc_mask is None else c_pc_mask.bool().reshape(B, 1).repeat(1, G)   # :152-153
         mask = torch.cat([torch.zeros(B, 1, dtype=torch.bool), tm, cm, x_mask], dim=1)
     for i in range(num_layers):
-        seq = encoder_layer(sd, f"self_attn_layer.layers.{i}", seq, mask, nhead)
+        seq = encoder_layer(sd, f"self_attn_layer.layers.{i}", seq, mask, nhead, None if masks is None else masks["layers"][i])
     out = _lin(sd, "motion_layer", seq[:, 2 + G:, :])
     return (out, seq) if return_tokens else out
 
@@ -250,26 +292,32 @@ def cdm_pointtrans_forward(sd: SD, x, t, text_feat, c_pc_xyz, pc_emb=None, *, v2
     return _lin(sd, "contact_layer", y.view(B, N, -1))
 
 
-def _attn(q, k, v, nhead, key_mask=None):
+def _attn(q, k, v, nhead, key_mask=None, keep=None, keep_out=None):
     B, Tq, d = q.shape
     sp = lambda z: z.view(B, z.shape[1], nhead, d // nhead).transpose(1, 2)
     s = sp(q) @ sp(k).transpose(-1, -2) / math.sqrt(d // nhead)
     if key_mask is not None:
         s = s.masked_fill(key_mask[:, None, None, :], float("-inf"))
-    return (torch.softmax(s, dim=-1) @ sp(v)).transpose(1, 2).reshape(B, Tq, d)
+    p = torch.softmax(s, dim=-1)
+    o = (p if keep is None else p * keep) @ sp(v)
+    return (o if keep_out is None else o * keep_out).transpose(1, 2).reshape(B, Tq, d)
 
 
-def decoder_layer(sd: SD, pre: str, x, mem, tgt_mask, mem_mask, nhead: int):
-    """nn.TransformerDecoderLayer(batch_first, post-LN, exact-erf GELU): self-attention, cross-attention over `mem`, FFN."""
+def decoder_layer(sd: SD, pre: str, x, mem, tgt_mask, mem_mask, nhead: int, masks: Optional[dict] = None):
+    """nn.TransformerDecoderLayer(batch_first, post-LN, exact-erf GELU): self-attention, cross-attention over `mem`, FFN.  ``masks``
+    (decoder_layer_masks; None: eval mode): the six train-mode dropouts where afm/autograd.py applies them ("attn_out" / "cross_out" [B, H, T, dh]: the
+    deliberately wrong variants of encoder_layer's "attn_out")."""
     d = x.shape[-1]
+    m = masks or {}
     qkv = F.linear(x, sd[pre + ".self_attn.in_proj_weight"], sd[pre + ".self_attn.in_proj_bias"])
     q, k, v = qkv.split(d, dim=-1)
-    x = _ln(sd, pre + ".norm1", x + _lin(sd, pre + ".self_attn.out_proj", _attn(q, k, v, nhead, tgt_mask)))
+    x = _ln(sd, pre + ".norm1", x + _drop(_lin(sd, pre + ".self_attn.out_proj", _attn(q, k, v, nhead, tgt_mask, m.get("attn"), m.get("attn_out"))), masks, "drop1"))
     W, bq = sd[pre + ".multihead_attn.in_proj_weight"], sd[pre + ".multihead_attn.in_proj_bias"]
     q = F.linear(x, W[:d], bq[:d])
     k, v = F.linear(mem, W[d:2 * d], bq[d:2 * d]), F.linear(mem, W[2 * d:], bq[2 * d:])
-    x = _ln(sd, pre + ".norm2", x + _lin(sd, pre + ".multihead_attn.out_proj", _attn(q, k, v, nhead, mem_mask)))
-    return _ln(sd, pre + ".norm3", x + _lin(sd, pre + ".linear2", F.gelu(_lin(sd, pre + ".linear1", x))))
+    x = _ln(sd, pre + ".norm2", x + _drop(_lin(sd, pre + ".multihead_attn.out_proj", _attn(q, k, v, nhead, mem_mask, m.get("cross"), m.get("cross_out"))), masks, "drop2"))
+    ff = _drop(_lin(sd, pre + ".linear2", _drop(F.gelu(_lin(sd, pre + ".linear1", x)), masks, "ffn")), masks, "drop3")
+    return _ln(sd, pre + ".norm3", x + ff)
 
 
 def cmdm_trans_dec_forward(sd: SD, x, t, text_feat, c_pc_xyz, c_pc_contact, x_mask=None, *, time_emb_dim: int = 512, nhead: int = 8,
